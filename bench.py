@@ -1,20 +1,24 @@
 #!/usr/bin/env python
 """bench.py — tiles/sec of the MI355X tile hot path (BASELINE.json), one JSON line on rank 0.
 
-    python bench.py --gpus N --steps K --warmup W [--total-tiles T]
+    python bench.py --gpus N --steps K --warmup W [--total-tiles T] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (project -> per-op pre-pass -> fused fill/stroke/blend raster -> RGBA8
 framebuffer) over one batch of synthetic tiles, display lists already resident in HBM, framebuffers written to HBM.
+A plain run sets up, warms up, times the K steps of the headline and prints its line; everything listed under
+"Objects on the line" runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step rendered as .npy
+files (see dump_outputs) so that two builds can be compared output for output on the same seeded inputs.
 
 Headline (`value`): BASELINE configs[1] — 1024 z=15 256x256 tiles (50 polygons + 200 stroke segments each) PER GPU;
 with N > 1 (launched by torch.distributed.run, one rank per GPU) tile i of the global batch belongs to rank i mod N
 (weak scaling), no data-path collective, one RCCL all-reduce of the tile count per step.
 `--total-tiles T` switches the headline to STRONG scaling on a fixed global batch (configs[3]: T = 10000, tile i ->
 rank i mod N, x = 19000 + i mod 100, y = 10000 + i / 100; N = 1 renders the same T tiles).  The same 10000-tile
-strong-scaling batch is ALSO timed in every default run, at every N, as the `config4_strong` object, so a 1/2/4/8-GPU
-sweep of the default command carries the north_star's ">= 6x at 8 GPUs on the 10k-tile batch" numbers.
+strong-scaling batch is ALSO timed in every --full run, at every N, as the `config4_strong` object, so a 1/2/4/8-GPU
+sweep of `bench.py --full` carries the north_star's ">= 6x at 8 GPUs on the 10k-tile batch" numbers.
 
-Objects on the line (N = 1 unless said otherwise):
+Objects on the line with --full (N = 1 unless said otherwise):
+  one_batch_at_a_time the same K steps with one resident batch on one stream (the run the roofline's kernel time comes from)
   roofline            k_raster, the dominant kernel: algorithmic bytes / HIP-event kernel time vs 8 TB/s (+ measured copy ceiling)
   roofline_issue      k_raster's real bound: VALU/SALU wave-instructions and VALU-busy cycles from an SQ counter pass of this run
   roofline_composite  the 8-layer @2x composite pass (the kernel the >= 40 % HBM target is defined on)
@@ -88,6 +92,11 @@ def parse_args():
     ap.add_argument("--no-png", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (child processes)")
     ap.add_argument("--no-extra", action="store_true", help="headline + roofline only (no config4/5, 2x, sustained, end-to-end legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: one-batch-at-a-time run and rooflines, config4/5, 2x, composite, PNG, "
+                         "labels, end-to-end legs, CPU baseline, counter passes, sustained (the --no-* switches select among them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one rendered to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--keep-pmc", default="", help="directory to keep the rocpd databases of the counter passes in")
     ap.add_argument("--pmc-child", default="", help="internal: render a few steps of the named workload and exit (run under rocprofv3)")
     return ap.parse_args()
@@ -124,6 +133,24 @@ def pmc_child(name):
         ctx.render_stages(scene, abi.STAGE_RASTER, out)
     torch.cuda.synchronize()
     scene.free()
+
+
+def dump_outputs(out, directory, sample_bytes=32 << 20, seed=0):
+    """--dump-outputs: what the last timed step handed its caller — the RGBA8 framebuffers [tiles, H, W, 4] — as .npy files:
+      tile_channel_sums.npy          float64 [tiles, 4]: per tile, the sum of each channel over all its pixels (exact; every tile)
+      framebuffer_sample.npy         float32 [S, H, W, 4]: whole framebuffers of S tiles, S as many as fit in 32 MiB of float32
+      framebuffer_sample_tiles.npy   float64 [S]: which tiles, a fixed seeded choice (the same for the same arguments)
+    Under a launcher these are rank 0's tiles (global tile i * N for local tile i)."""
+    import numpy as np
+
+    fb = out.cpu().numpy()
+    n = fb.shape[0]
+    per_tile = fb[0].size * 4
+    idx = np.sort(np.random.default_rng(seed).choice(n, size=max(1, min(n, sample_bytes // per_tile)), replace=False))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "tile_channel_sums.npy"), fb.reshape(n, -1, fb.shape[-1]).sum(axis=1, dtype=np.uint64).astype(np.float64))
+    np.save(os.path.join(directory, "framebuffer_sample.npy"), fb[idx].astype(np.float32))
+    np.save(os.path.join(directory, "framebuffer_sample_tiles.npy"), idx.astype(np.float64))
 
 
 def latency_leg(ctx, args, batches=(1, 8, 64), workers=(1, 4, 16), seconds=0.35, entry="batch"):
@@ -288,6 +315,8 @@ def main():
     n_dev = torch.cuda.device_count()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     launched = "WORLD_SIZE" in os.environ
     pinned = any(os.environ.get(k) for k in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"))
     if n_dev < args.gpus and not (launched and pinned):
@@ -447,27 +476,34 @@ def main():
             if got_n != want_n:
                 sys.exit(f"bench.py: tiles per rank {got_n} differ from the round-robin shards {want_n}: refusing to report")
         raster_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
+        last_out = outs[(turn[0] - 1) % slots]  # the framebuffers of the last timed step
         for extra in scenes[1:]:
             extra.free()
         if slots > 1:  # the copies are gone: later callers of step() run on the first one
             scenes[1:], outs[1:], lanes[1:] = [], [], []
             slots = 1
-        return {"elapsed": elapsed, "total_tiles": total, "raster_ms": raster_ms, "dl": dl, "scene": scene, "out": out, "step": step}
+        return {"elapsed": elapsed, "total_tiles": total, "raster_ms": raster_ms, "dl": dl, "scene": scene, "out": out, "step": step,
+                "last_out": last_out}
 
     # ---- headline ----------------------------------------------------------------------------------
     strong = args.total_tiles > 0
     n_global = args.total_tiles if strong else args.tiles * world
-    head = run_sharded(synth.config_tiles(n_global), 15, args.scale, args.n_poly, args.n_line, args.steps, args.warmup)
-    dl, scene, out = head["dl"], head["scene"], head["out"]
-    alg_bytes = dl.algorithmic_bytes()  # SURVEY.md 8(d): 16*N_pts + 64*N_ops + 8*N_dashes + 4*W*H per tile
-    raster_s = head["raster_ms"] / 1e3  # the kernel's own duration: always from the one-batch-at-a-time run (nothing overlaps it there)
-    sequential = {"ms_per_step": head["elapsed"] / args.steps * 1e3, "tiles_per_s": head["total_tiles"] * args.steps / head["elapsed"]}
+    # one batch at a time: the headline itself with --streams 1; with --full also timed before the pipelined headline (the
+    # roofline's kernel time is taken there, where nothing overlaps the raster stage, and the --full legs reuse its batch)
+    seq = None
+    if args.full or args.streams == 1:
+        seq = run_sharded(synth.config_tiles(n_global), 15, args.scale, args.n_poly, args.n_line, args.steps, args.warmup)
+    head = seq
     if args.streams > 1:
         piped = run_sharded(synth.config_tiles(n_global), 15, args.scale, args.n_poly, args.n_line, args.steps, args.warmup, slots=args.streams)
-        piped["scene"].free()
-        head = dict(head, elapsed=piped["elapsed"], total_tiles=piped["total_tiles"])
+        if seq is None:
+            head = piped
+        else:
+            piped["scene"].free()
+            head = dict(seq, elapsed=piped["elapsed"], total_tiles=piped["total_tiles"], last_out=piped["last_out"])
         del piped
-    achieved = alg_bytes / raster_s / 1e9
+    last_out = head.pop("last_out")
+    dl, scene, out = head["dl"], head["scene"], head["out"]
     named = args.n_poly == 50 and args.n_line == 40
     if strong:
         workload = (f"BASELINE.json configs[3]: fixed global batch of {n_global} z=15 {dl.dim}x{dl.dim} tiles (x = 19000 + i mod 100, "
@@ -476,7 +512,8 @@ def main():
         workload = (f"BASELINE.json configs[1]: batch of {args.tiles} z=15 {dl.dim}x{dl.dim} tiles per GPU, synthetic 50-poly/200-segment "
                     "geometry per tile (SplitMix64, SURVEY.md 8(d)), lat/lon f64 input resident in HBM, RGBA8 framebuffers written to HBM"
                     + (f"; {args.streams} batches in flight (step i on resident copy / stream i mod {args.streams}: the pre-pass of one batch "
-                       "overlaps the raster stage of the previous one; one_batch_at_a_time = the same steps strictly one after the other)"
+                       "overlaps the raster stage of the previous one"
+                       + ("; one_batch_at_a_time = the same steps strictly one after the other)" if seq is not None else ")")
                        if args.streams > 1 else ""))
     result = {
         "metric": "tiles/sec (256x256 z=15)",
@@ -505,21 +542,46 @@ def main():
             "rccl_nranks_seen": nranks_seen,
             "batches_in_flight": args.streams,
         },
-        "one_batch_at_a_time": dict(sequential, what="the same K steps with ONE resident batch on ONE stream: every step waits for the one before; "
-                                                     "roofline.avg_launch_ms is measured in this run"),
-        "roofline": {
-            "kernel": "k_raster (fused fill/stroke/blend/to_rgb) — instruction-issue bound by construction, see roofline_issue; "
-                      "the HBM fraction is reported because the metric asks for it, it is not this kernel's ceiling",
-            "bound": "hbm",
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            "traffic": None,
-            "algorithmic_bytes_per_launch": alg_bytes,
-            "avg_launch_ms": raster_s * 1e3,
-            "timing": "HIP events around the raster stage on the launch stream, averaged over the timed steps",
-        },
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if comm_hung:
+            # a helper thread is still inside RCCL: tearing down the context or the process group under it can block — the line is out
+            sys.stderr.flush()
+            os._exit(0)
+        scene.free()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out, args.dump_outputs)
+    del last_out
+    if not args.full:
+        finish()
+        return
+
+    alg_bytes = dl.algorithmic_bytes()  # SURVEY.md 8(d): 16*N_pts + 64*N_ops + 8*N_dashes + 4*W*H per tile
+    raster_s = seq["raster_ms"] / 1e3  # the kernel's own duration: always from the one-batch-at-a-time run (nothing overlaps it there)
+    achieved = alg_bytes / raster_s / 1e9
+    result["one_batch_at_a_time"] = {
+        "ms_per_step": seq["elapsed"] / args.steps * 1e3, "tiles_per_s": seq["total_tiles"] * args.steps / seq["elapsed"],
+        "what": "the same K steps with ONE resident batch on ONE stream: every step waits for the one before; roofline.avg_launch_ms is "
+                "measured in this run",
+    }
+    result["roofline"] = {
+        "kernel": "k_raster (fused fill/stroke/blend/to_rgb) — instruction-issue bound by construction, see roofline_issue; "
+                  "the HBM fraction is reported because the metric asks for it, it is not this kernel's ceiling",
+        "bound": "hbm",
+        "achieved": achieved,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS,
+        "traffic": None,
+        "algorithmic_bytes_per_launch": alg_bytes,
+        "avg_launch_ms": raster_s * 1e3,
+        "timing": "HIP events around the raster stage on the launch stream, averaged over the timed steps",
     }
 
     # ---- configs[3]: the 10000-tile strong-scaling batch, at every N ---------------------------------
@@ -973,15 +1035,7 @@ def main():
         if v is not None:
             result[name] = v
 
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if comm_hung:
-        # a helper thread is still inside RCCL: tearing down the context or the process group under it can block — the line is out
-        sys.stderr.flush()
-        os._exit(0)
-    scene.free()
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

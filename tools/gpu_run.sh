@@ -5,7 +5,7 @@
 #   pytest[:<pytest args>]      the GPU suite (default: tests -m gpu -x -q), under OSMT_POISON_ALLOC=1 (tests/conftest.py)
 #   variants:<v1,v2,...>        tools/time_variants.py over libosmtile_<v>.so ("base" = libosmtile.so); BIG=1 adds 256 config-5 tiles
 #   fuzz[:<seconds>[:<seed>]]   tools/fuzz_parity.py (areas) ; fuzzlabels[:<seconds>[:<seed>]] with a label pass per tile
-#   bench[:<bench.py args>]     python bench.py -> bench.json (+ the scalars the round's bars are set on)
+#   bench[:<bench.py args>]     python bench.py --full -> bench.json (+ the scalars the round's bars are set on)
 #   prof:<workload>[@<passes>]  tools/prof_workload.py: kernel trace + counter passes (kt,sq1,sq2,sq3,fetch,write) of a bench.py --pmc-child workload ("config5:256")
 #   smoke                       __graft_entry__.smoke()
 #   worker                      tools/worker_bench.sh (native request threads)
@@ -27,7 +27,7 @@ for step in "$@"; do
       extra=""; [ $kind = fuzzlabels ] && extra="labels"
       timeout $((secs + 240)) python tools/fuzz_parity.py $secs $seed $extra > $O/${kind}_$n.txt 2>&1; tail -1 $O/${kind}_$n.txt ;;
     bench)
-      timeout 1500 python bench.py $arg > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -2 $O/bench.err
+      timeout 1500 python bench.py --full $arg > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -2 $O/bench.err
       python - <<PY
 import json
 try:
