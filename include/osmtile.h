@@ -146,8 +146,8 @@ typedef struct osmt_label {
     uint8_t text_color[3]; /* Rasterizer::color (text_placer.rs:50-54) */
     uint8_t _pad[3];
     uint32_t image_id;     /* has_icon: id from osmt_register_image */
-    uint32_t seg_off;      /* first draw_line call in osmt_label_batch.segs */
-    uint32_t n_segs;
+    uint32_t seg_off;      /* first draw_line call in osmt_label_batch.segs (osmt_glyph_label_batch: first glyph instance) */
+    uint32_t n_segs;       /* draw_line calls (osmt_glyph_label_batch: glyph instances) */
     uint32_t _reserved;
     double icon_center_x, icon_center_y; /* get_label_position (labeler.rs:57-60), already scaled */
 } osmt_label;
@@ -161,6 +161,52 @@ typedef struct osmt_label_batch {
     const double* segs;            /* [n_segs][4] = (x0, y0, x1, y1) exactly as passed to Rasterizer::draw_line */
     size_t n_segs;
 } osmt_label_batch;
+
+/* ---- label text as glyph runs ------------------------------------------------ */
+/* The second, optional form of label text: instead of the draw_line calls of the glyph walk, the caller registers the
+ * font's outlines once per context and names, per label, the glyph instances TextPlacer::place would rasterize
+ * (font/text_placer.rs:24-160) with the transform it would pass to Glyph::rasterize (:232-259).  The GPU walks the
+ * outlines — including Rasterizer::draw_quad's subdivision (font/rasterizer.rs:90-113) with a device hypot equal to the
+ * host libm's — and writes exactly the draw_line sequence the host would have produced, in the same order, into the
+ * segment arena the label kernels read.  64 bytes per glyph instead of ~32 bytes x hundreds of calls. */
+
+/* stb_truetype's Vertex (10 bytes): one outline command in font units; type 1 = MoveTo, 2 = LineTo, 3 = CurveTo
+ * (text_placer.rs:241-256).  (cx, cy) is the control point of a CurveTo. */
+typedef struct osmt_glyph_vertex {
+    int16_t x, y, cx, cy;
+    uint8_t type;
+    uint8_t _pad;
+} osmt_glyph_vertex;
+
+#define OSMT_GLYPH_MOVE_TO 1u
+#define OSMT_GLYPH_LINE_TO 2u
+#define OSMT_GLYPH_CURVE_TO 3u
+
+/* osmt_glyph_instance.form: which of TextPlacer::place's two `tr` closures maps outline points to pixels */
+#define OSMT_GLYPH_CENTER 0u /* p = {x_offset, baseline}: tr(x, y) = (x_offset + x, baseline - y)   (text_placer.rs:150-153) */
+#define OSMT_GLYPH_LINE 1u   /* p = {glyph_center_x, glyph_center_y, angle_sin, angle_cos, way_x, way_y}, with
+                              * (angle_sin, angle_cos) = (-way_pos.angle).sin_cos() computed by the caller's libm:
+                              * tr = translate by -glyph_center, rotate, back-translate to way_pos  (text_placer.rs:87-101) */
+
+/* One Glyph::rasterize call (64 bytes).  `scale` is f64::from(font.scale_for_pixel_height(size as f32)); the GPU applies
+ * `convert` (f64::from(v) * scale) itself.  Unused entries of p are ignored (CENTER reads p[0], p[1]). */
+typedef struct osmt_glyph_instance {
+    uint32_t glyph_id; /* id from osmt_register_glyphs */
+    uint32_t form;     /* OSMT_GLYPH_CENTER / OSMT_GLYPH_LINE */
+    double scale;
+    double p[6];
+} osmt_glyph_instance;
+
+/* Labels of a batch with glyph-run text.  The osmt_label records are the same as in osmt_label_batch — icons, has_text
+ * and colours mean what they mean there — except that seg_off / n_segs name a range of GLYPH INSTANCES of `glyphs`
+ * (in rasterize order), not of draw_line calls. */
+typedef struct osmt_glyph_label_batch {
+    const osmt_label* labels;
+    size_t n_labels;
+    const uint32_t* job_label_off; /* [n_jobs + 1] */
+    const osmt_glyph_instance* glyphs;
+    size_t n_glyphs;
+} osmt_glyph_label_batch;
 
 typedef struct osmt_config {
     int32_t device; /* HIP device ordinal */
@@ -257,6 +303,31 @@ int osmt_scene_read_label_status(osmt_ctx* ctx, osmt_scene* scene, uint8_t* ok);
 int osmt_scene_check(osmt_ctx* ctx, osmt_scene* scene);
 /* Copies the projected integer points of the scene back: xy = [n_pts][2]. */
 int osmt_scene_read_points(osmt_ctx* ctx, osmt_scene* scene, int32_t* xy);
+
+/* ---- label text as glyph runs (see osmt_glyph_label_batch) ------------------------------------ */
+/* Appends n_glyphs outlines to the context's glyph table; glyph i is v[vertex_off[i] .. vertex_off[i + 1]) (vertex_off:
+ * n_glyphs + 1 non-decreasing entries, vertex_off[0] == 0) and gets id *out_first_id + i.  An empty outline is legal (a
+ * glyph with `shape: None`, the space).  Vertex types must be 1..3.  The table is append-only with the snapshot
+ * semantics of osmt_register_image: a render that holds an older snapshot never reads freed memory. */
+int osmt_register_glyphs(osmt_ctx* ctx, const osmt_glyph_vertex* v, const uint32_t* vertex_off, uint32_t n_glyphs,
+                         uint32_t* out_first_id);
+/* osmt_scene_set_labels with glyph-run text: the glyph instances are expanded on the GPU into the draw_line calls of
+ * the glyph walk (a count pass, one read-back of ~20 bytes per label, an emit pass); the label kernels then run exactly
+ * as with osmt_scene_set_labels on those calls.  NULL / n_labels == 0 detaches.  Errors, never silent:
+ *   - OSMT_INVALID_ARG: NULL pools, glyph ids outside the table, an instance range out of bounds, an unknown form, a
+ *     scale or used parameter that is not finite;
+ *   - OSMT_UNSUPPORTED: a produced draw_line coordinate that is not finite or has |v| > 2^20 (as osmt_scene_set_labels),
+ *     or a curve whose subdivision is deeper than the device walk's cap (62 levels; never a truncated outline). */
+int osmt_scene_set_glyph_labels(osmt_ctx* ctx, osmt_scene* scene, const osmt_glyph_label_batch* labels);
+/* osmt_render_batch_rgb with glyph-run labels: scene, osmt_scene_set_glyph_labels, render, packed RGB8 out. */
+int osmt_render_batch_rgb_glyphs(osmt_ctx* ctx, const osmt_batch* batch, const osmt_glyph_label_batch* labels, uint8_t* out_rgb,
+                                 size_t out_tile_stride_bytes);
+/* Inspection: the scene's draw_line arena as the label kernels read it, out = [n][4] (x0, y0, x1, y1).  For glyph-run
+ * labels it is in label order (label, glyph, vertex, subdivision); for segment labels it is the caller's segs.  *n is
+ * always set; out may be NULL to ask for the size; cap (in calls) < *n with a non-NULL out is OSMT_INVALID_ARG. */
+int osmt_scene_read_label_segs(osmt_ctx* ctx, osmt_scene* scene, double* out, size_t cap, size_t* n);
+/* Diagnostics: out[i] = the device hypot of (xy[2i], xy[2i + 1]) — the function the glyph walk flattens curves with. */
+int osmt_debug_hypot(osmt_ctx* ctx, const double* xy, size_t n, double* out);
 
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */

@@ -19,6 +19,9 @@ COORD_LATLON_F64, COORD_POINT_I32, COORD_NODE_REF = 0, 1, 2
 
 STAGE_PROJECT, STAGE_OPINFO, STAGE_RASTER = 1, 2, 4
 
+GLYPH_MOVE_TO, GLYPH_LINE_TO, GLYPH_CURVE_TO = 1, 2, 3  # osmt_glyph_vertex.type (stb_truetype's Vertex)
+GLYPH_CENTER, GLYPH_LINE = 0, 1  # osmt_glyph_instance.form: TextPlacer::place's two `tr` closures
+
 
 class Op(C.Structure):
     _fields_ = [
@@ -104,6 +107,36 @@ class LabelBatch(C.Structure):
     ]
 
 
+class GlyphVertex(C.Structure):
+    _fields_ = [
+        ("x", C.c_int16),
+        ("y", C.c_int16),
+        ("cx", C.c_int16),
+        ("cy", C.c_int16),
+        ("type", C.c_uint8),
+        ("_pad", C.c_uint8),
+    ]
+
+
+class GlyphInstance(C.Structure):
+    _fields_ = [
+        ("glyph_id", C.c_uint32),
+        ("form", C.c_uint32),
+        ("scale", C.c_double),
+        ("p", C.c_double * 6),
+    ]
+
+
+class GlyphLabelBatch(C.Structure):
+    _fields_ = [
+        ("labels", C.POINTER(Label)),
+        ("n_labels", C.c_size_t),
+        ("job_label_off", C.POINTER(C.c_uint32)),
+        ("glyphs", C.POINTER(GlyphInstance)),
+        ("n_glyphs", C.c_size_t),
+    ]
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32)]
 
@@ -112,3 +145,5 @@ assert C.sizeof(Op) == 64
 assert C.sizeof(Ring) == 8
 assert C.sizeof(TileJob) == 32
 assert C.sizeof(Label) == 40
+assert C.sizeof(GlyphVertex) == 10
+assert C.sizeof(GlyphInstance) == 64

@@ -100,6 +100,14 @@ struct osmt_ctx {
     uint32_t d_n_images = 0;
     std::vector<void*> image_graveyard;
     bool images_dirty = false;
+    /* the glyph table of osmt_register_glyphs (outlines of glyph-run labels), same snapshot rules as the icons: a
+     * registration followed by a use makes a new device pair, the old one joins image_graveyard */
+    std::vector<osmt_glyph_vertex> glyph_verts;
+    std::vector<uint32_t> glyph_voff{0u};
+    osmt_glyph_vertex* d_glyph_verts = nullptr;
+    uint32_t* d_glyph_voff = nullptr;
+    uint32_t d_n_glyphs = 0;
+    bool glyphs_dirty = false;
     /* one reference for the handle returned by osmt_create + one per live scene: osmt_destroy on a context that still
      * has scenes only drops the handle's reference, the last osmt_scene_free tears the context down */
     std::atomic<int> refs{1};
@@ -441,6 +449,44 @@ int sync_images(osmt_ctx* ctx, image_snapshot* snap) {
     return OSMT_OK;
 }
 
+struct glyph_snapshot {
+    const osmt_glyph_vertex* verts = nullptr;
+    const uint32_t* voff = nullptr;
+    uint32_t n = 0;
+};
+
+/* Brings the device copy of the glyph table up to date; the snapshot stays valid for the life of the context. */
+int sync_glyphs(osmt_ctx* ctx, glyph_snapshot* snap) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->glyphs_dirty) {
+        osmt_glyph_vertex* nv = nullptr;
+        uint32_t* no = nullptr;
+        const size_t nvb = std::max<size_t>(ctx->glyph_verts.size(), 1) * sizeof(osmt_glyph_vertex);
+        HIP_TRY(hipMalloc((void**)&no, ctx->glyph_voff.size() * sizeof(uint32_t)));
+        hipError_t e = hipMalloc((void**)&nv, nvb);
+        if (e == hipSuccess) e = hipMemcpy(no, ctx->glyph_voff.data(), ctx->glyph_voff.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !ctx->glyph_verts.empty())
+            e = hipMemcpy(nv, ctx->glyph_verts.data(), ctx->glyph_verts.size() * sizeof(osmt_glyph_vertex), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(no);
+            if (nv) (void)hipFree(nv);
+            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "glyph table upload failed: %s", hipGetErrorString(e));
+        }
+        if (ctx->d_glyph_verts) ctx->image_graveyard.push_back(ctx->d_glyph_verts);
+        if (ctx->d_glyph_voff) ctx->image_graveyard.push_back(ctx->d_glyph_voff);
+        ctx->d_glyph_verts = nv;
+        ctx->d_glyph_voff = no;
+        ctx->d_n_glyphs = (uint32_t)(ctx->glyph_voff.size() - 1);
+        ctx->glyphs_dirty = false;
+    }
+    if (snap) {
+        snap->verts = ctx->d_glyph_verts;
+        snap->voff = ctx->d_glyph_voff;
+        snap->n = ctx->d_n_glyphs;
+    }
+    return OSMT_OK;
+}
+
 void comm_destroy(osmt_ctx* ctx);
 
 void ctx_teardown(osmt_ctx* ctx) {
@@ -448,6 +494,8 @@ void ctx_teardown(osmt_ctx* ctx) {
     comm_destroy(ctx);
     if (ctx->d_images) (void)hipFree(ctx->d_images);
     if (ctx->d_image_pool) (void)hipFree(ctx->d_image_pool);
+    if (ctx->d_glyph_verts) (void)hipFree(ctx->d_glyph_verts);
+    if (ctx->d_glyph_voff) (void)hipFree(ctx->d_glyph_voff);
     for (void* p : ctx->image_graveyard) (void)hipFree(p);
     for (auto& c : ctx->cache) (void)hipFree(c.p);
     for (hipStream_t st : ctx->idle_streams) (void)hipStreamDestroy(st);
@@ -837,7 +885,7 @@ int render_impl(osmt_ctx* ctx, osmt_scene* sc, uint32_t stages, void* d_out, siz
 
 extern "C" {
 
-uint32_t osmt_version(void) { return (1u << 16) | 0u; }
+uint32_t osmt_version(void) { return (1u << 16) | 1u; }
 
 const char* osmt_last_error(void) { return g_last_error.c_str(); }
 
@@ -894,6 +942,30 @@ static int osmt_register_image_body(osmt_ctx* ctx, const uint8_t* rgba8, uint32_
 
 int osmt_register_image(osmt_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_t height, uint32_t* out_id) {
     return guarded([&] { return osmt_register_image_body(ctx, rgba8, width, height, out_id); });
+}
+
+static int osmt_register_glyphs_body(osmt_ctx* ctx, const osmt_glyph_vertex* v, const uint32_t* voff, uint32_t n, uint32_t* out_first) {
+    if (!ctx || !voff || !out_first) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (voff[0] != 0) return fail(OSMT_INVALID_ARG, "vertex_off[0] must be 0");
+    for (uint32_t i = 0; i < n; ++i)
+        if (voff[i] > voff[i + 1]) return fail(OSMT_INVALID_ARG, "vertex_off is not monotonic at glyph %u", i);
+    const uint32_t nv = voff[n];
+    if (nv && !v) return fail(OSMT_INVALID_ARG, "NULL vertex pool");
+    for (uint32_t k = 0; k < nv; ++k)
+        if (v[k].type < OSMT_GLYPH_MOVE_TO || v[k].type > OSMT_GLYPH_CURVE_TO)
+            return fail(OSMT_INVALID_ARG, "glyph vertex %u: type %u is not MoveTo / LineTo / CurveTo", k, (unsigned)v[k].type);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t base = ctx->glyph_verts.size();
+    if (base + nv >= 0xFFFFFFFFull || ctx->glyph_voff.size() + n >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "glyph table too large");
+    *out_first = (uint32_t)(ctx->glyph_voff.size() - 1);
+    ctx->glyph_verts.insert(ctx->glyph_verts.end(), v, v + nv);
+    for (uint32_t i = 1; i <= n; ++i) ctx->glyph_voff.push_back((uint32_t)(base + voff[i]));
+    ctx->glyphs_dirty = true;
+    return OSMT_OK;
+}
+
+int osmt_register_glyphs(osmt_ctx* ctx, const osmt_glyph_vertex* v, const uint32_t* vertex_off, uint32_t n_glyphs, uint32_t* out_first_id) {
+    return guarded([&] { return osmt_register_glyphs_body(ctx, v, vertex_off, n_glyphs, out_first_id); });
 }
 
 /* The pre-pass writes into two arenas whose sizes depend on the PROJECTED geometry (how many sub-tiles every op
@@ -1391,11 +1463,87 @@ void osmt_scene_free(osmt_scene* s) {
     scene_delete(s);
 }
 
+/* Glyph-run labels, first half: validates the instances, builds the (label, instance) pairs in label order, runs the
+ * count pass and reads back each label's window summary (osmt_label_extent, ~20 bytes per label) and the error word.
+ * *gtmp: the device buffer the emit pass still needs (the caller frees it after synchronising `st`). */
+static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_label_batch* gb, hipStream_t st, char** gtmp,
+                              osmt_glyph_pass* gp, std::vector<osmt_label_extent>& ext) {
+    glyph_snapshot snap;
+    {
+        const int rc = sync_glyphs(ctx, &snap);
+        if (rc != OSMT_OK) return rc;
+    }
+    for (size_t i = 0; i < gb->n_glyphs; ++i) {
+        const osmt_glyph_instance& g = gb->glyphs[i];
+        if (g.glyph_id >= snap.n) return fail(OSMT_INVALID_ARG, "glyph instance %zu: glyph id %u is not in the glyph table (%u glyphs)", i, g.glyph_id, snap.n);
+        if (g.form != OSMT_GLYPH_CENTER && g.form != OSMT_GLYPH_LINE) return fail(OSMT_INVALID_ARG, "glyph instance %zu: unknown form %u", i, g.form);
+        const int n_p = g.form == OSMT_GLYPH_LINE ? 6 : 2;
+        bool finite = std::isfinite(g.scale);
+        for (int k = 0; k < n_p; ++k) finite = finite && std::isfinite(g.p[k]);
+        if (!finite) return fail(OSMT_INVALID_ARG, "glyph instance %zu: scale or placement not finite", i);
+    }
+    std::vector<uint32_t> pair_inst, pair_label;
+    for (size_t l = 0; l < gb->n_labels; ++l) {
+        const osmt_label& in = gb->labels[l];
+        if (!in.has_text || in.n_segs == 0) continue;
+        if ((size_t)in.seg_off + in.n_segs > gb->n_glyphs) return fail(OSMT_INVALID_ARG, "label %zu: glyph instance range out of bounds", l);
+        if (pair_inst.size() + in.n_segs >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "too many glyph instances");
+        for (uint32_t k = 0; k < in.n_segs; ++k) {
+            pair_inst.push_back(in.seg_off + k);
+            pair_label.push_back((uint32_t)l);
+        }
+    }
+    const size_t n_pairs = pair_inst.size(), n_labels = gb->n_labels;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    const size_t o_inst = carve(gb->n_glyphs * sizeof(osmt_glyph_instance));
+    const size_t o_pi = carve(n_pairs * 4), o_pl = carve(n_pairs * 4), o_pc = carve(n_pairs * 4), o_pb = carve(n_pairs * 4);
+    const size_t o_blk = carve((n_pairs / 1024 + 1) * 4);
+    const size_t o_sum = carve(n_labels * sizeof(osmt_label_extent) + 4); /* the error word right behind: one read-back */
+    HIP_TRY(dev_alloc(ctx, (void**)gtmp, off));
+    char* base = *gtmp;
+    gp->verts = snap.verts;
+    gp->voff = snap.voff;
+    gp->inst = (const osmt_glyph_instance*)(base + o_inst);
+    gp->pair_inst = (const uint32_t*)(base + o_pi);
+    gp->pair_label = (const uint32_t*)(base + o_pl);
+    gp->n_pairs = (uint32_t)n_pairs;
+    gp->W = (int32_t)(OSMT_TILE_SIZE * sc->scale);
+    gp->sum = (osmt_label_extent*)(base + o_sum);
+    gp->err = (uint32_t*)(base + o_sum + n_labels * sizeof(osmt_label_extent));
+    gp->pair_cnt = (uint32_t*)(base + o_pc);
+    gp->pair_base = (uint32_t*)(base + o_pb);
+    gp->blk = (uint32_t*)(base + o_blk);
+    if (gb->n_glyphs) HIP_TRY(hipMemcpyAsync(base + o_inst, gb->glyphs, gb->n_glyphs * sizeof(osmt_glyph_instance), hipMemcpyHostToDevice, st));
+    if (n_pairs) {
+        HIP_TRY(hipMemcpyAsync(base + o_pi, pair_inst.data(), n_pairs * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(base + o_pl, pair_label.data(), n_pairs * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(osmt_launch_glyph_count(*gp, (uint32_t)n_labels, st));
+    std::vector<char> back(n_labels * sizeof(osmt_label_extent) + 4);
+    HIP_TRY(hipMemcpyAsync(back.data(), gp->sum, back.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st)); /* also: pair_inst / pair_label may be read until here */
+    uint32_t err = 0;
+    memcpy(&err, back.data() + n_labels * sizeof(osmt_label_extent), 4);
+    if (err & OSMT_GLYPH_ERR_COORD) return fail(OSMT_UNSUPPORTED, "glyph labels: a draw_line coordinate is not finite or |v| > 2^20");
+    if (err & OSMT_GLYPH_ERR_DEPTH)
+        return fail(OSMT_UNSUPPORTED, "glyph labels: a curve needs more than %d levels of subdivision", OSMT_QUAD_MAX_DEPTH);
+    if (err) return fail(OSMT_HIP_ERROR, "glyph count pass: internal error %u", err);
+    ext.resize(n_labels);
+    memcpy(ext.data(), back.data(), n_labels * sizeof(osmt_label_extent));
+    return OSMT_OK;
+}
+
 /* Drawer::draw_labels (drawer.rs:221-262) as data: validates, sizes each label's coverage window and
  * uploads.  Window of a label = stripes its draw_line calls can create inside labels_bb's rows
  * (tile_pixels.rs:67-72) x every column those stripes can hold a key in (+-2 cells of slack for the
- * rounding of eval_x_at_y, font/rasterizer.rs:37). */
-static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_label_batch* lb) {
+ * rounding of eval_x_at_y, font/rasterizer.rs:37).  Exactly one of lb (draw_line calls from the host) and gb (glyph
+ * runs, expanded on the device) is used; both feed the same per-label summaries (osmt_label_extent) to the window code. */
+static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_label_batch* lb, const osmt_glyph_label_batch* gb = nullptr) {
     if (!ctx || !sc || sc->ctx != ctx) return fail(OSMT_INVALID_ARG, "bad ctx/scene");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = sc->own_stream;
@@ -1418,16 +1566,48 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
     dev_free(ctx, sc->d_lab_base);
     sc->d_lab_base = nullptr;
     sc->n_labels = sc->n_label_segs = 0;
-    if (!lb || lb->n_labels == 0) return OSMT_OK;
-    if (!lb->labels || !lb->job_label_off || (lb->n_segs && !lb->segs)) return fail(OSMT_INVALID_ARG, "NULL label pool");
-    if (lb->n_labels >= 0xFFFFFFFFull || lb->n_segs >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "label batch too large");
-    if (lb->job_label_off[0] != 0 || lb->job_label_off[sc->n_jobs] != lb->n_labels)
+    const osmt_label* const labels = lb ? lb->labels : gb ? gb->labels : nullptr;
+    const size_t n_labels = lb ? lb->n_labels : gb ? gb->n_labels : 0;
+    const uint32_t* const job_label_off = lb ? lb->job_label_off : gb ? gb->job_label_off : nullptr;
+    if (n_labels == 0) return OSMT_OK;
+    if (!labels || !job_label_off || (lb && lb->n_segs && !lb->segs) || (gb && gb->n_glyphs && !gb->glyphs))
+        return fail(OSMT_INVALID_ARG, "NULL label pool");
+    if (n_labels >= 0xFFFFFFFFull || (lb ? lb->n_segs : gb->n_glyphs) >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "label batch too large");
+    if (job_label_off[0] != 0 || job_label_off[sc->n_jobs] != n_labels)
         return fail(OSMT_INVALID_ARG, "job_label_off must run from 0 to n_labels over n_jobs + 1 entries");
     for (uint32_t j = 0; j < sc->n_jobs; ++j)
-        if (lb->job_label_off[j] > lb->job_label_off[j + 1]) return fail(OSMT_INVALID_ARG, "job_label_off is not monotonic");
+        if (job_label_off[j] > job_label_off[j + 1]) return fail(OSMT_INVALID_ARG, "job_label_off is not monotonic");
     const double LIM = 1048576.0; /* 2^20 */
-    for (size_t i = 0; i < 4 * lb->n_segs; ++i)
-        if (!(std::fabs(lb->segs[i]) <= LIM)) return fail(OSMT_UNSUPPORTED, "label segment %zu: coordinate not finite or |v| > 2^20", i / 4);
+    if (lb)
+        for (size_t i = 0; i < 4 * lb->n_segs; ++i)
+            if (!(std::fabs(lb->segs[i]) <= LIM)) return fail(OSMT_UNSUPPORTED, "label segment %zu: coordinate not finite or |v| > 2^20", i / 4);
+    /* glyph runs: the count pass on the device gives every label's summary; the emit pass (below, once the arena is
+     * carved) writes the calls.  gtmp lives until the emit pass has run. */
+    std::vector<osmt_label_extent> gext;
+    std::vector<uint32_t> gseg_off;
+    osmt_glyph_pass gp{};
+    struct tmp_guard {
+        osmt_ctx* c;
+        hipStream_t s;
+        char* p;
+        ~tmp_guard() {
+            if (p) {
+                (void)hipStreamSynchronize(s);
+                dev_free(c, p);
+            }
+        }
+    } gtmp{ctx, st, nullptr};
+    size_t n_segs_total = lb ? lb->n_segs : 0;
+    if (gb) {
+        const int rc = glyph_labels_count(ctx, sc, gb, st, &gtmp.p, &gp, gext);
+        if (rc != OSMT_OK) return rc;
+        gseg_off.resize(n_labels);
+        for (size_t l = 0; l < n_labels; ++l) {
+            gseg_off[l] = (uint32_t)n_segs_total;
+            n_segs_total += gext[l].n_segs;
+            if (n_segs_total >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "glyph labels expand to more than 2^32 draw_line calls");
+        }
+    }
 
     std::vector<osmt_image_desc> images;
     {
@@ -1439,12 +1619,12 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
     std::vector<uint32_t>& wide = sc->h_lab_wide;
     std::vector<osmt_label_band>& bands = sc->h_lab_bands;
     bands.clear();
-    info.assign(lb->n_labels, osmt_labelinfo{});
+    info.assign(n_labels, osmt_labelinfo{});
     wide.clear();
     size_t cells = 0, wide_cells = 0, bit_words = 0; /* bit_words < cells / 64 + bands <= 2^26 */
     for (uint32_t j = 0; j < sc->n_jobs; ++j) {
-        for (uint32_t l = lb->job_label_off[j]; l < lb->job_label_off[j + 1]; ++l) {
-            const osmt_label& in = lb->labels[l];
+        for (uint32_t l = job_label_off[j]; l < job_label_off[j + 1]; ++l) {
+            const osmt_label& in = labels[l];
             osmt_labelinfo& o = info[l];
             memset(&o, 0, sizeof o);
             o.ry0 = 1;
@@ -1462,22 +1642,22 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
             o.has_text = in.has_text ? 1 : 0;
             memcpy(o.color, in.text_color, 3);
             if (!in.has_text || in.n_segs == 0) continue;
-            if ((size_t)in.seg_off + in.n_segs > lb->n_segs) return fail(OSMT_INVALID_ARG, "label %u: segment range out of bounds", l);
-            o.seg_off = in.seg_off;
-            o.n_segs = in.n_segs;
-            int32_t ry0 = INT32_MAX, ry1 = INT32_MIN, cx0 = INT32_MAX, cx1 = INT32_MIN;
-            for (uint32_t k = 0; k < in.n_segs; ++k) {
-                const double* q = lb->segs + 4 * ((size_t)in.seg_off + k);
-                if (q[3] - q[1] == 0.0) continue; /* draw_line returns (font/rasterizer.rs:30-32) */
-                int32_t a = (int32_t)std::floor(std::fmin(q[1], q[3])), b = (int32_t)std::floor(std::fmax(q[1], q[3]));
-                a = std::max(a, -W);
-                b = std::min(b, 2 * W - 1);
-                if (a > b) continue; /* no stripe inside labels_bb */
-                ry0 = std::min(ry0, a);
-                ry1 = std::max(ry1, b);
-                cx0 = std::min(cx0, (int32_t)std::floor(std::fmin(q[0], q[2])) - 2);
-                cx1 = std::max(cx1, (int32_t)std::floor(std::fmax(q[0], q[2])) + 3);
+            osmt_label_extent ext;
+            if (lb) {
+                if ((size_t)in.seg_off + in.n_segs > lb->n_segs) return fail(OSMT_INVALID_ARG, "label %u: segment range out of bounds", l);
+                o.seg_off = in.seg_off;
+                osmt_label_extent_init(&ext);
+                for (uint32_t k = 0; k < in.n_segs; ++k) {
+                    const double* q = lb->segs + 4 * ((size_t)in.seg_off + k);
+                    osmt_label_extent_add(&ext, q[0], q[1], q[2], q[3], W);
+                }
+            } else {
+                ext = gext[l];
+                if (ext.n_segs == 0) continue; /* blanks only: a text that drew nothing */
+                o.seg_off = gseg_off[l];
             }
+            o.n_segs = ext.n_segs;
+            const int32_t ry0 = ext.ry0, ry1 = ext.ry1, cx0 = ext.cx0, cx1 = ext.cx1;
             if (ry0 > ry1) continue;
             const size_t rows = (size_t)(ry1 - ry0 + 1), cols = (size_t)(cx1 - cx0 + 1);
             if (rows * cols > ((size_t)1 << 24))
@@ -1530,18 +1710,18 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
     };
     const size_t EW = 3 * (size_t)W;
     const size_t words = (EW * EW + 31) / 32;
-    const size_t o_info = carve(lb->n_labels * sizeof(osmt_labelinfo));
+    const size_t o_info = carve(n_labels * sizeof(osmt_labelinfo));
     const size_t o_off = carve(((size_t)sc->n_jobs + 1) * 4);
-    const size_t o_segs = carve(lb->n_segs * 32);
+    const size_t o_segs = carve(n_segs_total * 32);
     const size_t o_a = carve((cells + 1) * 8);
     const size_t o_s = carve((wide_cells + 1) * 8);
     const size_t o_bits = carve((bit_words + 2) * 8); /* + the word a funnel read may touch behind the last stream */
     const size_t o_wide = carve((wide.size() + 1) * 4);
     const size_t o_bands = carve((bands.size() + 1) * sizeof(osmt_label_band));
     const size_t o_bm = carve(words * 4 <= 96 * 1024 ? 4 : (size_t)sc->n_jobs * words * 4); /* scale 1: the map lives in LDS */
-    const size_t o_tl = carve(lb->n_labels * sizeof(osmt_tile_label));
+    const size_t o_tl = carve(n_labels * sizeof(osmt_tile_label));
     const size_t o_tlc = carve((size_t)sc->n_jobs * 4);
-    const size_t o_ok = carve(lb->n_labels);
+    const size_t o_ok = carve(n_labels);
     const size_t o_err = carve(4);
     hipError_t e = dev_alloc(ctx, (void**)&sc->d_lab_base, off + 256);
     if (e != hipSuccess) {
@@ -1570,8 +1750,13 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
         return st ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
     };
     e = up(sc->d_lab, info.data(), info.size() * sizeof(osmt_labelinfo));
-    if (e == hipSuccess) e = up(sc->d_job_label_off, lb->job_label_off, ((size_t)sc->n_jobs + 1) * 4);
-    if (e == hipSuccess) e = up(sc->d_lab_segs, lb->segs, lb->n_segs * 32);
+    if (e == hipSuccess) e = up(sc->d_job_label_off, job_label_off, ((size_t)sc->n_jobs + 1) * 4);
+    if (e == hipSuccess && lb) e = up(sc->d_lab_segs, lb->segs, lb->n_segs * 32);
+    if (e == hipSuccess && gb) { /* the glyph runs' calls, written straight into the arena */
+        gp.segs = sc->d_lab_segs;
+        gp.n_segs = (uint32_t)n_segs_total;
+        e = osmt_launch_glyph_emit(gp, st);
+    }
     if (e == hipSuccess) e = up(sc->d_lab_wide, wide.data(), wide.size() * 4);
     if (e == hipSuccess) e = up(sc->d_lab_bands, bands.data(), bands.size() * sizeof(osmt_label_band));
     /* The verdicts and the error word are cleared by the label stage itself, on the render stream (osmt_launch_labels).
@@ -1585,13 +1770,66 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
         sc->d_lab_base = nullptr;
         return fail(OSMT_HIP_ERROR, "label upload failed: %s", hipGetErrorString(e));
     }
-    sc->n_labels = (uint32_t)lb->n_labels;
-    sc->n_label_segs = (uint32_t)lb->n_segs;
+    if (gb) { /* the emit pass's own check (a call beyond the arena the count pass sized): a 4-byte read-back */
+        uint32_t err = 0;
+        e = hipMemcpyAsync(&err, gp.err, 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess || err) {
+            dev_free(ctx, sc->d_lab_base);
+            sc->d_lab_base = nullptr;
+            return e != hipSuccess ? fail(OSMT_HIP_ERROR, "glyph emit pass failed: %s", hipGetErrorString(e))
+                                   : fail(OSMT_HIP_ERROR, "glyph emit pass: internal error %u", err);
+        }
+    }
+    sc->n_labels = (uint32_t)n_labels;
+    sc->n_label_segs = (uint32_t)n_segs_total;
     return OSMT_OK;
 }
 
 int osmt_scene_set_labels(osmt_ctx* ctx, osmt_scene* sc, const osmt_label_batch* lb) {
     return guarded([&] { return osmt_scene_set_labels_body(ctx, sc, lb); });
+}
+
+int osmt_scene_set_glyph_labels(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_label_batch* gb) {
+    return guarded([&] { return osmt_scene_set_labels_body(ctx, sc, nullptr, gb); });
+}
+
+static int osmt_scene_read_label_segs_body(osmt_ctx* ctx, osmt_scene* sc, double* out, size_t cap, size_t* n) {
+    if (!ctx || !sc || sc->ctx != ctx || !n) return fail(OSMT_INVALID_ARG, "NULL argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(scene_wait_idle(sc));
+    *n = sc->n_labels ? sc->n_label_segs : 0;
+    if (!out) return OSMT_OK;
+    if (cap < *n) return fail(OSMT_INVALID_ARG, "out holds %zu draw_line calls, the arena has %zu", cap, *n);
+    if (*n) HIP_TRY(copy_back(ctx, out, sc->d_lab_segs, *n * 32));
+    return OSMT_OK;
+}
+
+int osmt_scene_read_label_segs(osmt_ctx* ctx, osmt_scene* sc, double* out, size_t cap, size_t* n) {
+    return guarded([&] { return osmt_scene_read_label_segs_body(ctx, sc, out, cap, n); });
+}
+
+static int osmt_debug_hypot_body(osmt_ctx* ctx, const double* xy, size_t n, double* out) {
+    if (!ctx || (n && (!xy || !out))) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (n >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "too many pairs");
+    if (!n) return OSMT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = nullptr;
+    HIP_TRY(stream_acquire(ctx, &st));
+    char* d = nullptr;
+    hipError_t e = dev_alloc(ctx, (void**)&d, n * 24);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, xy, n * 16, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = osmt_launch_hypot((const double*)d, (uint32_t)n, (double*)(d + n * 16), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + n * 16, n * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (d) dev_free(ctx, d);
+    stream_release(ctx, st);
+    if (e != hipSuccess) return fail(OSMT_HIP_ERROR, "device hypot failed: %s", hipGetErrorString(e));
+    return OSMT_OK;
+}
+
+int osmt_debug_hypot(osmt_ctx* ctx, const double* xy, size_t n, double* out) {
+    return guarded([&] { return osmt_debug_hypot_body(ctx, xy, n, out); });
 }
 
 static int osmt_scene_read_label_status_body(osmt_ctx* ctx, osmt_scene* sc, uint8_t* ok) {
@@ -1665,22 +1903,22 @@ int osmt_render_batch(osmt_ctx* ctx, const osmt_batch* batch, uint8_t* out_rgba,
 }
 
 static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba, size_t stride,
-                                         bool rgb, bool trusted, bool allow_guess);
+                                         bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels);
 
 /* the host-buffer render: arenas guessed from the recent densities first; a miss renders again with exact sizing */
 static int osmt_render_batch_labels_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,
-                                         size_t stride, bool rgb = false, bool trusted = false) {
+                                         size_t stride, bool rgb = false, bool trusted = false, const osmt_glyph_label_batch* glabels = nullptr) {
     g_arena_guess_missed = false;
-    int rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, trusted, true);
+    int rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, trusted, true, glabels);
     if (rc != OSMT_OK && g_arena_guess_missed) {
         g_arena_guess_missed = false;
-        rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, true, false); /* validated the first time */
+        rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, true, false, glabels); /* validated the first time */
     }
     return rc;
 }
 
 static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba, size_t stride,
-                                         bool rgb, bool trusted, bool allow_guess) {
+                                         bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels) {
     if (!ctx || !out_rgba) return fail(OSMT_INVALID_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = nullptr; /* the whole call lives on its own stream: concurrent callers overlap on the GPU */
@@ -1691,8 +1929,8 @@ static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch,
         stream_release(ctx, st);
         return rc;
     }
-    if (labels) {
-        rc = osmt_scene_set_labels(ctx, sc, labels);
+    if (labels || glabels) {
+        rc = labels ? osmt_scene_set_labels(ctx, sc, labels) : osmt_scene_set_glyph_labels(ctx, sc, glabels);
         if (rc != OSMT_OK) {
             osmt_scene_free(sc);
             stream_release(ctx, st);
@@ -1826,6 +2064,10 @@ static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch,
 
 int osmt_render_batch_rgb(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgb, size_t stride) {
     return guarded([&] { return osmt_render_batch_labels_body(ctx, batch, labels, out_rgb, stride, true); });
+}
+
+int osmt_render_batch_rgb_glyphs(osmt_ctx* ctx, const osmt_batch* batch, const osmt_glyph_label_batch* labels, uint8_t* out_rgb, size_t stride) {
+    return guarded([&] { return osmt_render_batch_labels_body(ctx, batch, nullptr, out_rgb, stride, true, false, labels); });
 }
 
 int osmt_render_batch_labels(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/osmtile.h"
+#include "osmt_glyph.h"
 
 /* Sub-tile geometry of k_raster: OSMT_SUB_W x OSMT_SUB_H pixels per workgroup.  Sub-tile
  * coverage masks (osmt_raster_args.submask) have one 32-bit word per sub-tile ROW. */
@@ -233,6 +234,24 @@ struct osmt_label_args {
     const double* plane;           /* A pool after k_label_cover: min(a + s_acc, 1.0) per cell, 0 where no key */
 };
 
+/* glyph-run labels (osmt_glyphs.hip): one (label, glyph instance) pair per wave, pairs in label order */
+struct osmt_glyph_pass {
+    const osmt_glyph_vertex* verts; /* the context's glyph table snapshot */
+    const uint32_t* voff;           /* [n_glyphs + 1] */
+    const osmt_glyph_instance* inst;
+    const uint32_t* pair_inst;  /* [n_pairs] instance of the pair */
+    const uint32_t* pair_label; /* [n_pairs] its label */
+    uint32_t n_pairs;
+    int32_t W;                 /* tile width in pixels */
+    osmt_label_extent* sum;    /* [n_labels] per-label window summary (count pass) */
+    uint32_t* pair_cnt;        /* [n_pairs] draw_line calls of the pair (count pass) */
+    uint32_t* pair_base;       /* [n_pairs] exclusive scan inside blocks of 1024 pairs */
+    uint32_t* blk;             /* [n_pairs / 1024 + 1] block totals -> their exclusive scan */
+    uint32_t* err;             /* OSMT_GLYPH_ERR_* */
+    double* segs;              /* emit pass: the label pass's draw_line arena, n_segs calls */
+    uint32_t n_segs;
+};
+
 /* SMALL batches (the one-tile request, a gathered worker group): a tile with at most this many ops gets no per-sub-tile lists
  * from k_sublist — one word of op bits per lane (two rounds) and a ballot give a sub-tile wave its list in op order directly,
  * and a launch (8 us of a 105 us request) is saved.  Big batches keep the lists: there the scattered reads of the op bits by
@@ -323,6 +342,12 @@ hipError_t osmt_launch_prepass(const osmt_prepass_args& a, hipStream_t st, bool 
 hipError_t osmt_launch_raster(const osmt_raster_args& a, bool out_f64, hipStream_t st);
 /* label pass: cover (one wave per label) -> resolve (one workgroup per tile, labels in order) */
 hipError_t osmt_launch_labels(const osmt_label_launch& a, hipStream_t st);
+/* glyph-run labels: k_glyph_init + k_glyph_count (window summaries, pair counts, error word) */
+hipError_t osmt_launch_glyph_count(const osmt_glyph_pass& a, uint32_t n_labels, hipStream_t st);
+/* the scan of the pair counts + k_glyph_emit (draw_line calls into a.segs) */
+hipError_t osmt_launch_glyph_emit(const osmt_glyph_pass& a, hipStream_t st);
+/* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
+hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */
 hipError_t osmt_launch_png(const void* rgba, size_t tile_stride, uint32_t n, uint32_t W, uint32_t H, uint32_t ihdr_crc, void* out,
                            size_t out_stride, uint32_t* out_len, hipStream_t st);

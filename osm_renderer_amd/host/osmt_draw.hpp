@@ -93,6 +93,14 @@ class Context {
         check(osmt_register_image(ctx_, rgba8, w, h, &id));
         return id;
     }
+    /* the font's outlines for glyph-run texts (Rasterizer::draw_glyph): glyph i of the call is v[vertex_off[i] ..
+     * vertex_off[i + 1]) (stb_truetype's Vertex list of get_glyph_shape; empty for a glyph without shape) and gets the
+     * returned id + i */
+    uint32_t register_glyphs(const osmt_glyph_vertex* v, const uint32_t* vertex_off, uint32_t n_glyphs) {
+        uint32_t id = 0;
+        check(osmt_register_glyphs(ctx_, v, vertex_off, n_glyphs, &id));
+        return id;
+    }
 
   private:
     osmt_ctx* ctx_ = nullptr;
@@ -123,6 +131,7 @@ class TilePixels {
         pending_op_ = false;
         labels_.clear();
         label_segs_.clear();
+        label_glyphs_.clear();
         pending_label_ = osmt_label{};
     }
     /* drawer.rs:218: closes the current area; an area that drew nothing still counts */
@@ -153,8 +162,14 @@ class TilePixels {
         const size_t dim = dimension();
         std::vector<uint8_t> rgb(dim * dim * 3); /* the reference's triples, packed (std::tuple's own layout is not) */
         const uint32_t off[2] = {0u, (uint32_t)labels_.size()};
-        osmt_label_batch lb{labels_.data(), labels_.size(), off, label_segs_.data(), label_segs_.size() / 4};
-        check(osmt_render_batch_rgb(ctx_->raw(), &b, labels_.empty() ? nullptr : &lb, rgb.data(), rgb.size()));
+        if (!label_glyphs_.empty()) { /* texts recorded as glyph runs (Rasterizer::draw_glyph): expanded on the GPU */
+            if (!label_segs_.empty()) throw Error(OSMT_UNSUPPORTED, "a tile's texts are either draw_line calls or glyph runs, not both");
+            osmt_glyph_label_batch gb{labels_.data(), labels_.size(), off, label_glyphs_.data(), label_glyphs_.size()};
+            check(osmt_render_batch_rgb_glyphs(ctx_->raw(), &b, &gb, rgb.data(), rgb.size()));
+        } else {
+            osmt_label_batch lb{labels_.data(), labels_.size(), off, label_segs_.data(), label_segs_.size() / 4};
+            check(osmt_render_batch_rgb(ctx_->raw(), &b, labels_.empty() ? nullptr : &lb, rgb.data(), rgb.size()));
+        }
         RgbTriples out(dim * dim);
         for (size_t i = 0; i < dim * dim; ++i) out[i] = {rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]};
         return out;
@@ -243,6 +258,7 @@ class TilePixels {
     bool pending_op_ = false;
     std::vector<osmt_label> labels_;
     std::vector<double> label_segs_; /* x0, y0, x1, y1 per Rasterizer::draw_line call */
+    std::vector<osmt_glyph_instance> label_glyphs_; /* per Rasterizer::draw_glyph call */
     osmt_label pending_label_{};
 };
 
@@ -286,6 +302,20 @@ class Rasterizer {
         draw_quad(x0, y0, m01_x, m01_y, m012_x, m012_y);
         draw_quad(m012_x, m012_y, m12_x, m12_y, x2, y2);
     }
+    /* Glyph::rasterize (font/text_placer.rs:232-259) recorded as one glyph instance instead of its draw_line /
+     * draw_quad calls: the GPU walks the outline (osmt_scene_set_glyph_labels).  glyph_id from osmt_register_glyphs,
+     * scale = f64::from(scale_for_pixel_height(..)), form OSMT_GLYPH_CENTER with params {x_offset, baseline} or
+     * OSMT_GLYPH_LINE with {glyph_center_x, glyph_center_y, angle_sin, angle_cos, way_x, way_y}.  A text is either
+     * draw_line calls or glyph instances.  Only TilePixels::to_rgb_triples renders glyph-run texts so far: TileBatch
+     * (and its PNG call) refuses a tile that holds one with OSMT_UNSUPPORTED. */
+    void draw_glyph(uint32_t glyph_id, double scale, uint32_t form, const double* params) {
+        osmt_glyph_instance g{};
+        g.glyph_id = glyph_id;
+        g.form = form;
+        g.scale = scale;
+        for (int k = 0; k < (form == OSMT_GLYPH_LINE ? 6 : 2); ++k) g.p[k] = params[k];
+        glyphs_.push_back(g);
+    }
     /* :115-147: hands the text of the label being built to the canvas.  Always true (see draw_icon). */
     bool save_to_figure(TilePixels& pixels) const {
         osmt_label& l = pixels.pending_label_;
@@ -293,6 +323,13 @@ class Rasterizer {
         l.text_color[0] = color_.r;
         l.text_color[1] = color_.g;
         l.text_color[2] = color_.b;
+        if (!glyphs_.empty()) {
+            if (!segs_.empty()) throw Error(OSMT_UNSUPPORTED, "a text is either draw_line calls or glyph runs, not both");
+            l.seg_off = (uint32_t)pixels.label_glyphs_.size();
+            l.n_segs = (uint32_t)glyphs_.size();
+            pixels.label_glyphs_.insert(pixels.label_glyphs_.end(), glyphs_.begin(), glyphs_.end());
+            return true;
+        }
         l.seg_off = (uint32_t)(pixels.label_segs_.size() / 4);
         l.n_segs = (uint32_t)(segs_.size() / 4);
         pixels.label_segs_.insert(pixels.label_segs_.end(), segs_.begin(), segs_.end());
@@ -302,6 +339,7 @@ class Rasterizer {
   private:
     Color color_;
     std::vector<double> segs_;
+    std::vector<osmt_glyph_instance> glyphs_;
 };
 
 /* fill.rs:16 */
@@ -353,6 +391,9 @@ class TileBatch {
   public:
     explicit TileBatch(Context& ctx, size_t scale) : ctx_(&ctx), scale_(scale) {}
     void add(const Tile& tile, const TilePixels& px) {
+        /* the batch entries take draw_line calls only: a glyph-run label's seg_off / n_segs name glyph instances and
+         * would be read as another label's calls */
+        if (!px.label_glyphs_.empty()) throw Error(OSMT_UNSUPPORTED, "TileBatch takes no glyph-run texts (Rasterizer::draw_glyph) yet");
         const uint32_t op_off = (uint32_t)ops_.size(), pt_off = (uint32_t)(points_.size() / 2);
         const uint32_t ring_off = (uint32_t)rings_.size(), dash_off = (uint32_t)dashes_.size();
         jobs_.push_back(px.make_job(tile, op_off, pt_off));

@@ -4,7 +4,12 @@ One osmt_label == one Labeler::label_entity call (labeler.rs:16-38): an optional
 optional text, the text given as the Rasterizer::draw_line calls (font/rasterizer.rs:27-88) the
 reference's glyph walk makes.  Curves are flattened HERE (host side) exactly like
 Rasterizer::draw_quad (font/rasterizer.rs:90-113) with libm's hypot, which is what f64::hypot is.
+
+The second form, glyph runs (GlyphTable + GlyphLabelList), names glyph instances with the transform
+TextPlacer::place passes to Glyph::rasterize; the library expands them on the GPU.
+GlyphLabelList.to_label_list() is the same expansion on the host, with glyph_segments below.
 """
+import math
 import ctypes as C
 import ctypes.util
 
@@ -246,3 +251,219 @@ def make_labels(n_tiles, labels_per_tile=24, scale=1, seed=7, n_images=0, image_
             tl.label(icon=icon, text=text)
         out.append(tl.build())
     return concat_labels(out)
+
+
+# ---- glyph runs (osmt_glyph_label_batch) ---------------------------------------------------------
+GLYPH_VERTEX_DTYPE = np.dtype([("x", "i2"), ("y", "i2"), ("cx", "i2"), ("cy", "i2"), ("type", "u1"), ("_pad", "u1")])
+GLYPH_INSTANCE_DTYPE = np.dtype([("glyph_id", "u4"), ("form", "u4"), ("scale", "f8"), ("p", "f8", (6,))])
+assert GLYPH_VERTEX_DTYPE.itemsize == 10 and GLYPH_INSTANCE_DTYPE.itemsize == 64
+_VERTEX_TYPE = {"M": abi.GLYPH_MOVE_TO, "L": abi.GLYPH_LINE_TO, "Q": abi.GLYPH_CURVE_TO}
+
+
+def center_tr(x_offset, baseline):
+    """TextPlacer::place, TextPosition::Center (font/text_placer.rs:150-153)."""
+    return lambda p: (x_offset + p[0], baseline - p[1])
+
+
+def line_tr(glyph_center_x, glyph_center_y, angle_sin, angle_cos, way_x, way_y):
+    """TextPlacer::place, TextPosition::Line (font/text_placer.rs:87-101); (angle_sin, angle_cos) = (-angle).sin_cos()."""
+
+    def tr(p):
+        translated_x = p[0] - glyph_center_x
+        translated_y = p[1] - glyph_center_y
+        rotated_x = translated_x * angle_cos - translated_y * angle_sin
+        rotated_y = translated_y * angle_cos + translated_x * angle_sin
+        return (way_x + rotated_x, way_y - rotated_y)
+
+    return tr
+
+
+class GlyphTable:
+    """Glyph outlines as stb-style vertex lists [(type, x, y, cx, cy)] with type 'M' / 'L' / 'Q' in font units (an
+    empty list is a glyph without shape).  Context.register_glyphs uploads them and sets `first_id`: glyph i of the
+    table has id first_id + i."""
+
+    def __init__(self, outlines):
+        self.outlines = [list(o) if o else [] for o in outlines]
+        self.first_id = 0
+
+    def __len__(self):
+        return len(self.outlines)
+
+    def outline(self, glyph_id):
+        return self.outlines[glyph_id - self.first_id]
+
+    def arrays(self):
+        """(vertices GLYPH_VERTEX_DTYPE, vertex_off uint32 [n + 1]) as osmt_register_glyphs takes them."""
+        voff = np.zeros(len(self.outlines) + 1, dtype=np.uint32)
+        verts = np.zeros(sum(len(o) for o in self.outlines), dtype=GLYPH_VERTEX_DTYPE)
+        k = 0
+        for i, o in enumerate(self.outlines):
+            for t, x, y, cx, cy in o:
+                verts[k] = (x, y, cx, cy, _VERTEX_TYPE[t], 0)
+                k += 1
+            voff[i + 1] = k
+        return verts, voff
+
+
+class GlyphLabelList:
+    """Labels of a batch with glyph-run text (osmt_glyph_label_batch): `labels` are osmt_label records whose
+    seg_off / n_segs name a range of `glyphs` (GLYPH_INSTANCE_DTYPE) instead of draw_line calls."""
+
+    def __init__(self, labels, job_label_off, glyphs):
+        self.labels = np.ascontiguousarray(labels, dtype=LABEL_DTYPE)
+        self.job_label_off = np.ascontiguousarray(job_label_off, dtype=np.uint32)
+        self.glyphs = np.ascontiguousarray(glyphs, dtype=GLYPH_INSTANCE_DTYPE)
+
+    @property
+    def n_jobs(self):
+        return len(self.job_label_off) - 1
+
+    def as_batch(self):
+        b = abi.GlyphLabelBatch()
+        b.labels = self.labels.ctypes.data_as(C.POINTER(abi.Label))
+        b.n_labels = len(self.labels)
+        b.job_label_off = self.job_label_off.ctypes.data_as(C.POINTER(C.c_uint32))
+        b.glyphs = self.glyphs.ctypes.data_as(C.POINTER(abi.GlyphInstance)) if len(self.glyphs) else None
+        b.n_glyphs = len(self.glyphs)
+        return b
+
+    def input_bytes(self):
+        """bytes handed to the library: 40 per label + 64 per glyph instance + the job offsets."""
+        return 40 * len(self.labels) + 64 * len(self.glyphs) + 4 * len(self.job_label_off)
+
+    def subset(self, idx):
+        """The labels of tiles idx (in that order) as a GlyphLabelList of their own, instances re-packed."""
+        parts = []
+        for i in idx:
+            a, b = int(self.job_label_off[i]), int(self.job_label_off[i + 1])
+            lab = self.labels[a:b].copy()
+            gs, cur = [], 0
+            for l in lab:
+                n = int(l["n_segs"])
+                gs.append(self.glyphs[int(l["seg_off"]) : int(l["seg_off"]) + n])
+                l["seg_off"] = cur if n else 0
+                cur += n
+            parts.append(GlyphLabelList(lab, [0, len(lab)], np.concatenate(gs) if gs else np.zeros(0, GLYPH_INSTANCE_DTYPE)))
+        return concat_glyph_labels(parts)
+
+    def to_label_list(self, table):
+        """The host expansion: every label's draw_line calls in label, glyph, vertex order (Glyph::rasterize with
+        glyph_segments and the instance's `tr`), as the segment-form LabelList the GPU expansion must equal."""
+        labels = self.labels.copy()
+        segs = []
+        n = 0
+        for l in labels:
+            if not l["has_text"]:
+                l["seg_off"], l["n_segs"] = 0, 0
+                continue
+            out = []
+            for g in self.glyphs[int(l["seg_off"]) : int(l["seg_off"]) + int(l["n_segs"])]:
+                p = [float(v) for v in g["p"]]
+                tr = center_tr(p[0], p[1]) if int(g["form"]) == abi.GLYPH_CENTER else line_tr(*p)
+                glyph_segments(table.outline(int(g["glyph_id"])), float(g["scale"]), tr, out)
+            l["seg_off"] = n if out else 0
+            l["n_segs"] = len(out)
+            n += len(out)
+            segs.extend(out)
+        return LabelList(labels, self.job_label_off.copy(), np.array(segs, dtype=np.float64).reshape(-1, 4))
+
+
+def concat_glyph_labels(lists):
+    labels, offs, glyphs = [], [0], []
+    cur = 0
+    for gl in lists:
+        lab = gl.labels.copy()
+        lab["seg_off"][lab["n_segs"] > 0] += cur
+        labels.append(lab)
+        glyphs.append(gl.glyphs)
+        cur += len(gl.glyphs)
+        offs.extend((offs[-1] + gl.job_label_off[1:].astype(np.int64)).tolist())
+    return GlyphLabelList(np.concatenate(labels) if labels else np.zeros(0, LABEL_DTYPE), offs,
+                          np.concatenate(glyphs) if glyphs else np.zeros(0, GLYPH_INSTANCE_DTYPE))
+
+
+def synth_glyph_table():
+    """SYNTH_GLYPHS as a GlyphTable (the last one, the space, has no shape)."""
+    return GlyphTable([v for _, v in SYNTH_GLYPHS])
+
+
+# vertical metrics of the synthetic 1000-unit em (ascent, descent, line_gap) and TextPlacer's MAX_TEXT_WIDTH-free one-row layout
+_SYNTH_ASCENT, _SYNTH_DESCENT, _SYNTH_GAP = 800.0, -200.0, 0.0
+
+
+def _instance(glyph_id, form, scale, p):
+    g = np.zeros((), GLYPH_INSTANCE_DTYPE)
+    g["glyph_id"], g["form"], g["scale"] = glyph_id, form, scale
+    g["p"][: len(p)] = p
+    return g
+
+
+def synth_glyph_run(rng, table, cx, cy, font_px, n_glyphs, y_offset=0.0, angle=None):
+    """Glyph instances of one synthetic text laid out as TextPlacer::place does: TextPosition::Center around (cx, cy)
+    (one row; y_offset > 0 puts it below an icon, text_placer.rs:130-139), or, with `angle`, TextPosition::Line along
+    a straight way through (cx, cy) at that angle (compute_way_position on one segment)."""
+    scale = font_px / 1000.0
+    ids = [int(rng.integers(0, len(SYNTH_GLYPHS))) for _ in range(n_glyphs)]
+    widths = [float(SYNTH_GLYPHS[i][0]) * scale for i in ids]
+    total = 0.0
+    for w in widths:
+        total += w
+    asc, desc, gap = _SYNTH_ASCENT * scale, _SYNTH_DESCENT * scale, _SYNTH_GAP * scale
+    out = []
+    if angle is None:
+        row_height = asc - desc + gap
+        cur_y = cy + y_offset if y_offset > 0 else cy - row_height * 1.0 / 2.0
+        cur_x = cx - total / 2.0
+        for i, w in zip(ids, widths):
+            out.append(_instance(table.first_id + i, abi.GLYPH_CENTER, scale, [cur_x, cur_y + asc]))
+            cur_x += w
+    else:
+        s, c = math.sin(-angle), math.cos(-angle)
+        ux, uy = math.cos(angle), math.sin(angle)
+        length = total + float(rng.integers(0, 40))
+        sx, sy = cx - ux * length / 2.0, cy - uy * length / 2.0
+        cur = (length - total) / 2.0
+        gcy = (desc + asc) / 2.0
+        for i, w in zip(ids, widths):
+            gcx = w / 2.0
+            d = cur + gcx
+            out.append(_instance(table.first_id + i, abi.GLYPH_LINE, scale, [gcx, gcy, s, c, sx + ux * d, sy + uy * d]))
+            cur += w
+    return np.array(out, dtype=GLYPH_INSTANCE_DTYPE) if out else np.zeros(0, GLYPH_INSTANCE_DTYPE)
+
+
+def make_glyph_labels(n_tiles, table, labels_per_tile=24, scale=1, seed=7, n_images=0, image_sizes=None, text_frac=0.85,
+                      icon_frac=0.4, line_frac=0.3, empty_frac=0.03):
+    """The label workload of make_labels as glyph runs: center- and line-form texts over SYNTH_GLYPHS (spaces = empty
+    glyphs included) scattered over the 3x3-tile label area so that labels collide inside and outside the tile, icons
+    (n_images > 0), labels without text and texts of zero glyphs (empty_frac)."""
+    rng = np.random.default_rng(seed)
+    W = 256 * scale
+    lists = []
+    for _ in range(n_tiles):
+        labs, glyphs = [], []
+        for _ in range(labels_per_tile):
+            l = np.zeros((), LABEL_DTYPE)
+            cx = float(rng.integers(-W // 2, W + W // 2)) + float(rng.integers(0, 2)) * 0.5
+            cy = float(rng.integers(-W // 2, W + W // 2)) + float(rng.integers(0, 4)) * 0.25
+            y_off = 0.0
+            if n_images and rng.random() < icon_frac:
+                img = int(rng.integers(0, n_images))
+                l["has_icon"], l["image_id"] = 1, img
+                l["icon_center_x"], l["icon_center_y"] = cx, cy
+                y_off = float(image_sizes[img][0] // 2)
+            if rng.random() < text_frac:
+                l["has_text"] = 1
+                l["text_color"] = [int(v) for v in rng.integers(0, 256, size=3)]
+                font_px = float(rng.choice([9.0, 10.0, 11.0, 12.0, 14.0])) * scale
+                n_gl = 0 if rng.random() < empty_frac else int(rng.integers(3, 13))
+                angle = float(rng.uniform(-1.2, 1.2)) if rng.random() < line_frac else None
+                run = synth_glyph_run(rng, table, cx, cy, font_px, n_gl, y_offset=y_off, angle=angle)
+                l["seg_off"] = sum(len(g) for g in glyphs) if len(run) else 0
+                l["n_segs"] = len(run)
+                glyphs.append(run)
+            labs.append(l)
+        lists.append(GlyphLabelList(np.array(labs, dtype=LABEL_DTYPE), [0, len(labs)],
+                                    np.concatenate(glyphs) if glyphs else np.zeros(0, GLYPH_INSTANCE_DTYPE)))
+    return concat_glyph_labels(lists)

@@ -29,6 +29,8 @@ EXPORTS = [
     "osmt_comm_unique_id", "osmt_comm_init_rank", "osmt_comm_init_local", "osmt_allreduce_tile_count",
     "osmt_allreduce_tile_count_local", "osmt_allreduce_tile_count_enqueue", "osmt_allreduce_tile_count_result", "osmt_hbm_copy_probe",
     "osmt_debug_poison_enabled",
+    "osmt_register_glyphs", "osmt_scene_set_glyph_labels", "osmt_render_batch_rgb_glyphs", "osmt_scene_read_label_segs",
+    "osmt_debug_hypot",
 ]
 
 
@@ -105,6 +107,12 @@ def load():
     L.osmt_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.osmt_host_free.argtypes = [vp, vp]
     L.osmt_host_free.restype = None
+    if hasattr(L, "osmt_register_glyphs"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_register_glyphs.argtypes = [vp, C.POINTER(abi.GlyphVertex), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
+        L.osmt_scene_set_glyph_labels.argtypes = [vp, vp, C.POINTER(abi.GlyphLabelBatch)]
+        L.osmt_render_batch_rgb_glyphs.argtypes = [vp, C.POINTER(abi.Batch), C.POINTER(abi.GlyphLabelBatch), u8p, C.c_size_t]
+        L.osmt_scene_read_label_segs.argtypes = [vp, vp, dp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.osmt_debug_hypot.argtypes = [vp, dp, C.c_size_t, dp]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

@@ -50,6 +50,26 @@ class Scene:
             check(load().osmt_scene_set_labels(self.ctx._h, self._h, C.byref(lb)))
         self.labels = labels
 
+    def set_glyph_labels(self, glyph_labels):
+        """osmt_scene_set_glyph_labels: attach glyph-run labels (labels.GlyphLabelList; None detaches).  The glyph ids
+        must be registered on this scene's context (Context.register_glyphs)."""
+        if glyph_labels is None:
+            check(load().osmt_scene_set_glyph_labels(self.ctx._h, self._h, None))
+        else:
+            assert glyph_labels.n_jobs == self.n_jobs
+            gb = glyph_labels.as_batch()
+            check(load().osmt_scene_set_glyph_labels(self.ctx._h, self._h, C.byref(gb)))
+        self.labels = glyph_labels
+
+    def read_label_segs(self):
+        """osmt_scene_read_label_segs: the draw_line arena the label kernels read, float64 [n, 4]."""
+        L, n = load(), C.c_size_t(0)
+        check(L.osmt_scene_read_label_segs(self.ctx._h, self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 4), dtype=np.float64)
+        if n.value:
+            check(L.osmt_scene_read_label_segs(self.ctx._h, self._h, out.ctypes.data_as(C.POINTER(C.c_double)), n.value, C.byref(n)))
+        return out
+
     def label_status(self):
         """label_generation_statuses of the last render (tile_pixels.rs:160-162)."""
         n = len(self.labels.labels) if self.labels is not None else 0
@@ -174,6 +194,25 @@ class Context:
         check(load().osmt_register_image(self._h, img.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, C.byref(out)))
         return out.value
 
+    # -- glyph outlines (glyph-run labels) -----------------------------------------
+    def register_glyphs(self, table):
+        """osmt_register_glyphs: appends the outlines of a labels.GlyphTable; returns (and records in the table) the id
+        of its first glyph."""
+        verts, voff = table.arrays()
+        out = C.c_uint32()
+        check(load().osmt_register_glyphs(self._h, verts.ctypes.data_as(C.POINTER(abi.GlyphVertex)) if len(verts) else None,
+                                          voff.ctypes.data_as(C.POINTER(C.c_uint32)), len(voff) - 1, C.byref(out)))
+        table.first_id = out.value
+        return out.value
+
+    def debug_hypot(self, x, y):
+        """osmt_debug_hypot: the device hypot of the glyph walk over pairs, float64."""
+        xy = np.ascontiguousarray(np.stack([np.asarray(x, np.float64).ravel(), np.asarray(y, np.float64).ravel()], axis=1))
+        out = np.empty(len(xy), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        check(load().osmt_debug_hypot(self._h, xy.ctypes.data_as(dp), len(xy), out.ctypes.data_as(dp)))
+        return out
+
     # -- whole path --------------------------------------------------------------
     def upload(self, dl: DisplayList, labels=None) -> Scene:
         return Scene(self, dl, labels)
@@ -245,6 +284,19 @@ class Context:
         lb = labels.as_batch() if labels is not None else None
         check(load().osmt_render_batch_rgb(self._h, C.byref(b), C.byref(lb) if lb is not None else None,
                                            out.ctypes.data_as(C.POINTER(C.c_uint8)), stride))
+        return out
+
+    def render_batch_rgb_glyphs(self, dl: DisplayList, glyph_labels, out=None, stride=None):
+        """osmt_render_batch_rgb_glyphs: osmt_render_batch_rgb with glyph-run labels (labels.GlyphLabelList)."""
+        b = dl.as_batch()
+        tight = dl.dim * dl.dim * 3
+        stride = tight if stride is None else stride
+        if out is None:
+            out = np.empty((dl.n_jobs, stride), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size >= dl.n_jobs * stride
+        gb = glyph_labels.as_batch() if glyph_labels is not None else None
+        check(load().osmt_render_batch_rgb_glyphs(self._h, C.byref(b), C.byref(gb) if gb is not None else None,
+                                                  out.ctypes.data_as(C.POINTER(C.c_uint8)), stride))
         return out
 
     # -- PNG files from the GPU ----------------------------------------------------
