@@ -849,6 +849,37 @@ __device__ __forceinline__ void walk_plain(RunState& st, const StrokeConst& kc, 
     }
 }
 
+/* fmod(x, total) by subtracting total * 2^k, each step exact by Sterbenz (total * 2^k <= x <= 2 total * 2^k); fmod(x, +inf)
+ * == x.  At most ~2100 steps (exponent range): the cold path of dash_rem. */
+__device__ __noinline__ double dash_rem_by_halving(double x, const double total) {
+    if (!(total < INFINITY)) return x;
+    while (x >= total) {
+        double t = ldexp(total, ilogb(x) - ilogb(total));
+        if (t > x) t *= 0.5;
+        x -= t;
+    }
+    return x;
+}
+
+/* dist_rem % total (opacity_calculator.rs:57-60) for a finite x >= 0 and total > 0 (+inf included), bit for bit fmod.
+ * The quotient is estimated with RN(1 / total) and corrected once.  A result that lands in [0, total) is exact: x, total
+ * and the integer nq make v = x - nq * total a multiple of the smallest denormal, RN is monotone and never rounds such a
+ * v != 0 to 0, so RN(v) in [0, total) means v in [0, total), i.e. nq is the quotient and v = fmod(x, total), which is
+ * representable.  Anything else — quotients beyond ~2^52 (tiny dashes, long polylines), total = +inf (0 * inf is NaN),
+ * a denormal total (RN(1 / total) = inf) — is reduced exactly by dash_rem_by_halving. */
+__device__ __forceinline__ double dash_rem(const double x, const double total, const double r_total) {
+    double nq = trunc(x * r_total);
+    double rr = fma(-nq, total, x);
+    if (rr < 0.0) {
+        nq -= 1.0;
+        rr = fma(-nq, total, x);
+    } else if (rr >= total) {
+        nq += 1.0;
+        rr = fma(-nq, total, x);
+    }
+    return (rr >= 0.0 && rr < total) ? rr : dash_rem_by_halving(x, total);
+}
+
 /* A run of a calculator WITH dash segments — a dashed edge, or a cap stub (opacity_calculator_for_outer_caps,
  * line.rs:22) — opacity_calculator.rs:32-80 in full.  `t` is wave-uniform (edges and stubs are walked in separate
  * passes), so the table is read with scalar loads. */
@@ -865,18 +896,7 @@ __device__ __forceinline__ void walk_dashed(RunState& st, const StrokeConst& kc,
         const double ld = sqrt(ddx * ddx + ddy * ddy);          /* dist(pixel, p1), line.rs:119 */
         const double sd = sqrt(fmax(ld * ld - cd * cd, 0.0));    /* line.rs:120 */
         double dist_rem = traveled + sd;
-        if (total > 0.0) { /* dist_rem >= 0: exact `%` (opacity_calculator.rs:57-60), quotient estimated with RN(1 / total) */
-            double nq = trunc(dist_rem * r_total);
-            double rr = fma(-nq, total, dist_rem);
-            if (rr < 0.0) {
-                nq -= 1.0;
-                rr = fma(-nq, total, dist_rem);
-            } else if (rr >= total) {
-                nq += 1.0;
-                rr = fma(-nq, total, dist_rem);
-            }
-            dist_rem = rr;
-        }
+        if (total > 0.0) dist_rem = dash_rem(dist_rem, total, r_total); /* dist_rem >= 0 */
         double sd_op = 0.0, dic = 0.0;
         bool has = false;
         for (int i = 0; i < n; ++i) {
@@ -920,7 +940,7 @@ __device__ __forceinline__ void walk_dashed(RunState& st, const StrokeConst& kc,
 /* ---- dashed edges without original_endpoints: the calculator only where the dash phase needs it (round 6) -----------
  * A pixel of a dashed edge costs the full calculator — dist(pixel, p1), two square roots, the exact `%`, the loop over
  * the DashSegments (opacity_calculator.rs:32-80): ~280 instructions against the 57 of an un-dashed one; a quarter of
- * config 2's stroke ops cost as much as the other three quarters (profiles/r06_a_heavy_split.txt).  But WITHOUT
+ * config 2's stroke ops cost as much as the other three quarters (profiles/r06_a_occupancy_and_heavy_probes.txt).  But WITHOUT
  * original_endpoints (cap_dist == 0 for every pixel: the line cap is not Round, or use_caps_for_dashes is off)
  *   (1) how far a run goes does not depend on the dashes: is_in_line <=> cdop > 0 <=> cd < feather_to, as for an
  *       un-dashed edge (mul0 > 0; STROKE_TINY_MUL ops do not come here);
@@ -935,31 +955,28 @@ __device__ __forceinline__ void walk_dashed(RunState& st, const StrokeConst& kc,
  *     ld^2 = S (1 + d3), |d3| <= 2^-50;   cd^2 = CD^2 (1 + d5), |d5| <= 2^-49;   diff = SD^2 + e,
  *     |e| <= S 2^-50 + CD^2 2^-49 + 2^-53 |diff| <= SD^2 2^-49 + CD^2 2^-48,
  *     |sqrt(max(diff, 0)) - SD| <= min(|e| / SD, sqrt(2 |e|)) <= SD 2^-49 + CD 2^-23  (CD < feather_to <= 2^15 + 1: <= 2^-7.9),
- * then adds `traveled` (one rounding, <= 2^-53 of the sum) and takes an exact `%`; the approximation has relative error
- * 2^-50.  mu = 2^-7 + 2^-40 (traveled + distance along the line + 64) is above all of it for every input the
- * validation admits (|coordinates| <= 2^28, widths <= 65536).  Pixels within mu of a ramp, of 0 or of the pattern
- * length — a few per cent for real dash patterns — are queued (sub-tile cell + record: four bytes) and evaluated by the
- * EXACT calculator with lanes packed, once the queue holds a wave's worth or the op's runs are walked; everything
- * a queued pixel needs is recomputed from its cell and its record, bit for bit what the run held
- * (center_dist_raw is an exact integer either way).  tests/test_gpu_parity_ops.py::test_dash_phase_*, the fuzzer and the
- * golden crops "dashed" / "subway" hold the two paths against the oracle. */
+ * then adds `traveled` (one rounding, <= 2^-53 of the sum) and takes an exact `%` (dash_rem).  The approximation
+ * |dotv| * rdenom has relative error 2^-50 only while dotv = dot(pixel - p1, p2 - p1) is an exact integer, i.e. below
+ * 2^53: it is set up from two products and then updated by additions.  A run's pixels lie within feather_to + 2 of the
+ * edge's span, so |dotv| <= len (len + 2^15 + 3); for len < 2^26 (len^2 < 2^52) that is below 2^53 and every value of
+ * dotv is exact.  A longer edge (possible only at coordinates beyond ~2^25) gets no window: each of its pixels is queued
+ * for the exact calculator.  The window itself is base + [bounds of the interval] -+ mu with base = dt0 - fmod(dt0, total)
+ * (dash_rem: exact, also for total = +inf, where base = 0): base is q * total up to one rounding, and each bound takes two
+ * more, together <= 2^-51 of the bound, i.e. of the phases it separates.  mu = 2^-7 + 2^-40 (traveled + distance along
+ * the line + 64) is above all of it for every input the validation admits (|coordinates| <= 2^28, widths <= 65536; a
+ * pixel's distance along the line is within 2^16 of its run's first pixel's).  Pixels within mu of a ramp, of 0 or of
+ * the pattern length — a few per cent for real dash patterns — are queued (sub-tile cell + record: four bytes) and
+ * evaluated by the EXACT calculator with lanes packed, once the queue holds a wave's worth or the op's runs are walked;
+ * everything a queued pixel needs is recomputed from its cell and its record, bit for bit what the run held
+ * (center_dist_raw is an exact integer either way).  tests/test_gpu_parity_ops.py::test_dash_phase_ramp_edges,
+ * ::test_dash_phase_large_traveled, ::test_dash_phase_extreme_coordinates and ::test_dash_phase_extreme_dash_lists
+ * place pixels on, and ulps and fractions of mu beside, every boundary; with the fuzzer and the golden crops "dashed" /
+ * "subway" they hold the two paths against the oracle. */
 __device__ __forceinline__ double dashed_exact_opacity(const double (*dtab)[DTAB_F], int n, double total, double r_total, double ddx,
                                                        double ddy, double cd, double traveled) {
     const double ld = sqrt(ddx * ddx + ddy * ddy);       /* dist(pixel, p1), line.rs:119 */
     const double sd = sqrt(fmax(ld * ld - cd * cd, 0.0)); /* line.rs:120 */
-    double dist_rem = traveled + sd;
-    { /* total > 0, dist_rem >= 0: exact `%` (opacity_calculator.rs:57-60), quotient estimated with RN(1 / total) */
-        double nq = trunc(dist_rem * r_total);
-        double rr = fma(-nq, total, dist_rem);
-        if (rr < 0.0) {
-            nq -= 1.0;
-            rr = fma(-nq, total, dist_rem);
-        } else if (rr >= total) {
-            nq += 1.0;
-            rr = fma(-nq, total, dist_rem);
-        }
-        dist_rem = rr;
-    }
+    const double dist_rem = dash_rem(traveled + sd, total, r_total); /* total > 0, dist_rem >= 0 */
     double sd_op = 0.0;
     for (int i = 0; i < n; ++i) { /* opacity_calculator.rs:145-157 */
         const double s_from = dtab[i][0], s_to = dtab[i][1], e_from = dtab[i][2], e_to = dtab[i][3];
@@ -1041,16 +1058,18 @@ __device__ __forceinline__ void walk_items_dashed(Shared& sh, uint32_t slot0, ui
                 slot_tag = lo_s << 16;
                 const double dt0 = trav + fabs(dotv) * st.rdenom;
                 const double mu = 0x1p-7 + 0x1p-40 * (dt0 + 64.0);
-                const double base = trunc(dt0 * r_total) * total;
-                const double p0 = dt0 - base;
-                bool in_any = false, interior = false;
+                const double p0 = dash_rem(dt0, total, r_total); /* the exact phase of dt0: base = q * total up to one rounding */
+                const double base = dt0 - p0;
+                /* an edge of 2^26 px or more: dotv may pass 2^53 and lose bits in the additions, no window (every pixel exact) */
+                const bool short_edge = (int64_t)(r.p2x - r.p1x) * (r.p2x - r.p1x) + (int64_t)(r.p2y - r.p1y) * (r.p2y - r.p1y) < (1ll << 52);
+                bool in_any = !short_edge, interior = false;
                 double g_lo = 0.0, g_hi = total, i_lo = 0.0, i_hi = 0.0;
                 for (int i = 0; i < n; ++i) {
                     const double s_from = sh.dtab[i][0], s_to = sh.dtab[i][1], e_from = sh.dtab[i][2], e_to = sh.dtab[i][3];
                     in_any = in_any || (p0 >= s_from && p0 <= e_to);
                     g_lo = e_to < p0 ? fmax(g_lo, e_to) : g_lo;
                     g_hi = s_from > p0 ? fmin(g_hi, s_from) : g_hi;
-                    if (sh.dtab[i][4] == 1.0 && p0 > s_to && p0 < e_from) {
+                    if (short_edge && sh.dtab[i][4] == 1.0 && p0 > s_to && p0 < e_from) {
                         interior = true;
                         i_lo = fmax(s_to, 0.0);
                         i_hi = fmin(e_from, total);

@@ -479,3 +479,201 @@ def test_sublist_sift_ring_boundaries(gpu_ctx, oracle, hits):
     empty = TileBuilder(x=9, canvas=(1, 2, 3)).build()
     dl = concat(tiles + [empty] * 64)  # 66 tiles: every tile's lists come from k_sublist
     assert_parity(gpu_ctx, oracle, dl, f64_jobs=[0, 1], msg=f"{hits} ops in one sub-tile row")
+
+
+# ---- the dashed fast path (walk_items_dashed) at its boundaries --------------------------------------------------------
+# A pixel of a dashed edge without original_endpoints is sorted from an APPROXIMATE phase into inside-a-dash / inside-a-gap /
+# near-a-ramp with a margin mu = 2^-7 + 2^-40 (dt0 + 64); only the last kind meets the exact calculator.  These tests put
+# pixel phases ON start_from / start_to / end_from / end_to / 0 / total and 1 ulp, mu/2, mu and 2 mu beside them: on the
+# centre line of axis-aligned and (3, 4, 5) k edges the phase is an integer, and the dash values carry the offset.
+DASH_DELTAS = [0.0, 2.0**-50, -(2.0**-50), 2.0**-8, -(2.0**-8), 2.0**-7, -(2.0**-7), 2.0**-6, -(2.0**-6)]
+DASH_CAPS = [(abi.CAP_NONE, False), (abi.CAP_NONE, True), (abi.CAP_BUTT, False), (abi.CAP_BUTT, True), (abi.CAP_SQUARE, False),
+             (abi.CAP_SQUARE, True), (abi.CAP_ROUND, True)]  # the last one: original_endpoints, the exact walk_dashed (control)
+
+
+def _dash_patterns(d):
+    return {
+        "four-boundaries": [3.0, 2.5 + d, 4.0, 4.5],  # 2nd dash: start_from/start_to/end_from/end_to at 5+d, 6+d, 9+d, 10+d
+        "end-ramp": [6.5 + d, 3.5],                   # end_from / end_to at 6+d / 7+d, total 10+d (the wrap drifts by d)
+        "wrap": [4.0, 6.0 + d],                       # phases 10k land on 0 / total, k d beside them
+        "sub-pixel": [0.5 + d, 1.5],                  # opacity_mul 0.5, ramps below 0, overlapping halves
+        "odd": [3.0, 1.5 + d, 2.0],                   # the chained dash 0 starts at 6.5+d and runs past total
+        "zero-dash": [0.0, 5.0 + d],                  # a dash of length 0
+        "single": [10.0 + d],                         # one entry: dash and chained dash share the wrap
+    }
+
+
+def _dash_parity(gpu_ctx, oracle, tiles, names, msg, chunk=48):
+    """RGBA8 and the f64 canvas bit for bit on EVERY tile; reports every tile that differs."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    bad = []
+    for c0 in range(0, len(tiles), chunk):
+        dl = display_list.concat(tiles[c0:c0 + chunk])
+        scene = gpu_ctx.upload(dl)
+        got = gpu_ctx.render(scene).cpu().numpy()
+        f64 = gpu_ctx.render_f64(scene).cpu().numpy()
+        scene.free()
+        with ThreadPoolExecutor(16) as ex:
+            refs = list(ex.map(lambda j: oracle.render_job(dl, j, want_f64=True), range(dl.n_jobs)))
+        for j, (rgba, ref) in enumerate(refs):
+            n8 = int((got[j] != rgba).any(axis=-1).sum())
+            n64 = int((f64[j].view(np.uint64) != ref.view(np.uint64)).any(axis=-1).sum())
+            if n8 or n64:
+                bad.append(f"{names[c0 + j]}: {n8} RGBA8 / {n64} f64 pixels")
+    assert not bad, f"{msg}: {len(bad)} of {len(tiles)} tiles differ: " + "; ".join(bad[:12])
+
+
+def _ramp_tile(scale, dashes, cap, ucd):
+    W = 256 * scale
+    tb = TileBuilder(scale=scale, canvas=None)
+    k = (W + 80) // 4
+    ops = [
+        ([(-40, 20), (W + 40, 20)], 2.0),                                          # along +x, phase = x + 40
+        ([(W + 40, 60), (-40, 60)], 4.0),                                          # along -x
+        ([(100, -40), (100, W + 40)], 1.0),                                        # along +y
+        ([(-30, -40), (-30 + 3 * k, -40 + 4 * k)], 2.0),                           # (3, 4) k: lattice pixels at phase 5 m
+        ([(W + 40, 30), (W + 40 - 4 * k, 30 + 3 * k)], 6.0),                       # (-4, 3) k
+        ([(-40, 7 * W // 10), (6 * W // 10, 7 * W // 10), (6 * W // 10, 45 * W // 100),
+          (6 * W // 10 - 60, 45 * W // 100 - 80), (W + 40, 45 * W // 100 - 80)], 2.0),  # corners inside the tile: dotv changes sign
+    ]
+    for pts, w in ops:
+        tb.stroke(pts, w, (255, 255, 255), 1.0, dashes=dashes, cap=cap, use_caps_for_dashes=ucd)
+    return tb.build()
+
+
+@pytest.mark.parametrize("scale", [1, 2])
+def test_dash_phase_ramp_edges(gpu_ctx, oracle, scale):
+    tiles, names = [], []
+    for d in DASH_DELTAS:
+        for pname, dashes in _dash_patterns(d).items():
+            for cap, ucd in DASH_CAPS:
+                tiles.append(_ramp_tile(scale, dashes, cap, ucd))
+                names.append(f"{pname} d={d!r} cap={cap} ucd={ucd}")
+    _dash_parity(gpu_ctx, oracle, tiles, names, f"ramp edges scale {scale}")
+
+
+@pytest.mark.parametrize("scale", [1, 2])
+def test_dash_phase_large_traveled(gpu_ctx, oracle, scale):
+    """The first edge lies off the tile and is 1e4 / 1e6 / 1e7 px long (an exact integer: axis-aligned or (3, 4, 5) k), so
+    the phases on the tile are integers near `traveled`, where the 2^-40 term of mu and the quotient of the `%` grow."""
+    W = 256 * scale
+    tiles, names = [], []
+    for L in (10_000, 1_000_000, 10_000_000):
+        k = L // 5
+        deltas = DASH_DELTAS if L < 10_000_000 else [0.0, 2.0**-50, -(2.0**-7), 2.0**-6]
+        caps = DASH_CAPS if L < 10_000_000 else [(abi.CAP_NONE, False), (abi.CAP_SQUARE, True)]
+        for d in deltas:
+            for pname, dashes in (("four-boundaries", [3.0, 2.5 + d, 4.0, 4.5 - d]), ("end-ramp", [6.5 + d, 3.5 - d])):
+                for cap, ucd in caps:
+                    tb = TileBuilder(scale=scale, canvas=None)
+                    if L < 10_000_000:
+                        tb.stroke([(-40 - L, 20), (-40, 20), (W + 40, 20)], 1.0, (255, 255, 255), 1.0, dashes=dashes, cap=cap,
+                                  use_caps_for_dashes=ucd)
+                        tb.stroke([(100, W + 40 + L), (100, W + 40), (100, -40)], 2.0, (255, 255, 255), 1.0, dashes=dashes, cap=cap,
+                                  use_caps_for_dashes=ucd)
+                    p1 = (-30, -40)
+                    tb.stroke([(p1[0] - 3 * k, p1[1] - 4 * k), p1, (p1[0] + 3 * (W // 4), p1[1] + 4 * (W // 4))], 2.0, (255, 255, 255), 1.0,
+                              dashes=dashes, cap=cap, use_caps_for_dashes=ucd)
+                    tiles.append(tb.build())
+                    names.append(f"L={L} {pname} d={d!r} cap={cap} ucd={ucd}")
+    _dash_parity(gpu_ctx, oracle, tiles, names, f"large traveled scale {scale}")
+
+
+def _model_parity(gpu_ctx, oracle, cases, scale, msg):
+    """cases: (name, points, width, dashes, cap, ucd); the expected tile comes from tests/_dash_pixel_model.py"""
+    from tests import _dash_pixel_model as model
+
+    tiles = []
+    for _, pts, w, dashes, cap, ucd in cases:
+        tb = TileBuilder(scale=scale, canvas=None)
+        tb.stroke(pts, w, (255, 255, 255), 1.0, dashes=dashes, cap=cap, use_caps_for_dashes=ucd)
+        tiles.append(tb.build())
+    bad = []
+    for c0 in range(0, len(tiles), 16):
+        dl = display_list.concat(tiles[c0:c0 + 16])
+        scene = gpu_ctx.upload(dl)
+        got = gpu_ctx.render(scene).cpu().numpy()
+        f64 = gpu_ctx.render_f64(scene).cpu().numpy()
+        scene.free()
+        for j in range(dl.n_jobs):
+            name, pts, w, dashes, cap, ucd = cases[c0 + j]
+            alpha = model.alpha_plane(pts, w, dashes, cap, ucd, 1.0, scale, oracle)
+            rgba, ref = model.expected_canvas(alpha, scale, oracle)
+            if dashes is None:
+                assert (alpha > 0).sum() > 100, f"{name}: the edge misses the tile"
+            n8 = int((got[j] != rgba).any(axis=-1).sum())
+            n64 = int((f64[j].view(np.uint64) != ref.view(np.uint64)).any(axis=-1).sum())
+            if n8 or n64:
+                bad.append(f"{name}: {n8} RGBA8 / {n64} f64 pixels")
+    assert not bad, f"{msg}: {len(bad)} of {len(tiles)} tiles differ: " + "; ".join(bad[:12])
+
+
+@pytest.mark.parametrize("scale", [1, 2])
+def test_dash_phase_extreme_coordinates(gpu_ctx, oracle, scale):
+    """Endpoints at |coordinate| = 2^28, widths up to 65536 (the whole tile in the band), shallow and steep slopes,
+    `traveled` up to 2^30 from far first edges whose bands miss the tile; edges just below 2^26 px (the longest that keep
+    the approximate phase) beside edges of 2^29 px (routed to the exact calculator).  The oracle would walk 2^29 px per
+    edge: the reference is tests/_dash_pixel_model.py, whose visiting condition the undashed renders check first."""
+    W = 256 * scale
+    M = 2**28
+    h = 2**25 - 8  # an edge of just under 2^26 px
+    geoms = [
+        ("shallow-2^28", [(-M, 100), (M, 100 + 40)]),
+        ("steep-2^28", [(120, M), (90, -M)]),
+        ("axis-2^28", [(M, W // 3), (-M, W // 3)]),
+        ("diag-2^28", [(-M, -M + 7), (M, M - 13)]),
+        ("traveled-2^30", [(-M, M), (M, M), (M, -M + W), (-M + W, M)]),
+        ("shallow-2^26", [(W // 2 - h, 90), (W // 2 + h, 90 + 37)]),
+        ("steep-2^26", [(70, W // 2 + h), (70 + 53, W // 2 - h)]),
+    ]
+    widths = [3.0, 301.0, 65536.0] if scale == 1 else [5.0, 65536.0]
+    plain = [(f"{g} w={w} undashed", pts, w, None, abi.CAP_BUTT, False) for g, pts in geoms for w in widths]
+    _model_parity(gpu_ctx, oracle, plain, scale, "undashed (visiting condition)")
+    cases = []
+    for i, (g, pts) in enumerate(geoms):
+        for j, w in enumerate(widths):
+            d = DASH_DELTAS[(3 * i + j) % len(DASH_DELTAS)]
+            pats = _dash_patterns(d)
+            pname = list(pats)[(i + 2 * j) % len(pats)]
+            cap, ucd = DASH_CAPS[(i + j) % (len(DASH_CAPS) - 1)]  # no Round dash caps: the model needs cap_dist == 0
+            cases.append((f"{g} w={w} {pname} d={d!r} cap={cap} ucd={ucd}", pts, w, pats[pname], cap, ucd))
+    _model_parity(gpu_ctx, oracle, cases, scale, "dashed")
+
+
+EXTREME_DASH_LISTS = {
+    "tiny-1.65e-11": [1.65e-11, 1.65e-11],
+    "tiny-1e-12": [1e-12, 1e-12],
+    "tiny-2^-40": [2.0**-40],
+    "huge-1e15": [1e15, 5.0],
+    "huge-1e300": [1e300],
+    "overflow-1e308x2": [1e308, 1e308],
+    "inf": [float("inf")],
+    "inf-1": [float("inf"), 1.0],
+    "nan": [float("nan")],
+    "nan-second": [5.0, float("nan")],
+    "negative-first": [-3.0, 5.0],
+    "negative-second": [5.0, -3.0],
+    "zero": [0.0],
+    "zeros": [0.0, 0.0],
+    "denormal-total": [5e-324, 5e-324],
+    "denormal-gap": [3.0, 1e-310],
+}
+
+
+def test_dash_phase_extreme_dash_lists(gpu_ctx, oracle):
+    """Dash values validation admits (it checks the count, not the values): totals whose quotient passes 2^52, totals that
+    overflow to +inf (fmod(x, inf) == x), NaN, negative, zero and denormal entries; `traveled` 0 and ~4e5 (past 2^52 times every tiny total)."""
+    W = 256
+    caps = [(c, u) for c in CAPS for u in (False, True)]
+    tiles, names = [], []
+    for lname, dashes in EXTREME_DASH_LISTS.items():
+        for cap, ucd in caps:
+            tb = TileBuilder(canvas=None)
+            tb.stroke([(-40, 30), (200, 30), (120, 110), (W + 40, 115)], 3.0, (255, 255, 255), 1.0, dashes=dashes, cap=cap,
+                      use_caps_for_dashes=ucd)
+            tb.stroke([(-400_040, 150), (-40, 150), (W + 40, 190), (60, W + 40)], 1.0, (255, 255, 255), 1.0, dashes=dashes,
+                      cap=cap, use_caps_for_dashes=ucd)
+            tiles.append(tb.build())
+            names.append(f"{lname} cap={cap} ucd={ucd}")
+    _dash_parity(gpu_ctx, oracle, tiles, names, "extreme dash lists")

@@ -42,6 +42,12 @@ def rand_pts(n, W, spread):
 BATCH_SIZES = (1, 12, 64, 65, 130)
 
 
+# dash lists past the usual: quotients of the `%` beyond 2^52, totals that overflow to +inf, NaN, negative, zero and
+# denormal entries (tests/test_gpu_parity_ops.py::test_dash_phase_extreme_dash_lists pins each of them)
+EXTREME_DASHES = ([1.65e-11, 1.65e-11], [1e-12, 1e-12], [2.0**-40], [1e15, 5.0], [1e300], [1e308, 1e308], [float("inf")],
+                  [float("inf"), 1.0], [float("nan")], [-3.0, 5.0], [5.0, -3.0], [0.0], [0.0, 0.0], [5e-324, 5e-324])
+
+
 def rand_op_count():
     u = rnd.random()
     if u < 0.10:
@@ -76,6 +82,8 @@ def make_tile(scale, image_ids=(), n_ops=None):
             if rnd.random() < 0.5:
                 nd = int(rnd.integers(1, 7))
                 d = [float(rnd.choice([0.3, 1.0, 2.0, 3.0, 5.5, 8.0, 13.0, 40.0])) * scale for _ in range(nd)]
+            elif rnd.random() < 0.04:  # rare: values validation admits but no stylesheet has (the exact `%` and its edges)
+                d = list(EXTREME_DASHES[int(rnd.integers(0, len(EXTREME_DASHES)))])
             w = float(rnd.choice([0.0, 0.05, 0.2, 0.5, 0.99, 1.0, 1.01, 1.5, 2.0, 2.5, 3.0, 4.0, 7.0, 12.5, 25.0, 40.0, -3.0, 1.3, 2e-101, 0.7])) * scale
             tb.stroke(rand_pts(int(rnd.integers(2, 9)), W, int(rnd.choice([3, 30, 90, 300]))), w, col, op, dashes=d,
                       cap=CAPS[int(rnd.integers(0, 4))], use_caps_for_dashes=bool(rnd.integers(0, 2)))
