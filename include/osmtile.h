@@ -329,6 +329,64 @@ int osmt_scene_read_label_segs(osmt_ctx* ctx, osmt_scene* scene, double* out, si
 /* Diagnostics: out[i] = the device hypot of (xy[2i], xy[2i + 1]) — the function the glyph walk flattens curves with. */
 int osmt_debug_hypot(osmt_ctx* ctx, const double* xy, size_t n, double* out);
 
+/* ---- label anchors: where a polygon's label goes (src/draw/labelable.rs:191-204) ------------------------------ */
+/* Labelable::get_label_position of a Way or Multipolygon — the start of every icon (labeler.rs:56) and every centred
+ * text (text_placer.rs:113) — for a whole batch of polygons per call: the largest ring is chosen, rings not inside it
+ * are dropped (filter_polygons, :206-232) and the "polylabel" search (:125-189) runs on the device, one wave per request,
+ * step for step as the reference runs it (pop order with std's BinaryHeap tie order, stop rule, first cell of the best
+ * fitness).  x and y have the bits the reference returns.
+ *
+ * A request is n_rings consecutive osmt_ring entries (a way: one ring; a multipolygon: polygon_count() rings in file
+ * order) over one pool of double[n_pts][2].  Points are what nodes_to_points produces (:61-68):
+ * coords_to_xy_tile_relative(node, tile) * scale, UNROUNDED f64.  The host projects: the device projection's tan / log are
+ * only exact behind Point::from_node's rounding to i32, and a last-bit difference here can flip a branch of the search —
+ * there is no (lat, lon) input form.  Points must be finite with |v| <= 2^28. */
+typedef struct osmt_label_request {
+    uint32_t ring_off; /* first entry in osmt_label_request_batch.rings */
+    uint32_t n_rings;
+    double scale;      /* the `scale` get_label_position receives: precision = max(w, h) / 100.0 * scale */
+} osmt_label_request;
+
+typedef struct osmt_label_request_batch {
+    const osmt_label_request* requests;
+    size_t n_requests;
+    const osmt_ring* rings; /* first_pt / n_pts index `points` */
+    size_t n_rings;
+    const double* points;   /* [n_pts][2] = (x, y) */
+    size_t n_pts;
+} osmt_label_request_batch;
+
+#define OSMT_LABEL_OK 0u        /* (x, y) is the label position */
+#define OSMT_LABEL_NONE 1u      /* the reference returns None: no rings, or the first ring AS GIVEN is empty (labelable.rs:194) */
+#define OSMT_LABEL_TOO_LARGE 2u /* the reference's run would hold more than OSMT_LABEL_MAX_CELLS cells in its queue at once, or
+                                 * pop more than OSMT_LABEL_MAX_CELLS cells: not computed (x = y = 0).  Exactly then and only
+                                 * then; osmt::LabelPositions (host/osmt_labelable.hpp) computes such a request on the host. */
+#define OSMT_LABEL_MAX_CELLS 65536u
+
+/* 24 bytes per request.  Never a wrong or truncated position: status says what x and y are. */
+typedef struct osmt_label_position {
+    double x, y;
+    uint32_t status; /* OSMT_LABEL_* */
+    uint32_t _pad;
+} osmt_label_position;
+
+/* Validates on the host (nothing is uploaded before it passes, `out` is not touched when it fails), uploads, runs the
+ * kernels, reads `out` back: n_requests records.  OSMT_INVALID_ARG: NULL pointers, ring or point ranges outside the
+ * tables, a scale that is not finite; OSMT_UNSUPPORTED: a coordinate that is not finite or has |v| > 2^28.  Zero
+ * requests: OSMT_OK, no device is touched. */
+int osmt_label_positions(osmt_ctx* ctx, const osmt_label_request_batch* batch, osmt_label_position* out);
+/* The same call in two halves, as osmt_render_batch_png_begin / _end: _begin validates, uploads and queues the kernels
+ * and the read-back and returns without waiting; _end waits, copies the records into `out` and frees the job whatever it
+ * returns.  The arrays of `batch` must stay valid until _end returns.  A server thread begins the anchors of batch k + 1
+ * while the GPU renders batch k. */
+typedef struct osmt_label_job osmt_label_job;
+int osmt_label_positions_begin(osmt_ctx* ctx, const osmt_label_request_batch* batch, osmt_label_job** out_job);
+int osmt_label_positions_end(osmt_label_job* job, osmt_label_position* out);
+/* Inspection (tests, tools): what the last completed osmt_label_positions / _end on this context did — stats[0] = its
+ * requests, stats[1] = those whose queue outgrew the LDS tier and were run again with a queue in device memory,
+ * stats[2] = those answered OSMT_LABEL_TOO_LARGE. */
+int osmt_label_positions_stats(osmt_ctx* ctx, uint64_t stats[3]);
+
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */
 int osmt_project(osmt_ctx* ctx, const double* latlon, size_t n, uint8_t zoom, uint32_t tile_x, uint32_t tile_y,

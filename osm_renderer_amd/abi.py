@@ -20,6 +20,8 @@ COORD_LATLON_F64, COORD_POINT_I32, COORD_NODE_REF = 0, 1, 2
 STAGE_PROJECT, STAGE_OPINFO, STAGE_RASTER = 1, 2, 4
 
 GLYPH_MOVE_TO, GLYPH_LINE_TO, GLYPH_CURVE_TO = 1, 2, 3  # osmt_glyph_vertex.type (stb_truetype's Vertex)
+LABEL_OK, LABEL_NONE, LABEL_TOO_LARGE = 0, 1, 2  # osmt_label_position.status
+LABEL_MAX_CELLS = 65536
 GLYPH_CENTER, GLYPH_LINE = 0, 1  # osmt_glyph_instance.form: TextPlacer::place's two `tr` closures
 
 
@@ -137,6 +139,25 @@ class GlyphLabelBatch(C.Structure):
     ]
 
 
+class LabelRequest(C.Structure):
+    _fields_ = [("ring_off", C.c_uint32), ("n_rings", C.c_uint32), ("scale", C.c_double)]
+
+
+class LabelRequestBatch(C.Structure):
+    _fields_ = [
+        ("requests", C.POINTER(LabelRequest)),
+        ("n_requests", C.c_size_t),
+        ("rings", C.POINTER(Ring)),
+        ("n_rings", C.c_size_t),
+        ("points", C.POINTER(C.c_double)),
+        ("n_pts", C.c_size_t),
+    ]
+
+
+class LabelPosition(C.Structure):
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("status", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32)]
 
@@ -147,3 +168,5 @@ assert C.sizeof(TileJob) == 32
 assert C.sizeof(Label) == 40
 assert C.sizeof(GlyphVertex) == 10
 assert C.sizeof(GlyphInstance) == 64
+assert C.sizeof(LabelRequest) == 16
+assert C.sizeof(LabelPosition) == 24

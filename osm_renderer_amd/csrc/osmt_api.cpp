@@ -133,6 +133,8 @@ struct osmt_ctx {
     std::condition_variable co_cv;
     std::deque<struct coalesce_req*> co_queue;
     int co_in_flight = 0;
+    /* osmt_label_positions_stats: requests / left the LDS tier / answered TOO_LARGE of the last completed call (cache_mu) */
+    uint64_t pl_stats[3] = {0, 0, 0};
 };
 
 struct osmt_scene {
@@ -1830,6 +1832,161 @@ static int osmt_debug_hypot_body(osmt_ctx* ctx, const double* xy, size_t n, doub
 
 int osmt_debug_hypot(osmt_ctx* ctx, const double* xy, size_t n, double* out) {
     return guarded([&] { return osmt_debug_hypot_body(ctx, xy, n, out); });
+}
+
+/* ---- label anchors (osmt_label_positions) ---------------------------------------------------------------------- */
+struct osmt_label_job {
+    osmt_ctx* ctx = nullptr;
+    hipStream_t st = nullptr;
+    char* d_base = nullptr;
+    char* stage = nullptr; /* pinned: the request records going up, then the positions and the counters coming back */
+    size_t n = 0, back_off = 0;
+};
+
+static void label_job_free(osmt_label_job* j) {
+    if (!j) return;
+    if (j->ctx) {
+        if (j->d_base) dev_free(j->ctx, j->d_base);
+        if (j->stage) stage_release(j->ctx, j->stage);
+        if (j->st) stream_release(j->ctx, j->st);
+    }
+    delete j;
+}
+
+static int label_positions_validate(const osmt_label_request_batch* b, size_t* keep_words) {
+    if (b->n_requests >= 0xFFFFFFFFull || b->n_rings >= 0xFFFFFFFFull || b->n_pts >= 0xFFFFFFFFull)
+        return fail(OSMT_INVALID_ARG, "label request batch too large for 32-bit indices");
+    if (!b->requests || (b->n_rings && !b->rings) || (b->n_pts && !b->points)) return fail(OSMT_INVALID_ARG, "NULL pool with non-zero count");
+    size_t words = 0;
+    for (size_t i = 0; i < b->n_requests; ++i) {
+        const osmt_label_request& rq = b->requests[i];
+        if ((size_t)rq.ring_off + rq.n_rings > b->n_rings) return fail(OSMT_INVALID_ARG, "label request %zu: ring range out of bounds", i);
+        if (!std::isfinite(rq.scale)) return fail(OSMT_INVALID_ARG, "label request %zu: scale not finite", i);
+        for (uint32_t k = 0; k < rq.n_rings; ++k) {
+            const osmt_ring& r = b->rings[rq.ring_off + k];
+            if ((size_t)r.first_pt + r.n_pts > b->n_pts) return fail(OSMT_INVALID_ARG, "label request %zu ring %u: point range out of bounds", i, k);
+        }
+        words += rq.n_rings;
+    }
+    if (words >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "label request batch too large for 32-bit indices");
+    /* the whole pool is uploaded, so the whole pool is checked: under 2^28 no intermediate of the search overflows */
+    const double LIM = 268435456.0;
+    for (size_t i = 0; i < 2 * b->n_pts; ++i)
+        if (!(std::fabs(b->points[i]) <= LIM)) return fail(OSMT_UNSUPPORTED, "label point %zu: coordinate not finite or |v| > 2^28", i / 2);
+    *keep_words = words;
+    return OSMT_OK;
+}
+
+static int osmt_label_positions_begin_body(osmt_ctx* ctx, const osmt_label_request_batch* b, osmt_label_job** out_job) {
+    if (!ctx || !b || !out_job) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *out_job = nullptr;
+    osmt_label_job* j = new osmt_label_job();
+    j->ctx = ctx;
+    j->n = b->n_requests;
+    if (!j->n) { /* no device is touched */
+        *out_job = j;
+        return OSMT_OK;
+    }
+    struct guard {
+        osmt_label_job* j;
+        ~guard() { label_job_free(j); }
+    } gd{j};
+    size_t keep_words = 0;
+    const int rc = label_positions_validate(b, &keep_words);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(stream_acquire(ctx, &j->st));
+    const size_t n = j->n;
+    const uint32_t n_slots = (uint32_t)std::min<size_t>(n, OSMT_PL_MAX_SLOTS);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    const size_t o_req = take(n * sizeof(osmt_pl_req)), o_rings = take(b->n_rings * sizeof(osmt_ring)), o_pts = take(b->n_pts * 16),
+                 o_keep = take(keep_words * 4), o_over = take(n * 4), o_back = take(n * sizeof(osmt_label_position) + 16),
+                 o_ws = take((size_t)n_slots * OSMT_PL_CELL_DOUBLES * OSMT_PL_GLOBAL_CELLS * sizeof(double));
+    const size_t back_bytes = n * sizeof(osmt_label_position) + 16;
+    j->back_off = align_up(n * sizeof(osmt_pl_req), 64);
+    j->stage = (char*)stage_acquire(ctx, j->back_off + back_bytes);
+    if (!j->stage) return fail(OSMT_OOM, "pinned staging for %zu label requests could not be allocated", n);
+    osmt_pl_req* rq = (osmt_pl_req*)j->stage;
+    uint32_t words = 0;
+    for (size_t i = 0; i < n; ++i) {
+        rq[i] = {b->requests[i].ring_off, b->requests[i].n_rings, words, 0u, b->requests[i].scale};
+        words += b->requests[i].n_rings;
+    }
+    HIP_TRY(dev_alloc(ctx, (void**)&j->d_base, off));
+    char* d = j->d_base;
+    HIP_TRY(hipMemcpyAsync(d + o_req, rq, n * sizeof(osmt_pl_req), hipMemcpyHostToDevice, j->st));
+    if (b->n_rings) HIP_TRY(hipMemcpyAsync(d + o_rings, b->rings, b->n_rings * sizeof(osmt_ring), hipMemcpyHostToDevice, j->st));
+    if (b->n_pts) HIP_TRY(hipMemcpyAsync(d + o_pts, b->points, b->n_pts * 16, hipMemcpyHostToDevice, j->st));
+    osmt_polylabel_args a{};
+    a.req = (const osmt_pl_req*)(d + o_req);
+    a.n_req = (uint32_t)n;
+    a.rings = (const osmt_ring*)(d + o_rings);
+    a.n_rings = (uint32_t)b->n_rings;
+    a.pts = (const double2*)(d + o_pts);
+    a.keep = (uint32_t*)(d + o_keep);
+    a.over = (uint32_t*)(d + o_over);
+    a.out = (osmt_label_position*)(d + o_back);
+    a.cnt = (uint32_t*)(d + o_back + n * sizeof(osmt_label_position));
+    a.ws = (double*)(d + o_ws);
+    a.n_slots = n_slots;
+    HIP_TRY(osmt_launch_polylabel(a, j->st));
+    HIP_TRY(hipMemcpyAsync(j->stage + j->back_off, d + o_back, back_bytes, hipMemcpyDeviceToHost, j->st));
+    gd.j = nullptr;
+    *out_job = j;
+    return OSMT_OK;
+}
+
+static int osmt_label_positions_end_body(osmt_label_job* j, osmt_label_position* out) {
+    if (!j) return fail(OSMT_INVALID_ARG, "NULL job");
+    struct guard {
+        osmt_label_job* j;
+        ~guard() { label_job_free(j); }
+    } gd{j};
+    if (!j->n) return OSMT_OK;
+    HIP_TRY(hipSetDevice(j->ctx->device));
+    HIP_TRY(hipStreamSynchronize(j->st));
+    if (!out) return fail(OSMT_INVALID_ARG, "out is NULL");
+    const char* back = j->stage + j->back_off;
+    uint32_t cnt[4];
+    memcpy(cnt, back + j->n * sizeof(osmt_label_position), sizeof cnt);
+    if (cnt[3]) return fail(OSMT_HIP_ERROR, "label positions: internal error %u (a bounded loop of the kernel passed its bound)", cnt[3]);
+    memcpy(out, back, j->n * sizeof(osmt_label_position));
+    std::lock_guard<std::mutex> lk(j->ctx->cache_mu);
+    j->ctx->pl_stats[0] = j->n;
+    j->ctx->pl_stats[1] = cnt[0];
+    j->ctx->pl_stats[2] = cnt[2];
+    return OSMT_OK;
+}
+
+int osmt_label_positions_begin(osmt_ctx* ctx, const osmt_label_request_batch* b, osmt_label_job** out_job) {
+    return guarded([&] { return osmt_label_positions_begin_body(ctx, b, out_job); });
+}
+
+int osmt_label_positions_end(osmt_label_job* j, osmt_label_position* out) {
+    return guarded([&] { return osmt_label_positions_end_body(j, out); });
+}
+
+int osmt_label_positions(osmt_ctx* ctx, const osmt_label_request_batch* b, osmt_label_position* out) {
+    return guarded([&] {
+        if (b && b->n_requests && !out) return fail(OSMT_INVALID_ARG, "out is NULL");
+        osmt_label_job* j = nullptr;
+        const int rc = osmt_label_positions_begin_body(ctx, b, &j);
+        return rc != OSMT_OK ? rc : osmt_label_positions_end_body(j, out);
+    });
+}
+
+int osmt_label_positions_stats(osmt_ctx* ctx, uint64_t stats[3]) {
+    return guarded([&] {
+        if (!ctx || !stats) return fail(OSMT_INVALID_ARG, "NULL argument");
+        std::lock_guard<std::mutex> lk(ctx->cache_mu);
+        for (int i = 0; i < 3; ++i) stats[i] = ctx->pl_stats[i];
+        return (int)OSMT_OK;
+    });
 }
 
 static int osmt_scene_read_label_status_body(osmt_ctx* ctx, osmt_scene* sc, uint8_t* ok) {

@@ -329,6 +329,42 @@ struct osmt_prepass_args {
 #define OSMT_PREPASS_ERR_STROKE_ARENA 2u
 #define OSMT_PREPASS_ERR_LIST_ARENA 4u
 
+/* ---- label anchors (osmt_polylabel.hip) ----------------------------------------------------------------------- */
+/* one request as the kernels read it */
+struct osmt_pl_req {
+    uint32_t ring_off, n_rings;
+    uint32_t keep_off; /* first word of the request's slice of `keep` (n_rings words: the rings filter_polygons keeps, the largest first) */
+    uint32_t _pad;
+    double scale;
+};
+static_assert(sizeof(osmt_pl_req) == 24, "osmt_pl_req");
+
+#define OSMT_PL_GLOBAL_CELLS OSMT_LABEL_MAX_CELLS /* queue capacity of the second tier = the cap of the contract */
+#define OSMT_PL_CELL_DOUBLES 5u                   /* centre x, y, half size, fitness, max fitness */
+#define OSMT_PL_ERR_HEAP 1u   /* a sift walked more levels than a heap of 2^32 cells has */
+#define OSMT_PL_ERR_KEEP 2u   /* the kept-ring list names a ring outside the table */
+#define OSMT_PL_ERR_GRID 4u   /* the grid walk outran the queue cap without a push failing */
+#define OSMT_PL_ERR_LIST 8u   /* the second tier took more rounds than there are requests */
+#define OSMT_PL_ERR_TIER1 16u /* (where: first / second tier) */
+#define OSMT_PL_ERR_TIER2 32u
+#define OSMT_PL_MAX_SLOTS 64u                     /* second-tier queues (2.6 MB each) a call allocates at most */
+
+struct osmt_polylabel_args {
+    const osmt_pl_req* req;
+    uint32_t n_req;
+    const osmt_ring* rings;
+    uint32_t n_rings;
+    const double2* pts;
+    uint32_t* keep;           /* [sum of n_rings] */
+    osmt_label_position* out; /* [n_req] */
+    uint32_t* over;           /* [n_req] requests whose queue outgrew the LDS tier, in no particular order */
+    uint32_t* cnt;            /* [0] entries of `over`, [1] the second tier's cursor into it, [2] requests answered TOO_LARGE, [3] OSMT_PL_ERR_*; zeroed by the launcher */
+    double* ws;               /* [n_slots][OSMT_PL_CELL_DOUBLES][OSMT_PL_GLOBAL_CELLS] */
+    uint32_t n_slots;
+};
+/* zeroes cnt, then k_polylabel (one wave per request, queue in LDS) and k_polylabel_big (n_slots waves work through `over`) */
+hipError_t osmt_launch_polylabel(const osmt_polylabel_args& a, hipStream_t st);
+
 /* zero / n_zero (optional): 32-bit words the kernel clears on the way — the cursors and list counts of the pre-pass that follows */
 hipError_t osmt_launch_project(const osmt_tile_job* jobs, const uint32_t* pt_job, const double* latlon, const uint32_t* refs,
                                uint32_t n_pts, double scale, int32_t* pts, hipStream_t st, uint32_t* zero = nullptr, size_t n_zero = 0);

@@ -33,6 +33,12 @@ LABEL_DTYPE = np.dtype(
 )
 assert LABEL_DTYPE.itemsize == 40
 
+# osmt_label_request / osmt_label_position (label anchors, Context.label_positions)
+LABEL_REQUEST_DTYPE = np.dtype([("ring_off", "<u4"), ("n_rings", "<u4"), ("scale", "<f8")])
+LABEL_POSITION_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("status", "<u4"), ("_pad", "<u4")])
+assert LABEL_REQUEST_DTYPE.itemsize == C.sizeof(abi.LabelRequest) == 16
+assert LABEL_POSITION_DTYPE.itemsize == C.sizeof(abi.LabelPosition) == 24
+
 _libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
 _libm.hypot.restype = C.c_double
 _libm.hypot.argtypes = [C.c_double, C.c_double]

@@ -213,6 +213,53 @@ class Context:
         check(load().osmt_debug_hypot(self._h, xy.ctypes.data_as(dp), len(xy), out.ctypes.data_as(dp)))
         return out
 
+    # -- label anchors --------------------------------------------------------------
+    def _label_request_batch(self, rings, points, requests):
+        from . import labels
+
+        rings = np.ascontiguousarray(rings, dtype=np.uint32).reshape(-1, 2)  # osmt_ring: (first_pt, n_pts)
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        requests = np.ascontiguousarray(requests, dtype=labels.LABEL_REQUEST_DTYPE)
+        b = abi.LabelRequestBatch(
+            requests=requests.ctypes.data_as(C.POINTER(abi.LabelRequest)), n_requests=len(requests),
+            rings=rings.ctypes.data_as(C.POINTER(abi.Ring)), n_rings=len(rings),
+            points=points.ctypes.data_as(C.POINTER(C.c_double)), n_pts=len(points))
+        return b, (rings, points, requests)
+
+    def label_positions(self, rings, points, requests, out=None):
+        """osmt_label_positions: get_label_position (src/draw/labelable.rs:191-204) of every request on the GPU.
+        rings: [n, 2] uint32 (first_pt, n_pts); points: [m, 2] float64, projected and scaled by the caller; requests:
+        labels.LABEL_REQUEST_DTYPE.  Returns a labels.LABEL_POSITION_DTYPE array (status: abi.LABEL_*)."""
+        from . import labels
+
+        b, keep = self._label_request_batch(rings, points, requests)
+        if out is None:
+            out = np.zeros(len(keep[2]), labels.LABEL_POSITION_DTYPE)
+        assert out.dtype == labels.LABEL_POSITION_DTYPE and len(out) == len(keep[2]) and out.flags.c_contiguous
+        check(load().osmt_label_positions(self._h, C.byref(b), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def label_positions_begin(self, rings, points, requests):
+        """osmt_label_positions_begin: validates, uploads and queues the kernels; returns a job for label_positions_end."""
+        b, keep = self._label_request_batch(rings, points, requests)
+        job = C.c_void_p()
+        check(load().osmt_label_positions_begin(self._h, C.byref(b), C.byref(job)))
+        return job, keep
+
+    def label_positions_end(self, job):
+        from . import labels
+
+        h, keep = job
+        out = np.zeros(len(keep[2]), labels.LABEL_POSITION_DTYPE)
+        check(load().osmt_label_positions_end(h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def label_positions_stats(self):
+        """(requests, requests that left the LDS tier, requests answered TOO_LARGE) of the last completed call."""
+        st = (C.c_uint64 * 3)()
+        check(load().osmt_label_positions_stats(self._h, st))
+        return int(st[0]), int(st[1]), int(st[2])
+
     # -- whole path --------------------------------------------------------------
     def upload(self, dl: DisplayList, labels=None) -> Scene:
         return Scene(self, dl, labels)
