@@ -208,6 +208,60 @@ typedef struct osmt_glyph_label_batch {
     size_t n_glyphs;
 } osmt_glyph_label_batch;
 
+/* ---- label text as text runs ---------------------------------------------------- */
+/* The third, optional form of label text: the caller says WHAT the text is (glyph ids and the font's metrics) and WHERE
+ * it goes (an anchor, or the way's points); the GPU runs TextPlacer::place (font/text_placer.rs:24-168) — the width
+ * sums, the row breaking of centred text, the walk along a way — and feeds the glyph instances it produces, without
+ * leaving the device, to the expansion of osmt_scene_set_glyph_labels.  What stays with the caller is the font lookup
+ * (cmap, hmtx, kern) and libm: atan2 and sin_cos are not reproducible bit for bit on the device, so the caller hands in
+ * (-get_angle(points, e)).sin_cos() per edge, as OSMT_GLYPH_LINE already requires per glyph.  16 bytes per glyph + 64 per
+ * label + 24 per way point instead of 64 bytes per glyph. */
+
+/* one char of text_to_glyphs (text_placer.rs:170-197); 16 bytes */
+typedef struct osmt_text_glyph {
+    uint32_t glyph_id; /* id from osmt_register_glyphs */
+    int32_t advance;   /* get_glyph_h_metrics(g).advance_width, font units */
+    int32_t kern;      /* get_glyph_kern_advance(prev, g); ignored for the first glyph of a text */
+    uint32_t flags;    /* bit 0: ch.is_whitespace() */
+} osmt_text_glyph;
+
+#define OSMT_TEXT_CENTER 0u /* TextPosition::Center: rows around (center_x, center_y)  (text_placer.rs:112-163) */
+#define OSMT_TEXT_LINE 1u   /* TextPosition::Line: along way_pts[pt_off .. pt_off + n_pts)  (text_placer.rs:60-111) */
+
+/* One TextPlacer::place call; 64 bytes, one per label, read only when the label has_text.
+ * LINE: way_pts holds get_waypoints ALREADY in walking order — the caller applies the reversal of text_placer.rs:65-67
+ * (points[0].x > last.x) before it fills way_pts and way_sincos, because the angles depend on it.  A LINE run with
+ * n_pts < 2 and a text wider than its way are legal and place nothing (place() returns early). */
+typedef struct osmt_text_run {
+    uint32_t position; /* OSMT_TEXT_CENTER / OSMT_TEXT_LINE */
+    uint32_t y_offset; /* CENTER: what label_with_icon returned (icon.height / 2, or 0) */
+    uint32_t pt_off, n_pts; /* LINE: range in way_pts / way_sincos */
+    double scale;      /* f64::from(font.scale_for_pixel_height(font_size as f32)) */
+    int32_t ascent, descent, line_gap, _pad; /* font.get_v_metrics(), font units */
+    double center_x, center_y; /* CENTER: get_label_position */
+    double _reserved;
+} osmt_text_run;
+
+/* Labels of a batch with text-run text.  The osmt_label records are the same as in osmt_label_batch, except that
+ * seg_off / n_segs name a range of `glyphs` (the chars of the text, in order). */
+typedef struct osmt_text_label_batch {
+    const osmt_label* labels;
+    size_t n_labels;
+    const uint32_t* job_label_off; /* [n_jobs + 1] */
+    const osmt_text_run* runs;     /* [n_labels] */
+    const osmt_text_glyph* glyphs;
+    size_t n_glyphs;
+    const int32_t* way_pts;   /* [n_way_pts][2]: Point (x, y) of get_waypoints, in walking order */
+    const double* way_sincos; /* [n_way_pts][2]: entry pt_off + e = (-get_angle(points, e)).sin_cos() of edge e -> e + 1;
+                               * the last entry of a label's range is unused */
+    size_t n_way_pts;
+} osmt_text_label_batch;
+
+/* osmt_glyph_instance.form of a glyph whose text place() returned from before rasterizing (wider than its way, fewer
+ * than two way points): expands to no draw_line call.  Only ever seen through osmt_scene_read_glyph_instances; not a
+ * form osmt_scene_set_glyph_labels accepts. */
+#define OSMT_GLYPH_NONE 2u
+
 typedef struct osmt_config {
     int32_t device; /* HIP device ordinal */
     uint32_t flags; /* reserved, 0 */
@@ -326,6 +380,31 @@ int osmt_render_batch_rgb_glyphs(osmt_ctx* ctx, const osmt_batch* batch, const o
  * labels it is in label order (label, glyph, vertex, subdivision); for segment labels it is the caller's segs.  *n is
  * always set; out may be NULL to ask for the size; cap (in calls) < *n with a non-NULL out is OSMT_INVALID_ARG. */
 int osmt_scene_read_label_segs(osmt_ctx* ctx, osmt_scene* scene, double* out, size_t cap, size_t* n);
+
+/* ---- label text as text runs (see osmt_text_label_batch) ---------------------------------------- */
+/* The checks osmt_scene_set_text_labels runs first, without a device.  OSMT_OK, or with the reason in osmt_last_error():
+ *   - OSMT_INVALID_ARG: NULL pools; job_label_off not running from 0 to n_labels monotonically; a glyph or way-point
+ *     range outside its table; glyph ranges of two labels that overlap (a slot has one owner: one wave writes a
+ *     label's slots); an unknown position; a scale, centre or used way_sincos entry that is not finite; |advance| or
+ *     |kern| > 65535; y_offset > 2^20; |center| > 2^20;
+ *   - OSMT_UNSUPPORTED: a way point with |v| > 2^28 (the i32 differences of Point::dist must not overflow).
+ * Only labels with has_text are looked at; n_segs == 0 and a LINE run with n_pts < 2 are legal and place nothing. */
+int osmt_validate_text_labels(const osmt_text_label_batch* labels, size_t n_jobs);
+/* osmt_scene_set_labels with text-run text: TextPlacer::place runs on the device (k_text_place, one wave per label)
+ * and writes one osmt_glyph_instance per glyph — slot seg_off + k is glyph k of the label — which the count / emit
+ * passes of osmt_scene_set_glyph_labels expand on the same stream; the label kernels run unchanged behind them.  NULL /
+ * n_labels == 0 detaches.  Errors: those of osmt_validate_text_labels, OSMT_INVALID_ARG for a glyph id outside the
+ * table, and everything osmt_scene_set_glyph_labels reports downstream (a produced draw_line coordinate that is not
+ * finite or beyond 2^20 is OSMT_UNSUPPORTED). */
+int osmt_scene_set_text_labels(osmt_ctx* ctx, osmt_scene* scene, const osmt_text_label_batch* labels);
+/* osmt_render_batch_rgb with text-run labels: scene, osmt_scene_set_text_labels, render, packed RGB8 out. */
+int osmt_render_batch_rgb_text(osmt_ctx* ctx, const osmt_batch* batch, const osmt_text_label_batch* labels, uint8_t* out_rgb,
+                               size_t out_tile_stride_bytes);
+/* Inspection: the glyph instances the last osmt_scene_set_text_labels placed, out = [n] in slot order (n = the batch's
+ * n_glyphs).  CENTER instances carry p[0..1], LINE instances p[0..5], skipped texts OSMT_GLYPH_NONE; unused entries of p
+ * and slots no has_text label names read as zero.  With any other label form attached *n is 0.  *n is always set; out
+ * may be NULL to ask for the size; cap < *n with a non-NULL out is OSMT_INVALID_ARG. */
+int osmt_scene_read_glyph_instances(osmt_ctx* ctx, osmt_scene* scene, osmt_glyph_instance* out, size_t cap, size_t* n);
 /* Diagnostics: out[i] = the device hypot of (xy[2i], xy[2i + 1]) — the function the glyph walk flattens curves with. */
 int osmt_debug_hypot(osmt_ctx* ctx, const double* xy, size_t n, double* out);
 

@@ -23,6 +23,8 @@ GLYPH_MOVE_TO, GLYPH_LINE_TO, GLYPH_CURVE_TO = 1, 2, 3  # osmt_glyph_vertex.type
 LABEL_OK, LABEL_NONE, LABEL_TOO_LARGE = 0, 1, 2  # osmt_label_position.status
 LABEL_MAX_CELLS = 65536
 GLYPH_CENTER, GLYPH_LINE = 0, 1  # osmt_glyph_instance.form: TextPlacer::place's two `tr` closures
+GLYPH_NONE = 2  # a glyph of a text place() skipped (seen through osmt_scene_read_glyph_instances only)
+TEXT_CENTER, TEXT_LINE = 0, 1  # osmt_text_run.position: TextPosition
 
 
 class Op(C.Structure):
@@ -139,6 +141,41 @@ class GlyphLabelBatch(C.Structure):
     ]
 
 
+class TextGlyph(C.Structure):
+    _fields_ = [("glyph_id", C.c_uint32), ("advance", C.c_int32), ("kern", C.c_int32), ("flags", C.c_uint32)]
+
+
+class TextRun(C.Structure):
+    _fields_ = [
+        ("position", C.c_uint32),
+        ("y_offset", C.c_uint32),
+        ("pt_off", C.c_uint32),
+        ("n_pts", C.c_uint32),
+        ("scale", C.c_double),
+        ("ascent", C.c_int32),
+        ("descent", C.c_int32),
+        ("line_gap", C.c_int32),
+        ("_pad", C.c_int32),
+        ("center_x", C.c_double),
+        ("center_y", C.c_double),
+        ("_reserved", C.c_double),
+    ]
+
+
+class TextLabelBatch(C.Structure):
+    _fields_ = [
+        ("labels", C.POINTER(Label)),
+        ("n_labels", C.c_size_t),
+        ("job_label_off", C.POINTER(C.c_uint32)),
+        ("runs", C.POINTER(TextRun)),
+        ("glyphs", C.POINTER(TextGlyph)),
+        ("n_glyphs", C.c_size_t),
+        ("way_pts", C.POINTER(C.c_int32)),
+        ("way_sincos", C.POINTER(C.c_double)),
+        ("n_way_pts", C.c_size_t),
+    ]
+
+
 class LabelRequest(C.Structure):
     _fields_ = [("ring_off", C.c_uint32), ("n_rings", C.c_uint32), ("scale", C.c_double)]
 
@@ -168,5 +205,7 @@ assert C.sizeof(TileJob) == 32
 assert C.sizeof(Label) == 40
 assert C.sizeof(GlyphVertex) == 10
 assert C.sizeof(GlyphInstance) == 64
+assert C.sizeof(TextGlyph) == 16
+assert C.sizeof(TextRun) == 64
 assert C.sizeof(LabelRequest) == 16
 assert C.sizeof(LabelPosition) == 24

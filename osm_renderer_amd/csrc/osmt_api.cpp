@@ -26,6 +26,7 @@
 #include "osmt_geom.h"
 #include "osmt_internal.h"
 #include "osmt_png_table.h" /* PNG_LMAX, PNG_BLOCK_HDR_BITS: the slot bound */
+#include "../host/osmt_textplacer.hpp" /* osmt::validate_text_labels */
 
 namespace {
 
@@ -207,6 +208,10 @@ struct osmt_scene {
     uint32_t* d_lab_err = nullptr;
     osmt_tile_label* d_tile_labels = nullptr;
     uint32_t* d_tile_label_cnt = nullptr;
+    /* text-run labels (osmt_scene_set_text_labels): the glyph instances k_text_place wrote, kept for
+     * osmt_scene_read_glyph_instances; an allocation of its own, gone with the next set call */
+    osmt_glyph_instance* d_text_inst = nullptr;
+    uint32_t n_text_inst = 0;
 };
 
 namespace {
@@ -1461,21 +1466,26 @@ void osmt_scene_free(osmt_scene* s) {
     dev_free(s->ctx, s->d_front);
     dev_free(s->ctx, s->d_arena);
     dev_free(s->ctx, s->d_lab_base);
+    dev_free(s->ctx, s->d_text_inst);
     stage_release(s->ctx, s->h_stage);
     scene_delete(s);
 }
 
 /* Glyph-run labels, first half: validates the instances, builds the (label, instance) pairs in label order, runs the
  * count pass and reads back each label's window summary (osmt_label_extent, ~20 bytes per label) and the error word.
- * *gtmp: the device buffer the emit pass still needs (the caller frees it after synchronising `st`). */
-static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_label_batch* gb, hipStream_t st, char** gtmp,
-                              osmt_glyph_pass* gp, std::vector<osmt_label_extent>& ext) {
+ * *gtmp: the device buffer the emit pass still needs (the caller frees it after synchronising `st`).
+ * Exactly one of gb (instances from the host) and tb (text runs: k_text_place writes the instances into sc->d_text_inst,
+ * in front of the count pass on the same stream; tb has passed osmt::validate_text_labels) is given. */
+static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_label_batch* gb, const osmt_text_label_batch* tb, hipStream_t st,
+                              char** gtmp, osmt_glyph_pass* gp, std::vector<osmt_label_extent>& ext) {
     glyph_snapshot snap;
     {
         const int rc = sync_glyphs(ctx, &snap);
         if (rc != OSMT_OK) return rc;
     }
-    for (size_t i = 0; i < gb->n_glyphs; ++i) {
+    const osmt_label* const labels = gb ? gb->labels : tb->labels;
+    const size_t n_labels = gb ? gb->n_labels : tb->n_labels, n_glyphs = gb ? gb->n_glyphs : tb->n_glyphs;
+    for (size_t i = 0; gb && i < n_glyphs; ++i) {
         const osmt_glyph_instance& g = gb->glyphs[i];
         if (g.glyph_id >= snap.n) return fail(OSMT_INVALID_ARG, "glyph instance %zu: glyph id %u is not in the glyph table (%u glyphs)", i, g.glyph_id, snap.n);
         if (g.form != OSMT_GLYPH_CENTER && g.form != OSMT_GLYPH_LINE) return fail(OSMT_INVALID_ARG, "glyph instance %zu: unknown form %u", i, g.form);
@@ -1485,24 +1495,31 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
         if (!finite) return fail(OSMT_INVALID_ARG, "glyph instance %zu: scale or placement not finite", i);
     }
     std::vector<uint32_t> pair_inst, pair_label;
-    for (size_t l = 0; l < gb->n_labels; ++l) {
-        const osmt_label& in = gb->labels[l];
+    for (size_t l = 0; l < n_labels; ++l) {
+        const osmt_label& in = labels[l];
         if (!in.has_text || in.n_segs == 0) continue;
-        if ((size_t)in.seg_off + in.n_segs > gb->n_glyphs) return fail(OSMT_INVALID_ARG, "label %zu: glyph instance range out of bounds", l);
+        if ((size_t)in.seg_off + in.n_segs > n_glyphs) return fail(OSMT_INVALID_ARG, "label %zu: glyph instance range out of bounds", l);
         if (pair_inst.size() + in.n_segs >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "too many glyph instances");
         for (uint32_t k = 0; k < in.n_segs; ++k) {
+            if (tb && tb->glyphs[(size_t)in.seg_off + k].glyph_id >= snap.n)
+                return fail(OSMT_INVALID_ARG, "label %zu, glyph %u: glyph id %u is not in the glyph table (%u glyphs)", l, k,
+                            tb->glyphs[(size_t)in.seg_off + k].glyph_id, snap.n);
             pair_inst.push_back(in.seg_off + k);
             pair_label.push_back((uint32_t)l);
         }
     }
-    const size_t n_pairs = pair_inst.size(), n_labels = gb->n_labels;
+    const size_t n_pairs = pair_inst.size();
     size_t off = 0;
     auto carve = [&](size_t bytes) {
         const size_t o = off;
         off = align_up(off + bytes, 256);
         return o;
     };
-    const size_t o_inst = carve(gb->n_glyphs * sizeof(osmt_glyph_instance));
+    const size_t o_inst = carve(gb ? n_glyphs * sizeof(osmt_glyph_instance) : 0);
+    /* text runs: what k_text_place reads */
+    const size_t n_way = tb ? tb->n_way_pts : 0;
+    const size_t o_tlab = carve(tb ? n_labels * sizeof(osmt_label) : 0), o_trun = carve(tb ? n_labels * sizeof(osmt_text_run) : 0);
+    const size_t o_tgl = carve(tb ? n_glyphs * sizeof(osmt_text_glyph) : 0), o_twp = carve(n_way * 8), o_tws = carve(n_way * 16);
     const size_t o_pi = carve(n_pairs * 4), o_pl = carve(n_pairs * 4), o_pc = carve(n_pairs * 4), o_pb = carve(n_pairs * 4);
     const size_t o_blk = carve((n_pairs / 1024 + 1) * 4);
     const size_t o_sum = carve(n_labels * sizeof(osmt_label_extent) + 4); /* the error word right behind: one read-back */
@@ -1510,7 +1527,12 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
     char* base = *gtmp;
     gp->verts = snap.verts;
     gp->voff = snap.voff;
-    gp->inst = (const osmt_glyph_instance*)(base + o_inst);
+    if (tb) { /* the instances outlive this call (osmt_scene_read_glyph_instances) */
+        HIP_TRY(dev_alloc(ctx, (void**)&sc->d_text_inst, std::max<size_t>(n_glyphs, 1) * sizeof(osmt_glyph_instance)));
+        gp->inst = sc->d_text_inst;
+    } else {
+        gp->inst = (const osmt_glyph_instance*)(base + o_inst);
+    }
     gp->pair_inst = (const uint32_t*)(base + o_pi);
     gp->pair_label = (const uint32_t*)(base + o_pl);
     gp->n_pairs = (uint32_t)n_pairs;
@@ -1520,7 +1542,27 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
     gp->pair_cnt = (uint32_t*)(base + o_pc);
     gp->pair_base = (uint32_t*)(base + o_pb);
     gp->blk = (uint32_t*)(base + o_blk);
-    if (gb->n_glyphs) HIP_TRY(hipMemcpyAsync(base + o_inst, gb->glyphs, gb->n_glyphs * sizeof(osmt_glyph_instance), hipMemcpyHostToDevice, st));
+    if (gb && n_glyphs) HIP_TRY(hipMemcpyAsync(base + o_inst, gb->glyphs, n_glyphs * sizeof(osmt_glyph_instance), hipMemcpyHostToDevice, st));
+    if (tb) {
+        osmt_text_pass tp{};
+        tp.labels = (const osmt_label*)(base + o_tlab);
+        tp.n_labels = (uint32_t)n_labels;
+        tp.runs = (const osmt_text_run*)(base + o_trun);
+        tp.glyphs = (const osmt_text_glyph*)(base + o_tgl);
+        tp.way_pts = (const int32_t*)(base + o_twp);
+        tp.way_sincos = (const double*)(base + o_tws);
+        tp.inst = sc->d_text_inst;
+        HIP_TRY(hipMemcpyAsync(base + o_tlab, tb->labels, n_labels * sizeof(osmt_label), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(base + o_trun, tb->runs, n_labels * sizeof(osmt_text_run), hipMemcpyHostToDevice, st));
+        if (n_glyphs) HIP_TRY(hipMemcpyAsync(base + o_tgl, tb->glyphs, n_glyphs * sizeof(osmt_text_glyph), hipMemcpyHostToDevice, st));
+        if (n_way) {
+            HIP_TRY(hipMemcpyAsync(base + o_twp, tb->way_pts, n_way * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(base + o_tws, tb->way_sincos, n_way * 16, hipMemcpyHostToDevice, st));
+        }
+        /* slots no label with text names read as zero */
+        HIP_TRY(hipMemsetAsync(sc->d_text_inst, 0, std::max<size_t>(n_glyphs, 1) * sizeof(osmt_glyph_instance), st));
+        HIP_TRY(osmt_launch_text_place(tp, st));
+    }
     if (n_pairs) {
         HIP_TRY(hipMemcpyAsync(base + o_pi, pair_inst.data(), n_pairs * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(base + o_pl, pair_label.data(), n_pairs * 4, hipMemcpyHostToDevice, st));
@@ -1545,7 +1587,8 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
  * (tile_pixels.rs:67-72) x every column those stripes can hold a key in (+-2 cells of slack for the
  * rounding of eval_x_at_y, font/rasterizer.rs:37).  Exactly one of lb (draw_line calls from the host) and gb (glyph
  * runs, expanded on the device) is used; both feed the same per-label summaries (osmt_label_extent) to the window code. */
-static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_label_batch* lb, const osmt_glyph_label_batch* gb = nullptr) {
+static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_label_batch* lb, const osmt_glyph_label_batch* gb = nullptr,
+                                      const osmt_text_label_batch* tb = nullptr) {
     if (!ctx || !sc || sc->ctx != ctx) return fail(OSMT_INVALID_ARG, "bad ctx/scene");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = sc->own_stream;
@@ -1568,13 +1611,22 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
     dev_free(ctx, sc->d_lab_base);
     sc->d_lab_base = nullptr;
     sc->n_labels = sc->n_label_segs = 0;
-    const osmt_label* const labels = lb ? lb->labels : gb ? gb->labels : nullptr;
-    const size_t n_labels = lb ? lb->n_labels : gb ? gb->n_labels : 0;
-    const uint32_t* const job_label_off = lb ? lb->job_label_off : gb ? gb->job_label_off : nullptr;
+    dev_free(ctx, sc->d_text_inst);
+    sc->d_text_inst = nullptr;
+    sc->n_text_inst = 0;
+    const osmt_label* const labels = lb ? lb->labels : gb ? gb->labels : tb ? tb->labels : nullptr;
+    const size_t n_labels = lb ? lb->n_labels : gb ? gb->n_labels : tb ? tb->n_labels : 0;
+    const uint32_t* const job_label_off = lb ? lb->job_label_off : gb ? gb->job_label_off : tb ? tb->job_label_off : nullptr;
     if (n_labels == 0) return OSMT_OK;
+    if (tb) {
+        std::string why;
+        const int rc = osmt::validate_text_labels(tb, sc->n_jobs, &why);
+        if (rc != OSMT_OK) return fail(rc, "%s", why.c_str());
+    }
     if (!labels || !job_label_off || (lb && lb->n_segs && !lb->segs) || (gb && gb->n_glyphs && !gb->glyphs))
         return fail(OSMT_INVALID_ARG, "NULL label pool");
-    if (n_labels >= 0xFFFFFFFFull || (lb ? lb->n_segs : gb->n_glyphs) >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "label batch too large");
+    if (n_labels >= 0xFFFFFFFFull || (lb ? lb->n_segs : gb ? gb->n_glyphs : tb->n_glyphs) >= 0xFFFFFFFFull)
+        return fail(OSMT_INVALID_ARG, "label batch too large");
     if (job_label_off[0] != 0 || job_label_off[sc->n_jobs] != n_labels)
         return fail(OSMT_INVALID_ARG, "job_label_off must run from 0 to n_labels over n_jobs + 1 entries");
     for (uint32_t j = 0; j < sc->n_jobs; ++j)
@@ -1599,9 +1651,23 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
             }
         }
     } gtmp{ctx, st, nullptr};
+    /* text runs: the instances stay with the scene only if the whole call succeeds */
+    struct inst_guard {
+        osmt_ctx* c;
+        osmt_scene* s;
+        hipStream_t st;
+        bool keep;
+        ~inst_guard() {
+            if (!keep && s->d_text_inst) {
+                (void)hipStreamSynchronize(st);
+                dev_free(c, s->d_text_inst);
+                s->d_text_inst = nullptr;
+            }
+        }
+    } text_inst{ctx, sc, st, false};
     size_t n_segs_total = lb ? lb->n_segs : 0;
-    if (gb) {
-        const int rc = glyph_labels_count(ctx, sc, gb, st, &gtmp.p, &gp, gext);
+    if (!lb) {
+        const int rc = glyph_labels_count(ctx, sc, gb, tb, st, &gtmp.p, &gp, gext);
         if (rc != OSMT_OK) return rc;
         gseg_off.resize(n_labels);
         for (size_t l = 0; l < n_labels; ++l) {
@@ -1754,7 +1820,7 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
     e = up(sc->d_lab, info.data(), info.size() * sizeof(osmt_labelinfo));
     if (e == hipSuccess) e = up(sc->d_job_label_off, job_label_off, ((size_t)sc->n_jobs + 1) * 4);
     if (e == hipSuccess && lb) e = up(sc->d_lab_segs, lb->segs, lb->n_segs * 32);
-    if (e == hipSuccess && gb) { /* the glyph runs' calls, written straight into the arena */
+    if (e == hipSuccess && !lb) { /* the glyph runs' calls, written straight into the arena */
         gp.segs = sc->d_lab_segs;
         gp.n_segs = (uint32_t)n_segs_total;
         e = osmt_launch_glyph_emit(gp, st);
@@ -1772,7 +1838,7 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
         sc->d_lab_base = nullptr;
         return fail(OSMT_HIP_ERROR, "label upload failed: %s", hipGetErrorString(e));
     }
-    if (gb) { /* the emit pass's own check (a call beyond the arena the count pass sized): a 4-byte read-back */
+    if (!lb) { /* the emit pass's own check (a call beyond the arena the count pass sized): a 4-byte read-back */
         uint32_t err = 0;
         e = hipMemcpyAsync(&err, gp.err, 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1785,6 +1851,10 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
     }
     sc->n_labels = (uint32_t)n_labels;
     sc->n_label_segs = (uint32_t)n_segs_total;
+    if (tb) {
+        sc->n_text_inst = (uint32_t)tb->n_glyphs;
+        text_inst.keep = true;
+    }
     return OSMT_OK;
 }
 
@@ -1794,6 +1864,33 @@ int osmt_scene_set_labels(osmt_ctx* ctx, osmt_scene* sc, const osmt_label_batch*
 
 int osmt_scene_set_glyph_labels(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_label_batch* gb) {
     return guarded([&] { return osmt_scene_set_labels_body(ctx, sc, nullptr, gb); });
+}
+
+int osmt_scene_set_text_labels(osmt_ctx* ctx, osmt_scene* sc, const osmt_text_label_batch* tb) {
+    return guarded([&] { return osmt_scene_set_labels_body(ctx, sc, nullptr, nullptr, tb); });
+}
+
+int osmt_validate_text_labels(const osmt_text_label_batch* tb, size_t n_jobs) {
+    return guarded([&] {
+        std::string why;
+        const int rc = osmt::validate_text_labels(tb, n_jobs, &why);
+        return rc == OSMT_OK ? OSMT_OK : fail(rc, "%s", why.c_str());
+    });
+}
+
+static int osmt_scene_read_glyph_instances_body(osmt_ctx* ctx, osmt_scene* sc, osmt_glyph_instance* out, size_t cap, size_t* n) {
+    if (!ctx || !sc || sc->ctx != ctx || !n) return fail(OSMT_INVALID_ARG, "NULL argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(scene_wait_idle(sc));
+    *n = sc->n_labels && sc->d_text_inst ? sc->n_text_inst : 0;
+    if (!out) return OSMT_OK;
+    if (cap < *n) return fail(OSMT_INVALID_ARG, "out holds %zu glyph instances, the scene has %zu", cap, *n);
+    if (*n) HIP_TRY(copy_back(ctx, out, sc->d_text_inst, *n * sizeof(osmt_glyph_instance)));
+    return OSMT_OK;
+}
+
+int osmt_scene_read_glyph_instances(osmt_ctx* ctx, osmt_scene* sc, osmt_glyph_instance* out, size_t cap, size_t* n) {
+    return guarded([&] { return osmt_scene_read_glyph_instances_body(ctx, sc, out, cap, n); });
 }
 
 static int osmt_scene_read_label_segs_body(osmt_ctx* ctx, osmt_scene* sc, double* out, size_t cap, size_t* n) {
@@ -2060,22 +2157,25 @@ int osmt_render_batch(osmt_ctx* ctx, const osmt_batch* batch, uint8_t* out_rgba,
 }
 
 static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba, size_t stride,
-                                         bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels);
+                                         bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels,
+                                         const osmt_text_label_batch* tlabels);
 
 /* the host-buffer render: arenas guessed from the recent densities first; a miss renders again with exact sizing */
 static int osmt_render_batch_labels_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,
-                                         size_t stride, bool rgb = false, bool trusted = false, const osmt_glyph_label_batch* glabels = nullptr) {
+                                         size_t stride, bool rgb = false, bool trusted = false, const osmt_glyph_label_batch* glabels = nullptr,
+                                         const osmt_text_label_batch* tlabels = nullptr) {
     g_arena_guess_missed = false;
-    int rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, trusted, true, glabels);
+    int rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, trusted, true, glabels, tlabels);
     if (rc != OSMT_OK && g_arena_guess_missed) {
         g_arena_guess_missed = false;
-        rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, true, false, glabels); /* validated the first time */
+        rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, true, false, glabels, tlabels); /* validated the first time */
     }
     return rc;
 }
 
 static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba, size_t stride,
-                                         bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels) {
+                                         bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels,
+                                         const osmt_text_label_batch* tlabels) {
     if (!ctx || !out_rgba) return fail(OSMT_INVALID_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = nullptr; /* the whole call lives on its own stream: concurrent callers overlap on the GPU */
@@ -2086,8 +2186,9 @@ static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch,
         stream_release(ctx, st);
         return rc;
     }
-    if (labels || glabels) {
-        rc = labels ? osmt_scene_set_labels(ctx, sc, labels) : osmt_scene_set_glyph_labels(ctx, sc, glabels);
+    if (labels || glabels || tlabels) {
+        rc = labels ? osmt_scene_set_labels(ctx, sc, labels)
+                    : glabels ? osmt_scene_set_glyph_labels(ctx, sc, glabels) : osmt_scene_set_text_labels(ctx, sc, tlabels);
         if (rc != OSMT_OK) {
             osmt_scene_free(sc);
             stream_release(ctx, st);
@@ -2225,6 +2326,10 @@ int osmt_render_batch_rgb(osmt_ctx* ctx, const osmt_batch* batch, const osmt_lab
 
 int osmt_render_batch_rgb_glyphs(osmt_ctx* ctx, const osmt_batch* batch, const osmt_glyph_label_batch* labels, uint8_t* out_rgb, size_t stride) {
     return guarded([&] { return osmt_render_batch_labels_body(ctx, batch, nullptr, out_rgb, stride, true, false, labels); });
+}
+
+int osmt_render_batch_rgb_text(osmt_ctx* ctx, const osmt_batch* batch, const osmt_text_label_batch* labels, uint8_t* out_rgb, size_t stride) {
+    return guarded([&] { return osmt_render_batch_labels_body(ctx, batch, nullptr, out_rgb, stride, true, false, nullptr, labels); });
 }
 
 int osmt_render_batch_labels(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,

@@ -94,9 +94,10 @@ __global__ __launch_bounds__(256) void k_glyph_count(osmt_glyph_pass a) {
     if (p >= a.n_pairs) return; /* whole wave */
     const osmt_glyph_instance& in = a.inst[a.pair_inst[p]];
     const uint32_t label = a.pair_label[p];
-    const uint32_t v0 = a.voff[in.glyph_id], nv = a.voff[in.glyph_id + 1] - v0;
-    const double scale = in.scale;
     const uint32_t form = in.form;
+    /* OSMT_GLYPH_NONE (a text k_text_place skipped): no call */
+    const uint32_t v0 = a.voff[in.glyph_id], nv = form == OSMT_GLYPH_NONE ? 0u : a.voff[in.glyph_id + 1] - v0;
+    const double scale = in.scale;
     double prm[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) prm[k] = in.p[k];
@@ -174,9 +175,10 @@ __global__ __launch_bounds__(256) void k_glyph_emit(osmt_glyph_pass a) {
     const uint32_t lane = threadIdx.x & 63u;
     if (p >= a.n_pairs) return;
     const osmt_glyph_instance& in = a.inst[a.pair_inst[p]];
-    const uint32_t v0 = a.voff[in.glyph_id], nv = a.voff[in.glyph_id + 1] - v0;
-    const double scale = in.scale;
     const uint32_t form = in.form;
+    /* OSMT_GLYPH_NONE (a text k_text_place skipped): no call */
+    const uint32_t v0 = a.voff[in.glyph_id], nv = form == OSMT_GLYPH_NONE ? 0u : a.voff[in.glyph_id + 1] - v0;
+    const double scale = in.scale;
     double prm[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) prm[k] = in.p[k];

@@ -382,6 +382,18 @@ hipError_t osmt_launch_labels(const osmt_label_launch& a, hipStream_t st);
 hipError_t osmt_launch_glyph_count(const osmt_glyph_pass& a, uint32_t n_labels, hipStream_t st);
 /* the scan of the pair counts + k_glyph_emit (draw_line calls into a.segs) */
 hipError_t osmt_launch_glyph_emit(const osmt_glyph_pass& a, hipStream_t st);
+/* text-run labels (osmt_textplace.hip): one label per wave; the batch has passed osmt::validate_text_labels */
+struct osmt_text_pass {
+    const osmt_label* labels;
+    uint32_t n_labels;
+    const osmt_text_run* runs;     /* [n_labels] */
+    const osmt_text_glyph* glyphs; /* a label's text: glyphs[seg_off .. seg_off + n_segs) */
+    const int32_t* way_pts;        /* [n_way_pts][2] */
+    const double* way_sincos;      /* [n_way_pts][2] */
+    osmt_glyph_instance* inst;     /* out: slot seg_off + k = glyph k of its label */
+};
+/* k_text_place: TextPlacer::place of every label with text, glyph instances into a.inst */
+hipError_t osmt_launch_text_place(const osmt_text_pass& a, hipStream_t st);
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

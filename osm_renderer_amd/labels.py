@@ -473,3 +473,198 @@ def make_glyph_labels(n_tiles, table, labels_per_tile=24, scale=1, seed=7, n_ima
         lists.append(GlyphLabelList(np.array(labs, dtype=LABEL_DTYPE), [0, len(labs)],
                                     np.concatenate(glyphs) if glyphs else np.zeros(0, GLYPH_INSTANCE_DTYPE)))
     return concat_glyph_labels(lists)
+
+
+# ---- text runs (osmt_text_label_batch) -----------------------------------------------------------
+TEXT_GLYPH_DTYPE = np.dtype([("glyph_id", "<u4"), ("advance", "<i4"), ("kern", "<i4"), ("flags", "<u4")])
+TEXT_RUN_DTYPE = np.dtype([("position", "<u4"), ("y_offset", "<u4"), ("pt_off", "<u4"), ("n_pts", "<u4"), ("scale", "<f8"),
+                           ("ascent", "<i4"), ("descent", "<i4"), ("line_gap", "<i4"), ("_pad", "<i4"),
+                           ("center_x", "<f8"), ("center_y", "<f8"), ("_reserved", "<f8")])
+assert TEXT_GLYPH_DTYPE.itemsize == C.sizeof(abi.TextGlyph) == 16
+assert TEXT_RUN_DTYPE.itemsize == C.sizeof(abi.TextRun) == 64
+
+
+def way_sincos(points):
+    """(-get_angle(points, e)).sin_cos() of every edge e -> e + 1 of a way (text_placer.rs:93, 256-262) with this
+    process's libm, as osmt_text_label_batch.way_sincos wants it: float64 [n, 2], the last row unused (zero)."""
+    out = np.zeros((len(points), 2), dtype=np.float64)
+    for e in range(len(points) - 1):
+        angle = math.atan2(float(int(points[e + 1][1]) - int(points[e][1])), float(int(points[e + 1][0]) - int(points[e][0])))
+        out[e] = (math.sin(-angle), math.cos(-angle))
+    return out
+
+
+def walking_order(points):
+    """The reversal of text_placer.rs:65-67: a way is walked from its end when points[0].x > last.x."""
+    points = np.asarray(points, dtype=np.int32).reshape(-1, 2)
+    if len(points) >= 2 and points[0][0] > points[-1][0]:
+        points = points[::-1]
+    return np.ascontiguousarray(points)
+
+
+class TextLabelList:
+    """Labels of a batch with text-run text (osmt_text_label_batch): `labels` are osmt_label records whose seg_off /
+    n_segs name a range of `glyphs` (TEXT_GLYPH_DTYPE, the chars of the text), `runs` (TEXT_RUN_DTYPE) holds one
+    TextPlacer::place call per label, `way_pts` (int32 [n, 2], in walking order) and `way_sincos` (float64 [n, 2]) the
+    ways of the line-form runs."""
+
+    def __init__(self, labels, job_label_off, runs, glyphs, way_pts, way_sincos):
+        self.labels = np.ascontiguousarray(labels, dtype=LABEL_DTYPE)
+        self.job_label_off = np.ascontiguousarray(job_label_off, dtype=np.uint32)
+        self.runs = np.ascontiguousarray(runs, dtype=TEXT_RUN_DTYPE)
+        self.glyphs = np.ascontiguousarray(glyphs, dtype=TEXT_GLYPH_DTYPE)
+        self.way_pts = np.ascontiguousarray(way_pts, dtype=np.int32).reshape(-1, 2)
+        self.way_sincos = np.ascontiguousarray(way_sincos, dtype=np.float64).reshape(-1, 2)
+        assert len(self.runs) == len(self.labels) and len(self.way_pts) == len(self.way_sincos)
+
+    @property
+    def n_jobs(self):
+        return len(self.job_label_off) - 1
+
+    def as_batch(self):
+        b = abi.TextLabelBatch()
+        b.labels = self.labels.ctypes.data_as(C.POINTER(abi.Label))
+        b.n_labels = len(self.labels)
+        b.job_label_off = self.job_label_off.ctypes.data_as(C.POINTER(C.c_uint32))
+        b.runs = self.runs.ctypes.data_as(C.POINTER(abi.TextRun))
+        b.glyphs = self.glyphs.ctypes.data_as(C.POINTER(abi.TextGlyph)) if len(self.glyphs) else None
+        b.n_glyphs = len(self.glyphs)
+        b.way_pts = self.way_pts.ctypes.data_as(C.POINTER(C.c_int32)) if len(self.way_pts) else None
+        b.way_sincos = self.way_sincos.ctypes.data_as(C.POINTER(C.c_double)) if len(self.way_pts) else None
+        b.n_way_pts = len(self.way_pts)
+        return b
+
+    def input_bytes(self):
+        """bytes handed to the library: 40 + 64 per label, 16 per glyph, 24 per way point + the job offsets."""
+        return 104 * len(self.labels) + 16 * len(self.glyphs) + 24 * len(self.way_pts) + 4 * len(self.job_label_off)
+
+    def subset(self, idx):
+        """The labels of tiles idx (in that order) as a TextLabelList of their own, glyphs and ways re-packed."""
+        parts = []
+        for i in idx:
+            a, b = int(self.job_label_off[i]), int(self.job_label_off[i + 1])
+            lab, runs = self.labels[a:b].copy(), self.runs[a:b].copy()
+            gs, ps, ss, cur, pcur = [], [], [], 0, 0
+            for l, r in zip(lab, runs):
+                n = int(l["n_segs"])
+                gs.append(self.glyphs[int(l["seg_off"]) : int(l["seg_off"]) + n])
+                l["seg_off"] = cur if n else 0
+                cur += n
+                m = int(r["n_pts"]) if int(r["position"]) == abi.TEXT_LINE else 0
+                ps.append(self.way_pts[int(r["pt_off"]) : int(r["pt_off"]) + m])
+                ss.append(self.way_sincos[int(r["pt_off"]) : int(r["pt_off"]) + m])
+                r["pt_off"] = pcur if m else 0
+                pcur += m
+            parts.append(TextLabelList(lab, [0, len(lab)], runs, np.concatenate(gs) if gs else np.zeros(0, TEXT_GLYPH_DTYPE),
+                                       np.concatenate(ps) if ps else np.zeros((0, 2), np.int32),
+                                       np.concatenate(ss) if ss else np.zeros((0, 2))))
+        return concat_text_labels(parts)
+
+
+def concat_text_labels(lists):
+    labels, offs, runs, glyphs, pts, scs = [], [0], [], [], [], []
+    cur = pcur = 0
+    for tl in lists:
+        lab, run = tl.labels.copy(), tl.runs.copy()
+        lab["seg_off"][lab["n_segs"] > 0] += cur
+        run["pt_off"][(run["position"] == abi.TEXT_LINE) & (run["n_pts"] > 0)] += pcur
+        labels.append(lab)
+        runs.append(run)
+        glyphs.append(tl.glyphs)
+        pts.append(tl.way_pts)
+        scs.append(tl.way_sincos)
+        cur += len(tl.glyphs)
+        pcur += len(tl.way_pts)
+        offs.extend((offs[-1] + tl.job_label_off[1:].astype(np.int64)).tolist())
+    return TextLabelList(np.concatenate(labels) if labels else np.zeros(0, LABEL_DTYPE), offs,
+                         np.concatenate(runs) if runs else np.zeros(0, TEXT_RUN_DTYPE),
+                         np.concatenate(glyphs) if glyphs else np.zeros(0, TEXT_GLYPH_DTYPE),
+                         np.concatenate(pts) if pts else np.zeros((0, 2), np.int32), np.concatenate(scs) if scs else np.zeros((0, 2)))
+
+
+def synth_text_glyphs(rng, table, n_words):
+    """A synthetic text of n_words words over SYNTH_GLYPHS, single spaces (the shapeless last glyph, whitespace)
+    between them; every glyph but the first gets a kern, non-zero for about a third of the pairs."""
+    space = len(SYNTH_GLYPHS) - 1
+    ids = []
+    for w in range(n_words):
+        if w:
+            ids.append(space)
+        ids.extend(int(rng.integers(0, space)) for _ in range(int(rng.integers(1, 6))))
+    g = np.zeros(len(ids), TEXT_GLYPH_DTYPE)
+    for k, i in enumerate(ids):
+        kern = int(rng.integers(-60, 41)) if k and rng.random() < 0.35 else 0
+        g[k] = (table.first_id + i, SYNTH_GLYPHS[i][0], kern, 1 if i == space else 0)
+    return g
+
+
+def synth_way(rng, cx, cy, n_pts, step):
+    """A way of n_pts integer points through about (cx, cy): a heading that bends at every point, steps of about `step`
+    pixels, now and then a repeated point (a zero-length edge)."""
+    heading = float(rng.uniform(-math.pi, math.pi))
+    x, y = float(cx), float(cy)
+    pts = [(int(x), int(y))]
+    for _ in range(n_pts - 1):
+        if rng.random() < 0.05:
+            pts.append(pts[-1])
+            continue
+        heading += float(rng.uniform(-0.6, 0.6))
+        d = float(rng.uniform(0.3, 1.7)) * step
+        x, y = x + d * math.cos(heading), y + d * math.sin(heading)
+        pts.append((int(x), int(y)))
+    pts = np.array(pts, dtype=np.int32).reshape(-1, 2)
+    pts += np.array([int(cx), int(cy)], dtype=np.int32) - (pts[0] + pts[-1]) // 2  # about centred on (cx, cy)
+    return pts
+
+
+def make_text_labels(n_tiles, table, labels_per_tile=24, scale=1, seed=7, n_images=0, image_sizes=None, text_frac=0.85,
+                     icon_frac=0.4, line_frac=0.3, empty_frac=0.03):
+    """The label workload of make_glyph_labels as text runs: what TextPlacer::place is GIVEN instead of what it
+    computes.  Multi-word texts over SYNTH_GLYPHS with kerns (the centred ones wrap into rows at MAX_TEXT_WIDTH), ways
+    of 2..40 points with bends (some too short for their text: place() skips those; now and then a way of one point
+    or none), icons whose half height becomes y_offset, labels without text and texts of zero glyphs (empty_frac)."""
+    rng = np.random.default_rng(seed)
+    W = 256 * scale
+    lists = []
+    for _ in range(n_tiles):
+        labs, runs, glyphs, pts = [], [], [], []
+        n_gl = n_pt = 0
+        for _ in range(labels_per_tile):
+            l, r = np.zeros((), LABEL_DTYPE), np.zeros((), TEXT_RUN_DTYPE)
+            cx = float(rng.integers(-W // 2, W + W // 2)) + float(rng.integers(0, 2)) * 0.5
+            cy = float(rng.integers(-W // 2, W + W // 2)) + float(rng.integers(0, 4)) * 0.25
+            y_off = 0
+            if n_images and rng.random() < icon_frac:
+                img = int(rng.integers(0, n_images))
+                l["has_icon"], l["image_id"] = 1, img
+                l["icon_center_x"], l["icon_center_y"] = cx, cy
+                y_off = int(image_sizes[img][0] // 2)
+            if rng.random() < text_frac:
+                l["has_text"] = 1
+                l["text_color"] = [int(v) for v in rng.integers(0, 256, size=3)]
+                font_px = float(rng.choice([9.0, 10.0, 11.0, 12.0, 14.0])) * scale
+                r["scale"] = font_px / 1000.0
+                r["ascent"], r["descent"], r["line_gap"] = int(_SYNTH_ASCENT), int(_SYNTH_DESCENT), int(_SYNTH_GAP)
+                text = np.zeros(0, TEXT_GLYPH_DTYPE) if rng.random() < empty_frac else synth_text_glyphs(rng, table, int(rng.integers(1, 5)))
+                if rng.random() < line_frac:
+                    r["position"] = abi.TEXT_LINE
+                    u = rng.random()
+                    n = 0 if u < 0.02 else 1 if u < 0.04 else int(rng.integers(2, 41))
+                    way = walking_order(synth_way(rng, cx, cy, n, 6.0 * scale)) if n else np.zeros((0, 2), np.int32)
+                    r["pt_off"], r["n_pts"] = (n_pt if n else 0), n
+                    pts.append(way)
+                    n_pt += n
+                else:
+                    r["position"] = abi.TEXT_CENTER
+                    r["y_offset"] = y_off
+                    r["center_x"], r["center_y"] = cx, cy
+                l["seg_off"], l["n_segs"] = (n_gl if len(text) else 0), len(text)
+                glyphs.append(text)
+                n_gl += len(text)
+            labs.append(l)
+            runs.append(r)
+        way_pts = np.concatenate(pts) if pts else np.zeros((0, 2), np.int32)
+        sincos = np.concatenate([way_sincos(p) for p in pts]) if pts else np.zeros((0, 2))
+        lists.append(TextLabelList(np.array(labs, dtype=LABEL_DTYPE), [0, len(labs)], np.array(runs, dtype=TEXT_RUN_DTYPE),
+                                   np.concatenate(glyphs) if glyphs else np.zeros(0, TEXT_GLYPH_DTYPE), way_pts, sincos))
+    return concat_text_labels(lists)

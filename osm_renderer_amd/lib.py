@@ -31,6 +31,7 @@ EXPORTS = [
     "osmt_debug_poison_enabled",
     "osmt_register_glyphs", "osmt_scene_set_glyph_labels", "osmt_render_batch_rgb_glyphs", "osmt_scene_read_label_segs",
     "osmt_debug_hypot",
+    "osmt_validate_text_labels", "osmt_scene_set_text_labels", "osmt_render_batch_rgb_text", "osmt_scene_read_glyph_instances",
     "osmt_label_positions", "osmt_label_positions_begin", "osmt_label_positions_end", "osmt_label_positions_stats",
 ]
 
@@ -114,6 +115,11 @@ def load():
         L.osmt_render_batch_rgb_glyphs.argtypes = [vp, C.POINTER(abi.Batch), C.POINTER(abi.GlyphLabelBatch), u8p, C.c_size_t]
         L.osmt_scene_read_label_segs.argtypes = [vp, vp, dp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.osmt_debug_hypot.argtypes = [vp, dp, C.c_size_t, dp]
+    if hasattr(L, "osmt_scene_set_text_labels"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_validate_text_labels.argtypes = [C.POINTER(abi.TextLabelBatch), C.c_size_t]
+        L.osmt_scene_set_text_labels.argtypes = [vp, vp, C.POINTER(abi.TextLabelBatch)]
+        L.osmt_render_batch_rgb_text.argtypes = [vp, C.POINTER(abi.Batch), C.POINTER(abi.TextLabelBatch), u8p, C.c_size_t]
+        L.osmt_scene_read_glyph_instances.argtypes = [vp, vp, C.POINTER(abi.GlyphInstance), C.c_size_t, C.POINTER(C.c_size_t)]
     if hasattr(L, "osmt_label_positions"):  # absent only from older variant builds loaded through OSMT_LIB
         L.osmt_label_positions.argtypes = [vp, C.POINTER(abi.LabelRequestBatch), vp]
         L.osmt_label_positions_begin.argtypes = [vp, C.POINTER(abi.LabelRequestBatch), C.POINTER(vp)]

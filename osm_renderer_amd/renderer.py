@@ -61,6 +61,29 @@ class Scene:
             check(load().osmt_scene_set_glyph_labels(self.ctx._h, self._h, C.byref(gb)))
         self.labels = glyph_labels
 
+    def set_text_labels(self, text_labels):
+        """osmt_scene_set_text_labels: attach text-run labels (labels.TextLabelList; None detaches): TextPlacer::place
+        runs on the device.  The glyph ids must be registered on this scene's context (Context.register_glyphs)."""
+        if text_labels is None:
+            check(load().osmt_scene_set_text_labels(self.ctx._h, self._h, None))
+        else:
+            assert text_labels.n_jobs == self.n_jobs
+            tb = text_labels.as_batch()
+            check(load().osmt_scene_set_text_labels(self.ctx._h, self._h, C.byref(tb)))
+        self.labels = text_labels
+
+    def read_glyph_instances(self):
+        """osmt_scene_read_glyph_instances: the glyph instances the device placed for the attached text-run labels
+        (labels.GLYPH_INSTANCE_DTYPE [n_glyphs], skipped texts with form GLYPH_NONE); empty for the other label forms."""
+        from .labels import GLYPH_INSTANCE_DTYPE
+
+        L, n = load(), C.c_size_t(0)
+        check(L.osmt_scene_read_glyph_instances(self.ctx._h, self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=GLYPH_INSTANCE_DTYPE)
+        if n.value:
+            check(L.osmt_scene_read_glyph_instances(self.ctx._h, self._h, out.ctypes.data_as(C.POINTER(abi.GlyphInstance)), n.value, C.byref(n)))
+        return out
+
     def read_label_segs(self):
         """osmt_scene_read_label_segs: the draw_line arena the label kernels read, float64 [n, 4]."""
         L, n = load(), C.c_size_t(0)
@@ -344,6 +367,19 @@ class Context:
         gb = glyph_labels.as_batch() if glyph_labels is not None else None
         check(load().osmt_render_batch_rgb_glyphs(self._h, C.byref(b), C.byref(gb) if gb is not None else None,
                                                   out.ctypes.data_as(C.POINTER(C.c_uint8)), stride))
+        return out
+
+    def render_batch_rgb_text(self, dl: DisplayList, text_labels, out=None, stride=None):
+        """osmt_render_batch_rgb_text: osmt_render_batch_rgb with text-run labels (labels.TextLabelList)."""
+        b = dl.as_batch()
+        tight = dl.dim * dl.dim * 3
+        stride = tight if stride is None else stride
+        if out is None:
+            out = np.empty((dl.n_jobs, stride), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size >= dl.n_jobs * stride
+        tb = text_labels.as_batch() if text_labels is not None else None
+        check(load().osmt_render_batch_rgb_text(self._h, C.byref(b), C.byref(tb) if tb is not None else None,
+                                                out.ctypes.data_as(C.POINTER(C.c_uint8)), stride))
         return out
 
     # -- PNG files from the GPU ----------------------------------------------------
