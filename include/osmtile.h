@@ -380,6 +380,18 @@ int osmt_render_batch_rgb_glyphs(osmt_ctx* ctx, const osmt_batch* batch, const o
  * labels it is in label order (label, glyph, vertex, subdivision); for segment labels it is the caller's segs.  *n is
  * always set; out may be NULL to ask for the size; cap (in calls) < *n with a non-NULL out is OSMT_INVALID_ARG. */
 int osmt_scene_read_label_segs(osmt_ctx* ctx, osmt_scene* scene, double* out, size_t cap, size_t* n);
+/* Inspection: the coverage plane of label `label` of the attached label batch (any of the three forms) as the last
+ * render's label stage left it: window = { ry0, ry1, cx0, cols } as sized at upload, out = [ry1 - ry0 + 1][cols] with
+ * out[r][c] = the f64 total of cell (cx0 + c, ry0 + r) — min(a + s_acc, 1.0) of save_to_figure
+ * (font/rasterizer.rs:121-143), 0 where the stripe has no key; k_raster blends it, total > 0 is the pixel set the
+ * collision test sees.  Synchronises the stream.  A label without a window (no text, no draw_line call, or no stripe
+ * inside the label area's rows) reports window = { 1, 0, 0, 0 } and *n = 0: not an error.  *n (in cells) is set
+ * whenever the label has a window; out may be NULL to ask for the size; cap (in cells) < *n with a non-NULL out is
+ * OSMT_INVALID_ARG, and so is a label index beyond the batch.  The planes are written by a render: between
+ * osmt_scene_set_*labels and the next osmt_render_scene the call fails with OSMT_INVALID_ARG rather than hand back
+ * memory nobody has written. */
+int osmt_scene_read_label_cover(osmt_ctx* ctx, osmt_scene* scene, uint32_t label, int32_t window[4], double* out, size_t cap,
+                                size_t* n);
 
 /* ---- label text as text runs (see osmt_text_label_batch) ---------------------------------------- */
 /* The checks osmt_scene_set_text_labels runs first, without a device.  OSMT_OK, or with the reason in osmt_last_error():

@@ -203,6 +203,7 @@ struct osmt_scene {
     unsigned long long* d_lab_bits = nullptr;
     uint32_t n_lab_bands = 0;
     uint32_t n_lab_wide = 0;
+    bool lab_cover_valid = false; /* a render has written the coverage planes of the attached labels (osmt_scene_read_label_cover) */
     uint32_t* d_lab_bitmap = nullptr;
     uint8_t* d_lab_ok = nullptr;
     uint32_t* d_lab_err = nullptr;
@@ -843,6 +844,7 @@ int render_impl(osmt_ctx* ctx, osmt_scene* sc, uint32_t stages, void* d_out, siz
         ll.tile_labels = sc->d_tile_labels;
         ll.tile_label_cnt = sc->d_tile_label_cnt;
         HIP_TRY(osmt_launch_labels(ll, st));
+        sc->lab_cover_valid = true;
     }
     if (stages & 4u) {
         image_snapshot img;
@@ -1611,6 +1613,7 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
     dev_free(ctx, sc->d_lab_base);
     sc->d_lab_base = nullptr;
     sc->n_labels = sc->n_label_segs = 0;
+    sc->lab_cover_valid = false;
     dev_free(ctx, sc->d_text_inst);
     sc->d_text_inst = nullptr;
     sc->n_text_inst = 0;
@@ -1906,6 +1909,34 @@ static int osmt_scene_read_label_segs_body(osmt_ctx* ctx, osmt_scene* sc, double
 
 int osmt_scene_read_label_segs(osmt_ctx* ctx, osmt_scene* sc, double* out, size_t cap, size_t* n) {
     return guarded([&] { return osmt_scene_read_label_segs_body(ctx, sc, out, cap, n); });
+}
+
+static int osmt_scene_read_label_cover_body(osmt_ctx* ctx, osmt_scene* sc, uint32_t label, int32_t window[4], double* out, size_t cap,
+                                            size_t* n) {
+    if (!ctx || !sc || sc->ctx != ctx || !window || !n) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *n = 0;
+    window[0] = 1, window[1] = 0, window[2] = 0, window[3] = 0;
+    if (label >= sc->n_labels) return fail(OSMT_INVALID_ARG, "label %u: the scene has %u labels attached", label, sc->n_labels);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(scene_wait_idle(sc));
+    /* The planes are written by the label stage of a render, not at upload: before the first one the pool holds
+     * whatever the recycled buffer held (the lesson of osmt_scene_read_label_status). */
+    if (!sc->lab_cover_valid) return fail(OSMT_INVALID_ARG, "no render has written the coverage planes of these labels yet");
+    const osmt_labelinfo& li = sc->h_lab_info[label];
+    if (!li.has_text || li.n_segs == 0 || li.ry0 > li.ry1) return OSMT_OK; /* no window: zero rows */
+    window[0] = li.ry0, window[1] = li.ry1, window[2] = li.cx0, window[3] = (int32_t)li.cols;
+    *n = (size_t)(li.ry1 - li.ry0 + 1) * li.cols;
+    if (!out) return OSMT_OK;
+    if (cap < *n) return fail(OSMT_INVALID_ARG, "out holds %zu cells, the window of label %u has %zu", cap, label, *n);
+    uint32_t err = 0;
+    HIP_TRY(copy_back(ctx, &err, sc->d_lab_err, 4));
+    if (err) return fail(OSMT_HIP_ERROR, "label coverage window overflow (internal error %u)", err);
+    HIP_TRY(copy_back(ctx, out, sc->d_lab_a + li.plane_off, *n * 8));
+    return OSMT_OK;
+}
+
+int osmt_scene_read_label_cover(osmt_ctx* ctx, osmt_scene* sc, uint32_t label, int32_t window[4], double* out, size_t cap, size_t* n) {
+    return guarded([&] { return osmt_scene_read_label_cover_body(ctx, sc, label, window, out, cap, n); });
 }
 
 static int osmt_debug_hypot_body(osmt_ctx* ctx, const double* xy, size_t n, double* out) {

@@ -30,7 +30,7 @@ EXPORTS = [
     "osmt_allreduce_tile_count_local", "osmt_allreduce_tile_count_enqueue", "osmt_allreduce_tile_count_result", "osmt_hbm_copy_probe",
     "osmt_debug_poison_enabled",
     "osmt_register_glyphs", "osmt_scene_set_glyph_labels", "osmt_render_batch_rgb_glyphs", "osmt_scene_read_label_segs",
-    "osmt_debug_hypot",
+    "osmt_debug_hypot", "osmt_scene_read_label_cover",
     "osmt_validate_text_labels", "osmt_scene_set_text_labels", "osmt_render_batch_rgb_text", "osmt_scene_read_glyph_instances",
     "osmt_label_positions", "osmt_label_positions_begin", "osmt_label_positions_end", "osmt_label_positions_stats",
 ]
@@ -125,6 +125,8 @@ def load():
         L.osmt_label_positions_begin.argtypes = [vp, C.POINTER(abi.LabelRequestBatch), C.POINTER(vp)]
         L.osmt_label_positions_end.argtypes = [vp, vp]
         L.osmt_label_positions_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "osmt_scene_read_label_cover"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_scene_read_label_cover.argtypes = [vp, vp, C.c_uint32, ip, dp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

@@ -93,6 +93,20 @@ class Scene:
             check(L.osmt_scene_read_label_segs(self.ctx._h, self._h, out.ctypes.data_as(C.POINTER(C.c_double)), n.value, C.byref(n)))
         return out
 
+    def read_label_cover(self, label):
+        """osmt_scene_read_label_cover: (ry0, cx0, plane float64 [rows, cols]) of one label of the attached batch, the
+        f64 totals the last render's label stage left (cell [r, c] is pixel (cx0 + c, ry0 + r)).  A label without a
+        window gives a plane of zero rows.  Raises before the first render after the labels were set."""
+        L, n, win = load(), C.c_size_t(0), (C.c_int32 * 4)()
+        check(L.osmt_scene_read_label_cover(self.ctx._h, self._h, int(label), win, None, 0, C.byref(n)))
+        ry0, ry1, cx0, cols = (int(v) for v in win)
+        rows = ry1 - ry0 + 1 if n.value else 0
+        out = np.zeros((rows, cols), dtype=np.float64)
+        if n.value:
+            check(L.osmt_scene_read_label_cover(self.ctx._h, self._h, int(label), win, out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                out.size, C.byref(n)))
+        return ry0, cx0, out
+
     def label_status(self):
         """label_generation_statuses of the last render (tile_pixels.rs:160-162)."""
         n = len(self.labels.labels) if self.labels is not None else 0
