@@ -262,6 +262,69 @@ typedef struct osmt_text_label_batch {
  * form osmt_scene_set_glyph_labels accepts. */
 #define OSMT_GLYPH_NONE 2u
 
+/* ---- label text as strings ------------------------------------------------------ */
+/* The fourth, optional form of label text: the caller registers a font's lookup tables once per context
+ * (osmt_register_font) and gives a label as its code points and a font size; the GPU runs TextPlacer::text_to_glyphs
+ * (font/text_placer.rs:170-197) — find_glyph_index, get_glyph_h_metrics, get_glyph_kern_advance, the "no kern for the
+ * first glyph" rule, ch.is_whitespace() — and writes the osmt_text_glyph records the text-run form uploads (k_text_shape),
+ * in front of k_text_place on the same stream.  What stays with the caller is parsing the TrueType file, once per font,
+ * and libm (way_sincos), as in the text-run form.  4 bytes per char + 64 per label + 24 per way point.
+ * Only the scene entries below and osmt_render_batch_rgb_strings take string labels; the PNG, worker and multi-GPU
+ * entries take osmt_label_batch only, as they do for glyph and text runs. */
+
+/* The flat tables of one font, read out of the file once by the caller (stb_truetype names in INTEGRATION.md 2b).
+ * Borrowed for the call; the library keeps copies. */
+typedef struct osmt_cmap_entry {
+    uint32_t code_point, glyph;
+} osmt_cmap_entry;
+
+typedef struct osmt_kern_pair {
+    uint32_t left, right; /* glyph indices */
+    int32_t value;        /* get_glyph_kern_advance(left, right), font units */
+} osmt_kern_pair;
+
+typedef struct osmt_font_desc {
+    const osmt_cmap_entry* cmap; /* [n_cmap], strictly increasing in code point, glyph < n_glyphs; a code point that is
+                                  * not listed is glyph 0 (find_glyph_index) */
+    size_t n_cmap;
+    const int32_t* advance;      /* [n_glyphs]: get_glyph_h_metrics(g).advance_width, |v| <= 65535 */
+    const uint32_t* outline_id;  /* [n_glyphs]: id from osmt_register_glyphs of glyph g's outline (no shape: an empty outline) */
+    size_t n_glyphs;             /* >= 1: glyph 0 is what a missing code point shapes to */
+    const osmt_kern_pair* kern;  /* [n_kern], strictly increasing in (left, right), left and right < n_glyphs, |value| <=
+                                  * 65535; a pair that is not listed is 0 (get_glyph_kern_advance) */
+    size_t n_kern;               /* 0 is legal (kern may be NULL then) */
+    int32_t ascent, descent, line_gap; /* get_v_metrics(), font units; ascent - descent != 0 */
+    int32_t _pad;
+} osmt_font_desc;
+
+/* One TextPlacer::place call of a string label; 64 bytes, one per label, read only when the label has_text: osmt_text_run
+ * without what the font knows.  The library computes scale = (double)((float)font_size / (float)(ascent - descent)) =
+ * f64::from(font.scale_for_pixel_height(font_size as f32)). */
+typedef struct osmt_string_run {
+    uint32_t position; /* OSMT_TEXT_CENTER / OSMT_TEXT_LINE */
+    uint32_t y_offset; /* CENTER: what label_with_icon returned (icon.height / 2, or 0) */
+    uint32_t pt_off, n_pts; /* LINE: range in way_pts / way_sincos */
+    uint32_t font_id;  /* id from osmt_register_font */
+    uint32_t _pad;
+    double font_size;  /* text_style.font_size * global_scale: the value place() casts to f32 */
+    double center_x, center_y; /* CENTER: get_label_position */
+    double _reserved[2];
+} osmt_string_run;
+
+/* Labels of a batch with string text.  The osmt_label records are the same as in osmt_label_batch, except that seg_off /
+ * n_segs name a range of `chars` (the code points of the text, in text order). */
+typedef struct osmt_string_label_batch {
+    const osmt_label* labels;
+    size_t n_labels;
+    const uint32_t* job_label_off; /* [n_jobs + 1] */
+    const osmt_string_run* runs;   /* [n_labels] */
+    const uint32_t* chars;         /* Unicode scalar values (Rust `char`): <= 0x10FFFF and no surrogate */
+    size_t n_chars;
+    const int32_t* way_pts;   /* as in osmt_text_label_batch */
+    const double* way_sincos; /* as in osmt_text_label_batch */
+    size_t n_way_pts;
+} osmt_string_label_batch;
+
 typedef struct osmt_config {
     int32_t device; /* HIP device ordinal */
     uint32_t flags; /* reserved, 0 */
@@ -417,6 +480,36 @@ int osmt_render_batch_rgb_text(osmt_ctx* ctx, const osmt_batch* batch, const osm
  * and slots no has_text label names read as zero.  With any other label form attached *n is 0.  *n is always set; out
  * may be NULL to ask for the size; cap < *n with a non-NULL out is OSMT_INVALID_ARG. */
 int osmt_scene_read_glyph_instances(osmt_ctx* ctx, osmt_scene* scene, osmt_glyph_instance* out, size_t cap, size_t* n);
+
+/* ---- label text as strings (see osmt_string_label_batch) ---------------------------------------- */
+/* Appends one font to the context's font table and returns its id.  Append-only with the snapshot semantics of
+ * osmt_register_image / osmt_register_glyphs: a render that holds an older snapshot never reads freed memory, and a font
+ * registered after a scene was set does not disturb that scene.  OSMT_INVALID_ARG, with the offender named in
+ * osmt_last_error(): NULL tables (kern may be NULL when n_kern == 0; cmap when n_cmap == 0) or n_glyphs == 0; cmap or
+ * kern not strictly increasing; a glyph index >= n_glyphs in cmap or kern; |advance| or |kern value| > 65535; an
+ * outline_id that is not in the glyph table (register the outlines first); a code point > 0x10FFFF or in 0xD800-0xDFFF;
+ * ascent - descent == 0. */
+int osmt_register_font(osmt_ctx* ctx, const osmt_font_desc* font, uint32_t* out_font_id);
+/* The checks osmt_scene_set_string_labels runs first, without a device (`ctx` is only asked for its fonts): everything
+ * osmt_validate_text_labels checks — the char ranges in the place of the glyph ranges — plus, as OSMT_INVALID_ARG, an
+ * unknown font_id, a code point that is not a Rust `char` (> 0x10FFFF, or a surrogate) and a font_size that is not finite
+ * or whose scale is not.  A valid code point the font does not have is NOT an error: it shapes to glyph 0 with glyph 0's
+ * advance and outline, as the reference does. */
+int osmt_validate_string_labels(const osmt_string_label_batch* labels, size_t n_jobs, osmt_ctx* ctx);
+/* osmt_scene_set_text_labels with string text: k_text_shape (one lane per char) writes the osmt_text_glyph records,
+ * k_text_place and the count / emit passes run behind it on the same stream, unchanged.  NULL / n_labels == 0 detaches.
+ * Errors: those of osmt_validate_string_labels and everything osmt_scene_set_text_labels reports downstream. */
+int osmt_scene_set_string_labels(osmt_ctx* ctx, osmt_scene* scene, const osmt_string_label_batch* labels);
+/* osmt_render_batch_rgb with string labels: scene, osmt_scene_set_string_labels, render, packed RGB8 out. */
+int osmt_render_batch_rgb_strings(osmt_ctx* ctx, const osmt_batch* batch, const osmt_string_label_batch* labels, uint8_t* out_rgb,
+                                  size_t out_tile_stride_bytes);
+/* Inspection: the records the last osmt_scene_set_string_labels shaped, out = [n] in slot order (n = the batch's
+ * n_chars; slot seg_off + k is char k of its label): exactly what a text-run caller would have uploaded — glyph_id is
+ * the OUTLINE id, kern of a label's first char is 0.  Slots no has_text label names read as zero.  Kept with the scene
+ * like the glyph instances (which osmt_scene_read_glyph_instances returns after a string set call as after a text one),
+ * gone with the next set call; with any other label form attached *n is 0.  *n is always set; out may be NULL to ask for
+ * the size; cap < *n with a non-NULL out is OSMT_INVALID_ARG. */
+int osmt_scene_read_text_glyphs(osmt_ctx* ctx, osmt_scene* scene, osmt_text_glyph* out, size_t cap, size_t* n);
 /* Diagnostics: out[i] = the device hypot of (xy[2i], xy[2i + 1]) — the function the glyph walk flattens curves with. */
 int osmt_debug_hypot(osmt_ctx* ctx, const double* xy, size_t n, double* out);
 

@@ -176,6 +176,59 @@ class TextLabelBatch(C.Structure):
     ]
 
 
+class CmapEntry(C.Structure):
+    _fields_ = [("code_point", C.c_uint32), ("glyph", C.c_uint32)]
+
+
+class KernPair(C.Structure):
+    _fields_ = [("left", C.c_uint32), ("right", C.c_uint32), ("value", C.c_int32)]
+
+
+class FontDesc(C.Structure):
+    _fields_ = [
+        ("cmap", C.POINTER(CmapEntry)),
+        ("n_cmap", C.c_size_t),
+        ("advance", C.POINTER(C.c_int32)),
+        ("outline_id", C.POINTER(C.c_uint32)),
+        ("n_glyphs", C.c_size_t),
+        ("kern", C.POINTER(KernPair)),
+        ("n_kern", C.c_size_t),
+        ("ascent", C.c_int32),
+        ("descent", C.c_int32),
+        ("line_gap", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
+class StringRun(C.Structure):
+    _fields_ = [
+        ("position", C.c_uint32),
+        ("y_offset", C.c_uint32),
+        ("pt_off", C.c_uint32),
+        ("n_pts", C.c_uint32),
+        ("font_id", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("font_size", C.c_double),
+        ("center_x", C.c_double),
+        ("center_y", C.c_double),
+        ("_reserved", C.c_double * 2),
+    ]
+
+
+class StringLabelBatch(C.Structure):
+    _fields_ = [
+        ("labels", C.POINTER(Label)),
+        ("n_labels", C.c_size_t),
+        ("job_label_off", C.POINTER(C.c_uint32)),
+        ("runs", C.POINTER(StringRun)),
+        ("chars", C.POINTER(C.c_uint32)),
+        ("n_chars", C.c_size_t),
+        ("way_pts", C.POINTER(C.c_int32)),
+        ("way_sincos", C.POINTER(C.c_double)),
+        ("n_way_pts", C.c_size_t),
+    ]
+
+
 class LabelRequest(C.Structure):
     _fields_ = [("ring_off", C.c_uint32), ("n_rings", C.c_uint32), ("scale", C.c_double)]
 
@@ -207,5 +260,8 @@ assert C.sizeof(GlyphVertex) == 10
 assert C.sizeof(GlyphInstance) == 64
 assert C.sizeof(TextGlyph) == 16
 assert C.sizeof(TextRun) == 64
+assert C.sizeof(CmapEntry) == 8
+assert C.sizeof(KernPair) == 12
+assert C.sizeof(StringRun) == 64
 assert C.sizeof(LabelRequest) == 16
 assert C.sizeof(LabelPosition) == 24

@@ -16,6 +16,7 @@
 #include <deque>
 #include <dlfcn.h>
 
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <new>
@@ -27,6 +28,7 @@
 #include "osmt_internal.h"
 #include "osmt_png_table.h" /* PNG_LMAX, PNG_BLOCK_HDR_BITS: the slot bound */
 #include "../host/osmt_textplacer.hpp" /* osmt::validate_text_labels */
+#include "../host/osmt_textshaper.hpp" /* osmt::validate_font, osmt::validate_string_labels */
 
 namespace {
 
@@ -109,6 +111,23 @@ struct osmt_ctx {
     uint32_t* d_glyph_voff = nullptr;
     uint32_t d_n_glyphs = 0;
     bool glyphs_dirty = false;
+    /* the fonts of osmt_register_font (string labels).  The host copies serve the validation (metrics, table sizes) and
+     * the upload; a font's tables get ONE device allocation at their first use and never move, so only the array of
+     * osmt_font_dev records is replaced when a font is appended — the old array joins image_graveyard, and a launch
+     * that holds it keeps reading valid records of valid tables */
+    struct font_host {
+        std::vector<osmt_cmap_entry> cmap;
+        std::vector<int32_t> advance;
+        std::vector<uint32_t> outline;
+        std::vector<osmt_kern_pair> kern;
+        osmt_font_desc view{}; /* over the vectors above */
+        void* d_pool = nullptr;
+        osmt_font_dev dev{};
+    };
+    std::vector<std::shared_ptr<font_host>> fonts;
+    osmt_font_dev* d_fonts = nullptr;
+    uint32_t d_n_fonts = 0;
+    bool fonts_dirty = false;
     /* one reference for the handle returned by osmt_create + one per live scene: osmt_destroy on a context that still
      * has scenes only drops the handle's reference, the last osmt_scene_free tears the context down */
     std::atomic<int> refs{1};
@@ -213,6 +232,10 @@ struct osmt_scene {
      * osmt_scene_read_glyph_instances; an allocation of its own, gone with the next set call */
     osmt_glyph_instance* d_text_inst = nullptr;
     uint32_t n_text_inst = 0;
+    /* string labels (osmt_scene_set_string_labels): the records k_text_shape wrote and k_text_place read, kept for
+     * osmt_scene_read_text_glyphs under the same rules */
+    osmt_text_glyph* d_text_glyphs = nullptr;
+    uint32_t n_text_glyphs = 0;
 };
 
 namespace {
@@ -495,6 +518,64 @@ int sync_glyphs(osmt_ctx* ctx, glyph_snapshot* snap) {
     return OSMT_OK;
 }
 
+struct font_snapshot {
+    const osmt_font_dev* fonts = nullptr;
+    uint32_t n = 0;
+};
+
+/* Brings the device copy of the font table up to date: the tables of fonts not yet uploaded, then a new array of records
+ * if one was added.  The snapshot stays valid for the life of the context. */
+int sync_fonts(osmt_ctx* ctx, font_snapshot* snap) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->fonts_dirty) {
+        for (auto& fp : ctx->fonts) {
+            osmt_ctx::font_host& f = *fp;
+            if (f.d_pool) continue;
+            const size_t b_cmap = f.cmap.size() * sizeof(osmt_cmap_entry), b_adv = f.advance.size() * 4, b_out = f.outline.size() * 4;
+            const size_t b_kern = f.kern.size() * sizeof(osmt_kern_pair);
+            const size_t o_cmap = 0, o_adv = align_up(o_cmap + b_cmap, 256), o_out = align_up(o_adv + b_adv, 256), o_kern = align_up(o_out + b_out, 256);
+            char* pool = nullptr;
+            HIP_TRY(hipMalloc((void**)&pool, o_kern + std::max<size_t>(b_kern, 4)));
+            hipError_t e = b_cmap ? hipMemcpy(pool + o_cmap, f.cmap.data(), b_cmap, hipMemcpyHostToDevice) : hipSuccess;
+            if (e == hipSuccess) e = hipMemcpy(pool + o_adv, f.advance.data(), b_adv, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(pool + o_out, f.outline.data(), b_out, hipMemcpyHostToDevice);
+            if (e == hipSuccess && b_kern) e = hipMemcpy(pool + o_kern, f.kern.data(), b_kern, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipFree(pool);
+                return fail(OSMT_HIP_ERROR, "font table upload failed: %s", hipGetErrorString(e));
+            }
+            f.d_pool = pool;
+            f.dev.cmap = (const osmt_cmap_entry*)(pool + o_cmap);
+            f.dev.advance = (const int32_t*)(pool + o_adv);
+            f.dev.outline = (const uint32_t*)(pool + o_out);
+            f.dev.kern = b_kern ? (const osmt_kern_pair*)(pool + o_kern) : nullptr;
+            f.dev.n_cmap = (uint32_t)f.cmap.size();
+            f.dev.n_kern = (uint32_t)f.kern.size();
+            f.dev.n_glyphs = (uint32_t)f.advance.size();
+        }
+        std::vector<osmt_font_dev> recs;
+        for (const auto& fp : ctx->fonts) recs.push_back(fp->dev);
+        osmt_font_dev* nd = nullptr;
+        HIP_TRY(hipMalloc((void**)&nd, std::max<size_t>(recs.size(), 1) * sizeof(osmt_font_dev)));
+        if (!recs.empty()) {
+            const hipError_t e = hipMemcpy(nd, recs.data(), recs.size() * sizeof(osmt_font_dev), hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipFree(nd);
+                return fail(OSMT_HIP_ERROR, "font table upload failed: %s", hipGetErrorString(e));
+            }
+        }
+        if (ctx->d_fonts) ctx->image_graveyard.push_back(ctx->d_fonts);
+        ctx->d_fonts = nd;
+        ctx->d_n_fonts = (uint32_t)recs.size();
+        ctx->fonts_dirty = false;
+    }
+    if (snap) {
+        snap->fonts = ctx->d_fonts;
+        snap->n = ctx->d_n_fonts;
+    }
+    return OSMT_OK;
+}
+
 void comm_destroy(osmt_ctx* ctx);
 
 void ctx_teardown(osmt_ctx* ctx) {
@@ -504,6 +585,9 @@ void ctx_teardown(osmt_ctx* ctx) {
     if (ctx->d_image_pool) (void)hipFree(ctx->d_image_pool);
     if (ctx->d_glyph_verts) (void)hipFree(ctx->d_glyph_verts);
     if (ctx->d_glyph_voff) (void)hipFree(ctx->d_glyph_voff);
+    if (ctx->d_fonts) (void)hipFree(ctx->d_fonts);
+    for (auto& f : ctx->fonts)
+        if (f->d_pool) (void)hipFree(f->d_pool);
     for (void* p : ctx->image_graveyard) (void)hipFree(p);
     for (auto& c : ctx->cache) (void)hipFree(c.p);
     for (hipStream_t st : ctx->idle_streams) (void)hipStreamDestroy(st);
@@ -975,6 +1059,45 @@ static int osmt_register_glyphs_body(osmt_ctx* ctx, const osmt_glyph_vertex* v, 
 
 int osmt_register_glyphs(osmt_ctx* ctx, const osmt_glyph_vertex* v, const uint32_t* vertex_off, uint32_t n_glyphs, uint32_t* out_first_id) {
     return guarded([&] { return osmt_register_glyphs_body(ctx, v, vertex_off, n_glyphs, out_first_id); });
+}
+
+static int osmt_register_font_body(osmt_ctx* ctx, const osmt_font_desc* font, uint32_t* out_id) {
+    if (!ctx || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    std::string why;
+    const int rc = osmt::validate_font(font, ctx->glyph_voff.size() - 1, &why); /* the glyph table is append-only: an id once valid stays valid */
+    if (rc != OSMT_OK) return fail(rc, "%s", why.c_str());
+    if (ctx->fonts.size() + 1 >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "font table too large");
+    auto f = std::make_shared<osmt_ctx::font_host>();
+    f->cmap.assign(font->cmap, font->cmap + font->n_cmap);
+    f->advance.assign(font->advance, font->advance + font->n_glyphs);
+    f->outline.assign(font->outline_id, font->outline_id + font->n_glyphs);
+    if (font->n_kern) f->kern.assign(font->kern, font->kern + font->n_kern);
+    f->view = *font;
+    f->view.cmap = f->cmap.data();
+    f->view.advance = f->advance.data();
+    f->view.outline_id = f->outline.data();
+    f->view.kern = f->kern.empty() ? nullptr : f->kern.data();
+    *out_id = (uint32_t)ctx->fonts.size();
+    ctx->fonts.push_back(std::move(f));
+    ctx->fonts_dirty = true;
+    return OSMT_OK;
+}
+
+int osmt_register_font(osmt_ctx* ctx, const osmt_font_desc* font, uint32_t* out_font_id) {
+    return guarded([&] { return osmt_register_font_body(ctx, font, out_font_id); });
+}
+
+/* The fonts registered so far, as osmt::validate_string_labels takes them; `keep` holds them alive (a font is never
+ * removed, but the vector may grow under another thread). */
+static std::vector<const osmt_font_desc*> font_views(osmt_ctx* ctx, std::vector<std::shared_ptr<osmt_ctx::font_host>>* keep) {
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        *keep = ctx->fonts;
+    }
+    std::vector<const osmt_font_desc*> v;
+    for (const auto& f : *keep) v.push_back(&f->view);
+    return v;
 }
 
 /* The pre-pass writes into two arenas whose sizes depend on the PROJECTED geometry (how many sub-tiles every op
@@ -1469,6 +1592,7 @@ void osmt_scene_free(osmt_scene* s) {
     dev_free(s->ctx, s->d_arena);
     dev_free(s->ctx, s->d_lab_base);
     dev_free(s->ctx, s->d_text_inst);
+    dev_free(s->ctx, s->d_text_glyphs);
     stage_release(s->ctx, s->h_stage);
     scene_delete(s);
 }
@@ -1477,12 +1601,21 @@ void osmt_scene_free(osmt_scene* s) {
  * count pass and reads back each label's window summary (osmt_label_extent, ~20 bytes per label) and the error word.
  * *gtmp: the device buffer the emit pass still needs (the caller frees it after synchronising `st`).
  * Exactly one of gb (instances from the host) and tb (text runs: k_text_place writes the instances into sc->d_text_inst,
- * in front of the count pass on the same stream; tb has passed osmt::validate_text_labels) is given. */
+ * in front of the count pass on the same stream; tb has passed osmt::validate_text_labels) is given.
+ * String labels come as tb too — the runs the validation built, tb->glyphs NULL, tb->n_glyphs the number of chars — with
+ * the code points (chars) and the font id of every label (label_font): k_text_shape writes the records k_text_place
+ * reads into sc->d_text_glyphs, in front of it on the same stream. */
 static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_label_batch* gb, const osmt_text_label_batch* tb, hipStream_t st,
-                              char** gtmp, osmt_glyph_pass* gp, std::vector<osmt_label_extent>& ext) {
+                              char** gtmp, osmt_glyph_pass* gp, std::vector<osmt_label_extent>& ext, const uint32_t* chars = nullptr,
+                              const uint32_t* label_font = nullptr) {
     glyph_snapshot snap;
     {
         const int rc = sync_glyphs(ctx, &snap);
+        if (rc != OSMT_OK) return rc;
+    }
+    font_snapshot fsnap;
+    if (label_font) {
+        const int rc = sync_fonts(ctx, &fsnap);
         if (rc != OSMT_OK) return rc;
     }
     const osmt_label* const labels = gb ? gb->labels : tb->labels;
@@ -1503,7 +1636,7 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
         if ((size_t)in.seg_off + in.n_segs > n_glyphs) return fail(OSMT_INVALID_ARG, "label %zu: glyph instance range out of bounds", l);
         if (pair_inst.size() + in.n_segs >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "too many glyph instances");
         for (uint32_t k = 0; k < in.n_segs; ++k) {
-            if (tb && tb->glyphs[(size_t)in.seg_off + k].glyph_id >= snap.n)
+            if (tb && !label_font && tb->glyphs[(size_t)in.seg_off + k].glyph_id >= snap.n)
                 return fail(OSMT_INVALID_ARG, "label %zu, glyph %u: glyph id %u is not in the glyph table (%u glyphs)", l, k,
                             tb->glyphs[(size_t)in.seg_off + k].glyph_id, snap.n);
             pair_inst.push_back(in.seg_off + k);
@@ -1521,7 +1654,9 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
     /* text runs: what k_text_place reads */
     const size_t n_way = tb ? tb->n_way_pts : 0;
     const size_t o_tlab = carve(tb ? n_labels * sizeof(osmt_label) : 0), o_trun = carve(tb ? n_labels * sizeof(osmt_text_run) : 0);
-    const size_t o_tgl = carve(tb ? n_glyphs * sizeof(osmt_text_glyph) : 0), o_twp = carve(n_way * 8), o_tws = carve(n_way * 16);
+    const size_t o_tgl = carve(tb && !label_font ? n_glyphs * sizeof(osmt_text_glyph) : 0), o_twp = carve(n_way * 8), o_tws = carve(n_way * 16);
+    /* string labels: what k_text_shape reads */
+    const size_t o_chr = carve(label_font ? n_glyphs * 4 : 0), o_lfn = carve(label_font ? n_labels * 4 : 0);
     const size_t o_pi = carve(n_pairs * 4), o_pl = carve(n_pairs * 4), o_pc = carve(n_pairs * 4), o_pb = carve(n_pairs * 4);
     const size_t o_blk = carve((n_pairs / 1024 + 1) * 4);
     const size_t o_sum = carve(n_labels * sizeof(osmt_label_extent) + 4); /* the error word right behind: one read-back */
@@ -1545,18 +1680,43 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
     gp->pair_base = (uint32_t*)(base + o_pb);
     gp->blk = (uint32_t*)(base + o_blk);
     if (gb && n_glyphs) HIP_TRY(hipMemcpyAsync(base + o_inst, gb->glyphs, n_glyphs * sizeof(osmt_glyph_instance), hipMemcpyHostToDevice, st));
+    if (n_pairs) {
+        HIP_TRY(hipMemcpyAsync(base + o_pi, pair_inst.data(), n_pairs * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(base + o_pl, pair_label.data(), n_pairs * 4, hipMemcpyHostToDevice, st));
+    }
     if (tb) {
         osmt_text_pass tp{};
         tp.labels = (const osmt_label*)(base + o_tlab);
         tp.n_labels = (uint32_t)n_labels;
         tp.runs = (const osmt_text_run*)(base + o_trun);
-        tp.glyphs = (const osmt_text_glyph*)(base + o_tgl);
+        if (label_font) { /* the records outlive this call (osmt_scene_read_text_glyphs) */
+            HIP_TRY(dev_alloc(ctx, (void**)&sc->d_text_glyphs, std::max<size_t>(n_glyphs, 1) * sizeof(osmt_text_glyph)));
+            tp.glyphs = sc->d_text_glyphs;
+        } else {
+            tp.glyphs = (const osmt_text_glyph*)(base + o_tgl);
+        }
         tp.way_pts = (const int32_t*)(base + o_twp);
         tp.way_sincos = (const double*)(base + o_tws);
         tp.inst = sc->d_text_inst;
         HIP_TRY(hipMemcpyAsync(base + o_tlab, tb->labels, n_labels * sizeof(osmt_label), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(base + o_trun, tb->runs, n_labels * sizeof(osmt_text_run), hipMemcpyHostToDevice, st));
-        if (n_glyphs) HIP_TRY(hipMemcpyAsync(base + o_tgl, tb->glyphs, n_glyphs * sizeof(osmt_text_glyph), hipMemcpyHostToDevice, st));
+        if (n_glyphs && !label_font) HIP_TRY(hipMemcpyAsync(base + o_tgl, tb->glyphs, n_glyphs * sizeof(osmt_text_glyph), hipMemcpyHostToDevice, st));
+        if (label_font) {
+            osmt_shape_pass sp{};
+            sp.labels = tp.labels;
+            sp.label_font = (const uint32_t*)(base + o_lfn);
+            sp.pair_inst = gp->pair_inst;
+            sp.pair_label = gp->pair_label;
+            sp.n_pairs = gp->n_pairs;
+            sp.chars = (const uint32_t*)(base + o_chr);
+            sp.fonts = fsnap.fonts;
+            sp.out = sc->d_text_glyphs;
+            if (n_glyphs) HIP_TRY(hipMemcpyAsync(base + o_chr, chars, n_glyphs * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(base + o_lfn, label_font, n_labels * 4, hipMemcpyHostToDevice, st));
+            /* slots no label with text names read as zero */
+            HIP_TRY(hipMemsetAsync(sc->d_text_glyphs, 0, std::max<size_t>(n_glyphs, 1) * sizeof(osmt_text_glyph), st));
+            HIP_TRY(osmt_launch_text_shape(sp, st));
+        }
         if (n_way) {
             HIP_TRY(hipMemcpyAsync(base + o_twp, tb->way_pts, n_way * 8, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(base + o_tws, tb->way_sincos, n_way * 16, hipMemcpyHostToDevice, st));
@@ -1564,10 +1724,6 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
         /* slots no label with text names read as zero */
         HIP_TRY(hipMemsetAsync(sc->d_text_inst, 0, std::max<size_t>(n_glyphs, 1) * sizeof(osmt_glyph_instance), st));
         HIP_TRY(osmt_launch_text_place(tp, st));
-    }
-    if (n_pairs) {
-        HIP_TRY(hipMemcpyAsync(base + o_pi, pair_inst.data(), n_pairs * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(base + o_pl, pair_label.data(), n_pairs * 4, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(osmt_launch_glyph_count(*gp, (uint32_t)n_labels, st));
     std::vector<char> back(n_labels * sizeof(osmt_label_extent) + 4);
@@ -1590,7 +1746,7 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
  * rounding of eval_x_at_y, font/rasterizer.rs:37).  Exactly one of lb (draw_line calls from the host) and gb (glyph
  * runs, expanded on the device) is used; both feed the same per-label summaries (osmt_label_extent) to the window code. */
 static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_label_batch* lb, const osmt_glyph_label_batch* gb = nullptr,
-                                      const osmt_text_label_batch* tb = nullptr) {
+                                      const osmt_text_label_batch* tb = nullptr, const osmt_string_label_batch* sb = nullptr) {
     if (!ctx || !sc || sc->ctx != ctx) return fail(OSMT_INVALID_ARG, "bad ctx/scene");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = sc->own_stream;
@@ -1617,11 +1773,38 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
     dev_free(ctx, sc->d_text_inst);
     sc->d_text_inst = nullptr;
     sc->n_text_inst = 0;
+    dev_free(ctx, sc->d_text_glyphs);
+    sc->d_text_glyphs = nullptr;
+    sc->n_text_glyphs = 0;
+    /* string labels: validated here, then carried as text runs whose glyph records the device writes itself */
+    std::vector<osmt_text_run> s_runs;
+    std::vector<uint32_t> s_font;
+    osmt_text_label_batch s_tb{};
+    if (sb) {
+        if (sb->n_labels == 0) return OSMT_OK;
+        std::vector<std::shared_ptr<osmt_ctx::font_host>> keep;
+        const std::vector<const osmt_font_desc*> fonts = font_views(ctx, &keep);
+        std::string why;
+        const int rc = osmt::validate_string_labels(sb, sc->n_jobs, fonts.data(), fonts.size(), &why, &s_runs);
+        if (rc != OSMT_OK) return fail(rc, "%s", why.c_str());
+        s_font.assign(sb->n_labels, 0u);
+        for (size_t l = 0; l < sb->n_labels; ++l)
+            if (sb->labels[l].has_text) s_font[l] = sb->runs[l].font_id;
+        s_tb.labels = sb->labels;
+        s_tb.n_labels = sb->n_labels;
+        s_tb.job_label_off = sb->job_label_off;
+        s_tb.runs = s_runs.data();
+        s_tb.n_glyphs = sb->n_chars;
+        s_tb.way_pts = sb->way_pts;
+        s_tb.way_sincos = sb->way_sincos;
+        s_tb.n_way_pts = sb->n_way_pts;
+        tb = &s_tb;
+    }
     const osmt_label* const labels = lb ? lb->labels : gb ? gb->labels : tb ? tb->labels : nullptr;
     const size_t n_labels = lb ? lb->n_labels : gb ? gb->n_labels : tb ? tb->n_labels : 0;
     const uint32_t* const job_label_off = lb ? lb->job_label_off : gb ? gb->job_label_off : tb ? tb->job_label_off : nullptr;
     if (n_labels == 0) return OSMT_OK;
-    if (tb) {
+    if (tb && !sb) {
         std::string why;
         const int rc = osmt::validate_text_labels(tb, sc->n_jobs, &why);
         if (rc != OSMT_OK) return fail(rc, "%s", why.c_str());
@@ -1661,16 +1844,18 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
         hipStream_t st;
         bool keep;
         ~inst_guard() {
-            if (!keep && s->d_text_inst) {
+            if (!keep && (s->d_text_inst || s->d_text_glyphs)) {
                 (void)hipStreamSynchronize(st);
                 dev_free(c, s->d_text_inst);
+                dev_free(c, s->d_text_glyphs);
                 s->d_text_inst = nullptr;
+                s->d_text_glyphs = nullptr;
             }
         }
     } text_inst{ctx, sc, st, false};
     size_t n_segs_total = lb ? lb->n_segs : 0;
     if (!lb) {
-        const int rc = glyph_labels_count(ctx, sc, gb, tb, st, &gtmp.p, &gp, gext);
+        const int rc = glyph_labels_count(ctx, sc, gb, tb, st, &gtmp.p, &gp, gext, sb ? sb->chars : nullptr, sb ? s_font.data() : nullptr);
         if (rc != OSMT_OK) return rc;
         gseg_off.resize(n_labels);
         for (size_t l = 0; l < n_labels; ++l) {
@@ -1856,6 +2041,7 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
     sc->n_label_segs = (uint32_t)n_segs_total;
     if (tb) {
         sc->n_text_inst = (uint32_t)tb->n_glyphs;
+        if (sb) sc->n_text_glyphs = (uint32_t)sb->n_chars;
         text_inst.keep = true;
     }
     return OSMT_OK;
@@ -1879,6 +2065,37 @@ int osmt_validate_text_labels(const osmt_text_label_batch* tb, size_t n_jobs) {
         const int rc = osmt::validate_text_labels(tb, n_jobs, &why);
         return rc == OSMT_OK ? OSMT_OK : fail(rc, "%s", why.c_str());
     });
+}
+
+int osmt_scene_set_string_labels(osmt_ctx* ctx, osmt_scene* sc, const osmt_string_label_batch* sb) {
+    if (!sb) return osmt_scene_set_text_labels(ctx, sc, nullptr);
+    return guarded([&] { return osmt_scene_set_labels_body(ctx, sc, nullptr, nullptr, nullptr, sb); });
+}
+
+int osmt_validate_string_labels(const osmt_string_label_batch* sb, size_t n_jobs, osmt_ctx* ctx) {
+    return guarded([&] {
+        if (!ctx) return fail(OSMT_INVALID_ARG, "NULL context");
+        std::vector<std::shared_ptr<osmt_ctx::font_host>> keep;
+        const std::vector<const osmt_font_desc*> fonts = font_views(ctx, &keep);
+        std::string why;
+        const int rc = osmt::validate_string_labels(sb, n_jobs, fonts.data(), fonts.size(), &why);
+        return rc == OSMT_OK ? OSMT_OK : fail(rc, "%s", why.c_str());
+    });
+}
+
+static int osmt_scene_read_text_glyphs_body(osmt_ctx* ctx, osmt_scene* sc, osmt_text_glyph* out, size_t cap, size_t* n) {
+    if (!ctx || !sc || sc->ctx != ctx || !n) return fail(OSMT_INVALID_ARG, "NULL argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(scene_wait_idle(sc));
+    *n = sc->n_labels && sc->d_text_glyphs ? sc->n_text_glyphs : 0;
+    if (!out) return OSMT_OK;
+    if (cap < *n) return fail(OSMT_INVALID_ARG, "out holds %zu text glyphs, the scene has %zu", cap, *n);
+    if (*n) HIP_TRY(copy_back(ctx, out, sc->d_text_glyphs, *n * sizeof(osmt_text_glyph)));
+    return OSMT_OK;
+}
+
+int osmt_scene_read_text_glyphs(osmt_ctx* ctx, osmt_scene* sc, osmt_text_glyph* out, size_t cap, size_t* n) {
+    return guarded([&] { return osmt_scene_read_text_glyphs_body(ctx, sc, out, cap, n); });
 }
 
 static int osmt_scene_read_glyph_instances_body(osmt_ctx* ctx, osmt_scene* sc, osmt_glyph_instance* out, size_t cap, size_t* n) {
@@ -2189,24 +2406,24 @@ int osmt_render_batch(osmt_ctx* ctx, const osmt_batch* batch, uint8_t* out_rgba,
 
 static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba, size_t stride,
                                          bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels,
-                                         const osmt_text_label_batch* tlabels);
+                                         const osmt_text_label_batch* tlabels, const osmt_string_label_batch* slabels);
 
 /* the host-buffer render: arenas guessed from the recent densities first; a miss renders again with exact sizing */
 static int osmt_render_batch_labels_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,
                                          size_t stride, bool rgb = false, bool trusted = false, const osmt_glyph_label_batch* glabels = nullptr,
-                                         const osmt_text_label_batch* tlabels = nullptr) {
+                                         const osmt_text_label_batch* tlabels = nullptr, const osmt_string_label_batch* slabels = nullptr) {
     g_arena_guess_missed = false;
-    int rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, trusted, true, glabels, tlabels);
+    int rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, trusted, true, glabels, tlabels, slabels);
     if (rc != OSMT_OK && g_arena_guess_missed) {
         g_arena_guess_missed = false;
-        rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, true, false, glabels, tlabels); /* validated the first time */
+        rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, true, false, glabels, tlabels, slabels); /* validated the first time */
     }
     return rc;
 }
 
 static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba, size_t stride,
                                          bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels,
-                                         const osmt_text_label_batch* tlabels) {
+                                         const osmt_text_label_batch* tlabels, const osmt_string_label_batch* slabels) {
     if (!ctx || !out_rgba) return fail(OSMT_INVALID_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = nullptr; /* the whole call lives on its own stream: concurrent callers overlap on the GPU */
@@ -2217,9 +2434,10 @@ static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch,
         stream_release(ctx, st);
         return rc;
     }
-    if (labels || glabels || tlabels) {
+    if (labels || glabels || tlabels || slabels) {
         rc = labels ? osmt_scene_set_labels(ctx, sc, labels)
-                    : glabels ? osmt_scene_set_glyph_labels(ctx, sc, glabels) : osmt_scene_set_text_labels(ctx, sc, tlabels);
+                    : glabels ? osmt_scene_set_glyph_labels(ctx, sc, glabels)
+                              : tlabels ? osmt_scene_set_text_labels(ctx, sc, tlabels) : osmt_scene_set_string_labels(ctx, sc, slabels);
         if (rc != OSMT_OK) {
             osmt_scene_free(sc);
             stream_release(ctx, st);
@@ -2361,6 +2579,10 @@ int osmt_render_batch_rgb_glyphs(osmt_ctx* ctx, const osmt_batch* batch, const o
 
 int osmt_render_batch_rgb_text(osmt_ctx* ctx, const osmt_batch* batch, const osmt_text_label_batch* labels, uint8_t* out_rgb, size_t stride) {
     return guarded([&] { return osmt_render_batch_labels_body(ctx, batch, nullptr, out_rgb, stride, true, false, nullptr, labels); });
+}
+
+int osmt_render_batch_rgb_strings(osmt_ctx* ctx, const osmt_batch* batch, const osmt_string_label_batch* labels, uint8_t* out_rgb, size_t stride) {
+    return guarded([&] { return osmt_render_batch_labels_body(ctx, batch, nullptr, out_rgb, stride, true, false, nullptr, nullptr, labels); });
 }
 
 int osmt_render_batch_labels(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,

@@ -394,6 +394,28 @@ struct osmt_text_pass {
 };
 /* k_text_place: TextPlacer::place of every label with text, glyph instances into a.inst */
 hipError_t osmt_launch_text_place(const osmt_text_pass& a, hipStream_t st);
+/* string labels (osmt_textshape.hip): a registered font as the kernel reads it.  The tables of a font are uploaded once
+ * and never move; only the array of these records is replaced when a font is appended. */
+struct osmt_font_dev {
+    const osmt_cmap_entry* cmap;
+    const int32_t* advance;     /* [n_glyphs] */
+    const uint32_t* outline;    /* [n_glyphs] ids in the glyph table */
+    const osmt_kern_pair* kern; /* NULL when n_kern == 0 */
+    uint32_t n_cmap, n_kern, n_glyphs, _pad;
+};
+/* one char per lane, over the (slot, label) pairs of the glyph expansion; the batch has passed osmt::validate_string_labels */
+struct osmt_shape_pass {
+    const osmt_label* labels;
+    const uint32_t* label_font; /* [n_labels] font id (read for the labels the pairs name) */
+    const uint32_t* pair_inst;  /* [n_pairs] slot of the pair = index into chars and out */
+    const uint32_t* pair_label; /* [n_pairs] its label */
+    uint32_t n_pairs;
+    const uint32_t* chars;
+    const osmt_font_dev* fonts; /* the context's font table snapshot */
+    osmt_text_glyph* out;       /* slot seg_off + k = char k of its label */
+};
+/* k_text_shape: TextPlacer::text_to_glyphs of every label with text, osmt_text_glyph records into a.out */
+hipError_t osmt_launch_text_shape(const osmt_shape_pass& a, hipStream_t st);
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

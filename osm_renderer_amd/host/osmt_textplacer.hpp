@@ -171,9 +171,12 @@ inline void place_text_labels(const osmt_text_label_batch& b, osmt_glyph_instanc
     }
 }
 
-/* What osmt_validate_text_labels checks (the list is in include/osmtile.h).  Returns an OSMT_* status; *why gets the
- * reason. */
-inline int validate_text_labels(const osmt_text_label_batch* b, size_t n_jobs, std::string* why) {
+namespace textplacer_detail {
+
+/* The body of validate_text_labels.  have_glyphs == false: the batch is the placement half of a string-label batch
+ * (host/osmt_textshaper.hpp) — b->glyphs is not there yet (the device shapes it), b->n_glyphs is the number of chars, and
+ * the limits on advance and kern were checked when the font was registered. */
+inline int validate_runs(const osmt_text_label_batch* b, size_t n_jobs, std::string* why, bool have_glyphs) {
     char buf[256];
     auto bad = [&](int code, const char* fmt, auto... a) {
         std::snprintf(buf, sizeof buf, fmt, a...);
@@ -182,7 +185,7 @@ inline int validate_text_labels(const osmt_text_label_batch* b, size_t n_jobs, s
     };
     if (!b) return bad(OSMT_INVALID_ARG, "%s", "NULL text label batch");
     if (b->n_labels == 0) return OSMT_OK;
-    if (!b->labels || !b->job_label_off || !b->runs || (b->n_glyphs && !b->glyphs) || (b->n_way_pts && (!b->way_pts || !b->way_sincos)))
+    if (!b->labels || !b->job_label_off || !b->runs || (have_glyphs && b->n_glyphs && !b->glyphs) || (b->n_way_pts && (!b->way_pts || !b->way_sincos)))
         return bad(OSMT_INVALID_ARG, "%s", "NULL text label pool");
     if (b->n_labels >= 0xFFFFFFFFull || b->n_glyphs >= 0xFFFFFFFFull || b->n_way_pts >= 0xFFFFFFFFull)
         return bad(OSMT_INVALID_ARG, "%s", "text label batch too large");
@@ -200,7 +203,7 @@ inline int validate_text_labels(const osmt_text_label_batch* b, size_t n_jobs, s
         if (r.position != OSMT_TEXT_CENTER && r.position != OSMT_TEXT_LINE)
             return bad(OSMT_INVALID_ARG, "label %zu: unknown text position %u", l, r.position);
         if (!std::isfinite(r.scale)) return bad(OSMT_INVALID_ARG, "label %zu: scale is not finite", l);
-        for (uint32_t k = 0; k < in.n_segs; ++k) {
+        for (uint32_t k = 0; have_glyphs && k < in.n_segs; ++k) {
             const osmt_text_glyph& g = b->glyphs[(size_t)in.seg_off + k];
             if (g.advance > 65535 || g.advance < -65535 || g.kern > 65535 || g.kern < -65535)
                 return bad(OSMT_INVALID_ARG, "label %zu, glyph %u: |advance| or |kern| > 65535", l, k);
@@ -231,6 +234,14 @@ inline int validate_text_labels(const osmt_text_label_batch* b, size_t n_jobs, s
         if ((uint64_t)slots[i - 1].first + slots[i - 1].second > slots[i].first)
             return bad(OSMT_INVALID_ARG, "the glyph ranges of two labels overlap at glyph %u", slots[i].first);
     return OSMT_OK;
+}
+
+}  // namespace textplacer_detail
+
+/* What osmt_validate_text_labels checks (the list is in include/osmtile.h).  Returns an OSMT_* status; *why gets the
+ * reason. */
+inline int validate_text_labels(const osmt_text_label_batch* b, size_t n_jobs, std::string* why) {
+    return textplacer_detail::validate_runs(b, n_jobs, why, true);
 }
 
 }  // namespace osmt

@@ -618,11 +618,14 @@ def synth_way(rng, cx, cy, n_pts, step):
 
 
 def make_text_labels(n_tiles, table, labels_per_tile=24, scale=1, seed=7, n_images=0, image_sizes=None, text_frac=0.85,
-                     icon_frac=0.4, line_frac=0.3, empty_frac=0.03):
+                     icon_frac=0.4, line_frac=0.3, empty_frac=0.03, f32_scale=False, _font_px=None):
     """The label workload of make_glyph_labels as text runs: what TextPlacer::place is GIVEN instead of what it
     computes.  Multi-word texts over SYNTH_GLYPHS with kerns (the centred ones wrap into rows at MAX_TEXT_WIDTH), ways
     of 2..40 points with bends (some too short for their text: place() skips those; now and then a way of one point
-    or none), icons whose half height becomes y_offset, labels without text and texts of zero glyphs (empty_frac)."""
+    or none), icons whose half height becomes y_offset, labels without text and texts of zero glyphs (empty_frac).
+    f32_scale: the run's scale is the f32 quotient scale_for_pixel_height computes, widened (what the string form derives
+    from a font size) instead of the f64 quotient; nothing else changes.  _font_px: a list that receives the font size
+    of every label (0.0 without text), for make_string_labels."""
     rng = np.random.default_rng(seed)
     W = 256 * scale
     lists = []
@@ -633,7 +636,7 @@ def make_text_labels(n_tiles, table, labels_per_tile=24, scale=1, seed=7, n_imag
             l, r = np.zeros((), LABEL_DTYPE), np.zeros((), TEXT_RUN_DTYPE)
             cx = float(rng.integers(-W // 2, W + W // 2)) + float(rng.integers(0, 2)) * 0.5
             cy = float(rng.integers(-W // 2, W + W // 2)) + float(rng.integers(0, 4)) * 0.25
-            y_off = 0
+            y_off, font_px = 0, 0.0
             if n_images and rng.random() < icon_frac:
                 img = int(rng.integers(0, n_images))
                 l["has_icon"], l["image_id"] = 1, img
@@ -643,7 +646,7 @@ def make_text_labels(n_tiles, table, labels_per_tile=24, scale=1, seed=7, n_imag
                 l["has_text"] = 1
                 l["text_color"] = [int(v) for v in rng.integers(0, 256, size=3)]
                 font_px = float(rng.choice([9.0, 10.0, 11.0, 12.0, 14.0])) * scale
-                r["scale"] = font_px / 1000.0
+                r["scale"] = float(np.float32(font_px) / np.float32(1000.0)) if f32_scale else font_px / 1000.0
                 r["ascent"], r["descent"], r["line_gap"] = int(_SYNTH_ASCENT), int(_SYNTH_DESCENT), int(_SYNTH_GAP)
                 text = np.zeros(0, TEXT_GLYPH_DTYPE) if rng.random() < empty_frac else synth_text_glyphs(rng, table, int(rng.integers(1, 5)))
                 if rng.random() < line_frac:
@@ -661,6 +664,8 @@ def make_text_labels(n_tiles, table, labels_per_tile=24, scale=1, seed=7, n_imag
                 l["seg_off"], l["n_segs"] = (n_gl if len(text) else 0), len(text)
                 glyphs.append(text)
                 n_gl += len(text)
+            if _font_px is not None:
+                _font_px.append(font_px if l["has_text"] else 0.0)
             labs.append(l)
             runs.append(r)
         way_pts = np.concatenate(pts) if pts else np.zeros((0, 2), np.int32)
@@ -668,3 +673,253 @@ def make_text_labels(n_tiles, table, labels_per_tile=24, scale=1, seed=7, n_imag
         lists.append(TextLabelList(np.array(labs, dtype=LABEL_DTYPE), [0, len(labs)], np.array(runs, dtype=TEXT_RUN_DTYPE),
                                    np.concatenate(glyphs) if glyphs else np.zeros(0, TEXT_GLYPH_DTYPE), way_pts, sincos))
     return concat_text_labels(lists)
+
+
+# ---- string labels (osmt_string_label_batch) -------------------------------------------------------
+STRING_RUN_DTYPE = np.dtype([("position", "<u4"), ("y_offset", "<u4"), ("pt_off", "<u4"), ("n_pts", "<u4"), ("font_id", "<u4"),
+                             ("_pad", "<u4"), ("font_size", "<f8"), ("center_x", "<f8"), ("center_y", "<f8"), ("_reserved", "<f8", (2,))])
+CMAP_DTYPE = np.dtype([("code_point", "<u4"), ("glyph", "<u4")])
+KERN_DTYPE = np.dtype([("left", "<u4"), ("right", "<u4"), ("value", "<i4")])
+assert STRING_RUN_DTYPE.itemsize == C.sizeof(abi.StringRun) == 64
+assert CMAP_DTYPE.itemsize == C.sizeof(abi.CmapEntry) == 8 and KERN_DTYPE.itemsize == C.sizeof(abi.KernPair) == 12
+
+# char::is_whitespace of Rust: the Unicode White_Space set (not str.isspace: U+001C-001F are not in it)
+WHITE_SPACE = frozenset(list(range(0x09, 0x0E)) + [0x20, 0x85, 0xA0, 0x1680] + list(range(0x2000, 0x200B)) + [0x2028, 0x2029, 0x202F, 0x205F, 0x3000])
+
+
+class FontTable:
+    """The flat tables of one font as osmt_register_font takes them (osmt_font_desc): `cmap` [(code point, glyph)] rising
+    in code point, `advance` and `outline_id` per glyph index (outline ids as Context.register_glyphs assigned them),
+    `kern` [(left, right, value)] rising in (left, right), and the v-metrics.  Context.register_font uploads it and sets
+    `font_id`."""
+
+    def __init__(self, cmap, advance, outline_id, kern=(), ascent=800, descent=-200, line_gap=0):
+        def records(rows, dtype):
+            if isinstance(rows, np.ndarray) and rows.dtype == dtype:
+                return np.ascontiguousarray(rows)
+            return np.array([tuple(int(v) for v in r) for r in rows], dtype=dtype) if len(rows) else np.zeros(0, dtype)
+
+        self.cmap = records(cmap, CMAP_DTYPE)
+        self.kern = records(kern, KERN_DTYPE)
+        self.advance = np.ascontiguousarray(advance, dtype=np.int32)
+        self.outline_id = np.ascontiguousarray(outline_id, dtype=np.uint32)
+        assert len(self.advance) == len(self.outline_id)
+        self.ascent, self.descent, self.line_gap = int(ascent), int(descent), int(line_gap)
+        self.font_id = 0
+        self._glyph_of = self._kern_of = None
+
+    def as_desc(self):
+        """(abi.FontDesc, the arrays it points into)."""
+        d = abi.FontDesc()
+        d.cmap = self.cmap.ctypes.data_as(C.POINTER(abi.CmapEntry)) if len(self.cmap) else None
+        d.n_cmap = len(self.cmap)
+        d.advance = self.advance.ctypes.data_as(C.POINTER(C.c_int32)) if len(self.advance) else None
+        d.outline_id = self.outline_id.ctypes.data_as(C.POINTER(C.c_uint32)) if len(self.advance) else None
+        d.n_glyphs = len(self.advance)
+        d.kern = self.kern.ctypes.data_as(C.POINTER(abi.KernPair)) if len(self.kern) else None
+        d.n_kern = len(self.kern)
+        d.ascent, d.descent, d.line_gap = self.ascent, self.descent, self.line_gap
+        return d, (self.cmap, self.advance, self.outline_id, self.kern)
+
+    def scale(self, font_size):
+        """f64::from(scale_for_pixel_height(font_size as f32)): one f32 division, widened."""
+        return float(np.float32(font_size) / np.float32(self.ascent - self.descent))
+
+    def shape(self, chars):
+        """TextPlacer::text_to_glyphs (text_placer.rs:170-197) of one text given as code points: TEXT_GLYPH_DTYPE records
+        with the outline id as glyph_id, kern 0 for the first char, Rust's is_whitespace as the flag."""
+        if self._glyph_of is None:
+            self._glyph_of = dict(zip(self.cmap["code_point"].tolist(), self.cmap["glyph"].tolist()))
+            self._kern_of = {(l, r): v for l, r, v in self.kern.tolist()}
+        out = np.zeros(len(chars), TEXT_GLYPH_DTYPE)
+        prev = None
+        for k, cp in enumerate(int(c) for c in chars):
+            g = self._glyph_of.get(cp, 0)
+            kern = self._kern_of.get((prev, g), 0) if prev is not None else 0
+            out[k] = (int(self.outline_id[g]), int(self.advance[g]), kern, 1 if cp in WHITE_SPACE else 0)
+            prev = g
+        return out
+
+
+class StringLabelList:
+    """Labels of a batch with string text (osmt_string_label_batch): `labels` are osmt_label records whose seg_off /
+    n_segs name a range of `chars` (uint32 code points, in text order), `runs` (STRING_RUN_DTYPE) holds the font id, the
+    font size and the placement of every label, `way_pts` / `way_sincos` the ways of the line-form runs as in
+    TextLabelList."""
+
+    def __init__(self, labels, job_label_off, runs, chars, way_pts, way_sincos):
+        self.labels = np.ascontiguousarray(labels, dtype=LABEL_DTYPE)
+        self.job_label_off = np.ascontiguousarray(job_label_off, dtype=np.uint32)
+        self.runs = np.ascontiguousarray(runs, dtype=STRING_RUN_DTYPE)
+        self.chars = np.ascontiguousarray(chars, dtype=np.uint32).reshape(-1)
+        self.way_pts = np.ascontiguousarray(way_pts, dtype=np.int32).reshape(-1, 2)
+        self.way_sincos = np.ascontiguousarray(way_sincos, dtype=np.float64).reshape(-1, 2)
+        assert len(self.runs) == len(self.labels) and len(self.way_pts) == len(self.way_sincos)
+
+    @property
+    def n_jobs(self):
+        return len(self.job_label_off) - 1
+
+    def as_batch(self):
+        b = abi.StringLabelBatch()
+        b.labels = self.labels.ctypes.data_as(C.POINTER(abi.Label))
+        b.n_labels = len(self.labels)
+        b.job_label_off = self.job_label_off.ctypes.data_as(C.POINTER(C.c_uint32))
+        b.runs = self.runs.ctypes.data_as(C.POINTER(abi.StringRun))
+        b.chars = self.chars.ctypes.data_as(C.POINTER(C.c_uint32)) if len(self.chars) else None
+        b.n_chars = len(self.chars)
+        b.way_pts = self.way_pts.ctypes.data_as(C.POINTER(C.c_int32)) if len(self.way_pts) else None
+        b.way_sincos = self.way_sincos.ctypes.data_as(C.POINTER(C.c_double)) if len(self.way_pts) else None
+        b.n_way_pts = len(self.way_pts)
+        return b
+
+    def input_bytes(self):
+        """bytes handed to the library: 40 + 64 per label, 4 per char, 24 per way point + the job offsets."""
+        return 104 * len(self.labels) + 4 * len(self.chars) + 24 * len(self.way_pts) + 4 * len(self.job_label_off)
+
+    def with_font(self, font):
+        """Names `font` (a registered FontTable, or a font id) in every run; returns self."""
+        self.runs["font_id"] = font.font_id if isinstance(font, FontTable) else int(font)
+        return self
+
+    def subset(self, idx):
+        """The labels of tiles idx (in that order) as a StringLabelList of their own, chars and ways re-packed."""
+        parts = []
+        for i in idx:
+            a, b = int(self.job_label_off[i]), int(self.job_label_off[i + 1])
+            lab, runs = self.labels[a:b].copy(), self.runs[a:b].copy()
+            cs, ps, ss, cur, pcur = [], [], [], 0, 0
+            for l, r in zip(lab, runs):
+                n = int(l["n_segs"])
+                cs.append(self.chars[int(l["seg_off"]) : int(l["seg_off"]) + n])
+                l["seg_off"] = cur if n else 0
+                cur += n
+                m = int(r["n_pts"]) if int(r["position"]) == abi.TEXT_LINE else 0
+                ps.append(self.way_pts[int(r["pt_off"]) : int(r["pt_off"]) + m])
+                ss.append(self.way_sincos[int(r["pt_off"]) : int(r["pt_off"]) + m])
+                r["pt_off"] = pcur if m else 0
+                pcur += m
+            parts.append(StringLabelList(lab, [0, len(lab)], runs, np.concatenate(cs) if cs else np.zeros(0, np.uint32),
+                                         np.concatenate(ps) if ps else np.zeros((0, 2), np.int32),
+                                         np.concatenate(ss) if ss else np.zeros((0, 2))))
+        return concat_string_labels(parts)
+
+    def to_text_label_list(self, font):
+        """The same labels as text runs, shaped here (FontTable.shape): what a caller of osmt_scene_set_text_labels
+        would upload.  `font`: a FontTable, or a sequence of them indexed by font id."""
+        fonts = {font.font_id: font} if isinstance(font, FontTable) else {f.font_id: f for f in font}
+        runs = np.zeros(len(self.runs), TEXT_RUN_DTYPE)
+        for name in ("position", "y_offset", "pt_off", "n_pts", "center_x", "center_y"):
+            runs[name] = self.runs[name]
+        glyphs = np.zeros(len(self.chars), TEXT_GLYPH_DTYPE)
+        for i, (l, s) in enumerate(zip(self.labels, self.runs)):
+            if not l["has_text"]:
+                continue
+            f = fonts[int(s["font_id"])]
+            runs[i]["scale"] = f.scale(float(s["font_size"]))
+            runs[i]["ascent"], runs[i]["descent"], runs[i]["line_gap"] = f.ascent, f.descent, f.line_gap
+            a, n = int(l["seg_off"]), int(l["n_segs"])
+            glyphs[a : a + n] = f.shape(self.chars[a : a + n])
+        return TextLabelList(self.labels.copy(), self.job_label_off.copy(), runs, glyphs, self.way_pts.copy(), self.way_sincos.copy())
+
+
+def concat_string_labels(lists):
+    labels, offs, runs, chars, pts, scs = [], [0], [], [], [], []
+    cur = pcur = 0
+    for sl in lists:
+        lab, run = sl.labels.copy(), sl.runs.copy()
+        lab["seg_off"][lab["n_segs"] > 0] += cur
+        run["pt_off"][(run["position"] == abi.TEXT_LINE) & (run["n_pts"] > 0)] += pcur
+        labels.append(lab)
+        runs.append(run)
+        chars.append(sl.chars)
+        pts.append(sl.way_pts)
+        scs.append(sl.way_sincos)
+        cur += len(sl.chars)
+        pcur += len(sl.way_pts)
+        offs.extend((offs[-1] + sl.job_label_off[1:].astype(np.int64)).tolist())
+    return StringLabelList(np.concatenate(labels) if labels else np.zeros(0, LABEL_DTYPE), offs,
+                           np.concatenate(runs) if runs else np.zeros(0, STRING_RUN_DTYPE),
+                           np.concatenate(chars) if chars else np.zeros(0, np.uint32),
+                           np.concatenate(pts) if pts else np.zeros((0, 2), np.int32), np.concatenate(scs) if scs else np.zeros((0, 2)))
+
+
+_SYNTH_CP_BASE = 0x4E00  # code point of synthetic glyph g (not a space): _SYNTH_CP_BASE + g
+
+
+def make_string_labels(n_tiles, table, **kw):
+    """The label workload of make_text_labels as strings: (StringLabelList, FontTable).  The labels are those of
+    make_text_labels(n_tiles, table, f32_scale=True, **kw) — same seed, same texts, anchors, ways, icons — and the font
+    is built so that shaping the strings gives exactly that workload's glyph records: make_text_labels draws a kern per
+    OCCURRENCE of a pair, so every shape of SYNTH_GLYPHS gets as many glyph indices (variants with the same advance and
+    outline, a code point each) as it takes for every (left, right) pair of glyph indices to carry one kern value.  A
+    variant of the space must have a White_Space code point, of which there are 25; when they run out for a left glyph,
+    the left char gets a variant of its own.  Glyph 0 is .notdef (no shape).  Register the font (Context.register_font)
+    and name it with StringLabelList.with_font before use."""
+    sizes = []
+    tl = make_text_labels(n_tiles, table, f32_scale=True, _font_px=sizes, **kw)
+    n_shapes, space = len(SYNTH_GLYPHS), len(SYNTH_GLYPHS) - 1
+    ws = sorted(WHITE_SPACE)
+    shape_of = [space]            # glyph index -> shape; glyph 0 = .notdef
+    code_of = [None]              # glyph index -> code point
+    variants = [[] for _ in range(n_shapes)]
+    kern_of = {}                  # (left, right) -> value, zeros included (pinned as "not listed")
+    by_value = {}                 # (left, shape, value) -> right
+    used = {}                     # (left, shape) -> variants of shape already paired with left (in order)
+
+    def new_variant(s):
+        if s == space and len(variants[s]) == len(ws):
+            return None
+        g = len(shape_of)
+        shape_of.append(s)
+        code_of.append(ws[len(variants[s])] if s == space else _SYNTH_CP_BASE + g)
+        variants[s].append(g)
+        return g
+
+    def right_for(left, s, value):
+        """a glyph of shape s whose pair with `left` carries `value` (None: the space's code points are used up)"""
+        g = by_value.get((left, s, value))
+        if g is None:
+            n = used.get((left, s), 0)
+            while n < len(variants[s]) and (left, variants[s][n]) in kern_of:
+                n += 1
+            g = variants[s][n] if n < len(variants[s]) else new_variant(s)
+            if g is None:
+                return None
+            used[(left, s)] = n + 1
+            pin(left, g, value)
+        return g
+
+    def pin(left, g, value):
+        kern_of[(left, g)] = value
+        by_value.setdefault((left, shape_of[g], value), g)
+
+    chars = np.zeros(len(tl.glyphs), np.uint32)
+    for l in tl.labels:
+        if not l["has_text"]:
+            continue
+        a, n = int(l["seg_off"]), int(l["n_segs"])
+        gs = []
+        for k in range(n):
+            t = tl.glyphs[a + k]
+            s, value = int(t["glyph_id"]) - table.first_id, int(t["kern"])
+            if k == 0:
+                g = variants[s][0] if variants[s] else new_variant(s)
+            else:
+                g = right_for(gs[-1], s, value)
+                if g is None:  # the space's code points are used up for this left glyph: a fresh one pairs with anything
+                    gs[-1] = new_variant(shape_of[gs[-1]])
+                    if k >= 2:
+                        pin(gs[-2], gs[-1], int(tl.glyphs[a + k - 1]["kern"]))
+                    g = right_for(gs[-1], s, value)
+            gs.append(g)
+        chars[a : a + n] = [code_of[g] for g in gs]
+    cmap = sorted((code_of[g], g) for g in range(1, len(shape_of)))
+    kern = sorted((lft, r, v) for (lft, r), v in kern_of.items() if v)
+    font = FontTable(cmap, [500] + [SYNTH_GLYPHS[s][0] for s in shape_of[1:]], [table.first_id + s for s in shape_of], kern,
+                     int(_SYNTH_ASCENT), int(_SYNTH_DESCENT), int(_SYNTH_GAP))
+    runs = np.zeros(len(tl.runs), STRING_RUN_DTYPE)
+    for name in ("position", "y_offset", "pt_off", "n_pts", "center_x", "center_y"):
+        runs[name] = tl.runs[name]
+    runs["font_size"] = sizes
+    return StringLabelList(tl.labels, tl.job_label_off, runs, chars, tl.way_pts, tl.way_sincos), font

@@ -32,6 +32,8 @@ EXPORTS = [
     "osmt_register_glyphs", "osmt_scene_set_glyph_labels", "osmt_render_batch_rgb_glyphs", "osmt_scene_read_label_segs",
     "osmt_debug_hypot", "osmt_scene_read_label_cover",
     "osmt_validate_text_labels", "osmt_scene_set_text_labels", "osmt_render_batch_rgb_text", "osmt_scene_read_glyph_instances",
+    "osmt_register_font", "osmt_validate_string_labels", "osmt_scene_set_string_labels", "osmt_render_batch_rgb_strings",
+    "osmt_scene_read_text_glyphs",
     "osmt_label_positions", "osmt_label_positions_begin", "osmt_label_positions_end", "osmt_label_positions_stats",
 ]
 
@@ -120,6 +122,12 @@ def load():
         L.osmt_scene_set_text_labels.argtypes = [vp, vp, C.POINTER(abi.TextLabelBatch)]
         L.osmt_render_batch_rgb_text.argtypes = [vp, C.POINTER(abi.Batch), C.POINTER(abi.TextLabelBatch), u8p, C.c_size_t]
         L.osmt_scene_read_glyph_instances.argtypes = [vp, vp, C.POINTER(abi.GlyphInstance), C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "osmt_scene_set_string_labels"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_register_font.argtypes = [vp, C.POINTER(abi.FontDesc), C.POINTER(C.c_uint32)]
+        L.osmt_validate_string_labels.argtypes = [C.POINTER(abi.StringLabelBatch), C.c_size_t, vp]
+        L.osmt_scene_set_string_labels.argtypes = [vp, vp, C.POINTER(abi.StringLabelBatch)]
+        L.osmt_render_batch_rgb_strings.argtypes = [vp, C.POINTER(abi.Batch), C.POINTER(abi.StringLabelBatch), u8p, C.c_size_t]
+        L.osmt_scene_read_text_glyphs.argtypes = [vp, vp, C.POINTER(abi.TextGlyph), C.c_size_t, C.POINTER(C.c_size_t)]
     if hasattr(L, "osmt_label_positions"):  # absent only from older variant builds loaded through OSMT_LIB
         L.osmt_label_positions.argtypes = [vp, C.POINTER(abi.LabelRequestBatch), vp]
         L.osmt_label_positions_begin.argtypes = [vp, C.POINTER(abi.LabelRequestBatch), C.POINTER(vp)]

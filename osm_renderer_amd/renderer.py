@@ -72,9 +72,33 @@ class Scene:
             check(load().osmt_scene_set_text_labels(self.ctx._h, self._h, C.byref(tb)))
         self.labels = text_labels
 
+    def set_string_labels(self, string_labels):
+        """osmt_scene_set_string_labels: attach string labels (labels.StringLabelList; None detaches):
+        TextPlacer::text_to_glyphs and TextPlacer::place run on the device.  The font ids must be registered on this
+        scene's context (Context.register_font)."""
+        if string_labels is None:
+            check(load().osmt_scene_set_string_labels(self.ctx._h, self._h, None))
+        else:
+            assert string_labels.n_jobs == self.n_jobs
+            sb = string_labels.as_batch()
+            check(load().osmt_scene_set_string_labels(self.ctx._h, self._h, C.byref(sb)))
+        self.labels = string_labels
+
+    def read_text_glyphs(self):
+        """osmt_scene_read_text_glyphs: the records the device shaped for the attached string labels
+        (labels.TEXT_GLYPH_DTYPE [n_chars], glyph_id = the outline id); empty for the other label forms."""
+        from .labels import TEXT_GLYPH_DTYPE
+
+        L, n = load(), C.c_size_t(0)
+        check(L.osmt_scene_read_text_glyphs(self.ctx._h, self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=TEXT_GLYPH_DTYPE)
+        if n.value:
+            check(L.osmt_scene_read_text_glyphs(self.ctx._h, self._h, out.ctypes.data_as(C.POINTER(abi.TextGlyph)), n.value, C.byref(n)))
+        return out
+
     def read_glyph_instances(self):
-        """osmt_scene_read_glyph_instances: the glyph instances the device placed for the attached text-run labels
-        (labels.GLYPH_INSTANCE_DTYPE [n_glyphs], skipped texts with form GLYPH_NONE); empty for the other label forms."""
+        """osmt_scene_read_glyph_instances: the glyph instances the device placed for the attached text-run or string
+        labels (labels.GLYPH_INSTANCE_DTYPE [n_glyphs], skipped texts with form GLYPH_NONE); empty for the other forms."""
         from .labels import GLYPH_INSTANCE_DTYPE
 
         L, n = load(), C.c_size_t(0)
@@ -242,6 +266,21 @@ class Context:
         table.first_id = out.value
         return out.value
 
+    # -- fonts (string labels) -------------------------------------------------------
+    def register_font(self, font):
+        """osmt_register_font: appends a labels.FontTable (its outline ids must be registered already); returns (and
+        records in the table) the font id."""
+        d, _keep = font.as_desc()
+        out = C.c_uint32()
+        check(load().osmt_register_font(self._h, C.byref(d), C.byref(out)))
+        font.font_id = out.value
+        return out.value
+
+    def validate_string_labels(self, string_labels, n_jobs=None):
+        """osmt_validate_string_labels against this context's fonts (host only); raises OsmtError."""
+        sb = string_labels.as_batch()
+        check(load().osmt_validate_string_labels(C.byref(sb), string_labels.n_jobs if n_jobs is None else n_jobs, self._h))
+
     def debug_hypot(self, x, y):
         """osmt_debug_hypot: the device hypot of the glyph walk over pairs, float64."""
         xy = np.ascontiguousarray(np.stack([np.asarray(x, np.float64).ravel(), np.asarray(y, np.float64).ravel()], axis=1))
@@ -394,6 +433,19 @@ class Context:
         tb = text_labels.as_batch() if text_labels is not None else None
         check(load().osmt_render_batch_rgb_text(self._h, C.byref(b), C.byref(tb) if tb is not None else None,
                                                 out.ctypes.data_as(C.POINTER(C.c_uint8)), stride))
+        return out
+
+    def render_batch_rgb_strings(self, dl: DisplayList, string_labels, out=None, stride=None):
+        """osmt_render_batch_rgb_strings: osmt_render_batch_rgb with string labels (labels.StringLabelList)."""
+        b = dl.as_batch()
+        tight = dl.dim * dl.dim * 3
+        stride = tight if stride is None else stride
+        if out is None:
+            out = np.empty((dl.n_jobs, stride), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size >= dl.n_jobs * stride
+        sb = string_labels.as_batch() if string_labels is not None else None
+        check(load().osmt_render_batch_rgb_strings(self._h, C.byref(b), C.byref(sb) if sb is not None else None,
+                                                   out.ctypes.data_as(C.POINTER(C.c_uint8)), stride))
         return out
 
     # -- PNG files from the GPU ----------------------------------------------------
