@@ -571,6 +571,130 @@ int osmt_label_positions_end(osmt_label_job* job, osmt_label_position* out);
  * stats[2] = those answered OSMT_LABEL_TOO_LARGE. */
 int osmt_label_positions_stats(osmt_ctx* ctx, uint64_t stats[3]);
 
+/* ---- display lists built on the GPU from registered geodata and styles ------------------ */
+/* The third way to a scene: instead of an osmt_batch the caller registers, once per context, the topology of a geodata file
+ * (reader.rs:291-336: nodes, ways, polygons, multipolygons) and the Style records of its stylesheet (styler.rs:48-71), and then
+ * names per tile the (entity, style) pairs Styler::style_entities pushes — 8 bytes each.  The GPU does what
+ * Styler::style_areas (styler.rs:168-203) and the three passes of Drawer::draw_to_pixels (drawer.rs:60-99,133-219) do: it
+ * sorts every tile's areas into draw order and writes jobs, ops, rings, node references and dashes where the renderer reads
+ * them.  The result is an ordinary scene with coord_kind == OSMT_COORD_NODE_REF: byte for byte the display list
+ * osmt::SceneBuilder (host/osmt_styled.hpp) builds on the host.  Only osmt_scene_build_styled starts from a styled batch; the
+ * PNG, worker and multi-GPU entries take osmt_batch. */
+
+#define OSMT_STYLED_MAX_TILE_AREAS 65536u /* (entity, style) pairs of one tile */
+#define OSMT_STYLED_LDS_AREAS 2048u       /* up to here a tile is sorted in LDS (16-byte keys: 32 KB), beyond in device memory */
+
+/* The flat arrays of one geodata file, as GeodataReader hands them out (osmt::GeodataDesc in host/osmt_geodata.hpp fills
+ * one).  Borrowed for the call; the library keeps device copies.  Every *_off array has count + 1 non-decreasing entries, the
+ * first 0 and the last the length of the array it indexes. */
+typedef struct osmt_geodata_desc {
+    const double* nodes; /* [n_nodes][2] = (lat, lon) degrees */
+    size_t n_nodes;
+    const uint64_t* way_ids;      /* [n_ways] global ids (Way::global_id) */
+    const uint32_t* way_node_off; /* [n_ways + 1] into way_nodes */
+    size_t n_ways;
+    const uint32_t* way_nodes; /* node indices */
+    size_t n_way_nodes;
+    const uint32_t* polygon_node_off; /* [n_polygons + 1] into polygon_nodes */
+    size_t n_polygons;
+    const uint32_t* polygon_nodes; /* node indices */
+    size_t n_polygon_nodes;
+    const uint64_t* multipolygon_ids;         /* [n_multipolygons] global ids */
+    const uint32_t* multipolygon_polygon_off; /* [n_multipolygons + 1] into multipolygon_polygons */
+    size_t n_multipolygons;
+    const uint32_t* multipolygon_polygons; /* polygon indices */
+    size_t n_multipolygon_polygons;
+} osmt_geodata_desc;
+
+/* mapcss::styler::Style (styler.rs:48-71) as a POD of 96 bytes: an Option is a has_* byte in front of its value, a dash list
+ * a range of the pool handed over with the records (UNSCALED, as the stylesheet has them), a line cap an osmt_line_cap.
+ * A value whose has_* byte is 0 is ignored, whatever its bits. */
+typedef struct osmt_style_rec {
+    int64_t layer;
+    double z_index;
+    double opacity, fill_opacity, width, casing_width;
+    uint32_t fill_image; /* id from osmt_register_image */
+    uint32_t dashes_off, n_dashes, casing_dashes_off, n_casing_dashes;
+    uint8_t has_layer, is_foreground_fill;
+    uint8_t has_color, color[3];
+    uint8_t has_fill_color, fill_color[3];
+    uint8_t has_opacity, has_fill_opacity, has_width, has_dashes, line_cap;
+    uint8_t has_casing_color, casing_color[3];
+    uint8_t has_casing_width, has_casing_dashes, casing_line_cap, has_fill_image;
+    uint8_t has_background_color, background_color[3]; /* carried for completeness: no area op reads it */
+    uint8_t _pad;
+} osmt_style_rec;
+
+/* One element of what Styler::style_entities returns for the areas of a tile; 8 bytes. */
+#define OSMT_STYLED_MULTIPOLYGON 0x80000000u
+typedef struct osmt_styled_area {
+    uint32_t entity; /* local id in the registered geodata (< 2^31); | OSMT_STYLED_MULTIPOLYGON: a multipolygon, else a way */
+    uint32_t style;  /* id from osmt_register_styles */
+} osmt_styled_area;
+
+/* One Drawer::draw_to_pixels call, minus labels; 24 bytes. */
+typedef struct osmt_styled_tile {
+    uint32_t x, y;
+    uint8_t zoom;
+    uint8_t has_canvas;    /* 0: canvas = opaque black */
+    uint8_t canvas_rgb[3]; /* Styler::canvas_fill_color */
+    uint8_t _pad[3];
+    uint32_t area_off; /* the tile's areas: areas[area_off .. area_off + n_areas), ways in entity order among themselves, */
+    uint32_t n_areas;  /* multipolygons too; how the two kinds interleave carries no meaning */
+} osmt_styled_tile;
+
+typedef struct osmt_styled_batch {
+    const osmt_styled_tile* tiles;
+    size_t n_tiles;
+    const osmt_styled_area* areas;
+    size_t n_areas;
+    uint32_t geodata_id; /* id from osmt_register_geodata */
+    uint32_t scale;      /* 1 .. OSMT_MAX_SCALE */
+    uint32_t use_caps_for_dashes; /* Styler::use_caps_for_dashes: 0 / 1 */
+    uint32_t _pad;
+} osmt_styled_batch;
+
+/* The checks osmt_register_geodata runs first, without a device.  OSMT_INVALID_ARG with the offender named in
+ * osmt_last_error(): a NULL array with a non-zero count; offsets that do not start at 0, decrease, or do not end at the length of
+ * the array they index; a node or polygon index out of range; a node that is not finite or lies outside the Web-Mercator
+ * square (what osmt_validate_batch refuses of a node table).  OSMT_UNSUPPORTED: more than 2^31 - 1 ways or multipolygons, or
+ * node-index arrays that together do not fit 32-bit offsets. */
+int osmt_validate_geodata(const osmt_geodata_desc* geodata);
+/* Uploads one geodata file's topology and returns its id.  Append-only with the snapshot semantics of osmt_register_image /
+ * osmt_register_font: a file's tables get one device allocation that never moves and lives as long as the context, so a scene
+ * built from it — whose node table IS the registered one; the scene neither owns nor frees it — is not disturbed by a later
+ * registration. */
+int osmt_register_geodata(osmt_ctx* ctx, const osmt_geodata_desc* geodata, uint32_t* out_geodata_id);
+/* The checks osmt_register_styles runs first, without a device (`ctx` is only asked for its icons): everything that would make
+ * an op built from the style one that osmt_validate_batch refuses.  OSMT_INVALID_ARG, naming the style: a NaN z_index; opacity or
+ * fill_opacity outside [0, 2^52]; a width or casing_width that is not finite or is not finite after multiplication by
+ * OSMT_MAX_SCALE; an unknown line cap; a dash list that is Some([]) or outside the pool; a fill_image that is not
+ * registered.  OSMT_UNSUPPORTED: more than OSMT_MAX_DASHES dashes; |width| * OSMT_MAX_SCALE > 65536.  Only values whose has_*
+ * byte is set are looked at.  A NULL `ctx` has no icons. */
+int osmt_validate_styles(const osmt_style_rec* styles, size_t n, const double* dashes, size_t n_dashes, osmt_ctx* ctx);
+/* Appends n styles (and their dash pool) to the context's style table; style i gets id *out_first_style_id + i.  Same
+ * snapshot rules as above. */
+int osmt_register_styles(osmt_ctx* ctx, const osmt_style_rec* styles, size_t n, const double* dashes, size_t n_dashes,
+                         uint32_t* out_first_style_id);
+/* The checks osmt_scene_build_styled runs first, without a device, O(n_areas).  OSMT_INVALID_ARG: NULL arrays, an unknown
+ * geodata id, a way, multipolygon or style id out of range, zoom > OSMT_MAX_ZOOM, scale outside 1..OSMT_MAX_SCALE, a tile's
+ * area range outside the area array or overlapping another tile's.  OSMT_UNSUPPORTED: a tile with more than
+ * OSMT_STYLED_MAX_TILE_AREAS areas, or more areas in all than 32-bit element indices hold.  The batch's own shape is checked
+ * first, its ids against the context's tables last; a NULL `ctx` has nothing registered. */
+int osmt_validate_styled_batch(const osmt_styled_batch* batch, osmt_ctx* ctx);
+/* Builds the scene of a styled batch on the device: per tile a sort under the total order of compare_styled_entities +
+ * style_areas' merge (layer or 0, is_foreground_fill, z_index, global id, multipolygon before way, input position), a count
+ * pass over (tile, pass in Fill / Casing / Stroke, area), one read-back of eight totals, and an emit pass into the scene's
+ * own arrays.  Errors: those of osmt_validate_styled_batch; OSMT_UNSUPPORTED when the ops, rings, node references, dashes,
+ * 64-edge blocks or virtual stroke segments of the batch do not fit 32-bit indices.  *out_scene is NULL on every error:
+ * never a truncated or mis-ordered list. */
+int osmt_scene_build_styled(osmt_ctx* ctx, const osmt_styled_batch* batch, osmt_scene** out_scene);
+/* Inspection: the device-resident display list of ANY scene, uploaded or built, copied back.  counts = { jobs, ops, rings,
+ * node references (0 unless the scene is OSMT_COORD_NODE_REF), dashes } is always set; each output may be NULL (all NULL:
+ * ask for the sizes). */
+int osmt_scene_read_display_list(osmt_ctx* ctx, osmt_scene* scene, osmt_tile_job* jobs, osmt_op* ops, osmt_ring* rings,
+                                 uint32_t* node_refs, double* dashes, size_t counts[5]);
+
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */
 int osmt_project(osmt_ctx* ctx, const double* latlon, size_t n, uint8_t zoom, uint32_t tile_x, uint32_t tile_y,

@@ -25,6 +25,10 @@ LABEL_MAX_CELLS = 65536
 GLYPH_CENTER, GLYPH_LINE = 0, 1  # osmt_glyph_instance.form: TextPlacer::place's two `tr` closures
 GLYPH_NONE = 2  # a glyph of a text place() skipped (seen through osmt_scene_read_glyph_instances only)
 TEXT_CENTER, TEXT_LINE = 0, 1  # osmt_text_run.position: TextPosition
+STYLED_MAX_TILE_AREAS = 65536  # (entity, style) pairs of one tile of an osmt_styled_batch
+STYLED_LDS_AREAS = 2048  # up to here osmt_scene_build_styled sorts a tile in LDS
+STYLED_MULTIPOLYGON = 0x80000000  # osmt_styled_area.entity: the entity is a multipolygon
+MAX_SCALE = 4
 
 
 class Op(C.Structure):
@@ -248,6 +252,93 @@ class LabelPosition(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("status", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class GeodataDesc(C.Structure):
+    _fields_ = [
+        ("nodes", C.POINTER(C.c_double)),
+        ("n_nodes", C.c_size_t),
+        ("way_ids", C.POINTER(C.c_uint64)),
+        ("way_node_off", C.POINTER(C.c_uint32)),
+        ("n_ways", C.c_size_t),
+        ("way_nodes", C.POINTER(C.c_uint32)),
+        ("n_way_nodes", C.c_size_t),
+        ("polygon_node_off", C.POINTER(C.c_uint32)),
+        ("n_polygons", C.c_size_t),
+        ("polygon_nodes", C.POINTER(C.c_uint32)),
+        ("n_polygon_nodes", C.c_size_t),
+        ("multipolygon_ids", C.POINTER(C.c_uint64)),
+        ("multipolygon_polygon_off", C.POINTER(C.c_uint32)),
+        ("n_multipolygons", C.c_size_t),
+        ("multipolygon_polygons", C.POINTER(C.c_uint32)),
+        ("n_multipolygon_polygons", C.c_size_t),
+    ]
+
+
+class StyleRec(C.Structure):
+    _fields_ = [
+        ("layer", C.c_int64),
+        ("z_index", C.c_double),
+        ("opacity", C.c_double),
+        ("fill_opacity", C.c_double),
+        ("width", C.c_double),
+        ("casing_width", C.c_double),
+        ("fill_image", C.c_uint32),
+        ("dashes_off", C.c_uint32),
+        ("n_dashes", C.c_uint32),
+        ("casing_dashes_off", C.c_uint32),
+        ("n_casing_dashes", C.c_uint32),
+        ("has_layer", C.c_uint8),
+        ("is_foreground_fill", C.c_uint8),
+        ("has_color", C.c_uint8),
+        ("color", C.c_uint8 * 3),
+        ("has_fill_color", C.c_uint8),
+        ("fill_color", C.c_uint8 * 3),
+        ("has_opacity", C.c_uint8),
+        ("has_fill_opacity", C.c_uint8),
+        ("has_width", C.c_uint8),
+        ("has_dashes", C.c_uint8),
+        ("line_cap", C.c_uint8),
+        ("has_casing_color", C.c_uint8),
+        ("casing_color", C.c_uint8 * 3),
+        ("has_casing_width", C.c_uint8),
+        ("has_casing_dashes", C.c_uint8),
+        ("casing_line_cap", C.c_uint8),
+        ("has_fill_image", C.c_uint8),
+        ("has_background_color", C.c_uint8),
+        ("background_color", C.c_uint8 * 3),
+        ("_pad", C.c_uint8),
+    ]
+
+
+class StyledArea(C.Structure):
+    _fields_ = [("entity", C.c_uint32), ("style", C.c_uint32)]
+
+
+class StyledTile(C.Structure):
+    _fields_ = [
+        ("x", C.c_uint32),
+        ("y", C.c_uint32),
+        ("zoom", C.c_uint8),
+        ("has_canvas", C.c_uint8),
+        ("canvas_rgb", C.c_uint8 * 3),
+        ("_pad", C.c_uint8 * 3),
+        ("area_off", C.c_uint32),
+        ("n_areas", C.c_uint32),
+    ]
+
+
+class StyledBatch(C.Structure):
+    _fields_ = [
+        ("tiles", C.POINTER(StyledTile)),
+        ("n_tiles", C.c_size_t),
+        ("areas", C.POINTER(StyledArea)),
+        ("n_areas", C.c_size_t),
+        ("geodata_id", C.c_uint32),
+        ("scale", C.c_uint32),
+        ("use_caps_for_dashes", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32)]
 
@@ -265,3 +356,8 @@ assert C.sizeof(KernPair) == 12
 assert C.sizeof(StringRun) == 64
 assert C.sizeof(LabelRequest) == 16
 assert C.sizeof(LabelPosition) == 24
+assert C.sizeof(StyleRec) == 96
+assert C.sizeof(StyledArea) == 8
+assert C.sizeof(StyledTile) == 24
+assert C.sizeof(StyledBatch) == 48
+assert C.sizeof(GeodataDesc) == 128

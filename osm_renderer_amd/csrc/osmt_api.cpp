@@ -128,6 +128,23 @@ struct osmt_ctx {
     osmt_font_dev* d_fonts = nullptr;
     uint32_t d_n_fonts = 0;
     bool fonts_dirty = false;
+    /* the geodata files of osmt_register_geodata (scenes built on the device): one device allocation per file, made at
+     * registration, that never moves and lives as long as the context — a built scene's node table points into it */
+    struct geodata_host {
+        size_t n_nodes = 0, n_ways = 0, n_mps = 0;
+        void* d_pool = nullptr;
+        osmt_geo_dev dev{};
+    };
+    std::vector<geodata_host> geodata;
+    /* the styles of osmt_register_styles, same snapshot rules as the glyph table: a registration followed by a build makes
+     * a new device triple (records, ranks, dash pool), the old one joins image_graveyard */
+    std::vector<osmt_style_rec> styles;
+    std::vector<double> style_dashes;
+    osmt_style_rec* d_styles = nullptr;
+    uint32_t* d_style_rank = nullptr;
+    double* d_style_dashes = nullptr;
+    uint32_t d_n_styles = 0;
+    bool styles_dirty = false;
     /* one reference for the handle returned by osmt_create + one per live scene: osmt_destroy on a context that still
      * has scenes only drops the handle's reference, the last osmt_scene_free tears the context down */
     std::atomic<int> refs{1};
@@ -588,6 +605,11 @@ void ctx_teardown(osmt_ctx* ctx) {
     if (ctx->d_fonts) (void)hipFree(ctx->d_fonts);
     for (auto& f : ctx->fonts)
         if (f->d_pool) (void)hipFree(f->d_pool);
+    for (auto& g : ctx->geodata)
+        if (g.d_pool) (void)hipFree(g.d_pool);
+    if (ctx->d_styles) (void)hipFree(ctx->d_styles);
+    if (ctx->d_style_rank) (void)hipFree(ctx->d_style_rank);
+    if (ctx->d_style_dashes) (void)hipFree(ctx->d_style_dashes);
     for (void* p : ctx->image_graveyard) (void)hipFree(p);
     for (auto& c : ctx->cache) (void)hipFree(c.p);
     for (hipStream_t st : ctx->idle_streams) (void)hipStreamDestroy(st);
@@ -1182,6 +1204,45 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
     return OSMT_OK;
 }
 
+/* The back half of a scene's memory, behind the arrays the caller (osmt_scene_upload) or the build kernels
+ * (osmt_scene_build_styled) fill: the work areas of the pre-pass per op, per stroke slot, per 64-edge block, per virtual
+ * segment and per sub-tile.  Both paths carve them with this function, right behind their front arrays, and then size the
+ * arenas with scene_size_arenas. */
+struct scene_back {
+    size_t o_info, o_aux, o_dseg, o_submask, o_blk, o_vseg, o_cursors, o_hdr;
+};
+static scene_back scene_carve_back(size_t& off, size_t n_jobs, size_t n_ops, size_t n_strokes, size_t n_blk, size_t n_vsegs, uint32_t scale) {
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    scene_back k;
+    k.o_info = carve(n_ops * sizeof(osmt_opinfo));
+    /* per virtual segment (not per point: two stroke ops may share a ring, e.g. a casing and its stroke) */
+    k.o_aux = carve((size_t)(n_strokes + 1) * sizeof(osmt_stroke_aux));
+    k.o_dseg = carve((size_t)(n_strokes + 1) * OSMT_MAX_DASH_SEGS * sizeof(osmt_dash_seg)); /* touched by dashed ops only */
+    const size_t sub_rows = (size_t)OSMT_TILE_SIZE * scale / OSMT_SUB_H;
+    k.o_submask = carve(n_ops * sub_rows * 4);
+    k.o_blk = carve((n_blk + 1) * sizeof(osmt_blk_bbox));
+    k.o_vseg = carve((n_vsegs + 1) * sizeof(osmt_vseg));
+    const size_t n_sub = ((size_t)OSMT_TILE_SIZE * scale / OSMT_SUB_W) * sub_rows;
+    k.o_cursors = carve(32 + n_jobs * n_sub * 4); /* cursors + list counts: zeroed together every frame */
+    k.o_hdr = carve(n_jobs * n_sub * sizeof(uint2));
+    return k;
+}
+static void scene_point_back(osmt_scene* s, char* rbase, const scene_back& k) {
+    s->d_info = (osmt_opinfo*)(rbase + k.o_info);
+    s->d_aux = (osmt_stroke_aux*)(rbase + k.o_aux);
+    s->d_dseg = (osmt_dash_seg*)(rbase + k.o_dseg);
+    s->d_submask = (uint32_t*)(rbase + k.o_submask);
+    s->d_blk = (osmt_blk_bbox*)(rbase + k.o_blk);
+    s->d_vseg = (osmt_vseg*)(rbase + k.o_vseg);
+    s->d_cursors = (unsigned long long*)(rbase + k.o_cursors);
+    s->d_cnt = (uint32_t*)(rbase + k.o_cursors + 32);
+    s->d_hdr = (uint2*)(rbase + k.o_hdr);
+}
+
 /* st == nullptr: blocking copies (the public osmt_scene_upload); otherwise stream-ordered on `st`, the caller
  * synchronises the stream before the batch's host arrays go away */
 /* trusted: the batch was built by the library itself from a batch it has already validated (the shards of osmt_render_batch_multi) */
@@ -1411,17 +1472,7 @@ static int scene_upload_impl(osmt_ctx* ctx, const osmt_batch* b, osmt_scene** ou
     s->scale = b->scale;
     s->coord_kind = b->coord_kind;
 
-    const size_t o_info = carve(b->n_ops * sizeof(osmt_opinfo));
-    /* per virtual segment (not per point: two stroke ops may share a ring, e.g. a casing and its stroke) */
-    const size_t o_aux = carve((size_t)(n_strokes + 1) * sizeof(osmt_stroke_aux));
-    const size_t o_dseg = carve((size_t)(n_strokes + 1) * OSMT_MAX_DASH_SEGS * sizeof(osmt_dash_seg)); /* touched by dashed ops only */
-    const size_t sub_rows = (size_t)OSMT_TILE_SIZE * b->scale / OSMT_SUB_H;
-    const size_t o_submask = carve(b->n_ops * sub_rows * 4);
-    const size_t o_blk = carve((n_blk + 1) * sizeof(osmt_blk_bbox));
-    const size_t o_vseg = carve((n_vsegs + 1) * sizeof(osmt_vseg));
-    const size_t n_sub = ((size_t)OSMT_TILE_SIZE * b->scale / OSMT_SUB_W) * sub_rows;
-    const size_t o_cursors = carve(32 + b->n_jobs * n_sub * 4); /* cursors + list counts: zeroed together every frame */
-    const size_t o_hdr = carve(b->n_jobs * n_sub * sizeof(uint2));
+    const scene_back bk = scene_carve_back(off, b->n_jobs, b->n_ops, n_strokes, n_blk, n_vsegs, b->scale);
     s->bytes = off - (split ? front_bytes : 0) + 256;
     mark(1);
     hipError_t e = dev_alloc(ctx, (void**)&s->d_base, s->bytes);
@@ -1443,18 +1494,10 @@ static int scene_upload_impl(osmt_ctx* ctx, const osmt_batch* b, osmt_scene** ou
     s->d_dashes = (double*)(fbase + o_dashes);
     s->d_pt_job = (uint32_t*)(fbase + o_ptjob);
     s->d_op_aux = (uint32_t*)(fbase + o_opaux);
-    s->d_info = (osmt_opinfo*)(rbase + o_info);
-    s->d_aux = (osmt_stroke_aux*)(rbase + o_aux);
-    s->d_dseg = (osmt_dash_seg*)(rbase + o_dseg);
-    s->d_submask = (uint32_t*)(rbase + o_submask);
     s->d_op_blk = (uint32_t*)(fbase + o_opblk);
     s->d_op_vseg = (uint32_t*)(fbase + o_opvseg);
-    s->d_blk = (osmt_blk_bbox*)(rbase + o_blk);
     s->d_op_job = (uint32_t*)(fbase + o_opjob);
-    s->d_vseg = (osmt_vseg*)(rbase + o_vseg);
-    s->d_cursors = (unsigned long long*)(rbase + o_cursors);
-    s->d_cnt = (uint32_t*)(rbase + o_cursors + 32);
-    s->d_hdr = (uint2*)(rbase + o_hdr);
+    scene_point_back(s, rbase, bk);
 
     auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
         if (!bytes) return hipSuccess;
@@ -1595,6 +1638,538 @@ void osmt_scene_free(osmt_scene* s) {
     dev_free(s->ctx, s->d_text_glyphs);
     stage_release(s->ctx, s->h_stage);
     scene_delete(s);
+}
+
+/* ---- display lists built on the device (include/osmtile.h "display lists built on the GPU") --------------------------- */
+namespace {
+
+/* offs: count + 1 entries from 0 to `total`, never decreasing */
+int check_offsets(const char* what, const uint32_t* offs, size_t count, size_t total) {
+    if (offs[0] != 0u) return fail(OSMT_INVALID_ARG, "geodata: %s[0] is %u, not 0", what, offs[0]);
+    for (size_t i = 0; i < count; ++i)
+        if (offs[i + 1] < offs[i]) return fail(OSMT_INVALID_ARG, "geodata: %s[%zu] = %u is less than the entry before it (%u)", what, i + 1, offs[i + 1], offs[i]);
+    if ((size_t)offs[count] != total) return fail(OSMT_INVALID_ARG, "geodata: %s[%zu] = %u does not end at the %zu entries it indexes", what, count, offs[count], total);
+    return OSMT_OK;
+}
+
+int validate_geodata(const osmt_geodata_desc* g) {
+    if (!g) return fail(OSMT_INVALID_ARG, "geodata is NULL");
+    if ((g->n_nodes && !g->nodes) || (g->n_ways && !g->way_ids) || !g->way_node_off || (g->n_way_nodes && !g->way_nodes) || !g->polygon_node_off ||
+        (g->n_polygon_nodes && !g->polygon_nodes) || (g->n_multipolygons && !g->multipolygon_ids) || !g->multipolygon_polygon_off ||
+        (g->n_multipolygon_polygons && !g->multipolygon_polygons))
+        return fail(OSMT_INVALID_ARG, "geodata: NULL array (every offset array has at least its first entry)");
+    if (g->n_nodes >= 0xFFFFFFFFull || g->n_ways >= 0x7FFFFFFFull || g->n_multipolygons >= 0x7FFFFFFFull || g->n_polygons >= 0xFFFFFFFFull ||
+        g->n_multipolygon_polygons >= 0xFFFFFFFFull || (unsigned long long)g->n_way_nodes + g->n_polygon_nodes >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "geodata: too large for 32-bit indices (ways and multipolygons: 31 bits)");
+    int rc = check_offsets("way_node_off", g->way_node_off, g->n_ways, g->n_way_nodes);
+    if (rc == OSMT_OK) rc = check_offsets("polygon_node_off", g->polygon_node_off, g->n_polygons, g->n_polygon_nodes);
+    if (rc == OSMT_OK) rc = check_offsets("multipolygon_polygon_off", g->multipolygon_polygon_off, g->n_multipolygons, g->n_multipolygon_polygons);
+    if (rc != OSMT_OK) return rc;
+    for (size_t i = 0; i < g->n_way_nodes; ++i)
+        if (g->way_nodes[i] >= g->n_nodes) return fail(OSMT_INVALID_ARG, "geodata: way_nodes[%zu] = %u is not a node (%zu nodes)", i, g->way_nodes[i], g->n_nodes);
+    for (size_t i = 0; i < g->n_polygon_nodes; ++i)
+        if (g->polygon_nodes[i] >= g->n_nodes)
+            return fail(OSMT_INVALID_ARG, "geodata: polygon_nodes[%zu] = %u is not a node (%zu nodes)", i, g->polygon_nodes[i], g->n_nodes);
+    for (size_t i = 0; i < g->n_multipolygon_polygons; ++i)
+        if (g->multipolygon_polygons[i] >= g->n_polygons)
+            return fail(OSMT_INVALID_ARG, "geodata: multipolygon_polygons[%zu] = %u is not a polygon (%zu polygons)", i, g->multipolygon_polygons[i],
+                        g->n_polygons);
+    /* what validate_nodes refuses of the node table of an OSMT_COORD_NODE_REF batch */
+    for (size_t i = 0; i < g->n_nodes; ++i) {
+        const double lat = g->nodes[2 * i], lon = g->nodes[2 * i + 1];
+        if (!(std::fabs(lat) <= OSMT_MAX_ABS_LAT) || !(std::fabs(lon) <= 180.0))
+            return fail(OSMT_INVALID_ARG, "geodata: node %zu: (lat, lon) = (%g, %g) outside the Web-Mercator square (|lat| <= %g, |lon| <= 180)", i, lat, lon,
+                        OSMT_MAX_ABS_LAT);
+    }
+    return OSMT_OK;
+}
+
+int validate_styles(const osmt_style_rec* st, size_t n, const double* dashes, size_t n_dashes, size_t n_images) {
+    if (n && !st) return fail(OSMT_INVALID_ARG, "styles is NULL");
+    if (n_dashes && !dashes) return fail(OSMT_INVALID_ARG, "the styles' dash pool is NULL");
+    for (size_t i = 0; i < n; ++i) {
+        const osmt_style_rec& s = st[i];
+        if (std::isnan(s.z_index)) return fail(OSMT_INVALID_ARG, "style %zu: z_index is NaN", i);
+        auto opacity = [&](const char* what, uint8_t has, double v) {
+            if (has && (!(v >= 0.0) || !(v <= 4503599627370496.0))) return fail(OSMT_INVALID_ARG, "style %zu: %s must be in [0, 2^52]", i, what);
+            return (int)OSMT_OK;
+        };
+        auto width = [&](const char* what, uint8_t has, double v) {
+            if (!has) return (int)OSMT_OK;
+            if (!std::isfinite(v) || !std::isfinite(v * (double)OSMT_MAX_SCALE)) return fail(OSMT_INVALID_ARG, "style %zu: %s not finite", i, what);
+            if (std::fabs(v * (double)OSMT_MAX_SCALE) > 65536.0) return fail(OSMT_UNSUPPORTED, "style %zu: |%s| * %u > 65536 px", i, what, OSMT_MAX_SCALE);
+            return (int)OSMT_OK;
+        };
+        auto dash_list = [&](const char* what, uint8_t has, uint32_t off, uint32_t cnt) {
+            if (!has) return (int)OSMT_OK;
+            if (cnt == 0) return fail(OSMT_INVALID_ARG, "style %zu: empty %s list", i, what);
+            if (cnt > OSMT_MAX_DASHES) return fail(OSMT_UNSUPPORTED, "style %zu: more than %u %s", i, OSMT_MAX_DASHES, what);
+            if ((size_t)off + cnt > n_dashes) return fail(OSMT_INVALID_ARG, "style %zu: %s range outside the pool", i, what);
+            return (int)OSMT_OK;
+        };
+        int rc = opacity("opacity", s.has_opacity, s.opacity);
+        if (rc == OSMT_OK) rc = opacity("fill_opacity", s.has_fill_opacity, s.fill_opacity);
+        if (rc == OSMT_OK) rc = width("width", s.has_width, s.width);
+        if (rc == OSMT_OK) rc = width("casing_width", s.has_casing_width, s.casing_width);
+        if (rc == OSMT_OK && s.line_cap > OSMT_CAP_SQUARE) rc = fail(OSMT_INVALID_ARG, "style %zu: unknown line_cap %u", i, s.line_cap);
+        if (rc == OSMT_OK && s.casing_line_cap > OSMT_CAP_SQUARE) rc = fail(OSMT_INVALID_ARG, "style %zu: unknown casing_line_cap %u", i, s.casing_line_cap);
+        if (rc == OSMT_OK) rc = dash_list("dashes", s.has_dashes, s.dashes_off, s.n_dashes);
+        if (rc == OSMT_OK) rc = dash_list("casing_dashes", s.has_casing_dashes, s.casing_dashes_off, s.n_casing_dashes);
+        if (rc == OSMT_OK && s.has_fill_image && s.fill_image >= n_images)
+            rc = fail(OSMT_INVALID_ARG, "style %zu: fill_image %u is not registered (%zu images)", i, s.fill_image, n_images);
+        if (rc != OSMT_OK) return rc;
+    }
+    return OSMT_OK;
+}
+
+size_t ctx_image_count(osmt_ctx* ctx) {
+    if (!ctx) return 0;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return ctx->images.size();
+}
+
+/* the part of compare_styled_entities (styler.rs:246-272) that depends on the style alone */
+int style_key_cmp(const osmt_style_rec& a, const osmt_style_rec& b) {
+    const int64_t la = a.has_layer ? a.layer : 0, lb = b.has_layer ? b.layer : 0;
+    if (la != lb) return la < lb ? -1 : 1;
+    const bool fa = a.is_foreground_fill != 0, fb = b.is_foreground_fill != 0;
+    if (fa != fb) return fa ? 1 : -1; /* false < true */
+    if (a.z_index != b.z_index) return a.z_index < b.z_index ? -1 : 1; /* -0.0 == +0.0; never NaN */
+    return 0;
+}
+
+struct styles_snapshot {
+    const osmt_style_rec* styles = nullptr;
+    const uint32_t* rank = nullptr;
+    const double* dashes = nullptr;
+    uint32_t n = 0;
+};
+
+/* Brings the device copy of the style table up to date (records, their dense ranks under style_key_cmp, the dash pool);
+ * the snapshot stays valid for the life of the context. */
+int sync_styles(osmt_ctx* ctx, styles_snapshot* snap) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->styles_dirty) {
+        const size_t n = ctx->styles.size();
+        std::vector<uint32_t> order(n), rank(n);
+        for (size_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
+        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return style_key_cmp(ctx->styles[x], ctx->styles[y]) < 0; });
+        uint32_t r = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if (i && style_key_cmp(ctx->styles[order[i - 1]], ctx->styles[order[i]]) != 0) ++r;
+            rank[order[i]] = r;
+        }
+        osmt_style_rec* ds = nullptr;
+        uint32_t* dr = nullptr;
+        double* dd = nullptr;
+        const size_t nd = ctx->style_dashes.size();
+        hipError_t e = hipMalloc((void**)&ds, std::max<size_t>(n, 1) * sizeof(osmt_style_rec));
+        if (e == hipSuccess) e = hipMalloc((void**)&dr, std::max<size_t>(n, 1) * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&dd, std::max<size_t>(nd, 1) * 8);
+        if (e == hipSuccess && n) e = hipMemcpy(ds, ctx->styles.data(), n * sizeof(osmt_style_rec), hipMemcpyHostToDevice);
+        if (e == hipSuccess && n) e = hipMemcpy(dr, rank.data(), n * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && nd) e = hipMemcpy(dd, ctx->style_dashes.data(), nd * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (ds) (void)hipFree(ds);
+            if (dr) (void)hipFree(dr);
+            if (dd) (void)hipFree(dd);
+            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "style table upload failed: %s", hipGetErrorString(e));
+        }
+        if (ctx->d_styles) ctx->image_graveyard.push_back(ctx->d_styles);
+        if (ctx->d_style_rank) ctx->image_graveyard.push_back(ctx->d_style_rank);
+        if (ctx->d_style_dashes) ctx->image_graveyard.push_back(ctx->d_style_dashes);
+        ctx->d_styles = ds;
+        ctx->d_style_rank = dr;
+        ctx->d_style_dashes = dd;
+        ctx->d_n_styles = (uint32_t)n;
+        ctx->styles_dirty = false;
+    }
+    snap->styles = ctx->d_styles;
+    snap->rank = ctx->d_style_rank;
+    snap->dashes = ctx->d_style_dashes;
+    snap->n = ctx->d_n_styles;
+    return OSMT_OK;
+}
+
+/* tile_base (optional): n_tiles + 1 entries, the areas of the tiles in front of each tile */
+int validate_styled_batch(const osmt_styled_batch* b, osmt_ctx* ctx, std::vector<uint32_t>* tile_base) {
+    if (!b) return fail(OSMT_INVALID_ARG, "styled batch is NULL");
+    if (b->scale < 1 || b->scale > OSMT_MAX_SCALE) return fail(OSMT_INVALID_ARG, "scale %u not in 1..%u", b->scale, OSMT_MAX_SCALE);
+    if ((b->n_tiles && !b->tiles) || (b->n_areas && !b->areas)) return fail(OSMT_INVALID_ARG, "NULL array with non-zero count");
+    if (b->n_tiles >= 0x7FFFFFFFull / 64) return fail(OSMT_INVALID_ARG, "styled batch too large for 32-bit indices (tiles)");
+    struct range {
+        uint64_t lo, hi;
+        uint32_t tile;
+    };
+    std::vector<range> rr;
+    rr.reserve(b->n_tiles);
+    unsigned long long total = 0;
+    if (tile_base) tile_base->assign(b->n_tiles + 1, 0u);
+    for (size_t t = 0; t < b->n_tiles; ++t) {
+        const osmt_styled_tile& tl = b->tiles[t];
+        if (tl.zoom > OSMT_MAX_ZOOM) return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u > MAX_ZOOM (src/tile.rs:5)", t, tl.zoom);
+        if ((size_t)tl.area_off + tl.n_areas > b->n_areas) return fail(OSMT_INVALID_ARG, "tile %zu: area range out of bounds", t);
+        if (tl.n_areas > OSMT_STYLED_MAX_TILE_AREAS)
+            return fail(OSMT_UNSUPPORTED, "tile %zu: %u areas (> OSMT_STYLED_MAX_TILE_AREAS = %u)", t, tl.n_areas, OSMT_STYLED_MAX_TILE_AREAS);
+        if (tl.n_areas) rr.push_back({tl.area_off, (uint64_t)tl.area_off + tl.n_areas, (uint32_t)t});
+        if (tile_base) (*tile_base)[t] = (uint32_t)total;
+        total += tl.n_areas;
+        if (3ull * total >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "styled batch too large for 32-bit indices (%llu areas x 3 passes)", total);
+    }
+    if (tile_base) (*tile_base)[b->n_tiles] = (uint32_t)total;
+    std::sort(rr.begin(), rr.end(), [](const range& x, const range& y) { return x.lo < y.lo; });
+    for (size_t i = 1; i < rr.size(); ++i)
+        if (rr[i].lo < rr[i - 1].hi)
+            return fail(OSMT_INVALID_ARG, "tile %u: area %llu also belongs to tile %u (area ranges must not overlap)", rr[i].tile, (unsigned long long)rr[i].lo,
+                        rr[i - 1].tile);
+    /* what the context has registered (a NULL context has nothing) */
+    size_t n_ways = 0, n_mps = 0, n_styles = 0;
+    if (!ctx) return fail(OSMT_INVALID_ARG, "geodata id %u is not registered (no context)", b->geodata_id);
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (b->geodata_id >= ctx->geodata.size()) return fail(OSMT_INVALID_ARG, "geodata id %u is not registered (%zu files)", b->geodata_id, ctx->geodata.size());
+        n_ways = ctx->geodata[b->geodata_id].n_ways;
+        n_mps = ctx->geodata[b->geodata_id].n_mps;
+        n_styles = ctx->styles.size();
+    }
+    /* only areas a tile names are read by the kernels, and only they are checked */
+    for (const range& r : rr)
+        for (uint64_t i = r.lo; i < r.hi; ++i) {
+            const osmt_styled_area& a = b->areas[i];
+            const uint32_t id = a.entity & ~OSMT_STYLED_MULTIPOLYGON;
+            if (a.entity & OSMT_STYLED_MULTIPOLYGON) {
+                if (id >= n_mps) return fail(OSMT_INVALID_ARG, "area %llu: multipolygon %u out of range (%zu multipolygons)", (unsigned long long)i, id, n_mps);
+            } else if (id >= n_ways) {
+                return fail(OSMT_INVALID_ARG, "area %llu: way %u out of range (%zu ways)", (unsigned long long)i, id, n_ways);
+            }
+            if (a.style >= n_styles) return fail(OSMT_INVALID_ARG, "area %llu: style %u is not registered (%zu styles)", (unsigned long long)i, a.style, n_styles);
+        }
+    return OSMT_OK;
+}
+
+int register_geodata_body(osmt_ctx* ctx, const osmt_geodata_desc* g, uint32_t* out_id) {
+    if (!ctx || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    const int rc = validate_geodata(g);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    /* per multipolygon: its rings of >= 2 nodes and their nodes (point_pairs.rs:36-40 drops the others) */
+    std::vector<uint2> mp_sum(g->n_multipolygons);
+    for (size_t m = 0; m < g->n_multipolygons; ++m) {
+        unsigned long long rings = 0, refs = 0;
+        for (uint32_t k = g->multipolygon_polygon_off[m]; k < g->multipolygon_polygon_off[m + 1]; ++k) {
+            const uint32_t p = g->multipolygon_polygons[k];
+            const uint32_t nn = g->polygon_node_off[p + 1] - g->polygon_node_off[p];
+            if (nn >= 2) ++rings, refs += nn;
+        }
+        if (refs >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "geodata: multipolygon %zu has %llu nodes (> 2^32)", m, refs);
+        mp_sum[m] = make_uint2((uint32_t)rings, (uint32_t)refs);
+    }
+    std::vector<uint32_t> poly_off(g->n_polygons + 1);
+    for (size_t p = 0; p <= g->n_polygons; ++p) poly_off[p] = g->polygon_node_off[p] + (uint32_t)g->n_way_nodes;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_nodes = carve(g->n_nodes * 16), o_wgid = carve(g->n_ways * 8), o_mgid = carve(g->n_multipolygons * 8);
+    const size_t o_woff = carve((g->n_ways + 1) * 4), o_poff = carve((g->n_polygons + 1) * 4), o_moff = carve((g->n_multipolygons + 1) * 4);
+    const size_t o_mpol = carve(g->n_multipolygon_polygons * 4), o_idx = carve((g->n_way_nodes + g->n_polygon_nodes) * 4);
+    const size_t o_sum = carve(g->n_multipolygons * 8);
+    char* pool = nullptr;
+    HIP_TRY(hipMalloc((void**)&pool, off));
+    hipError_t e = hipSuccess;
+    auto put = [&](size_t o, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+    };
+    put(o_nodes, g->nodes, g->n_nodes * 16);
+    put(o_wgid, g->way_ids, g->n_ways * 8);
+    put(o_mgid, g->multipolygon_ids, g->n_multipolygons * 8);
+    put(o_woff, g->way_node_off, (g->n_ways + 1) * 4);
+    put(o_poff, poly_off.data(), (g->n_polygons + 1) * 4);
+    put(o_moff, g->multipolygon_polygon_off, (g->n_multipolygons + 1) * 4);
+    put(o_mpol, g->multipolygon_polygons, g->n_multipolygon_polygons * 4);
+    put(o_idx, g->way_nodes, g->n_way_nodes * 4);
+    put(o_idx + g->n_way_nodes * 4, g->polygon_nodes, g->n_polygon_nodes * 4);
+    put(o_sum, mp_sum.data(), g->n_multipolygons * 8);
+    if (e != hipSuccess) {
+        (void)hipFree(pool);
+        return fail(OSMT_HIP_ERROR, "geodata upload failed: %s", hipGetErrorString(e));
+    }
+    osmt_ctx::geodata_host h;
+    h.n_nodes = g->n_nodes, h.n_ways = g->n_ways, h.n_mps = g->n_multipolygons;
+    h.d_pool = pool;
+    h.dev.nodes = (const double*)(pool + o_nodes);
+    h.dev.way_gid = (const uint64_t*)(pool + o_wgid);
+    h.dev.mp_gid = (const uint64_t*)(pool + o_mgid);
+    h.dev.way_off = (const uint32_t*)(pool + o_woff);
+    h.dev.poly_off = (const uint32_t*)(pool + o_poff);
+    h.dev.mp_off = (const uint32_t*)(pool + o_moff);
+    h.dev.mp_polys = (const uint32_t*)(pool + o_mpol);
+    h.dev.idx = (const uint32_t*)(pool + o_idx);
+    h.dev.mp_sum = (const uint2*)(pool + o_sum);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->geodata.size() + 1 >= 0xFFFFFFFFull) {
+        (void)hipFree(pool);
+        return fail(OSMT_INVALID_ARG, "geodata table too large");
+    }
+    *out_id = (uint32_t)ctx->geodata.size();
+    ctx->geodata.push_back(h);
+    return OSMT_OK;
+}
+
+int register_styles_body(osmt_ctx* ctx, const osmt_style_rec* st, size_t n, const double* dashes, size_t n_dashes, uint32_t* out_first) {
+    if (!ctx || !out_first) return fail(OSMT_INVALID_ARG, "NULL argument");
+    const int rc = validate_styles(st, n, dashes, n_dashes, ctx_image_count(ctx));
+    if (rc != OSMT_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->styles.size() + n >= 0xFFFFFFFFull || ctx->style_dashes.size() + n_dashes >= 0xFFFFFFFFull)
+        return fail(OSMT_INVALID_ARG, "style table too large");
+    const uint32_t first = (uint32_t)ctx->styles.size(), dash_base = (uint32_t)ctx->style_dashes.size();
+    ctx->styles.reserve(ctx->styles.size() + n);
+    ctx->style_dashes.insert(ctx->style_dashes.end(), dashes, dashes + n_dashes);
+    for (size_t i = 0; i < n; ++i) {
+        osmt_style_rec s = st[i];
+        s.dashes_off = s.has_dashes ? s.dashes_off + dash_base : 0u;
+        s.casing_dashes_off = s.has_casing_dashes ? s.casing_dashes_off + dash_base : 0u;
+        ctx->styles.push_back(s);
+    }
+    ctx->styles_dirty = true;
+    *out_first = first;
+    return OSMT_OK;
+}
+
+int scene_build_styled_body(osmt_ctx* ctx, const osmt_styled_batch* b, osmt_scene** out_scene) {
+    if (!ctx || !out_scene) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *out_scene = nullptr;
+    std::vector<uint32_t> tile_base;
+    int rc = validate_styled_batch(b, ctx, &tile_base);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    styles_snapshot ss;
+    rc = sync_styles(ctx, &ss);
+    if (rc != OSMT_OK) return rc;
+    osmt_ctx::geodata_host geo;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        geo = ctx->geodata[b->geodata_id];
+    }
+    const size_t n_tiles = b->n_tiles, total = tile_base[n_tiles], n_elems = 3 * total, n_blk = (n_elems + 255) / 256;
+    /* the span of `areas` the tiles name (their ranges may lie anywhere in the array; the device indexes it as the caller does) */
+    size_t a_lo = b->n_areas, a_hi = 0;
+    for (size_t t = 0; t < n_tiles; ++t)
+        if (b->tiles[t].n_areas) {
+            a_lo = std::min<size_t>(a_lo, b->tiles[t].area_off);
+            a_hi = std::max<size_t>(a_hi, (size_t)b->tiles[t].area_off + b->tiles[t].n_areas);
+        }
+    if (a_hi < a_lo) a_lo = a_hi = 0;
+
+    /* everything that lives only during the build: one allocation, given back at the end */
+    struct work_guard {
+        osmt_ctx* ctx;
+        hipStream_t st = nullptr;
+        char* work = nullptr;
+        uint32_t* ring_src = nullptr;
+        ~work_guard() {
+            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's arrays */
+            dev_free(ctx, work);
+            dev_free(ctx, ring_src);
+            stream_release(ctx, st);
+        }
+    } wg{ctx};
+    HIP_TRY(stream_acquire(ctx, &wg.st));
+    hipStream_t st = wg.st;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    const size_t o_tiles = carve(n_tiles * sizeof(osmt_styled_tile)), o_base = carve((n_tiles + 1) * 4), o_areas = carve((a_hi - a_lo) * sizeof(osmt_styled_area));
+    const size_t o_keys = carve(total * 16), o_sorted = carve(total * 4), o_pre = carve((size_t)OSMT_SQ_N * (n_elems + 1) * 4);
+    const size_t o_blk = carve((size_t)OSMT_SQ_N * std::max<size_t>(n_blk, 1) * 8), o_tot = carve(OSMT_STYLED_TOTALS * 8);
+    {
+        const hipError_t e = dev_alloc(ctx, (void**)&wg.work, off + 256);
+        if (e != hipSuccess) {
+            wg.work = nullptr;
+            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the styled build failed: %s", off, hipGetErrorString(e));
+        }
+    }
+    char* w = wg.work;
+    if (n_tiles) HIP_TRY(hipMemcpyAsync(w + o_tiles, b->tiles, n_tiles * sizeof(osmt_styled_tile), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w + o_base, tile_base.data(), (n_tiles + 1) * 4, hipMemcpyHostToDevice, st));
+    if (a_hi > a_lo) HIP_TRY(hipMemcpyAsync(w + o_areas, b->areas + a_lo, (a_hi - a_lo) * sizeof(osmt_styled_area), hipMemcpyHostToDevice, st));
+    osmt_styled_pass P;
+    memset(&P, 0, sizeof P);
+    P.geo = geo.dev;
+    P.styles = ss.styles;
+    P.style_rank = ss.rank;
+    P.style_dashes = ss.dashes;
+    P.tiles = (const osmt_styled_tile*)(w + o_tiles);
+    P.tile_base = (const uint32_t*)(w + o_base);
+    P.areas = (const osmt_styled_area*)(w + o_areas) - a_lo; /* indexed with the caller's offsets, from a_lo on */
+    P.n_tiles = (uint32_t)n_tiles;
+    P.n_elems = (uint32_t)n_elems;
+    P.scale = b->scale;
+    P.use_caps = b->use_caps_for_dashes ? 1u : 0u;
+    P.keys = (ulonglong2*)(w + o_keys);
+    P.sorted = (uint32_t*)(w + o_sorted);
+    P.pre = (uint32_t*)(w + o_pre);
+    P.blk = (unsigned long long*)(w + o_blk);
+    P.totals = (unsigned long long*)(w + o_tot);
+    /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the two launch sequences, one line on stderr */
+    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct ev_guard {
+        hipEvent_t* ev;
+        ~ev_guard() {
+            for (int i = 0; i < 4; ++i)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } evg{ev};
+    if (trace)
+        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+    if (trace) HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(osmt_launch_styled_count(P, st));
+    if (trace) HIP_TRY(hipEventRecord(ev[1], st));
+    unsigned long long tot[OSMT_STYLED_TOTALS];
+    HIP_TRY(hipMemcpyAsync(tot, P.totals, sizeof tot, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    static const char* const what[OSMT_SQ_N] = {"ops", "rings", "node references", "dashes", "stroke ops", "64-edge blocks", "virtual stroke segments"};
+    for (int q = 0; q < OSMT_SQ_N; ++q)
+        if (tot[q] >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "styled batch needs %llu %s (> 2^32): split the batch", tot[q], what[q]);
+    const size_t n_ops = tot[OSMT_SQ_OPS], n_rings = tot[OSMT_SQ_RINGS], n_pts = tot[OSMT_SQ_REFS], n_dashes = tot[OSMT_SQ_DASHES];
+    const size_t n_strokes = tot[OSMT_SQ_STROKES], n_blocks = tot[OSMT_SQ_BLOCKS], n_vsegs = tot[OSMT_SQ_VSEGS];
+
+    osmt_scene* s = new (std::nothrow) osmt_scene();
+    if (!s) return fail(OSMT_OOM, "out of host memory");
+    s->own_stream = st; /* until the build is complete: everything about the scene happens on this stream */
+    s->ctx = ctx;
+    ctx->refs.fetch_add(1);
+    s->h_err = err_slot_acquire(ctx);
+    s->n_jobs = (uint32_t)n_tiles;
+    s->max_job_ops = (uint32_t)tot[OSMT_SQ_N];
+    s->n_ops = (uint32_t)n_ops;
+    s->n_rings = (uint32_t)n_rings;
+    s->n_pts = (uint32_t)n_pts;
+    s->n_dashes = (uint32_t)n_dashes;
+    s->n_strokes = (uint32_t)n_strokes;
+    s->n_blk = (uint32_t)n_blocks;
+    s->n_vsegs = (uint32_t)n_vsegs;
+    s->scale = b->scale;
+    s->coord_kind = OSMT_COORD_NODE_REF;
+    /* the front arrays in the order of scene_upload_impl — without a node table: d_latlon is the registered one */
+    off = 0;
+    const size_t o_jobs = carve(n_tiles * sizeof(osmt_tile_job)), o_ops = carve(n_ops * sizeof(osmt_op)), o_rings = carve(n_rings * sizeof(osmt_ring));
+    const size_t o_refs = carve(n_pts * 4), o_pts = carve(n_pts * 8), o_dashes = carve((n_dashes + 1) * 8), o_ptjob = carve(n_pts * 4);
+    const size_t o_opaux = carve(n_ops * 4), o_opblk = carve(n_ops * 4), o_opvseg = carve(n_ops * 4), o_opjob = carve(n_ops * 4);
+    const scene_back bk = scene_carve_back(off, n_tiles, n_ops, n_strokes, n_blocks, n_vsegs, b->scale);
+    s->bytes = off + 256;
+    hipError_t e = dev_alloc(ctx, (void**)&s->d_base, s->bytes);
+    if (e == hipSuccess) {
+        e = dev_alloc(ctx, (void**)&wg.ring_src, std::max<size_t>(n_rings, 1) * 4);
+        if (e != hipSuccess) wg.ring_src = nullptr;
+    } else {
+        s->d_base = nullptr;
+    }
+    if (e != hipSuccess) {
+        dev_free(ctx, s->d_base);
+        scene_delete(s);
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
+    }
+    char* base = s->d_base;
+    s->d_jobs = (osmt_tile_job*)(base + o_jobs);
+    s->d_ops = (osmt_op*)(base + o_ops);
+    s->d_rings = (osmt_ring*)(base + o_rings);
+    s->d_latlon = const_cast<double*>(geo.dev.nodes); /* not the scene's: the geodata snapshot's, never freed under it */
+    s->d_node_refs = (uint32_t*)(base + o_refs);
+    s->d_pts = (int32_t*)(base + o_pts);
+    s->d_dashes = (double*)(base + o_dashes);
+    s->d_pt_job = (uint32_t*)(base + o_ptjob);
+    s->d_op_aux = (uint32_t*)(base + o_opaux);
+    s->d_op_blk = (uint32_t*)(base + o_opblk);
+    s->d_op_vseg = (uint32_t*)(base + o_opvseg);
+    s->d_op_job = (uint32_t*)(base + o_opjob);
+    scene_point_back(s, base, bk);
+    P.jobs = s->d_jobs;
+    P.ops = s->d_ops;
+    P.rings = s->d_rings;
+    P.refs = s->d_node_refs;
+    P.dashes = s->d_dashes;
+    P.op_job = s->d_op_job;
+    P.op_aux = s->d_op_aux;
+    P.op_blk = s->d_op_blk;
+    P.op_vseg = s->d_op_vseg;
+    P.ring_src = wg.ring_src;
+    P.n_rings = (uint32_t)n_rings;
+    P.n_refs = (uint32_t)n_pts;
+    if (trace) (void)hipEventRecord(ev[2], st);
+    e = osmt_launch_styled_emit(P, st);
+    if (e == hipSuccess) e = osmt_launch_ptjob(s->d_jobs, s->n_jobs, s->d_pt_job, s->n_pts, st);
+    if (trace) (void)hipEventRecord(ev[3], st);
+    if (e != hipSuccess) {
+        osmt_scene_free(s);
+        return fail(OSMT_HIP_ERROR, "styled build failed: %s", hipGetErrorString(e));
+    }
+    rc = scene_size_arenas(ctx, s, n_ops - n_strokes, false);
+    if (rc == OSMT_OK) {
+        e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(OSMT_HIP_ERROR, "styled build failed: %s", hipGetErrorString(e));
+    }
+    if (rc != OSMT_OK) {
+        osmt_scene_free(s);
+        return rc;
+    }
+    if (trace) {
+        float ms_count = 0.f, ms_emit = 0.f;
+        (void)hipEventElapsedTime(&ms_count, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&ms_emit, ev[2], ev[3]);
+        fprintf(stderr, "osmt styled build: sort + count + scan kernels %.1f us, emit kernels %.1f us (%zu tiles, %zu areas, %zu ops)\n",
+                ms_count * 1e3, ms_emit * 1e3, n_tiles, total, n_ops);
+    }
+    s->own_stream = nullptr; /* from here on a public scene: waits go through its last-use events */
+    *out_scene = s;
+    return OSMT_OK;
+}
+
+int scene_read_display_list_body(osmt_ctx* ctx, osmt_scene* sc, osmt_tile_job* jobs, osmt_op* ops, osmt_ring* rings, uint32_t* refs, double* dashes,
+                                 size_t counts[5]) {
+    if (!ctx || !sc || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
+    const bool nr = sc->coord_kind == OSMT_COORD_NODE_REF;
+    counts[0] = sc->n_jobs, counts[1] = sc->n_ops, counts[2] = sc->n_rings, counts[3] = nr ? sc->n_pts : 0, counts[4] = sc->n_dashes;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(scene_wait_idle(sc));
+    if (jobs) HIP_TRY(copy_back(ctx, jobs, sc->d_jobs, (size_t)sc->n_jobs * sizeof(osmt_tile_job)));
+    if (ops) HIP_TRY(copy_back(ctx, ops, sc->d_ops, (size_t)sc->n_ops * sizeof(osmt_op)));
+    if (rings) HIP_TRY(copy_back(ctx, rings, sc->d_rings, (size_t)sc->n_rings * sizeof(osmt_ring)));
+    if (refs && nr) HIP_TRY(copy_back(ctx, refs, sc->d_node_refs, (size_t)sc->n_pts * 4));
+    if (dashes) HIP_TRY(copy_back(ctx, dashes, sc->d_dashes, (size_t)sc->n_dashes * 8));
+    return OSMT_OK;
+}
+
+}  // namespace
+
+int osmt_validate_geodata(const osmt_geodata_desc* geodata) {
+    return guarded([&] { return validate_geodata(geodata); });
+}
+int osmt_register_geodata(osmt_ctx* ctx, const osmt_geodata_desc* geodata, uint32_t* out_geodata_id) {
+    return guarded([&] { return register_geodata_body(ctx, geodata, out_geodata_id); });
+}
+int osmt_validate_styles(const osmt_style_rec* styles, size_t n, const double* dashes, size_t n_dashes, osmt_ctx* ctx) {
+    return guarded([&] { return validate_styles(styles, n, dashes, n_dashes, ctx_image_count(ctx)); });
+}
+int osmt_register_styles(osmt_ctx* ctx, const osmt_style_rec* styles, size_t n, const double* dashes, size_t n_dashes, uint32_t* out_first_style_id) {
+    return guarded([&] { return register_styles_body(ctx, styles, n, dashes, n_dashes, out_first_style_id); });
+}
+int osmt_validate_styled_batch(const osmt_styled_batch* batch, osmt_ctx* ctx) {
+    return guarded([&] { return validate_styled_batch(batch, ctx, nullptr); });
+}
+int osmt_scene_build_styled(osmt_ctx* ctx, const osmt_styled_batch* batch, osmt_scene** out_scene) {
+    return guarded([&] { return scene_build_styled_body(ctx, batch, out_scene); });
+}
+int osmt_scene_read_display_list(osmt_ctx* ctx, osmt_scene* scene, osmt_tile_job* jobs, osmt_op* ops, osmt_ring* rings, uint32_t* node_refs,
+                                 double* dashes, size_t counts[5]) {
+    return guarded([&] { return scene_read_display_list_body(ctx, scene, jobs, ops, rings, node_refs, dashes, counts); });
 }
 
 /* Glyph-run labels, first half: validates the instances, builds the (label, instance) pairs in label order, runs the

@@ -416,6 +416,56 @@ struct osmt_shape_pass {
 };
 /* k_text_shape: TextPlacer::text_to_glyphs of every label with text, osmt_text_glyph records into a.out */
 hipError_t osmt_launch_text_shape(const osmt_shape_pass& a, hipStream_t st);
+/* ---- display lists built on the device (osmt_styled.hip) ------------------------------------------------------- */
+/* a registered geodata file as the kernels read it: one allocation that never moves */
+struct osmt_geo_dev {
+    const double* nodes;      /* [n_nodes][2] */
+    const uint64_t* way_gid;  /* [n_ways] */
+    const uint64_t* mp_gid;   /* [n_mps] */
+    const uint32_t* way_off;  /* [n_ways + 1] into idx */
+    const uint32_t* poly_off; /* [n_polys + 1] into idx (the polygons' nodes sit behind the ways': already shifted) */
+    const uint32_t* mp_off;   /* [n_mps + 1] into mp_polys */
+    const uint32_t* mp_polys; /* polygon indices */
+    const uint32_t* idx;      /* node indices: the ways', then the polygons' */
+    const uint2* mp_sum;      /* [n_mps]: (rings of >= 2 nodes, their nodes in all), summed once at registration */
+};
+
+/* what is counted per (tile, pass, area) element and scanned in that order */
+enum { OSMT_SQ_OPS = 0, OSMT_SQ_RINGS, OSMT_SQ_REFS, OSMT_SQ_DASHES, OSMT_SQ_STROKES, OSMT_SQ_BLOCKS, OSMT_SQ_VSEGS, OSMT_SQ_N };
+#define OSMT_STYLED_TOTALS (OSMT_SQ_N + 1) /* the totals of the scans + the most ops of any tile */
+
+struct osmt_styled_pass {
+    osmt_geo_dev geo;
+    const osmt_style_rec* styles;
+    const uint32_t* style_rank; /* [n_styles]: dense rank under (layer or 0, is_foreground_fill, z_index); equal keys, equal rank */
+    const double* style_dashes; /* the styles' pool, unscaled */
+    const osmt_styled_tile* tiles;
+    const uint32_t* tile_base; /* [n_tiles + 1]: areas of the tiles in front (the tiles' ranges may lie anywhere in `areas`) */
+    const osmt_styled_area* areas;
+    uint32_t n_tiles;
+    uint32_t n_elems; /* 3 * tile_base[n_tiles]: element (t, p, k) = 3 * tile_base[t] + p * n_areas(t) + k */
+    uint32_t scale, use_caps;
+    /* work areas */
+    ulonglong2* keys;         /* [tile_base[n_tiles]]: the sort keys of tiles beyond the LDS tier */
+    uint32_t* sorted;         /* [tile_base[n_tiles]]: absolute area index, tile by tile in draw order */
+    uint32_t* pre;            /* [OSMT_SQ_N][n_elems + 1]: counts, then their exclusive scans (mod 2^32: exact once the totals fit) */
+    unsigned long long* blk;  /* [OSMT_SQ_N][blocks of 256 elements]: block totals, then their exclusive scan */
+    unsigned long long* totals; /* [OSMT_STYLED_TOTALS] */
+    /* the scene's arrays (emit pass) */
+    osmt_tile_job* jobs;
+    osmt_op* ops;
+    osmt_ring* rings;
+    uint32_t* refs;
+    double* dashes;
+    uint32_t *op_job, *op_aux, *op_blk, *op_vseg;
+    uint32_t* ring_src; /* [n_rings]: where in geo.idx a ring's nodes start */
+    uint32_t n_rings, n_refs;
+};
+/* k_styled_sort -> k_styled_count -> k_styled_scan_blocks -> k_styled_scan_apply -> k_styled_tilemax: everything up to the totals */
+hipError_t osmt_launch_styled_count(const osmt_styled_pass& a, hipStream_t st);
+/* k_styled_emit -> k_styled_jobs -> k_styled_refs */
+hipError_t osmt_launch_styled_emit(const osmt_styled_pass& a, hipStream_t st);
+
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

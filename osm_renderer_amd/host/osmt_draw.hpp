@@ -101,9 +101,35 @@ class Context {
         check(osmt_register_glyphs(ctx_, v, vertex_off, n_glyphs, &id));
         return id;
     }
+    /* display lists built on the GPU: a geodata file's topology (osmt::GeodataDesc in osmt_geodata.hpp fills the desc) and
+     * the stylesheet's Style records (osmt::style_rec_of in osmt_styled.hpp), registered once per context */
+    uint32_t register_geodata(const osmt_geodata_desc& desc) {
+        uint32_t id = 0;
+        check(osmt_register_geodata(ctx_, &desc, &id));
+        return id;
+    }
+    uint32_t register_styles(const std::vector<osmt_style_rec>& styles, const std::vector<double>& dash_pool) {
+        uint32_t first = 0;
+        check(osmt_register_styles(ctx_, styles.data(), styles.size(), dash_pool.data(), dash_pool.size(), &first));
+        return first;
+    }
 
   private:
     osmt_ctx* ctx_ = nullptr;
+};
+
+/* A scene whose display list the GPU built from a styled batch (osmt_scene_build_styled): what SceneBuilder::add_tile per
+ * tile + osmt_scene_upload give, from 8 bytes per styled area.  Render it with osmt_render_scene on raw(). */
+class StyledScene {
+  public:
+    StyledScene(Context& ctx, const osmt_styled_batch& batch) { check(osmt_scene_build_styled(ctx.raw(), &batch, &scene_)); }
+    ~StyledScene() { osmt_scene_free(scene_); }
+    StyledScene(const StyledScene&) = delete;
+    StyledScene& operator=(const StyledScene&) = delete;
+    osmt_scene* raw() const { return scene_; }
+
+  private:
+    osmt_scene* scene_ = nullptr;
 };
 
 struct Filler { /* fill.rs:11-14 */

@@ -33,6 +33,8 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/osmtile.h"
+
 namespace osmt {
 
 constexpr uint8_t GEODATA_MAX_ZOOM = 18; /* tile.rs:5 */
@@ -299,6 +301,43 @@ class GeodataReader {
     const uint32_t* ints_ = nullptr;
     size_t n_ints_ = 0;
     const char* strings_ = nullptr;
+};
+
+/* The flat arrays of a geodata file as osmt_register_geodata takes them, with owning vectors: the node table, the ways'
+ * and multipolygons' global ids, and the three reference lists as offset + index arrays.  `desc` points into the vectors:
+ * valid as long as this object lives and is not copied from. */
+struct GeodataDesc {
+    std::vector<double> nodes;
+    std::vector<uint64_t> way_ids, multipolygon_ids;
+    std::vector<uint32_t> way_node_off{0u}, way_nodes, polygon_node_off{0u}, polygon_nodes, multipolygon_polygon_off{0u}, multipolygon_polygons;
+    osmt_geodata_desc desc{};
+
+    explicit GeodataDesc(const GeodataReader& r) : nodes(r.node_table()) {
+        auto append = [](std::vector<uint32_t>& off, std::vector<uint32_t>& flat, std::pair<const uint32_t*, size_t> ids) {
+            flat.insert(flat.end(), ids.first, ids.first + ids.second);
+            if (flat.size() >= 0xFFFFFFFFull) throw std::runtime_error("geodata file too large for 32-bit offsets");
+            off.push_back((uint32_t)flat.size());
+        };
+        for (size_t i = 0; i < r.way_count(); ++i) {
+            way_ids.push_back(r.way_global_id(i));
+            append(way_node_off, way_nodes, r.way_node_ids(i));
+        }
+        for (size_t i = 0; i < r.polygon_count(); ++i) append(polygon_node_off, polygon_nodes, r.polygon_node_ids(i));
+        for (size_t i = 0; i < r.multipolygon_count(); ++i) {
+            multipolygon_ids.push_back(r.multipolygon_global_id(i));
+            append(multipolygon_polygon_off, multipolygon_polygons, r.multipolygon_polygon_ids(i));
+        }
+        desc.nodes = nodes.data(), desc.n_nodes = nodes.size() / 2;
+        desc.way_ids = way_ids.data(), desc.way_node_off = way_node_off.data(), desc.n_ways = way_ids.size();
+        desc.way_nodes = way_nodes.data(), desc.n_way_nodes = way_nodes.size();
+        desc.polygon_node_off = polygon_node_off.data(), desc.n_polygons = polygon_node_off.size() - 1;
+        desc.polygon_nodes = polygon_nodes.data(), desc.n_polygon_nodes = polygon_nodes.size();
+        desc.multipolygon_ids = multipolygon_ids.data(), desc.multipolygon_polygon_off = multipolygon_polygon_off.data();
+        desc.n_multipolygons = multipolygon_ids.size();
+        desc.multipolygon_polygons = multipolygon_polygons.data(), desc.n_multipolygon_polygons = multipolygon_polygons.size();
+    }
+    GeodataDesc(const GeodataDesc&) = delete;
+    GeodataDesc& operator=(const GeodataDesc&) = delete;
 };
 
 }  // namespace osmt

@@ -62,6 +62,50 @@ struct Style {
     std::optional<uint32_t> fill_image; /* id from osmt_register_image; empty: no fill-image, or its icon is not in the cache */
 };
 
+/* Style -> the fixed-size record osmt_register_styles takes: an Option becomes a has_* byte in front of its value, a dash
+ * list a range of `dash_pool` (appended here, UNSCALED: the device multiplies by the batch's scale, drawer.rs:170-171), a
+ * line cap an osmt_line_cap.  Values of empty Options are left zero. */
+inline osmt_style_rec style_rec_of(const Style& s, std::vector<double>& dash_pool) {
+    osmt_style_rec r{};
+    auto color = [](const std::optional<Color>& c, uint8_t& has, uint8_t (&rgb)[3]) {
+        has = c ? 1 : 0;
+        if (c) rgb[0] = c->r, rgb[1] = c->g, rgb[2] = c->b;
+    };
+    auto number = [](const std::optional<double>& v, uint8_t& has, double& out) {
+        has = v ? 1 : 0;
+        if (v) out = *v;
+    };
+    auto dashes = [&](const std::optional<std::vector<double>>& d, uint8_t& has, uint32_t& off, uint32_t& n) {
+        has = d ? 1 : 0;
+        if (!d) return;
+        off = (uint32_t)dash_pool.size();
+        n = (uint32_t)d->size();
+        dash_pool.insert(dash_pool.end(), d->begin(), d->end());
+    };
+    auto cap = [](const std::optional<LineCap>& c) -> uint8_t {
+        return !c ? OSMT_CAP_NONE : *c == LineCap::Butt ? OSMT_CAP_BUTT : *c == LineCap::Round ? OSMT_CAP_ROUND : OSMT_CAP_SQUARE;
+    };
+    r.has_layer = s.layer ? 1 : 0;
+    if (s.layer) r.layer = *s.layer;
+    r.z_index = s.z_index;
+    r.is_foreground_fill = s.is_foreground_fill ? 1 : 0;
+    color(s.color, r.has_color, r.color);
+    color(s.fill_color, r.has_fill_color, r.fill_color);
+    color(s.background_color, r.has_background_color, r.background_color);
+    color(s.casing_color, r.has_casing_color, r.casing_color);
+    number(s.opacity, r.has_opacity, r.opacity);
+    number(s.fill_opacity, r.has_fill_opacity, r.fill_opacity);
+    number(s.width, r.has_width, r.width);
+    number(s.casing_width, r.has_casing_width, r.casing_width);
+    dashes(s.dashes, r.has_dashes, r.dashes_off, r.n_dashes);
+    dashes(s.casing_dashes, r.has_casing_dashes, r.casing_dashes_off, r.n_casing_dashes);
+    r.line_cap = cap(s.line_cap);
+    r.casing_line_cap = cap(s.casing_line_cap);
+    r.has_fill_image = s.fill_image ? 1 : 0;
+    if (s.fill_image) r.fill_image = *s.fill_image;
+    return r;
+}
+
 /* one element of what Styler::style_entities returns: an entity of the tile (LOCAL id in the geodata file) and one
  * of its styles (one per MapCSS layer) */
 struct StyledEntity {

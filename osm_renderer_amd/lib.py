@@ -35,6 +35,8 @@ EXPORTS = [
     "osmt_register_font", "osmt_validate_string_labels", "osmt_scene_set_string_labels", "osmt_render_batch_rgb_strings",
     "osmt_scene_read_text_glyphs",
     "osmt_label_positions", "osmt_label_positions_begin", "osmt_label_positions_end", "osmt_label_positions_stats",
+    "osmt_validate_geodata", "osmt_register_geodata", "osmt_validate_styles", "osmt_register_styles", "osmt_validate_styled_batch",
+    "osmt_scene_build_styled", "osmt_scene_read_display_list",
 ]
 
 
@@ -135,6 +137,14 @@ def load():
         L.osmt_label_positions_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     if hasattr(L, "osmt_scene_read_label_cover"):  # absent only from older variant builds loaded through OSMT_LIB
         L.osmt_scene_read_label_cover.argtypes = [vp, vp, C.c_uint32, ip, dp, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "osmt_scene_build_styled"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_validate_geodata.argtypes = [C.POINTER(abi.GeodataDesc)]
+        L.osmt_register_geodata.argtypes = [vp, C.POINTER(abi.GeodataDesc), C.POINTER(C.c_uint32)]
+        L.osmt_validate_styles.argtypes = [C.POINTER(abi.StyleRec), C.c_size_t, dp, C.c_size_t, vp]
+        L.osmt_register_styles.argtypes = [vp, C.POINTER(abi.StyleRec), C.c_size_t, dp, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.osmt_validate_styled_batch.argtypes = [C.POINTER(abi.StyledBatch), vp]
+        L.osmt_scene_build_styled.argtypes = [vp, C.POINTER(abi.StyledBatch), C.POINTER(vp)]
+        L.osmt_scene_read_display_list.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

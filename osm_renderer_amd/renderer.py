@@ -18,6 +18,12 @@ def _torch():
     return torch
 
 
+def _styled():
+    from . import styled
+
+    return styled
+
+
 def _stream_ptr(stream=None):
     torch = _torch()
     s = torch.cuda.current_stream() if stream is None else stream
@@ -29,7 +35,7 @@ class Scene:
 
     def __init__(self, ctx, dl: DisplayList, labels=None):
         self.ctx = ctx
-        self.dl = dl
+        self._dl = dl
         self.n_jobs = dl.n_jobs
         self.dim = dl.dim
         b = dl.as_batch()
@@ -39,6 +45,41 @@ class Scene:
         self.labels = None
         if labels is not None:
             self.set_labels(labels)
+
+    @classmethod
+    def _built(cls, ctx, h, n_jobs, scale, nodes):
+        """A scene osmt_scene_build_styled made: its display list lives on the device only (`dl` reads it back on demand)."""
+        self = cls.__new__(cls)
+        self.ctx, self._h, self.n_jobs, self.dim, self.labels = ctx, h, n_jobs, abi.TILE_SIZE * scale, None
+        self._scale, self._nodes, self._dl = scale, nodes, None
+        return self
+
+    @property
+    def dl(self):
+        if self._dl is None:
+            self._dl = self.read_display_list()
+        return self._dl
+
+    @dl.setter
+    def dl(self, value):
+        self._dl = value
+
+    def read_display_list(self):
+        """osmt_scene_read_display_list: the device-resident display list of this scene, uploaded or built, as a
+        DisplayList (jobs, ops, rings, node references, dashes byte for byte as the renderer reads them)."""
+        from .display_list import JOB_DTYPE, OP_DTYPE, RING_DTYPE
+
+        L, n = load(), (C.c_size_t * 5)()
+        check(L.osmt_scene_read_display_list(self.ctx._h, self._h, None, None, None, None, None, n))
+        jobs, ops, rings = np.zeros(n[0], JOB_DTYPE), np.zeros(n[1], OP_DTYPE), np.zeros(n[2], RING_DTYPE)
+        refs, dashes = np.zeros(n[3], np.uint32), np.zeros(n[4], np.float64)
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+        check(L.osmt_scene_read_display_list(self.ctx._h, self._h, ptr(jobs), ptr(ops), ptr(rings), ptr(refs), ptr(dashes), n))
+        if self._dl is not None and self._dl.coord_kind != abi.COORD_NODE_REF:  # an uploaded scene with per-point coordinates
+            return DisplayList(jobs, ops, rings, self._dl.coords, dashes, self._dl.coord_kind, self._dl.scale)
+        nodes = self._dl.nodes if self._dl is not None else self._nodes
+        scale = self._dl.scale if self._dl is not None else self._scale
+        return DisplayList(jobs, ops, rings, refs, dashes, abi.COORD_NODE_REF, scale, nodes=nodes)
 
     def set_labels(self, labels):
         """osmt_scene_set_labels: attach (or, with None, detach) the label pass of every tile."""
@@ -254,6 +295,38 @@ class Context:
         out = C.c_uint32()
         check(load().osmt_register_image(self._h, img.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, C.byref(out)))
         return out.value
+
+    # -- display lists built on the GPU ---------------------------------------------
+    def register_geodata(self, geodata):
+        """osmt_register_geodata: uploads a styled.Geodata (a geodata file's topology); returns its id."""
+        d = geodata.as_desc()
+        out = C.c_uint32()
+        check(load().osmt_register_geodata(self._h, C.byref(d), C.byref(out)))
+        self._geodata_nodes = getattr(self, "_geodata_nodes", {})
+        self._geodata_nodes[out.value] = geodata.nodes
+        return out.value
+
+    def register_styles(self, styles, dashes=()):
+        """osmt_register_styles: appends styled.STYLE_REC_DTYPE records and the (unscaled) dash pool their dash ranges
+        index; returns the id of the first."""
+        st = np.ascontiguousarray(styles, dtype=_styled().STYLE_REC_DTYPE).reshape(-1)
+        pool = np.ascontiguousarray(dashes, dtype=np.float64).reshape(-1)
+        out = C.c_uint32()
+        check(load().osmt_register_styles(self._h, st.ctypes.data_as(C.POINTER(abi.StyleRec)) if len(st) else None, len(st),
+                                          pool.ctypes.data_as(C.POINTER(C.c_double)) if len(pool) else None, len(pool), C.byref(out)))
+        return out.value
+
+    def validate_styled(self, batch):
+        """osmt_validate_styled_batch against this context's registrations (host only); raises OsmtError."""
+        b = batch.as_batch()
+        check(load().osmt_validate_styled_batch(C.byref(b), self._h))
+
+    def build_styled(self, batch) -> Scene:
+        """osmt_scene_build_styled: the scene of a styled.StyledBatch, its display list built on the GPU."""
+        b = batch.as_batch()
+        h = C.c_void_p()
+        check(load().osmt_scene_build_styled(self._h, C.byref(b), C.byref(h)))
+        return Scene._built(self, h, batch.n_jobs, batch.scale, getattr(self, "_geodata_nodes", {}).get(batch.geodata_id))
 
     # -- glyph outlines (glyph-run labels) -----------------------------------------
     def register_glyphs(self, table):

@@ -1,0 +1,95 @@
+"""Styled batches: the inputs of osmt_scene_build_styled, backed by numpy arrays.
+
+Instead of a display list the caller registers a geodata file's topology (Geodata) and its stylesheet's Style records
+(STYLE_REC_DTYPE) once per context and sends, per tile, the (entity, style) pairs Styler::style_entities pushes
+(reference: src/mapcss/styler.rs:86-92,163-203); the GPU builds the display list.  The dtypes mirror include/osmtile.h.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import abi
+
+STYLE_REC_DTYPE = np.dtype(
+    [
+        ("layer", "<i8"), ("z_index", "<f8"), ("opacity", "<f8"), ("fill_opacity", "<f8"), ("width", "<f8"), ("casing_width", "<f8"),
+        ("fill_image", "<u4"), ("dashes_off", "<u4"), ("n_dashes", "<u4"), ("casing_dashes_off", "<u4"), ("n_casing_dashes", "<u4"),
+        ("has_layer", "u1"), ("is_foreground_fill", "u1"),
+        ("has_color", "u1"), ("color", "u1", (3,)),
+        ("has_fill_color", "u1"), ("fill_color", "u1", (3,)),
+        ("has_opacity", "u1"), ("has_fill_opacity", "u1"), ("has_width", "u1"), ("has_dashes", "u1"), ("line_cap", "u1"),
+        ("has_casing_color", "u1"), ("casing_color", "u1", (3,)),
+        ("has_casing_width", "u1"), ("has_casing_dashes", "u1"), ("casing_line_cap", "u1"), ("has_fill_image", "u1"),
+        ("has_background_color", "u1"), ("background_color", "u1", (3,)),
+        ("_pad", "u1"),
+    ]
+)
+STYLED_AREA_DTYPE = np.dtype([("entity", "<u4"), ("style", "<u4")])
+STYLED_TILE_DTYPE = np.dtype(
+    [("x", "<u4"), ("y", "<u4"), ("zoom", "u1"), ("has_canvas", "u1"), ("canvas_rgb", "u1", (3,)), ("_pad", "u1", (3,)), ("area_off", "<u4"),
+     ("n_areas", "<u4")]
+)
+assert STYLE_REC_DTYPE.itemsize == 96 and STYLED_AREA_DTYPE.itemsize == 8 and STYLED_TILE_DTYPE.itemsize == 24
+
+
+def _csr(lists, dtype=np.uint32):
+    off = np.zeros(len(lists) + 1, dtype=np.uint32)
+    if len(lists):
+        off[1:] = np.cumsum([len(v) for v in lists])
+    flat = np.array([x for v in lists for x in v], dtype=dtype)
+    return off, flat
+
+
+class Geodata:
+    """The flat arrays of osmt_geodata_desc.  nodes: [n, 2] (lat, lon); ways: [(global id, [node idx])]; polygons:
+    [[node idx]]; multipolygons: [(global id, [polygon idx])]."""
+
+    def __init__(self, nodes, ways=(), polygons=(), multipolygons=()):
+        self.nodes = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, 2)
+        self.way_ids = np.array([w[0] for w in ways], dtype=np.uint64)
+        self.way_node_off, self.way_nodes = _csr([w[1] for w in ways])
+        self.polygon_node_off, self.polygon_nodes = _csr(list(polygons))
+        self.multipolygon_ids = np.array([m[0] for m in multipolygons], dtype=np.uint64)
+        self.multipolygon_polygon_off, self.multipolygon_polygons = _csr([m[1] for m in multipolygons])
+
+    def as_desc(self):
+        """ctypes osmt_geodata_desc pointing into this object's arrays (keep `self` alive)."""
+        u32, u64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        d = abi.GeodataDesc()
+        d.nodes, d.n_nodes = self.nodes.ctypes.data_as(C.POINTER(C.c_double)), len(self.nodes)
+        d.way_ids, d.way_node_off, d.n_ways = self.way_ids.ctypes.data_as(u64), self.way_node_off.ctypes.data_as(u32), len(self.way_ids)
+        d.way_nodes, d.n_way_nodes = self.way_nodes.ctypes.data_as(u32), len(self.way_nodes)
+        d.polygon_node_off, d.n_polygons = self.polygon_node_off.ctypes.data_as(u32), len(self.polygon_node_off) - 1
+        d.polygon_nodes, d.n_polygon_nodes = self.polygon_nodes.ctypes.data_as(u32), len(self.polygon_nodes)
+        d.multipolygon_ids, d.multipolygon_polygon_off = self.multipolygon_ids.ctypes.data_as(u64), self.multipolygon_polygon_off.ctypes.data_as(u32)
+        d.n_multipolygons = len(self.multipolygon_ids)
+        d.multipolygon_polygons, d.n_multipolygon_polygons = self.multipolygon_polygons.ctypes.data_as(u32), len(self.multipolygon_polygons)
+        return d
+
+
+class StyledBatch:
+    """osmt_styled_batch.  tiles: [(zoom, x, y, ways, multipolygons)] with ways / multipolygons lists of (local id, style
+    id) in the order Styler::style_entities pushes them; canvas: (r, g, b) or None."""
+
+    def __init__(self, geodata_id, tiles, scale=1, use_caps_for_dashes=True, canvas=(241, 238, 232)):
+        self.geodata_id, self.scale, self.use_caps_for_dashes = int(geodata_id), int(scale), bool(use_caps_for_dashes)
+        self.tiles = np.zeros(len(tiles), STYLED_TILE_DTYPE)
+        areas = []
+        for t, (zoom, x, y, ways, mps) in zip(self.tiles, tiles):
+            t["zoom"], t["x"], t["y"] = zoom, x, y
+            if canvas is not None:
+                t["has_canvas"], t["canvas_rgb"] = 1, canvas
+            t["area_off"], t["n_areas"] = len(areas), len(ways) + len(mps)
+            areas += [(int(i), int(s)) for i, s in ways] + [(int(i) | abi.STYLED_MULTIPOLYGON, int(s)) for i, s in mps]
+        self.areas = np.array(areas, dtype=STYLED_AREA_DTYPE).reshape(-1)
+
+    @property
+    def n_jobs(self):
+        return len(self.tiles)
+
+    def as_batch(self):
+        b = abi.StyledBatch()
+        b.tiles, b.n_tiles = self.tiles.ctypes.data_as(C.POINTER(abi.StyledTile)), len(self.tiles)
+        b.areas, b.n_areas = self.areas.ctypes.data_as(C.POINTER(abi.StyledArea)), len(self.areas)
+        b.geodata_id, b.scale, b.use_caps_for_dashes = self.geodata_id, self.scale, int(self.use_caps_for_dashes)
+        return b

@@ -1,0 +1,206 @@
+"""What the feed costs: host-built display lists against display lists built on the GPU, on the same tiles.
+
+Workload: N z15 tiles (default 1024) over a synthetic world with config 2's per-tile content — 50 closed ways and 40 open
+ways of 6 nodes per tile, every tile with ways of its own — written as a geodata file, and a table of 64 styles.
+
+  (a) the host feed:   osmt::SceneBuilder::add_tile for every tile on one thread, then osmt_scene_upload
+  (b) the device feed: osmt_scene_build_styled over the registered geodata and styles (8 bytes per styled area)
+
+Both are timed in one process, alternating, from the caller's arrays to a scene that is complete on the device (each
+library call synchronises its stream before it returns); then each scene is rendered once and the pixels are compared.
+The device time of the new kernels comes from a child run with OSMT_TRACE_UPLOAD=1 (HIP events around the two launch
+sequences).  PCIe bytes are computed from the shapes.  One JSON document on stdout and in profiles/styled_feed_bench.json.
+
+    python tools/bench_styled_feed.py [--tiles 1024] [--reps 12] [--warmup 3] [--out profiles/styled_feed_bench.json]
+"""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+from osm_renderer_amd import abi, lib, styled  # noqa: E402
+from osm_renderer_amd.renderer import Context, Scene  # noqa: E402
+from tests._geodata import write_geodata  # noqa: E402
+from tests._styled_feed import recs_of  # noqa: E402
+from tests.test_styled_builder import _random_styles  # noqa: E402
+
+SO = os.path.join(ROOT, "tests", "_build", "libstyled_feed_bench.so")
+ZOOM, X0, Y0 = 15, 19800, 10250
+
+
+def _native():
+    src = os.path.join(ROOT, "tools", "styled_feed_bench.cpp")
+    deps = [src, os.path.join(ROOT, "tests", "styled_shim.cpp"), os.path.join(ROOT, "osm_renderer_amd", "host", "osmt_styled.hpp"), lib.LIB_PATH]
+    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in deps):
+        os.makedirs(os.path.dirname(SO), exist_ok=True)
+        pkg = os.path.join(ROOT, "osm_renderer_amd")
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO, src, "-L" + pkg, "-losmtile", "-Wl,-rpath," + pkg,
+                               "-Wl,-rpath-link,/opt/rocm/lib"])
+    lib.load()  # libosmtile.so (and the HIP runtime it binds to) first
+    L = C.CDLL(SO)
+    vp, sz = C.c_void_p, C.c_size_t
+    L.sfb_new.restype = vp
+    L.sfb_new.argtypes = [C.c_char_p, vp, sz, vp]
+    L.sfb_free.argtypes = [vp]
+    L.sfb_add_tile.argtypes = [vp, C.c_uint8, C.c_uint32, C.c_uint32, vp, vp, sz]
+    L.sfb_run_host_feed.argtypes = [vp, vp, C.c_uint32, vp, C.POINTER(vp), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.sfb_run_device_feed.argtypes = [vp, C.POINTER(abi.StyledBatch), C.POINTER(vp), C.POINTER(C.c_double)]
+    return L
+
+
+def _latlon(px, py):
+    """pixel coordinates at ZOOM (256 per tile) -> (lat, lon) degrees"""
+    n = 256.0 * (1 << ZOOM)
+    return math.degrees(math.atan(math.sinh(math.pi * (1.0 - 2.0 * py / n)))), px / n * 360.0 - 180.0
+
+
+def make_world(n_tiles, seed=2):
+    """config 2's content per tile: 50 closed ways (7-gons), 40 open ways of 6 nodes"""
+    rng = np.random.default_rng(seed)
+    side = int(math.ceil(math.sqrt(n_tiles)))
+    nodes, ways, tiles = [], [], []
+    for t in range(n_tiles):
+        tx, ty = X0 + t % side, Y0 + t // side
+        ids = []
+        for k in range(90):
+            cx, cy = rng.uniform(10, 246, 2)
+            if k < 50:
+                rad, ang = rng.uniform(4.0, 24.0), np.sort(rng.uniform(0, 2 * np.pi, 7))
+                pts = [(cx + rad * math.cos(a), cy + rad * math.sin(a)) for a in ang]
+                pts.append(pts[0])
+            else:
+                pts = [(cx, cy)]
+                for _ in range(5):
+                    pts.append((pts[-1][0] + rng.uniform(-20, 20), pts[-1][1] + rng.uniform(-20, 20)))
+            first = len(nodes)
+            for i, (x, y) in enumerate(pts[:-1] if k < 50 else pts):
+                lat, lon = _latlon(256.0 * tx + x, 256.0 * ty + y)
+                nodes.append((10**6 + len(nodes), lat, lon, {}))
+            nid = list(range(first, len(nodes)))
+            if k < 50:
+                nid.append(first)
+            ways.append((2 * 10**6 + len(ways), nid, {}))
+            ids.append(len(ways) - 1)
+        tiles.append((ZOOM, tx, ty, ids))
+    return nodes, ways, tiles
+
+
+def device_times(args):
+    """the same workload in a child with OSMT_TRACE_UPLOAD=1: medians of the two launch sequences of osmt_scene_build_styled"""
+    env = dict(os.environ, OSMT_TRACE_UPLOAD="1")
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--tiles", str(args.tiles), "--reps", str(args.reps), "--warmup", str(args.warmup),
+                        "--child"], env=env, capture_output=True, text=True, timeout=900)
+    rows = re.findall(r"osmt styled build: sort \+ count \+ scan kernels ([0-9.]+) us, emit kernels ([0-9.]+) us", p.stderr)
+    if p.returncode != 0 or len(rows) <= args.warmup:
+        raise RuntimeError("the traced child run failed:\n" + p.stderr[-2000:])
+    rows = np.array(rows[args.warmup:], dtype=np.float64)
+    return {"count_us_median": float(np.median(rows[:, 0])), "emit_us_median": float(np.median(rows[:, 1])),
+            "total_us_median": float(np.median(rows.sum(axis=1))), "runs": int(len(rows))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tiles", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=12)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "styled_feed_bench.json"))
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    assert args.reps >= 10 or args.child
+
+    L = _native()
+    rng = np.random.default_rng(1)
+    st, pool = _random_styles(rng, 64)
+    nodes, ways, tiles = make_world(args.tiles)
+    way_style = [rng.integers(0, len(st), len(ids)).astype(np.uint32) for _, _, _, ids in tiles]
+    tmp = tempfile.mkdtemp(prefix="styled_feed_")
+    path = os.path.join(tmp, "world.bin")
+    write_geodata(path, nodes, ways, tile_refs={})
+    ctx = Context(0)
+    geo = styled.Geodata([[n[1], n[2]] for n in nodes], [(w[0], w[1]) for w in ways])
+    gid = ctx.register_geodata(geo)
+    first = ctx.register_styles(recs_of(st), pool)
+    h = L.sfb_new(path.encode(), st.ctypes.data, len(st), pool.ctypes.data)
+    assert h
+    for (zoom, tx, ty, ids), ws in zip(tiles, way_style):
+        wi = np.array(ids, dtype=np.uint32)
+        L.sfb_add_tile(h, zoom, tx, ty, wi.ctypes.data, ws.ctypes.data, len(wi))
+    sb = styled.StyledBatch(gid, [(z, x, y, [(i, int(s) + first) for i, s in zip(ids, ws)], []) for (z, x, y, ids), ws in zip(tiles, way_style)])
+    b = sb.as_batch()
+    canvas = (C.c_uint8 * 3)(241, 238, 232)
+    counts = (C.c_uint64 * 5)()
+
+    def run(which):
+        sc, sec = C.c_void_p(), C.c_double()
+        if which == "a":
+            rc = L.sfb_run_host_feed(h, ctx._h, 1, canvas, C.byref(sc), C.byref(sec), counts)
+        else:
+            rc = L.sfb_run_device_feed(ctx._h, C.byref(b), C.byref(sc), C.byref(sec))
+        lib.check(rc)
+        return sc, sec.value
+
+    times = {"a": [], "b": []}
+    for rep in range(args.warmup + args.reps):
+        for which in ("a", "b") if rep % 2 == 0 else ("b", "a"):
+            sc, sec = run(which)
+            lib.load().osmt_scene_free(sc)
+            if rep >= args.warmup:
+                times[which].append(sec)
+    if args.child:
+        return
+    # the pixels agree
+    sa, _ = run("a")
+    sb_, _ = run("b")
+    scene_a, scene_b = Scene._built(ctx, sa, len(tiles), 1, geo.nodes), Scene._built(ctx, sb_, len(tiles), 1, geo.nodes)
+    pa, pb = ctx.render(scene_a).cpu().numpy(), ctx.render(scene_b).cpu().numpy()
+    scene_a.check()
+    scene_b.check()
+    same = bool(np.array_equal(pa, pb))
+    dl_a, dl_b = scene_a.read_display_list(), scene_b.read_display_list()
+    same_list = all(getattr(dl_a, k).tobytes() == getattr(dl_b, k).tobytes() for k in ("jobs", "ops", "rings", "coords", "dashes"))
+    scene_a.free()
+    scene_b.free()
+    L.sfb_free(h)
+
+    n_ops, n_rings, n_refs, n_dashes, n_nodes = (int(v) for v in counts)
+    T, A = len(tiles), len(sb.areas)
+    stat = lambda v: {"median_ms": float(np.median(v) * 1e3), "min_ms": float(np.min(v) * 1e3), "max_ms": float(np.max(v) * 1e3),
+                      "p25_ms": float(np.percentile(v, 25) * 1e3), "p75_ms": float(np.percentile(v, 75) * 1e3), "runs": len(v)}
+    res = {
+        "workload": {"tiles": T, "zoom": ZOOM, "closed_ways_per_tile": 50, "open_ways_per_tile": 40, "styles": int(len(st)), "areas": A, "ops": n_ops,
+                     "rings": n_rings, "node_refs": n_refs, "dashes": n_dashes, "nodes": n_nodes},
+        "host_feed_a": stat(times["a"]),
+        "device_feed_b": stat(times["b"]),
+        "speedup_median_a_over_b": float(np.median(times["a"]) / np.median(times["b"])),
+        "device_kernels_b": device_times(args),
+        "pcie_bytes_per_batch": {
+            # osmt_scene_upload: jobs, ops, rings, node refs, dashes, the node table, and the four op index tables
+            "host_feed_a": 32 * T + 64 * n_ops + 8 * n_rings + 4 * n_refs + 8 * n_dashes + 16 * n_nodes + 16 * n_ops,
+            # osmt_scene_build_styled: tiles, their area bases, areas; 64 bytes of totals back
+            "device_feed_b": 24 * T + 4 * (T + 1) + 8 * A + 64,
+            "registered_once_b": 16 * n_nodes + 8 * len(ways) + 4 * (len(ways) + 1) + 4 * len(geo.way_nodes) + 96 * len(st) + 4 * len(st) + 8 * len(pool),
+        },
+        "same_pixels": same,
+        "same_display_list": bool(same_list),
+    }
+    text = json.dumps(res, indent=1)
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    if not (same and same_list):
+        sys.exit("the two feeds disagree")
+
+
+if __name__ == "__main__":
+    main()
