@@ -694,6 +694,9 @@ int osmt_scene_build_styled(osmt_ctx* ctx, const osmt_styled_batch* batch, osmt_
  * ask for the sizes). */
 int osmt_scene_read_display_list(osmt_ctx* ctx, osmt_scene* scene, osmt_tile_job* jobs, osmt_op* ops, osmt_ring* rings,
                                  uint32_t* node_refs, double* dashes, size_t counts[5]);
+/* Inspection: the most ops of any tile of the scene, as the renderer knows it (a batch of at most 64 tiles runs the list
+ * kernel only if this exceeds 128).  Counted on the host for an uploaded scene, by k_styled_tilemax for a built one. */
+int osmt_scene_max_tile_ops(osmt_ctx* ctx, osmt_scene* scene, uint32_t* out_max_ops);
 
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */

@@ -2171,6 +2171,13 @@ int osmt_scene_read_display_list(osmt_ctx* ctx, osmt_scene* scene, osmt_tile_job
                                  double* dashes, size_t counts[5]) {
     return guarded([&] { return scene_read_display_list_body(ctx, scene, jobs, ops, rings, node_refs, dashes, counts); });
 }
+int osmt_scene_max_tile_ops(osmt_ctx* ctx, osmt_scene* scene, uint32_t* out_max_ops) {
+    return guarded([&] {
+        if (!ctx || !scene || !out_max_ops) return fail(OSMT_INVALID_ARG, "NULL argument");
+        *out_max_ops = scene->max_job_ops;
+        return (int)OSMT_OK;
+    });
+}
 
 /* Glyph-run labels, first half: validates the instances, builds the (label, instance) pairs in label order, runs the
  * count pass and reads back each label's window summary (osmt_label_extent, ~20 bytes per label) and the error word.

@@ -20,7 +20,9 @@
  *                         64 bits.
  *   k_styled_scan_blocks  one workgroup: exclusive scan of the block totals, the seven grand totals.
  *   k_styled_scan_apply   counts -> exclusive scans in (tile, pass, position) order = op order.  32-bit with wrap-around:
- *                         exact as soon as the host has seen that the 64-bit totals fit, and nothing is emitted before.
+ *                         a scan of non-negative terms whose true total is below 2^32 wrapped nowhere, so every offset
+ *                         is exact once the host has seen the 64-bit totals (k_styled_count's block sums, their scan
+ *                         and its carry: unsigned long long throughout) fit; nothing is emitted before.
  *   k_styled_tilemax      the most ops of any tile (the renderer chooses its list kernel by it).
  *   k_styled_emit         one lane per element again: the op header as four 16-byte stores, its rings, its scaled dashes,
  *                         op -> job / stroke slot / first block / first virtual segment.

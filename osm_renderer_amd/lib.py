@@ -36,7 +36,7 @@ EXPORTS = [
     "osmt_scene_read_text_glyphs",
     "osmt_label_positions", "osmt_label_positions_begin", "osmt_label_positions_end", "osmt_label_positions_stats",
     "osmt_validate_geodata", "osmt_register_geodata", "osmt_validate_styles", "osmt_register_styles", "osmt_validate_styled_batch",
-    "osmt_scene_build_styled", "osmt_scene_read_display_list",
+    "osmt_scene_build_styled", "osmt_scene_read_display_list", "osmt_scene_max_tile_ops",
 ]
 
 
@@ -145,6 +145,7 @@ def load():
         L.osmt_validate_styled_batch.argtypes = [C.POINTER(abi.StyledBatch), vp]
         L.osmt_scene_build_styled.argtypes = [vp, C.POINTER(abi.StyledBatch), C.POINTER(vp)]
         L.osmt_scene_read_display_list.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]
+        L.osmt_scene_max_tile_ops.argtypes = [vp, vp, C.POINTER(C.c_uint32)]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

@@ -81,6 +81,12 @@ class Scene:
         scale = self._dl.scale if self._dl is not None else self._scale
         return DisplayList(jobs, ops, rings, refs, dashes, abi.COORD_NODE_REF, scale, nodes=nodes)
 
+    def max_tile_ops(self):
+        """osmt_scene_max_tile_ops: the most ops of any tile, as the renderer knows it (it picks its list kernel by it)"""
+        out = C.c_uint32()
+        check(load().osmt_scene_max_tile_ops(self.ctx._h, self._h, C.byref(out)))
+        return out.value
+
     def set_labels(self, labels):
         """osmt_scene_set_labels: attach (or, with None, detach) the label pass of every tile."""
         if labels is None:

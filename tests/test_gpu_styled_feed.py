@@ -12,14 +12,11 @@ import pytest
 from osm_renderer_amd import abi, labels, lib, styled
 from osm_renderer_amd.display_list import DisplayList
 from osm_renderer_amd.lib import OsmtError
-from tests._geodata import Reader, write_geodata
-from tests._styled_feed import CachedReader, geodata_of, recs_of
+from tests._styled_feed import LAT0, LON0, CachedReader, _center_tile, _file, _square, geodata_of, recs_of
 from tests.test_styled_builder import (STYLE_DTYPE, _build_cpp, _icons, _lib, _ops_of, _random_styles, _scene, _styled, _twin_areas,
                                        _twin_ops)
 
 pytestmark = pytest.mark.gpu
-
-LAT0, LON0 = 55.75, 37.61
 
 
 def _batch(gid, tiles, first, scale=1, use_caps=True):
@@ -45,18 +42,6 @@ def _build_both(gpu_ctx, r, gid, tiles, st, pool, first, scale=1, use_caps=True)
     want = _build_cpp(_lib(), r, tiles, st, pool, scale, use_caps)
     scene = gpu_ctx.build_styled(_batch(gid, tiles, first, scale, use_caps))
     return scene, scene.read_display_list(), want
-
-
-def _file(tmp_path, oracle, nodes, ways, polygons, multis, name="w.bin"):
-    p = str(tmp_path / name)
-    write_geodata(p, nodes, ways, polygons, multis, max_zoom_tile=lambda a, b: oracle.coords_to_max_zoom_tile(a, b))
-    return Reader(p)
-
-
-def _center_tile(oracle, zoom=15, dx=0):
-    cx, cy = oracle.coords_to_max_zoom_tile(LAT0, LON0)
-    f = 1 << (18 - zoom)
-    return cx // f + dx, cy // f
 
 
 @pytest.mark.parametrize("seed,n_ways,scale,use_caps,with_oracle", [(13, 80, 1, True, True), (14, 50, 2, False, False)])
@@ -98,13 +83,6 @@ def test_built_list_equals_the_scene_builders_bit_for_bit(tmp_path, gpu_ctx, ora
     twin.free()
     scene.free()
     r.close()
-
-
-def _square(node, k, size=0.0004):
-    """a closed way of five nodes, the k-th of a row across the centre tile"""
-    lat, lon = LAT0 - 0.002 + 0.0003 * (k % 7), LON0 - 0.004 + 0.0011 * k
-    ids = [node(lat, lon), node(lat + size, lon), node(lat + size, lon + 1.5 * size), node(lat, lon + 1.5 * size)]
-    return ids + [ids[0]]
 
 
 def test_order_one_rule_at_a_time(tmp_path, gpu_ctx, oracle):

@@ -17,22 +17,11 @@ import pytest
 from osm_renderer_amd import abi
 from osm_renderer_amd.display_list import JOB_DTYPE, OP_DTYPE, RING_DTYPE, DisplayList
 from tests._geodata import ROOT, Reader, write_geodata
+from tests._styled_feed import STYLE_DTYPE
 from tests.test_geodata_reader import _world
 
 SHIM = os.path.join(ROOT, "tests", "_build", "libstyled_shim.so")
 
-STYLE_DTYPE = np.dtype(
-    [
-        ("layer", "<i8"), ("z_index", "<f8"), ("opacity", "<f8"), ("fill_opacity", "<f8"), ("width", "<f8"), ("casing_width", "<f8"),
-        ("fill_image", "<u4"), ("dashes_off", "<u4"), ("n_dashes", "<u4"), ("casing_dashes_off", "<u4"), ("n_casing_dashes", "<u4"),
-        ("has_layer", "u1"), ("is_foreground_fill", "u1"),
-        ("has_color", "u1"), ("color", "u1", (3,)),
-        ("has_fill_color", "u1"), ("fill_color", "u1", (3,)),
-        ("has_opacity", "u1"), ("has_fill_opacity", "u1"), ("has_width", "u1"), ("has_dashes", "u1"), ("line_cap", "u1"),
-        ("has_casing_color", "u1"), ("casing_color", "u1", (3,)),
-        ("has_casing_width", "u1"), ("has_casing_dashes", "u1"), ("casing_line_cap", "u1"), ("has_fill_image", "u1"),
-    ]
-)
 CAPS = {0: abi.CAP_NONE, 1: abi.CAP_BUTT, 2: abi.CAP_ROUND, 3: abi.CAP_SQUARE}
 
 

@@ -9,9 +9,10 @@ import pytest
 
 from osm_renderer_amd import abi, lib, styled
 from tests._geodata import Reader, write_geodata
-from tests._styled_feed import recs_of, shim
+from tests import _styled_order_model as model
+from tests._styled_feed import _center_tile, extreme_id_world, fill_only_styles, random_pairs, recs_of, shim
 from tests.test_geodata_reader import _world
-from tests.test_styled_builder import STYLE_DTYPE, _random_styles
+from tests.test_styled_builder import STYLE_DTYPE, _build_cpp, _lib, _random_styles
 
 
 def _validate_styles(recs, pool, ctx=None):
@@ -221,3 +222,25 @@ def test_validate_styled_batch_refusals_that_need_no_registration():
     assert rc == abi.UNSUPPORTED and "tile 0" in msg and "65537" in msg
     L = lib.load()
     assert L.osmt_validate_styled_batch(None, None) == abi.INVALID_ARG
+
+
+@pytest.mark.parametrize("seed,n", [(41, abi.STYLED_MAX_TILE_AREAS), (42, 3001)])
+def test_scene_builder_against_the_order_model(tmp_path, oracle, seed, n):
+    """osmt::SceneBuilder, the yardstick of the GPU build, against a third statement of the order that shares no code with it
+    (tests/_styled_order_model.py) — at the tile limit, where the Python twin is too slow to go, over global ids at both
+    ends of 32, 63 and 64 bits, z-indices that include both zeros, 1e300 and the smallest denormal"""
+    r = extreme_id_world(tmp_path, oracle)
+    way_gids, mp_gids = model.gids(r)
+    assert {0, 1, 2**32 - 1, 2**32, 2**63 - 1, 2**63, 2**64 - 1} <= set(way_gids) and {2**63, 2**64 - 1} <= set(way_gids) & set(mp_gids)
+    rng = np.random.default_rng(seed)
+    st, pool = fill_only_styles(rng)
+    assert len(st) == 200 and len({tuple(c) for c in st["fill_color"]}) == 200
+    assert {0.0, 1.0, 2.5, -1.0, 1e300, 5e-324} <= set(st["z_index"].tolist()) and np.signbit(st["z_index"][st["z_index"] == 0.0]).any()
+    n_w = int(0.8 * n)
+    ways, mps = random_pairs(rng, n_w, r.n_ways, len(st)), random_pairs(rng, n - n_w, r.n_multipolygons, len(st))
+    tx, ty = _center_tile(oracle)
+    dl = _build_cpp(_lib(), r, [(15, tx, ty, ways, mps)], st, pool, 1, True)
+    assert int(dl.jobs["n_ops"][0]) == n  # every entity has a ring, every style fills: one op per area
+    want = model.expected_marks(ways, mps, st, way_gids, mp_gids, *model.first_nodes(r))
+    assert np.array_equal(model.seen_marks(dl, 0), want)
+    r.close()
