@@ -698,6 +698,86 @@ int osmt_scene_read_display_list(osmt_ctx* ctx, osmt_scene* scene, osmt_tile_job
  * kernel only if this exceeds 128).  Counted on the host for an uploaded scene, by k_styled_tilemax for a built one. */
 int osmt_scene_max_tile_ops(osmt_ctx* ctx, osmt_scene* scene, uint32_t* out_max_ops);
 
+/* ---- scenes built from tile coordinates: the tile query and the style lookup on the GPU ------------------------ */
+/* The fourth way to a scene.  With the z18 tile index of a registered geodata file (reader.rs:217-229) and a table
+ * "entity -> the styles Styler::style_entities pushes for it" registered too, a tile is 16 bytes: (zoom, x, y) and its
+ * canvas.  The GPU does GeodataReader::get_entities_in_tile_with_neighbors (reader.rs:60-133) — the z18 tiles of the 3 x 3
+ * neighbourhood, their way and multipolygon lists gathered, sorted, made unique, multipolygons without polygons dropped —
+ * expands every entity by its bound styles and hands the resulting styled batch to the build of osmt_scene_build_styled:
+ * byte for byte the display list that call builds from the batch osmt::styled_areas_of_tile (host/osmt_tilequery.hpp)
+ * makes on the host.  The osm_ids debug filter of the reference is not supported. */
+
+#define OSMT_QUERY_MAX_TILE_CANDIDATES (1u << 20) /* way (or multipolygon) references gathered for ONE tile before dedup */
+#define OSMT_QUERY_LDS_CANDIDATES 8192u           /* up to here a tile's candidates are sorted in LDS (32 KB of u32) */
+#define OSMT_BINDINGS_NONE 0xFFFFFFFFu
+
+/* the z18 tile storage of a geodata file (reader.rs:217-229, saver.rs:167-226), ways and multipolygons only */
+typedef struct osmt_tile_index_desc {
+    const uint32_t* tile_xy; /* [n_tiles][2] = (x, y) at zoom 18, STRICTLY ascending lexicographically */
+    size_t n_tiles;
+    const uint32_t* way_off; /* [n_tiles + 1] into ways */
+    const uint32_t* ways;    /* local way ids, any order, duplicates allowed */
+    size_t n_way_refs;
+    const uint32_t* multipolygon_off; /* [n_tiles + 1] into multipolygons */
+    const uint32_t* multipolygons;
+    size_t n_multipolygon_refs;
+} osmt_tile_index_desc;
+
+/* (entity -> style ids) for a range of zooms: what Styler::style_entities pushes for the entity, in push order */
+typedef struct osmt_style_bindings_desc {
+    uint32_t geodata_id;
+    uint8_t zoom_lo, zoom_hi, _pad[2]; /* inclusive */
+    const uint32_t* way_style_off;     /* [n_ways + 1] */
+    const uint32_t* way_styles;        /* ids from osmt_register_styles */
+    size_t n_way_styles;
+    const uint32_t* multipolygon_style_off; /* [n_multipolygons + 1] */
+    const uint32_t* multipolygon_styles;
+    size_t n_multipolygon_styles;
+} osmt_style_bindings_desc;
+
+typedef struct osmt_query_tile { /* 16 bytes */
+    uint32_t x, y;
+    uint8_t zoom, has_canvas, canvas_rgb[3], _pad[3];
+} osmt_query_tile;
+
+typedef struct osmt_tile_batch {
+    const osmt_query_tile* tiles;
+    size_t n_tiles;
+    uint32_t geodata_id, scale, use_caps_for_dashes, _pad;
+    uint32_t bindings_of_zoom[OSMT_MAX_ZOOM + 1]; /* id from osmt_register_style_bindings, or OSMT_BINDINGS_NONE */
+} osmt_tile_batch;
+
+/* The checks osmt_register_tile_index runs first, without a device.  OSMT_INVALID_ARG, naming the offender: a NULL array with a
+ * non-zero count; offsets that do not start at 0, decrease or do not end at the pool length; tile_xy not strictly ascending; a
+ * coordinate >= 2^18 (with it the reference's u32 wrap at the world's edge is a plain clip: a neighbour column at x = -1 or
+ * x = 2^zoom holds no tile); a way or multipolygon id >= n_ways / n_multipolygons. */
+int osmt_validate_tile_index(const osmt_tile_index_desc* index, size_t n_ways, size_t n_multipolygons);
+/* Uploads the tile index of a registered geodata file: one allocation that never moves and lives as long as the context,
+ * together with a column directory (the distinct x and the first tile of each) built here.  One index per geodata id: a second
+ * registration is OSMT_INVALID_ARG. */
+int osmt_register_tile_index(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tile_index_desc* index);
+/* OSMT_INVALID_ARG: an unknown geodata id (a NULL `ctx` has none), zoom_lo > zoom_hi or zoom_hi > OSMT_MAX_ZOOM, bad offsets
+ * (as above), a style id that is not registered at the time of the call. */
+int osmt_validate_style_bindings(const osmt_style_bindings_desc* b, osmt_ctx* ctx);
+/* Appends a bindings table.  Append-only with the snapshot semantics of images, fonts and styles: a table's device copy never
+ * moves, a later registration never disturbs a scene that is already built. */
+int osmt_register_style_bindings(osmt_ctx* ctx, const osmt_style_bindings_desc* b, uint32_t* out_bindings_id);
+/* OSMT_INVALID_ARG: zoom > 18, x or y >= 2^zoom, scale outside 1..OSMT_MAX_SCALE, an unknown geodata id or one without a tile
+ * index, a tile whose zoom has OSMT_BINDINGS_NONE, a bindings id that is unknown, belongs to another geodata id or does not
+ * cover that zoom.  The same tile may appear any number of times; 0 tiles are a valid batch. */
+int osmt_validate_tile_batch(const osmt_tile_batch* batch, osmt_ctx* ctx);
+/* Query, style lookup and display-list build on the device (csrc/osmt_tilequery.hip, then the kernels of
+ * osmt_scene_build_styled).  OSMT_UNSUPPORTED with the exact figure: a tile that gathers more than
+ * OSMT_QUERY_MAX_TILE_CANDIDATES references of one kind, a candidate or area total that does not fit 32 bits, a tile with more
+ * than OSMT_STYLED_MAX_TILE_AREAS areas; and whatever osmt_scene_build_styled refuses.  *out_scene is NULL on every error and
+ * the context stays usable.  The scene is an ordinary OSMT_COORD_NODE_REF scene. */
+int osmt_scene_build_tiles(osmt_ctx* ctx, const osmt_tile_batch* batch, osmt_scene** out_scene);
+/* Inspection: the styled batch the device derived for a scene of osmt_scene_build_tiles (tiles[i].area_off / n_areas index
+ * `areas`); NULL outputs ask for sizes (*n_areas is always set; the tile count is the scene's).  OSMT_INVALID_ARG for a scene
+ * from any other source, or when areas_cap is less than *n_areas. */
+int osmt_scene_read_styled_areas(osmt_ctx* ctx, osmt_scene* scene, osmt_styled_tile* tiles, osmt_styled_area* areas,
+                                 size_t areas_cap, size_t* n_areas);
+
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */
 int osmt_project(osmt_ctx* ctx, const double* latlon, size_t n, uint8_t zoom, uint32_t tile_x, uint32_t tile_y,

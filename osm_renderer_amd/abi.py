@@ -29,6 +29,9 @@ STYLED_MAX_TILE_AREAS = 65536  # (entity, style) pairs of one tile of an osmt_st
 STYLED_LDS_AREAS = 2048  # up to here osmt_scene_build_styled sorts a tile in LDS
 STYLED_MULTIPOLYGON = 0x80000000  # osmt_styled_area.entity: the entity is a multipolygon
 MAX_SCALE = 4
+QUERY_MAX_TILE_CANDIDATES = 1 << 20  # references of one kind osmt_scene_build_tiles gathers for one tile before dedup
+QUERY_LDS_CANDIDATES = 8192  # up to here a tile's candidates are sorted in LDS
+BINDINGS_NONE = 0xFFFFFFFF  # osmt_tile_batch.bindings_of_zoom: the zoom has no bindings
 
 
 class Op(C.Structure):
@@ -339,6 +342,57 @@ class StyledBatch(C.Structure):
     ]
 
 
+class TileIndexDesc(C.Structure):
+    _fields_ = [
+        ("tile_xy", C.POINTER(C.c_uint32)),
+        ("n_tiles", C.c_size_t),
+        ("way_off", C.POINTER(C.c_uint32)),
+        ("ways", C.POINTER(C.c_uint32)),
+        ("n_way_refs", C.c_size_t),
+        ("multipolygon_off", C.POINTER(C.c_uint32)),
+        ("multipolygons", C.POINTER(C.c_uint32)),
+        ("n_multipolygon_refs", C.c_size_t),
+    ]
+
+
+class StyleBindingsDesc(C.Structure):
+    _fields_ = [
+        ("geodata_id", C.c_uint32),
+        ("zoom_lo", C.c_uint8),
+        ("zoom_hi", C.c_uint8),
+        ("_pad", C.c_uint8 * 2),
+        ("way_style_off", C.POINTER(C.c_uint32)),
+        ("way_styles", C.POINTER(C.c_uint32)),
+        ("n_way_styles", C.c_size_t),
+        ("multipolygon_style_off", C.POINTER(C.c_uint32)),
+        ("multipolygon_styles", C.POINTER(C.c_uint32)),
+        ("n_multipolygon_styles", C.c_size_t),
+    ]
+
+
+class QueryTile(C.Structure):
+    _fields_ = [
+        ("x", C.c_uint32),
+        ("y", C.c_uint32),
+        ("zoom", C.c_uint8),
+        ("has_canvas", C.c_uint8),
+        ("canvas_rgb", C.c_uint8 * 3),
+        ("_pad", C.c_uint8 * 3),
+    ]
+
+
+class TileBatch(C.Structure):
+    _fields_ = [
+        ("tiles", C.POINTER(QueryTile)),
+        ("n_tiles", C.c_size_t),
+        ("geodata_id", C.c_uint32),
+        ("scale", C.c_uint32),
+        ("use_caps_for_dashes", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("bindings_of_zoom", C.c_uint32 * (MAX_ZOOM + 1)),
+    ]
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32)]
 
@@ -361,3 +415,7 @@ assert C.sizeof(StyledArea) == 8
 assert C.sizeof(StyledTile) == 24
 assert C.sizeof(StyledBatch) == 48
 assert C.sizeof(GeodataDesc) == 128
+assert C.sizeof(TileIndexDesc) == 64
+assert C.sizeof(StyleBindingsDesc) == 56
+assert C.sizeof(QueryTile) == 16
+assert C.sizeof(TileBatch) == 112

@@ -134,8 +134,20 @@ struct osmt_ctx {
         size_t n_nodes = 0, n_ways = 0, n_mps = 0;
         void* d_pool = nullptr;
         osmt_geo_dev dev{};
+        /* its z18 tile index (osmt_register_tile_index): at most one, an allocation of its own under the same rules */
+        void* d_index = nullptr;
+        osmt_tq_index_dev ix{};
     };
     std::vector<geodata_host> geodata;
+    /* the tables of osmt_register_style_bindings: append-only, one device allocation each that never moves, so a build
+     * that holds a table's pointers is not disturbed by a later registration */
+    struct bindings_host {
+        uint32_t geodata_id = 0;
+        uint8_t zoom_lo = 0, zoom_hi = 0;
+        void* d_pool = nullptr;
+        osmt_tq_bind_dev dev{};
+    };
+    std::vector<bindings_host> bindings;
     /* the styles of osmt_register_styles, same snapshot rules as the glyph table: a registration followed by a build makes
      * a new device triple (records, ranks, dash pool), the old one joins image_graveyard */
     std::vector<osmt_style_rec> styles;
@@ -253,6 +265,12 @@ struct osmt_scene {
      * osmt_scene_read_text_glyphs under the same rules */
     osmt_text_glyph* d_text_glyphs = nullptr;
     uint32_t n_text_glyphs = 0;
+    /* a scene of osmt_scene_build_tiles: the styled batch the device derived, kept for osmt_scene_read_styled_areas */
+    char* d_tq = nullptr;           /* tiles + tile_base */
+    char* d_tq_areas_buf = nullptr; /* the areas */
+    const osmt_styled_tile* d_tq_tiles = nullptr;
+    const osmt_styled_area* d_tq_areas = nullptr;
+    size_t n_tq_areas = 0;
 };
 
 namespace {
@@ -606,7 +624,12 @@ void ctx_teardown(osmt_ctx* ctx) {
     for (auto& f : ctx->fonts)
         if (f->d_pool) (void)hipFree(f->d_pool);
     for (auto& g : ctx->geodata)
+    {
         if (g.d_pool) (void)hipFree(g.d_pool);
+        if (g.d_index) (void)hipFree(g.d_index);
+    }
+    for (auto& b : ctx->bindings)
+        if (b.d_pool) (void)hipFree(b.d_pool);
     if (ctx->d_styles) (void)hipFree(ctx->d_styles);
     if (ctx->d_style_rank) (void)hipFree(ctx->d_style_rank);
     if (ctx->d_style_dashes) (void)hipFree(ctx->d_style_dashes);
@@ -1636,6 +1659,8 @@ void osmt_scene_free(osmt_scene* s) {
     dev_free(s->ctx, s->d_lab_base);
     dev_free(s->ctx, s->d_text_inst);
     dev_free(s->ctx, s->d_text_glyphs);
+    dev_free(s->ctx, s->d_tq);
+    dev_free(s->ctx, s->d_tq_areas_buf);
     stage_release(s->ctx, s->h_stage);
     scene_delete(s);
 }
@@ -1939,53 +1964,38 @@ int register_styles_body(osmt_ctx* ctx, const osmt_style_rec* st, size_t n, cons
     return OSMT_OK;
 }
 
-int scene_build_styled_body(osmt_ctx* ctx, const osmt_styled_batch* b, osmt_scene** out_scene) {
-    if (!ctx || !out_scene) return fail(OSMT_INVALID_ARG, "NULL argument");
-    *out_scene = nullptr;
-    std::vector<uint32_t> tile_base;
-    int rc = validate_styled_batch(b, ctx, &tile_base);
-    if (rc != OSMT_OK) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    styles_snapshot ss;
-    rc = sync_styles(ctx, &ss);
-    if (rc != OSMT_OK) return rc;
-    osmt_ctx::geodata_host geo;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        geo = ctx->geodata[b->geodata_id];
-    }
-    const size_t n_tiles = b->n_tiles, total = tile_base[n_tiles], n_elems = 3 * total, n_blk = (n_elems + 255) / 256;
-    /* the span of `areas` the tiles name (their ranges may lie anywhere in the array; the device indexes it as the caller does) */
-    size_t a_lo = b->n_areas, a_hi = 0;
-    for (size_t t = 0; t < n_tiles; ++t)
-        if (b->tiles[t].n_areas) {
-            a_lo = std::min<size_t>(a_lo, b->tiles[t].area_off);
-            a_hi = std::max<size_t>(a_hi, (size_t)b->tiles[t].area_off + b->tiles[t].n_areas);
-        }
-    if (a_hi < a_lo) a_lo = a_hi = 0;
+/* a styled batch on the device: what both entries hand to the shared half of the build */
+struct styled_src {
+    const osmt_styled_tile* tiles;
+    const uint32_t* tile_base; /* [n_tiles + 1] */
+    const osmt_styled_area* areas; /* indexed with the tiles' area_off */
+    size_t n_tiles, total;         /* total = tile_base[n_tiles] */
+    uint32_t scale, use_caps;
+};
 
+/* The half of the build both entries share: everything from osmt_launch_styled_count on, over a styled batch that is on the
+ * device already (uploaded by osmt_scene_build_styled, derived by osmt_scene_build_tiles), on the caller's stream. */
+int styled_build_back(osmt_ctx* ctx, hipStream_t st, const osmt_ctx::geodata_host& geo, const styles_snapshot& ss, const styled_src& in,
+                      osmt_scene** out_scene) {
+    const size_t n_tiles = in.n_tiles, total = in.total, n_elems = 3 * total, n_blk = (n_elems + 255) / 256;
     /* everything that lives only during the build: one allocation, given back at the end */
     struct work_guard {
         osmt_ctx* ctx;
-        hipStream_t st = nullptr;
+        hipStream_t st;
         char* work = nullptr;
         uint32_t* ring_src = nullptr;
         ~work_guard() {
-            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's arrays */
+            (void)hipStreamSynchronize(st); /* nothing may still read the buffers */
             dev_free(ctx, work);
             dev_free(ctx, ring_src);
-            stream_release(ctx, st);
         }
-    } wg{ctx};
-    HIP_TRY(stream_acquire(ctx, &wg.st));
-    hipStream_t st = wg.st;
+    } wg{ctx, st};
     size_t off = 0;
     auto carve = [&](size_t bytes) {
         const size_t o = off;
         off = align_up(off + bytes, 256);
         return o;
     };
-    const size_t o_tiles = carve(n_tiles * sizeof(osmt_styled_tile)), o_base = carve((n_tiles + 1) * 4), o_areas = carve((a_hi - a_lo) * sizeof(osmt_styled_area));
     const size_t o_keys = carve(total * 16), o_sorted = carve(total * 4), o_pre = carve((size_t)OSMT_SQ_N * (n_elems + 1) * 4);
     const size_t o_blk = carve((size_t)OSMT_SQ_N * std::max<size_t>(n_blk, 1) * 8), o_tot = carve(OSMT_STYLED_TOTALS * 8);
     {
@@ -1996,22 +2006,20 @@ int scene_build_styled_body(osmt_ctx* ctx, const osmt_styled_batch* b, osmt_scen
         }
     }
     char* w = wg.work;
-    if (n_tiles) HIP_TRY(hipMemcpyAsync(w + o_tiles, b->tiles, n_tiles * sizeof(osmt_styled_tile), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(w + o_base, tile_base.data(), (n_tiles + 1) * 4, hipMemcpyHostToDevice, st));
-    if (a_hi > a_lo) HIP_TRY(hipMemcpyAsync(w + o_areas, b->areas + a_lo, (a_hi - a_lo) * sizeof(osmt_styled_area), hipMemcpyHostToDevice, st));
+    int rc = OSMT_OK;
     osmt_styled_pass P;
     memset(&P, 0, sizeof P);
     P.geo = geo.dev;
     P.styles = ss.styles;
     P.style_rank = ss.rank;
     P.style_dashes = ss.dashes;
-    P.tiles = (const osmt_styled_tile*)(w + o_tiles);
-    P.tile_base = (const uint32_t*)(w + o_base);
-    P.areas = (const osmt_styled_area*)(w + o_areas) - a_lo; /* indexed with the caller's offsets, from a_lo on */
+    P.tiles = in.tiles;
+    P.tile_base = in.tile_base;
+    P.areas = in.areas;
     P.n_tiles = (uint32_t)n_tiles;
     P.n_elems = (uint32_t)n_elems;
-    P.scale = b->scale;
-    P.use_caps = b->use_caps_for_dashes ? 1u : 0u;
+    P.scale = in.scale;
+    P.use_caps = in.use_caps;
     P.keys = (ulonglong2*)(w + o_keys);
     P.sorted = (uint32_t*)(w + o_sorted);
     P.pre = (uint32_t*)(w + o_pre);
@@ -2056,14 +2064,14 @@ int scene_build_styled_body(osmt_ctx* ctx, const osmt_styled_batch* b, osmt_scen
     s->n_strokes = (uint32_t)n_strokes;
     s->n_blk = (uint32_t)n_blocks;
     s->n_vsegs = (uint32_t)n_vsegs;
-    s->scale = b->scale;
+    s->scale = in.scale;
     s->coord_kind = OSMT_COORD_NODE_REF;
     /* the front arrays in the order of scene_upload_impl — without a node table: d_latlon is the registered one */
     off = 0;
     const size_t o_jobs = carve(n_tiles * sizeof(osmt_tile_job)), o_ops = carve(n_ops * sizeof(osmt_op)), o_rings = carve(n_rings * sizeof(osmt_ring));
     const size_t o_refs = carve(n_pts * 4), o_pts = carve(n_pts * 8), o_dashes = carve((n_dashes + 1) * 8), o_ptjob = carve(n_pts * 4);
     const size_t o_opaux = carve(n_ops * 4), o_opblk = carve(n_ops * 4), o_opvseg = carve(n_ops * 4), o_opjob = carve(n_ops * 4);
-    const scene_back bk = scene_carve_back(off, n_tiles, n_ops, n_strokes, n_blocks, n_vsegs, b->scale);
+    const scene_back bk = scene_carve_back(off, n_tiles, n_ops, n_strokes, n_blocks, n_vsegs, in.scale);
     s->bytes = off + 256;
     hipError_t e = dev_alloc(ctx, (void**)&s->d_base, s->bytes);
     if (e == hipSuccess) {
@@ -2132,6 +2140,525 @@ int scene_build_styled_body(osmt_ctx* ctx, const osmt_styled_batch* b, osmt_scen
     return OSMT_OK;
 }
 
+int scene_build_styled_body(osmt_ctx* ctx, const osmt_styled_batch* b, osmt_scene** out_scene) {
+    if (!ctx || !out_scene) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *out_scene = nullptr;
+    std::vector<uint32_t> tile_base;
+    int rc = validate_styled_batch(b, ctx, &tile_base);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    styles_snapshot ss;
+    rc = sync_styles(ctx, &ss);
+    if (rc != OSMT_OK) return rc;
+    osmt_ctx::geodata_host geo;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        geo = ctx->geodata[b->geodata_id];
+    }
+    const size_t n_tiles = b->n_tiles;
+    /* the span of `areas` the tiles name (their ranges may lie anywhere in the array; the device indexes it as the caller does) */
+    size_t a_lo = b->n_areas, a_hi = 0;
+    for (size_t t = 0; t < n_tiles; ++t)
+        if (b->tiles[t].n_areas) {
+            a_lo = std::min<size_t>(a_lo, b->tiles[t].area_off);
+            a_hi = std::max<size_t>(a_hi, (size_t)b->tiles[t].area_off + b->tiles[t].n_areas);
+        }
+    if (a_hi < a_lo) a_lo = a_hi = 0;
+    /* the caller's arrays on the device: given back when the build is over */
+    struct front_guard {
+        osmt_ctx* ctx;
+        hipStream_t st = nullptr;
+        char* work = nullptr;
+        ~front_guard() {
+            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's arrays */
+            dev_free(ctx, work);
+            stream_release(ctx, st);
+        }
+    } fg{ctx};
+    HIP_TRY(stream_acquire(ctx, &fg.st));
+    hipStream_t st = fg.st;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    const size_t o_tiles = carve(n_tiles * sizeof(osmt_styled_tile)), o_base = carve((n_tiles + 1) * 4), o_areas = carve((a_hi - a_lo) * sizeof(osmt_styled_area));
+    {
+        const hipError_t e = dev_alloc(ctx, (void**)&fg.work, off + 256);
+        if (e != hipSuccess) {
+            fg.work = nullptr;
+            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the styled build failed: %s", off, hipGetErrorString(e));
+        }
+    }
+    char* w = fg.work;
+    if (n_tiles) HIP_TRY(hipMemcpyAsync(w + o_tiles, b->tiles, n_tiles * sizeof(osmt_styled_tile), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w + o_base, tile_base.data(), (n_tiles + 1) * 4, hipMemcpyHostToDevice, st));
+    if (a_hi > a_lo) HIP_TRY(hipMemcpyAsync(w + o_areas, b->areas + a_lo, (a_hi - a_lo) * sizeof(osmt_styled_area), hipMemcpyHostToDevice, st));
+    styled_src in;
+    in.tiles = (const osmt_styled_tile*)(w + o_tiles);
+    in.tile_base = (const uint32_t*)(w + o_base);
+    in.areas = (const osmt_styled_area*)(w + o_areas) - a_lo; /* indexed with the caller's offsets, from a_lo on */
+    in.n_tiles = n_tiles, in.total = tile_base[n_tiles];
+    in.scale = b->scale, in.use_caps = b->use_caps_for_dashes ? 1u : 0u;
+    return styled_build_back(ctx, st, geo, ss, in, out_scene);
+}
+
+/* ---- scenes built from tile coordinates (include/osmtile.h, csrc/osmt_tilequery.hip) ---------------------------------- */
+/* offs: count + 1 entries from 0 to `total`, never decreasing */
+int check_offsets_of(const char* who, const char* what, const uint32_t* offs, size_t count, size_t total) {
+    if (offs[0] != 0u) return fail(OSMT_INVALID_ARG, "%s: %s[0] is %u, not 0", who, what, offs[0]);
+    for (size_t i = 0; i < count; ++i)
+        if (offs[i + 1] < offs[i])
+            return fail(OSMT_INVALID_ARG, "%s: %s[%zu] = %u is less than the entry before it (%u)", who, what, i + 1, offs[i + 1], offs[i]);
+    if ((size_t)offs[count] != total)
+        return fail(OSMT_INVALID_ARG, "%s: %s[%zu] = %u does not end at the %zu entries it indexes", who, what, count, offs[count], total);
+    return OSMT_OK;
+}
+
+int validate_tile_index(const osmt_tile_index_desc* x, size_t n_ways, size_t n_mps) {
+    if (!x) return fail(OSMT_INVALID_ARG, "tile index is NULL");
+    if ((x->n_tiles && !x->tile_xy) || !x->way_off || (x->n_way_refs && !x->ways) || !x->multipolygon_off || (x->n_multipolygon_refs && !x->multipolygons))
+        return fail(OSMT_INVALID_ARG, "tile index: NULL array (every offset array has at least its first entry)");
+    if (x->n_tiles >= 0xFFFFFFFFull || x->n_way_refs >= 0xFFFFFFFFull || x->n_multipolygon_refs >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "tile index: too large for 32-bit indices");
+    int rc = check_offsets_of("tile index", "way_off", x->way_off, x->n_tiles, x->n_way_refs);
+    if (rc == OSMT_OK) rc = check_offsets_of("tile index", "multipolygon_off", x->multipolygon_off, x->n_tiles, x->n_multipolygon_refs);
+    if (rc != OSMT_OK) return rc;
+    const uint32_t world = 1u << OSMT_MAX_ZOOM;
+    for (size_t i = 0; i < x->n_tiles; ++i) {
+        const uint32_t tx = x->tile_xy[2 * i], ty = x->tile_xy[2 * i + 1];
+        if (tx >= world || ty >= world) return fail(OSMT_INVALID_ARG, "tile index: tile %zu = (%u, %u) outside the zoom-18 world (coordinates < %u)", i, tx, ty, world);
+        if (i) {
+            const uint32_t px = x->tile_xy[2 * i - 2], py = x->tile_xy[2 * i - 1];
+            if (px > tx || (px == tx && py >= ty))
+                return fail(OSMT_INVALID_ARG, "tile index: tile %zu = (%u, %u) does not come after tile %zu = (%u, %u) (strictly ascending by x, then y)", i, tx, ty,
+                            i - 1, px, py);
+        }
+    }
+    for (size_t i = 0; i < x->n_way_refs; ++i)
+        if (x->ways[i] >= n_ways) return fail(OSMT_INVALID_ARG, "tile index: ways[%zu] = %u is not a way (%zu ways)", i, x->ways[i], n_ways);
+    for (size_t i = 0; i < x->n_multipolygon_refs; ++i)
+        if (x->multipolygons[i] >= n_mps)
+            return fail(OSMT_INVALID_ARG, "tile index: multipolygons[%zu] = %u is not a multipolygon (%zu multipolygons)", i, x->multipolygons[i], n_mps);
+    return OSMT_OK;
+}
+
+int register_tile_index_body(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tile_index_desc* x) {
+    if (!ctx) return fail(OSMT_INVALID_ARG, "NULL argument");
+    size_t n_ways = 0, n_mps = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (geodata_id >= ctx->geodata.size()) return fail(OSMT_INVALID_ARG, "geodata id %u is not registered (%zu files)", geodata_id, ctx->geodata.size());
+        if (ctx->geodata[geodata_id].d_index) return fail(OSMT_INVALID_ARG, "geodata id %u has a tile index already (one per file)", geodata_id);
+        n_ways = ctx->geodata[geodata_id].n_ways, n_mps = ctx->geodata[geodata_id].n_mps;
+    }
+    const int rc = validate_tile_index(x, n_ways, n_mps);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    /* the column directory: the distinct x and the first tile of each */
+    const size_t n = x->n_tiles;
+    std::vector<uint32_t> col_x, col_first, tile_y(n);
+    for (size_t i = 0; i < n; ++i) {
+        tile_y[i] = x->tile_xy[2 * i + 1];
+        if (i == 0 || x->tile_xy[2 * i] != x->tile_xy[2 * i - 2]) {
+            col_x.push_back(x->tile_xy[2 * i]);
+            col_first.push_back((uint32_t)i);
+        }
+    }
+    col_first.push_back((uint32_t)n);
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_cx = carve(col_x.size() * 4), o_cf = carve(col_first.size() * 4), o_ty = carve(n * 4), o_wo = carve((n + 1) * 4);
+    const size_t o_w = carve(x->n_way_refs * 4), o_mo = carve((n + 1) * 4), o_m = carve(x->n_multipolygon_refs * 4);
+    char* pool = nullptr;
+    HIP_TRY(hipMalloc((void**)&pool, off));
+    hipError_t e = hipSuccess;
+    auto put = [&](size_t o, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+    };
+    put(o_cx, col_x.data(), col_x.size() * 4);
+    put(o_cf, col_first.data(), col_first.size() * 4);
+    put(o_ty, tile_y.data(), n * 4);
+    put(o_wo, x->way_off, (n + 1) * 4);
+    put(o_w, x->ways, x->n_way_refs * 4);
+    put(o_mo, x->multipolygon_off, (n + 1) * 4);
+    put(o_m, x->multipolygons, x->n_multipolygon_refs * 4);
+    if (e != hipSuccess) {
+        (void)hipFree(pool);
+        return fail(OSMT_HIP_ERROR, "tile index upload failed: %s", hipGetErrorString(e));
+    }
+    osmt_tq_index_dev d{};
+    d.col_x = (const uint32_t*)(pool + o_cx);
+    d.col_first = (const uint32_t*)(pool + o_cf);
+    d.tile_y = (const uint32_t*)(pool + o_ty);
+    d.way_off = (const uint32_t*)(pool + o_wo);
+    d.ways = (const uint32_t*)(pool + o_w);
+    d.mp_off = (const uint32_t*)(pool + o_mo);
+    d.mps = (const uint32_t*)(pool + o_m);
+    d.n_cols = (uint32_t)col_x.size();
+    d.n_tiles = (uint32_t)n;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->geodata[geodata_id].d_index) { /* another thread was first */
+        (void)hipFree(pool);
+        return fail(OSMT_INVALID_ARG, "geodata id %u has a tile index already (one per file)", geodata_id);
+    }
+    ctx->geodata[geodata_id].d_index = pool;
+    ctx->geodata[geodata_id].ix = d;
+    return OSMT_OK;
+}
+
+int validate_style_bindings(const osmt_style_bindings_desc* b, osmt_ctx* ctx) {
+    if (!b) return fail(OSMT_INVALID_ARG, "style bindings are NULL");
+    if (b->zoom_lo > b->zoom_hi || b->zoom_hi > OSMT_MAX_ZOOM)
+        return fail(OSMT_INVALID_ARG, "style bindings: zoom range %u..%u (zoom_lo <= zoom_hi <= %u)", b->zoom_lo, b->zoom_hi, OSMT_MAX_ZOOM);
+    if (!ctx) return fail(OSMT_INVALID_ARG, "style bindings: geodata id %u is not registered (no context)", b->geodata_id);
+    size_t n_ways = 0, n_mps = 0, n_styles = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (b->geodata_id >= ctx->geodata.size())
+            return fail(OSMT_INVALID_ARG, "style bindings: geodata id %u is not registered (%zu files)", b->geodata_id, ctx->geodata.size());
+        n_ways = ctx->geodata[b->geodata_id].n_ways, n_mps = ctx->geodata[b->geodata_id].n_mps;
+        n_styles = ctx->styles.size();
+    }
+    if (!b->way_style_off || (b->n_way_styles && !b->way_styles) || !b->multipolygon_style_off || (b->n_multipolygon_styles && !b->multipolygon_styles))
+        return fail(OSMT_INVALID_ARG, "style bindings: NULL array (every offset array has at least its first entry)");
+    if (b->n_way_styles >= 0xFFFFFFFFull || b->n_multipolygon_styles >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "style bindings: too large for 32-bit indices");
+    int rc = check_offsets_of("style bindings", "way_style_off", b->way_style_off, n_ways, b->n_way_styles);
+    if (rc == OSMT_OK) rc = check_offsets_of("style bindings", "multipolygon_style_off", b->multipolygon_style_off, n_mps, b->n_multipolygon_styles);
+    if (rc != OSMT_OK) return rc;
+    for (size_t i = 0; i < b->n_way_styles; ++i)
+        if (b->way_styles[i] >= n_styles)
+            return fail(OSMT_INVALID_ARG, "style bindings: way_styles[%zu] = %u is not a registered style (%zu styles)", i, b->way_styles[i], n_styles);
+    for (size_t i = 0; i < b->n_multipolygon_styles; ++i)
+        if (b->multipolygon_styles[i] >= n_styles)
+            return fail(OSMT_INVALID_ARG, "style bindings: multipolygon_styles[%zu] = %u is not a registered style (%zu styles)", i, b->multipolygon_styles[i],
+                        n_styles);
+    return OSMT_OK;
+}
+
+int register_style_bindings_body(osmt_ctx* ctx, const osmt_style_bindings_desc* b, uint32_t* out_id) {
+    if (!ctx || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    const int rc = validate_style_bindings(b, ctx);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    size_t n_ways = 0, n_mps = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        n_ways = ctx->geodata[b->geodata_id].n_ways, n_mps = ctx->geodata[b->geodata_id].n_mps;
+    }
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_wo = carve((n_ways + 1) * 4), o_w = carve(b->n_way_styles * 4), o_mo = carve((n_mps + 1) * 4), o_m = carve(b->n_multipolygon_styles * 4);
+    char* pool = nullptr;
+    HIP_TRY(hipMalloc((void**)&pool, off));
+    hipError_t e = hipSuccess;
+    auto put = [&](size_t o, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+    };
+    put(o_wo, b->way_style_off, (n_ways + 1) * 4);
+    put(o_w, b->way_styles, b->n_way_styles * 4);
+    put(o_mo, b->multipolygon_style_off, (n_mps + 1) * 4);
+    put(o_m, b->multipolygon_styles, b->n_multipolygon_styles * 4);
+    if (e != hipSuccess) {
+        (void)hipFree(pool);
+        return fail(OSMT_HIP_ERROR, "style bindings upload failed: %s", hipGetErrorString(e));
+    }
+    osmt_ctx::bindings_host h;
+    h.geodata_id = b->geodata_id, h.zoom_lo = b->zoom_lo, h.zoom_hi = b->zoom_hi;
+    h.d_pool = pool;
+    h.dev.way_off = (const uint32_t*)(pool + o_wo);
+    h.dev.way_styles = (const uint32_t*)(pool + o_w);
+    h.dev.mp_off = (const uint32_t*)(pool + o_mo);
+    h.dev.mp_styles = (const uint32_t*)(pool + o_m);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->bindings.size() + 1 >= 0xFFFFFFFFull) {
+        (void)hipFree(pool);
+        return fail(OSMT_INVALID_ARG, "bindings table too large");
+    }
+    *out_id = (uint32_t)ctx->bindings.size();
+    ctx->bindings.push_back(h);
+    return OSMT_OK;
+}
+
+/* bind (optional): the device tables of the zooms the batch's tiles have */
+int validate_tile_batch(const osmt_tile_batch* b, osmt_ctx* ctx, osmt_tq_bind_dev* bind) {
+    if (!b) return fail(OSMT_INVALID_ARG, "tile batch is NULL");
+    if (b->scale < 1 || b->scale > OSMT_MAX_SCALE) return fail(OSMT_INVALID_ARG, "scale %u not in 1..%u", b->scale, OSMT_MAX_SCALE);
+    if (b->n_tiles && !b->tiles) return fail(OSMT_INVALID_ARG, "NULL array with non-zero count");
+    if (b->n_tiles >= 0x7FFFFFFFull / 64) return fail(OSMT_INVALID_ARG, "tile batch too large for 32-bit indices (tiles)");
+    bool zoom_used[OSMT_MAX_ZOOM + 1] = {};
+    size_t first_of_zoom[OSMT_MAX_ZOOM + 1] = {};
+    for (size_t t = 0; t < b->n_tiles; ++t) {
+        const osmt_query_tile& q = b->tiles[t];
+        if (q.zoom > OSMT_MAX_ZOOM) return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u > MAX_ZOOM (src/tile.rs:5)", t, q.zoom);
+        if (q.x >= (1u << q.zoom) || q.y >= (1u << q.zoom))
+            return fail(OSMT_INVALID_ARG, "tile %zu: (x, y) = (%u, %u) outside the %u x %u tiles of zoom %u", t, q.x, q.y, 1u << q.zoom, 1u << q.zoom, q.zoom);
+        if (!zoom_used[q.zoom]) zoom_used[q.zoom] = true, first_of_zoom[q.zoom] = t;
+    }
+    if (!ctx) return fail(OSMT_INVALID_ARG, "geodata id %u is not registered (no context)", b->geodata_id);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (b->geodata_id >= ctx->geodata.size()) return fail(OSMT_INVALID_ARG, "geodata id %u is not registered (%zu files)", b->geodata_id, ctx->geodata.size());
+    if (!ctx->geodata[b->geodata_id].d_index) return fail(OSMT_INVALID_ARG, "geodata id %u has no tile index (osmt_register_tile_index)", b->geodata_id);
+    for (uint32_t z = 0; z <= OSMT_MAX_ZOOM; ++z) {
+        if (!zoom_used[z]) continue;
+        const uint32_t id = b->bindings_of_zoom[z];
+        if (id == OSMT_BINDINGS_NONE) return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u has no bindings (OSMT_BINDINGS_NONE)", first_of_zoom[z], z);
+        if (id >= ctx->bindings.size())
+            return fail(OSMT_INVALID_ARG, "tile %zu: bindings id %u of zoom %u is not registered (%zu tables)", first_of_zoom[z], id, z, ctx->bindings.size());
+        const osmt_ctx::bindings_host& h = ctx->bindings[id];
+        if (h.geodata_id != b->geodata_id)
+            return fail(OSMT_INVALID_ARG, "tile %zu: bindings id %u of zoom %u belongs to geodata id %u, not %u", first_of_zoom[z], id, z, h.geodata_id, b->geodata_id);
+        if (z < h.zoom_lo || z > h.zoom_hi)
+            return fail(OSMT_INVALID_ARG, "tile %zu: bindings id %u covers zooms %u..%u, not zoom %u", first_of_zoom[z], id, h.zoom_lo, h.zoom_hi, z);
+        if (bind) bind[z] = h.dev;
+    }
+    return OSMT_OK;
+}
+
+int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene** out_scene) {
+    if (!ctx || !out_scene) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *out_scene = nullptr;
+    osmt_tq_bind_dev bind[OSMT_MAX_ZOOM + 1];
+    memset(bind, 0, sizeof bind);
+    int rc = validate_tile_batch(b, ctx, bind);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    styles_snapshot ss;
+    rc = sync_styles(ctx, &ss);
+    if (rc != OSMT_OK) return rc;
+    osmt_ctx::geodata_host geo;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        geo = ctx->geodata[b->geodata_id];
+    }
+    const size_t n_tiles = b->n_tiles;
+    /* work[0]: per tile, work[1]: per item, work[2]: per candidate — given back at the end */
+    struct work_guard {
+        osmt_ctx* ctx;
+        hipStream_t st = nullptr;
+        char* work[3] = {nullptr, nullptr, nullptr};
+        ~work_guard() {
+            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's tiles */
+            for (char* p : work) dev_free(ctx, p);
+            stream_release(ctx, st);
+        }
+    } wg{ctx};
+    HIP_TRY(stream_acquire(ctx, &wg.st));
+    hipStream_t st = wg.st;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    auto alloc = [&](char** out, const char* what) {
+        const hipError_t e = dev_alloc(ctx, (void**)out, off + 256);
+        if (e == hipSuccess) return (int)OSMT_OK;
+        *out = nullptr;
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the tile query (%s) failed: %s", off, what, hipGetErrorString(e));
+    };
+    /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the stages, one line on stderr */
+    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    enum { EV_SPAN0, EV_SPAN1, EV_COL0, EV_COL1, EV_GATHER0, EV_SORT0, EV_MARK0, EV_MARK1, EV_EMIT0, EV_EMIT1, EV_N };
+    hipEvent_t ev[EV_N] = {};
+    struct ev_guard {
+        hipEvent_t* ev;
+        ~ev_guard() {
+            for (int i = 0; i < EV_N; ++i)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } evg{ev};
+    if (trace)
+        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+
+    unsigned long long tot[OSMT_TQ_N] = {};
+    osmt_tq_pass P;
+    memset(&P, 0, sizeof P);
+    off = 0;
+    const size_t o_q = carve(n_tiles * sizeof(osmt_query_tile)), o_bind = carve(sizeof bind), o_c0 = carve(n_tiles * 4), o_ib = carve((n_tiles + 1) * 4);
+    const size_t o_tw = carve((n_tiles + 1) * 4), o_tm = carve((n_tiles + 1) * 4), o_tot = carve(OSMT_TQ_N * 8), o_blk0 = carve((n_tiles / 256 + 1) * 8);
+    rc = alloc(&wg.work[0], "tiles");
+    if (rc != OSMT_OK) return rc;
+    char* w0 = wg.work[0];
+    size_t n_items = 0, n_way_cand = 0, n_mp_cand = 0, n_cand = 0, n_areas = 0;
+    if (n_tiles) {
+        HIP_TRY(hipMemcpyAsync(w0 + o_q, b->tiles, n_tiles * sizeof(osmt_query_tile), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(w0 + o_bind, bind, sizeof bind, hipMemcpyHostToDevice, st));
+        P.ix = geo.ix;
+        P.geo_mp_off = geo.dev.mp_off;
+        P.bind = (const osmt_tq_bind_dev*)(w0 + o_bind);
+        P.q = (const osmt_query_tile*)(w0 + o_q);
+        P.n_tiles = (uint32_t)n_tiles;
+        P.span_c0 = (uint32_t*)(w0 + o_c0);
+        P.item_base = (uint32_t*)(w0 + o_ib);
+        P.t_wbase = (uint32_t*)(w0 + o_tw);
+        P.t_mbase = (uint32_t*)(w0 + o_tm);
+        P.tot = (unsigned long long*)(w0 + o_tot);
+        P.blk = (unsigned long long*)(w0 + o_blk0);
+        /* 1. span */
+        HIP_TRY(mark(EV_SPAN0));
+        HIP_TRY(osmt_launch_tq_span(P, st));
+        HIP_TRY(mark(EV_SPAN1));
+        HIP_TRY(hipMemcpyAsync(tot, P.tot, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (tot[OSMT_TQ_ITEMS] >= 0xFFFFFFFFull)
+            return fail(OSMT_UNSUPPORTED, "tile batch needs %llu (tile, column) items (> 2^32): split the batch", tot[OSMT_TQ_ITEMS]);
+        n_items = (size_t)tot[OSMT_TQ_ITEMS];
+        /* 2. columns */
+        off = 0;
+        const size_t o_it = carve(n_items * 4), o_ws = carve(n_items * 4), o_ms = carve(n_items * 4), o_wb = carve((n_items + 1) * 4);
+        const size_t o_mb = carve((n_items + 1) * 4), o_blk1 = carve((n_items / 256 + 1) * 8);
+        rc = alloc(&wg.work[1], "columns");
+        if (rc != OSMT_OK) return rc;
+        char* w1 = wg.work[1];
+        P.n_items = (uint32_t)n_items;
+        P.item_tile = (uint32_t*)(w1 + o_it);
+        P.item_wsrc = (uint32_t*)(w1 + o_ws);
+        P.item_msrc = (uint32_t*)(w1 + o_ms);
+        P.wbase = (uint32_t*)(w1 + o_wb);
+        P.mbase = (uint32_t*)(w1 + o_mb);
+        P.blk = (unsigned long long*)(w1 + o_blk1);
+        HIP_TRY(mark(EV_COL0));
+        HIP_TRY(osmt_launch_tq_columns(P, st));
+        HIP_TRY(mark(EV_COL1));
+        /* first read-back: the candidate totals, the largest tile, the first tile over the limit — nothing is gathered before */
+        HIP_TRY(hipMemcpyAsync(tot, P.tot, OSMT_TQ_OVER_CAND * 8 + 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (tot[OSMT_TQ_OVER_CAND] != ~0ull) {
+            const size_t t = (size_t)tot[OSMT_TQ_OVER_CAND];
+            uint32_t base[4]; /* t_wbase[t], t_wbase[t + 1], t_mbase[t], t_mbase[t + 1] */
+            HIP_TRY(hipMemcpyAsync(base, P.t_wbase + t, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(base + 2, P.t_mbase + t, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            const uint32_t nw = base[1] - base[0], nm = base[3] - base[2];
+            return fail(OSMT_UNSUPPORTED, "tile %zu gathers %u %s references (> OSMT_QUERY_MAX_TILE_CANDIDATES = %u)", t,
+                        nw > OSMT_QUERY_MAX_TILE_CANDIDATES ? nw : nm, nw > OSMT_QUERY_MAX_TILE_CANDIDATES ? "way" : "multipolygon",
+                        OSMT_QUERY_MAX_TILE_CANDIDATES);
+        }
+        if (tot[OSMT_TQ_WAYS] + tot[OSMT_TQ_MPS] >= 0xFFFFFFFFull)
+            return fail(OSMT_UNSUPPORTED, "tile batch gathers %llu references (%llu way + %llu multipolygon, > 2^32): split the batch",
+                        tot[OSMT_TQ_WAYS] + tot[OSMT_TQ_MPS], tot[OSMT_TQ_WAYS], tot[OSMT_TQ_MPS]);
+        n_way_cand = (size_t)tot[OSMT_TQ_WAYS], n_mp_cand = (size_t)tot[OSMT_TQ_MPS], n_cand = n_way_cand + n_mp_cand;
+        /* 3. gather, 4. sort, mark */
+        off = 0;
+        const size_t o_cand = carve(n_cand * 4), o_apos = carve((n_cand + 1) * 4), o_blk2 = carve((n_cand / 256 + 1) * 8);
+        rc = alloc(&wg.work[2], "candidates");
+        if (rc != OSMT_OK) return rc;
+        char* w2 = wg.work[2];
+        P.n_ways = (uint32_t)n_way_cand;
+        P.n_mps = (uint32_t)n_mp_cand;
+        P.cand = (uint32_t*)(w2 + o_cand);
+        P.apos = (uint32_t*)(w2 + o_apos);
+        P.blk = (unsigned long long*)(w2 + o_blk2);
+    }
+    /* the derived styled batch: the tiles' records and tile_base (written before the areas are counted), and the areas;
+     * two allocations that go to the scene (osmt_scene_read_styled_areas) */
+    struct keep_guard {
+        osmt_ctx* ctx;
+        hipStream_t st;
+        char* head = nullptr;
+        char* areas = nullptr;
+        ~keep_guard() {
+            if (!head && !areas) return;
+            (void)hipStreamSynchronize(st);
+            dev_free(ctx, head);
+            dev_free(ctx, areas);
+        }
+    } kg{ctx, st};
+    off = 0;
+    const size_t o_tiles = carve(n_tiles * sizeof(osmt_styled_tile)), o_base = carve((n_tiles + 1) * 4);
+    rc = alloc(&kg.head, "styled tiles");
+    if (rc != OSMT_OK) return rc;
+    P.tiles = (osmt_styled_tile*)(kg.head + o_tiles);
+    P.tile_base = (uint32_t*)(kg.head + o_base);
+    if (n_tiles) {
+        HIP_TRY(mark(EV_GATHER0));
+        HIP_TRY(osmt_launch_tq_gather(P, st));
+        HIP_TRY(mark(EV_SORT0));
+        HIP_TRY(osmt_launch_tq_sort(P, st));
+        HIP_TRY(mark(EV_MARK0));
+        HIP_TRY(osmt_launch_tq_mark(P, st));
+        HIP_TRY(mark(EV_MARK1));
+        /* second read-back: the area total, the most areas of a tile, the first tile over the limit */
+        HIP_TRY(hipMemcpyAsync(tot + OSMT_TQ_AREAS, P.tot + OSMT_TQ_AREAS, 3 * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (3ull * tot[OSMT_TQ_AREAS] >= 0xFFFFFFFFull)
+            return fail(OSMT_UNSUPPORTED, "tile batch too large for 32-bit indices (%llu areas x 3 passes): split the batch", tot[OSMT_TQ_AREAS]);
+        if (tot[OSMT_TQ_OVER_AREAS] != ~0ull) {
+            const size_t t = (size_t)tot[OSMT_TQ_OVER_AREAS];
+            osmt_styled_tile tl;
+            HIP_TRY(hipMemcpyAsync(&tl, P.tiles + t, sizeof tl, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            return fail(OSMT_UNSUPPORTED, "tile %zu: %u areas (> OSMT_STYLED_MAX_TILE_AREAS = %u)", t, tl.n_areas, OSMT_STYLED_MAX_TILE_AREAS);
+        }
+        n_areas = (size_t)tot[OSMT_TQ_AREAS];
+    } else {
+        HIP_TRY(hipMemsetAsync(P.tile_base, 0, 4, st));
+    }
+    /* 5. emit */
+    off = 0;
+    (void)carve(n_areas * sizeof(osmt_styled_area));
+    rc = alloc(&kg.areas, "styled areas");
+    if (rc != OSMT_OK) return rc;
+    P.areas = (osmt_styled_area*)kg.areas;
+    if (n_tiles) {
+        HIP_TRY(mark(EV_EMIT0));
+        HIP_TRY(osmt_launch_tq_emit(P, st));
+        HIP_TRY(mark(EV_EMIT1));
+    }
+    styled_src in;
+    in.tiles = P.tiles;
+    in.tile_base = P.tile_base;
+    in.areas = P.areas;
+    in.n_tiles = n_tiles, in.total = n_areas;
+    in.scale = b->scale, in.use_caps = b->use_caps_for_dashes ? 1u : 0u;
+    rc = styled_build_back(ctx, st, geo, ss, in, out_scene);
+    if (rc != OSMT_OK) return rc;
+    osmt_scene* s = *out_scene;
+    s->d_tq = kg.head;
+    s->d_tq_areas_buf = kg.areas;
+    s->d_tq_tiles = P.tiles;
+    s->d_tq_areas = P.areas;
+    s->n_tq_areas = n_areas;
+    kg.head = kg.areas = nullptr;
+    if (trace && n_tiles) {
+        auto us = [&](int a, int b2) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
+            return ms * 1e3;
+        };
+        fprintf(stderr,
+                "osmt tile query: span %.1f us, columns %.1f us, gather %.1f us, sort %.1f us, mark + scan %.1f us, emit %.1f us (%zu tiles, %zu items, "
+                "%zu + %zu candidates, at most %llu of one kind in a tile, %zu areas, at most %llu in a tile, %zu bytes sent)\n",
+                us(EV_SPAN0, EV_SPAN1), us(EV_COL0, EV_COL1), us(EV_GATHER0, EV_SORT0), us(EV_SORT0, EV_MARK0), us(EV_MARK0, EV_MARK1),
+                us(EV_EMIT0, EV_EMIT1), n_tiles, n_items, n_way_cand, n_mp_cand, tot[OSMT_TQ_MAX_CAND], n_areas, tot[OSMT_TQ_MAX_AREAS],
+                n_tiles * sizeof(osmt_query_tile) + sizeof bind);
+    }
+    return OSMT_OK;
+}
+
+int scene_read_styled_areas_body(osmt_ctx* ctx, osmt_scene* sc, osmt_styled_tile* tiles, osmt_styled_area* areas, size_t areas_cap, size_t* n_areas) {
+    if (!ctx || !sc || !n_areas) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (!sc->d_tq) return fail(OSMT_INVALID_ARG, "the scene was not built by osmt_scene_build_tiles: it has no derived styled batch");
+    *n_areas = sc->n_tq_areas;
+    if (areas && areas_cap < sc->n_tq_areas) return fail(OSMT_INVALID_ARG, "areas_cap %zu is less than the scene's %zu areas", areas_cap, sc->n_tq_areas);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(scene_wait_idle(sc));
+    if (tiles && sc->n_jobs) HIP_TRY(copy_back(ctx, tiles, sc->d_tq_tiles, (size_t)sc->n_jobs * sizeof(osmt_styled_tile)));
+    if (areas && sc->n_tq_areas) HIP_TRY(copy_back(ctx, areas, sc->d_tq_areas, sc->n_tq_areas * sizeof(osmt_styled_area)));
+    return OSMT_OK;
+}
+
 int scene_read_display_list_body(osmt_ctx* ctx, osmt_scene* sc, osmt_tile_job* jobs, osmt_op* ops, osmt_ring* rings, uint32_t* refs, double* dashes,
                                  size_t counts[5]) {
     if (!ctx || !sc || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
@@ -2166,6 +2693,28 @@ int osmt_validate_styled_batch(const osmt_styled_batch* batch, osmt_ctx* ctx) {
 }
 int osmt_scene_build_styled(osmt_ctx* ctx, const osmt_styled_batch* batch, osmt_scene** out_scene) {
     return guarded([&] { return scene_build_styled_body(ctx, batch, out_scene); });
+}
+int osmt_validate_tile_index(const osmt_tile_index_desc* index, size_t n_ways, size_t n_multipolygons) {
+    return guarded([&] { return validate_tile_index(index, n_ways, n_multipolygons); });
+}
+int osmt_register_tile_index(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tile_index_desc* index) {
+    return guarded([&] { return register_tile_index_body(ctx, geodata_id, index); });
+}
+int osmt_validate_style_bindings(const osmt_style_bindings_desc* b, osmt_ctx* ctx) {
+    return guarded([&] { return validate_style_bindings(b, ctx); });
+}
+int osmt_register_style_bindings(osmt_ctx* ctx, const osmt_style_bindings_desc* b, uint32_t* out_bindings_id) {
+    return guarded([&] { return register_style_bindings_body(ctx, b, out_bindings_id); });
+}
+int osmt_validate_tile_batch(const osmt_tile_batch* batch, osmt_ctx* ctx) {
+    return guarded([&] { return validate_tile_batch(batch, ctx, nullptr); });
+}
+int osmt_scene_build_tiles(osmt_ctx* ctx, const osmt_tile_batch* batch, osmt_scene** out_scene) {
+    return guarded([&] { return scene_build_tiles_body(ctx, batch, out_scene); });
+}
+int osmt_scene_read_styled_areas(osmt_ctx* ctx, osmt_scene* scene, osmt_styled_tile* tiles, osmt_styled_area* areas, size_t areas_cap,
+                                 size_t* n_areas) {
+    return guarded([&] { return scene_read_styled_areas_body(ctx, scene, tiles, areas, areas_cap, n_areas); });
 }
 int osmt_scene_read_display_list(osmt_ctx* ctx, osmt_scene* scene, osmt_tile_job* jobs, osmt_op* ops, osmt_ring* rings, uint32_t* node_refs,
                                  double* dashes, size_t counts[5]) {

@@ -466,6 +466,74 @@ hipError_t osmt_launch_styled_count(const osmt_styled_pass& a, hipStream_t st);
 /* k_styled_emit -> k_styled_jobs -> k_styled_refs */
 hipError_t osmt_launch_styled_emit(const osmt_styled_pass& a, hipStream_t st);
 
+/* ---- scenes built from tile coordinates (osmt_tilequery.hip) --------------------------------------------------- */
+/* a registered z18 tile index as the kernels read it: one allocation that never moves.  The tiles are sorted by (x, y), so a
+ * column (one x) is a contiguous run of them and its tiles' reference lists are ONE contiguous slice of each pool. */
+struct osmt_tq_index_dev {
+    const uint32_t* col_x;     /* [n_cols] the distinct x, ascending (the column directory, built at registration) */
+    const uint32_t* col_first; /* [n_cols + 1] first index tile of the column */
+    const uint32_t* tile_y;    /* [n_tiles] */
+    const uint32_t* way_off;   /* [n_tiles + 1] into ways */
+    const uint32_t* ways;
+    const uint32_t* mp_off;    /* [n_tiles + 1] into mps */
+    const uint32_t* mps;
+    uint32_t n_cols, n_tiles;
+};
+/* a registered bindings table: entity -> its style ids, in push order */
+struct osmt_tq_bind_dev {
+    const uint32_t *way_off, *way_styles, *mp_off, *mp_styles;
+};
+/* words of osmt_tq_pass::tot */
+enum {
+    OSMT_TQ_ITEMS = 0,  /* (tile, column) items */
+    OSMT_TQ_WAYS,       /* way candidates */
+    OSMT_TQ_MPS,        /* multipolygon candidates */
+    OSMT_TQ_MAX_CAND,   /* the largest per-tile count of either kind */
+    OSMT_TQ_OVER_CAND,  /* the first tile with more than OSMT_QUERY_MAX_TILE_CANDIDATES of one kind (none: all ones) */
+    OSMT_TQ_AREAS,      /* areas */
+    OSMT_TQ_MAX_AREAS,  /* the most areas of any tile */
+    OSMT_TQ_OVER_AREAS, /* the first tile with more than OSMT_STYLED_MAX_TILE_AREAS (none: all ones) */
+    OSMT_TQ_N
+};
+struct osmt_tq_pass {
+    osmt_tq_index_dev ix;
+    const uint32_t* geo_mp_off;   /* osmt_geo_dev::mp_off: a multipolygon without polygons is dropped */
+    const osmt_tq_bind_dev* bind; /* [OSMT_MAX_ZOOM + 1] the bindings of each zoom (zooms no tile has: never read) */
+    const osmt_query_tile* q;     /* [n_tiles] */
+    uint32_t n_tiles, n_items, n_ways, n_mps; /* the last three: totals, known once they have been read back */
+    /* per tile */
+    uint32_t* span_c0;   /* [n_tiles] first present column of the tile's rectangle */
+    uint32_t* item_base; /* [n_tiles + 1] span widths, then their exclusive scan: the tile's (tile, column) items */
+    uint32_t* t_wbase;   /* [n_tiles + 1] way candidates of the tiles in front */
+    uint32_t* t_mbase;   /* [n_tiles + 1] */
+    /* per item */
+    uint32_t* item_tile;
+    uint32_t *item_wsrc, *item_msrc; /* where in ix.ways / ix.mps the item's slice starts */
+    uint32_t *wbase, *mbase;         /* [n_items + 1] slice lengths, then their exclusive scans */
+    /* per candidate; a tile's ways, then its multipolygons, tile by tile: slot = t_wbase[t] + t_mbase[t] (+ way count) + k */
+    uint32_t* cand; /* ids: gathered, sorted in place per (tile, kind) */
+    uint32_t* apos; /* [n_ways + n_mps + 1] areas of the candidate (0 for a repeat), then their exclusive scan */
+    /* scans */
+    unsigned long long* blk; /* block totals of the scan under way */
+    unsigned long long* tot; /* [OSMT_TQ_N] */
+    /* the derived styled batch */
+    osmt_styled_tile* tiles;
+    uint32_t* tile_base; /* [n_tiles + 1] */
+    osmt_styled_area* areas;
+};
+/* k_tq_span + scan: the tiles' column ranges, tot[OSMT_TQ_ITEMS] */
+hipError_t osmt_launch_tq_span(const osmt_tq_pass& a, hipStream_t st);
+/* k_tq_columns + two scans + k_tq_tilecand: per-item slices, per-tile candidate counts, the first read-back's words */
+hipError_t osmt_launch_tq_columns(const osmt_tq_pass& a, hipStream_t st);
+/* k_tq_gather (both kinds) */
+hipError_t osmt_launch_tq_gather(const osmt_tq_pass& a, hipStream_t st);
+/* k_tq_sort (one workgroup per tile and kind) */
+hipError_t osmt_launch_tq_sort(const osmt_tq_pass& a, hipStream_t st);
+/* k_tq_mark + scan + k_tq_tiles: area positions, styled tiles, tile_base, the second read-back's words */
+hipError_t osmt_launch_tq_mark(const osmt_tq_pass& a, hipStream_t st);
+/* k_tq_emit: the styled areas */
+hipError_t osmt_launch_tq_emit(const osmt_tq_pass& a, hipStream_t st);
+
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

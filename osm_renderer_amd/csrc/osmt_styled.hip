@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "osmt_bitonic.h"
 #include "osmt_internal.h"
 
 namespace {
@@ -123,35 +124,9 @@ __device__ __forceinline__ void counts_of(const elem& o, uint32_t c[OSMT_SQ_N]) 
 /* ---- sort ---------------------------------------------------------------------------------------------------- */
 __device__ __forceinline__ bool key_less(const ulonglong2& a, const ulonglong2& b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
 
-__device__ __forceinline__ void cmpx(ulonglong2* k, uint32_t i, uint32_t l) {
-    const ulonglong2 a = k[i], b = k[l];
-    if (key_less(b, a)) {
-        k[i] = b;
-        k[l] = a;
-    }
-}
-
-/* k[0 .. n) ascending; N = the power of two >= n.  Slots n .. N - 1 are +inf and exist only in the index arithmetic: every
- * exchange puts the smaller key at the smaller index, so a pair that reaches into them is a no-op. */
-__device__ __forceinline__ void bitonic(ulonglong2* k, uint32_t n, uint32_t N) {
-    for (uint32_t k2 = 2u; k2 <= N; k2 <<= 1) {
-        const uint32_t h = k2 >> 1;
-        for (uint32_t p = threadIdx.x; p < (N >> 1); p += WG) { /* mirror step */
-            const uint32_t blk = p / h, w = p - blk * h;
-            const uint32_t i = blk * k2 + w, l = blk * k2 + (k2 - 1u - w);
-            if (l < n) cmpx(k, i, l);
-        }
-        __syncthreads();
-        for (uint32_t j = k2 >> 2; j > 0u; j >>= 1) {
-            for (uint32_t p = threadIdx.x; p < (N >> 1); p += WG) {
-                const uint32_t blk = p / j, w = p - blk * j;
-                const uint32_t i = blk * 2u * j + w, l = i + j;
-                if (l < n) cmpx(k, i, l);
-            }
-            __syncthreads();
-        }
-    }
-}
+struct key_lt {
+    __device__ __forceinline__ bool operator()(const ulonglong2& a, const ulonglong2& b) const { return key_less(a, b); }
+};
 
 __global__ __launch_bounds__(256) void k_styled_sort(osmt_styled_pass P) {
     __shared__ ulonglong2 lds_keys[OSMT_STYLED_LDS_AREAS];
@@ -178,10 +153,10 @@ __global__ __launch_bounds__(256) void k_styled_sort(osmt_styled_pass P) {
     uint32_t N = 1u;
     while (N < n) N <<= 1;
     if (in_lds) {
-        bitonic(lds_keys, n, N);
+        osmt_bitonic<WG>(lds_keys, n, N, key_lt{});
         for (uint32_t i = threadIdx.x; i < n; i += WG) P.sorted[base + i] = aoff + (uint32_t)(lds_keys[i].y & 0xFFFFull);
     } else {
-        bitonic(gk, n, N);
+        osmt_bitonic<WG>(gk, n, N, key_lt{});
         for (uint32_t i = threadIdx.x; i < n; i += WG) P.sorted[base + i] = aoff + (uint32_t)(gk[i].y & 0xFFFFull);
     }
 }

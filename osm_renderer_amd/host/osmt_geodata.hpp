@@ -168,6 +168,11 @@ class GeodataReader {
     std::pair<const uint32_t*, size_t> multipolygon_polygon_ids(size_t i) const { return ints_by_ref(multipolygons_.at(i) + 8); }
     Tags multipolygon_tags(size_t i) const { return tags(multipolygons_.at(i) + 16); }
 
+    /* Tile (reader.rs:217-229): the z18 tiles in file order = ascending (x, y), and their reference lists */
+    std::pair<uint32_t, uint32_t> tile_xy(size_t i) const { return {tile_x_at(i), tile_y_at(i)}; }
+    std::pair<const uint32_t*, size_t> tile_way_ids(size_t i) const { return ints_by_ref(tiles_.at(i) + 16); }
+    std::pair<const uint32_t*, size_t> tile_multipolygon_ids(size_t i) const { return ints_by_ref(tiles_.at(i) + 24); }
+
     /* every node's (lat, lon), packed for osmt_batch.nodes: one upload serves every tile of the file */
     std::vector<double> node_table() const {
         std::vector<double> t(2 * nodes_.count);

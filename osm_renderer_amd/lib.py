@@ -37,6 +37,8 @@ EXPORTS = [
     "osmt_label_positions", "osmt_label_positions_begin", "osmt_label_positions_end", "osmt_label_positions_stats",
     "osmt_validate_geodata", "osmt_register_geodata", "osmt_validate_styles", "osmt_register_styles", "osmt_validate_styled_batch",
     "osmt_scene_build_styled", "osmt_scene_read_display_list", "osmt_scene_max_tile_ops",
+    "osmt_validate_tile_index", "osmt_register_tile_index", "osmt_validate_style_bindings", "osmt_register_style_bindings",
+    "osmt_validate_tile_batch", "osmt_scene_build_tiles", "osmt_scene_read_styled_areas",
 ]
 
 
@@ -146,6 +148,14 @@ def load():
         L.osmt_scene_build_styled.argtypes = [vp, C.POINTER(abi.StyledBatch), C.POINTER(vp)]
         L.osmt_scene_read_display_list.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]
         L.osmt_scene_max_tile_ops.argtypes = [vp, vp, C.POINTER(C.c_uint32)]
+    if hasattr(L, "osmt_scene_build_tiles"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_validate_tile_index.argtypes = [C.POINTER(abi.TileIndexDesc), C.c_size_t, C.c_size_t]
+        L.osmt_register_tile_index.argtypes = [vp, C.c_uint32, C.POINTER(abi.TileIndexDesc)]
+        L.osmt_validate_style_bindings.argtypes = [C.POINTER(abi.StyleBindingsDesc), vp]
+        L.osmt_register_style_bindings.argtypes = [vp, C.POINTER(abi.StyleBindingsDesc), C.POINTER(C.c_uint32)]
+        L.osmt_validate_tile_batch.argtypes = [C.POINTER(abi.TileBatch), vp]
+        L.osmt_scene_build_tiles.argtypes = [vp, C.POINTER(abi.TileBatch), C.POINTER(vp)]
+        L.osmt_scene_read_styled_areas.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

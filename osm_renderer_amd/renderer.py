@@ -81,6 +81,18 @@ class Scene:
         scale = self._dl.scale if self._dl is not None else self._scale
         return DisplayList(jobs, ops, rings, refs, dashes, abi.COORD_NODE_REF, scale, nodes=nodes)
 
+    def read_styled_areas(self):
+        """osmt_scene_read_styled_areas: the styled batch the device derived for a scene of build_tiles, as (tiles in
+        styled.STYLED_TILE_DTYPE, areas in styled.STYLED_AREA_DTYPE)."""
+        from . import styled
+
+        L, n = load(), C.c_size_t()
+        check(L.osmt_scene_read_styled_areas(self.ctx._h, self._h, None, None, 0, C.byref(n)))
+        tiles, areas = np.zeros(self.n_jobs, styled.STYLED_TILE_DTYPE), np.zeros(n.value, styled.STYLED_AREA_DTYPE)
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+        check(L.osmt_scene_read_styled_areas(self.ctx._h, self._h, ptr(tiles), ptr(areas), len(areas), C.byref(n)))
+        return tiles, areas
+
     def max_tile_ops(self):
         """osmt_scene_max_tile_ops: the most ops of any tile, as the renderer knows it (it picks its list kernel by it)"""
         out = C.c_uint32()
@@ -332,6 +344,31 @@ class Context:
         b = batch.as_batch()
         h = C.c_void_p()
         check(load().osmt_scene_build_styled(self._h, C.byref(b), C.byref(h)))
+        return Scene._built(self, h, batch.n_jobs, batch.scale, getattr(self, "_geodata_nodes", {}).get(batch.geodata_id))
+
+    # -- scenes built from tile coordinates -----------------------------------------
+    def register_tile_index(self, geodata_id, index):
+        """osmt_register_tile_index: uploads a styled.TileIndex for a registered geodata file (one per file)."""
+        d = index.as_desc()
+        check(load().osmt_register_tile_index(self._h, geodata_id, C.byref(d)))
+
+    def register_style_bindings(self, bindings):
+        """osmt_register_style_bindings: appends a styled.StyleBindings table; returns its id."""
+        d = bindings.as_desc()
+        out = C.c_uint32()
+        check(load().osmt_register_style_bindings(self._h, C.byref(d), C.byref(out)))
+        return out.value
+
+    def validate_tiles(self, batch):
+        """osmt_validate_tile_batch against this context's registrations (host only); raises OsmtError."""
+        b = batch.as_batch()
+        check(load().osmt_validate_tile_batch(C.byref(b), self._h))
+
+    def build_tiles(self, batch) -> Scene:
+        """osmt_scene_build_tiles: the scene of a styled.TileBatch — tile query, style lookup and display list on the GPU."""
+        b = batch.as_batch()
+        h = C.c_void_p()
+        check(load().osmt_scene_build_tiles(self._h, C.byref(b), C.byref(h)))
         return Scene._built(self, h, batch.n_jobs, batch.scale, getattr(self, "_geodata_nodes", {}).get(batch.geodata_id))
 
     # -- glyph outlines (glyph-run labels) -----------------------------------------

@@ -29,6 +29,8 @@ STYLED_TILE_DTYPE = np.dtype(
     [("x", "<u4"), ("y", "<u4"), ("zoom", "u1"), ("has_canvas", "u1"), ("canvas_rgb", "u1", (3,)), ("_pad", "u1", (3,)), ("area_off", "<u4"),
      ("n_areas", "<u4")]
 )
+QUERY_TILE_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("zoom", "u1"), ("has_canvas", "u1"), ("canvas_rgb", "u1", (3,)), ("_pad", "u1", (3,))])
+assert QUERY_TILE_DTYPE.itemsize == 16
 assert STYLE_REC_DTYPE.itemsize == 96 and STYLED_AREA_DTYPE.itemsize == 8 and STYLED_TILE_DTYPE.itemsize == 24
 
 
@@ -92,4 +94,71 @@ class StyledBatch:
         b.tiles, b.n_tiles = self.tiles.ctypes.data_as(C.POINTER(abi.StyledTile)), len(self.tiles)
         b.areas, b.n_areas = self.areas.ctypes.data_as(C.POINTER(abi.StyledArea)), len(self.areas)
         b.geodata_id, b.scale, b.use_caps_for_dashes = self.geodata_id, self.scale, int(self.use_caps_for_dashes)
+        return b
+
+
+class TileIndex:
+    """osmt_tile_index_desc: the z18 tile storage of a geodata file.  tiles: {(x, y): (way ids, multipolygon ids)} or a
+    list of ((x, y), way ids, multipolygon ids) in the order to hand over (strictly ascending (x, y) is what registers)."""
+
+    def __init__(self, tiles):
+        if isinstance(tiles, dict):
+            tiles = [(k, tiles[k][0], tiles[k][1]) for k in sorted(tiles)]
+        self.tile_xy = np.array([k for k, _, _ in tiles], dtype=np.uint32).reshape(-1, 2)
+        self.way_off, self.ways = _csr([list(w) for _, w, _ in tiles])
+        self.multipolygon_off, self.multipolygons = _csr([list(m) for _, _, m in tiles])
+
+    def as_desc(self):
+        """ctypes osmt_tile_index_desc pointing into this object's arrays (keep `self` alive)."""
+        u32 = C.POINTER(C.c_uint32)
+        d = abi.TileIndexDesc()
+        d.tile_xy, d.n_tiles = self.tile_xy.ctypes.data_as(u32), len(self.tile_xy)
+        d.way_off, d.ways, d.n_way_refs = self.way_off.ctypes.data_as(u32), self.ways.ctypes.data_as(u32), len(self.ways)
+        d.multipolygon_off, d.multipolygons = self.multipolygon_off.ctypes.data_as(u32), self.multipolygons.ctypes.data_as(u32)
+        d.n_multipolygon_refs = len(self.multipolygons)
+        return d
+
+
+class StyleBindings:
+    """osmt_style_bindings_desc: per way and per multipolygon the style ids Styler::style_entities pushes for it at zooms
+    zoom_lo..zoom_hi, in push order.  way_styles / multipolygon_styles: one list of style ids per entity."""
+
+    def __init__(self, geodata_id, zoom_lo, zoom_hi, way_styles, multipolygon_styles=()):
+        self.geodata_id, self.zoom_lo, self.zoom_hi = int(geodata_id), int(zoom_lo), int(zoom_hi)
+        self.way_style_off, self.way_styles = _csr([list(v) for v in way_styles])
+        self.multipolygon_style_off, self.multipolygon_styles = _csr([list(v) for v in multipolygon_styles])
+
+    def as_desc(self):
+        u32 = C.POINTER(C.c_uint32)
+        d = abi.StyleBindingsDesc()
+        d.geodata_id, d.zoom_lo, d.zoom_hi = self.geodata_id, self.zoom_lo, self.zoom_hi
+        d.way_style_off, d.way_styles, d.n_way_styles = self.way_style_off.ctypes.data_as(u32), self.way_styles.ctypes.data_as(u32), len(self.way_styles)
+        d.multipolygon_style_off, d.multipolygon_styles = self.multipolygon_style_off.ctypes.data_as(u32), self.multipolygon_styles.ctypes.data_as(u32)
+        d.n_multipolygon_styles = len(self.multipolygon_styles)
+        return d
+
+
+class TileBatch:
+    """osmt_tile_batch.  tiles: [(zoom, x, y)]; bindings: {zoom: bindings id} (a zoom that is missing has none); canvas:
+    (r, g, b) or None."""
+
+    def __init__(self, geodata_id, tiles, bindings, scale=1, use_caps_for_dashes=True, canvas=(241, 238, 232)):
+        self.geodata_id, self.scale, self.use_caps_for_dashes = int(geodata_id), int(scale), bool(use_caps_for_dashes)
+        self.bindings = {int(z): int(i) for z, i in dict(bindings).items()}
+        self.tiles = np.zeros(len(tiles), QUERY_TILE_DTYPE)
+        for t, (zoom, x, y) in zip(self.tiles, tiles):
+            t["zoom"], t["x"], t["y"] = zoom, x, y
+            if canvas is not None:
+                t["has_canvas"], t["canvas_rgb"] = 1, canvas
+
+    @property
+    def n_jobs(self):
+        return len(self.tiles)
+
+    def as_batch(self):
+        b = abi.TileBatch()
+        b.tiles, b.n_tiles = self.tiles.ctypes.data_as(C.POINTER(abi.QueryTile)), len(self.tiles)
+        b.geodata_id, b.scale, b.use_caps_for_dashes = self.geodata_id, self.scale, int(self.use_caps_for_dashes)
+        for z in range(abi.MAX_ZOOM + 1):
+            b.bindings_of_zoom[z] = self.bindings.get(z, abi.BINDINGS_NONE)
         return b

@@ -12,6 +12,16 @@ The device time of the new kernels comes from a child run with OSMT_TRACE_UPLOAD
 sequences).  PCIe bytes are computed from the shapes.  One JSON document on stdout and in profiles/styled_feed_bench.json.
 
     python tools/bench_styled_feed.py [--tiles 1024] [--reps 12] [--warmup 3] [--out profiles/styled_feed_bench.json]
+
+--tiles-only runs another pair on the same world, written this time with its z18 tile index (every way in the z18 tiles its
+nodes span) and with one style bound to every way:
+
+  (c) the host query:  GeodataReader::get_entities_in_tile_with_neighbors + the style lookup per entity for every tile on one
+                       thread (osmt::styled_areas_of_tile), then osmt_scene_build_styled
+  (d) tiles only:      osmt_scene_build_tiles over the registered index and bindings (16 bytes per tile)
+
+timed the same way — scene build only, and build + one render —, the stages of (d) from OSMT_TRACE_UPLOAD=1 in a child run.
+Output: profiles/tile_query_bench.json.
 """
 import argparse
 import ctypes as C
@@ -108,6 +118,115 @@ def device_times(args):
             "total_us_median": float(np.median(rows.sum(axis=1))), "runs": int(len(rows))}
 
 
+def tiles_only(args):
+    import time
+
+    import torch
+
+    from tests import _tilequery as tq
+    from tests._geodata import Reader
+
+    rng = np.random.default_rng(1)
+    st, pool = _random_styles(rng, 64)
+    nodes, ways, tiles = make_world(args.tiles)
+    tmp = tempfile.mkdtemp(prefix="tile_query_")
+    path = os.path.join(tmp, "world.bin")
+    refs = write_geodata(path, nodes, ways, max_zoom_tile=tq.max_zoom_tile)
+    r = Reader(path)
+    ctx = Context(0)
+    geo = styled.Geodata([[n[1], n[2]] for n in nodes], [(w[0], w[1]) for w in ways])
+    gid = ctx.register_geodata(geo)
+    first = ctx.register_styles(recs_of(st), pool)
+    ctx.register_tile_index(gid, tq.index_of(refs))
+    ws = [[int(s) + first] for s in rng.integers(0, len(st), len(ways))]
+    bid = ctx.register_style_bindings(styled.StyleBindings(gid, 0, 18, ws, []))
+    mir = tq.Mirror(r, ws, [], gid)
+    zxy = np.array([(z, x, y) for z, x, y, _ in tiles], dtype=np.uint32)
+    tb = styled.TileBatch(gid, [(z, x, y) for z, x, y, _ in tiles], {ZOOM: bid})
+    S = tq.shim()
+    sb = styled.StyledBatch(gid, [(z, x, y, [], []) for z, x, y, _ in tiles])
+    cap = S.tq_batch(r.h, mir.h, zxy.ctypes.data, len(zxy), sb.tiles.ctypes.data, None, 0)
+    sb.areas = np.zeros(cap, styled.STYLED_AREA_DTYPE)
+
+    def run(which, render):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if which == "c":
+            n = S.tq_batch(r.h, mir.h, zxy.ctypes.data, len(zxy), sb.tiles.ctypes.data, sb.areas.ctypes.data, cap)
+            assert n == cap
+            t1 = time.perf_counter()
+            scene = ctx.build_styled(sb)
+        else:
+            t1 = t0
+            scene = ctx.build_tiles(tb)
+        t2 = time.perf_counter()
+        if render:
+            ctx.render(scene)
+            torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        return scene, (t1 - t0, t2 - t0, t3 - t0)
+
+    times = {(w, rd): [] for w in "cd" for rd in (False, True)}
+    for rep in range(args.warmup + args.reps):
+        for render in (False, True):
+            for which in ("c", "d") if rep % 2 == 0 else ("d", "c"):
+                scene, t = run(which, render)
+                scene.free()
+                if rep >= args.warmup:
+                    times[(which, render)].append(t)
+    if args.child:
+        return
+    sc, _ = run("c", False)
+    sd, _ = run("d", False)
+    dl_c, dl_d = sc.read_display_list(), sd.read_display_list()
+    same_list = all(getattr(dl_c, k).tobytes() == getattr(dl_d, k).tobytes() for k in ("jobs", "ops", "rings", "coords", "dashes"))
+    t_d, a_d = sd.read_styled_areas()
+    same_areas = bool(a_d.tobytes() == sb.areas.tobytes() and np.array_equal(t_d["n_areas"], sb.tiles["n_areas"]))
+    same_px = bool(np.array_equal(ctx.render(sc).cpu().numpy(), ctx.render(sd).cpu().numpy()))
+    n_ops = len(dl_d.ops)
+    sc.free()
+    sd.free()
+
+    def stat(rows, k):
+        v = np.array([row[k] for row in rows])
+        return {"median_ms": float(np.median(v) * 1e3), "min_ms": float(v.min() * 1e3), "max_ms": float(v.max() * 1e3),
+                "p25_ms": float(np.percentile(v, 25) * 1e3), "p75_ms": float(np.percentile(v, 75) * 1e3), "runs": len(v)}
+
+    env = dict(os.environ, OSMT_TRACE_UPLOAD="1")
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--tiles-only", "--tiles", str(args.tiles), "--reps", str(args.reps), "--warmup",
+                        str(args.warmup), "--child"], env=env, capture_output=True, text=True, timeout=900)
+    names = ("span", "columns", "gather", "sort", "mark_scan", "emit")
+    rows = re.findall(r"osmt tile query: span ([0-9.]+) us, columns ([0-9.]+) us, gather ([0-9.]+) us, sort ([0-9.]+) us, mark \+ scan ([0-9.]+) us, "
+                      r"emit ([0-9.]+) us", p.stderr)
+    if p.returncode != 0 or len(rows) <= 2 * args.warmup:
+        raise RuntimeError("the traced child run failed:\n" + p.stderr[-2000:])
+    rows = np.array(rows[2 * args.warmup:], dtype=np.float64)
+    T, A = len(tiles), int(cap)
+    res = {
+        "workload": {"tiles": T, "zoom": ZOOM, "ways": len(ways), "index_tiles": len(refs), "way_refs_in_index": int(sum(len(v[1]) for v in refs.values())),
+                     "styles": int(len(st)), "areas": A, "ops": n_ops},
+        "host_query_c": {"query_and_lookup": stat(times[("c", False)], 0), "scene_build": stat(times[("c", False)], 1),
+                         "build_and_render": stat(times[("c", True)], 2)},
+        "tiles_only_d": {"scene_build": stat(times[("d", False)], 1), "build_and_render": stat(times[("d", True)], 2)},
+        "host_ms_removed_median": float(np.median([t[0] for t in times[("c", False)]]) * 1e3),
+        "build_speedup_median_c_over_d": float(np.median([t[1] for t in times[("c", False)]]) / np.median([t[1] for t in times[("d", False)]])),
+        "device_stages_d_us_median": dict({n: float(np.median(rows[:, i])) for i, n in enumerate(names)}, total=float(np.median(rows.sum(axis=1))),
+                                          runs=int(len(rows))),
+        "bytes_sent_per_tile": {"host_query_c": (24 * T + 4 * (T + 1) + 8 * A) / T, "tiles_only_d": (16 * T + 32 * (abi.MAX_ZOOM + 1)) / T},
+        "same_styled_areas": same_areas,
+        "same_display_list": bool(same_list),
+        "same_pixels": same_px,
+    }
+    text = json.dumps(res, indent=1)
+    print(text)
+    out = os.path.join(os.path.dirname(args.out), "tile_query_bench.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text + "\n")
+    if not (same_areas and same_list and same_px):
+        sys.exit("the two feeds disagree")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=1024)
@@ -115,8 +234,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "styled_feed_bench.json"))
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--tiles-only", action="store_true", help="the tile-query pair (c) / (d) instead of (a) / (b)")
     args = ap.parse_args()
     assert args.reps >= 10 or args.child
+    if args.tiles_only:
+        return tiles_only(args)
 
     L = _native()
     rng = np.random.default_rng(1)
