@@ -778,6 +778,102 @@ int osmt_scene_build_tiles(osmt_ctx* ctx, const osmt_tile_batch* batch, osmt_sce
 int osmt_scene_read_styled_areas(osmt_ctx* ctx, osmt_scene* scene, osmt_styled_tile* tiles, osmt_styled_area* areas,
                                  size_t areas_cap, size_t* n_areas);
 
+/* ---- node labels of tile-built scenes: query, order and label records on the GPU --------------------------------- */
+/* What Drawer::draw_labels does for the NODES of a tile (drawer.rs:251-260), for a scene of osmt_scene_build_tiles: the 3 x 3
+ * neighbourhood query over the node lists of the tile index (reader.rs:60-133), the styles bound to every node under the
+ * tile's zoom, the stable sort of Styler::style_entities(nodes, zoom, true) (styler.rs:163, compare_styled_entities with
+ * for_labels: layer or 0, z_index, global id), and per (node, style) the osmt_label + osmt_string_run Labeler::label_entity
+ * implies (labeler.rs:16-106, text_placer.rs:24-58): the anchor is Point::from_node (labelable.rs:15-24), the default text
+ * position of a node is Center.  The batch goes through the string-label path of osmt_scene_set_string_labels.  Labels of
+ * ways and multipolygons stay host-built (polylabel, libm angles) and may be handed in: they are drawn in front of the
+ * nodes' (drawer.rs:229-250).  The host twin is osmt::node_labels_of_tile (host/osmt_tilelabels.hpp). */
+
+#define OSMT_TILE_LABELS_MAX 65536u /* (node, style) labels of one tile */
+#define OSMT_TEXT_NONE 0xFFFFFFFFu  /* osmt_label_binding.text: the tag text_style.text names is absent (text_placer.rs:42-45) */
+
+#define OSMT_LABEL_POSITION_NONE 0u   /* text_style.text_position is None: the default of the entity kind (a node: Center) */
+#define OSMT_LABEL_POSITION_CENTER 1u
+#define OSMT_LABEL_POSITION_LINE 2u   /* on a node: nothing is rasterized, save_to_figure of an empty figure is true */
+
+/* the node half of the z18 tile storage (reader.rs:217-229, tile_local_ids(i, 0)), for the tiles of the tile index already
+ * registered for the geodata id, plus the nodes' global ids */
+typedef struct osmt_node_index_desc {
+    const uint64_t* node_ids; /* [n_nodes] global ids (Node::global_id) */
+    size_t n_nodes;           /* the geodata's node count */
+    const uint32_t* node_off; /* [n_tiles + 1] into nodes, n_tiles = the registered tile index's */
+    const uint32_t* nodes;    /* local node ids, any order, duplicates allowed */
+    size_t n_node_refs;
+} osmt_node_index_desc;
+
+/* The label half of mapcss::styler::Style (styler.rs:42-72) as a POD of 48 bytes; a value whose has_* byte is 0 is ignored. */
+typedef struct osmt_label_style_rec {
+    int64_t layer;
+    double z_index;
+    double font_size;    /* text_style.font_size, as property_map_to_style produced it (unscaled) */
+    uint32_t icon_image; /* id from osmt_register_image; an icon missing from the cache is has_icon = 0 (labeler.rs:55-66) */
+    uint32_t font_id;    /* id from osmt_register_font; read when has_text_style and has_font_size */
+    uint8_t has_layer, has_icon, has_text_style, has_font_size;
+    uint8_t has_text_color, text_color[3];
+    uint8_t text_position; /* OSMT_LABEL_POSITION_* */
+    uint8_t _pad[7];
+} osmt_label_style_rec;
+
+typedef struct osmt_label_binding { /* one element Styler::style_entities pushes for a node */
+    uint32_t style;                 /* id from osmt_register_label_styles */
+    uint32_t text;                  /* index into the table's text pool, or OSMT_TEXT_NONE */
+} osmt_label_binding;
+
+/* (node -> label style, text) for a range of zooms, in push order, and the texts the bindings name */
+typedef struct osmt_label_bindings_desc {
+    uint32_t geodata_id;
+    uint8_t zoom_lo, zoom_hi, _pad[2]; /* inclusive */
+    const uint32_t* node_off;          /* [n_nodes + 1] into bindings */
+    const osmt_label_binding* bindings;
+    size_t n_bindings;
+    const uint32_t* text_off; /* [n_texts + 1] into chars */
+    size_t n_texts;
+    const uint32_t* chars; /* Unicode scalar values, as osmt_string_label_batch.chars */
+    size_t n_chars;
+} osmt_label_bindings_desc;
+
+/* OSMT_INVALID_ARG: an unknown geodata id (a NULL `ctx` has none) or one without a tile index; n_nodes different from the
+ * geodata's; offsets that do not start at 0, decrease or do not end at the pool length; a node id >= n_nodes.
+ * OSMT_UNSUPPORTED: more than 2^32 - 2 references. */
+int osmt_validate_node_index(const osmt_node_index_desc* index, uint32_t geodata_id, osmt_ctx* ctx);
+/* Uploads the node lists of a registered tile index and the nodes' global ids: one allocation that never moves and lives as
+ * long as the context.  One per geodata id: a second registration is OSMT_INVALID_ARG. */
+int osmt_register_node_index(osmt_ctx* ctx, uint32_t geodata_id, const osmt_node_index_desc* index);
+/* OSMT_INVALID_ARG, naming the style: a NaN z_index; an icon_image or font_id that is not registered (`ctx` is only asked for
+ * its icons and fonts, a NULL one has none); a font_size that is not finite or is not finite after multiplication by
+ * OSMT_MAX_SCALE; an unknown text_position.  Only values whose has_* byte is set are looked at. */
+int osmt_validate_label_styles(const osmt_label_style_rec* styles, size_t n, osmt_ctx* ctx);
+/* Appends n label styles; style i gets id *out_first_style_id + i.  Append-only with the snapshot rules of
+ * osmt_register_styles; the dense rank of every style under (layer or 0, z_index with -0.0 == +0.0) is recomputed when
+ * the table has grown. */
+int osmt_register_label_styles(osmt_ctx* ctx, const osmt_label_style_rec* styles, size_t n, uint32_t* out_first_style_id);
+/* OSMT_INVALID_ARG: an unknown geodata id, zoom_lo > zoom_hi or zoom_hi > OSMT_MAX_ZOOM, bad offsets (as above), a style id
+ * that is not registered at the time of the call, a text id that is neither in the pool nor OSMT_TEXT_NONE, a char that is
+ * not a Unicode scalar value. */
+int osmt_validate_label_bindings(const osmt_label_bindings_desc* b, osmt_ctx* ctx);
+/* Appends a label bindings table (one device allocation that never moves) and returns its id. */
+int osmt_register_label_bindings(osmt_ctx* ctx, const osmt_label_bindings_desc* b, uint32_t* out_bindings_id);
+/* Builds the node labels of every tile of `scene` on the device (csrc/osmt_tilelabels.hip), reads the batch back, puts
+ * each tile's `area_labels` (may be NULL; job_label_off over the scene's tiles) in front of its node labels and attaches the
+ * result as osmt_scene_set_string_labels does.  label_bindings_of_zoom[z]: id from osmt_register_label_bindings or
+ * OSMT_BINDINGS_NONE.  OSMT_INVALID_ARG: a scene that osmt_scene_build_tiles did not build, a geodata id without node
+ * index, a tile whose zoom has no bindings or bindings of another geodata id or zoom range; OSMT_UNSUPPORTED with the exact
+ * figure: a tile that gathers more than OSMT_QUERY_MAX_TILE_CANDIDATES node references or has more than
+ * OSMT_TILE_LABELS_MAX labels, a label or char total that does not fit 32 bits; and whatever osmt_scene_set_string_labels
+ * refuses.  On an error of the build the scene keeps the labels it had; an error of the attach leaves it without labels, as
+ * osmt_scene_set_string_labels does. */
+int osmt_scene_build_tile_labels(osmt_ctx* ctx, osmt_scene* scene, const uint32_t label_bindings_of_zoom[OSMT_MAX_ZOOM + 1],
+                                 const osmt_string_label_batch* area_labels);
+/* Inspection: the node batch the device built in the last osmt_scene_build_tile_labels of the scene, before the splice.
+ * counts = { labels, chars } is always set; caps = { labels, chars } bound what is written (a smaller cap with a non-NULL
+ * output is OSMT_INVALID_ARG); each output may be NULL; job_label_off gets n_tiles + 1 entries. */
+int osmt_scene_read_tile_labels(osmt_ctx* ctx, osmt_scene* scene, osmt_label* labels, osmt_string_run* runs, uint32_t* chars,
+                                uint32_t* job_label_off, const size_t caps[2], size_t counts[2]);
+
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */
 int osmt_project(osmt_ctx* ctx, const double* latlon, size_t n, uint8_t zoom, uint32_t tile_x, uint32_t tile_y,

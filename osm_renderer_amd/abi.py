@@ -32,6 +32,9 @@ MAX_SCALE = 4
 QUERY_MAX_TILE_CANDIDATES = 1 << 20  # references of one kind osmt_scene_build_tiles gathers for one tile before dedup
 QUERY_LDS_CANDIDATES = 8192  # up to here a tile's candidates are sorted in LDS
 BINDINGS_NONE = 0xFFFFFFFF  # osmt_tile_batch.bindings_of_zoom: the zoom has no bindings
+TILE_LABELS_MAX = 65536  # (node, style) labels osmt_scene_build_tile_labels builds for one tile
+TEXT_NONE = 0xFFFFFFFF  # osmt_label_binding.text: the tag text_style.text names is absent on the node
+LABEL_POSITION_NONE, LABEL_POSITION_CENTER, LABEL_POSITION_LINE = 0, 1, 2  # osmt_label_style_rec.text_position
 
 
 class Op(C.Structure):
@@ -419,3 +422,51 @@ assert C.sizeof(TileIndexDesc) == 64
 assert C.sizeof(StyleBindingsDesc) == 56
 assert C.sizeof(QueryTile) == 16
 assert C.sizeof(TileBatch) == 112
+
+
+class NodeIndexDesc(C.Structure):
+    _fields_ = [
+        ("node_ids", C.POINTER(C.c_uint64)),
+        ("n_nodes", C.c_size_t),
+        ("node_off", C.POINTER(C.c_uint32)),
+        ("nodes", C.POINTER(C.c_uint32)),
+        ("n_node_refs", C.c_size_t),
+    ]
+
+
+class LabelStyleRec(C.Structure):
+    _fields_ = [
+        ("layer", C.c_int64),
+        ("z_index", C.c_double),
+        ("font_size", C.c_double),
+        ("icon_image", C.c_uint32),
+        ("font_id", C.c_uint32),
+        ("has_layer", C.c_uint8),
+        ("has_icon", C.c_uint8),
+        ("has_text_style", C.c_uint8),
+        ("has_font_size", C.c_uint8),
+        ("has_text_color", C.c_uint8),
+        ("text_color", C.c_uint8 * 3),
+        ("text_position", C.c_uint8),
+        ("_pad", C.c_uint8 * 7),
+    ]
+
+
+class LabelBinding(C.Structure):
+    _fields_ = [("style", C.c_uint32), ("text", C.c_uint32)]
+
+
+class LabelBindingsDesc(C.Structure):
+    _fields_ = [
+        ("geodata_id", C.c_uint32),
+        ("zoom_lo", C.c_uint8),
+        ("zoom_hi", C.c_uint8),
+        ("_pad", C.c_uint8 * 2),
+        ("node_off", C.POINTER(C.c_uint32)),
+        ("bindings", C.POINTER(LabelBinding)),
+        ("n_bindings", C.c_size_t),
+        ("text_off", C.POINTER(C.c_uint32)),
+        ("n_texts", C.c_size_t),
+        ("chars", C.POINTER(C.c_uint32)),
+        ("n_chars", C.c_size_t),
+    ]

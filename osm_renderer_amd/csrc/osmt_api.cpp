@@ -137,6 +137,10 @@ struct osmt_ctx {
         /* its z18 tile index (osmt_register_tile_index): at most one, an allocation of its own under the same rules */
         void* d_index = nullptr;
         osmt_tq_index_dev ix{};
+        /* the node lists of that index and the nodes' global ids (osmt_register_node_index): at most one, same rules */
+        void* d_node_index = nullptr;
+        const uint32_t *d_node_off = nullptr, *d_node_refs = nullptr, *d_zero_off = nullptr; /* [ix.n_tiles + 1], pool, [ix.n_tiles + 1] zeros */
+        const uint64_t* d_node_gid = nullptr;
     };
     std::vector<geodata_host> geodata;
     /* the tables of osmt_register_style_bindings: append-only, one device allocation each that never moves, so a build
@@ -148,6 +152,20 @@ struct osmt_ctx {
         osmt_tq_bind_dev dev{};
     };
     std::vector<bindings_host> bindings;
+    /* the tables of osmt_register_label_bindings, under the same rules */
+    struct label_bindings_host {
+        uint32_t geodata_id = 0;
+        uint8_t zoom_lo = 0, zoom_hi = 0;
+        void* d_pool = nullptr;
+        osmt_tl_bind_dev dev{};
+    };
+    std::vector<label_bindings_host> label_bindings;
+    /* the label styles of osmt_register_label_styles: records and ranks, replaced like the style table when it has grown */
+    std::vector<osmt_label_style_rec> label_styles;
+    osmt_label_style_rec* d_label_styles = nullptr;
+    uint32_t* d_label_rank = nullptr;
+    uint32_t d_n_label_styles = 0;
+    bool label_styles_dirty = false;
     /* the styles of osmt_register_styles, same snapshot rules as the glyph table: a registration followed by a build makes
      * a new device triple (records, ranks, dash pool), the old one joins image_graveyard */
     std::vector<osmt_style_rec> styles;
@@ -271,6 +289,12 @@ struct osmt_scene {
     const osmt_styled_tile* d_tq_tiles = nullptr;
     const osmt_styled_area* d_tq_areas = nullptr;
     size_t n_tq_areas = 0;
+    std::vector<osmt_query_tile> h_tq_tiles; /* the tiles it was built from, for osmt_scene_build_tile_labels */
+    uint32_t tq_geodata_id = 0;
+    /* the node batch the last osmt_scene_build_tile_labels read back (osmt_scene_read_tile_labels) */
+    std::vector<osmt_label> h_tl_labels;
+    std::vector<osmt_string_run> h_tl_runs;
+    std::vector<uint32_t> h_tl_chars, h_tl_off;
 };
 
 namespace {
@@ -627,9 +651,14 @@ void ctx_teardown(osmt_ctx* ctx) {
     {
         if (g.d_pool) (void)hipFree(g.d_pool);
         if (g.d_index) (void)hipFree(g.d_index);
+        if (g.d_node_index) (void)hipFree(g.d_node_index);
     }
     for (auto& b : ctx->bindings)
         if (b.d_pool) (void)hipFree(b.d_pool);
+    for (auto& b : ctx->label_bindings)
+        if (b.d_pool) (void)hipFree(b.d_pool);
+    if (ctx->d_label_styles) (void)hipFree(ctx->d_label_styles);
+    if (ctx->d_label_rank) (void)hipFree(ctx->d_label_rank);
     if (ctx->d_styles) (void)hipFree(ctx->d_styles);
     if (ctx->d_style_rank) (void)hipFree(ctx->d_style_rank);
     if (ctx->d_style_dashes) (void)hipFree(ctx->d_style_dashes);
@@ -2630,6 +2659,8 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
     s->d_tq_tiles = P.tiles;
     s->d_tq_areas = P.areas;
     s->n_tq_areas = n_areas;
+    s->h_tq_tiles.assign(b->tiles, b->tiles + n_tiles);
+    s->tq_geodata_id = b->geodata_id;
     kg.head = kg.areas = nullptr;
     if (trace && n_tiles) {
         auto us = [&](int a, int b2) {
@@ -3201,6 +3232,568 @@ int osmt_validate_text_labels(const osmt_text_label_batch* tb, size_t n_jobs) {
 int osmt_scene_set_string_labels(osmt_ctx* ctx, osmt_scene* sc, const osmt_string_label_batch* sb) {
     if (!sb) return osmt_scene_set_text_labels(ctx, sc, nullptr);
     return guarded([&] { return osmt_scene_set_labels_body(ctx, sc, nullptr, nullptr, nullptr, sb); });
+}
+
+/* ---- node labels of tile-built scenes (include/osmtile.h, csrc/osmt_tilelabels.hip) ------------------------------------ */
+static int validate_node_index(const osmt_node_index_desc* x, uint32_t geodata_id, osmt_ctx* ctx, size_t* out_tiles) {
+    if (!x) return fail(OSMT_INVALID_ARG, "node index is NULL");
+    if (!ctx) return fail(OSMT_INVALID_ARG, "node index: geodata id %u is not registered (no context)", geodata_id);
+    size_t n_nodes = 0, n_tiles = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (geodata_id >= ctx->geodata.size())
+            return fail(OSMT_INVALID_ARG, "node index: geodata id %u is not registered (%zu files)", geodata_id, ctx->geodata.size());
+        const osmt_ctx::geodata_host& g = ctx->geodata[geodata_id];
+        if (!g.d_index) return fail(OSMT_INVALID_ARG, "node index: geodata id %u has no tile index (osmt_register_tile_index)", geodata_id);
+        if (g.d_node_index) return fail(OSMT_INVALID_ARG, "node index: geodata id %u has a node index already (one per file)", geodata_id);
+        n_nodes = g.n_nodes, n_tiles = g.ix.n_tiles;
+    }
+    if (x->n_nodes != n_nodes) return fail(OSMT_INVALID_ARG, "node index: n_nodes = %zu, the geodata has %zu nodes", x->n_nodes, n_nodes);
+    if ((x->n_nodes && !x->node_ids) || !x->node_off || (x->n_node_refs && !x->nodes))
+        return fail(OSMT_INVALID_ARG, "node index: NULL array (every offset array has at least its first entry)");
+    if (x->n_node_refs >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "node index: too large for 32-bit indices");
+    const int rc = check_offsets_of("node index", "node_off", x->node_off, n_tiles, x->n_node_refs);
+    if (rc != OSMT_OK) return rc;
+    for (size_t i = 0; i < x->n_node_refs; ++i)
+        if (x->nodes[i] >= n_nodes) return fail(OSMT_INVALID_ARG, "node index: nodes[%zu] = %u is not a node (%zu nodes)", i, x->nodes[i], n_nodes);
+    if (out_tiles) *out_tiles = n_tiles;
+    return OSMT_OK;
+}
+
+static int register_node_index_body(osmt_ctx* ctx, uint32_t geodata_id, const osmt_node_index_desc* x) {
+    if (!ctx) return fail(OSMT_INVALID_ARG, "NULL argument");
+    size_t n = 0;
+    const int rc = validate_node_index(x, geodata_id, ctx, &n);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_gid = carve(x->n_nodes * 8), o_off = carve((n + 1) * 4), o_refs = carve(x->n_node_refs * 4), o_zero = carve((n + 1) * 4);
+    char* pool = nullptr;
+    HIP_TRY(hipMalloc((void**)&pool, off));
+    const std::vector<uint32_t> zeros(n + 1, 0u); /* the offsets of the empty second kind */
+    hipError_t e = hipSuccess;
+    auto put = [&](size_t o, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+    };
+    put(o_gid, x->node_ids, x->n_nodes * 8);
+    put(o_off, x->node_off, (n + 1) * 4);
+    put(o_refs, x->nodes, x->n_node_refs * 4);
+    put(o_zero, zeros.data(), (n + 1) * 4);
+    if (e != hipSuccess) {
+        (void)hipFree(pool);
+        return fail(OSMT_HIP_ERROR, "node index upload failed: %s", hipGetErrorString(e));
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    osmt_ctx::geodata_host& g = ctx->geodata[geodata_id];
+    if (g.d_node_index) { /* another thread was first */
+        (void)hipFree(pool);
+        return fail(OSMT_INVALID_ARG, "node index: geodata id %u has a node index already (one per file)", geodata_id);
+    }
+    g.d_node_index = pool;
+    g.d_node_gid = (const uint64_t*)(pool + o_gid);
+    g.d_node_off = (const uint32_t*)(pool + o_off);
+    g.d_node_refs = (const uint32_t*)(pool + o_refs);
+    g.d_zero_off = (const uint32_t*)(pool + o_zero);
+    return OSMT_OK;
+}
+
+static int validate_label_styles(const osmt_label_style_rec* st, size_t n, osmt_ctx* ctx) {
+    if (n && !st) return fail(OSMT_INVALID_ARG, "label styles are NULL");
+    size_t n_images = 0, n_fonts = 0;
+    if (ctx) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        n_images = ctx->images.size(), n_fonts = ctx->fonts.size();
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const osmt_label_style_rec& s = st[i];
+        if (std::isnan(s.z_index)) return fail(OSMT_INVALID_ARG, "label style %zu: z_index is NaN", i);
+        if (s.has_icon && s.icon_image >= n_images)
+            return fail(OSMT_INVALID_ARG, "label style %zu: icon_image %u is not registered (%zu images)", i, s.icon_image, n_images);
+        if (s.text_position > OSMT_LABEL_POSITION_LINE) return fail(OSMT_INVALID_ARG, "label style %zu: unknown text_position %u", i, s.text_position);
+        if (s.has_text_style && s.has_font_size) {
+            if (!std::isfinite(s.font_size) || !std::isfinite(s.font_size * (double)OSMT_MAX_SCALE))
+                return fail(OSMT_INVALID_ARG, "label style %zu: font_size not finite (after multiplication by %u)", i, OSMT_MAX_SCALE);
+            if (s.font_id >= n_fonts) return fail(OSMT_INVALID_ARG, "label style %zu: font_id %u is not registered (%zu fonts)", i, s.font_id, n_fonts);
+        }
+    }
+    return OSMT_OK;
+}
+
+static int register_label_styles_body(osmt_ctx* ctx, const osmt_label_style_rec* st, size_t n, uint32_t* out_first) {
+    if (!ctx || !out_first) return fail(OSMT_INVALID_ARG, "NULL argument");
+    const int rc = validate_label_styles(st, n, ctx);
+    if (rc != OSMT_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->label_styles.size() + n >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "label style table too large");
+    *out_first = (uint32_t)ctx->label_styles.size();
+    ctx->label_styles.insert(ctx->label_styles.end(), st, st + n);
+    if (n) ctx->label_styles_dirty = true;
+    return OSMT_OK;
+}
+
+/* compare_styled_entities with for_labels (styler.rs:246-272), the part that depends on the style alone */
+static int label_style_key_cmp(const osmt_label_style_rec& a, const osmt_label_style_rec& b) {
+    const int64_t la = a.has_layer ? a.layer : 0, lb = b.has_layer ? b.layer : 0;
+    if (la != lb) return la < lb ? -1 : 1;
+    if (a.z_index != b.z_index) return a.z_index < b.z_index ? -1 : 1; /* -0.0 == +0.0; never NaN */
+    return 0;
+}
+
+/* brings the device copy of the label style table up to date; the pointers stay valid for the life of the context */
+static int sync_label_styles(osmt_ctx* ctx, const osmt_label_style_rec** styles, const uint32_t** rank) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->label_styles_dirty || !ctx->d_label_styles) {
+        const size_t n = ctx->label_styles.size();
+        std::vector<uint32_t> order(n), rk(n);
+        for (size_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
+        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return label_style_key_cmp(ctx->label_styles[x], ctx->label_styles[y]) < 0; });
+        uint32_t r = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if (i && label_style_key_cmp(ctx->label_styles[order[i - 1]], ctx->label_styles[order[i]]) != 0) ++r;
+            rk[order[i]] = r;
+        }
+        osmt_label_style_rec* ds = nullptr;
+        uint32_t* dr = nullptr;
+        hipError_t e = hipMalloc((void**)&ds, std::max<size_t>(n, 1) * sizeof(osmt_label_style_rec));
+        if (e == hipSuccess) e = hipMalloc((void**)&dr, std::max<size_t>(n, 1) * 4);
+        if (e == hipSuccess && n) e = hipMemcpy(ds, ctx->label_styles.data(), n * sizeof(osmt_label_style_rec), hipMemcpyHostToDevice);
+        if (e == hipSuccess && n) e = hipMemcpy(dr, rk.data(), n * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (ds) (void)hipFree(ds);
+            if (dr) (void)hipFree(dr);
+            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "label style table upload failed: %s", hipGetErrorString(e));
+        }
+        if (ctx->d_label_styles) ctx->image_graveyard.push_back(ctx->d_label_styles);
+        if (ctx->d_label_rank) ctx->image_graveyard.push_back(ctx->d_label_rank);
+        ctx->d_label_styles = ds;
+        ctx->d_label_rank = dr;
+        ctx->d_n_label_styles = (uint32_t)n;
+        ctx->label_styles_dirty = false;
+    }
+    *styles = ctx->d_label_styles;
+    *rank = ctx->d_label_rank;
+    return OSMT_OK;
+}
+
+static int validate_label_bindings(const osmt_label_bindings_desc* b, osmt_ctx* ctx, size_t* out_nodes) {
+    if (!b) return fail(OSMT_INVALID_ARG, "label bindings are NULL");
+    if (b->zoom_lo > b->zoom_hi || b->zoom_hi > OSMT_MAX_ZOOM)
+        return fail(OSMT_INVALID_ARG, "label bindings: zoom range %u..%u (zoom_lo <= zoom_hi <= %u)", b->zoom_lo, b->zoom_hi, OSMT_MAX_ZOOM);
+    if (!ctx) return fail(OSMT_INVALID_ARG, "label bindings: geodata id %u is not registered (no context)", b->geodata_id);
+    size_t n_nodes = 0, n_styles = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (b->geodata_id >= ctx->geodata.size())
+            return fail(OSMT_INVALID_ARG, "label bindings: geodata id %u is not registered (%zu files)", b->geodata_id, ctx->geodata.size());
+        n_nodes = ctx->geodata[b->geodata_id].n_nodes;
+        n_styles = ctx->label_styles.size();
+    }
+    if (!b->node_off || (b->n_bindings && !b->bindings) || !b->text_off || (b->n_chars && !b->chars))
+        return fail(OSMT_INVALID_ARG, "label bindings: NULL array (every offset array has at least its first entry)");
+    if (b->n_bindings >= 0xFFFFFFFFull || b->n_texts >= 0xFFFFFFFFull || b->n_chars >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "label bindings: too large for 32-bit indices");
+    int rc = check_offsets_of("label bindings", "node_off", b->node_off, n_nodes, b->n_bindings);
+    if (rc == OSMT_OK) rc = check_offsets_of("label bindings", "text_off", b->text_off, b->n_texts, b->n_chars);
+    if (rc != OSMT_OK) return rc;
+    for (size_t i = 0; i < b->n_bindings; ++i) {
+        if (b->bindings[i].style >= n_styles)
+            return fail(OSMT_INVALID_ARG, "label bindings: bindings[%zu].style = %u is not a registered label style (%zu styles)", i, b->bindings[i].style, n_styles);
+        if (b->bindings[i].text != OSMT_TEXT_NONE && b->bindings[i].text >= b->n_texts)
+            return fail(OSMT_INVALID_ARG, "label bindings: bindings[%zu].text = %u is not in the text pool (%zu texts) nor OSMT_TEXT_NONE", i, b->bindings[i].text,
+                        b->n_texts);
+    }
+    for (size_t i = 0; i < b->n_chars; ++i)
+        if (!osmt::textshaper_detail::is_char(b->chars[i])) return fail(OSMT_INVALID_ARG, "label bindings: chars[%zu] = U+%X is not a Unicode scalar value", i, b->chars[i]);
+    if (out_nodes) *out_nodes = n_nodes;
+    return OSMT_OK;
+}
+
+static int register_label_bindings_body(osmt_ctx* ctx, const osmt_label_bindings_desc* b, uint32_t* out_id) {
+    if (!ctx || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    size_t n_nodes = 0;
+    const int rc = validate_label_bindings(b, ctx, &n_nodes);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_no = carve((n_nodes + 1) * 4), o_b = carve(b->n_bindings * sizeof(osmt_label_binding)), o_to = carve((b->n_texts + 1) * 4);
+    const size_t o_c = carve(b->n_chars * 4);
+    char* pool = nullptr;
+    HIP_TRY(hipMalloc((void**)&pool, off));
+    hipError_t e = hipSuccess;
+    auto put = [&](size_t o, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+    };
+    put(o_no, b->node_off, (n_nodes + 1) * 4);
+    put(o_b, b->bindings, b->n_bindings * sizeof(osmt_label_binding));
+    put(o_to, b->text_off, (b->n_texts + 1) * 4);
+    put(o_c, b->chars, b->n_chars * 4);
+    if (e != hipSuccess) {
+        (void)hipFree(pool);
+        return fail(OSMT_HIP_ERROR, "label bindings upload failed: %s", hipGetErrorString(e));
+    }
+    osmt_ctx::label_bindings_host h;
+    h.geodata_id = b->geodata_id, h.zoom_lo = b->zoom_lo, h.zoom_hi = b->zoom_hi;
+    h.d_pool = pool;
+    h.dev.node_off = (const uint32_t*)(pool + o_no);
+    h.dev.bindings = (const osmt_label_binding*)(pool + o_b);
+    h.dev.text_off = (const uint32_t*)(pool + o_to);
+    h.dev.chars = (const uint32_t*)(pool + o_c);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->label_bindings.size() + 1 >= 0xFFFFFFFFull) {
+        (void)hipFree(pool);
+        return fail(OSMT_INVALID_ARG, "label bindings table too large");
+    }
+    *out_id = (uint32_t)ctx->label_bindings.size();
+    ctx->label_bindings.push_back(h);
+    return OSMT_OK;
+}
+
+static int scene_build_tile_labels_body(osmt_ctx* ctx, osmt_scene* sc, const uint32_t* bindings_of_zoom, const osmt_string_label_batch* area) {
+    if (!ctx || !sc || sc->ctx != ctx || !bindings_of_zoom) return fail(OSMT_INVALID_ARG, "bad ctx/scene/bindings");
+    if (!sc->d_tq) return fail(OSMT_INVALID_ARG, "the scene was not built by osmt_scene_build_tiles: it has no tiles to query");
+    const size_t n_tiles = sc->n_jobs;
+    const std::vector<osmt_query_tile>& q = sc->h_tq_tiles;
+    osmt_tl_bind_dev bind[OSMT_MAX_ZOOM + 1];
+    memset(bind, 0, sizeof bind);
+    osmt_ctx::geodata_host geo;
+    std::vector<uint32_t> icon_h;
+    {
+        bool zoom_used[OSMT_MAX_ZOOM + 1] = {};
+        size_t first_of_zoom[OSMT_MAX_ZOOM + 1] = {};
+        for (size_t t = 0; t < n_tiles; ++t)
+            if (!zoom_used[q[t].zoom]) zoom_used[q[t].zoom] = true, first_of_zoom[q[t].zoom] = t;
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        geo = ctx->geodata[sc->tq_geodata_id];
+        if (!geo.d_node_index) return fail(OSMT_INVALID_ARG, "geodata id %u has no node index (osmt_register_node_index)", sc->tq_geodata_id);
+        for (uint32_t z = 0; z <= OSMT_MAX_ZOOM; ++z) {
+            if (!zoom_used[z]) continue;
+            const uint32_t id = bindings_of_zoom[z];
+            if (id == OSMT_BINDINGS_NONE) return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u has no label bindings (OSMT_BINDINGS_NONE)", first_of_zoom[z], z);
+            if (id >= ctx->label_bindings.size())
+                return fail(OSMT_INVALID_ARG, "tile %zu: label bindings id %u of zoom %u is not registered (%zu tables)", first_of_zoom[z], id, z,
+                            ctx->label_bindings.size());
+            const osmt_ctx::label_bindings_host& h = ctx->label_bindings[id];
+            if (h.geodata_id != sc->tq_geodata_id)
+                return fail(OSMT_INVALID_ARG, "tile %zu: label bindings id %u of zoom %u belongs to geodata id %u, not %u", first_of_zoom[z], id, z, h.geodata_id,
+                            sc->tq_geodata_id);
+            if (z < h.zoom_lo || z > h.zoom_hi)
+                return fail(OSMT_INVALID_ARG, "tile %zu: label bindings id %u covers zooms %u..%u, not zoom %u", first_of_zoom[z], id, h.zoom_lo, h.zoom_hi, z);
+            bind[z] = h.dev;
+        }
+        icon_h.resize(ctx->images.size());
+        for (size_t i = 0; i < icon_h.size(); ++i) icon_h[i] = ctx->images[i].height;
+    }
+    if (area) {
+        if ((area->n_labels && (!area->labels || !area->runs)) || !area->job_label_off || (area->n_chars && !area->chars) ||
+            (area->n_way_pts && (!area->way_pts || !area->way_sincos)))
+            return fail(OSMT_INVALID_ARG, "area labels: NULL array with a non-zero count (job_label_off has at least its first entry)");
+        if (area->job_label_off[0] != 0 || area->job_label_off[n_tiles] != area->n_labels)
+            return fail(OSMT_INVALID_ARG, "area labels: job_label_off must run from 0 to n_labels over the scene's %zu tiles", n_tiles);
+        for (size_t t = 0; t < n_tiles; ++t)
+            if (area->job_label_off[t] > area->job_label_off[t + 1]) return fail(OSMT_INVALID_ARG, "area labels: job_label_off is not monotonic");
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const osmt_label_style_rec* d_styles = nullptr;
+    const uint32_t* d_rank = nullptr;
+    int rc = sync_label_styles(ctx, &d_styles, &d_rank);
+    if (rc != OSMT_OK) return rc;
+    /* work[0]: per tile, [1]: per item, [2]: per candidate, [3]: per label, [4]: the chars — given back at the end */
+    struct work_guard {
+        osmt_ctx* ctx;
+        hipStream_t st = nullptr;
+        char* work[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~work_guard() {
+            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers */
+            for (char* p : work) dev_free(ctx, p);
+            stream_release(ctx, st);
+        }
+    } wg{ctx};
+    HIP_TRY(stream_acquire(ctx, &wg.st));
+    hipStream_t st = wg.st;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    auto alloc = [&](char** out, const char* what) {
+        const hipError_t e = dev_alloc(ctx, (void**)out, off + 256);
+        if (e == hipSuccess) return (int)OSMT_OK;
+        *out = nullptr;
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the tile labels (%s) failed: %s", off, what, hipGetErrorString(e));
+    };
+    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    enum { EV_Q0, EV_Q1, EV_G0, EV_M0, EV_M1, EV_O0, EV_O1, EV_E0, EV_E1, EV_N };
+    hipEvent_t ev[EV_N] = {};
+    struct ev_guard {
+        hipEvent_t* ev;
+        ~ev_guard() {
+            for (int i = 0; i < EV_N; ++i)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } evg{ev};
+    if (trace)
+        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+
+    std::vector<osmt_label> labels;
+    std::vector<osmt_string_run> runs;
+    std::vector<uint32_t> chars, job_off(n_tiles + 1, 0u);
+    size_t n_items = 0, n_cand = 0, n_labels = 0, n_chars = 0;
+    unsigned long long max_labels = 0;
+    if (n_tiles) {
+        unsigned long long tq_tot[OSMT_TQ_N] = {}, tl_tot[OSMT_TL_N] = {};
+        osmt_tq_pass Q;
+        memset(&Q, 0, sizeof Q);
+        osmt_tl_pass P;
+        memset(&P, 0, sizeof P);
+        off = 0;
+        const size_t o_q = carve(n_tiles * sizeof(osmt_query_tile)), o_bind = carve(sizeof bind), o_c0 = carve(n_tiles * 4), o_ib = carve((n_tiles + 1) * 4);
+        const size_t o_tw = carve((n_tiles + 1) * 4), o_tm = carve((n_tiles + 1) * 4), o_tot = carve((OSMT_TQ_N + OSMT_TL_N) * 8);
+        const size_t o_blk0 = carve((n_tiles / 256 + 1) * 8), o_ih = carve(std::max<size_t>(icon_h.size(), 1) * 4), o_jo = carve((n_tiles + 1) * 4);
+        rc = alloc(&wg.work[0], "tiles");
+        if (rc != OSMT_OK) return rc;
+        char* w0 = wg.work[0];
+        HIP_TRY(hipMemcpyAsync(w0 + o_q, q.data(), n_tiles * sizeof(osmt_query_tile), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(w0 + o_bind, bind, sizeof bind, hipMemcpyHostToDevice, st));
+        if (!icon_h.empty()) HIP_TRY(hipMemcpyAsync(w0 + o_ih, icon_h.data(), icon_h.size() * 4, hipMemcpyHostToDevice, st));
+        /* the query over the node pools: the node lists as the "ways", no second kind */
+        Q.ix = geo.ix;
+        Q.ix.way_off = geo.d_node_off, Q.ix.ways = geo.d_node_refs;
+        Q.ix.mp_off = geo.d_zero_off, Q.ix.mps = geo.d_node_refs;
+        Q.q = (const osmt_query_tile*)(w0 + o_q);
+        Q.n_tiles = (uint32_t)n_tiles;
+        Q.span_c0 = (uint32_t*)(w0 + o_c0);
+        Q.item_base = (uint32_t*)(w0 + o_ib);
+        Q.t_wbase = (uint32_t*)(w0 + o_tw);
+        Q.t_mbase = (uint32_t*)(w0 + o_tm);
+        Q.tot = (unsigned long long*)(w0 + o_tot);
+        Q.blk = (unsigned long long*)(w0 + o_blk0);
+        HIP_TRY(mark(EV_Q0));
+        HIP_TRY(osmt_launch_tq_span(Q, st));
+        HIP_TRY(hipMemcpyAsync(tq_tot, Q.tot, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (tq_tot[OSMT_TQ_ITEMS] >= 0xFFFFFFFFull)
+            return fail(OSMT_UNSUPPORTED, "tile labels: the batch needs %llu (tile, column) items (> 2^32): split the batch", tq_tot[OSMT_TQ_ITEMS]);
+        n_items = (size_t)tq_tot[OSMT_TQ_ITEMS];
+        off = 0;
+        const size_t o_it = carve(n_items * 4), o_ws = carve(n_items * 4), o_ms = carve(n_items * 4), o_wb = carve((n_items + 1) * 4);
+        const size_t o_mb = carve((n_items + 1) * 4), o_blk1 = carve((n_items / 256 + 1) * 8);
+        rc = alloc(&wg.work[1], "columns");
+        if (rc != OSMT_OK) return rc;
+        char* w1 = wg.work[1];
+        Q.n_items = (uint32_t)n_items;
+        Q.item_tile = (uint32_t*)(w1 + o_it);
+        Q.item_wsrc = (uint32_t*)(w1 + o_ws);
+        Q.item_msrc = (uint32_t*)(w1 + o_ms);
+        Q.wbase = (uint32_t*)(w1 + o_wb);
+        Q.mbase = (uint32_t*)(w1 + o_mb);
+        Q.blk = (unsigned long long*)(w1 + o_blk1);
+        HIP_TRY(osmt_launch_tq_columns(Q, st));
+        HIP_TRY(mark(EV_Q1));
+        /* first read-back: the candidate total, the first tile over the limit — nothing is gathered before */
+        HIP_TRY(hipMemcpyAsync(tq_tot, Q.tot, OSMT_TQ_OVER_CAND * 8 + 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (tq_tot[OSMT_TQ_OVER_CAND] != ~0ull) {
+            const size_t t = (size_t)tq_tot[OSMT_TQ_OVER_CAND];
+            uint32_t base[2];
+            HIP_TRY(hipMemcpyAsync(base, Q.t_wbase + t, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            return fail(OSMT_UNSUPPORTED, "tile %zu gathers %u node references (> OSMT_QUERY_MAX_TILE_CANDIDATES = %u)", t, base[1] - base[0],
+                        OSMT_QUERY_MAX_TILE_CANDIDATES);
+        }
+        if (tq_tot[OSMT_TQ_WAYS] >= 0xFFFFFFFFull)
+            return fail(OSMT_UNSUPPORTED, "tile labels: the batch gathers %llu node references (> 2^32): split the batch", tq_tot[OSMT_TQ_WAYS]);
+        n_cand = (size_t)tq_tot[OSMT_TQ_WAYS];
+        off = 0;
+        const size_t o_cand = carve(n_cand * 4), o_lpos = carve((n_cand + 1) * 4), o_blk2 = carve((n_cand / 256 + 1) * 8);
+        rc = alloc(&wg.work[2], "candidates");
+        if (rc != OSMT_OK) return rc;
+        char* w2 = wg.work[2];
+        Q.n_ways = (uint32_t)n_cand;
+        Q.n_mps = 0u;
+        Q.cand = (uint32_t*)(w2 + o_cand);
+        HIP_TRY(mark(EV_G0));
+        HIP_TRY(osmt_launch_tq_gather(Q, st));
+        HIP_TRY(osmt_launch_tq_sort(Q, st));
+        /* expand */
+        P.q = Q.q;
+        P.bind = (const osmt_tl_bind_dev*)(w0 + o_bind);
+        P.nodes = geo.dev.nodes;
+        P.node_gid = geo.d_node_gid;
+        P.styles = d_styles;
+        P.style_rank = d_rank;
+        P.icon_h = (const uint32_t*)(w0 + o_ih);
+        P.n_tiles = (uint32_t)n_tiles;
+        P.n_cand = (uint32_t)n_cand;
+        P.scale = sc->scale;
+        P.t_base = Q.t_wbase;
+        P.cand = Q.cand;
+        P.lpos = (uint32_t*)(w2 + o_lpos);
+        P.job_label_off = (uint32_t*)(w0 + o_jo);
+        P.blk = (unsigned long long*)(w2 + o_blk2);
+        P.tot = Q.tot + OSMT_TQ_N;
+        HIP_TRY(mark(EV_M0));
+        HIP_TRY(osmt_launch_tl_mark(P, st));
+        HIP_TRY(mark(EV_M1));
+        /* second read-back: the label total, the most labels of a tile, the first tile over the limit */
+        HIP_TRY(hipMemcpyAsync(tl_tot, P.tot, 3 * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (tl_tot[OSMT_TL_OVER] != ~0ull) {
+            const size_t t = (size_t)tl_tot[OSMT_TL_OVER];
+            uint32_t base[2];
+            HIP_TRY(hipMemcpyAsync(base, P.job_label_off + t, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            return fail(OSMT_UNSUPPORTED, "tile %zu: %u node labels (> OSMT_TILE_LABELS_MAX = %u)", t, base[1] - base[0], OSMT_TILE_LABELS_MAX);
+        }
+        if (tl_tot[OSMT_TL_LABELS] >= 0xFFFFFFFFull)
+            return fail(OSMT_UNSUPPORTED, "tile labels: the batch has %llu node labels (> 2^32): split the batch", tl_tot[OSMT_TL_LABELS]);
+        n_labels = (size_t)tl_tot[OSMT_TL_LABELS];
+        max_labels = tl_tot[OSMT_TL_MAX_LABELS];
+        off = 0;
+        const size_t o_keys = carve(n_labels * 16), o_eb = carve(n_labels * 4), o_en = carve(n_labels * 4), o_cp = carve((n_labels + 1) * 4);
+        const size_t o_cs = carve(n_labels * 4), o_blk3 = carve((n_labels / 256 + 1) * 8), o_lab = carve(n_labels * sizeof(osmt_label));
+        const size_t o_run = carve(n_labels * sizeof(osmt_string_run));
+        rc = alloc(&wg.work[3], "labels");
+        if (rc != OSMT_OK) return rc;
+        char* w3 = wg.work[3];
+        P.n_labels = (uint32_t)n_labels;
+        P.keys = (ulonglong2*)(w3 + o_keys);
+        P.el_bind = (uint32_t*)(w3 + o_eb);
+        P.el_node = (uint32_t*)(w3 + o_en);
+        P.chpos = (uint32_t*)(w3 + o_cp);
+        P.ch_src = (uint32_t*)(w3 + o_cs);
+        P.blk = (unsigned long long*)(w3 + o_blk3);
+        P.labels = (osmt_label*)(w3 + o_lab);
+        P.runs = (osmt_string_run*)(w3 + o_run);
+        HIP_TRY(mark(EV_O0));
+        HIP_TRY(osmt_launch_tl_order(P, st));
+        HIP_TRY(mark(EV_O1));
+        /* third read-back: the char total */
+        HIP_TRY(hipMemcpyAsync(tl_tot + OSMT_TL_CHARS, P.tot + OSMT_TL_CHARS, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (tl_tot[OSMT_TL_CHARS] >= 0xFFFFFFFFull)
+            return fail(OSMT_UNSUPPORTED, "tile labels: the batch has %llu chars of label text (> 2^32): split the batch", tl_tot[OSMT_TL_CHARS]);
+        n_chars = (size_t)tl_tot[OSMT_TL_CHARS];
+        off = 0;
+        (void)carve(n_chars * 4);
+        rc = alloc(&wg.work[4], "chars");
+        if (rc != OSMT_OK) return rc;
+        P.n_chars = (uint32_t)n_chars;
+        P.chars = (uint32_t*)wg.work[4];
+        HIP_TRY(mark(EV_E0));
+        HIP_TRY(osmt_launch_tl_emit(P, st));
+        HIP_TRY(mark(EV_E1));
+        /* the batch comes back: a few KB per tile */
+        labels.resize(n_labels), runs.resize(n_labels), chars.resize(n_chars);
+        if (n_labels) HIP_TRY(hipMemcpyAsync(labels.data(), P.labels, n_labels * sizeof(osmt_label), hipMemcpyDeviceToHost, st));
+        if (n_labels) HIP_TRY(hipMemcpyAsync(runs.data(), P.runs, n_labels * sizeof(osmt_string_run), hipMemcpyDeviceToHost, st));
+        if (n_chars) HIP_TRY(hipMemcpyAsync(chars.data(), P.chars, n_chars * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(job_off.data(), P.job_label_off, (n_tiles + 1) * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (trace) {
+            auto us = [&](int a, int b2) {
+                float ms = 0.f;
+                (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
+                return ms * 1e3;
+            };
+            fprintf(stderr,
+                    "osmt tile labels: span + columns %.1f us, gather + sort %.1f us, mark + scan %.1f us, expand + sort + count %.1f us, emit %.1f us "
+                    "(%zu tiles, %zu items, %zu candidates, %zu labels, at most %llu in a tile, %zu chars, %zu bytes read back)\n",
+                    us(EV_Q0, EV_Q1), us(EV_G0, EV_M0), us(EV_M0, EV_M1), us(EV_O0, EV_O1), us(EV_E0, EV_E1), n_tiles, n_items, n_cand, n_labels, max_labels,
+                    n_chars, n_labels * (sizeof(osmt_label) + sizeof(osmt_string_run)) + n_chars * 4 + (n_tiles + 1) * 4);
+        }
+    }
+    /* splice: each tile's area labels in front of its node labels (drawer.rs:229-261), seg_off and pt_off re-based */
+    osmt_string_label_batch sb{};
+    std::vector<osmt_label> m_labels;
+    std::vector<osmt_string_run> m_runs;
+    std::vector<uint32_t> m_chars, m_off;
+    if (area && area->n_labels) {
+        if ((unsigned long long)area->n_labels + n_labels >= 0xFFFFFFFFull || (unsigned long long)area->n_chars + n_chars >= 0xFFFFFFFFull)
+            return fail(OSMT_UNSUPPORTED, "tile labels: area and node labels together do not fit 32-bit indices");
+        m_labels.reserve(area->n_labels + n_labels), m_runs.reserve(area->n_labels + n_labels);
+        m_off.assign(n_tiles + 1, 0u);
+        m_chars.assign(area->chars, area->chars + area->n_chars);
+        m_chars.insert(m_chars.end(), chars.begin(), chars.end());
+        for (size_t t = 0; t < n_tiles; ++t) {
+            m_off[t] = (uint32_t)m_labels.size();
+            m_labels.insert(m_labels.end(), area->labels + area->job_label_off[t], area->labels + area->job_label_off[t + 1]);
+            m_runs.insert(m_runs.end(), area->runs + area->job_label_off[t], area->runs + area->job_label_off[t + 1]);
+            for (uint32_t l = job_off[t]; l < job_off[t + 1]; ++l) {
+                osmt_label x = labels[l];
+                x.seg_off += (uint32_t)area->n_chars; /* the node chars sit behind the areas'; a node label has no way points */
+                m_labels.push_back(x);
+                m_runs.push_back(runs[l]);
+            }
+        }
+        m_off[n_tiles] = (uint32_t)m_labels.size();
+        sb.labels = m_labels.data(), sb.n_labels = m_labels.size(), sb.job_label_off = m_off.data(), sb.runs = m_runs.data();
+        sb.chars = m_chars.data(), sb.n_chars = m_chars.size();
+        sb.way_pts = area->way_pts, sb.way_sincos = area->way_sincos, sb.n_way_pts = area->n_way_pts;
+    } else {
+        sb.labels = labels.data(), sb.n_labels = labels.size(), sb.job_label_off = job_off.data(), sb.runs = runs.data();
+        sb.chars = chars.data(), sb.n_chars = chars.size();
+    }
+    rc = osmt_scene_set_labels_body(ctx, sc, nullptr, nullptr, nullptr, &sb);
+    if (rc != OSMT_OK) return rc;
+    sc->h_tl_labels.swap(labels);
+    sc->h_tl_runs.swap(runs);
+    sc->h_tl_chars.swap(chars);
+    sc->h_tl_off.swap(job_off);
+    return OSMT_OK;
+}
+
+static int scene_read_tile_labels_body(osmt_ctx* ctx, osmt_scene* sc, osmt_label* labels, osmt_string_run* runs, uint32_t* chars, uint32_t* job_label_off,
+                                       const size_t* caps, size_t* counts) {
+    if (!ctx || !sc || sc->ctx != ctx || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (sc->h_tl_off.empty()) return fail(OSMT_INVALID_ARG, "the scene has no device-built node labels (osmt_scene_build_tile_labels)");
+    counts[0] = sc->h_tl_labels.size(), counts[1] = sc->h_tl_chars.size();
+    if ((labels || runs || chars) && !caps) return fail(OSMT_INVALID_ARG, "caps is NULL");
+    if ((labels || runs) && caps[0] < counts[0]) return fail(OSMT_INVALID_ARG, "caps[0] = %zu is less than the scene's %zu node labels", caps[0], counts[0]);
+    if (chars && caps[1] < counts[1]) return fail(OSMT_INVALID_ARG, "caps[1] = %zu is less than the scene's %zu chars", caps[1], counts[1]);
+    if (labels && counts[0]) memcpy(labels, sc->h_tl_labels.data(), counts[0] * sizeof(osmt_label));
+    if (runs && counts[0]) memcpy(runs, sc->h_tl_runs.data(), counts[0] * sizeof(osmt_string_run));
+    if (chars && counts[1]) memcpy(chars, sc->h_tl_chars.data(), counts[1] * 4);
+    if (job_label_off) memcpy(job_label_off, sc->h_tl_off.data(), sc->h_tl_off.size() * 4);
+    return OSMT_OK;
+}
+
+int osmt_validate_node_index(const osmt_node_index_desc* index, uint32_t geodata_id, osmt_ctx* ctx) {
+    return guarded([&] { return validate_node_index(index, geodata_id, ctx, nullptr); });
+}
+int osmt_register_node_index(osmt_ctx* ctx, uint32_t geodata_id, const osmt_node_index_desc* index) {
+    return guarded([&] { return register_node_index_body(ctx, geodata_id, index); });
+}
+int osmt_validate_label_styles(const osmt_label_style_rec* styles, size_t n, osmt_ctx* ctx) {
+    return guarded([&] { return validate_label_styles(styles, n, ctx); });
+}
+int osmt_register_label_styles(osmt_ctx* ctx, const osmt_label_style_rec* styles, size_t n, uint32_t* out_first_style_id) {
+    return guarded([&] { return register_label_styles_body(ctx, styles, n, out_first_style_id); });
+}
+int osmt_validate_label_bindings(const osmt_label_bindings_desc* b, osmt_ctx* ctx) {
+    return guarded([&] { return validate_label_bindings(b, ctx, nullptr); });
+}
+int osmt_register_label_bindings(osmt_ctx* ctx, const osmt_label_bindings_desc* b, uint32_t* out_bindings_id) {
+    return guarded([&] { return register_label_bindings_body(ctx, b, out_bindings_id); });
+}
+int osmt_scene_build_tile_labels(osmt_ctx* ctx, osmt_scene* scene, const uint32_t label_bindings_of_zoom[OSMT_MAX_ZOOM + 1],
+                                 const osmt_string_label_batch* area_labels) {
+    return guarded([&] { return scene_build_tile_labels_body(ctx, scene, label_bindings_of_zoom, area_labels); });
+}
+int osmt_scene_read_tile_labels(osmt_ctx* ctx, osmt_scene* scene, osmt_label* labels, osmt_string_run* runs, uint32_t* chars,
+                                uint32_t* job_label_off, const size_t caps[2], size_t counts[2]) {
+    return guarded([&] { return scene_read_tile_labels_body(ctx, scene, labels, runs, chars, job_label_off, caps, counts); });
 }
 
 int osmt_validate_string_labels(const osmt_string_label_batch* sb, size_t n_jobs, osmt_ctx* ctx) {

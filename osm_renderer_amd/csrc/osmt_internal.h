@@ -534,6 +534,59 @@ hipError_t osmt_launch_tq_mark(const osmt_tq_pass& a, hipStream_t st);
 /* k_tq_emit: the styled areas */
 hipError_t osmt_launch_tq_emit(const osmt_tq_pass& a, hipStream_t st);
 
+/* ---- node labels of tile-built scenes (osmt_tilelabels.hip) ----------------------------------------------------- */
+/* The query half is the k_tq_* stages over the NODE pools: osmt_tq_pass::ix with way_off / ways = the node lists and
+ * mp_off = an array of zeros (no second kind), so span, columns, gather and sort run unchanged. */
+/* the scan of the tile query: a[0 .. n) -> its exclusive scan (mod 2^32), a[n] = the total (mod 2^32), *tot = the 64-bit total;
+ * blk: one word per 256 elements, at least one */
+hipError_t osmt_tq_scan(uint32_t* a, uint32_t n, unsigned long long* blk, unsigned long long* tot, hipStream_t st);
+/* a registered label bindings table: node -> (label style, text) in push order, and the text pool */
+struct osmt_tl_bind_dev {
+    const uint32_t* node_off;
+    const osmt_label_binding* bindings;
+    const uint32_t* text_off;
+    const uint32_t* chars;
+};
+/* words of osmt_tl_pass::tot */
+enum {
+    OSMT_TL_LABELS = 0, /* labels of the batch */
+    OSMT_TL_MAX_LABELS, /* the most labels of any tile */
+    OSMT_TL_OVER,       /* the first tile with more than OSMT_TILE_LABELS_MAX labels (none: all ones) */
+    OSMT_TL_CHARS,      /* chars of the batch */
+    OSMT_TL_N
+};
+struct osmt_tl_pass {
+    const osmt_query_tile* q;        /* [n_tiles] */
+    const osmt_tl_bind_dev* bind;    /* [OSMT_MAX_ZOOM + 1] (zooms no tile has: never read) */
+    const double* nodes;             /* the geodata's node table [n_nodes][2] */
+    const uint64_t* node_gid;        /* [n_nodes] */
+    const osmt_label_style_rec* styles;
+    const uint32_t* style_rank;      /* dense rank under (layer or 0, z_index) */
+    const uint32_t* icon_h;          /* [images of the snapshot] heights */
+    uint32_t n_tiles, n_cand, n_labels, n_chars; /* the last three: totals, known once they have been read back */
+    uint32_t scale;
+    const uint32_t* t_base; /* [n_tiles + 1] candidates of the tiles in front (osmt_tq_pass::t_wbase) */
+    const uint32_t* cand;   /* sorted per tile */
+    uint32_t* lpos;         /* [n_cand + 1] labels of the candidate (0 for a repeat), then their exclusive scan */
+    uint32_t* job_label_off; /* [n_tiles + 1] */
+    ulonglong2* keys;       /* [n_labels] rank:32 | gid:64 | element position in the tile:32, sorted in place per tile */
+    uint32_t* el_bind;      /* [n_labels] the element's binding (absolute index in its table), by unsorted position */
+    uint32_t* el_node;      /* [n_labels] its node */
+    uint32_t* chpos;        /* [n_labels + 1] chars of the sorted label, then their exclusive scan */
+    uint32_t* ch_src;       /* [n_labels] where in its table's char pool the label's text starts */
+    unsigned long long* blk;
+    unsigned long long* tot; /* [OSMT_TL_N] */
+    osmt_label* labels;      /* [n_labels] */
+    osmt_string_run* runs;   /* [n_labels] */
+    uint32_t* chars;         /* [n_chars] */
+};
+/* k_tl_mark + scan + k_tl_tiles: label positions, job_label_off, tot[LABELS, MAX_LABELS, OVER] */
+hipError_t osmt_launch_tl_mark(const osmt_tl_pass& a, hipStream_t st);
+/* k_tl_expand + k_tl_sort + k_tl_count + scan: keys in draw order, char positions, tot[CHARS] */
+hipError_t osmt_launch_tl_order(const osmt_tl_pass& a, hipStream_t st);
+/* k_tl_emit + k_tl_chars: the records and the char pool */
+hipError_t osmt_launch_tl_emit(const osmt_tl_pass& a, hipStream_t st);
+
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

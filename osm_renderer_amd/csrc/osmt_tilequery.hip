@@ -326,6 +326,8 @@ inline dim3 grid_of(uint32_t n) { return dim3((n + WG - 1u) / WG); }
 
 }  // namespace
 
+hipError_t osmt_tq_scan(uint32_t* a, uint32_t n, unsigned long long* blk, unsigned long long* tot, hipStream_t st) { return scan(a, n, blk, tot, st); }
+
 hipError_t osmt_launch_tq_span(const osmt_tq_pass& a, hipStream_t st) {
     hipLaunchKernelGGL(k_tq_span, grid_of(a.n_tiles), dim3(WG), 0, st, a);
     return scan(a.item_base, a.n_tiles, a.blk, a.tot + OSMT_TQ_ITEMS, st);

@@ -113,6 +113,34 @@ class Context {
         check(osmt_register_styles(ctx_, styles.data(), styles.size(), dash_pool.data(), dash_pool.size(), &first));
         return first;
     }
+    /* scenes built from tile coordinates: the z18 tile index of a registered file (osmt::TileIndexDesc in
+     * osmt_tilequery.hpp) and a table entity -> style ids per zoom range (osmt::StyleBindings there) */
+    void register_tile_index(uint32_t geodata_id, const osmt_tile_index_desc& desc) { check(osmt_register_tile_index(ctx_, geodata_id, &desc)); }
+    uint32_t register_style_bindings(const osmt_style_bindings_desc& desc) {
+        uint32_t id = 0;
+        check(osmt_register_style_bindings(ctx_, &desc, &id));
+        return id;
+    }
+    /* a font's lookup tables for string labels (text_placer.rs:170-197) */
+    uint32_t register_font(const osmt_font_desc& font) {
+        uint32_t id = 0;
+        check(osmt_register_font(ctx_, &font, &id));
+        return id;
+    }
+    /* node labels of tile-built scenes: the node lists of the registered tile index (osmt::NodeIndexDesc in
+     * osmt_tilelabels.hpp), the label half of the Style records, and a table node -> (label style, text) per zoom range
+     * (osmt::LabelBindings there) */
+    void register_node_index(uint32_t geodata_id, const osmt_node_index_desc& desc) { check(osmt_register_node_index(ctx_, geodata_id, &desc)); }
+    uint32_t register_label_styles(const std::vector<osmt_label_style_rec>& styles) {
+        uint32_t first = 0;
+        check(osmt_register_label_styles(ctx_, styles.data(), styles.size(), &first));
+        return first;
+    }
+    uint32_t register_label_bindings(const osmt_label_bindings_desc& desc) {
+        uint32_t id = 0;
+        check(osmt_register_label_bindings(ctx_, &desc, &id));
+        return id;
+    }
 
   private:
     osmt_ctx* ctx_ = nullptr;
@@ -129,6 +157,45 @@ class StyledScene {
     osmt_scene* raw() const { return scene_; }
 
   private:
+    osmt_scene* scene_ = nullptr;
+};
+
+/* The node labels a TileScene built on the GPU, as read back: label l reads chars[labels[l].seg_off .. + n_segs), tile t owns
+ * labels [job_label_off[t], job_label_off[t + 1]). */
+struct TileLabels {
+    std::vector<osmt_label> labels;
+    std::vector<osmt_string_run> runs;
+    std::vector<uint32_t> chars, job_label_off;
+};
+
+/* A scene built from tile coordinates (osmt_scene_build_tiles): 16 bytes per tile in, the scene StyledScene builds from the
+ * same entities out.  build_tile_labels gives it the label pass of Drawer::draw_labels: the node labels are queried, ordered
+ * and assembled on the GPU, the caller's way and multipolygon labels are drawn in front of them (drawer.rs:229-261). */
+class TileScene {
+  public:
+    TileScene(Context& ctx, const osmt_tile_batch& batch) : ctx_(&ctx), n_tiles_(batch.n_tiles) { check(osmt_scene_build_tiles(ctx.raw(), &batch, &scene_)); }
+    ~TileScene() { osmt_scene_free(scene_); }
+    TileScene(const TileScene&) = delete;
+    TileScene& operator=(const TileScene&) = delete;
+    osmt_scene* raw() const { return scene_; }
+    size_t tile_count() const { return n_tiles_; }
+    /* label_bindings_of_zoom[z]: id from Context::register_label_bindings, or OSMT_BINDINGS_NONE */
+    void build_tile_labels(const uint32_t (&label_bindings_of_zoom)[OSMT_MAX_ZOOM + 1], const osmt_string_label_batch* area_labels = nullptr) {
+        check(osmt_scene_build_tile_labels(ctx_->raw(), scene_, label_bindings_of_zoom, area_labels));
+    }
+    /* the node batch the device built, before the area labels were put in front */
+    TileLabels read_tile_labels() const {
+        TileLabels out;
+        size_t n[2] = {0, 0};
+        check(osmt_scene_read_tile_labels(ctx_->raw(), scene_, nullptr, nullptr, nullptr, nullptr, nullptr, n));
+        out.labels.resize(n[0]), out.runs.resize(n[0]), out.chars.resize(n[1]), out.job_label_off.resize(n_tiles_ + 1);
+        check(osmt_scene_read_tile_labels(ctx_->raw(), scene_, out.labels.data(), out.runs.data(), out.chars.data(), out.job_label_off.data(), n, n));
+        return out;
+    }
+
+  private:
+    Context* ctx_;
+    size_t n_tiles_;
     osmt_scene* scene_ = nullptr;
 };
 

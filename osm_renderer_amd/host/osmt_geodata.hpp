@@ -170,6 +170,7 @@ class GeodataReader {
 
     /* Tile (reader.rs:217-229): the z18 tiles in file order = ascending (x, y), and their reference lists */
     std::pair<uint32_t, uint32_t> tile_xy(size_t i) const { return {tile_x_at(i), tile_y_at(i)}; }
+    std::pair<const uint32_t*, size_t> tile_node_ids(size_t i) const { return ints_by_ref(tiles_.at(i) + 8); }
     std::pair<const uint32_t*, size_t> tile_way_ids(size_t i) const { return ints_by_ref(tiles_.at(i) + 16); }
     std::pair<const uint32_t*, size_t> tile_multipolygon_ids(size_t i) const { return ints_by_ref(tiles_.at(i) + 24); }
 

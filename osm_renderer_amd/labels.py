@@ -844,6 +844,22 @@ def concat_string_labels(lists):
                            np.concatenate(pts) if pts else np.zeros((0, 2), np.int32), np.concatenate(scs) if scs else np.zeros((0, 2)))
 
 
+def splice_string_labels(area, node):
+    """What osmt_scene_build_tile_labels attaches: per tile the labels of `area` in front of those of `node` (a batch
+    without way points: node labels), the node chars behind the areas' and every node label's seg_off moved by them."""
+    assert area.n_jobs == node.n_jobs and len(node.way_pts) == 0
+    lab, runs, offs = [], [], [0]
+    moved = node.labels.copy()
+    moved["seg_off"] += len(area.chars)
+    for t in range(area.n_jobs):
+        a0, a1, n0, n1 = (int(v) for v in (*area.job_label_off[t : t + 2], *node.job_label_off[t : t + 2]))
+        lab += [area.labels[a0:a1], moved[n0:n1]]
+        runs += [area.runs[a0:a1], node.runs[n0:n1]]
+        offs.append(offs[-1] + (a1 - a0) + (n1 - n0))
+    return StringLabelList(np.concatenate(lab) if lab else np.zeros(0, LABEL_DTYPE), offs, np.concatenate(runs) if runs else np.zeros(0, STRING_RUN_DTYPE),
+                           np.concatenate([area.chars, node.chars]), area.way_pts, area.way_sincos)
+
+
 _SYNTH_CP_BASE = 0x4E00  # code point of synthetic glyph g (not a space): _SYNTH_CP_BASE + g
 
 

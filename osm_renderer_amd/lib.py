@@ -39,6 +39,8 @@ EXPORTS = [
     "osmt_scene_build_styled", "osmt_scene_read_display_list", "osmt_scene_max_tile_ops",
     "osmt_validate_tile_index", "osmt_register_tile_index", "osmt_validate_style_bindings", "osmt_register_style_bindings",
     "osmt_validate_tile_batch", "osmt_scene_build_tiles", "osmt_scene_read_styled_areas",
+    "osmt_validate_node_index", "osmt_register_node_index", "osmt_validate_label_styles", "osmt_register_label_styles",
+    "osmt_validate_label_bindings", "osmt_register_label_bindings", "osmt_scene_build_tile_labels", "osmt_scene_read_tile_labels",
 ]
 
 
@@ -156,6 +158,15 @@ def load():
         L.osmt_validate_tile_batch.argtypes = [C.POINTER(abi.TileBatch), vp]
         L.osmt_scene_build_tiles.argtypes = [vp, C.POINTER(abi.TileBatch), C.POINTER(vp)]
         L.osmt_scene_read_styled_areas.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "osmt_scene_build_tile_labels"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_validate_node_index.argtypes = [C.POINTER(abi.NodeIndexDesc), C.c_uint32, vp]
+        L.osmt_register_node_index.argtypes = [vp, C.c_uint32, C.POINTER(abi.NodeIndexDesc)]
+        L.osmt_validate_label_styles.argtypes = [C.POINTER(abi.LabelStyleRec), C.c_size_t, vp]
+        L.osmt_register_label_styles.argtypes = [vp, C.POINTER(abi.LabelStyleRec), C.c_size_t, C.POINTER(C.c_uint32)]
+        L.osmt_validate_label_bindings.argtypes = [C.POINTER(abi.LabelBindingsDesc), vp]
+        L.osmt_register_label_bindings.argtypes = [vp, C.POINTER(abi.LabelBindingsDesc), C.POINTER(C.c_uint32)]
+        L.osmt_scene_build_tile_labels.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(abi.StringLabelBatch)]
+        L.osmt_scene_read_tile_labels.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

@@ -93,6 +93,32 @@ class Scene:
         check(L.osmt_scene_read_styled_areas(self.ctx._h, self._h, ptr(tiles), ptr(areas), len(areas), C.byref(n)))
         return tiles, areas
 
+    def build_tile_labels(self, label_bindings, area_labels=None):
+        """osmt_scene_build_tile_labels: the node labels of every tile of a scene of Context.build_tiles, built on the GPU
+        and attached as string labels.  label_bindings: {zoom: id from Context.register_label_bindings}; area_labels: a
+        labels.StringLabelList of host-built way / multipolygon labels drawn in front of each tile's node labels."""
+        from .labels import splice_string_labels
+
+        ids = (C.c_uint32 * (abi.MAX_ZOOM + 1))(*[int(dict(label_bindings).get(z, abi.BINDINGS_NONE)) for z in range(abi.MAX_ZOOM + 1)])
+        sb = area_labels.as_batch() if area_labels is not None else None
+        check(load().osmt_scene_build_tile_labels(self.ctx._h, self._h, ids, C.byref(sb) if sb is not None else None))
+        node = self.read_tile_labels()
+        self.labels = node if area_labels is None else splice_string_labels(area_labels, node)
+        return node
+
+    def read_tile_labels(self):
+        """osmt_scene_read_tile_labels: the node batch the device built, before the splice, as a labels.StringLabelList."""
+        from .labels import LABEL_DTYPE, STRING_RUN_DTYPE, StringLabelList
+
+        L, n = load(), (C.c_size_t * 2)()
+        check(L.osmt_scene_read_tile_labels(self.ctx._h, self._h, None, None, None, None, None, n))
+        lab, runs, chars = np.zeros(n[0], LABEL_DTYPE), np.zeros(n[0], STRING_RUN_DTYPE), np.zeros(n[1], np.uint32)
+        off = np.zeros(self.n_jobs + 1, np.uint32)
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+        caps = (C.c_size_t * 2)(n[0], n[1])
+        check(L.osmt_scene_read_tile_labels(self.ctx._h, self._h, ptr(lab), ptr(runs), ptr(chars), ptr(off), caps, n))
+        return StringLabelList(lab, off, runs, chars, np.zeros((0, 2), np.int32), np.zeros((0, 2)))
+
     def max_tile_ops(self):
         """osmt_scene_max_tile_ops: the most ops of any tile, as the renderer knows it (it picks its list kernel by it)"""
         out = C.c_uint32()
@@ -370,6 +396,28 @@ class Context:
         h = C.c_void_p()
         check(load().osmt_scene_build_tiles(self._h, C.byref(b), C.byref(h)))
         return Scene._built(self, h, batch.n_jobs, batch.scale, getattr(self, "_geodata_nodes", {}).get(batch.geodata_id))
+
+    # -- node labels of tile-built scenes ---------------------------------------------
+    def register_node_index(self, geodata_id, index):
+        """osmt_register_node_index: uploads a styled.NodeIndex for a geodata file whose tile index is registered."""
+        d = index.as_desc()
+        check(load().osmt_register_node_index(self._h, geodata_id, C.byref(d)))
+
+    def register_label_styles(self, styles):
+        """osmt_register_label_styles: appends styled.LABEL_STYLE_REC_DTYPE records; returns the id of the first."""
+        from .styled import LABEL_STYLE_REC_DTYPE
+
+        st = np.ascontiguousarray(styles, dtype=LABEL_STYLE_REC_DTYPE)
+        out = C.c_uint32()
+        check(load().osmt_register_label_styles(self._h, st.ctypes.data_as(C.POINTER(abi.LabelStyleRec)) if len(st) else None, len(st), C.byref(out)))
+        return out.value
+
+    def register_label_bindings(self, bindings):
+        """osmt_register_label_bindings: appends a styled.LabelBindings table; returns its id."""
+        d = bindings.as_desc()
+        out = C.c_uint32()
+        check(load().osmt_register_label_bindings(self._h, C.byref(d), C.byref(out)))
+        return out.value
 
     # -- glyph outlines (glyph-run labels) -----------------------------------------
     def register_glyphs(self, table):

@@ -162,3 +162,54 @@ class TileBatch:
         for z in range(abi.MAX_ZOOM + 1):
             b.bindings_of_zoom[z] = self.bindings.get(z, abi.BINDINGS_NONE)
         return b
+
+
+LABEL_STYLE_REC_DTYPE = np.dtype(
+    [
+        ("layer", "<i8"), ("z_index", "<f8"), ("font_size", "<f8"), ("icon_image", "<u4"), ("font_id", "<u4"),
+        ("has_layer", "u1"), ("has_icon", "u1"), ("has_text_style", "u1"), ("has_font_size", "u1"),
+        ("has_text_color", "u1"), ("text_color", "u1", (3,)), ("text_position", "u1"), ("_pad", "u1", (7,)),
+    ]
+)
+LABEL_BINDING_DTYPE = np.dtype([("style", "<u4"), ("text", "<u4")])
+assert LABEL_STYLE_REC_DTYPE.itemsize == 48 and LABEL_BINDING_DTYPE.itemsize == 8
+
+
+class NodeIndex:
+    """osmt_node_index_desc: the nodes' global ids and the node lists of the z18 tiles of the TileIndex registered for the
+    same geodata id.  tiles: one list of local node ids per index tile, in the index's order."""
+
+    def __init__(self, node_ids, tiles):
+        self.node_ids = np.array(node_ids, dtype=np.uint64).reshape(-1)
+        self.node_off, self.nodes = _csr([list(v) for v in tiles])
+
+    def as_desc(self):
+        u32 = C.POINTER(C.c_uint32)
+        d = abi.NodeIndexDesc()
+        d.node_ids, d.n_nodes = self.node_ids.ctypes.data_as(C.POINTER(C.c_uint64)), len(self.node_ids)
+        d.node_off, d.nodes, d.n_node_refs = self.node_off.ctypes.data_as(u32), self.nodes.ctypes.data_as(u32), len(self.nodes)
+        return d
+
+
+class LabelBindings:
+    """osmt_label_bindings_desc: per node the (label style id, text id) pairs Styler::style_entities pushes for it at zooms
+    zoom_lo..zoom_hi, in push order.  node_bindings: one list of (style, text id or None) per node; texts: the pool, each a
+    str or a list of code points."""
+
+    def __init__(self, geodata_id, zoom_lo, zoom_hi, node_bindings, texts=()):
+        self.geodata_id, self.zoom_lo, self.zoom_hi = int(geodata_id), int(zoom_lo), int(zoom_hi)
+        self.node_off = np.zeros(len(node_bindings) + 1, dtype=np.uint32)
+        if len(node_bindings):
+            self.node_off[1:] = np.cumsum([len(v) for v in node_bindings])
+        flat = [(int(s), abi.TEXT_NONE if t is None else int(t)) for v in node_bindings for s, t in v]
+        self.bindings = np.array(flat, dtype=LABEL_BINDING_DTYPE).reshape(-1)
+        self.text_off, self.chars = _csr([[ord(c) for c in t] if isinstance(t, str) else list(t) for t in texts])
+
+    def as_desc(self):
+        u32 = C.POINTER(C.c_uint32)
+        d = abi.LabelBindingsDesc()
+        d.geodata_id, d.zoom_lo, d.zoom_hi = self.geodata_id, self.zoom_lo, self.zoom_hi
+        d.node_off, d.bindings, d.n_bindings = self.node_off.ctypes.data_as(u32), self.bindings.ctypes.data_as(C.POINTER(abi.LabelBinding)), len(self.bindings)
+        d.text_off, d.n_texts = self.text_off.ctypes.data_as(u32), len(self.text_off) - 1
+        d.chars, d.n_chars = self.chars.ctypes.data_as(u32), len(self.chars)
+        return d

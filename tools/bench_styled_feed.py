@@ -22,6 +22,16 @@ nodes span) and with one style bound to every way:
 
 timed the same way — scene build only, and build + one render —, the stages of (d) from OSMT_TRACE_UPLOAD=1 in a child run.
 Output: profiles/tile_query_bench.json.
+
+--labels runs a third pair on a world of labelled nodes (24 per tile: text, icon + text, icon only), over one scene of
+osmt_scene_build_tiles:
+
+  (e) the host labels:   osmt::node_labels_of_tile for every tile on one thread (query, style lookup, stable sort,
+                         Point::from_node, records), then osmt_scene_set_string_labels
+  (f) the device labels: osmt_scene_build_tile_labels over the registered node index, label styles and label bindings
+
+timed the same way, from the call to labels attached to the scene; the stages of (f) and the size of its read-back from
+OSMT_TRACE_UPLOAD=1 in a child run.  Output: profiles/tile_labels_bench.json.
 """
 import argparse
 import ctypes as C
@@ -227,6 +237,148 @@ def tiles_only(args):
         sys.exit("the two feeds disagree")
 
 
+def tile_labels(args):
+    import time
+
+    import torch
+
+    from osm_renderer_amd import labels
+    from tests import _tilelabels as tl
+    from tests import _tilequery as tq
+    from tests._geodata import Reader
+
+    rng = np.random.default_rng(3)
+    side = int(math.ceil(math.sqrt(args.tiles)))
+    tiles = [(ZOOM, X0 + t % side, Y0 + t // side) for t in range(args.tiles)]
+    per_tile = 24
+    nodes = []
+    for _, tx, ty in tiles:
+        for _ in range(per_tile):
+            x, y = rng.uniform(6, 250, 2)
+            lat, lon = _latlon(256.0 * tx + x, 256.0 * ty + y)
+            nodes.append((10**6 + len(nodes), lat, lon, {}))
+    tmp = tempfile.mkdtemp(prefix="tile_labels_")
+    path = os.path.join(tmp, "world.bin")
+    refs = write_geodata(path, nodes, max_zoom_tile=tq.max_zoom_tile)
+    r = Reader(path)
+    ctx = Context(0)
+    syn = labels.synth_glyph_table()
+    ctx.register_glyphs(syn)
+    ns = len(labels.SYNTH_GLYPHS)
+    shapes = [ns - 1] + [(g - 1) % (ns - 1) for g in range(1, 13)] + [ns - 1]
+    font = labels.FontTable([(0x20, 13)] + [(0x41 + i, 1 + i) for i in range(12)], [300] + [labels.SYNTH_GLYPHS[s][0] for s in shapes[1:]],
+                            [syn.first_id + s for s in shapes])
+    ctx.register_font(font)
+    icon = ctx.register_image(rng.integers(0, 256, size=(12, 12, 4)).astype(np.uint8))
+    gid = ctx.register_geodata(styled.Geodata([[n[1], n[2]] for n in nodes]))
+    ctx.register_tile_index(gid, styled.TileIndex([(k, [], []) for k in sorted(refs)]))
+    ctx.register_node_index(gid, styled.NodeIndex([n[0] for n in nodes], [sorted(refs[k][0]) for k in sorted(refs)]))
+    area_bind = ctx.register_style_bindings(styled.StyleBindings(gid, 0, 18, [], []))
+    rows = [dict(font_size=10.0, font_id=font.font_id), dict(layer=1, icon=icon, font_size=9.0, font_id=font.font_id, text_color=(120, 0, 40)),
+            dict(z_index=2.0, icon=icon), dict(layer=-1, font_size=12.0, font_id=font.font_id, text_color=(0, 60, 160))]
+    rec = tl.label_styles(rows)
+    first = ctx.register_label_styles(rec)
+    all_styles = np.concatenate([np.zeros(first, styled.LABEL_STYLE_REC_DTYPE), rec])
+    icon_h = np.array([0] * first + [0, 12, 12, 0], dtype=np.uint32)
+    texts = ["".join(chr(0x41 + int(c)) for c in rng.integers(0, 12, int(n))) for n in rng.integers(4, 13, 64)]
+    bind = [[(first + int(rng.integers(0, 4)), int(rng.integers(0, len(texts))))] for _ in nodes]
+    lbid = ctx.register_label_bindings(styled.LabelBindings(gid, 0, 18, bind, texts))
+    mir = tl.Mirror(r, bind, texts, gid)
+    scene = ctx.build_tiles(styled.TileBatch(gid, tiles, {ZOOM: area_bind}))
+    zxy = np.array(tiles, dtype=np.uint32)
+    S, L = tl.shim(), lib.load()
+    sz2 = C.c_size_t * 2
+    caps, n = sz2(per_tile * 9 * len(tiles), per_tile * 9 * len(tiles) * 12), sz2()
+    lab, runs = np.zeros(caps[0], labels.LABEL_DTYPE), np.zeros(caps[0], labels.STRING_RUN_DTYPE)
+    chars, off = np.zeros(caps[1], np.uint32), np.zeros(len(tiles) + 1, np.uint32)
+    ids = (C.c_uint32 * (abi.MAX_ZOOM + 1))(*[lbid if z == ZOOM else abi.BINDINGS_NONE for z in range(abi.MAX_ZOOM + 1)])
+
+    def host_batch():
+        S.tl_batch(r.h, mir.h, all_styles.ctypes.data, icon_h.ctypes.data_as(C.POINTER(C.c_uint32)), len(all_styles), zxy.ctypes.data, len(zxy), 1,
+                   lab.ctypes.data, runs.ctypes.data, chars.ctypes.data, off.ctypes.data, caps, n)
+        assert n[0] <= caps[0] and n[1] <= caps[1]
+        return labels.StringLabelList(lab[: n[0]], off, runs[: n[0]], chars[: n[1]], np.zeros((0, 2), np.int32), np.zeros((0, 2)))
+
+    def run(which, render):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if which == "e":
+            sl = host_batch()
+            t1 = time.perf_counter()
+            sb = sl.as_batch()
+            lib.check(L.osmt_scene_set_string_labels(ctx._h, scene._h, C.byref(sb)))
+        else:
+            t1 = t0
+            lib.check(L.osmt_scene_build_tile_labels(ctx._h, scene._h, ids, None))
+        t2 = time.perf_counter()
+        if render:
+            ctx.render(scene)
+            torch.cuda.synchronize()
+        return t1 - t0, t2 - t0, time.perf_counter() - t0
+
+    times = {(w, rd): [] for w in "ef" for rd in (False, True)}
+    for rep in range(args.warmup + args.reps):
+        for render in (False, True):
+            for which in ("e", "f") if rep % 2 == 0 else ("f", "e"):
+                t = run(which, render)
+                if rep >= args.warmup:
+                    times[(which, render)].append(t)
+    if args.child:
+        return
+    run("e", False)
+    want = host_batch()
+    px_e = ctx.render(scene).cpu().numpy()
+    st_e = np.zeros(len(want.labels), np.uint8)
+    lib.check(L.osmt_scene_read_label_status(ctx._h, scene._h, st_e.ctypes.data_as(C.POINTER(C.c_uint8))))
+    run("f", False)
+    got = scene.read_tile_labels()
+    same_batch = bool(all(getattr(got, k).tobytes() == getattr(want, k).tobytes() for k in ("labels", "runs", "chars", "job_label_off")))
+    px_f = ctx.render(scene).cpu().numpy()
+    st_f = np.zeros(len(got.labels), np.uint8)
+    lib.check(L.osmt_scene_read_label_status(ctx._h, scene._h, st_f.ctypes.data_as(C.POINTER(C.c_uint8))))
+    same_px = bool(np.array_equal(px_e, px_f) and np.array_equal(st_e, st_f))
+
+    def stat(rows, k):
+        v = np.array([row[k] for row in rows])
+        return {"median_ms": float(np.median(v) * 1e3), "min_ms": float(v.min() * 1e3), "max_ms": float(v.max() * 1e3),
+                "p25_ms": float(np.percentile(v, 25) * 1e3), "p75_ms": float(np.percentile(v, 75) * 1e3), "runs": len(v)}
+
+    env = dict(os.environ, OSMT_TRACE_UPLOAD="1")
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--labels", "--tiles", str(args.tiles), "--reps", str(args.reps), "--warmup",
+                        str(args.warmup), "--child"], env=env, capture_output=True, text=True, timeout=900)
+    names = ("span_columns", "gather_sort", "mark_scan", "expand_sort_count", "emit")
+    rows = re.findall(r"osmt tile labels: span \+ columns ([0-9.]+) us, gather \+ sort ([0-9.]+) us, mark \+ scan ([0-9.]+) us, expand \+ sort \+ count "
+                      r"([0-9.]+) us, emit ([0-9.]+) us .*?, (\d+) bytes read back", p.stderr)
+    if p.returncode != 0 or len(rows) <= 2 * args.warmup:
+        raise RuntimeError("the traced child run failed:\n" + p.stderr[-2000:])
+    rows = np.array(rows[2 * args.warmup:], dtype=np.float64)
+    med = lambda w, rd, k: float(np.median([t[k] for t in times[(w, rd)]]))
+    res = {
+        "workload": {"tiles": len(tiles), "zoom": ZOOM, "nodes": len(nodes), "index_tiles": len(refs), "label_styles": int(len(rec)),
+                     "labels": int(len(want.labels)), "chars": int(len(want.chars)), "labels_placed": int(st_f.sum())},
+        "host_labels_e": {"mirror": stat(times[("e", False)], 0), "labels_attached": stat(times[("e", False)], 1),
+                          "attach_and_render": stat(times[("e", True)], 2)},
+        "device_labels_f": {"labels_attached": stat(times[("f", False)], 1), "attach_and_render": stat(times[("f", True)], 2)},
+        "speedup_median_e_over_f": med("e", False, 1) / med("f", False, 1),
+        "device_path_is_faster": bool(med("f", False, 1) < med("e", False, 1)),
+        "device_stages_f_us_median": dict({k: float(np.median(rows[:, i])) for i, k in enumerate(names)}, total=float(np.median(rows[:, :5].sum(axis=1))),
+                                          runs=int(len(rows))),
+        "read_back_bytes_f": int(rows[-1, 5]),
+        "bytes_sent": {"host_labels_e": int(want.input_bytes()), "device_labels_f": int(want.input_bytes()),
+                       "note": "(f) reads the batch back and hands it to the string-label path, which uploads it again"},
+        "same_batch": same_batch,
+        "same_pixels_and_statuses": same_px,
+    }
+    text = json.dumps(res, indent=1)
+    print(text)
+    out = os.path.join(os.path.dirname(args.out), "tile_labels_bench.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text + "\n")
+    if not same_px:
+        sys.exit("the two label feeds disagree")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=1024)
@@ -235,10 +387,13 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "styled_feed_bench.json"))
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--tiles-only", action="store_true", help="the tile-query pair (c) / (d) instead of (a) / (b)")
+    ap.add_argument("--labels", action="store_true", help="the node-label pair (e) / (f) instead of (a) / (b)")
     args = ap.parse_args()
     assert args.reps >= 10 or args.child
     if args.tiles_only:
         return tiles_only(args)
+    if args.labels:
+        return tile_labels(args)
 
     L = _native()
     rng = np.random.default_rng(1)
