@@ -524,7 +524,9 @@ int osmt_debug_hypot(osmt_ctx* ctx, const double* xy, size_t n, double* out);
  * order) over one pool of double[n_pts][2].  Points are what nodes_to_points produces (:61-68):
  * coords_to_xy_tile_relative(node, tile) * scale, UNROUNDED f64.  The host projects: the device projection's tan / log are
  * only exact behind Point::from_node's rounding to i32, and a last-bit difference here can flip a branch of the search —
- * there is no (lat, lon) input form.  Points must be finite with |v| <= 2^28. */
+ * there is no (lat, lon) input form.  Points must be finite with |v| <= 2^28.  (The form that takes no points at all —
+ * an entity and a tile per request, projected on the device from Mercator factors the caller registered with its own libm —
+ * is osmt_label_positions_tiles below.) */
 typedef struct osmt_label_request {
     uint32_t ring_off; /* first entry in osmt_label_request_batch.rings */
     uint32_t n_rings;
@@ -777,6 +779,63 @@ int osmt_scene_build_tiles(osmt_ctx* ctx, const osmt_tile_batch* batch, osmt_sce
  * from any other source, or when areas_cap is less than *n_areas. */
 int osmt_scene_read_styled_areas(osmt_ctx* ctx, osmt_scene* scene, osmt_styled_tile* tiles, osmt_styled_area* areas,
                                  size_t areas_cap, size_t* n_areas);
+
+/* ---- label anchors from tile coordinates: the exact projection on the GPU ---------------------------------------- */
+/* osmt_label_positions for callers that hold a registered geodata file: a request is 8 bytes — an entity and a tile — and
+ * the device does what nodes_to_points does (labelable.rs:61-68), bit for bit.  The one libm step of coords_to_xy
+ * (tile.rs:88-95), PI - tan(..).ln(), and the division by 2 PI behind it depend on the node alone, not on zoom or tile: the
+ * caller computes them once per node and registers them.  Everything after that is exact IEEE arithmetic that every machine
+ * rounds alike: factor * f64::from(256 << zoom) (a power of two), - f64::from(tile.x * 256) (one rounding), * scale (one
+ * rounding).  The kernels (csrc/osmt_anchors.hip) run the three operations unfused and call no tan or log.
+ *
+ * factors[i] = ((lon_rad + PI) / (2 PI), (PI - ln(tan(PI / 4 + lat_rad / 2))) / (2 PI)) of node i, lat_rad = lat * (PI / 180)
+ * as f64::to_radians; osmt::mercator_factors (host/osmt_geodata.hpp) is that formula, INTEGRATION.md has the Rust line.
+ *
+ * Why no point is range-checked afterwards: a factor f lies in [0, 1] and dim = 256 << zoom <= 2^26 at zoom <= 18, so f * dim
+ * lies in [0, 2^26] (a multiplication by a power of two is exact); the tile offset 256 * x lies in [0, 2^26 - 256]; the
+ * difference therefore has magnitude <= 2^26 and, rounding being monotonic, so has its rounded value; times scale <=
+ * OSMT_MAX_SCALE = 4 that is <= 2^28 — the bound the polylabel kernels admit. */
+
+/* The checks osmt_register_node_mercator runs first, on the host.  OSMT_INVALID_ARG, naming the offender: NULL with a count; a
+ * factor that is not finite or lies outside [0, 1]; an unknown geodata id (a NULL `ctx` has none); n_nodes that is not the
+ * geodata's; a geodata id that has its factors already. */
+int osmt_validate_node_mercator(const double* factors /* [n_nodes][2] */, size_t n_nodes, uint32_t geodata_id, osmt_ctx* ctx);
+/* Uploads the factors of every node of a registered geodata file: one allocation that never moves and lives as long as the
+ * context (the snapshot rule of the tile index).  One table per geodata id: a second registration is OSMT_INVALID_ARG. */
+int osmt_register_node_mercator(osmt_ctx* ctx, uint32_t geodata_id, const double* factors /* [n_nodes][2] */);
+
+typedef struct osmt_label_tile_request { /* 8 bytes */
+    uint32_t entity; /* local id of a way; of a multipolygon: | OSMT_STYLED_MULTIPOLYGON */
+    uint32_t tile;   /* index into osmt_label_tile_batch.tiles */
+} osmt_label_tile_request;
+
+typedef struct osmt_label_tile_batch {
+    const osmt_label_tile_request* requests;
+    size_t n_requests;
+    const osmt_query_tile* tiles; /* the array a caller hands to osmt_scene_build_tiles; the canvas fields are ignored */
+    size_t n_tiles;
+    uint32_t geodata_id, scale; /* scale 1 .. OSMT_MAX_SCALE: the factor of nodes_to_points AND the `scale` of get_label_position */
+} osmt_label_tile_batch;
+
+/* Host only.  OSMT_INVALID_ARG, naming the offender: a NULL pool with a non-zero count; scale outside 1..OSMT_MAX_SCALE; a
+ * tile with zoom > 18 or x or y >= 2^zoom; a request whose tile index is >= n_tiles; an unknown geodata id (a NULL `ctx` has
+ * none) or one without registered factors; an entity id that is not a way / multipolygon of the geodata. */
+int osmt_validate_label_tile_batch(const osmt_label_tile_batch* batch, osmt_ctx* ctx);
+/* get_label_position of every request: a way is ONE ring of its nodes, a multipolygon ALL polygon_count() polygons in file
+ * order, polygons of 0 or 1 node included (labelable.rs:41-59) — not the >= 2-node rings a display list draws.  `out` gets
+ * n_requests records with the meaning they have in osmt_label_positions (OK, NONE, TOO_LARGE), and
+ * osmt_label_positions_stats reports the call.  Validates first (`out` is not touched when it fails).  OSMT_UNSUPPORTED with
+ * the exact figure: a ring total or a point total of the batch that does not fit 32 bits (decided from the device's 64-bit
+ * totals before anything is allocated for rings or points).  Zero requests: OSMT_OK, no device is touched. */
+int osmt_label_positions_tiles(osmt_ctx* ctx, const osmt_label_tile_batch* batch, osmt_label_position* out);
+/* The same call in two halves; the job ends with osmt_label_positions_end.  _begin waits for one small read-back (the
+ * totals that size the point pool) and returns with the projection, the search and the read-back of the positions queued. */
+int osmt_label_positions_tiles_begin(osmt_ctx* ctx, const osmt_label_tile_batch* batch, osmt_label_job** out_job);
+/* Inspection (tests, tools): the rings and points the search of this batch would be given — rings[i].first_pt / n_pts index
+ * `points` ([n][2], x then y), rings in request order.  counts[0] = rings, counts[1] = points, always set when the batch is
+ * accepted; NULL for both outputs asks for the sizes; a capacity below a count with a non-NULL output is OSMT_INVALID_ARG. */
+int osmt_label_tile_batch_expand(osmt_ctx* ctx, const osmt_label_tile_batch* batch, osmt_ring* rings, double* points, size_t rings_cap,
+                                 size_t points_cap, size_t counts[2]);
 
 /* ---- node labels of tile-built scenes: query, order and label records on the GPU --------------------------------- */
 /* What Drawer::draw_labels does for the NODES of a tile (drawer.rs:251-260), for a scene of osmt_scene_build_tiles: the 3 x 3

@@ -258,6 +258,10 @@ class LabelPosition(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("status", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class LabelTileRequest(C.Structure):
+    _fields_ = [("entity", C.c_uint32), ("tile", C.c_uint32)]
+
+
 class GeodataDesc(C.Structure):
     _fields_ = [
         ("nodes", C.POINTER(C.c_double)),
@@ -396,6 +400,17 @@ class TileBatch(C.Structure):
     ]
 
 
+class LabelTileBatch(C.Structure):
+    _fields_ = [
+        ("requests", C.POINTER(LabelTileRequest)),
+        ("n_requests", C.c_size_t),
+        ("tiles", C.POINTER(QueryTile)),
+        ("n_tiles", C.c_size_t),
+        ("geodata_id", C.c_uint32),
+        ("scale", C.c_uint32),
+    ]
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32)]
 
@@ -422,6 +437,8 @@ assert C.sizeof(TileIndexDesc) == 64
 assert C.sizeof(StyleBindingsDesc) == 56
 assert C.sizeof(QueryTile) == 16
 assert C.sizeof(TileBatch) == 112
+assert C.sizeof(LabelTileRequest) == 8
+assert C.sizeof(LabelTileBatch) == 40
 
 
 class NodeIndexDesc(C.Structure):

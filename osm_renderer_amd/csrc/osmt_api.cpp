@@ -14,6 +14,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <dlfcn.h>
 
 #include <memory>
@@ -141,6 +142,8 @@ struct osmt_ctx {
         void* d_node_index = nullptr;
         const uint32_t *d_node_off = nullptr, *d_node_refs = nullptr, *d_zero_off = nullptr; /* [ix.n_tiles + 1], pool, [ix.n_tiles + 1] zeros */
         const uint64_t* d_node_gid = nullptr;
+        /* the Mercator factors of its nodes (osmt_register_node_mercator): at most one table, same rules */
+        const double2* d_factors = nullptr; /* [n_nodes] */
     };
     std::vector<geodata_host> geodata;
     /* the tables of osmt_register_style_bindings: append-only, one device allocation each that never moves, so a build
@@ -652,6 +655,7 @@ void ctx_teardown(osmt_ctx* ctx) {
         if (g.d_pool) (void)hipFree(g.d_pool);
         if (g.d_index) (void)hipFree(g.d_index);
         if (g.d_node_index) (void)hipFree(g.d_node_index);
+        if (g.d_factors) (void)hipFree((void*)g.d_factors);
     }
     for (auto& b : ctx->bindings)
         if (b.d_pool) (void)hipFree(b.d_pool);
@@ -3908,6 +3912,7 @@ struct osmt_label_job {
     osmt_ctx* ctx = nullptr;
     hipStream_t st = nullptr;
     char* d_base = nullptr;
+    char* d_front = nullptr; /* tile requests: what was allocated before the totals were known */
     char* stage = nullptr; /* pinned: the request records going up, then the positions and the counters coming back */
     size_t n = 0, back_off = 0;
 };
@@ -3916,6 +3921,7 @@ static void label_job_free(osmt_label_job* j) {
     if (!j) return;
     if (j->ctx) {
         if (j->d_base) dev_free(j->ctx, j->d_base);
+        if (j->d_front) dev_free(j->ctx, j->d_front);
         if (j->stage) stage_release(j->ctx, j->stage);
         if (j->st) stream_release(j->ctx, j->st);
     }
@@ -4056,6 +4062,277 @@ int osmt_label_positions_stats(osmt_ctx* ctx, uint64_t stats[3]) {
         for (int i = 0; i < 3; ++i) stats[i] = ctx->pl_stats[i];
         return (int)OSMT_OK;
     });
+}
+
+/* ---- label anchors from tile coordinates (include/osmtile.h, csrc/osmt_anchors.hip) ------------------------------------ */
+static int validate_node_mercator(const double* f, size_t n, uint32_t geodata_id, osmt_ctx* ctx) {
+    if (n && !f) return fail(OSMT_INVALID_ARG, "node mercator: factors are NULL with n_nodes = %zu", n);
+    for (size_t i = 0; i < 2 * n; ++i)
+        if (!(f[i] >= 0.0) || !(f[i] <= 1.0)) /* a NaN fails both */
+            return fail(OSMT_INVALID_ARG, "node mercator: node %zu: %s factor %g is not finite or outside [0, 1]", i / 2, i % 2 ? "y" : "x", f[i]);
+    if (!ctx) return fail(OSMT_INVALID_ARG, "node mercator: geodata id %u is not registered (no context)", geodata_id);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (geodata_id >= ctx->geodata.size())
+        return fail(OSMT_INVALID_ARG, "node mercator: geodata id %u is not registered (%zu files)", geodata_id, ctx->geodata.size());
+    const osmt_ctx::geodata_host& g = ctx->geodata[geodata_id];
+    if (n != g.n_nodes) return fail(OSMT_INVALID_ARG, "node mercator: n_nodes = %zu, the geodata has %zu nodes", n, g.n_nodes);
+    if (g.d_factors) return fail(OSMT_INVALID_ARG, "node mercator: geodata id %u has its factors already (one table per file)", geodata_id);
+    return OSMT_OK;
+}
+
+static int register_node_mercator_body(osmt_ctx* ctx, uint32_t geodata_id, const double* f) {
+    if (!ctx) return fail(OSMT_INVALID_ARG, "NULL argument");
+    size_t n = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (geodata_id >= ctx->geodata.size())
+            return fail(OSMT_INVALID_ARG, "node mercator: geodata id %u is not registered (%zu files)", geodata_id, ctx->geodata.size());
+        n = ctx->geodata[geodata_id].n_nodes; /* the table's length is the file's: there is no count to get wrong */
+    }
+    const int rc = validate_node_mercator(f, n, geodata_id, ctx);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    void* pool = nullptr;
+    HIP_TRY(hipMalloc(&pool, std::max<size_t>(n * 16, 16)));
+    if (n) {
+        const hipError_t e = hipMemcpy(pool, f, n * 16, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(pool);
+            return fail(OSMT_HIP_ERROR, "node mercator upload failed: %s", hipGetErrorString(e));
+        }
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    osmt_ctx::geodata_host& g = ctx->geodata[geodata_id];
+    if (g.d_factors) { /* another thread was first */
+        (void)hipFree(pool);
+        return fail(OSMT_INVALID_ARG, "node mercator: geodata id %u has its factors already (one table per file)", geodata_id);
+    }
+    g.d_factors = (const double2*)pool;
+    return OSMT_OK;
+}
+
+/* geo (optional): the registered file's tables as they are at the time of the call */
+static int validate_label_tile_batch(const osmt_label_tile_batch* b, osmt_ctx* ctx, osmt_ctx::geodata_host* geo) {
+    if (!b) return fail(OSMT_INVALID_ARG, "label tile batch is NULL");
+    if ((b->n_requests && !b->requests) || (b->n_tiles && !b->tiles)) return fail(OSMT_INVALID_ARG, "label tile batch: NULL pool with non-zero count");
+    if (b->n_requests >= 0xFFFFFFFFull || b->n_tiles >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "label tile batch too large for 32-bit indices");
+    if (b->scale < 1u || b->scale > OSMT_MAX_SCALE) return fail(OSMT_INVALID_ARG, "label tile batch: scale %u outside 1..%u", b->scale, OSMT_MAX_SCALE);
+    for (size_t t = 0; t < b->n_tiles; ++t) {
+        const osmt_query_tile& q = b->tiles[t];
+        if (q.zoom > OSMT_MAX_ZOOM) return fail(OSMT_INVALID_ARG, "label tile batch: tile %zu: zoom %u > %u", t, q.zoom, OSMT_MAX_ZOOM);
+        if (q.x >= (1u << q.zoom) || q.y >= (1u << q.zoom))
+            return fail(OSMT_INVALID_ARG, "label tile batch: tile %zu: (x, y) = (%u, %u) outside zoom %u", t, q.x, q.y, q.zoom);
+    }
+    for (size_t i = 0; i < b->n_requests; ++i)
+        if (b->requests[i].tile >= b->n_tiles)
+            return fail(OSMT_INVALID_ARG, "label tile request %zu: tile %u is not a tile of the batch (%zu tiles)", i, b->requests[i].tile, b->n_tiles);
+    if (!ctx) return fail(OSMT_INVALID_ARG, "label tile batch: geodata id %u is not registered (no context)", b->geodata_id);
+    osmt_ctx::geodata_host g;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (b->geodata_id >= ctx->geodata.size())
+            return fail(OSMT_INVALID_ARG, "label tile batch: geodata id %u is not registered (%zu files)", b->geodata_id, ctx->geodata.size());
+        g = ctx->geodata[b->geodata_id];
+    }
+    if (!g.d_factors)
+        return fail(OSMT_INVALID_ARG, "label tile batch: geodata id %u has no Mercator factors (osmt_register_node_mercator)", b->geodata_id);
+    for (size_t i = 0; i < b->n_requests; ++i) {
+        const uint32_t e = b->requests[i].entity, id = e & ~OSMT_STYLED_MULTIPOLYGON;
+        if (e & OSMT_STYLED_MULTIPOLYGON) {
+            if (id >= g.n_mps) return fail(OSMT_INVALID_ARG, "label tile request %zu: multipolygon %u out of range (%zu multipolygons)", i, id, g.n_mps);
+        } else if (id >= g.n_ways) {
+            return fail(OSMT_INVALID_ARG, "label tile request %zu: way %u out of range (%zu ways)", i, id, g.n_ways);
+        }
+    }
+    if (geo) *geo = g;
+    return OSMT_OK;
+}
+
+/* The projection of a validated batch with requests, on j->st: count and scans, the wait for the totals (they decide the
+ * refusals and size everything else), then rings, records and points.  The second allocation gets extra_of(rings) bytes
+ * behind the arrays of the projection — the caller's arrays, starting at j->d_base + *extra_off.  sizes_only: the totals
+ * and nothing after them. */
+static int label_tiles_expand(osmt_ctx* ctx, const osmt_label_tile_batch* b, const osmt_ctx::geodata_host& geo, osmt_label_job* j, bool sizes_only,
+                              const std::function<size_t(size_t)>& extra_of, size_t* extra_off, osmt_an_pass* out_pass) {
+    const size_t n = b->n_requests;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_req = take(n * sizeof(osmt_label_tile_request)), o_tiles = take(b->n_tiles * sizeof(osmt_query_tile)), o_rpos = take((n + 1) * 4),
+                 o_ppos = take((n + 1) * 4), o_blk = take(((n + 255) / 256 + 1) * 8), o_tot = take(OSMT_AN_N * 8);
+    HIP_TRY(dev_alloc(ctx, (void**)&j->d_front, off));
+    char* d = j->d_front;
+    HIP_TRY(hipMemcpyAsync(d + o_req, b->requests, n * sizeof(osmt_label_tile_request), hipMemcpyHostToDevice, j->st));
+    HIP_TRY(hipMemcpyAsync(d + o_tiles, b->tiles, b->n_tiles * sizeof(osmt_query_tile), hipMemcpyHostToDevice, j->st));
+    osmt_an_pass a{};
+    a.geo = geo.dev;
+    a.factors = geo.d_factors;
+    a.req = (const osmt_label_tile_request*)(d + o_req);
+    a.tiles = (const osmt_query_tile*)(d + o_tiles);
+    a.n_req = (uint32_t)n;
+    a.scale = b->scale;
+    a.rpos = (uint32_t*)(d + o_rpos);
+    a.ppos = (uint32_t*)(d + o_ppos);
+    a.blk = (unsigned long long*)(d + o_blk);
+    a.tot = (unsigned long long*)(d + o_tot);
+    HIP_TRY(osmt_launch_an_count(a, j->st));
+    HIP_TRY(hipMemcpyAsync(j->stage, a.tot, 3 * 8, hipMemcpyDeviceToHost, j->st)); /* the front of the job's pinned buffer */
+    HIP_TRY(hipStreamSynchronize(j->st));
+    unsigned long long tot[3];
+    memcpy(tot, j->stage, sizeof tot);
+    const unsigned long long n_rings = tot[OSMT_AN_RINGS], n_pts = tot[OSMT_AN_POINTS] + tot[OSMT_AN_HIGH];
+    if (n_rings >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "label tile batch: %llu rings do not fit 32-bit indices", n_rings);
+    if (n_pts >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "label tile batch: %llu points do not fit 32-bit indices", n_pts);
+    a.n_rings = (uint32_t)n_rings;
+    a.n_pts = (uint32_t)n_pts;
+    *out_pass = a;
+    if (sizes_only) return OSMT_OK;
+    off = 0;
+    const size_t o_base = take((n_rings + 1) * 4), o_src = take(n_rings * 4), o_rreq = take(n_rings * 4), o_blk2 = take(((n_rings + 255) / 256 + 1) * 8),
+                 o_pl = take(n * sizeof(osmt_pl_req)), o_rings = take(n_rings * sizeof(osmt_ring)), o_pts = take(n_pts * 16);
+    *extra_off = off;
+    HIP_TRY(dev_alloc(ctx, (void**)&j->d_base, off + extra_of((size_t)n_rings)));
+    d = j->d_base;
+    a.ring_base = (uint32_t*)(d + o_base);
+    a.ring_src = (uint32_t*)(d + o_src);
+    a.ring_req = (uint32_t*)(d + o_rreq);
+    a.blk = (unsigned long long*)(d + o_blk2);
+    a.pl_req = (osmt_pl_req*)(d + o_pl);
+    a.rings = (osmt_ring*)(d + o_rings);
+    a.pts = (double2*)(d + o_pts);
+    HIP_TRY(osmt_launch_an_expand(a, j->st));
+    *out_pass = a;
+    return OSMT_OK;
+}
+
+static int osmt_label_positions_tiles_begin_body(osmt_ctx* ctx, const osmt_label_tile_batch* b, osmt_label_job** out_job) {
+    if (!ctx || !b || !out_job) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *out_job = nullptr;
+    osmt_ctx::geodata_host geo;
+    const int rc = validate_label_tile_batch(b, ctx, &geo);
+    if (rc != OSMT_OK) return rc;
+    osmt_label_job* j = new osmt_label_job();
+    j->ctx = ctx;
+    j->n = b->n_requests;
+    if (!j->n) { /* no device is touched */
+        *out_job = j;
+        return OSMT_OK;
+    }
+    struct guard {
+        osmt_label_job* j;
+        ~guard() { label_job_free(j); }
+    } gd{j};
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(stream_acquire(ctx, &j->st));
+    const size_t n = j->n;
+    const size_t back_bytes = n * sizeof(osmt_label_position) + 16;
+    j->back_off = 64; /* the totals come back in front of the positions */
+    j->stage = (char*)stage_acquire(ctx, j->back_off + back_bytes);
+    if (!j->stage) return fail(OSMT_OOM, "pinned staging for %zu label requests could not be allocated", n);
+    const uint32_t n_slots = (uint32_t)std::min<size_t>(n, OSMT_PL_MAX_SLOTS);
+    /* the work areas of the search, behind the arrays of the projection */
+    size_t o_keep = 0, o_over = 0, o_back = 0, o_ws = 0;
+    auto search_bytes = [&](size_t n_rings) {
+        size_t off = 0;
+        auto take = [&](size_t bytes) {
+            const size_t o = off;
+            off = align_up(off + std::max<size_t>(bytes, 4), 256);
+            return o;
+        };
+        o_keep = take(n_rings * 4), o_over = take(n * 4), o_back = take(back_bytes);
+        o_ws = take((size_t)n_slots * OSMT_PL_CELL_DOUBLES * OSMT_PL_GLOBAL_CELLS * sizeof(double));
+        return off;
+    };
+    osmt_an_pass p{};
+    size_t x0 = 0;
+    const int erc = label_tiles_expand(ctx, b, geo, j, false, search_bytes, &x0, &p);
+    if (erc != OSMT_OK) return erc;
+    char* d = j->d_base + x0;
+    osmt_polylabel_args a{};
+    a.req = p.pl_req;
+    a.n_req = (uint32_t)n;
+    a.rings = p.rings;
+    a.n_rings = p.n_rings;
+    a.pts = p.pts;
+    a.keep = (uint32_t*)(d + o_keep);
+    a.over = (uint32_t*)(d + o_over);
+    a.out = (osmt_label_position*)(d + o_back);
+    a.cnt = (uint32_t*)(d + o_back + n * sizeof(osmt_label_position));
+    a.ws = (double*)(d + o_ws);
+    a.n_slots = n_slots;
+    HIP_TRY(osmt_launch_polylabel(a, j->st));
+    HIP_TRY(hipMemcpyAsync(j->stage + j->back_off, d + o_back, back_bytes, hipMemcpyDeviceToHost, j->st));
+    gd.j = nullptr;
+    *out_job = j;
+    return OSMT_OK;
+}
+
+static int osmt_label_tile_batch_expand_body(osmt_ctx* ctx, const osmt_label_tile_batch* b, osmt_ring* rings, double* points, size_t rings_cap,
+                                             size_t points_cap, size_t counts[2]) {
+    if (!ctx || !b || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
+    osmt_ctx::geodata_host geo;
+    const int rc = validate_label_tile_batch(b, ctx, &geo);
+    if (rc != OSMT_OK) return rc;
+    counts[0] = counts[1] = 0;
+    if (!b->n_requests) return OSMT_OK;
+    osmt_label_job* j = new osmt_label_job();
+    j->ctx = ctx;
+    j->n = b->n_requests;
+    struct guard {
+        osmt_label_job* j;
+        ~guard() { label_job_free(j); }
+    } gd{j};
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(stream_acquire(ctx, &j->st));
+    j->stage = (char*)stage_acquire(ctx, 64);
+    if (!j->stage) return fail(OSMT_OOM, "pinned staging for the totals could not be allocated");
+    const bool sizes_only = !rings && !points;
+    osmt_an_pass p{};
+    size_t x0 = 0;
+    const int erc = label_tiles_expand(ctx, b, geo, j, sizes_only, [](size_t) { return (size_t)0; }, &x0, &p);
+    if (erc != OSMT_OK) return erc;
+    counts[0] = p.n_rings, counts[1] = p.n_pts;
+    if (sizes_only) return OSMT_OK;
+    int out_rc = OSMT_OK;
+    if ((rings && rings_cap < p.n_rings) || (points && points_cap < p.n_pts))
+        out_rc = fail(OSMT_INVALID_ARG, "label tile batch: %u rings and %u points, the capacities are %zu and %zu", p.n_rings, p.n_pts, rings_cap, points_cap);
+    if (out_rc == OSMT_OK && rings && p.n_rings) HIP_TRY(hipMemcpyAsync(rings, p.rings, (size_t)p.n_rings * sizeof(osmt_ring), hipMemcpyDeviceToHost, j->st));
+    if (out_rc == OSMT_OK && points && p.n_pts) HIP_TRY(hipMemcpyAsync(points, p.pts, (size_t)p.n_pts * 16, hipMemcpyDeviceToHost, j->st));
+    HIP_TRY(hipStreamSynchronize(j->st)); /* also on a refusal: the job's buffers go back to the pool behind the kernels */
+    return out_rc;
+}
+
+int osmt_validate_node_mercator(const double* factors, size_t n_nodes, uint32_t geodata_id, osmt_ctx* ctx) {
+    return guarded([&] { return validate_node_mercator(factors, n_nodes, geodata_id, ctx); });
+}
+
+int osmt_register_node_mercator(osmt_ctx* ctx, uint32_t geodata_id, const double* factors) {
+    return guarded([&] { return register_node_mercator_body(ctx, geodata_id, factors); });
+}
+
+int osmt_validate_label_tile_batch(const osmt_label_tile_batch* b, osmt_ctx* ctx) {
+    return guarded([&] { return validate_label_tile_batch(b, ctx, nullptr); });
+}
+
+int osmt_label_positions_tiles_begin(osmt_ctx* ctx, const osmt_label_tile_batch* b, osmt_label_job** out_job) {
+    return guarded([&] { return osmt_label_positions_tiles_begin_body(ctx, b, out_job); });
+}
+
+int osmt_label_positions_tiles(osmt_ctx* ctx, const osmt_label_tile_batch* b, osmt_label_position* out) {
+    return guarded([&] {
+        if (b && b->n_requests && !out) return fail(OSMT_INVALID_ARG, "out is NULL");
+        osmt_label_job* j = nullptr;
+        const int rc = osmt_label_positions_tiles_begin_body(ctx, b, &j);
+        return rc != OSMT_OK ? rc : osmt_label_positions_end_body(j, out);
+    });
+}
+
+int osmt_label_tile_batch_expand(osmt_ctx* ctx, const osmt_label_tile_batch* b, osmt_ring* rings, double* points, size_t rings_cap, size_t points_cap,
+                                 size_t counts[2]) {
+    return guarded([&] { return osmt_label_tile_batch_expand_body(ctx, b, rings, points, rings_cap, points_cap, counts); });
 }
 
 static int osmt_scene_read_label_status_body(osmt_ctx* ctx, osmt_scene* sc, uint8_t* ok) {

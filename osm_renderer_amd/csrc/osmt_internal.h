@@ -587,6 +587,39 @@ hipError_t osmt_launch_tl_order(const osmt_tl_pass& a, hipStream_t st);
 /* k_tl_emit + k_tl_chars: the records and the char pool */
 hipError_t osmt_launch_tl_emit(const osmt_tl_pass& a, hipStream_t st);
 
+/* ---- label anchors from tile coordinates (osmt_anchors.hip) ----------------------------------------------------- */
+/* words of osmt_an_pass::tot; the points of the batch are tot[POINTS] + tot[HIGH] */
+enum {
+    OSMT_AN_RINGS = 0,   /* rings of the batch */
+    OSMT_AN_POINTS,      /* the sum of the requests' point counts, each taken mod 2^32 */
+    OSMT_AN_HIGH,        /* what the requests' point counts hold above 32 bits */
+    OSMT_AN_RING_POINTS, /* the total of the per-ring scan (= the points again; not read back) */
+    OSMT_AN_N
+};
+struct osmt_an_pass {
+    osmt_geo_dev geo;
+    const double2* factors;             /* [n_nodes] the registered Mercator factors */
+    const osmt_label_tile_request* req; /* [n_req] */
+    const osmt_query_tile* tiles;
+    uint32_t n_req, n_rings, n_pts; /* the last two: totals, known once they have been read back */
+    uint32_t scale;
+    uint32_t* rpos;          /* [n_req + 1] rings of the request, then their exclusive scan */
+    uint32_t* ppos;          /* [n_req + 1] points of the request (mod 2^32), then their exclusive scan */
+    unsigned long long* blk; /* block totals of the scan under way: one word per 256 elements, at least one */
+    unsigned long long* tot; /* [OSMT_AN_N] */
+    uint32_t* ring_base;     /* [n_rings + 1] points of the ring, then their exclusive scan: the ring's first point */
+    uint32_t* ring_src;      /* [n_rings] where in geo.idx the ring's nodes start */
+    uint32_t* ring_req;      /* [n_rings] its request */
+    /* what osmt_launch_polylabel takes */
+    osmt_pl_req* pl_req; /* [n_req] */
+    osmt_ring* rings;    /* [n_rings] */
+    double2* pts;        /* [n_pts] */
+};
+/* zeroes tot, then k_an_count + two scans: everything up to the totals */
+hipError_t osmt_launch_an_count(const osmt_an_pass& a, hipStream_t st);
+/* k_an_rings + scan + k_an_records + k_an_points: pl_req, rings and pts */
+hipError_t osmt_launch_an_expand(const osmt_an_pass& a, hipStream_t st);
+
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

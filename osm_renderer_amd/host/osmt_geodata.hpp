@@ -25,6 +25,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -345,6 +346,22 @@ struct GeodataDesc {
     GeodataDesc(const GeodataDesc&) = delete;
     GeodataDesc& operator=(const GeodataDesc&) = delete;
 };
+
+/* The table osmt_register_node_mercator takes: per node of latlon[n][2] = (lat, lon) in degrees the part of coords_to_xy
+ * (tile.rs:88-95) that depends on the node alone, in the reference's operation order, with THIS machine's tan and log:
+ * ((lon_rad + PI) / (2 PI), (PI - ln(tan(PI / 4 + lat_rad / 2))) / (2 PI)).  Compile with -ffp-contract=off. */
+inline std::vector<double> mercator_factors(const double* latlon, size_t n) {
+    constexpr double PI = 3.14159265358979323846264338327950288; /* std::f64::consts::PI */
+    std::vector<double> f(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const double lat_rad = latlon[2 * i] * (PI / 180.0), lon_rad = latlon[2 * i + 1] * (PI / 180.0); /* f64::to_radians */
+        const double x = lon_rad + PI;
+        const double y = PI - std::log(std::tan((PI / 4.0) + (lat_rad / 2.0)));
+        f[2 * i] = x / (2.0 * PI);
+        f[2 * i + 1] = y / (2.0 * PI);
+    }
+    return f;
+}
 
 }  // namespace osmt
 #endif

@@ -340,5 +340,108 @@ class LabelPositions {
     size_t fallbacks_ = 0;
 };
 
+/* ---- anchors from tile coordinates (osmt_label_positions_tiles) ----------------------------------------------------- */
+/* coords_to_xy_tile_relative(node, tile) * scale from the node's registered Mercator factors f[2] (osmt::mercator_factors,
+ * host/osmt_geodata.hpp): what is left of tile.rs:94-106 and labelable.rs:64-65 once the libm step is in the factor — a
+ * multiplication by a power of two, a subtraction, a multiplication, each a statement of its own (-ffp-contract=off).  The
+ * tile offset is formed in u32 as the reference's `tile.x * TILE_SIZE`.  csrc/osmt_anchors.hip runs the same three operations. */
+inline std::array<double, 2> project_factors(const double* f, const osmt_query_tile& tile, uint32_t scale) {
+    const double dim = (double)(OSMT_TILE_SIZE * (1u << tile.zoom));
+    const double s = (double)scale;
+    const double off_x = (double)(uint32_t)(tile.x * OSMT_TILE_SIZE), off_y = (double)(uint32_t)(tile.y * OSMT_TILE_SIZE);
+    double x = f[0] * dim, y = f[1] * dim;
+    x = x - off_x;
+    y = y - off_y;
+    x = x * s;
+    y = y * s;
+    return {x, y};
+}
+
+/* The polygons get_label_position is given for `entity` (a way's local id, or a multipolygon's | OSMT_STYLED_MULTIPOLYGON)
+ * under `tile`: a way is one ring of its nodes, a multipolygon ALL its polygons in file order, the empty and the one-node
+ * ones included (labelable.rs:26-59).  factors: [n_nodes][2].  Throws std::out_of_range for an id the geodata does not have. */
+inline std::vector<LabelRing> label_rings_of(const osmt_geodata_desc& g, const double* factors, uint32_t entity, const osmt_query_tile& tile,
+                                             uint32_t scale) {
+    const uint32_t id = entity & ~OSMT_STYLED_MULTIPOLYGON;
+    auto ring_of = [&](const uint32_t* nodes, uint32_t n) {
+        LabelRing r(n);
+        for (uint32_t i = 0; i < n; ++i) r[i] = project_factors(factors + 2 * (size_t)nodes[i], tile, scale);
+        return r;
+    };
+    std::vector<LabelRing> rings;
+    if (entity & OSMT_STYLED_MULTIPOLYGON) {
+        if (id >= g.n_multipolygons) throw std::out_of_range("label_rings_of: multipolygon id out of range");
+        for (uint32_t k = g.multipolygon_polygon_off[id]; k < g.multipolygon_polygon_off[id + 1]; ++k) {
+            const uint32_t p = g.multipolygon_polygons[k];
+            rings.push_back(ring_of(g.polygon_nodes + g.polygon_node_off[p], g.polygon_node_off[p + 1] - g.polygon_node_off[p]));
+        }
+    } else {
+        if (id >= g.n_ways) throw std::out_of_range("label_rings_of: way id out of range");
+        rings.push_back(ring_of(g.way_nodes + g.way_node_off[id], g.way_node_off[id + 1] - g.way_node_off[id]));
+    }
+    return rings;
+}
+
+/* The twin of LabelPositions for callers that registered a geodata file and its Mercator factors: a request is an entity
+ * and a tile (8 bytes go to the device), run() answers all of them through osmt_label_positions_tiles and computes on this
+ * thread, from the same factors, the requests the device declines as too large.  `geodata` and `factors` are the arrays that
+ * were registered under `geodata_id`; they must outlive this object. */
+class TileLabelPositions {
+   public:
+    TileLabelPositions(const osmt_geodata_desc& geodata, const double* factors, uint32_t geodata_id, uint32_t scale)
+        : g_(geodata), f_(factors), id_(geodata_id), scale_(scale) {}
+    /* returns the tile's index for add() */
+    uint32_t add_tile(uint8_t zoom, uint32_t x, uint32_t y) {
+        osmt_query_tile t{};
+        t.x = x, t.y = y, t.zoom = zoom;
+        tiles_.push_back(t);
+        return (uint32_t)(tiles_.size() - 1);
+    }
+    /* returns the request's index into run()'s result */
+    size_t add_way(uint32_t way, uint32_t tile) { return add(way, tile); }
+    size_t add_multipolygon(uint32_t mp, uint32_t tile) { return add(mp | OSMT_STYLED_MULTIPOLYGON, tile); }
+    size_t size() const { return reqs_.size(); }
+    size_t cpu_fallbacks() const { return fallbacks_; } /* requests of the last run() computed on the host */
+    void clear() {
+        tiles_.clear();
+        reqs_.clear();
+    }
+    /* status is OSMT_LABEL_OK or OSMT_LABEL_NONE for every request; throws std::runtime_error on an ABI error */
+    std::vector<osmt_label_position> run(osmt_ctx* ctx) {
+        std::vector<osmt_label_position> out(reqs_.size());
+        osmt_label_tile_batch b{};
+        b.requests = reqs_.data();
+        b.n_requests = reqs_.size();
+        b.tiles = tiles_.data();
+        b.n_tiles = tiles_.size();
+        b.geodata_id = id_;
+        b.scale = scale_;
+        const int rc = osmt_label_positions_tiles(ctx, &b, out.data());
+        if (rc != OSMT_OK) throw std::runtime_error(std::string("osmt_label_positions_tiles: ") + osmt_last_error());
+        fallbacks_ = 0;
+        for (size_t i = 0; i < out.size(); ++i) {
+            if (out[i].status != OSMT_LABEL_TOO_LARGE) continue;
+            const LabelPosition r = get_label_position(label_rings_of(g_, f_, reqs_[i].entity, tiles_[reqs_[i].tile], scale_), (double)scale_);
+            out[i].x = r.x;
+            out[i].y = r.y;
+            out[i].status = r.status;
+            ++fallbacks_;
+        }
+        return out;
+    }
+
+   private:
+    size_t add(uint32_t entity, uint32_t tile) {
+        reqs_.push_back(osmt_label_tile_request{entity, tile});
+        return reqs_.size() - 1;
+    }
+    const osmt_geodata_desc& g_;
+    const double* f_;
+    uint32_t id_, scale_;
+    std::vector<osmt_query_tile> tiles_;
+    std::vector<osmt_label_tile_request> reqs_;
+    size_t fallbacks_ = 0;
+};
+
 }  // namespace osmt
 #endif

@@ -36,7 +36,9 @@ assert LABEL_DTYPE.itemsize == 40
 # osmt_label_request / osmt_label_position (label anchors, Context.label_positions)
 LABEL_REQUEST_DTYPE = np.dtype([("ring_off", "<u4"), ("n_rings", "<u4"), ("scale", "<f8")])
 LABEL_POSITION_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("status", "<u4"), ("_pad", "<u4")])
+LABEL_TILE_REQUEST_DTYPE = np.dtype([("entity", "<u4"), ("tile", "<u4")])  # osmt_label_tile_request (Context.label_positions_tiles)
 assert LABEL_REQUEST_DTYPE.itemsize == C.sizeof(abi.LabelRequest) == 16
+assert LABEL_TILE_REQUEST_DTYPE.itemsize == C.sizeof(abi.LabelTileRequest) == 8
 assert LABEL_POSITION_DTYPE.itemsize == C.sizeof(abi.LabelPosition) == 24
 
 _libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")

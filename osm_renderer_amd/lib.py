@@ -41,6 +41,8 @@ EXPORTS = [
     "osmt_validate_tile_batch", "osmt_scene_build_tiles", "osmt_scene_read_styled_areas",
     "osmt_validate_node_index", "osmt_register_node_index", "osmt_validate_label_styles", "osmt_register_label_styles",
     "osmt_validate_label_bindings", "osmt_register_label_bindings", "osmt_scene_build_tile_labels", "osmt_scene_read_tile_labels",
+    "osmt_validate_node_mercator", "osmt_register_node_mercator", "osmt_validate_label_tile_batch", "osmt_label_positions_tiles",
+    "osmt_label_positions_tiles_begin", "osmt_label_tile_batch_expand",
 ]
 
 
@@ -167,6 +169,13 @@ def load():
         L.osmt_register_label_bindings.argtypes = [vp, C.POINTER(abi.LabelBindingsDesc), C.POINTER(C.c_uint32)]
         L.osmt_scene_build_tile_labels.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(abi.StringLabelBatch)]
         L.osmt_scene_read_tile_labels.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    if hasattr(L, "osmt_label_positions_tiles"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_validate_node_mercator.argtypes = [dp, C.c_size_t, C.c_uint32, vp]
+        L.osmt_register_node_mercator.argtypes = [vp, C.c_uint32, dp]
+        L.osmt_validate_label_tile_batch.argtypes = [C.POINTER(abi.LabelTileBatch), vp]
+        L.osmt_label_positions_tiles.argtypes = [vp, C.POINTER(abi.LabelTileBatch), vp]
+        L.osmt_label_positions_tiles_begin.argtypes = [vp, C.POINTER(abi.LabelTileBatch), C.POINTER(vp)]
+        L.osmt_label_tile_batch_expand.argtypes = [vp, C.POINTER(abi.LabelTileBatch), vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

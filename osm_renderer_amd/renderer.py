@@ -500,6 +500,73 @@ class Context:
         check(load().osmt_label_positions_stats(self._h, st))
         return int(st[0]), int(st[1]), int(st[2])
 
+    # -- label anchors from tile coordinates ------------------------------------------
+    def register_node_mercator(self, geodata_id, factors):
+        """osmt_register_node_mercator: uploads the [n_nodes, 2] float64 Mercator factors of a registered geodata file (one
+        table per file) — (lon_rad + PI) / (2 PI) and (PI - ln(tan(PI / 4 + lat_rad / 2))) / (2 PI) per node, computed by the
+        caller with its own libm."""
+        f = np.ascontiguousarray(factors, dtype=np.float64).reshape(-1, 2)
+        # the C entry takes no count (the table's length is the file's): the validator is what compares the two
+        check(load().osmt_validate_node_mercator(f.ctypes.data_as(C.POINTER(C.c_double)) if len(f) else None, len(f), geodata_id, self._h))
+        check(load().osmt_register_node_mercator(self._h, geodata_id, f.ctypes.data_as(C.POINTER(C.c_double)) if len(f) else None))
+
+    def _label_tile_batch(self, geodata_id, tiles, requests, scale):
+        from . import labels, styled
+
+        if not (isinstance(tiles, np.ndarray) and tiles.dtype == styled.QUERY_TILE_DTYPE):
+            t = np.zeros(len(tiles), styled.QUERY_TILE_DTYPE)
+            for rec, (zoom, x, y) in zip(t, tiles):
+                rec["zoom"], rec["x"], rec["y"] = zoom, x, y
+            tiles = t
+        tiles = np.ascontiguousarray(tiles)
+        if not (isinstance(requests, np.ndarray) and requests.dtype == labels.LABEL_TILE_REQUEST_DTYPE):
+            requests = np.array([(int(e), int(t)) for e, t in requests], dtype=labels.LABEL_TILE_REQUEST_DTYPE).reshape(-1)
+        requests = np.ascontiguousarray(requests)
+        b = abi.LabelTileBatch(
+            requests=requests.ctypes.data_as(C.POINTER(abi.LabelTileRequest)) if len(requests) else None, n_requests=len(requests),
+            tiles=tiles.ctypes.data_as(C.POINTER(abi.QueryTile)) if len(tiles) else None, n_tiles=len(tiles),
+            geodata_id=int(geodata_id), scale=int(scale))
+        return b, (tiles, requests)
+
+    def validate_label_tiles(self, geodata_id, tiles, requests, scale=1):
+        """osmt_validate_label_tile_batch against this context's registrations (host only); raises OsmtError."""
+        b, _keep = self._label_tile_batch(geodata_id, tiles, requests, scale)
+        check(load().osmt_validate_label_tile_batch(C.byref(b), self._h))
+
+    def label_positions_tiles(self, geodata_id, tiles, requests, scale=1, out=None):
+        """osmt_label_positions_tiles: get_label_position of every (entity, tile) request, projected on the GPU from the
+        registered Mercator factors.  tiles: [(zoom, x, y)] or a styled.QUERY_TILE_DTYPE array; requests: [(entity, tile
+        index)] (a multipolygon's entity carries abi.STYLED_MULTIPOLYGON) or a labels.LABEL_TILE_REQUEST_DTYPE array.
+        Returns a labels.LABEL_POSITION_DTYPE array."""
+        from . import labels
+
+        b, keep = self._label_tile_batch(geodata_id, tiles, requests, scale)
+        if out is None:
+            out = np.zeros(len(keep[1]), labels.LABEL_POSITION_DTYPE)
+        assert out.dtype == labels.LABEL_POSITION_DTYPE and len(out) == len(keep[1]) and out.flags.c_contiguous
+        check(load().osmt_label_positions_tiles(self._h, C.byref(b), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def label_positions_tiles_begin(self, geodata_id, tiles, requests, scale=1):
+        """osmt_label_positions_tiles_begin: returns a job for label_positions_end."""
+        b, keep = self._label_tile_batch(geodata_id, tiles, requests, scale)
+        job = C.c_void_p()
+        check(load().osmt_label_positions_tiles_begin(self._h, C.byref(b), C.byref(job)))
+        return job, (None, None, keep[1])
+
+    def label_tile_batch_expand(self, geodata_id, tiles, requests, scale=1):
+        """osmt_label_tile_batch_expand: (rings [n, 2] uint32 (first_pt, n_pts), points [m, 2] float64) — what the search of
+        this batch is given."""
+        b, _keep = self._label_tile_batch(geodata_id, tiles, requests, scale)
+        counts = (C.c_size_t * 2)()
+        check(load().osmt_label_tile_batch_expand(self._h, C.byref(b), None, None, 0, 0, counts))
+        rings = np.zeros((counts[0], 2), np.uint32)
+        points = np.zeros((counts[1], 2), np.float64)
+        check(load().osmt_label_tile_batch_expand(self._h, C.byref(b), rings.ctypes.data_as(C.c_void_p), points.ctypes.data_as(C.c_void_p),
+                                                  len(rings), len(points), counts))
+        assert (counts[0], counts[1]) == (len(rings), len(points))
+        return rings, points
+
     # -- whole path --------------------------------------------------------------
     def upload(self, dl: DisplayList, labels=None) -> Scene:
         return Scene(self, dl, labels)
