@@ -22,6 +22,7 @@
 #include "../../include/osmtile.h"
 #include "osmt_geom.h"
 #include "osmt_internal.h"
+#include "osmt_prebin_roles.h"
 #include "osmt_project.h"
 
 namespace {
@@ -1619,8 +1620,8 @@ struct StrokeBinSeg {
     uint32_t _pad;
 };
 struct StrokeBinShared {
-    uint32_t incl[64]; /* inclusive pair count over the block's segments */
-    StrokeBinSeg seg[64];
+    uint32_t incl[OSMT_BIN_SEGS]; /* inclusive pair count over the block's segments */
+    StrokeBinSeg seg[OSMT_BIN_SEGS];
 };
 
 __device__ __forceinline__ void stroke_bin_body(StrokeBinShared& sh, const uint32_t blk, const uint32_t lane,
@@ -1630,11 +1631,11 @@ __device__ __forceinline__ void stroke_bin_body(StrokeBinShared& sh, const uint3
                                                 uint32_t* __restrict__ g_cnt, const osmt_vseg* __restrict__ g_vseg) {
     /* ---- step A, lane = virtual segment: its op, end points, sub-tile window — everything k_opinfo left per segment
      * comes in with ONE level of loads, the op's record with a second ---- */
-    const uint32_t g = blk * 64u + lane;
+    const uint32_t g = blk * OSMT_BIN_SEGS + lane; /* lanes from OSMT_BIN_SEGS on bring no segment: a shorter chain of step-B rounds */
     const int32_t W = (int32_t)(OSMT_TILE_SIZE * scale);
     const int32_t n_sub_x = W / SUB, n_sub_y = (int32_t)sub_rows;
     uint32_t n_pairs = 0u;
-    if (g < n_vsegs) {
+    if (lane < OSMT_BIN_SEGS && g < n_vsegs) {
         const osmt_vseg vsr = g_vseg[g];
         const uint32_t vo = vsr.vop;
         const int4 pp = make_int4(vsr.p1x, vsr.p1y, vsr.p2x, vsr.p2y);
@@ -1668,7 +1669,7 @@ __device__ __forceinline__ void stroke_bin_body(StrokeBinShared& sh, const uint3
         }
     }
     const uint32_t incl = wave_incl_scan(n_pairs);
-    sh.incl[lane] = incl;
+    if (lane < OSMT_BIN_SEGS) sh.incl[lane] = incl;
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     __syncthreads();
     /* ---- step B, lane = (segment, sub-tile of its window): the ranges of perpendicular runs that can reach the
@@ -1678,7 +1679,7 @@ __device__ __forceinline__ void stroke_bin_body(StrokeBinShared& sh, const uint3
     for (uint32_t i = lane; i < total; i += 64u) {
         uint32_t v = 0u; /* first segment whose inclusive count exceeds i */
 #pragma unroll
-        for (uint32_t step = 32u; step; step >>= 1)
+        for (uint32_t step = OSMT_BIN_SEGS / 2u; step; step >>= 1)
             if (sh.incl[v + step - 1u] <= i) v += step;
         const StrokeBinSeg& sg = sh.seg[v];
         const uint32_t j = i - (v ? sh.incl[v - 1u] : 0u);
@@ -1707,13 +1708,14 @@ __device__ __forceinline__ void stroke_bin_body(StrokeBinShared& sh, const uint3
     }
 }
 
-/* Both binning jobs in ONE launch: blocks [0, n_vblk) bin 64 stroke segments each (latency-bound: a bisection, a chain
- * of dependent loads, scattered 72-byte stores), the rest build the coverage rows of FILL_GROUP ops each (issue-bound) —
- * the two kinds overlap on the machine instead of running back to back. */
+/* Both binning jobs in ONE launch: n_vblk blocks bin OSMT_BIN_SEGS stroke segments each (latency-bound: a bisection, a
+ * chain of dependent loads, scattered 72-byte stores), n_fgrp blocks build the coverage rows of FILL_GROUP ops each
+ * (issue-bound).  The dispatcher places blocks in index order, so the two kinds overlap on the machine only when they
+ * alternate in the grid: osmt_prebin_role spreads the stroke blocks evenly through it (osmt_prebin_roles.h). */
 __global__ __launch_bounds__(64) void k_prebin(const osmt_op* __restrict__ g_ops, uint32_t n_ops, const osmt_opinfo* __restrict__ g_info,
                                                const osmt_ring* __restrict__ g_rings, const int2* __restrict__ g_pts,
                                                const uint32_t* __restrict__ g_op_blk,
-                                               const osmt_blk_bbox* __restrict__ g_blk, uint32_t n_vsegs, uint32_t n_vblk,
+                                               const osmt_blk_bbox* __restrict__ g_blk, uint32_t n_vsegs, const osmt_prebin_map roles,
                                                uint32_t scale, uint32_t sub_rows, uint32_t* __restrict__ g_submask,
                                                uint32_t* __restrict__ g_fmask,
                                                osmt_srec* __restrict__ g_srec, uint2* __restrict__ g_skey, const uint32_t* __restrict__ g_op_job,
@@ -1722,18 +1724,19 @@ __global__ __launch_bounds__(64) void k_prebin(const osmt_op* __restrict__ g_ops
         FillShared fill;
         StrokeBinShared bin;
     } shu;
-    const uint32_t b = blockIdx.x;
+    uint32_t idx;
+    const bool stroke = osmt_prebin_role(roles, blockIdx.x, &idx) != 0u;
 #if defined(OSMT_ABL) && OSMT_ABL == 9
-    if (b < n_vblk) return; /* ablation: no stroke binning */
+    if (stroke) return; /* ablation: no stroke binning */
 #endif
 #if defined(OSMT_ABL) && OSMT_ABL == 10
-    if (b >= n_vblk) return; /* ablation: no fill rows */
+    if (!stroke) return; /* ablation: no fill rows */
 #endif
-    if (b < n_vblk)
-        stroke_bin_body(shu.bin, b, threadIdx.x, g_info, n_vsegs, scale, sub_rows, g_submask,
+    if (stroke)
+        stroke_bin_body(shu.bin, idx, threadIdx.x, g_info, n_vsegs, scale, sub_rows, g_submask,
                         g_srec, g_skey, g_op_job, g_cnt, g_vseg);
     else
-        fill_rows_body(shu.fill, b - n_vblk, threadIdx.x, g_ops, n_ops, g_info, g_rings, g_pts, g_op_blk, g_blk, scale, sub_rows, g_submask, g_fmask,
+        fill_rows_body(shu.fill, idx, threadIdx.x, g_ops, n_ops, g_info, g_rings, g_pts, g_op_blk, g_blk, scale, sub_rows, g_submask, g_fmask,
                        g_op_job, g_cnt);
 }
 
@@ -2822,10 +2825,10 @@ hipError_t osmt_launch_prepass(const osmt_prepass_args& a, hipStream_t st, bool 
         hipLaunchKernelGGL(k_opinfo, dim3((a.n_ops + OPINFO_THREADS * OPINFO_WAVES - 1u) / (OPINFO_THREADS * OPINFO_WAVES)),
                            dim3(OPINFO_THREADS * OPINFO_WAVES), 0, st, a);
     if (a.fmask_cap == 0 && a.srec_cap == 0) return hipGetLastError(); /* sizing pass */
-    const uint32_t n_vblk = (a.n_vsegs + 63u) / 64u;
+    const osmt_prebin_map roles = osmt_prebin_map_make(osmt_prebin_n_vblk(a.n_vsegs, OSMT_BIN_SEGS), (a.n_ops + FILL_GROUP - 1u) / FILL_GROUP);
     if (a.n_ops)
-        hipLaunchKernelGGL(k_prebin, dim3(n_vblk + (a.n_ops + FILL_GROUP - 1u) / FILL_GROUP), dim3(64), 0, st, a.ops, a.n_ops, a.info, a.rings, a.pts,
-                           a.op_blk, a.blk, a.n_vsegs, n_vblk,
+        hipLaunchKernelGGL(k_prebin, dim3(roles.n_vblk + roles.n_fgrp), dim3(64), 0, st, a.ops, a.n_ops, a.info, a.rings, a.pts,
+                           a.op_blk, a.blk, a.n_vsegs, roles,
                            a.scale, a.sub_rows, a.submask, a.fmask, a.srec, a.skey, a.op_job, a.cnt, a.vseg);
     /* lists only for tiles with more than OSMT_FOLD_MAX_OPS ops (k_raster's waves put the others' together themselves) */
     if (a.n_jobs && (a.fold_max_ops == 0u || a.max_job_ops > a.fold_max_ops))
