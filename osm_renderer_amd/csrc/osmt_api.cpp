@@ -1187,7 +1187,9 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
     const size_t W = (size_t)OSMT_TILE_SIZE * s->scale;
     const size_t nsub = (W / OSMT_SUB_W) * (W / OSMT_SUB_H);
     unsigned long long groups = (unsigned long long)n_fills * nsub, recs = (unsigned long long)s->n_vsegs * nsub;
-    const unsigned long long worst_bytes = groups * 64ull + recs * (sizeof(osmt_srec) + 8ull) + ((unsigned long long)n_fills + s->n_strokes) * nsub * sizeof(osmt_ent);
+    /* (the list arena at the size its layout gives it: twice the entries for batches whose arena is cut into slices, osmt_list_slices.h) */
+    const unsigned long long worst_bytes = groups * 64ull + recs * (sizeof(osmt_srec) + 8ull) +
+                                           osmt_list_layout_make(s->n_jobs, ((unsigned long long)n_fills + s->n_strokes) * nsub).total * sizeof(osmt_ent);
     /* (taking the worst case up to 2 GB instead — 1.8 GB for 1024 config-2 tiles — was tried to save this sizing run,
      * 0.14 ms of a 0.84 ms upload: no gain on one thread, and four worker threads' arenas then outgrow the buffer cache) */
     bool guessed = false;
@@ -1244,7 +1246,9 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
     const size_t o_f = carve((size_t)(groups + 1) * 64);
     const size_t o_r = carve((size_t)(recs + 1) * sizeof(osmt_srec));
     const size_t o_k = carve((size_t)(recs + 1) * 8);
-    const size_t o_e = carve((size_t)(ents + 1) * sizeof(osmt_ent));
+    /* batches of many tiles: the arena in slices with a cursor each and an overflow slice behind them (osmt_list_slices.h) */
+    const osmt_list_layout lay = osmt_list_layout_make(s->n_jobs, ents + 1);
+    const size_t o_e = carve((size_t)lay.total * sizeof(osmt_ent));
     hipError_t e = dev_alloc(ctx, (void**)&s->d_arena, off + 256);
     if (e != hipSuccess) {
         s->d_arena = nullptr;
@@ -1255,6 +1259,12 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
     s->d_skey = (uint2*)(s->d_arena + o_k);
     s->d_ent = (osmt_ent*)(s->d_arena + o_e);
     s->ent_cap = ents + 1;
+    /* OSMT_TRACE_UPLOAD=1 (diagnostic): what the arenas take, one line on stderr */
+    static const bool trace_arenas = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    if (trace_arenas)
+        fprintf(stderr, "osmt arenas: %u tiles, fill groups %llu, stroke records %llu, list entries %llu in %u slice(s) of %llu (+ overflow): "
+                        "list arena %.1f MB of %.1f MB%s\n", s->n_jobs, groups, recs, ents + 1, lay.n_slices, lay.slice_cap,
+                (double)lay.total * sizeof(osmt_ent) / 1e6, (double)off / 1e6, guessed ? " (guessed)" : "");
     s->fmask_cap = groups + 1; /* never 0: 0 means "sizing pass" to the kernels */
     s->srec_cap = recs + 1;
     return OSMT_OK;
@@ -1283,7 +1293,8 @@ static scene_back scene_carve_back(size_t& off, size_t n_jobs, size_t n_ops, siz
     k.o_blk = carve((n_blk + 1) * sizeof(osmt_blk_bbox));
     k.o_vseg = carve((n_vsegs + 1) * sizeof(osmt_vseg));
     const size_t n_sub = ((size_t)OSMT_TILE_SIZE * scale / OSMT_SUB_W) * sub_rows;
-    k.o_cursors = carve(32 + n_jobs * n_sub * 4); /* cursors + list counts: zeroed together every frame */
+    /* cursors + list counts + the cursors of the list arena's slices: zeroed together every frame */
+    k.o_cursors = carve((osmt_list_cursor_word0(n_jobs * n_sub) + OSMT_LIST_CURSOR_WORDS) * 4);
     k.o_hdr = carve(n_jobs * n_sub * sizeof(uint2));
     return k;
 }

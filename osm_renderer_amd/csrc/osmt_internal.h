@@ -7,6 +7,7 @@
 
 #include "../../include/osmtile.h"
 #include "osmt_glyph.h"
+#include "osmt_list_slices.h"
 
 /* Sub-tile geometry of k_raster: OSMT_SUB_W x OSMT_SUB_H pixels per workgroup.  Sub-tile
  * coverage masks (osmt_raster_args.submask) have one 32-bit word per sub-tile ROW. */
@@ -312,10 +313,11 @@ struct osmt_prepass_args {
      * osmt_op -> ring -> points; rounds 4-5 kept six arrays: six scattered partial-line stores per edge) */
     osmt_vseg* vseg;
     unsigned long long* cursors; /* [0] fill arena (64-byte groups), [1] stroke arena (records), [2] list entries; zeroed by the launcher */
-    uint32_t* cnt;      /* [n_jobs][nsub], right behind the cursors (zeroed with them): ops that draw into the sub-tile */
+    uint32_t* cnt;      /* [n_jobs][nsub], right behind the cursors (zeroed with them): ops that draw into the sub-tile; behind the
+                         * counts, zeroed with them, the cursors of the list arena's slices (osmt_list_slices.h) */
     uint2* hdr;         /* [n_jobs][nsub]: k_sublist's (first entry, count) */
-    osmt_ent* ent;      /* list arena */
-    unsigned long long ent_cap;
+    osmt_ent* ent;      /* list arena: osmt_list_layout_make(n_jobs, ent_cap).total entries */
+    unsigned long long ent_cap; /* list entries the binning can produce */
     uint32_t* fmask;
     osmt_srec* srec;
     uint2* skey;

@@ -587,13 +587,16 @@ constexpr uint32_t FILTCAP = OSMT_V_FILTCAP; /* slots of a group's stroke entrie
 #endif
 constexpr int DTAB_F = 7; /* start_from, start_to, end_from, end_to, opacity_mul, r_start, r_end */
 struct RasterShared {
-    OSMT_DBG(uint32_t dbg[8];) /* diagnostic build: [0] stroke visits [1] passes [2] items [3] filter passes of groups [4] groups ended by the
-                                * 33rd kept record [5] fill visits [6] ops with more than SEGCAP records in the sub-tile [7] ops with more than FILTCAP slots */
+    OSMT_DBG(uint32_t dbg[12];) /* diagnostic build: [0] stroke visits [1] passes [2] items [3] filter passes of groups [4] groups ended by the
+                                 * 33rd kept record [5] fill visits [6] ops with more than SEGCAP records in the sub-tile [7] ops with more than FILTCAP slots
+                                 * [8] colour-fill visits of opacity exactly 1.0 [9] row pairs of fill visits that no lane covers */
     osmt_srec seg[SEGCAP];          /* records of the current group that belong to this sub-tile, compacted */
     SegDer der[SEGCAP];
     uint32_t pre[SEGCAP];           /* inclusive item prefix of the compacted records */
     unsigned long long plane[PLANE_STRIDE * SUBH]; /* generation alpha plane (f64 bit patterns) */
     StagedEnt ent[OPCHUNK];         /* ops of the chunk that draw into this sub-tile, in order */
+    uint32_t nvi[OPCHUNK];          /* inclusive prefix of the chunk's stroke slots: read at the head of every group (a register held
+                                     * across the per-op loop was the kernel's one spill, reloaded from scratch after every stroke blend) */
 #if OSMT_STAGE_UNION
     /* an entry is a fill OR a stroke: with a staging slot per ENTRY of the chunk (stage = the entry's place in it) the
      * coverage words and the stroke constants share their 64 bytes — 768 bytes that the dash table and the queue of the
@@ -614,7 +617,9 @@ struct RasterShared {
     uint8_t occupancy_experiment_pad[OSMT_V_LDSPAD];
 #endif
 };
+#if !(defined(OSMT_ABL) && OSMT_ABL == 5) /* (the diagnostic build's counters take it past the limit: it counts, it is not timed) */
 static_assert(sizeof(RasterShared) <= 10240, "16 waves per CU (four per SIMD) share 160 KB of LDS");
+#endif
 #if OSMT_STAGE_UNION
 #define SH_FMASK(sh, st) ((sh).stg[st].fmask)
 #define SH_SCONST(sh, st) ((sh).stg[st].sconst)
@@ -1760,7 +1765,8 @@ constexpr uint32_t SUBLIST_MAX_SUB = (OSMT_TILE_SIZE * OSMT_MAX_SCALE / OSMT_SUB
 __global__ __launch_bounds__(SUBLIST_THREADS) void k_sublist(const osmt_tile_job* __restrict__ g_jobs, uint32_t g_scale,
                                                              const osmt_opinfo* __restrict__ g_info, const uint32_t* __restrict__ g_submask,
                                                              uint32_t g_sub_rows, const uint32_t* __restrict__ g_cnt,
-                                                             unsigned long long* __restrict__ g_cursor, uint2* __restrict__ g_hdr,
+                                                             unsigned long long* __restrict__ g_cursor, unsigned long long* __restrict__ g_lcur,
+                                                             uint2* __restrict__ g_hdr,
                                                              osmt_ent* __restrict__ g_ent, unsigned long long ent_cap, uint32_t* g_err,
                                                              uint32_t g_fold_max_ops) {
     __shared__ uint32_t s_off[SUBLIST_MAX_SUB]; /* counts, then exclusive offsets inside the tile */
@@ -1845,9 +1851,20 @@ __global__ __launch_bounds__(SUBLIST_THREADS) void k_sublist(const osmt_tile_job
         }
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         if (lane == 0u) {
-            const unsigned long long first = total ? atomicAdd(g_cursor, (unsigned long long)total) : 0ull;
+            /* the tile's cursor and slice of the arena (osmt_list_slices.h): 1024 workgroups behind ONE cursor queued for ~12 ns each */
+            const osmt_list_layout lay = osmt_list_layout_make(gridDim.x, ent_cap);
+            const uint32_t slice = osmt_list_slice_of(lay, tile);
+            unsigned long long* const cur = lay.n_slices > 1u ? g_lcur + (size_t)slice * OSMT_LIST_CURSOR_STRIDE : g_cursor;
+            unsigned long long first = 0ull;
+            uint32_t ok = 1u;
+            if (total) {
+                ok = osmt_list_place(lay, slice, atomicAdd(cur, (unsigned long long)total), total, &first);
+                if (!ok && lay.n_slices > 1u) /* the slice is full: the overflow slice holds whatever the binning can produce */
+                    ok = osmt_list_place_overflow(lay, ent_cap, atomicAdd(g_lcur + (size_t)lay.n_slices * OSMT_LIST_CURSOR_STRIDE, (unsigned long long)total),
+                                                  total, &first);
+            }
             s_base[0] = (uint32_t)first;
-            s_base[1] = (first + total <= ent_cap) ? 1u : 0u; /* always: the arena holds every (op, sub-tile) pair the binning can produce */
+            s_base[1] = ok; /* always: the arena holds every (op, sub-tile) pair the binning can produce */
             if (!s_base[1] && g_err) *(volatile uint32_t*)g_err = OSMT_PREPASS_ERR_LIST_ARENA; /* the tile would be blank: tell the host */
         }
     }
@@ -2073,7 +2090,7 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
         }
     }
     bool plane_clean = false; /* the alpha plane is cleared when the first stroke op shows up */
-    OSMT_DBG(if (lane < 8) sh.dbg[lane] = 0u; __syncthreads();)
+    OSMT_DBG(if (lane < 12) sh.dbg[lane] = 0u; __syncthreads();)
 
     /* this sub-tile's own list (k_sublist): the ops that draw here, in order, OPCHUNK at a time.  (Fetching the next
      * chunk's entries a chunk ahead cost eight registers for the whole chunk: 21 more spilled registers at 128, whose
@@ -2165,9 +2182,10 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
 #endif
         /* slots of the stroke entries, prefix-summed over the chunk's lanes: the groups of the filter passes are cut out
          * of this scan with a ballot instead of a scalar loop over the entries (clamped: only "more than a pass" matters) */
-        const uint32_t nv_incl = wave_incl_scan(is_stroke ? min(e.nv, 1u << 20) : 0u);
+        const uint32_t nv_scan = wave_incl_scan(is_stroke ? min(e.nv, 1u << 20) : 0u);
         __syncthreads(); /* the previous chunk's list is consumed */
         if (hit) {
+            sh.nvi[fresh_lane()] = nv_scan; /* only the lanes of the chunk's entries are ever asked for theirs */
             StagedEnt se;
             const double cr = k_u8_over_255[(e.kind_color >> 8) & 255u], cg = k_u8_over_255[(e.kind_color >> 16) & 255u],
                          cb = k_u8_over_255[e.kind_color >> 24];
@@ -2226,6 +2244,9 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
         uint32_t gend = total, V = 0;
         bool big = false;
         uint32_t s_before = 0u;           /* slots of the chunk's entries in front of the group */
+        /* lanes in [total, OPCHUNK) read what an earlier chunk left there and the lanes above them alias the lanes below:
+         * harmless, every use of nv_incl below is guarded by lane < total, lane < gend or `mine` (readlanes take lanes < total) */
+        const uint32_t nv_incl = any_stroke ? sh.nvi[fresh_lane() & (uint32_t)(OPCHUNK - 1)] : 0u;
         if (any_stroke) {
             s_before = g0 ? (uint32_t)__builtin_amdgcn_readlane((int)nv_incl, (int)g0 - 1) : 0u;
             const unsigned long long over = __ballot(lane >= g0 && lane < total && nv_incl - s_before > (uint32_t)FILTCAP);
@@ -2505,10 +2526,13 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
                 for (int j = 0; j < PXT; ++j)
                     m_[j] = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)w_[2 * j]) |
                             ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)w_[2 * j + 1]) << 32);
+                OSMT_DBG(if (lane == 0) for (int j = 0; j < PXT; ++j) sh.dbg[9] += m_[j] == 0ull ? 1u : 0u;)
                 /* Filler::Color: the wave-uniform colour the staging lane prepared */
                 const bool image = kind != OSMT_OP_FILL_COLOR;
                 if (!image) {
                     const double c0 = en.c0, c1 = en.c1, c2 = en.c2;
+                    /* (opacity exactly 1.0: the staged factor 1 - o is +0.0, both words zero) */
+                    OSMT_DBG(if (lane == 0) sh.dbg[8] += (__double2hiint(cop) | __double2loint(cop)) == 0 ? 1u : 0u;)
 #pragma unroll
                     for (int j = 0; j < PXT; ++j) blend_masked(acc[AJ(j)][0], acc[AJ(j)][1], acc[AJ(j)][2], c0, c1, c2, cop, m_[j]);
                 }
@@ -2656,7 +2680,7 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
 #else
             __builtin_nontemporal_store(v, out);
 #endif
-            OSMT_DBG(__syncthreads(); if (j == 0 && ly_o == 0 && lx_o < 8) *out = sh.dbg[lx_o];)
+            OSMT_DBG(__syncthreads(); if (j == 0 && ly_o == 0 && lx_o < 12) *out = sh.dbg[lx_o];)
         }
     }
 }
@@ -2796,6 +2820,8 @@ hipError_t osmt_launch_project(const osmt_tile_job* jobs, const uint32_t* pt_job
 size_t osmt_prepass_zero_words(const osmt_prepass_args& a) {
     const uint32_t Wt = OSMT_TILE_SIZE * a.scale;
     const size_t n_cnt = (a.fmask_cap || a.srec_cap) ? (size_t)a.n_jobs * (Wt / SUB) * (Wt / SUBH) : 0;
+    /* a batch whose list arena is cut into slices has their cursors behind the counts (osmt_list_slices.h) */
+    if (n_cnt && osmt_list_layout_make(a.n_jobs, a.ent_cap).n_slices > 1u) return osmt_list_cursor_word0(n_cnt) + OSMT_LIST_CURSOR_WORDS;
     return 4 * sizeof(unsigned long long) / sizeof(uint32_t) + n_cnt;
 }
 
@@ -2831,9 +2857,13 @@ hipError_t osmt_launch_prepass(const osmt_prepass_args& a, hipStream_t st, bool 
                            a.op_blk, a.blk, a.n_vsegs, roles,
                            a.scale, a.sub_rows, a.submask, a.fmask, a.srec, a.skey, a.op_job, a.cnt, a.vseg);
     /* lists only for tiles with more than OSMT_FOLD_MAX_OPS ops (k_raster's waves put the others' together themselves) */
-    if (a.n_jobs && (a.fold_max_ops == 0u || a.max_job_ops > a.fold_max_ops))
+    if (a.n_jobs && (a.fold_max_ops == 0u || a.max_job_ops > a.fold_max_ops)) {
+        const uint32_t Wt = OSMT_TILE_SIZE * a.scale;
+        unsigned long long* const lcur = reinterpret_cast<unsigned long long*>(
+            reinterpret_cast<uint32_t*>(a.cursors) + osmt_list_cursor_word0((size_t)a.n_jobs * (Wt / SUB) * (Wt / SUBH)));
         hipLaunchKernelGGL(k_sublist, dim3(a.n_jobs), dim3(SUBLIST_THREADS), 0, st, a.jobs, a.scale, a.info, a.submask, a.sub_rows, a.cnt,
-                           a.cursors + 2, a.hdr, a.ent, a.ent_cap, a.err, a.fold_max_ops);
+                           a.cursors + 2, lcur, a.hdr, a.ent, a.ent_cap, a.err, a.fold_max_ops);
+    }
     return hipGetLastError();
 }
 

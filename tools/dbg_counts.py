@@ -1,5 +1,5 @@
 """Diagnostic: per-wave work counters of k_raster from a library built with -DOSMT_ABL=5 (the counters replace the
-first 8 pixels of every sub-tile's first row).  OSMT_LIB=.../libosmtile_dbg.so python tools/dbg_counts.py"""
+first 12 pixels of every sub-tile's first row).  OSMT_LIB=.../libosmtile_dbg.so python tools/dbg_counts.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -26,9 +26,11 @@ else:
     dl = synth.config5(16) if which == "config5" else synth.config2(64)
 NT = dl.n_jobs
 out = ctx.render(ctx.upload(dl)).cpu().numpy().view(np.uint32).reshape(NT, 256, 256)
-c = out[:, ::16, :].reshape(NT, 16, 8, 32)[:, :, :, :8].reshape(-1, 8).astype(np.int64)
-names = ["stroke_visits", "passes", "items", "group_filter_passes", "groups_cut_by_kept", "fill_visits", "ops_over_segcap_kept", "ops_over_filtcap_slots"]
+c = out[:, ::16, :].reshape(NT, 16, 8, 32)[:, :, :, :12].reshape(-1, 12).astype(np.int64)
+names = ["stroke_visits", "passes", "items", "group_filter_passes", "groups_cut_by_kept", "fill_visits", "ops_over_segcap_kept", "ops_over_filtcap_slots",
+         "opaque_fill_visits", "empty_fill_row_pairs", "-", "-"]
 print("waves", len(c))
 for i, n in enumerate(names):
     print(f"{n:16s} per wave {c[:, i].mean():10.2f}   per tile {c[:, i].sum() / NT:12.1f}")
+print("opaque share of fill visits", c[:, 8].sum() / max(c[:, 5].sum(), 1), " empty share of the row pairs of fill visits", c[:, 9].sum() / max(8 * c[:, 5].sum(), 1))
 print("items per pass", c[:, 2].sum() / max(c[:, 1].sum(), 1), " passes per stroke visit", c[:, 1].sum() / max(c[:, 0].sum(), 1))
