@@ -844,8 +844,8 @@ int osmt_label_tile_batch_expand(osmt_ctx* ctx, const osmt_label_tile_batch* bat
  * for_labels: layer or 0, z_index, global id), and per (node, style) the osmt_label + osmt_string_run Labeler::label_entity
  * implies (labeler.rs:16-106, text_placer.rs:24-58): the anchor is Point::from_node (labelable.rs:15-24), the default text
  * position of a node is Center.  The batch goes through the string-label path of osmt_scene_set_string_labels.  Labels of
- * ways and multipolygons stay host-built (polylabel, libm angles) and may be handed in: they are drawn in front of the
- * nodes' (drawer.rs:229-250).  The host twin is osmt::node_labels_of_tile (host/osmt_tilelabels.hpp). */
+ * ways and multipolygons may be handed in host-built: they are drawn in front of the nodes' (drawer.rs:229-250);
+ * osmt_scene_build_tile_labels_all below builds them on the device too.  The host twin is osmt::node_labels_of_tile (host/osmt_tilelabels.hpp). */
 
 #define OSMT_TILE_LABELS_MAX 65536u /* (node, style) labels of one tile */
 #define OSMT_TEXT_NONE 0xFFFFFFFFu  /* osmt_label_binding.text: the tag text_style.text names is absent (text_placer.rs:42-45) */
@@ -932,6 +932,80 @@ int osmt_scene_build_tile_labels(osmt_ctx* ctx, osmt_scene* scene, const uint32_
  * output is OSMT_INVALID_ARG); each output may be NULL; job_label_off gets n_tiles + 1 entries. */
 int osmt_scene_read_tile_labels(osmt_ctx* ctx, osmt_scene* scene, osmt_label* labels, osmt_string_run* runs, uint32_t* chars,
                                 uint32_t* job_label_off, const size_t caps[2], size_t counts[2]);
+
+/* ---- area labels of tile-built scenes: order, anchors and way text on the GPU ------------------------------------ */
+/* What Drawer::draw_labels does for the WAYS and MULTIPOLYGONS of a tile (drawer.rs:229-250), for a scene of
+ * osmt_scene_build_tiles: the 3 x 3 neighbourhood query over the way and multipolygon lists of the tile index, the label
+ * styles bound to every entity under the tile's zoom, the order of style_areas(.., for_labels = true) (styler.rs:168-203: each
+ * kind stably sorted by layer or 0, z_index, global id; merged with the multipolygon first on a tie), and per (entity, style)
+ * what Labeler::label_entity does (labeler.rs:16-106, text_placer.rs:24-168): the anchor get_label_position of the entity
+ * under the tile (the kernels of osmt_label_positions_tiles, fed on the device) for the icon and a centred text, the way's
+ * points in walking order for a text along the line.  The default text position is Line for a way and Center for a
+ * multipolygon; Line on a multipolygon and Center without an anchor rasterize nothing.  The angles of a text along a way —
+ * atan2, sin, cos of integer differences — are filled in by the library ON THE HOST, with the libm of the process, in the batch
+ * it reads back: the libm the caller's own code would have called.  The host twin is osmt::area_labels_of_tile
+ * (host/osmt_arealabels.hpp). */
+
+/* (way -> label style, text), (multipolygon -> label style, text) for a range of zooms, in push order, and the text pool */
+typedef struct osmt_area_label_bindings_desc {
+    uint32_t geodata_id;
+    uint8_t zoom_lo, zoom_hi, _pad[2]; /* inclusive */
+    const uint32_t* way_off;           /* [n_ways + 1] into way_bindings */
+    const osmt_label_binding* way_bindings; /* style: id from osmt_register_label_styles; text_position NONE: the kind's default */
+    size_t n_way_bindings;
+    const uint32_t* multipolygon_off; /* [n_multipolygons + 1] into multipolygon_bindings */
+    const osmt_label_binding* multipolygon_bindings;
+    size_t n_multipolygon_bindings;
+    const uint32_t* text_off; /* [n_texts + 1] into chars */
+    size_t n_texts;
+    const uint32_t* chars; /* Unicode scalar values */
+    size_t n_chars;
+} osmt_area_label_bindings_desc;
+
+/* The anchor of one (tile, entity) pair: what the search declined (osmt_scene_read_declined_anchors) and what the caller hands
+ * back computed (osmt_scene_build_tile_labels_all); 32 bytes. */
+typedef struct osmt_area_anchor {
+    uint32_t tile;   /* index of the tile in the scene */
+    uint32_t entity; /* local id of a way; of a multipolygon: | OSMT_STYLED_MULTIPOLYGON */
+    double x, y;
+    uint32_t status; /* OSMT_LABEL_OK / OSMT_LABEL_NONE (handed in); OSMT_LABEL_TOO_LARGE (read as declined) */
+    uint32_t _pad;
+} osmt_area_anchor;
+
+/* OSMT_INVALID_ARG, naming the offender: an unknown geodata id (a NULL `ctx` has none), one without a tile index
+ * (osmt_register_tile_index) or without Mercator factors (osmt_register_node_mercator); zoom_lo > zoom_hi or zoom_hi >
+ * OSMT_MAX_ZOOM; offsets that do not start at 0, decrease or do not end at the pool length (their counts are the geodata's);
+ * a style id that is not registered at the time of the call; a text id that is neither in the pool nor OSMT_TEXT_NONE; a char
+ * that is not a Unicode scalar value.  OSMT_UNSUPPORTED: a pool too large for 32-bit indices. */
+int osmt_validate_area_label_bindings(const osmt_area_label_bindings_desc* b, osmt_ctx* ctx);
+/* Appends an area label bindings table (one device allocation that never moves) and returns its id; ids are counted apart
+ * from those of osmt_register_label_bindings. */
+int osmt_register_area_label_bindings(osmt_ctx* ctx, const osmt_area_label_bindings_desc* b, uint32_t* out_bindings_id);
+/* Builds the area labels of every tile of `scene` on the device (csrc/osmt_arealabels.hip), then its node labels as
+ * osmt_scene_build_tile_labels does, and attaches each tile's area labels in front of its node labels as ONE string batch.
+ * area_bindings_of_zoom[z]: id from osmt_register_area_label_bindings; node_bindings_of_zoom[z]: id from
+ * osmt_register_label_bindings; either array may be NULL (no labels of that kind), an entry of a zoom some tile has may not
+ * be OSMT_BINDINGS_NONE.  `anchors` (may be NULL with n_anchors 0): anchors the caller computed for pairs an earlier call
+ * declined — strictly ascending by (tile, entity), status OK or NONE, x and y finite with |v| <= 2^28, tile and entity in
+ * range, else OSMT_INVALID_ARG; a listed pair is not searched.
+ * OSMT_UNSUPPORTED with the exact figure: a tile with more than OSMT_TILE_LABELS_MAX area labels; label, char, way point,
+ * ring or point totals that do not fit 32 bits; and: the anchor search declined pairs (OSMT_LABEL_TOO_LARGE) — the message
+ * names their number and the first (tile, entity), osmt_scene_read_declined_anchors returns all of them; compute them
+ * (osmt::get_label_position over osmt::label_rings_of) and call again.  A label is never wrong and never dropped.
+ * On an error of the build the scene keeps the labels it had and the context stays usable; an error of the attach leaves it
+ * without labels, as osmt_scene_set_string_labels does. */
+int osmt_scene_build_tile_labels_all(osmt_ctx* ctx, osmt_scene* scene, const uint32_t area_bindings_of_zoom[OSMT_MAX_ZOOM + 1],
+                                     const uint32_t node_bindings_of_zoom[OSMT_MAX_ZOOM + 1], const osmt_area_anchor* anchors, size_t n_anchors);
+/* The pairs the last osmt_scene_build_tile_labels_all of the scene declined, ascending by (tile, entity), status
+ * OSMT_LABEL_TOO_LARGE, x = y = 0; none after a call that did not decline.  *n is always set; out may be NULL to ask for the
+ * size; cap < *n with a non-NULL out is OSMT_INVALID_ARG. */
+int osmt_scene_read_declined_anchors(osmt_ctx* ctx, osmt_scene* scene, osmt_area_anchor* out, size_t cap, size_t* n);
+/* Inspection: the area batch the last successful osmt_scene_build_tile_labels_all of the scene built, before the splice
+ * (osmt_scene_read_tile_labels keeps returning the node batch).  counts = { labels, chars, way points } is always set; caps
+ * bound what is written (a smaller cap with a non-NULL output is OSMT_INVALID_ARG); each output may be NULL; way_pts is
+ * int32 [n][2], way_sincos double [n][2]; job_label_off gets n_tiles + 1 entries. */
+int osmt_scene_read_tile_area_labels(osmt_ctx* ctx, osmt_scene* scene, osmt_label* labels, osmt_string_run* runs, uint32_t* chars,
+                                     int32_t* way_pts, double* way_sincos, uint32_t* job_label_off, const size_t caps[3], size_t counts[3]);
 
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */

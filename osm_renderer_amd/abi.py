@@ -487,3 +487,30 @@ class LabelBindingsDesc(C.Structure):
         ("chars", C.POINTER(C.c_uint32)),
         ("n_chars", C.c_size_t),
     ]
+
+
+class AreaLabelBindingsDesc(C.Structure):
+    _fields_ = [
+        ("geodata_id", C.c_uint32),
+        ("zoom_lo", C.c_uint8),
+        ("zoom_hi", C.c_uint8),
+        ("_pad", C.c_uint8 * 2),
+        ("way_off", C.POINTER(C.c_uint32)),
+        ("way_bindings", C.POINTER(LabelBinding)),
+        ("n_way_bindings", C.c_size_t),
+        ("multipolygon_off", C.POINTER(C.c_uint32)),
+        ("multipolygon_bindings", C.POINTER(LabelBinding)),
+        ("n_multipolygon_bindings", C.c_size_t),
+        ("text_off", C.POINTER(C.c_uint32)),
+        ("n_texts", C.c_size_t),
+        ("chars", C.POINTER(C.c_uint32)),
+        ("n_chars", C.c_size_t),
+    ]
+
+
+class AreaAnchor(C.Structure):  # osmt_area_anchor
+    _fields_ = [("tile", C.c_uint32), ("entity", C.c_uint32), ("x", C.c_double), ("y", C.c_double), ("status", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+assert C.sizeof(AreaLabelBindingsDesc) == 88
+assert C.sizeof(AreaAnchor) == 32

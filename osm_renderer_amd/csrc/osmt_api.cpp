@@ -163,6 +163,14 @@ struct osmt_ctx {
         osmt_tl_bind_dev dev{};
     };
     std::vector<label_bindings_host> label_bindings;
+    /* the tables of osmt_register_area_label_bindings, under the same rules */
+    struct area_label_bindings_host {
+        uint32_t geodata_id = 0;
+        uint8_t zoom_lo = 0, zoom_hi = 0;
+        void* d_pool = nullptr;
+        osmt_al_bind_dev dev{};
+    };
+    std::vector<area_label_bindings_host> area_label_bindings;
     /* the label styles of osmt_register_label_styles: records and ranks, replaced like the style table when it has grown */
     std::vector<osmt_label_style_rec> label_styles;
     osmt_label_style_rec* d_label_styles = nullptr;
@@ -298,6 +306,14 @@ struct osmt_scene {
     std::vector<osmt_label> h_tl_labels;
     std::vector<osmt_string_run> h_tl_runs;
     std::vector<uint32_t> h_tl_chars, h_tl_off;
+    /* the area batch the last osmt_scene_build_tile_labels_all read back (osmt_scene_read_tile_area_labels), and the pairs
+     * its anchor search declined (osmt_scene_read_declined_anchors) */
+    std::vector<osmt_label> h_al_labels;
+    std::vector<osmt_string_run> h_al_runs;
+    std::vector<uint32_t> h_al_chars, h_al_off;
+    std::vector<int32_t> h_al_pts;
+    std::vector<double> h_al_sincos;
+    std::vector<osmt_area_anchor> h_al_declined;
 };
 
 namespace {
@@ -660,6 +676,8 @@ void ctx_teardown(osmt_ctx* ctx) {
     for (auto& b : ctx->bindings)
         if (b.d_pool) (void)hipFree(b.d_pool);
     for (auto& b : ctx->label_bindings)
+        if (b.d_pool) (void)hipFree(b.d_pool);
+    for (auto& b : ctx->area_label_bindings)
         if (b.d_pool) (void)hipFree(b.d_pool);
     if (ctx->d_label_styles) (void)hipFree(ctx->d_label_styles);
     if (ctx->d_label_rank) (void)hipFree(ctx->d_label_rank);
@@ -3473,7 +3491,17 @@ static int register_label_bindings_body(osmt_ctx* ctx, const osmt_label_bindings
     return OSMT_OK;
 }
 
-static int scene_build_tile_labels_body(osmt_ctx* ctx, osmt_scene* sc, const uint32_t* bindings_of_zoom, const osmt_string_label_batch* area) {
+/* the node labels of a batch as the device built them, tile behind tile */
+struct node_label_batch {
+    std::vector<osmt_label> labels;
+    std::vector<osmt_string_run> runs;
+    std::vector<uint32_t> chars, job_off;
+};
+
+/* The first half of osmt_scene_build_tile_labels: validates (the bindings, then the shape of `area`), builds the node labels on
+ * the device and reads them back into `nb`.  The scene is not touched. */
+static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t* bindings_of_zoom, const osmt_string_label_batch* area,
+                                  node_label_batch* nb) {
     if (!ctx || !sc || sc->ctx != ctx || !bindings_of_zoom) return fail(OSMT_INVALID_ARG, "bad ctx/scene/bindings");
     if (!sc->d_tq) return fail(OSMT_INVALID_ARG, "the scene was not built by osmt_scene_build_tiles: it has no tiles to query");
     const size_t n_tiles = sc->n_jobs;
@@ -3561,9 +3589,11 @@ static int scene_build_tile_labels_body(osmt_ctx* ctx, osmt_scene* sc, const uin
         for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
     auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
 
-    std::vector<osmt_label> labels;
-    std::vector<osmt_string_run> runs;
-    std::vector<uint32_t> chars, job_off(n_tiles + 1, 0u);
+    std::vector<osmt_label>& labels = nb->labels;
+    std::vector<osmt_string_run>& runs = nb->runs;
+    std::vector<uint32_t>&chars = nb->chars, &job_off = nb->job_off;
+    labels.clear(), runs.clear(), chars.clear();
+    job_off.assign(n_tiles + 1, 0u);
     size_t n_items = 0, n_cand = 0, n_labels = 0, n_chars = 0;
     unsigned long long max_labels = 0;
     if (n_tiles) {
@@ -3729,7 +3759,17 @@ static int scene_build_tile_labels_body(osmt_ctx* ctx, osmt_scene* sc, const uin
                     n_chars, n_labels * (sizeof(osmt_label) + sizeof(osmt_string_run)) + n_chars * 4 + (n_tiles + 1) * 4);
         }
     }
-    /* splice: each tile's area labels in front of its node labels (drawer.rs:229-261), seg_off and pt_off re-based */
+    return OSMT_OK;
+}
+
+/* The second half: each tile's area labels (may be NULL) in front of its node labels (drawer.rs:229-261), seg_off re-based,
+ * attached as one string batch; on success the scene keeps the node batch for osmt_scene_read_tile_labels. */
+static int tile_labels_attach(osmt_ctx* ctx, osmt_scene* sc, const osmt_string_label_batch* area, node_label_batch* nb) {
+    std::vector<osmt_label>& labels = nb->labels;
+    std::vector<osmt_string_run>& runs = nb->runs;
+    std::vector<uint32_t>&chars = nb->chars, &job_off = nb->job_off;
+    const size_t n_tiles = sc->n_jobs, n_labels = labels.size(), n_chars = chars.size();
+    int rc = OSMT_OK;
     osmt_string_label_batch sb{};
     std::vector<osmt_label> m_labels;
     std::vector<osmt_string_run> m_runs;
@@ -3767,6 +3807,12 @@ static int scene_build_tile_labels_body(osmt_ctx* ctx, osmt_scene* sc, const uin
     sc->h_tl_chars.swap(chars);
     sc->h_tl_off.swap(job_off);
     return OSMT_OK;
+}
+
+static int scene_build_tile_labels_body(osmt_ctx* ctx, osmt_scene* sc, const uint32_t* bindings_of_zoom, const osmt_string_label_batch* area) {
+    node_label_batch nb;
+    const int rc = tile_node_labels_build(ctx, sc, bindings_of_zoom, area, &nb);
+    return rc != OSMT_OK ? rc : tile_labels_attach(ctx, sc, area, &nb);
 }
 
 static int scene_read_tile_labels_body(osmt_ctx* ctx, osmt_scene* sc, osmt_label* labels, osmt_string_run* runs, uint32_t* chars, uint32_t* job_label_off,
@@ -4164,7 +4210,8 @@ static int validate_label_tile_batch(const osmt_label_tile_batch* b, osmt_ctx* c
  * behind the arrays of the projection — the caller's arrays, starting at j->d_base + *extra_off.  sizes_only: the totals
  * and nothing after them. */
 static int label_tiles_expand(osmt_ctx* ctx, const osmt_label_tile_batch* b, const osmt_ctx::geodata_host& geo, osmt_label_job* j, bool sizes_only,
-                              const std::function<size_t(size_t)>& extra_of, size_t* extra_off, osmt_an_pass* out_pass) {
+                              const std::function<size_t(size_t)>& extra_of, size_t* extra_off, osmt_an_pass* out_pass,
+                              const osmt_label_tile_request* d_req = nullptr, const osmt_query_tile* d_tiles = nullptr) {
     const size_t n = b->n_requests;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -4172,17 +4219,20 @@ static int label_tiles_expand(osmt_ctx* ctx, const osmt_label_tile_batch* b, con
         off = align_up(off + std::max<size_t>(bytes, 4), 256);
         return o;
     };
-    const size_t o_req = take(n * sizeof(osmt_label_tile_request)), o_tiles = take(b->n_tiles * sizeof(osmt_query_tile)), o_rpos = take((n + 1) * 4),
+    const size_t o_req = take(d_req ? 0 : n * sizeof(osmt_label_tile_request)), o_tiles = take(d_req ? 0 : b->n_tiles * sizeof(osmt_query_tile)),
+                 o_rpos = take((n + 1) * 4),
                  o_ppos = take((n + 1) * 4), o_blk = take(((n + 255) / 256 + 1) * 8), o_tot = take(OSMT_AN_N * 8);
     HIP_TRY(dev_alloc(ctx, (void**)&j->d_front, off));
     char* d = j->d_front;
-    HIP_TRY(hipMemcpyAsync(d + o_req, b->requests, n * sizeof(osmt_label_tile_request), hipMemcpyHostToDevice, j->st));
-    HIP_TRY(hipMemcpyAsync(d + o_tiles, b->tiles, b->n_tiles * sizeof(osmt_query_tile), hipMemcpyHostToDevice, j->st));
+    if (!d_req) { /* d_req, d_tiles: the requests and tiles are on the device already (b->requests and b->tiles are not read) */
+        HIP_TRY(hipMemcpyAsync(d + o_req, b->requests, n * sizeof(osmt_label_tile_request), hipMemcpyHostToDevice, j->st));
+        HIP_TRY(hipMemcpyAsync(d + o_tiles, b->tiles, b->n_tiles * sizeof(osmt_query_tile), hipMemcpyHostToDevice, j->st));
+    }
     osmt_an_pass a{};
     a.geo = geo.dev;
     a.factors = geo.d_factors;
-    a.req = (const osmt_label_tile_request*)(d + o_req);
-    a.tiles = (const osmt_query_tile*)(d + o_tiles);
+    a.req = d_req ? d_req : (const osmt_label_tile_request*)(d + o_req);
+    a.tiles = d_req ? d_tiles : (const osmt_query_tile*)(d + o_tiles);
     a.n_req = (uint32_t)n;
     a.scale = b->scale;
     a.rpos = (uint32_t*)(d + o_rpos);
@@ -4314,6 +4364,591 @@ static int osmt_label_tile_batch_expand_body(osmt_ctx* ctx, const osmt_label_til
     if (out_rc == OSMT_OK && points && p.n_pts) HIP_TRY(hipMemcpyAsync(points, p.pts, (size_t)p.n_pts * 16, hipMemcpyDeviceToHost, j->st));
     HIP_TRY(hipStreamSynchronize(j->st)); /* also on a refusal: the job's buffers go back to the pool behind the kernels */
     return out_rc;
+}
+
+/* ---- area labels of tile-built scenes (include/osmtile.h, csrc/osmt_arealabels.hip) ------------------------------------ */
+static int validate_area_label_bindings(const osmt_area_label_bindings_desc* b, osmt_ctx* ctx, size_t* out_ways, size_t* out_mps) {
+    if (!b) return fail(OSMT_INVALID_ARG, "area label bindings are NULL");
+    if (b->zoom_lo > b->zoom_hi || b->zoom_hi > OSMT_MAX_ZOOM)
+        return fail(OSMT_INVALID_ARG, "area label bindings: zoom range %u..%u (zoom_lo <= zoom_hi <= %u)", b->zoom_lo, b->zoom_hi, OSMT_MAX_ZOOM);
+    if (!ctx) return fail(OSMT_INVALID_ARG, "area label bindings: geodata id %u is not registered (no context)", b->geodata_id);
+    size_t n_ways = 0, n_mps = 0, n_styles = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (b->geodata_id >= ctx->geodata.size())
+            return fail(OSMT_INVALID_ARG, "area label bindings: geodata id %u is not registered (%zu files)", b->geodata_id, ctx->geodata.size());
+        const osmt_ctx::geodata_host& g = ctx->geodata[b->geodata_id];
+        if (!g.d_index) return fail(OSMT_INVALID_ARG, "area label bindings: geodata id %u has no tile index (osmt_register_tile_index)", b->geodata_id);
+        if (!g.d_factors)
+            return fail(OSMT_INVALID_ARG, "area label bindings: geodata id %u has no Mercator factors (osmt_register_node_mercator)", b->geodata_id);
+        n_ways = g.n_ways, n_mps = g.n_mps;
+        n_styles = ctx->label_styles.size();
+    }
+    if (!b->way_off || !b->multipolygon_off || (b->n_way_bindings && !b->way_bindings) || (b->n_multipolygon_bindings && !b->multipolygon_bindings) ||
+        !b->text_off || (b->n_chars && !b->chars))
+        return fail(OSMT_INVALID_ARG, "area label bindings: NULL array (every offset array has at least its first entry)");
+    if (b->n_way_bindings >= 0xFFFFFFFFull || b->n_multipolygon_bindings >= 0xFFFFFFFFull || b->n_texts >= 0xFFFFFFFFull || b->n_chars >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "area label bindings: too large for 32-bit indices");
+    int rc = check_offsets_of("area label bindings", "way_off", b->way_off, n_ways, b->n_way_bindings);
+    if (rc == OSMT_OK) rc = check_offsets_of("area label bindings", "multipolygon_off", b->multipolygon_off, n_mps, b->n_multipolygon_bindings);
+    if (rc == OSMT_OK) rc = check_offsets_of("area label bindings", "text_off", b->text_off, b->n_texts, b->n_chars);
+    if (rc != OSMT_OK) return rc;
+    for (int kind = 0; kind < 2; ++kind) {
+        const osmt_label_binding* v = kind ? b->multipolygon_bindings : b->way_bindings;
+        const size_t n = kind ? b->n_multipolygon_bindings : b->n_way_bindings;
+        const char* name = kind ? "multipolygon_bindings" : "way_bindings";
+        for (size_t i = 0; i < n; ++i) {
+            if (v[i].style >= n_styles)
+                return fail(OSMT_INVALID_ARG, "area label bindings: %s[%zu].style = %u is not a registered label style (%zu styles)", name, i, v[i].style, n_styles);
+            if (v[i].text != OSMT_TEXT_NONE && v[i].text >= b->n_texts)
+                return fail(OSMT_INVALID_ARG, "area label bindings: %s[%zu].text = %u is not in the text pool (%zu texts) nor OSMT_TEXT_NONE", name, i, v[i].text,
+                            b->n_texts);
+        }
+    }
+    for (size_t i = 0; i < b->n_chars; ++i)
+        if (!osmt::textshaper_detail::is_char(b->chars[i]))
+            return fail(OSMT_INVALID_ARG, "area label bindings: chars[%zu] = U+%X is not a Unicode scalar value", i, b->chars[i]);
+    if (out_ways) *out_ways = n_ways;
+    if (out_mps) *out_mps = n_mps;
+    return OSMT_OK;
+}
+
+static int register_area_label_bindings_body(osmt_ctx* ctx, const osmt_area_label_bindings_desc* b, uint32_t* out_id) {
+    if (!ctx || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    size_t n_ways = 0, n_mps = 0;
+    const int rc = validate_area_label_bindings(b, ctx, &n_ways, &n_mps);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_wo = carve((n_ways + 1) * 4), o_mo = carve((n_mps + 1) * 4), o_wb = carve(b->n_way_bindings * sizeof(osmt_label_binding));
+    const size_t o_mb = carve(b->n_multipolygon_bindings * sizeof(osmt_label_binding)), o_to = carve((b->n_texts + 1) * 4), o_c = carve(b->n_chars * 4);
+    char* pool = nullptr;
+    HIP_TRY(hipMalloc((void**)&pool, off));
+    hipError_t e = hipSuccess;
+    auto put = [&](size_t o, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+    };
+    put(o_wo, b->way_off, (n_ways + 1) * 4);
+    put(o_mo, b->multipolygon_off, (n_mps + 1) * 4);
+    put(o_wb, b->way_bindings, b->n_way_bindings * sizeof(osmt_label_binding));
+    put(o_mb, b->multipolygon_bindings, b->n_multipolygon_bindings * sizeof(osmt_label_binding));
+    put(o_to, b->text_off, (b->n_texts + 1) * 4);
+    put(o_c, b->chars, b->n_chars * 4);
+    if (e != hipSuccess) {
+        (void)hipFree(pool);
+        return fail(OSMT_HIP_ERROR, "area label bindings upload failed: %s", hipGetErrorString(e));
+    }
+    osmt_ctx::area_label_bindings_host h;
+    h.geodata_id = b->geodata_id, h.zoom_lo = b->zoom_lo, h.zoom_hi = b->zoom_hi;
+    h.d_pool = pool;
+    h.dev.way_off = (const uint32_t*)(pool + o_wo);
+    h.dev.mp_off = (const uint32_t*)(pool + o_mo);
+    h.dev.way_bind = (const osmt_label_binding*)(pool + o_wb);
+    h.dev.mp_bind = (const osmt_label_binding*)(pool + o_mb);
+    h.dev.text_off = (const uint32_t*)(pool + o_to);
+    h.dev.chars = (const uint32_t*)(pool + o_c);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->area_label_bindings.size() + 1 >= 0xFFFFFFFFull) {
+        (void)hipFree(pool);
+        return fail(OSMT_INVALID_ARG, "area label bindings table too large");
+    }
+    *out_id = (uint32_t)ctx->area_label_bindings.size();
+    ctx->area_label_bindings.push_back(h);
+    return OSMT_OK;
+}
+
+/* the area labels of a batch as the device built them, tile behind tile, with the angles of the host */
+struct area_label_batch {
+    std::vector<osmt_label> labels;
+    std::vector<osmt_string_run> runs;
+    std::vector<uint32_t> chars, job_off;
+    std::vector<int32_t> pts;   /* [n][2] */
+    std::vector<double> sincos; /* [n][2] */
+};
+
+static_assert(OSMT_STYLED_MAX_TILE_AREAS == OSMT_TILE_LABELS_MAX, "k_tq_tiles reports the first tile over OSMT_STYLED_MAX_TILE_AREAS: the two limits are one");
+
+/* way_sincos of the runs of a batch (text_placer.rs:87-101, 256-262): (-atan2(dy, dx)).sin_cos() of the integer differences
+ * of every edge, with the libm of the process — the one the caller's own code would have called; the last entry of a run is 0 */
+static void area_label_angles(const std::vector<osmt_label>& labels, const std::vector<osmt_string_run>& runs, const std::vector<int32_t>& pts,
+                              std::vector<double>* sincos) {
+    sincos->assign(pts.size(), 0.0);
+    for (size_t l = 0; l < labels.size(); ++l) {
+        const osmt_string_run& r = runs[l];
+        if (!labels[l].has_text || r.position != OSMT_TEXT_LINE) continue;
+        for (uint32_t e = 0; e + 1 < r.n_pts; ++e) {
+            const int32_t* p = pts.data() + 2 * ((size_t)r.pt_off + e);
+            const double dx = (double)((int64_t)p[2] - (int64_t)p[0]), dy = (double)((int64_t)p[3] - (int64_t)p[1]);
+            const double a = std::atan2(dy, dx);
+            double* o = sincos->data() + 2 * ((size_t)r.pt_off + e);
+            o[0] = std::sin(-a);
+            o[1] = std::cos(-a);
+        }
+    }
+}
+
+/* Builds the area labels of every tile of `sc` on the device and reads them back into `out`.  The scene's labels are not
+ * touched; sc->h_al_declined is what the anchor search declined in THIS call. */
+static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t* bindings_of_zoom, const osmt_area_anchor* anchors, size_t n_anchors,
+                                  area_label_batch* out) {
+    const size_t n_tiles = sc->n_jobs;
+    const std::vector<osmt_query_tile>& q = sc->h_tq_tiles;
+    osmt_al_bind_dev bind[OSMT_MAX_ZOOM + 1];
+    osmt_tq_bind_dev tq_bind[OSMT_MAX_ZOOM + 1];
+    memset(bind, 0, sizeof bind);
+    memset(tq_bind, 0, sizeof tq_bind);
+    osmt_ctx::geodata_host geo;
+    std::vector<uint32_t> icon_h;
+    {
+        bool zoom_used[OSMT_MAX_ZOOM + 1] = {};
+        size_t first_of_zoom[OSMT_MAX_ZOOM + 1] = {};
+        for (size_t t = 0; t < n_tiles; ++t)
+            if (!zoom_used[q[t].zoom]) zoom_used[q[t].zoom] = true, first_of_zoom[q[t].zoom] = t;
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        geo = ctx->geodata[sc->tq_geodata_id];
+        if (!geo.d_factors) return fail(OSMT_INVALID_ARG, "geodata id %u has no Mercator factors (osmt_register_node_mercator)", sc->tq_geodata_id);
+        for (uint32_t z = 0; z <= OSMT_MAX_ZOOM; ++z) {
+            if (!zoom_used[z]) continue;
+            const uint32_t id = bindings_of_zoom[z];
+            if (id == OSMT_BINDINGS_NONE)
+                return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u has no area label bindings (OSMT_BINDINGS_NONE)", first_of_zoom[z], z);
+            if (id >= ctx->area_label_bindings.size())
+                return fail(OSMT_INVALID_ARG, "tile %zu: area label bindings id %u of zoom %u is not registered (%zu tables)", first_of_zoom[z], id, z,
+                            ctx->area_label_bindings.size());
+            const osmt_ctx::area_label_bindings_host& h = ctx->area_label_bindings[id];
+            if (h.geodata_id != sc->tq_geodata_id)
+                return fail(OSMT_INVALID_ARG, "tile %zu: area label bindings id %u of zoom %u belongs to geodata id %u, not %u", first_of_zoom[z], id, z,
+                            h.geodata_id, sc->tq_geodata_id);
+            if (z < h.zoom_lo || z > h.zoom_hi)
+                return fail(OSMT_INVALID_ARG, "tile %zu: area label bindings id %u covers zooms %u..%u, not zoom %u", first_of_zoom[z], id, h.zoom_lo,
+                            h.zoom_hi, z);
+            bind[z] = h.dev;
+            tq_bind[z].way_off = h.dev.way_off, tq_bind[z].mp_off = h.dev.mp_off; /* k_tq_mark and k_tq_tiles read no style */
+        }
+        icon_h.resize(ctx->images.size());
+        for (size_t i = 0; i < icon_h.size(); ++i) icon_h[i] = ctx->images[i].height;
+    }
+    if (n_anchors && !anchors) return fail(OSMT_INVALID_ARG, "anchors are NULL with n_anchors = %zu", n_anchors);
+    if (n_anchors >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "too many anchors for 32-bit indices");
+    for (size_t i = 0; i < n_anchors; ++i) {
+        const osmt_area_anchor& a = anchors[i];
+        const uint32_t id = a.entity & ~OSMT_STYLED_MULTIPOLYGON;
+        if (a.tile >= n_tiles) return fail(OSMT_INVALID_ARG, "anchor %zu: tile %u is not a tile of the scene (%zu tiles)", i, a.tile, n_tiles);
+        if (id >= ((a.entity & OSMT_STYLED_MULTIPOLYGON) ? geo.n_mps : geo.n_ways))
+            return fail(OSMT_INVALID_ARG, "anchor %zu: %s %u out of range", i, (a.entity & OSMT_STYLED_MULTIPOLYGON) ? "multipolygon" : "way", id);
+        if (a.status != OSMT_LABEL_OK && a.status != OSMT_LABEL_NONE)
+            return fail(OSMT_INVALID_ARG, "anchor %zu: status %u (a handed-in anchor is OSMT_LABEL_OK or OSMT_LABEL_NONE)", i, a.status);
+        if (!(std::fabs(a.x) <= 268435456.0) || !(std::fabs(a.y) <= 268435456.0))
+            return fail(OSMT_INVALID_ARG, "anchor %zu: (x, y) not finite or |v| > 2^28", i);
+        if (i && !(anchors[i - 1].tile < a.tile || (anchors[i - 1].tile == a.tile && anchors[i - 1].entity < a.entity)))
+            return fail(OSMT_INVALID_ARG, "anchor %zu: the anchors must be strictly ascending by (tile, entity)", i);
+    }
+    out->labels.clear(), out->runs.clear(), out->chars.clear(), out->pts.clear(), out->sincos.clear();
+    out->job_off.assign(n_tiles + 1, 0u);
+    if (!n_tiles) return OSMT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const osmt_label_style_rec* d_styles = nullptr;
+    const uint32_t* d_rank = nullptr;
+    int rc = sync_label_styles(ctx, &d_styles, &d_rank);
+    if (rc != OSMT_OK) return rc;
+    /* the job carries the stream, the pinned words of the totals and the two allocations of the anchors' projection;
+     * work[0]: per tile, [1]: per item, [2]: per candidate, [3]: per label, [4]: requests, [5]: chars and way points */
+    struct work_guard {
+        osmt_ctx* ctx;
+        osmt_label_job* j = nullptr;
+        char* work[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~work_guard() {
+            if (j && j->st) (void)hipStreamSynchronize(j->st); /* nothing may still read the buffers */
+            for (char* p : work) dev_free(ctx, p);
+            label_job_free(j);
+        }
+    } wg{ctx};
+    wg.j = new osmt_label_job();
+    osmt_label_job* j = wg.j;
+    j->ctx = ctx;
+    HIP_TRY(stream_acquire(ctx, &j->st));
+    hipStream_t st = j->st;
+    j->stage = (char*)stage_acquire(ctx, 256);
+    if (!j->stage) return fail(OSMT_OOM, "pinned staging for the totals could not be allocated");
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    auto alloc = [&](char** o, const char* what) {
+        const hipError_t e = dev_alloc(ctx, (void**)o, off + 256);
+        if (e == hipSuccess) return (int)OSMT_OK;
+        *o = nullptr;
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the area labels (%s) failed: %s", off, what, hipGetErrorString(e));
+    };
+    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    enum { EV_Q0, EV_Q1, EV_X0, EV_X1, EV_A0, EV_A1, EV_C0, EV_C1, EV_E0, EV_E1, EV_N };
+    hipEvent_t ev[EV_N] = {};
+    struct ev_guard {
+        hipEvent_t* ev;
+        ~ev_guard() {
+            for (int i = 0; i < EV_N; ++i)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } evg{ev};
+    if (trace)
+        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+
+    unsigned long long tq_tot[OSMT_TQ_N] = {}, al_tot[OSMT_AL_N] = {};
+    osmt_tq_pass Q;
+    memset(&Q, 0, sizeof Q);
+    osmt_al_pass P;
+    memset(&P, 0, sizeof P);
+    off = 0;
+    const size_t o_q = carve(n_tiles * sizeof(osmt_query_tile)), o_bind = carve(sizeof bind), o_tqb = carve(sizeof tq_bind), o_c0 = carve(n_tiles * 4);
+    const size_t o_ib = carve((n_tiles + 1) * 4), o_tw = carve((n_tiles + 1) * 4), o_tm = carve((n_tiles + 1) * 4), o_tot = carve((OSMT_TQ_N + OSMT_AL_N) * 8);
+    const size_t o_blk0 = carve((n_tiles / 256 + 1) * 8), o_ih = carve(std::max<size_t>(icon_h.size(), 1) * 4), o_jo = carve((n_tiles + 1) * 4);
+    const size_t o_st = carve(n_tiles * sizeof(osmt_styled_tile)), o_an = carve(std::max<size_t>(n_anchors, 1) * sizeof(osmt_area_anchor));
+    rc = alloc(&wg.work[0], "tiles");
+    if (rc != OSMT_OK) return rc;
+    char* w0 = wg.work[0];
+    HIP_TRY(hipMemcpyAsync(w0 + o_q, q.data(), n_tiles * sizeof(osmt_query_tile), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w0 + o_bind, bind, sizeof bind, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w0 + o_tqb, tq_bind, sizeof tq_bind, hipMemcpyHostToDevice, st));
+    if (!icon_h.empty()) HIP_TRY(hipMemcpyAsync(w0 + o_ih, icon_h.data(), icon_h.size() * 4, hipMemcpyHostToDevice, st));
+    if (n_anchors) HIP_TRY(hipMemcpyAsync(w0 + o_an, anchors, n_anchors * sizeof(osmt_area_anchor), hipMemcpyHostToDevice, st));
+    /* 1. the query over the way and multipolygon pools, as osmt_scene_build_tiles runs it */
+    Q.ix = geo.ix;
+    Q.geo_mp_off = geo.dev.mp_off;
+    Q.bind = (const osmt_tq_bind_dev*)(w0 + o_tqb);
+    Q.q = (const osmt_query_tile*)(w0 + o_q);
+    Q.n_tiles = (uint32_t)n_tiles;
+    Q.span_c0 = (uint32_t*)(w0 + o_c0);
+    Q.item_base = (uint32_t*)(w0 + o_ib);
+    Q.t_wbase = (uint32_t*)(w0 + o_tw);
+    Q.t_mbase = (uint32_t*)(w0 + o_tm);
+    Q.tot = (unsigned long long*)(w0 + o_tot);
+    Q.blk = (unsigned long long*)(w0 + o_blk0);
+    Q.tiles = (osmt_styled_tile*)(w0 + o_st);
+    Q.tile_base = (uint32_t*)(w0 + o_jo);
+    HIP_TRY(mark(EV_Q0));
+    HIP_TRY(osmt_launch_tq_span(Q, st));
+    HIP_TRY(hipMemcpyAsync(tq_tot, Q.tot, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tq_tot[OSMT_TQ_ITEMS] >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "area labels: the batch needs %llu (tile, column) items (> 2^32): split the batch", tq_tot[OSMT_TQ_ITEMS]);
+    const size_t n_items = (size_t)tq_tot[OSMT_TQ_ITEMS];
+    off = 0;
+    const size_t o_it = carve(n_items * 4), o_ws = carve(n_items * 4), o_ms = carve(n_items * 4), o_wb = carve((n_items + 1) * 4);
+    const size_t o_mb = carve((n_items + 1) * 4), o_blk1 = carve((n_items / 256 + 1) * 8);
+    rc = alloc(&wg.work[1], "columns");
+    if (rc != OSMT_OK) return rc;
+    char* w1 = wg.work[1];
+    Q.n_items = (uint32_t)n_items;
+    Q.item_tile = (uint32_t*)(w1 + o_it);
+    Q.item_wsrc = (uint32_t*)(w1 + o_ws);
+    Q.item_msrc = (uint32_t*)(w1 + o_ms);
+    Q.wbase = (uint32_t*)(w1 + o_wb);
+    Q.mbase = (uint32_t*)(w1 + o_mb);
+    Q.blk = (unsigned long long*)(w1 + o_blk1);
+    HIP_TRY(osmt_launch_tq_columns(Q, st));
+    HIP_TRY(hipMemcpyAsync(tq_tot, Q.tot, OSMT_TQ_OVER_CAND * 8 + 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tq_tot[OSMT_TQ_OVER_CAND] != ~0ull) {
+        const size_t t = (size_t)tq_tot[OSMT_TQ_OVER_CAND];
+        uint32_t base[4];
+        HIP_TRY(hipMemcpyAsync(base, Q.t_wbase + t, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(base + 2, Q.t_mbase + t, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t nw = base[1] - base[0], nm = base[3] - base[2];
+        return fail(OSMT_UNSUPPORTED, "tile %zu gathers %u %s references (> OSMT_QUERY_MAX_TILE_CANDIDATES = %u)", t,
+                    nw > OSMT_QUERY_MAX_TILE_CANDIDATES ? nw : nm, nw > OSMT_QUERY_MAX_TILE_CANDIDATES ? "way" : "multipolygon",
+                    OSMT_QUERY_MAX_TILE_CANDIDATES);
+    }
+    if (tq_tot[OSMT_TQ_WAYS] + tq_tot[OSMT_TQ_MPS] >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "area labels: the batch gathers %llu references (> 2^32): split the batch", tq_tot[OSMT_TQ_WAYS] + tq_tot[OSMT_TQ_MPS]);
+    const size_t n_cand = (size_t)(tq_tot[OSMT_TQ_WAYS] + tq_tot[OSMT_TQ_MPS]);
+    off = 0;
+    const size_t o_cand = carve(n_cand * 4), o_apos = carve((n_cand + 1) * 4), o_need = carve((n_cand + 1) * 4), o_ov = carve(n_cand * 4);
+    const size_t o_blk2 = carve((n_cand / 256 + 1) * 8);
+    rc = alloc(&wg.work[2], "candidates");
+    if (rc != OSMT_OK) return rc;
+    char* w2 = wg.work[2];
+    Q.n_ways = (uint32_t)tq_tot[OSMT_TQ_WAYS];
+    Q.n_mps = (uint32_t)tq_tot[OSMT_TQ_MPS];
+    Q.cand = (uint32_t*)(w2 + o_cand);
+    Q.apos = (uint32_t*)(w2 + o_apos);
+    Q.blk = (unsigned long long*)(w2 + o_blk2);
+    HIP_TRY(osmt_launch_tq_gather(Q, st));
+    HIP_TRY(osmt_launch_tq_sort(Q, st));
+    HIP_TRY(osmt_launch_tq_mark(Q, st)); /* with the label bindings' offsets: apos counts labels, tile_base is job_label_off */
+    HIP_TRY(mark(EV_Q1));
+    HIP_TRY(hipMemcpyAsync(tq_tot + OSMT_TQ_AREAS, Q.tot + OSMT_TQ_AREAS, 3 * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tq_tot[OSMT_TQ_OVER_AREAS] != ~0ull) {
+        const size_t t = (size_t)tq_tot[OSMT_TQ_OVER_AREAS];
+        osmt_styled_tile tl;
+        HIP_TRY(hipMemcpyAsync(&tl, Q.tiles + t, sizeof tl, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return fail(OSMT_UNSUPPORTED, "tile %zu: %u area labels (> OSMT_TILE_LABELS_MAX = %u)", t, tl.n_areas, OSMT_TILE_LABELS_MAX);
+    }
+    if (tq_tot[OSMT_TQ_AREAS] >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "area labels: the batch has %llu area labels (> 2^32): split the batch", tq_tot[OSMT_TQ_AREAS]);
+    const size_t n_labels = (size_t)tq_tot[OSMT_TQ_AREAS];
+    /* 2. expand: keys, element tables, the pairs that are searched */
+    off = 0;
+    const size_t o_keys = carve(n_labels * 16), o_eb = carve(n_labels * 4), o_es = carve(n_labels * 4), o_cp = carve((n_labels + 1) * 4);
+    const size_t o_cs = carve(n_labels * 4), o_pp = carve((n_labels + 1) * 4), o_ps = carve(n_labels * 4), o_blk3 = carve((n_labels / 256 + 1) * 8);
+    const size_t o_lab = carve(n_labels * sizeof(osmt_label)), o_run = carve(n_labels * sizeof(osmt_string_run));
+    rc = alloc(&wg.work[3], "labels");
+    if (rc != OSMT_OK) return rc;
+    char* w3 = wg.work[3];
+    P.geo = geo.dev;
+    P.q = Q.q;
+    P.bind = (const osmt_al_bind_dev*)(w0 + o_bind);
+    P.styles = d_styles;
+    P.style_rank = d_rank;
+    P.icon_h = (const uint32_t*)(w0 + o_ih);
+    P.anchors = (const osmt_area_anchor*)(w0 + o_an);
+    P.n_tiles = (uint32_t)n_tiles;
+    P.n_cand = (uint32_t)n_cand;
+    P.n_labels = (uint32_t)n_labels;
+    P.n_anchors = (uint32_t)n_anchors;
+    P.scale = sc->scale;
+    P.t_wbase = Q.t_wbase, P.t_mbase = Q.t_mbase;
+    P.cand = Q.cand;
+    P.apos = Q.apos;
+    P.job_label_off = Q.tile_base;
+    P.need = (uint32_t*)(w2 + o_need);
+    P.ov = (uint32_t*)(w2 + o_ov);
+    P.keys = (ulonglong2*)(w3 + o_keys);
+    P.el_bind = (uint32_t*)(w3 + o_eb);
+    P.el_slot = (uint32_t*)(w3 + o_es);
+    P.chpos = (uint32_t*)(w3 + o_cp);
+    P.ch_src = (uint32_t*)(w3 + o_cs);
+    P.ptpos = (uint32_t*)(w3 + o_pp);
+    P.pt_src = (uint32_t*)(w3 + o_ps);
+    P.labels = (osmt_label*)(w3 + o_lab);
+    P.runs = (osmt_string_run*)(w3 + o_run);
+    P.tot = Q.tot + OSMT_TQ_N;
+    P.blk = (unsigned long long*)(w2 + o_blk2);
+    HIP_TRY(mark(EV_X0));
+    HIP_TRY(osmt_launch_al_expand(P, st));
+    {
+        osmt_tl_pass S;
+        memset(&S, 0, sizeof S);
+        S.keys = P.keys, S.job_label_off = Q.tile_base, S.n_tiles = (uint32_t)n_tiles;
+        if (n_labels) HIP_TRY(osmt_launch_tl_sort(S, st));
+    }
+    HIP_TRY(mark(EV_X1));
+    HIP_TRY(hipMemcpyAsync(j->stage, P.tot, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(al_tot, j->stage, 8);
+    const size_t n_req = (size_t)al_tot[OSMT_AL_REQS]; /* at most one per candidate: fits */
+    /* 3. anchors: the requests stay on the device; only the totals that size the pools come back */
+    uint32_t pl_cnt[4] = {0, 0, 0, 0};
+    const uint32_t* d_cnt = nullptr;
+    HIP_TRY(mark(EV_A0));
+    if (n_req) {
+        off = 0;
+        (void)carve(n_req * sizeof(osmt_label_tile_request));
+        rc = alloc(&wg.work[4], "anchor requests");
+        if (rc != OSMT_OK) return rc;
+        P.n_req = (uint32_t)n_req;
+        P.req = (osmt_label_tile_request*)wg.work[4];
+        HIP_TRY(osmt_launch_al_requests(P, st));
+        j->n = n_req;
+        osmt_label_tile_batch lb{};
+        lb.n_requests = n_req, lb.n_tiles = n_tiles, lb.geodata_id = sc->tq_geodata_id, lb.scale = sc->scale;
+        const size_t back_bytes = n_req * sizeof(osmt_label_position) + 16;
+        const uint32_t n_slots = (uint32_t)std::min<size_t>(n_req, OSMT_PL_MAX_SLOTS);
+        size_t o_keep = 0, o_over = 0, o_back = 0, o_wsp = 0;
+        auto search_bytes = [&](size_t n_rings) {
+            size_t o = 0;
+            auto take = [&](size_t bytes) {
+                const size_t at = o;
+                o = align_up(o + std::max<size_t>(bytes, 4), 256);
+                return at;
+            };
+            o_keep = take(n_rings * 4), o_over = take(n_req * 4), o_back = take(back_bytes);
+            o_wsp = take((size_t)n_slots * OSMT_PL_CELL_DOUBLES * OSMT_PL_GLOBAL_CELLS * sizeof(double));
+            return o;
+        };
+        osmt_an_pass ap{};
+        size_t x0 = 0;
+        rc = label_tiles_expand(ctx, &lb, geo, j, false, search_bytes, &x0, &ap, P.req, Q.q);
+        if (rc != OSMT_OK) return rc;
+        char* d = j->d_base + x0;
+        osmt_polylabel_args a{};
+        a.req = ap.pl_req;
+        a.n_req = (uint32_t)n_req;
+        a.rings = ap.rings;
+        a.n_rings = ap.n_rings;
+        a.pts = ap.pts;
+        a.keep = (uint32_t*)(d + o_keep);
+        a.over = (uint32_t*)(d + o_over);
+        a.out = (osmt_label_position*)(d + o_back);
+        a.cnt = (uint32_t*)(d + o_back + n_req * sizeof(osmt_label_position));
+        a.ws = (double*)(d + o_wsp);
+        a.n_slots = n_slots;
+        HIP_TRY(osmt_launch_polylabel(a, st));
+        P.pos = a.out;
+        d_cnt = a.cnt;
+    }
+    HIP_TRY(mark(EV_A1));
+    /* 4. what every sorted label holds: chars and way points */
+    P.blk = (unsigned long long*)(w3 + o_blk3);
+    HIP_TRY(mark(EV_C0));
+    HIP_TRY(osmt_launch_al_count(P, st));
+    HIP_TRY(mark(EV_C1));
+    HIP_TRY(hipMemcpyAsync(j->stage, P.tot, OSMT_AL_N * 8, hipMemcpyDeviceToHost, st));
+    if (d_cnt) HIP_TRY(hipMemcpyAsync(j->stage + 64, d_cnt, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(al_tot, j->stage, sizeof al_tot);
+    if (d_cnt) memcpy(pl_cnt, j->stage + 64, sizeof pl_cnt);
+    if (pl_cnt[3]) return fail(OSMT_HIP_ERROR, "area labels: internal error %u of the anchor search (a bounded loop of the kernel passed its bound)", pl_cnt[3]);
+    {
+        std::lock_guard<std::mutex> lk(ctx->cache_mu);
+        ctx->pl_stats[0] = n_req, ctx->pl_stats[1] = pl_cnt[0], ctx->pl_stats[2] = pl_cnt[2];
+    }
+    if (al_tot[OSMT_AL_DECLINED]) {
+        std::vector<osmt_label_tile_request> rq(n_req);
+        std::vector<osmt_label_position> ps(n_req);
+        HIP_TRY(hipMemcpyAsync(rq.data(), P.req, n_req * sizeof(osmt_label_tile_request), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ps.data(), P.pos, n_req * sizeof(osmt_label_position), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t i = 0; i < n_req; ++i) /* requests are in (tile, way before multipolygon, id) order: ascending by (tile, entity) */
+            if (ps[i].status == OSMT_LABEL_TOO_LARGE) sc->h_al_declined.push_back(osmt_area_anchor{rq[i].tile, rq[i].entity, 0.0, 0.0, OSMT_LABEL_TOO_LARGE, 0u});
+        const osmt_area_anchor& f = sc->h_al_declined.front();
+        return fail(OSMT_UNSUPPORTED,
+                    "area labels: the anchor search declined %zu (tile, entity) pairs as too large (OSMT_LABEL_MAX_CELLS = %u), the first is tile %u, %s %u: "
+                    "read them with osmt_scene_read_declined_anchors, compute them on the host and hand them in as anchors",
+                    sc->h_al_declined.size(), OSMT_LABEL_MAX_CELLS, f.tile, (f.entity & OSMT_STYLED_MULTIPOLYGON) ? "multipolygon" : "way",
+                    f.entity & ~OSMT_STYLED_MULTIPOLYGON);
+    }
+    if (al_tot[OSMT_AL_CHARS] >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "area labels: the batch has %llu chars of label text (> 2^32): split the batch", al_tot[OSMT_AL_CHARS]);
+    if (al_tot[OSMT_AL_PTS] >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "area labels: the batch has %llu way points of text along ways (> 2^32): split the batch", al_tot[OSMT_AL_PTS]);
+    const size_t n_chars = (size_t)al_tot[OSMT_AL_CHARS], n_pts = (size_t)al_tot[OSMT_AL_PTS];
+    /* 5. way points, records, chars */
+    off = 0;
+    const size_t o_ch = carve(n_chars * 4), o_pf = carve(n_pts * 8), o_pt = carve(n_pts * 8);
+    rc = alloc(&wg.work[5], "chars and way points");
+    if (rc != OSMT_OK) return rc;
+    char* w5 = wg.work[5];
+    P.n_chars = (uint32_t)n_chars;
+    P.n_pts = (uint32_t)n_pts;
+    P.chars = (uint32_t*)(w5 + o_ch);
+    P.pts_fwd = (int2*)(w5 + o_pf);
+    P.pts = (int2*)(w5 + o_pt);
+    HIP_TRY(mark(EV_E0));
+    HIP_TRY(osmt_launch_al_emit(P, st));
+    HIP_TRY(mark(EV_E1));
+    out->labels.resize(n_labels), out->runs.resize(n_labels), out->chars.resize(n_chars), out->pts.resize(2 * n_pts);
+    if (n_labels) HIP_TRY(hipMemcpyAsync(out->labels.data(), P.labels, n_labels * sizeof(osmt_label), hipMemcpyDeviceToHost, st));
+    if (n_labels) HIP_TRY(hipMemcpyAsync(out->runs.data(), P.runs, n_labels * sizeof(osmt_string_run), hipMemcpyDeviceToHost, st));
+    if (n_chars) HIP_TRY(hipMemcpyAsync(out->chars.data(), P.chars, n_chars * 4, hipMemcpyDeviceToHost, st));
+    if (n_pts) HIP_TRY(hipMemcpyAsync(out->pts.data(), P.pts, n_pts * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out->job_off.data(), P.job_label_off, (n_tiles + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    /* 6. the angles: libm, on the host */
+    const auto t0 = std::chrono::steady_clock::now();
+    area_label_angles(out->labels, out->runs, out->pts, &out->sincos);
+    if (trace) {
+        const double angle_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        auto us = [&](int a, int b2) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
+            return ms * 1e3;
+        };
+        fprintf(stderr,
+                "osmt area labels: query %.1f us, expand + sort %.1f us, anchors %.1f us, count + scans %.1f us, emit %.1f us, host angles %.1f us "
+                "(%zu tiles, %zu candidates, %zu labels, %zu anchor requests, %zu chars, %zu way points, %zu bytes read back)\n",
+                us(EV_Q0, EV_Q1), us(EV_X0, EV_X1), us(EV_A0, EV_A1), us(EV_C0, EV_C1), us(EV_E0, EV_E1), angle_us, n_tiles, n_cand, n_labels, n_req, n_chars,
+                n_pts, n_labels * (sizeof(osmt_label) + sizeof(osmt_string_run)) + n_chars * 4 + n_pts * 8 + (n_tiles + 1) * 4);
+    }
+    return OSMT_OK;
+}
+
+static int scene_build_tile_labels_all_body(osmt_ctx* ctx, osmt_scene* sc, const uint32_t* area_of_zoom, const uint32_t* node_of_zoom,
+                                            const osmt_area_anchor* anchors, size_t n_anchors) {
+    if (!ctx || !sc || sc->ctx != ctx) return fail(OSMT_INVALID_ARG, "bad ctx/scene");
+    if (!sc->d_tq) return fail(OSMT_INVALID_ARG, "the scene was not built by osmt_scene_build_tiles: it has no tiles to query");
+    sc->h_al_declined.clear();
+    const size_t n_tiles = sc->n_jobs;
+    area_label_batch ab;
+    ab.job_off.assign(n_tiles + 1, 0u);
+    if (area_of_zoom) {
+        const int rc = tile_area_labels_build(ctx, sc, area_of_zoom, anchors, n_anchors, &ab);
+        if (rc != OSMT_OK) return rc;
+    }
+    osmt_string_label_batch area{};
+    area.labels = ab.labels.data(), area.n_labels = ab.labels.size(), area.job_label_off = ab.job_off.data(), area.runs = ab.runs.data();
+    area.chars = ab.chars.data(), area.n_chars = ab.chars.size();
+    area.way_pts = ab.pts.data(), area.way_sincos = ab.sincos.data(), area.n_way_pts = ab.pts.size() / 2;
+    node_label_batch nb;
+    nb.job_off.assign(n_tiles + 1, 0u);
+    if (node_of_zoom) {
+        const int rc = tile_node_labels_build(ctx, sc, node_of_zoom, &area, &nb);
+        if (rc != OSMT_OK) return rc;
+    }
+    const int rc = tile_labels_attach(ctx, sc, &area, &nb);
+    if (rc != OSMT_OK) return rc;
+    sc->h_al_labels.swap(ab.labels);
+    sc->h_al_runs.swap(ab.runs);
+    sc->h_al_chars.swap(ab.chars);
+    sc->h_al_off.swap(ab.job_off);
+    sc->h_al_pts.swap(ab.pts);
+    sc->h_al_sincos.swap(ab.sincos);
+    return OSMT_OK;
+}
+
+static int scene_read_declined_anchors_body(osmt_ctx* ctx, osmt_scene* sc, osmt_area_anchor* out, size_t cap, size_t* n) {
+    if (!ctx || !sc || sc->ctx != ctx || !n) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *n = sc->h_al_declined.size();
+    if (!out) return OSMT_OK;
+    if (cap < *n) return fail(OSMT_INVALID_ARG, "out holds %zu anchors, the last build declined %zu", cap, *n);
+    if (*n) memcpy(out, sc->h_al_declined.data(), *n * sizeof(osmt_area_anchor));
+    return OSMT_OK;
+}
+
+static int scene_read_tile_area_labels_body(osmt_ctx* ctx, osmt_scene* sc, osmt_label* labels, osmt_string_run* runs, uint32_t* chars, int32_t* way_pts,
+                                            double* way_sincos, uint32_t* job_label_off, const size_t* caps, size_t* counts) {
+    if (!ctx || !sc || sc->ctx != ctx || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (sc->h_al_off.empty()) return fail(OSMT_INVALID_ARG, "the scene has no device-built area labels (osmt_scene_build_tile_labels_all)");
+    counts[0] = sc->h_al_labels.size(), counts[1] = sc->h_al_chars.size(), counts[2] = sc->h_al_pts.size() / 2;
+    if ((labels || runs || chars || way_pts || way_sincos) && !caps) return fail(OSMT_INVALID_ARG, "caps is NULL");
+    if ((labels || runs) && caps[0] < counts[0]) return fail(OSMT_INVALID_ARG, "caps[0] = %zu is less than the scene's %zu area labels", caps[0], counts[0]);
+    if (chars && caps[1] < counts[1]) return fail(OSMT_INVALID_ARG, "caps[1] = %zu is less than the scene's %zu chars", caps[1], counts[1]);
+    if ((way_pts || way_sincos) && caps[2] < counts[2]) return fail(OSMT_INVALID_ARG, "caps[2] = %zu is less than the scene's %zu way points", caps[2], counts[2]);
+    if (labels && counts[0]) memcpy(labels, sc->h_al_labels.data(), counts[0] * sizeof(osmt_label));
+    if (runs && counts[0]) memcpy(runs, sc->h_al_runs.data(), counts[0] * sizeof(osmt_string_run));
+    if (chars && counts[1]) memcpy(chars, sc->h_al_chars.data(), counts[1] * 4);
+    if (way_pts && counts[2]) memcpy(way_pts, sc->h_al_pts.data(), counts[2] * 8);
+    if (way_sincos && counts[2]) memcpy(way_sincos, sc->h_al_sincos.data(), counts[2] * 16);
+    if (job_label_off) memcpy(job_label_off, sc->h_al_off.data(), sc->h_al_off.size() * 4);
+    return OSMT_OK;
+}
+
+int osmt_validate_area_label_bindings(const osmt_area_label_bindings_desc* b, osmt_ctx* ctx) {
+    return guarded([&] { return validate_area_label_bindings(b, ctx, nullptr, nullptr); });
+}
+int osmt_register_area_label_bindings(osmt_ctx* ctx, const osmt_area_label_bindings_desc* b, uint32_t* out_bindings_id) {
+    return guarded([&] { return register_area_label_bindings_body(ctx, b, out_bindings_id); });
+}
+int osmt_scene_build_tile_labels_all(osmt_ctx* ctx, osmt_scene* scene, const uint32_t area_bindings_of_zoom[OSMT_MAX_ZOOM + 1],
+                                     const uint32_t node_bindings_of_zoom[OSMT_MAX_ZOOM + 1], const osmt_area_anchor* anchors, size_t n_anchors) {
+    return guarded([&] { return scene_build_tile_labels_all_body(ctx, scene, area_bindings_of_zoom, node_bindings_of_zoom, anchors, n_anchors); });
+}
+int osmt_scene_read_declined_anchors(osmt_ctx* ctx, osmt_scene* scene, osmt_area_anchor* out, size_t cap, size_t* n) {
+    return guarded([&] { return scene_read_declined_anchors_body(ctx, scene, out, cap, n); });
+}
+int osmt_scene_read_tile_area_labels(osmt_ctx* ctx, osmt_scene* scene, osmt_label* labels, osmt_string_run* runs, uint32_t* chars, int32_t* way_pts,
+                                     double* way_sincos, uint32_t* job_label_off, const size_t caps[3], size_t counts[3]) {
+    return guarded([&] { return scene_read_tile_area_labels_body(ctx, scene, labels, runs, chars, way_pts, way_sincos, job_label_off, caps, counts); });
 }
 
 int osmt_validate_node_mercator(const double* factors, size_t n_nodes, uint32_t geodata_id, osmt_ctx* ctx) {

@@ -622,6 +622,75 @@ hipError_t osmt_launch_an_count(const osmt_an_pass& a, hipStream_t st);
 /* k_an_rings + scan + k_an_records + k_an_points: pl_req, rings and pts */
 hipError_t osmt_launch_an_expand(const osmt_an_pass& a, hipStream_t st);
 
+/* ---- area labels of tile-built scenes (osmt_arealabels.hip) ------------------------------------------------------ */
+/* The query half is the k_tq_* stages over the way and multipolygon pools, up to and including osmt_launch_tq_mark with an
+ * osmt_tq_bind_dev whose offsets are the LABEL bindings' (mark and tiles read no style id): apos is then the first label of
+ * every candidate, tile_base the tiles' job_label_off, ways numbered in front of multipolygons. */
+/* k_tl_sort alone: reads a.keys, a.job_label_off and a.n_tiles only */
+hipError_t osmt_launch_tl_sort(const osmt_tl_pass& a, hipStream_t st);
+/* a registered area label bindings table */
+struct osmt_al_bind_dev {
+    const uint32_t *way_off, *mp_off;
+    const osmt_label_binding *way_bind, *mp_bind;
+    const uint32_t *text_off, *chars;
+};
+/* words of osmt_al_pass::tot */
+enum {
+    OSMT_AL_REQS = 0,       /* (tile, entity) pairs that need the anchor search */
+    OSMT_AL_CHARS,          /* chars of the batch */
+    OSMT_AL_PTS,            /* way points of the batch */
+    OSMT_AL_DECLINED,       /* requests answered OSMT_LABEL_TOO_LARGE */
+    OSMT_AL_FIRST_DECLINED, /* the first of them (none: all ones) */
+    OSMT_AL_N
+};
+#define OSMT_AL_NO_ANCHOR 3u /* beside OSMT_LABEL_*: the pair asked for no anchor */
+struct osmt_al_pass {
+    osmt_geo_dev geo;
+    const osmt_query_tile* q;     /* [n_tiles] */
+    const osmt_al_bind_dev* bind; /* [OSMT_MAX_ZOOM + 1] (zooms no tile has: never read) */
+    const osmt_label_style_rec* styles;
+    const uint32_t* style_rank;
+    const uint32_t* icon_h;
+    const osmt_area_anchor* anchors; /* [n_anchors] ascending by (tile, entity) */
+    uint32_t n_tiles, n_cand, n_labels, n_req, n_chars, n_pts, n_anchors, scale;
+    /* what the query left (osmt_tq_pass) */
+    const uint32_t *t_wbase, *t_mbase; /* [n_tiles + 1] */
+    const uint32_t* cand;              /* sorted per (tile, kind), a tile's ways in front of its multipolygons */
+    const uint32_t* apos;              /* [n_cand + 1] first label of the candidate in query numbering */
+    const uint32_t* job_label_off;     /* [n_tiles + 1] */
+    /* per candidate */
+    uint32_t* need; /* [n_cand + 1] 1: the pair is searched; then the exclusive scan: its request */
+    uint32_t* ov;   /* [n_cand] the pair's entry in `anchors`, or all ones */
+    /* per element, by position before the sort (multipolygons in front of ways) */
+    ulonglong2* keys;  /* rank:32 | gid:64 | position in the tile:32, sorted in place per tile */
+    uint32_t* el_bind; /* the binding: absolute index in its kind's pool */
+    uint32_t* el_slot; /* the candidate slot */
+    /* per sorted label */
+    uint32_t* chpos;  /* [n_labels + 1] chars, then their exclusive scan */
+    uint32_t* ch_src; /* [n_labels] */
+    uint32_t* ptpos;  /* [n_labels + 1] way points, then their exclusive scan */
+    uint32_t* pt_src; /* [n_labels] where in geo.idx the way's nodes start */
+    unsigned long long* blk;
+    unsigned long long* tot; /* [OSMT_AL_N] */
+    /* anchors */
+    osmt_label_tile_request* req;   /* [n_req] */
+    const osmt_label_position* pos; /* [n_req] what osmt_launch_polylabel wrote */
+    /* the batch */
+    osmt_label* labels;
+    osmt_string_run* runs;
+    uint32_t* chars;
+    int2* pts_fwd; /* [n_pts] the runs' points in the way's own order */
+    int2* pts;     /* [n_pts] in walking order */
+};
+/* zeroes tot, k_al_expand + the scan of `need`: keys, element tables, tot[REQS] */
+hipError_t osmt_launch_al_expand(const osmt_al_pass& a, hipStream_t st);
+/* k_al_requests: the osmt_label_tile_request records of the pairs that are searched */
+hipError_t osmt_launch_al_requests(const osmt_al_pass& a, hipStream_t st);
+/* k_al_declined (after the search) + k_al_count + two scans: tot[DECLINED, FIRST_DECLINED, CHARS, PTS]; the keys are sorted */
+hipError_t osmt_launch_al_count(const osmt_al_pass& a, hipStream_t st);
+/* k_al_project + k_al_waypts + k_al_emit + k_al_chars */
+hipError_t osmt_launch_al_emit(const osmt_al_pass& a, hipStream_t st);
+
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

@@ -212,6 +212,11 @@ hipError_t osmt_launch_tl_order(const osmt_tl_pass& a, hipStream_t st) {
     return osmt_tq_scan(a.chpos, a.n_labels, a.blk, a.tot + OSMT_TL_CHARS, st);
 }
 
+hipError_t osmt_launch_tl_sort(const osmt_tl_pass& a, hipStream_t st) {
+    if (a.n_tiles) hipLaunchKernelGGL(k_tl_sort, dim3(a.n_tiles), dim3(SORT_WG), 0, st, a);
+    return hipGetLastError();
+}
+
 hipError_t osmt_launch_tl_emit(const osmt_tl_pass& a, hipStream_t st) {
     if (a.n_labels) hipLaunchKernelGGL(k_tl_emit, grid_of(a.n_labels), dim3(WG), 0, st, a);
     if (a.n_chars) hipLaunchKernelGGL(k_tl_chars, grid_of(a.n_chars), dim3(WG), 0, st, a);

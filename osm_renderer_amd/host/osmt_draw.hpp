@@ -34,6 +34,7 @@
 #ifndef OSMT_DRAW_HPP
 #define OSMT_DRAW_HPP
 
+#include <algorithm>
 #include <cstdint>
 #include <cmath>
 #include <optional>
@@ -136,6 +137,11 @@ class Context {
         check(osmt_register_label_styles(ctx_, styles.data(), styles.size(), &first));
         return first;
     }
+    uint32_t register_area_label_bindings(const osmt_area_label_bindings_desc& desc) {
+        uint32_t id = 0;
+        check(osmt_register_area_label_bindings(ctx_, &desc, &id));
+        return id;
+    }
     uint32_t register_label_bindings(const osmt_label_bindings_desc& desc) {
         uint32_t id = 0;
         check(osmt_register_label_bindings(ctx_, &desc, &id));
@@ -168,6 +174,13 @@ struct TileLabels {
     std::vector<uint32_t> chars, job_label_off;
 };
 
+/* The area labels a TileScene built on the GPU, as read back: TileLabels plus the ways of the texts along a line — run l
+ * walks way_pts[runs[l].pt_off .. + n_pts) ([n][2], in walking order) with the angles way_sincos ([n][2]). */
+struct TileAreaLabels : TileLabels {
+    std::vector<int32_t> way_pts;
+    std::vector<double> way_sincos;
+};
+
 /* A scene built from tile coordinates (osmt_scene_build_tiles): 16 bytes per tile in, the scene StyledScene builds from the
  * same entities out.  build_tile_labels gives it the label pass of Drawer::draw_labels: the node labels are queried, ordered
  * and assembled on the GPU, the caller's way and multipolygon labels are drawn in front of them (drawer.rs:229-261). */
@@ -182,6 +195,45 @@ class TileScene {
     /* label_bindings_of_zoom[z]: id from Context::register_label_bindings, or OSMT_BINDINGS_NONE */
     void build_tile_labels(const uint32_t (&label_bindings_of_zoom)[OSMT_MAX_ZOOM + 1], const osmt_string_label_batch* area_labels = nullptr) {
         check(osmt_scene_build_tile_labels(ctx_->raw(), scene_, label_bindings_of_zoom, area_labels));
+    }
+    /* The whole label pass of Drawer::draw_labels from the GPU: the labels of ways and multipolygons (nullptr: none), then of
+     * nodes (nullptr: none).  Where the anchor search declines a pair as too large, host_anchor(tile index, entity) ->
+     * osmt_label_position computes it on this thread (osmt::HostAnchors of host/osmt_arealabels.hpp) and the build is repeated
+     * with the computed anchors; returns how many anchors the host computed. */
+    template <class HostAnchor>
+    size_t build_all_labels(const uint32_t* area_bindings_of_zoom, const uint32_t* node_bindings_of_zoom, HostAnchor host_anchor) {
+        std::vector<osmt_area_anchor> anchors;
+        for (;;) {
+            const int rc = osmt_scene_build_tile_labels_all(ctx_->raw(), scene_, area_bindings_of_zoom, node_bindings_of_zoom, anchors.data(), anchors.size());
+            if (rc == OSMT_OK) return anchors.size();
+            const std::string why = osmt_last_error();
+            size_t n = 0;
+            check(osmt_scene_read_declined_anchors(ctx_->raw(), scene_, nullptr, 0, &n));
+            if (rc != OSMT_UNSUPPORTED || n == 0) throw Error(rc, why);
+            std::vector<osmt_area_anchor> more(n);
+            check(osmt_scene_read_declined_anchors(ctx_->raw(), scene_, more.data(), n, &n));
+            for (osmt_area_anchor& a : more) {
+                const osmt_label_position p = host_anchor(a.tile, a.entity);
+                a.x = p.x, a.y = p.y, a.status = p.status;
+            }
+            /* a declined pair was not listed: the two lists are disjoint and each ascending */
+            std::vector<osmt_area_anchor> merged(anchors.size() + more.size());
+            std::merge(anchors.begin(), anchors.end(), more.begin(), more.end(), merged.begin(), [](const osmt_area_anchor& a, const osmt_area_anchor& b) {
+                return a.tile < b.tile || (a.tile == b.tile && a.entity < b.entity);
+            });
+            anchors.swap(merged);
+        }
+    }
+    /* the area batch the device built, before the splice */
+    TileAreaLabels read_tile_area_labels() const {
+        TileAreaLabels out;
+        size_t n[3] = {0, 0, 0};
+        check(osmt_scene_read_tile_area_labels(ctx_->raw(), scene_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n));
+        out.labels.resize(n[0]), out.runs.resize(n[0]), out.chars.resize(n[1]), out.way_pts.resize(2 * n[2]), out.way_sincos.resize(2 * n[2]);
+        out.job_label_off.resize(n_tiles_ + 1);
+        check(osmt_scene_read_tile_area_labels(ctx_->raw(), scene_, out.labels.data(), out.runs.data(), out.chars.data(), out.way_pts.data(),
+                                               out.way_sincos.data(), out.job_label_off.data(), n, n));
+        return out;
     }
     /* the node batch the device built, before the area labels were put in front */
     TileLabels read_tile_labels() const {

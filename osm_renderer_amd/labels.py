@@ -39,6 +39,8 @@ LABEL_POSITION_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("status", "<u4"), 
 LABEL_TILE_REQUEST_DTYPE = np.dtype([("entity", "<u4"), ("tile", "<u4")])  # osmt_label_tile_request (Context.label_positions_tiles)
 assert LABEL_REQUEST_DTYPE.itemsize == C.sizeof(abi.LabelRequest) == 16
 assert LABEL_TILE_REQUEST_DTYPE.itemsize == C.sizeof(abi.LabelTileRequest) == 8
+AREA_ANCHOR_DTYPE = np.dtype([("tile", "<u4"), ("entity", "<u4"), ("x", "<f8"), ("y", "<f8"), ("status", "<u4"), ("_pad", "<u4")])  # osmt_area_anchor
+assert AREA_ANCHOR_DTYPE.itemsize == C.sizeof(abi.AreaAnchor) == 32
 assert LABEL_POSITION_DTYPE.itemsize == C.sizeof(abi.LabelPosition) == 24
 
 _libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")

@@ -43,6 +43,8 @@ EXPORTS = [
     "osmt_validate_label_bindings", "osmt_register_label_bindings", "osmt_scene_build_tile_labels", "osmt_scene_read_tile_labels",
     "osmt_validate_node_mercator", "osmt_register_node_mercator", "osmt_validate_label_tile_batch", "osmt_label_positions_tiles",
     "osmt_label_positions_tiles_begin", "osmt_label_tile_batch_expand",
+    "osmt_validate_area_label_bindings", "osmt_register_area_label_bindings", "osmt_scene_build_tile_labels_all",
+    "osmt_scene_read_declined_anchors", "osmt_scene_read_tile_area_labels",
 ]
 
 
@@ -169,6 +171,15 @@ def load():
         L.osmt_register_label_bindings.argtypes = [vp, C.POINTER(abi.LabelBindingsDesc), C.POINTER(C.c_uint32)]
         L.osmt_scene_build_tile_labels.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(abi.StringLabelBatch)]
         L.osmt_scene_read_tile_labels.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    if hasattr(L, "osmt_scene_build_tile_labels_all"):  # absent only from older variant builds loaded through OSMT_LIB
+        for name in ("osmt_validate_area_label_bindings", "osmt_register_area_label_bindings", "osmt_scene_build_tile_labels_all",
+                     "osmt_scene_read_declined_anchors", "osmt_scene_read_tile_area_labels"):
+            getattr(L, name).restype = C.c_int
+        L.osmt_validate_area_label_bindings.argtypes = [C.POINTER(abi.AreaLabelBindingsDesc), vp]
+        L.osmt_register_area_label_bindings.argtypes = [vp, C.POINTER(abi.AreaLabelBindingsDesc), C.POINTER(C.c_uint32)]
+        L.osmt_scene_build_tile_labels_all.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, C.c_size_t]
+        L.osmt_scene_read_declined_anchors.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.osmt_scene_read_tile_area_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     if hasattr(L, "osmt_label_positions_tiles"):  # absent only from older variant builds loaded through OSMT_LIB
         L.osmt_validate_node_mercator.argtypes = [dp, C.c_size_t, C.c_uint32, vp]
         L.osmt_register_node_mercator.argtypes = [vp, C.c_uint32, dp]

@@ -106,6 +106,54 @@ class Scene:
         self.labels = node if area_labels is None else splice_string_labels(area_labels, node)
         return node
 
+    def build_tile_labels_all(self, area_bindings=None, node_bindings=None, anchors=None):
+        """osmt_scene_build_tile_labels_all: the labels of the ways and multipolygons of every tile, then of its nodes, built
+        on the GPU and attached as one string batch, areas in front.  area_bindings: {zoom: id from
+        Context.register_area_label_bindings} or None; node_bindings: {zoom: id from Context.register_label_bindings} or None;
+        anchors: a labels.AREA_ANCHOR_DTYPE array of anchors computed on the host for pairs an earlier call declined
+        (read_declined_anchors).  Returns (area batch, node batch) as labels.StringLabelList."""
+        from .labels import AREA_ANCHOR_DTYPE, splice_string_labels
+
+        def ids_of(b):
+            if b is None:
+                return None
+            return (C.c_uint32 * (abi.MAX_ZOOM + 1))(*[int(dict(b).get(z, abi.BINDINGS_NONE)) for z in range(abi.MAX_ZOOM + 1)])
+
+        n = 0
+        if anchors is not None:
+            anchors = np.ascontiguousarray(anchors, dtype=AREA_ANCHOR_DTYPE)
+            n = len(anchors)
+        check(load().osmt_scene_build_tile_labels_all(self.ctx._h, self._h, ids_of(area_bindings), ids_of(node_bindings),
+                                                      C.c_void_p(anchors.ctypes.data) if n else None, n))
+        area, node = self.read_tile_area_labels(), self.read_tile_labels()
+        self.labels = splice_string_labels(area, node) if len(area.labels) else node
+        return area, node
+
+    def read_declined_anchors(self):
+        """osmt_scene_read_declined_anchors: the (tile, entity) pairs the anchor search of the last build_tile_labels_all
+        declined, as a labels.AREA_ANCHOR_DTYPE array."""
+        from .labels import AREA_ANCHOR_DTYPE
+
+        L, n = load(), C.c_size_t()
+        check(L.osmt_scene_read_declined_anchors(self.ctx._h, self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, AREA_ANCHOR_DTYPE)
+        if n.value:
+            check(L.osmt_scene_read_declined_anchors(self.ctx._h, self._h, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+        return out
+
+    def read_tile_area_labels(self):
+        """osmt_scene_read_tile_area_labels: the area batch the device built, before the splice, as a labels.StringLabelList."""
+        from .labels import LABEL_DTYPE, STRING_RUN_DTYPE, StringLabelList
+
+        L, n = load(), (C.c_size_t * 3)()
+        check(L.osmt_scene_read_tile_area_labels(self.ctx._h, self._h, None, None, None, None, None, None, None, n))
+        lab, runs, chars = np.zeros(n[0], LABEL_DTYPE), np.zeros(n[0], STRING_RUN_DTYPE), np.zeros(n[1], np.uint32)
+        pts, sincos, off = np.zeros((n[2], 2), np.int32), np.zeros((n[2], 2)), np.zeros(self.n_jobs + 1, np.uint32)
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+        caps = (C.c_size_t * 3)(n[0], n[1], n[2])
+        check(L.osmt_scene_read_tile_area_labels(self.ctx._h, self._h, ptr(lab), ptr(runs), ptr(chars), ptr(pts), ptr(sincos), ptr(off), caps, n))
+        return StringLabelList(lab, off, runs, chars, pts, sincos)
+
     def read_tile_labels(self):
         """osmt_scene_read_tile_labels: the node batch the device built, before the splice, as a labels.StringLabelList."""
         from .labels import LABEL_DTYPE, STRING_RUN_DTYPE, StringLabelList
@@ -410,6 +458,13 @@ class Context:
         st = np.ascontiguousarray(styles, dtype=LABEL_STYLE_REC_DTYPE)
         out = C.c_uint32()
         check(load().osmt_register_label_styles(self._h, st.ctypes.data_as(C.POINTER(abi.LabelStyleRec)) if len(st) else None, len(st), C.byref(out)))
+        return out.value
+
+    def register_area_label_bindings(self, bindings):
+        """osmt_register_area_label_bindings: appends a styled.AreaLabelBindings table; returns its id."""
+        d = bindings.as_desc()
+        out = C.c_uint32()
+        check(load().osmt_register_area_label_bindings(self._h, C.byref(d), C.byref(out)))
         return out.value
 
     def register_label_bindings(self, bindings):

@@ -213,3 +213,34 @@ class LabelBindings:
         d.text_off, d.n_texts = self.text_off.ctypes.data_as(u32), len(self.text_off) - 1
         d.chars, d.n_chars = self.chars.ctypes.data_as(u32), len(self.chars)
         return d
+
+
+class AreaLabelBindings:
+    """osmt_area_label_bindings_desc: per way and per multipolygon the (label style id, text id) pairs
+    Styler::style_entities pushes for it at zooms zoom_lo..zoom_hi, in push order.  way_bindings / multipolygon_bindings: one
+    list of (style, text id or None) per entity; texts: the pool, each a str or a list of code points."""
+
+    def __init__(self, geodata_id, zoom_lo, zoom_hi, way_bindings, multipolygon_bindings, texts=()):
+        self.geodata_id, self.zoom_lo, self.zoom_hi = int(geodata_id), int(zoom_lo), int(zoom_hi)
+
+        def csr(rows):
+            off = np.zeros(len(rows) + 1, dtype=np.uint32)
+            if len(rows):
+                off[1:] = np.cumsum([len(v) for v in rows])
+            flat = [(int(s), abi.TEXT_NONE if t is None else int(t)) for v in rows for s, t in v]
+            return off, np.array(flat, dtype=LABEL_BINDING_DTYPE).reshape(-1)
+
+        self.way_off, self.way_bindings = csr(way_bindings)
+        self.multipolygon_off, self.multipolygon_bindings = csr(multipolygon_bindings)
+        self.text_off, self.chars = _csr([[ord(c) for c in t] if isinstance(t, str) else list(t) for t in texts])
+
+    def as_desc(self):
+        u32, lb = C.POINTER(C.c_uint32), C.POINTER(abi.LabelBinding)
+        d = abi.AreaLabelBindingsDesc()
+        d.geodata_id, d.zoom_lo, d.zoom_hi = self.geodata_id, self.zoom_lo, self.zoom_hi
+        d.way_off, d.way_bindings, d.n_way_bindings = self.way_off.ctypes.data_as(u32), self.way_bindings.ctypes.data_as(lb), len(self.way_bindings)
+        d.multipolygon_off, d.multipolygon_bindings = self.multipolygon_off.ctypes.data_as(u32), self.multipolygon_bindings.ctypes.data_as(lb)
+        d.n_multipolygon_bindings = len(self.multipolygon_bindings)
+        d.text_off, d.n_texts = self.text_off.ctypes.data_as(u32), len(self.text_off) - 1
+        d.chars, d.n_chars = self.chars.ctypes.data_as(u32), len(self.chars)
+        return d

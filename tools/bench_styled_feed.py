@@ -32,6 +32,18 @@ osmt_scene_build_tiles:
 
 timed the same way, from the call to labels attached to the scene; the stages of (f) and the size of its read-back from
 OSMT_TRACE_UPLOAD=1 in a child run.  Output: profiles/tile_labels_bench.json.
+
+--area-labels runs a fourth pair on the world of (a) / (b), written with its z18 tile index, every closed way labelled with
+an icon and a centred name, every open way with a name along the line, and five multipolygons per tile with a centred name:
+
+  (g) the caller's way:  per tile the query, the style lookup and the pairs that need an anchor; one
+                         osmt_label_positions_tiles; per tile osmt::area_labels_of_entities (order, Point::from_node, records, way
+                         points, libm angles) on one thread (tools/area_labels_bench.cpp); then osmt_scene_build_tile_labels
+                         with the batch as area_labels
+  (h) the device labels: osmt_scene_build_tile_labels_all over the registered area label bindings
+
+timed the same way, from the call to labels attached; the stages of (h), the share of its host angle loop and the size of its
+read-back from OSMT_TRACE_UPLOAD=1 in a child run.  Output: profiles/area_labels_bench.json.
 """
 import argparse
 import ctypes as C
@@ -379,6 +391,161 @@ def tile_labels(args):
         sys.exit("the two label feeds disagree")
 
 
+def area_labels(args):
+    import time
+
+    import torch
+
+    from osm_renderer_amd import labels
+    from tests import _anchors as an
+    from tests import _tilelabels as tl
+    from tests import _tilequery as tq
+
+    rng = np.random.default_rng(7)
+    nodes, ways, tiles = make_world(args.tiles)
+    polygons, mps = [], []
+    for t, (_, _, _, ids) in enumerate(tiles):  # five multipolygons per tile over the outlines of its first closed ways
+        for k in range(5):
+            polygons.append(list(ways[ids[k]][1]))
+            mps.append((5 * 10**6 + len(mps), [len(polygons) - 1], {}))
+    tmp = tempfile.mkdtemp(prefix="area_labels_")
+    path = os.path.join(tmp, "world.bin")
+    refs = write_geodata(path, nodes, ways, polygons, mps, max_zoom_tile=tq.max_zoom_tile)
+    ctx = Context(0)
+    syn = labels.synth_glyph_table()
+    ctx.register_glyphs(syn)
+    ns = len(labels.SYNTH_GLYPHS)
+    shapes = [ns - 1] + [(g - 1) % (ns - 1) for g in range(1, 13)] + [ns - 1]
+    font = labels.FontTable([(0x20, 13)] + [(0x41 + i, 1 + i) for i in range(12)], [300] + [labels.SYNTH_GLYPHS[s][0] for s in shapes[1:]],
+                            [syn.first_id + s for s in shapes])
+    ctx.register_font(font)
+    icon = ctx.register_image(rng.integers(0, 256, size=(12, 12, 4)).astype(np.uint8))
+    geo = styled.Geodata([[n[1], n[2]] for n in nodes], [(w[0], w[1]) for w in ways], polygons, [(m[0], m[1]) for m in mps])
+    gid = ctx.register_geodata(geo)
+    keys = sorted(refs)
+    ctx.register_tile_index(gid, styled.TileIndex([(k, sorted(refs[k][1]), sorted(refs[k][2])) for k in keys]))
+    ctx.register_node_mercator(gid, an.mercator_factors(geo.nodes))
+    ctx.register_node_index(gid, styled.NodeIndex([n[0] for n in nodes], [[] for _ in keys]))
+    draw_bind = ctx.register_style_bindings(styled.StyleBindings(gid, 0, 18, [[] for _ in ways], [[] for _ in mps]))
+    rows = [dict(layer=1, icon=icon, font_size=9.0, font_id=font.font_id, text_color=(120, 0, 40), text_position=abi.LABEL_POSITION_CENTER),
+            dict(font_size=10.0, font_id=font.font_id), dict(z_index=2.0, font_size=11.0, font_id=font.font_id, text_color=(0, 60, 160))]
+    rec = tl.label_styles(rows)
+    first = ctx.register_label_styles(rec)
+    all_styles = np.concatenate([np.zeros(first, styled.LABEL_STYLE_REC_DTYPE), rec])
+    icon_h = np.array([0] * first + [12, 0, 0], dtype=np.uint32)
+    texts = ["".join(chr(0x41 + int(c)) for c in rng.integers(0, 12, int(n))) for n in rng.integers(4, 13, 64)]
+    closed = [len(w[1]) >= 2 and w[1][0] == w[1][-1] for w in ways]
+    wb = [[(first + (0 if c else 1), int(rng.integers(0, len(texts))))] for c in closed]
+    mb = [[(first + 2, int(rng.integers(0, len(texts))))] for _ in mps]
+    tab = styled.AreaLabelBindings(gid, 0, 18, wb, mb, texts)
+    abid = ctx.register_area_label_bindings(tab)
+    nbid = ctx.register_label_bindings(styled.LabelBindings(gid, 0, 18, [[] for _ in nodes], []))
+    qt = [(z, x, y) for z, x, y, _ in tiles]
+    scene = ctx.build_tiles(styled.TileBatch(gid, qt, {ZOOM: draw_bind}))
+    L = lib.load()
+    so = os.path.join(ROOT, "tests", "_build", "libarea_labels_bench.so")
+    src = os.path.join(ROOT, "tools", "area_labels_bench.cpp")
+    hdr = os.path.join(ROOT, "osm_renderer_amd", "host", "osmt_arealabels.hpp")
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in (src, hdr, lib.LIB_PATH)):
+        os.makedirs(os.path.dirname(so), exist_ok=True)
+        pkg = os.path.join(ROOT, "osm_renderer_amd")
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, src, "-L" + pkg, "-losmtile", "-Wl,-rpath," + pkg,
+                               "-Wl,-rpath-link,/opt/rocm/lib"])
+    N = C.CDLL(so)
+    vp, sz, u32p = C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)
+    N.alb_new.restype = vp
+    N.alb_new.argtypes = [C.c_char_p, C.c_uint32, u32p, vp, u32p, vp, sz, u32p, u32p, vp, u32p, sz]
+    N.alb_run.argtypes = [vp, vp, C.c_uint32, vp, sz, C.c_uint32, C.POINTER(C.c_double), C.POINTER(sz)]
+    N.alb_batch.argtypes = [vp, C.POINTER(abi.StringLabelBatch)]
+    N.alb_free.argtypes = [vp]
+    h = N.alb_new(path.encode(), gid, tab.way_off.ctypes.data_as(u32p), tab.way_bindings.ctypes.data, tab.multipolygon_off.ctypes.data_as(u32p),
+                  tab.multipolygon_bindings.ctypes.data, len(tab.text_off) - 1, tab.text_off.ctypes.data_as(u32p), tab.chars.ctypes.data_as(u32p),
+                  all_styles.ctypes.data, icon_h.ctypes.data_as(u32p), len(all_styles))
+    assert h
+    qtiles = np.zeros(len(qt), styled.QUERY_TILE_DTYPE)
+    qtiles["zoom"], qtiles["x"], qtiles["y"] = [t[0] for t in qt], [t[1] for t in qt], [t[2] for t in qt]
+    a_ids = (C.c_uint32 * (abi.MAX_ZOOM + 1))(*[abid if z == ZOOM else abi.BINDINGS_NONE for z in range(abi.MAX_ZOOM + 1)])
+    n_ids = (C.c_uint32 * (abi.MAX_ZOOM + 1))(*[nbid if z == ZOOM else abi.BINDINGS_NONE for z in range(abi.MAX_ZOOM + 1)])
+    sec, cnt = (C.c_double * 3)(), (sz * 4)()
+
+    def run(which):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if which == "g":
+            lib.check(N.alb_run(h, ctx._h, gid, qtiles.ctypes.data, len(qtiles), 1, sec, cnt))
+            sb = abi.StringLabelBatch()
+            N.alb_batch(h, C.byref(sb))
+            t1 = time.perf_counter()
+            lib.check(L.osmt_scene_build_tile_labels(ctx._h, scene._h, n_ids, C.byref(sb)))
+            return (sec[0], sec[1], sec[2], t1 - t0, time.perf_counter() - t0)
+        lib.check(L.osmt_scene_build_tile_labels_all(ctx._h, scene._h, a_ids, n_ids, None, 0))
+        return (0.0, 0.0, 0.0, 0.0, time.perf_counter() - t0)
+
+    times = {"g": [], "h": []}
+    for rep in range(args.warmup + args.reps):
+        for which in ("g", "h") if rep % 2 == 0 else ("h", "g"):
+            t = run(which)
+            if rep >= args.warmup:
+                times[which].append(t)
+    if args.child:
+        return
+
+    def look(n_labels):
+        px = ctx.render(scene).cpu().numpy()
+        st = np.zeros(n_labels, np.uint8)
+        lib.check(L.osmt_scene_read_label_status(ctx._h, scene._h, st.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return px, st
+
+    run("g")
+    counts_g = [int(v) for v in cnt]
+    px_g, st_g = look(counts_g[0])
+    run("h")
+    got = scene.read_tile_area_labels()
+    px_h, st_h = look(len(got.labels))
+    same_px = bool(np.array_equal(px_g, px_h) and np.array_equal(st_g, st_h))
+    same_counts = counts_g[:3] == [len(got.labels), len(got.chars), len(got.way_pts)]
+
+    def stat(rows, k):
+        v = np.array([row[k] for row in rows])
+        return {"median_ms": float(np.median(v) * 1e3), "min_ms": float(v.min() * 1e3), "max_ms": float(v.max() * 1e3),
+                "p25_ms": float(np.percentile(v, 25) * 1e3), "p75_ms": float(np.percentile(v, 75) * 1e3), "runs": len(v)}
+
+    env = dict(os.environ, OSMT_TRACE_UPLOAD="1")
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--area-labels", "--tiles", str(args.tiles), "--reps", str(args.reps), "--warmup",
+                        str(args.warmup), "--child"], env=env, capture_output=True, text=True, timeout=900)
+    names = ("query", "expand_sort", "anchors", "count_scans", "emit", "host_angles")
+    rows = re.findall(r"osmt area labels: query ([0-9.]+) us, expand \+ sort ([0-9.]+) us, anchors ([0-9.]+) us, count \+ scans ([0-9.]+) us, emit ([0-9.]+) us, "
+                      r"host angles ([0-9.]+) us .*?, (\d+) anchor requests, .*?, (\d+) bytes read back", p.stderr)
+    if p.returncode != 0 or len(rows) <= args.warmup:
+        raise RuntimeError("the traced child run failed:\n" + p.stderr[-2000:])
+    rows = np.array(rows[args.warmup:], dtype=np.float64)
+    g_all, h_all = np.array([t[4] for t in times["g"]]), np.array([t[4] for t in times["h"]])
+    kernels_us = float(np.median(rows[:, :5].sum(axis=1)))
+    res = {
+        "workload": {"tiles": len(qt), "zoom": ZOOM, "ways": len(ways), "multipolygons": len(mps), "index_tiles": len(keys), "labels": len(got.labels),
+                     "chars": len(got.chars), "way_points": len(got.way_pts), "anchor_requests": int(rows[-1, 6]), "labels_placed": int(st_h.sum())},
+        "caller_g": {"query_and_requests": stat(times["g"], 0), "osmt_label_positions_tiles": stat(times["g"], 1), "records": stat(times["g"], 2),
+                     "batch_built": stat(times["g"], 3), "labels_attached": stat(times["g"], 4)},
+        "device_h": {"labels_attached": stat(times["h"], 4)},
+        "speedup_median_g_over_h": float(np.median(g_all) / np.median(h_all)),
+        "device_path_is_faster": bool(h_all.max() < g_all.min()),
+        "caller_path_is_faster": bool(g_all.max() < h_all.min()),
+        "device_stages_h_us_median": dict({k: float(np.median(rows[:, i])) for i, k in enumerate(names)}, kernels_total=kernels_us, runs=int(len(rows))),
+        "share_of_h": {"new_kernels_and_query": kernels_us * 1e-6 / float(np.median(h_all)), "host_angle_loop": float(np.median(rows[:, 5])) * 1e-6 / float(np.median(h_all))},
+        "read_back_bytes_h": int(rows[-1, 7]),
+        "same_label_chars_and_way_point_counts": bool(same_counts),
+        "same_pixels_and_statuses": same_px,
+        "note": "(g) projects with the host's libm, (h) on the device: a rounding tie may move a way point by one; pixels and statuses are compared",
+    }
+    text = json.dumps(res, indent=1)
+    print(text)
+    out = os.path.join(os.path.dirname(args.out), "area_labels_bench.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text + "\n")
+    N.alb_free(h)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=1024)
@@ -388,12 +555,15 @@ def main():
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--tiles-only", action="store_true", help="the tile-query pair (c) / (d) instead of (a) / (b)")
     ap.add_argument("--labels", action="store_true", help="the node-label pair (e) / (f) instead of (a) / (b)")
+    ap.add_argument("--area-labels", action="store_true", help="the area-label pair (g) / (h) instead of (a) / (b)")
     args = ap.parse_args()
     assert args.reps >= 10 or args.child
     if args.tiles_only:
         return tiles_only(args)
     if args.labels:
         return tile_labels(args)
+    if args.area_labels:
+        return area_labels(args)
 
     L = _native()
     rng = np.random.default_rng(1)
