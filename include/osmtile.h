@@ -1007,6 +1007,140 @@ int osmt_scene_read_declined_anchors(osmt_ctx* ctx, osmt_scene* scene, osmt_area
 int osmt_scene_read_tile_area_labels(osmt_ctx* ctx, osmt_scene* scene, osmt_label* labels, osmt_string_run* runs, uint32_t* chars,
                                      int32_t* way_pts, double* way_sincos, uint32_t* job_label_off, const size_t caps[3], size_t counts[3]);
 
+/* ---- style bindings from tags: MapCSS selector matching on the GPU ------------------------------------------------ */
+/* Rule matching (Styler::style_area -> area_matches -> matches_by_tags, mapcss/styler.rs:205-242,450-520) for every entity
+ * of a registered geodata file at once: which selectors of a registered selector set match each node, way and
+ * multipolygon (zoom left aside), and the entities' CLASSES.  A class is what the reference's style cache keys on
+ * (mapcss/style_cache.rs) plus what property_map_to_style reads of the entity: (cache slot, tags["layer"].parse::<i64>(),
+ * the matched selector ids ascending).  Entities of one class get the same styles at every zoom, so the caller cascades
+ * once per class and zoom and registers the result with osmt_register_style_bindings_matched.  Parsing MapCSS, the cascade
+ * and property_map_to_style stay with the caller; DESIGN.md 3.13 has the stages and the arguments. */
+
+#define OSMT_MATCH_MAX_SELECTORS 16384u    /* selectors of one set */
+#define OSMT_MATCH_MAX_SELECTOR_TESTS 16u  /* tests of one selector */
+
+/* the tags of a geodata file as the file has them (reader.rs:339-398): per kind a CSR over (k_off, k_len, v_off, v_len)
+ * quadruples into one string pool */
+typedef struct osmt_tags_desc {
+    const uint32_t* node_tag_off; /* [n_nodes + 1] into node_tags (in quadruples) */
+    const uint32_t* node_tags;    /* [n_node_tags][4] */
+    size_t n_nodes, n_node_tags;
+    const uint32_t* way_tag_off; /* [n_ways + 1] */
+    const uint32_t* way_tags;
+    size_t n_ways, n_way_tags;
+    const uint32_t* multipolygon_tag_off; /* [n_multipolygons + 1] */
+    const uint32_t* multipolygon_tags;
+    size_t n_multipolygons, n_multipolygon_tags;
+    const uint8_t* strings;
+    size_t n_string_bytes;
+} osmt_tags_desc;
+
+enum { OSMT_SEL_NODE = 0, OSMT_SEL_WAY = 1, OSMT_SEL_AREA = 2, OSMT_SEL_OTHER = 3 }; /* OTHER: All, Canvas, Meta — matches nothing */
+enum {
+    OSMT_TEST_EXISTS = 0,
+    OSMT_TEST_NOT_EXISTS,
+    OSMT_TEST_TRUE,
+    OSMT_TEST_FALSE,
+    OSMT_TEST_EQUAL,
+    OSMT_TEST_NOT_EQUAL,
+    OSMT_TEST_LESS,
+    OSMT_TEST_LESS_OR_EQUAL,
+    OSMT_TEST_GREATER,
+    OSMT_TEST_GREATER_OR_EQUAL,
+    OSMT_TEST_KINDS
+};
+typedef struct osmt_selector_test { /* 32 bytes */
+    uint32_t kind;                 /* OSMT_TEST_* */
+    uint32_t key_off, key_len;     /* the tag name, in the descriptor's string pool */
+    uint32_t value_off, value_len; /* EQUAL / NOT_EQUAL: the value; 0, 0 otherwise */
+    uint32_t _pad;
+    double value;                  /* the four numeric kinds: the right-hand side; 0 otherwise */
+} osmt_selector_test;
+typedef struct osmt_selector_rec { /* 16 bytes */
+    uint8_t object_type;           /* OSMT_SEL_* */
+    uint8_t has_min_zoom, min_zoom, has_max_zoom, max_zoom, _pad[3]; /* carried for the caller (osmt::selectors_at_zoom); the device ignores zoom */
+    uint32_t test_off, n_tests;    /* into tests */
+} osmt_selector_rec;
+/* selectors in stylesheet order: rule by rule, selector by selector */
+typedef struct osmt_selectors_desc {
+    const osmt_selector_rec* selectors;
+    size_t n_selectors;
+    const osmt_selector_test* tests;
+    size_t n_tests;
+    const uint8_t* strings;
+    size_t n_string_bytes;
+} osmt_selectors_desc;
+
+typedef struct osmt_match osmt_match;
+typedef struct osmt_number_override { /* 24 bytes: str::parse::<f64> of the tag value strings[v_off .. v_off + v_len) */
+    uint32_t v_off, v_len;
+    uint32_t has_value, _pad; /* 0: the parse is an error */
+    double value;
+} osmt_number_override;
+typedef struct osmt_declined_number { /* 8 bytes */
+    uint32_t v_off, v_len;
+} osmt_declined_number;
+typedef struct osmt_match_class { /* 24 bytes */
+    int64_t layer;                 /* 0 without */
+    uint32_t sel_off, n_sels;      /* into the pooled selector ids, ascending */
+    uint32_t first_entity;         /* the lowest-numbered member; entities are numbered nodes, then ways, then multipolygons */
+    uint8_t slot, has_layer, _pad[2]; /* slot: 0 node, 1 closed way, 2 open way, 3 multipolygon (styler.rs:559-579) */
+} osmt_match_class;
+
+/* The checks osmt_register_tags runs first, without a device.  OSMT_INVALID_ARG, naming the offender: NULL with a non-zero
+ * count; offsets that do not start at 0, decrease or do not end at the pool length; a key or value range outside the string
+ * pool; an entity whose keys are not STRICTLY ascending as unsigned bytes (the saver writes a BTreeMap; under that
+ * condition the bisection of Tags::get_by_key, reader.rs:351-373, equals any correct lookup); with a context, a geodata id
+ * that is unknown or entity counts that are not the registered file's (a NULL `ctx` skips these two).  OSMT_UNSUPPORTED:
+ * tags or string bytes beyond 32-bit indices. */
+int osmt_validate_tags(const osmt_tags_desc* tags, uint32_t geodata_id, osmt_ctx* ctx);
+/* Uploads the tags of a registered geodata file: one allocation that lives as long as the context.  One per geodata id: a
+ * second registration is OSMT_INVALID_ARG. */
+int osmt_register_tags(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tags_desc* tags);
+/* The checks osmt_register_selectors runs first, without a device.  OSMT_INVALID_ARG: NULL with a non-zero count, an object
+ * type or test kind outside the enums, a test range outside `tests`, a string range outside the pool, a zoom flag that is
+ * not 0 or 1.  OSMT_UNSUPPORTED with the figure: more than OSMT_MATCH_MAX_SELECTORS selectors, a selector with more than
+ * OSMT_MATCH_MAX_SELECTOR_TESTS tests. */
+int osmt_validate_selectors(const osmt_selectors_desc* selectors);
+/* Appends a selector set (append-only, the snapshot rules of styles and bindings: a set's device copy never moves).  At
+ * registration the distinct test keys are sorted byte-wise and numbered, and per key the distinct EQUAL / NOT_EQUAL values. */
+int osmt_register_selectors(osmt_ctx* ctx, const osmt_selectors_desc* selectors, uint32_t* out_selectors_id);
+/* Runs the match on the device (csrc/osmt_selmatch.hip).  `ov` (n_ov entries, STRICTLY ascending by (v_off, v_len), ranges
+ * inside the tags' string pool, has_value 0 or 1; anything else is OSMT_INVALID_ARG) lists tag values whose f64 the caller
+ * supplies: a listed value is not parsed on the device.
+ * Numbers are exact or declined, never guessed.  A tag value is parsed as f64 only where a numeric test names its key.  The
+ * device accepts the grammar of str::parse::<f64> and converts when the conversion is exact by construction: inf, infinity,
+ * nan, zero significands; otherwise the digits without leading zeros and trailing zeros form an integer w <= 2^53
+ * and the decimal exponent e left over has |e| <= 22, so the value is RN(w * 10^e) or RN(w / 10^-e) — one
+ * correctly rounded operation on two exact doubles.  A grammar error is an error (every comparison false), not a decline.
+ * Every other value is DECLINED: the call returns OSMT_UNSUPPORTED naming how many distinct (v_off, v_len) were declined and
+ * the first, and *out is a match that answers only osmt_match_read_declined_numbers and osmt_match_free.  The caller
+ * computes those values (osmt::HostNumbers, host/osmt_selmatch.hpp) and calls again with them as `ov`.
+ * tags["layer"] is parsed as i64 in full (sign, leading zeros, overflow = error) and is never declined.
+ * OSMT_INVALID_ARG: unknown ids, a geodata id without tags.  *out is NULL on every other error. */
+int osmt_match_selectors(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_id, const osmt_number_override* ov, size_t n_ov,
+                         osmt_match** out);
+void osmt_match_free(osmt_match* match);
+/* The distinct declined tag values, ascending by (v_off, v_len); none for a complete match.  *n is always set; out may be
+ * NULL to ask for the size; cap < *n with a non-NULL out is OSMT_INVALID_ARG. */
+int osmt_match_read_declined_numbers(osmt_match* match, osmt_declined_number* out, size_t cap, size_t* n);
+/* The result of a complete match (a declined one is OSMT_INVALID_ARG).  counts = { entities, classes, pooled selector ids }
+ * is always set; NULL outputs ask for sizes; caps bound what is written (a smaller cap with a non-NULL output is
+ * OSMT_INVALID_ARG).  entity_class: the class of every node, then way, then multipolygon.  Class ids are a pure function of
+ * the input: classes are numbered by their lowest-numbered member.  An entity that matches nothing still has a class. */
+int osmt_match_read(osmt_match* match, uint32_t* entity_class, osmt_match_class* classes, uint32_t* class_selectors, const size_t caps[3],
+                    size_t counts[3]);
+/* Bindings per class: class_style_off[n + 1] / class_styles give every class its style ids in push order for zooms
+ * zoom_lo..zoom_hi; the device expands them over the ways and multipolygons (count, scan, emit) into a table of exactly
+ * the form osmt_register_style_bindings makes from the per-entity lists; the id serves osmt_tile_batch::bindings_of_zoom like
+ * any other.  OSMT_INVALID_ARG: a match of another context or a declined one, n that is not the class count, bad offsets,
+ * a style id that is not registered, a bad zoom range.  OSMT_UNSUPPORTED: more than 2^32 - 2 bindings of one kind. */
+int osmt_register_style_bindings_matched(osmt_ctx* ctx, osmt_match* match, uint8_t zoom_lo, uint8_t zoom_hi, const uint32_t* class_style_off,
+                                         const uint32_t* class_styles, size_t n, uint32_t* out_bindings_id);
+/* Test hook in the spirit of osmt_debug_hypot: the class table of later osmt_match_selectors calls of this context keeps only
+ * the low `bits` bits of the key hash (32 = all; 0 puts every key into one probe chain).  The result must not change. */
+int osmt_debug_match_hash_bits(osmt_ctx* ctx, uint32_t bits);
+
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */
 int osmt_project(osmt_ctx* ctx, const double* latlon, size_t n, uint8_t zoom, uint32_t tile_x, uint32_t tile_y,

@@ -514,3 +514,67 @@ class AreaAnchor(C.Structure):  # osmt_area_anchor
 
 assert C.sizeof(AreaLabelBindingsDesc) == 88
 assert C.sizeof(AreaAnchor) == 32
+
+
+# ---- selector matching (osmt_match_selectors) ----------------------------------------------------------------------
+MATCH_MAX_SELECTORS = 16384
+MATCH_MAX_SELECTOR_TESTS = 16
+SEL_NODE, SEL_WAY, SEL_AREA, SEL_OTHER = 0, 1, 2, 3
+(TEST_EXISTS, TEST_NOT_EXISTS, TEST_TRUE, TEST_FALSE, TEST_EQUAL, TEST_NOT_EQUAL, TEST_LESS, TEST_LESS_OR_EQUAL, TEST_GREATER,
+ TEST_GREATER_OR_EQUAL) = range(10)
+
+
+class TagsDesc(C.Structure):
+    _fields_ = [
+        ("node_tag_off", C.POINTER(C.c_uint32)),
+        ("node_tags", C.POINTER(C.c_uint32)),
+        ("n_nodes", C.c_size_t),
+        ("n_node_tags", C.c_size_t),
+        ("way_tag_off", C.POINTER(C.c_uint32)),
+        ("way_tags", C.POINTER(C.c_uint32)),
+        ("n_ways", C.c_size_t),
+        ("n_way_tags", C.c_size_t),
+        ("multipolygon_tag_off", C.POINTER(C.c_uint32)),
+        ("multipolygon_tags", C.POINTER(C.c_uint32)),
+        ("n_multipolygons", C.c_size_t),
+        ("n_multipolygon_tags", C.c_size_t),
+        ("strings", C.POINTER(C.c_uint8)),
+        ("n_string_bytes", C.c_size_t),
+    ]
+
+
+class SelectorTest(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("key_off", C.c_uint32), ("key_len", C.c_uint32), ("value_off", C.c_uint32), ("value_len", C.c_uint32),
+                ("_pad", C.c_uint32), ("value", C.c_double)]
+
+
+class SelectorRec(C.Structure):
+    _fields_ = [("object_type", C.c_uint8), ("has_min_zoom", C.c_uint8), ("min_zoom", C.c_uint8), ("has_max_zoom", C.c_uint8), ("max_zoom", C.c_uint8),
+                ("_pad", C.c_uint8 * 3), ("test_off", C.c_uint32), ("n_tests", C.c_uint32)]
+
+
+class SelectorsDesc(C.Structure):
+    _fields_ = [("selectors", C.POINTER(SelectorRec)), ("n_selectors", C.c_size_t), ("tests", C.POINTER(SelectorTest)), ("n_tests", C.c_size_t),
+                ("strings", C.POINTER(C.c_uint8)), ("n_string_bytes", C.c_size_t)]
+
+
+class NumberOverride(C.Structure):
+    _fields_ = [("v_off", C.c_uint32), ("v_len", C.c_uint32), ("has_value", C.c_uint32), ("_pad", C.c_uint32), ("value", C.c_double)]
+
+
+class DeclinedNumber(C.Structure):
+    _fields_ = [("v_off", C.c_uint32), ("v_len", C.c_uint32)]
+
+
+class MatchClass(C.Structure):
+    _fields_ = [("layer", C.c_int64), ("sel_off", C.c_uint32), ("n_sels", C.c_uint32), ("first_entity", C.c_uint32), ("slot", C.c_uint8),
+                ("has_layer", C.c_uint8), ("_pad", C.c_uint8 * 2)]
+
+
+assert C.sizeof(TagsDesc) == 112
+assert C.sizeof(SelectorTest) == 32
+assert C.sizeof(SelectorRec) == 16
+assert C.sizeof(SelectorsDesc) == 48
+assert C.sizeof(NumberOverride) == 24
+assert C.sizeof(DeclinedNumber) == 8
+assert C.sizeof(MatchClass) == 24

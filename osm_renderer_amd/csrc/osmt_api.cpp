@@ -15,6 +15,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <map>
 #include <dlfcn.h>
 
 #include <memory>
@@ -27,6 +28,7 @@
 #include "../../include/osmtile.h"
 #include "osmt_geom.h"
 #include "osmt_internal.h"
+#include "osmt_numparse.h" /* osmt_bytes_cmp: the key order of osmt_validate_tags */
 #include "osmt_png_table.h" /* PNG_LMAX, PNG_BLOCK_HDR_BITS: the slot bound */
 #include "../host/osmt_textplacer.hpp" /* osmt::validate_text_labels */
 #include "../host/osmt_textshaper.hpp" /* osmt::validate_font, osmt::validate_string_labels */
@@ -144,8 +146,19 @@ struct osmt_ctx {
         const uint64_t* d_node_gid = nullptr;
         /* the Mercator factors of its nodes (osmt_register_node_mercator): at most one table, same rules */
         const double2* d_factors = nullptr; /* [n_nodes] */
+        /* its tags (osmt_register_tags): at most one table, same rules */
+        void* d_tags = nullptr;
+        osmt_sm_tags_dev tags{};
+        size_t tags_string_bytes = 0;
     };
     std::vector<geodata_host> geodata;
+    /* the selector sets of osmt_register_selectors: append-only, one device allocation each that never moves */
+    struct selectors_host {
+        void* d_pool = nullptr;
+        osmt_sm_sels_dev dev{};
+    };
+    std::vector<selectors_host> selectors;
+    uint32_t match_hash_bits = 32; /* osmt_debug_match_hash_bits */
     /* the tables of osmt_register_style_bindings: append-only, one device allocation each that never moves, so a build
      * that holds a table's pointers is not disturbed by a later registration */
     struct bindings_host {
@@ -672,7 +685,10 @@ void ctx_teardown(osmt_ctx* ctx) {
         if (g.d_index) (void)hipFree(g.d_index);
         if (g.d_node_index) (void)hipFree(g.d_node_index);
         if (g.d_factors) (void)hipFree((void*)g.d_factors);
+        if (g.d_tags) (void)hipFree(g.d_tags);
     }
+    for (auto& b : ctx->selectors)
+        if (b.d_pool) (void)hipFree(b.d_pool);
     for (auto& b : ctx->bindings)
         if (b.d_pool) (void)hipFree(b.d_pool);
     for (auto& b : ctx->label_bindings)
@@ -6450,6 +6466,620 @@ int osmt_debug_poison_enabled(void) { return poison_alloc() ? 1 : 0; }
 
 int osmt_hbm_copy_probe(osmt_ctx* ctx, size_t bytes, uint32_t iters, double* out_copy, double* out_read) {
     return guarded([&] { return hbm_copy_probe_body(ctx, bytes, iters, out_copy, out_read); });
+}
+
+} /* extern "C" */
+
+/* ---- selector matching (include/osmtile.h, csrc/osmt_selmatch.hip) ------------------------------------------------ */
+struct osmt_match {
+    osmt_ctx* ctx = nullptr;
+    uint32_t geodata_id = 0;
+    bool complete = false; /* false: the declined state, only the declined values can be read */
+    std::vector<osmt_declined_number> declined;
+    size_t n_nodes = 0, n_ways = 0, n_mps = 0, n_classes = 0, n_class_sels = 0;
+    char* d_keep = nullptr; /* one allocation: the three arrays below */
+    const uint32_t* d_ent_class = nullptr;
+    const osmt_match_class* d_classes = nullptr;
+    const uint32_t* d_class_sels = nullptr;
+};
+
+namespace {
+
+struct sm_tag_kind {
+    const char *off_name, *what;
+    const uint32_t *off, *tags;
+    size_t n, n_tags;
+};
+
+int validate_tags(const osmt_tags_desc* t, uint32_t geodata_id, osmt_ctx* ctx) {
+    if (!t) return fail(OSMT_INVALID_ARG, "tags are NULL");
+    const sm_tag_kind kinds[3] = {{"node_tag_off", "node", t->node_tag_off, t->node_tags, t->n_nodes, t->n_node_tags},
+                                  {"way_tag_off", "way", t->way_tag_off, t->way_tags, t->n_ways, t->n_way_tags},
+                                  {"multipolygon_tag_off", "multipolygon", t->multipolygon_tag_off, t->multipolygon_tags, t->n_multipolygons,
+                                   t->n_multipolygon_tags}};
+    for (const sm_tag_kind& k : kinds)
+        if (!k.off || (k.n_tags && !k.tags)) return fail(OSMT_INVALID_ARG, "tags: NULL %s array (every offset array has at least its first entry)", k.what);
+    if (t->n_string_bytes && !t->strings) return fail(OSMT_INVALID_ARG, "tags: NULL strings with %zu bytes", t->n_string_bytes);
+    if (t->n_nodes + t->n_ways + t->n_multipolygons > ((size_t)1 << 30))
+        return fail(OSMT_UNSUPPORTED, "tags: %zu entities (> 2^30)", t->n_nodes + t->n_ways + t->n_multipolygons);
+    if (t->n_node_tags + t->n_way_tags + t->n_multipolygon_tags >= 0xFFFFFFFFull || t->n_string_bytes >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "tags: too large for 32-bit indices");
+    for (const sm_tag_kind& k : kinds) {
+        const int rc = check_offsets_of("tags", k.off_name, k.off, k.n, k.n_tags);
+        if (rc != OSMT_OK) return rc;
+    }
+    for (const sm_tag_kind& k : kinds)
+        for (size_t i = 0; i < k.n; ++i)
+            for (uint32_t j = k.off[i]; j < k.off[i + 1]; ++j) {
+                const uint32_t* q = k.tags + 4 * (size_t)j;
+                if ((size_t)q[0] + q[1] > t->n_string_bytes || (size_t)q[2] + q[3] > t->n_string_bytes)
+                    return fail(OSMT_INVALID_ARG, "tags: tag %u of %s %zu = (%u, %u, %u, %u) leaves the %zu string bytes", j - k.off[i], k.what, i, q[0], q[1],
+                                q[2], q[3], t->n_string_bytes);
+                if (j > k.off[i] && osmt_bytes_cmp(t->strings + q[-4], q[-3], t->strings + q[0], q[1]) >= 0)
+                    return fail(OSMT_INVALID_ARG, "tags: the keys of %s %zu are not strictly ascending as unsigned bytes (tag %u against the one before)",
+                                k.what, i, j - k.off[i]);
+            }
+    if (!ctx) return OSMT_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (geodata_id >= ctx->geodata.size()) return fail(OSMT_INVALID_ARG, "tags: geodata id %u is not registered (%zu files)", geodata_id, ctx->geodata.size());
+    const osmt_ctx::geodata_host& g = ctx->geodata[geodata_id];
+    if (g.n_nodes != t->n_nodes || g.n_ways != t->n_ways || g.n_mps != t->n_multipolygons)
+        return fail(OSMT_INVALID_ARG, "tags: %zu nodes, %zu ways, %zu multipolygons, but geodata id %u has %zu, %zu, %zu", t->n_nodes, t->n_ways,
+                    t->n_multipolygons, geodata_id, g.n_nodes, g.n_ways, g.n_mps);
+    return OSMT_OK;
+}
+
+int register_tags_body(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tags_desc* t) {
+    if (!ctx) return fail(OSMT_INVALID_ARG, "NULL argument");
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (geodata_id < ctx->geodata.size() && ctx->geodata[geodata_id].d_tags)
+            return fail(OSMT_INVALID_ARG, "geodata id %u has tags already (one table per file)", geodata_id);
+    }
+    const int rc = validate_tags(t, geodata_id, ctx);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n_ent = t->n_nodes + t->n_ways + t->n_multipolygons, n_tags = t->n_node_tags + t->n_way_tags + t->n_multipolygon_tags;
+    std::vector<uint32_t> tag_off(n_ent + 1);
+    {
+        size_t e = 0;
+        for (size_t i = 0; i < t->n_nodes; ++i) tag_off[e++] = t->node_tag_off[i];
+        for (size_t i = 0; i < t->n_ways; ++i) tag_off[e++] = (uint32_t)(t->n_node_tags + t->way_tag_off[i]);
+        for (size_t i = 0; i < t->n_multipolygons; ++i) tag_off[e++] = (uint32_t)(t->n_node_tags + t->n_way_tags + t->multipolygon_tag_off[i]);
+        tag_off[e] = (uint32_t)n_tags;
+    }
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_off = carve((n_ent + 1) * 4), o_tags = carve(n_tags * 16), o_str = carve(t->n_string_bytes);
+    char* pool = nullptr;
+    HIP_TRY(hipMalloc((void**)&pool, off));
+    hipError_t e = hipSuccess;
+    auto put = [&](size_t o, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+    };
+    put(o_off, tag_off.data(), (n_ent + 1) * 4);
+    put(o_tags, t->node_tags, t->n_node_tags * 16);
+    put(o_tags + t->n_node_tags * 16, t->way_tags, t->n_way_tags * 16);
+    put(o_tags + (t->n_node_tags + t->n_way_tags) * 16, t->multipolygon_tags, t->n_multipolygon_tags * 16);
+    put(o_str, t->strings, t->n_string_bytes);
+    if (e != hipSuccess) {
+        (void)hipFree(pool);
+        return fail(OSMT_HIP_ERROR, "tags upload failed: %s", hipGetErrorString(e));
+    }
+    osmt_sm_tags_dev d{};
+    d.tag_off = (const uint32_t*)(pool + o_off);
+    d.tags = (const uint4*)(pool + o_tags);
+    d.strings = (const uint8_t*)(pool + o_str);
+    d.n_nodes = (uint32_t)t->n_nodes, d.n_ways = (uint32_t)t->n_ways, d.n_mps = (uint32_t)t->n_multipolygons, d.n_tags = (uint32_t)n_tags;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->geodata[geodata_id].d_tags) { /* another thread was first */
+        (void)hipFree(pool);
+        return fail(OSMT_INVALID_ARG, "geodata id %u has tags already (one table per file)", geodata_id);
+    }
+    ctx->geodata[geodata_id].d_tags = pool;
+    ctx->geodata[geodata_id].tags = d;
+    ctx->geodata[geodata_id].tags_string_bytes = t->n_string_bytes;
+    return OSMT_OK;
+}
+
+int validate_selectors(const osmt_selectors_desc* d) {
+    if (!d) return fail(OSMT_INVALID_ARG, "selectors are NULL");
+    if ((d->n_selectors && !d->selectors) || (d->n_tests && !d->tests) || (d->n_string_bytes && !d->strings))
+        return fail(OSMT_INVALID_ARG, "selectors: NULL array with non-zero count");
+    if (d->n_selectors > OSMT_MATCH_MAX_SELECTORS)
+        return fail(OSMT_UNSUPPORTED, "selectors: %zu selectors (> OSMT_MATCH_MAX_SELECTORS = %u)", d->n_selectors, OSMT_MATCH_MAX_SELECTORS);
+    if (d->n_tests >= 0xFFFFFFFFull || d->n_string_bytes >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "selectors: too large for 32-bit indices");
+    for (size_t i = 0; i < d->n_selectors; ++i) {
+        const osmt_selector_rec& s = d->selectors[i];
+        if (s.object_type > OSMT_SEL_OTHER) return fail(OSMT_INVALID_ARG, "selector %zu: object type %u is not an OSMT_SEL_* value", i, s.object_type);
+        if (s.has_min_zoom > 1 || s.has_max_zoom > 1) return fail(OSMT_INVALID_ARG, "selector %zu: a zoom flag that is not 0 or 1", i);
+        if (s.n_tests > OSMT_MATCH_MAX_SELECTOR_TESTS)
+            return fail(OSMT_UNSUPPORTED, "selector %zu has %u tests (> OSMT_MATCH_MAX_SELECTOR_TESTS = %u)", i, s.n_tests, OSMT_MATCH_MAX_SELECTOR_TESTS);
+        if ((size_t)s.test_off + s.n_tests > d->n_tests)
+            return fail(OSMT_INVALID_ARG, "selector %zu: tests %u..%u leave the %zu tests", i, s.test_off, s.test_off + s.n_tests, d->n_tests);
+    }
+    for (size_t i = 0; i < d->n_tests; ++i) {
+        const osmt_selector_test& t = d->tests[i];
+        if (t.kind >= OSMT_TEST_KINDS) return fail(OSMT_INVALID_ARG, "test %zu: kind %u is not an OSMT_TEST_* value", i, t.kind);
+        if ((size_t)t.key_off + t.key_len > d->n_string_bytes || (size_t)t.value_off + t.value_len > d->n_string_bytes)
+            return fail(OSMT_INVALID_ARG, "test %zu: a string range leaves the %zu string bytes", i, d->n_string_bytes);
+    }
+    return OSMT_OK;
+}
+
+int register_selectors_body(osmt_ctx* ctx, const osmt_selectors_desc* d, uint32_t* out_id) {
+    if (!ctx || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    const int rc = validate_selectors(d);
+    if (rc != OSMT_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    /* the distinct test keys in &str order (std::string compares as unsigned bytes) and per key its distinct string values */
+    struct key_info {
+        std::vector<std::string> vals;
+        bool numeric = false;
+        uint32_t id = 0;
+    };
+    std::map<std::string, key_info> keys;
+    auto str = [&](uint32_t off, uint32_t len) { return std::string((const char*)d->strings + off, len); };
+    for (size_t i = 0; i < d->n_tests; ++i) {
+        const osmt_selector_test& t = d->tests[i];
+        key_info& k = keys[str(t.key_off, t.key_len)];
+        if (t.kind == OSMT_TEST_EQUAL || t.kind == OSMT_TEST_NOT_EQUAL) k.vals.push_back(str(t.value_off, t.value_len));
+        if (t.kind >= OSMT_TEST_LESS) k.numeric = true;
+    }
+    std::vector<osmt_sm_key> h_keys;
+    std::vector<uint2> h_vals;
+    std::string blob;
+    for (auto& kv : keys) {
+        key_info& k = kv.second;
+        std::sort(k.vals.begin(), k.vals.end());
+        k.vals.erase(std::unique(k.vals.begin(), k.vals.end()), k.vals.end());
+        k.id = (uint32_t)h_keys.size();
+        osmt_sm_key r{};
+        r.off = (uint32_t)blob.size(), r.len = (uint32_t)kv.first.size();
+        blob += kv.first;
+        r.val_first = (uint32_t)h_vals.size(), r.n_vals = (uint32_t)k.vals.size();
+        r.numeric = k.numeric ? 1u : 0u;
+        for (const std::string& v : k.vals) {
+            h_vals.push_back(make_uint2((uint32_t)blob.size(), (uint32_t)v.size()));
+            blob += v;
+        }
+        h_keys.push_back(r);
+    }
+    if (blob.size() >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "selectors: too large for 32-bit indices");
+    std::vector<osmt_sm_test> h_tests(d->n_tests);
+    for (size_t i = 0; i < d->n_tests; ++i) {
+        const osmt_selector_test& t = d->tests[i];
+        const key_info& k = keys[str(t.key_off, t.key_len)];
+        osmt_sm_test r{};
+        r.kind = t.kind, r.key = k.id, r.vid = OSMT_SM_NONE, r.value = t.value;
+        if (t.kind == OSMT_TEST_EQUAL || t.kind == OSMT_TEST_NOT_EQUAL)
+            r.vid = (uint32_t)(std::lower_bound(k.vals.begin(), k.vals.end(), str(t.value_off, t.value_len)) - k.vals.begin());
+        h_tests[i] = r;
+    }
+    std::vector<osmt_sm_sel> h_sels(d->n_selectors);
+    for (size_t i = 0; i < d->n_selectors; ++i) {
+        osmt_sm_sel r{};
+        r.type = d->selectors[i].object_type, r.test_off = d->selectors[i].test_off, r.n_tests = d->selectors[i].n_tests;
+        h_sels[i] = r;
+    }
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_k = carve(h_keys.size() * sizeof(osmt_sm_key)), o_v = carve(h_vals.size() * sizeof(uint2)), o_s = carve(blob.size());
+    const size_t o_sel = carve(h_sels.size() * sizeof(osmt_sm_sel)), o_t = carve(h_tests.size() * sizeof(osmt_sm_test));
+    char* pool = nullptr;
+    HIP_TRY(hipMalloc((void**)&pool, off));
+    hipError_t e = hipSuccess;
+    auto put = [&](size_t o, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+    };
+    put(o_k, h_keys.data(), h_keys.size() * sizeof(osmt_sm_key));
+    put(o_v, h_vals.data(), h_vals.size() * sizeof(uint2));
+    put(o_s, blob.data(), blob.size());
+    put(o_sel, h_sels.data(), h_sels.size() * sizeof(osmt_sm_sel));
+    put(o_t, h_tests.data(), h_tests.size() * sizeof(osmt_sm_test));
+    if (e != hipSuccess) {
+        (void)hipFree(pool);
+        return fail(OSMT_HIP_ERROR, "selectors upload failed: %s", hipGetErrorString(e));
+    }
+    osmt_ctx::selectors_host h;
+    h.d_pool = pool;
+    h.dev.keys = (const osmt_sm_key*)(pool + o_k);
+    h.dev.vals = (const uint2*)(pool + o_v);
+    h.dev.strings = (const uint8_t*)(pool + o_s);
+    h.dev.sels = (const osmt_sm_sel*)(pool + o_sel);
+    h.dev.tests = (const osmt_sm_test*)(pool + o_t);
+    h.dev.n_keys = (uint32_t)h_keys.size(), h.dev.n_sels = (uint32_t)h_sels.size();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    *out_id = (uint32_t)ctx->selectors.size();
+    ctx->selectors.push_back(h);
+    return OSMT_OK;
+}
+
+int match_selectors_body(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_id, const osmt_number_override* ov, size_t n_ov, osmt_match** out) {
+    if (!ctx || !out) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    osmt_ctx::geodata_host geo;
+    osmt_ctx::selectors_host sel;
+    uint32_t hash_bits = 32;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (geodata_id >= ctx->geodata.size()) return fail(OSMT_INVALID_ARG, "geodata id %u is not registered (%zu files)", geodata_id, ctx->geodata.size());
+        if (!ctx->geodata[geodata_id].d_tags) return fail(OSMT_INVALID_ARG, "geodata id %u has no tags (osmt_register_tags)", geodata_id);
+        if (selectors_id >= ctx->selectors.size())
+            return fail(OSMT_INVALID_ARG, "selectors id %u is not registered (%zu sets)", selectors_id, ctx->selectors.size());
+        geo = ctx->geodata[geodata_id];
+        sel = ctx->selectors[selectors_id];
+        hash_bits = ctx->match_hash_bits;
+    }
+    if (n_ov && !ov) return fail(OSMT_INVALID_ARG, "number overrides: NULL array with non-zero count");
+    if (n_ov >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "number overrides: too many");
+    for (size_t i = 0; i < n_ov; ++i) {
+        const osmt_number_override& o = ov[i];
+        if ((size_t)o.v_off + o.v_len > geo.tags_string_bytes)
+            return fail(OSMT_INVALID_ARG, "number overrides: entry %zu = (%u, %u) leaves the %zu string bytes of the tags", i, o.v_off, o.v_len,
+                        geo.tags_string_bytes);
+        if (o.has_value > 1u) return fail(OSMT_INVALID_ARG, "number overrides: entry %zu has has_value = %u (0 or 1)", i, o.has_value);
+        if (i && !(ov[i - 1].v_off < o.v_off || (ov[i - 1].v_off == o.v_off && ov[i - 1].v_len < o.v_len)))
+            return fail(OSMT_INVALID_ARG, "number overrides: entry %zu = (%u, %u) does not come after entry %zu (strictly ascending by (v_off, v_len))", i,
+                        o.v_off, o.v_len, i - 1);
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    struct work_guard {
+        osmt_ctx* ctx;
+        hipStream_t st = nullptr;
+        char* work[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~work_guard() {
+            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's overrides */
+            for (char* p : work) dev_free(ctx, p);
+            stream_release(ctx, st);
+        }
+    } wg{ctx};
+    HIP_TRY(stream_acquire(ctx, &wg.st));
+    hipStream_t st = wg.st;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    auto alloc = [&](char** p, const char* what) {
+        const hipError_t e = dev_alloc(ctx, (void**)p, off + 256);
+        if (e == hipSuccess) return (int)OSMT_OK;
+        *p = nullptr;
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the selector match (%s) failed: %s", off, what, hipGetErrorString(e));
+    };
+    /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the stages, one line on stderr */
+    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    enum { EV_TAGS0, EV_TAGS1, EV_COUNT0, EV_COUNT1, EV_CLASS0, EV_CLASS1, EV_EMIT0, EV_EMIT1, EV_N };
+    hipEvent_t ev[EV_N] = {};
+    struct ev_guard {
+        hipEvent_t* ev;
+        ~ev_guard() {
+            for (int i = 0; i < EV_N; ++i)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } evg{ev};
+    if (trace)
+        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+
+    const size_t n_ent = (size_t)geo.tags.n_nodes + geo.tags.n_ways + geo.tags.n_mps, n_tags = geo.tags.n_tags;
+    unsigned long long tot[OSMT_SM_T_N] = {};
+    osmt_sm_pass P;
+    memset(&P, 0, sizeof P);
+    P.geo = geo.dev;
+    P.tg = geo.tags;
+    P.ss = sel.dev;
+    P.n_ov = (uint32_t)n_ov;
+    P.n_ent = (uint32_t)n_ent;
+    P.hash_mask = hash_bits >= 32u ? 0xFFFFFFFFu : (1u << hash_bits) - 1u;
+    /* 1. tags */
+    off = 0;
+    const size_t o_ov = carve(n_ov * sizeof(osmt_number_override)), o_code = carve(n_tags * 4), o_vf = carve(n_tags * 8), o_num = carve(n_tags * 8);
+    const size_t o_dp = carve((n_tags + 1) * 4), o_blk = carve((std::max(n_tags, n_ent) / 256 + 1) * 8), o_tot = carve(OSMT_SM_T_N * 8);
+    int rc = alloc(&wg.work[0], "tags");
+    if (rc != OSMT_OK) return rc;
+    char* w0 = wg.work[0];
+    if (n_ov) HIP_TRY(hipMemcpyAsync(w0 + o_ov, ov, n_ov * sizeof(osmt_number_override), hipMemcpyHostToDevice, st));
+    P.ov = (const osmt_number_override*)(w0 + o_ov);
+    P.tag_code = (uint32_t*)(w0 + o_code);
+    P.tag_vf = (uint2*)(w0 + o_vf);
+    P.tag_num = (double*)(w0 + o_num);
+    P.decl_pos = (uint32_t*)(w0 + o_dp);
+    P.blk = (unsigned long long*)(w0 + o_blk);
+    P.tot = (unsigned long long*)(w0 + o_tot);
+    HIP_TRY(mark(EV_TAGS0));
+    HIP_TRY(osmt_launch_sm_tags(P, st));
+    HIP_TRY(mark(EV_TAGS1));
+    HIP_TRY(hipMemcpyAsync(tot, P.tot, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tot[OSMT_SM_T_DECLINED]) {
+        const size_t n_decl = (size_t)tot[OSMT_SM_T_DECLINED];
+        off = 0;
+        (void)carve(n_decl * sizeof(osmt_declined_number));
+        rc = alloc(&wg.work[1], "declined values");
+        if (rc != OSMT_OK) return rc;
+        P.n_declined = (uint32_t)n_decl;
+        P.declined = (osmt_declined_number*)wg.work[1];
+        HIP_TRY(osmt_launch_sm_declined(P, st));
+        std::unique_ptr<osmt_match> m(new osmt_match);
+        m->declined.resize(n_decl);
+        HIP_TRY(hipMemcpyAsync(m->declined.data(), P.declined, n_decl * sizeof(osmt_declined_number), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        auto lt = [](const osmt_declined_number& a, const osmt_declined_number& b) { return a.v_off < b.v_off || (a.v_off == b.v_off && a.v_len < b.v_len); };
+        std::sort(m->declined.begin(), m->declined.end(), lt);
+        m->declined.erase(std::unique(m->declined.begin(), m->declined.end(),
+                                      [](const osmt_declined_number& a, const osmt_declined_number& b) { return a.v_off == b.v_off && a.v_len == b.v_len; }),
+                          m->declined.end());
+        const osmt_declined_number first = m->declined[0];
+        char text[49] = {};
+        const size_t shown = std::min<size_t>(first.v_len, sizeof text - 1);
+        if (shown) HIP_TRY(copy_back(ctx, text, geo.tags.strings + first.v_off, shown));
+        m->ctx = ctx;
+        m->geodata_id = geodata_id;
+        ctx->refs.fetch_add(1);
+        const size_t n_distinct = m->declined.size();
+        *out = m.release();
+        return fail(OSMT_UNSUPPORTED,
+                    "the exact number parse declines %zu distinct tag values, the first is \"%s\"%s (v_off %u, v_len %u): read them with "
+                    "osmt_match_read_declined_numbers and pass their values as overrides",
+                    n_distinct, text, shown < first.v_len ? "..." : "", first.v_off, first.v_len);
+    }
+    /* 2. count */
+    size_t table = 2;
+    while (table < 2 * n_ent) table <<= 1;
+    P.table_mask = (uint32_t)(table - 1);
+    off = 0;
+    const size_t o_sp = carve((n_ent + 1) * 4), o_lay = carve(n_ent * 8), o_key = carve(n_ent * 4), o_hash = carve(n_ent * 4), o_ts = carve(n_ent * 4);
+    const size_t o_fp = carve((n_ent + 1) * 4), o_tab = carve(table * 4), o_low = carve(table * 4);
+    rc = alloc(&wg.work[1], "entities");
+    if (rc != OSMT_OK) return rc;
+    char* w1 = wg.work[1];
+    P.sel_pos = (uint32_t*)(w1 + o_sp);
+    P.ent_layer = (long long*)(w1 + o_lay);
+    P.ent_key = (uint32_t*)(w1 + o_key);
+    P.ent_hash = (uint32_t*)(w1 + o_hash);
+    P.ent_tslot = (uint32_t*)(w1 + o_ts);
+    P.first_pos = (uint32_t*)(w1 + o_fp);
+    P.table = (uint32_t*)(w1 + o_tab);
+    P.lowest = (uint32_t*)(w1 + o_low);
+    HIP_TRY(mark(EV_COUNT0));
+    HIP_TRY(osmt_launch_sm_count(P, st));
+    HIP_TRY(mark(EV_COUNT1));
+    HIP_TRY(hipMemcpyAsync(tot + OSMT_SM_T_MATCHED, P.tot + OSMT_SM_T_MATCHED, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tot[OSMT_SM_T_MATCHED] >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "the match has %llu (entity, selector) pairs (> 2^32 - 2): split the selector set", tot[OSMT_SM_T_MATCHED]);
+    P.n_matched = (uint32_t)tot[OSMT_SM_T_MATCHED];
+    /* 3. lists and classes */
+    off = 0;
+    (void)carve((size_t)P.n_matched * 4);
+    rc = alloc(&wg.work[2], "selector lists");
+    if (rc != OSMT_OK) return rc;
+    P.ent_sels = (uint32_t*)wg.work[2];
+    HIP_TRY(mark(EV_CLASS0));
+    HIP_TRY(osmt_launch_sm_classes(P, st));
+    HIP_TRY(mark(EV_CLASS1));
+    HIP_TRY(hipMemcpyAsync(tot + OSMT_SM_T_CLASSES, P.tot + OSMT_SM_T_CLASSES, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    P.n_classes = (uint32_t)tot[OSMT_SM_T_CLASSES]; /* at most n_ent */
+    off = 0;
+    const size_t o_cp = carve(((size_t)P.n_classes + 1) * 4), o_cf = carve((size_t)P.n_classes * 4);
+    rc = alloc(&wg.work[3], "classes");
+    if (rc != OSMT_OK) return rc;
+    P.cls_pos = (uint32_t*)(wg.work[3] + o_cp);
+    P.cls_first = (uint32_t*)(wg.work[3] + o_cf);
+    HIP_TRY(mark(EV_EMIT0));
+    HIP_TRY(osmt_launch_sm_class_count(P, st));
+    HIP_TRY(hipMemcpyAsync(tot + OSMT_SM_T_CLASS_SELS, P.tot + OSMT_SM_T_CLASS_SELS, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    P.n_class_sels = (uint32_t)tot[OSMT_SM_T_CLASS_SELS]; /* at most n_matched */
+    /* 4. the result: one allocation that goes to the match */
+    off = 0;
+    const size_t o_ec = carve(n_ent * 4), o_cl = carve((size_t)P.n_classes * sizeof(osmt_match_class)), o_cs = carve((size_t)P.n_class_sels * 4);
+    rc = alloc(&wg.work[4], "result");
+    if (rc != OSMT_OK) return rc;
+    char* keep = wg.work[4];
+    P.ent_class = (uint32_t*)(keep + o_ec);
+    P.classes = (osmt_match_class*)(keep + o_cl);
+    P.class_sels = (uint32_t*)(keep + o_cs);
+    HIP_TRY(osmt_launch_sm_emit(P, st));
+    HIP_TRY(mark(EV_EMIT1));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::unique_ptr<osmt_match> m(new osmt_match);
+    m->ctx = ctx;
+    m->geodata_id = geodata_id;
+    m->complete = true;
+    m->n_nodes = geo.tags.n_nodes, m->n_ways = geo.tags.n_ways, m->n_mps = geo.tags.n_mps;
+    m->n_classes = P.n_classes, m->n_class_sels = P.n_class_sels;
+    m->d_keep = keep;
+    m->d_ent_class = P.ent_class, m->d_classes = P.classes, m->d_class_sels = P.class_sels;
+    wg.work[4] = nullptr;
+    ctx->refs.fetch_add(1);
+    *out = m.release();
+    if (trace) {
+        auto us = [&](int a, int b2) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
+            return ms * 1e3;
+        };
+        fprintf(stderr,
+                "osmt selector match: tags %.1f us, count %.1f us, lists + classes %.1f us, records %.1f us (%zu entities, %zu tags, %u selectors, "
+                "%u pairs, %u classes)\n",
+                us(EV_TAGS0, EV_TAGS1), us(EV_COUNT0, EV_COUNT1), us(EV_CLASS0, EV_CLASS1), us(EV_EMIT0, EV_EMIT1), n_ent, n_tags, sel.dev.n_sels,
+                P.n_matched, P.n_classes);
+    }
+    return OSMT_OK;
+}
+
+int match_read_body(osmt_match* m, uint32_t* ent_class, osmt_match_class* classes, uint32_t* class_sels, const size_t caps[3], size_t counts[3]) {
+    if (!m || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (!m->complete) return fail(OSMT_INVALID_ARG, "the match is in the declined state: it answers only osmt_match_read_declined_numbers");
+    const size_t n_ent = m->n_nodes + m->n_ways + m->n_mps;
+    counts[0] = n_ent, counts[1] = m->n_classes, counts[2] = m->n_class_sels;
+    if (!ent_class && !classes && !class_sels) return OSMT_OK;
+    if (!caps) return fail(OSMT_INVALID_ARG, "NULL caps with an output");
+    if ((ent_class && caps[0] < counts[0]) || (classes && caps[1] < counts[1]) || (class_sels && caps[2] < counts[2]))
+        return fail(OSMT_INVALID_ARG, "caps (%zu, %zu, %zu) are less than the match's (%zu, %zu, %zu)", caps[0], caps[1], caps[2], counts[0], counts[1],
+                    counts[2]);
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (ent_class) HIP_TRY(copy_back(m->ctx, ent_class, m->d_ent_class, n_ent * 4));
+    if (classes) HIP_TRY(copy_back(m->ctx, classes, m->d_classes, m->n_classes * sizeof(osmt_match_class)));
+    if (class_sels) HIP_TRY(copy_back(m->ctx, class_sels, m->d_class_sels, m->n_class_sels * 4));
+    return OSMT_OK;
+}
+
+int bindings_matched_body(osmt_ctx* ctx, osmt_match* m, uint8_t zoom_lo, uint8_t zoom_hi, const uint32_t* class_off, const uint32_t* class_styles, size_t n,
+                          uint32_t* out_id) {
+    if (!ctx || !m || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (m->ctx != ctx) return fail(OSMT_INVALID_ARG, "bindings per class: the match belongs to another context");
+    if (!m->complete) return fail(OSMT_INVALID_ARG, "bindings per class: the match is in the declined state");
+    if (zoom_lo > zoom_hi || zoom_hi > OSMT_MAX_ZOOM)
+        return fail(OSMT_INVALID_ARG, "bindings per class: zoom range %u..%u (zoom_lo <= zoom_hi <= %u)", zoom_lo, zoom_hi, OSMT_MAX_ZOOM);
+    if (n != m->n_classes) return fail(OSMT_INVALID_ARG, "bindings per class: %zu classes, the match has %zu", n, m->n_classes);
+    if (!class_off) return fail(OSMT_INVALID_ARG, "bindings per class: NULL class_style_off (it has at least its first entry)");
+    int rc = check_offsets_of("bindings per class", "class_style_off", class_off, n, class_off[n]);
+    if (rc != OSMT_OK) return rc;
+    const size_t n_styles_in = class_off[n];
+    if (n_styles_in && !class_styles) return fail(OSMT_INVALID_ARG, "bindings per class: NULL class_styles with %zu entries", n_styles_in);
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        for (size_t i = 0; i < n_styles_in; ++i)
+            if (class_styles[i] >= ctx->styles.size())
+                return fail(OSMT_INVALID_ARG, "bindings per class: class_styles[%zu] = %u is not a registered style (%zu styles)", i, class_styles[i],
+                            ctx->styles.size());
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    struct work_guard {
+        osmt_ctx* ctx;
+        hipStream_t st = nullptr;
+        char* work = nullptr;
+        char* pool = nullptr; /* the table, until it is registered */
+        ~work_guard() {
+            if (st) (void)hipStreamSynchronize(st);
+            dev_free(ctx, work);
+            if (pool) (void)hipFree(pool);
+            stream_release(ctx, st);
+        }
+    } wg{ctx};
+    HIP_TRY(stream_acquire(ctx, &wg.st));
+    hipStream_t st = wg.st;
+    const size_t n_ways = m->n_ways, n_mps = m->n_mps;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    const size_t o_co = carve((n + 1) * 4), o_cs = carve(n_styles_in * 4), o_pw = carve((n_ways + 1) * 4), o_pm = carve((n_mps + 1) * 4);
+    const size_t o_blk = carve((std::max(n_ways, n_mps) / 256 + 1) * 8), o_tot = carve(16);
+    {
+        const hipError_t e = dev_alloc(ctx, (void**)&wg.work, off + 256);
+        if (e != hipSuccess) {
+            wg.work = nullptr;
+            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the bindings per class failed: %s", off, hipGetErrorString(e));
+        }
+    }
+    char* w = wg.work;
+    HIP_TRY(hipMemcpyAsync(w + o_co, class_off, (n + 1) * 4, hipMemcpyHostToDevice, st));
+    if (n_styles_in) HIP_TRY(hipMemcpyAsync(w + o_cs, class_styles, n_styles_in * 4, hipMemcpyHostToDevice, st));
+    const uint32_t* d_co = (const uint32_t*)(w + o_co);
+    const uint32_t* d_cs = (const uint32_t*)(w + o_cs);
+    uint32_t *pw = (uint32_t*)(w + o_pw), *pm = (uint32_t*)(w + o_pm);
+    unsigned long long* d_tot = (unsigned long long*)(w + o_tot);
+    const uint32_t* way_class = m->d_ent_class + m->n_nodes;
+    const uint32_t* mp_class = way_class + n_ways;
+    HIP_TRY(osmt_launch_sm_bind_count(way_class, d_co, (uint32_t)n_ways, pw, (unsigned long long*)(w + o_blk), d_tot, st));
+    HIP_TRY(osmt_launch_sm_bind_count(mp_class, d_co, (uint32_t)n_mps, pm, (unsigned long long*)(w + o_blk), d_tot + 1, st));
+    unsigned long long tot[2] = {};
+    HIP_TRY(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tot[0] >= 0xFFFFFFFFull || tot[1] >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "bindings per class: %llu way and %llu multipolygon bindings (> 2^32 - 2 of one kind)", tot[0], tot[1]);
+    /* the table, laid out as osmt_register_style_bindings lays it out */
+    off = 0;
+    const size_t o_wo = carve((n_ways + 1) * 4), o_w = carve((size_t)tot[0] * 4), o_mo = carve((n_mps + 1) * 4), o_m = carve((size_t)tot[1] * 4);
+    HIP_TRY(hipMalloc((void**)&wg.pool, off));
+    char* pool = wg.pool;
+    HIP_TRY(hipMemcpyAsync(pool + o_wo, pw, (n_ways + 1) * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(pool + o_mo, pm, (n_mps + 1) * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(osmt_launch_sm_bind_emit(way_class, d_co, d_cs, (uint32_t)n_ways, pw, (uint32_t*)(pool + o_w), st));
+    HIP_TRY(osmt_launch_sm_bind_emit(mp_class, d_co, d_cs, (uint32_t)n_mps, pm, (uint32_t*)(pool + o_m), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    osmt_ctx::bindings_host h;
+    h.geodata_id = m->geodata_id, h.zoom_lo = zoom_lo, h.zoom_hi = zoom_hi;
+    h.d_pool = pool;
+    h.dev.way_off = (const uint32_t*)(pool + o_wo);
+    h.dev.way_styles = (const uint32_t*)(pool + o_w);
+    h.dev.mp_off = (const uint32_t*)(pool + o_mo);
+    h.dev.mp_styles = (const uint32_t*)(pool + o_m);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->bindings.size() + 1 >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "bindings table too large");
+    *out_id = (uint32_t)ctx->bindings.size();
+    ctx->bindings.push_back(h);
+    wg.pool = nullptr;
+    return OSMT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int osmt_validate_tags(const osmt_tags_desc* tags, uint32_t geodata_id, osmt_ctx* ctx) {
+    return guarded([&] { return validate_tags(tags, geodata_id, ctx); });
+}
+int osmt_register_tags(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tags_desc* tags) {
+    return guarded([&] { return register_tags_body(ctx, geodata_id, tags); });
+}
+int osmt_validate_selectors(const osmt_selectors_desc* selectors) {
+    return guarded([&] { return validate_selectors(selectors); });
+}
+int osmt_register_selectors(osmt_ctx* ctx, const osmt_selectors_desc* selectors, uint32_t* out_selectors_id) {
+    return guarded([&] { return register_selectors_body(ctx, selectors, out_selectors_id); });
+}
+int osmt_match_selectors(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_id, const osmt_number_override* ov, size_t n_ov, osmt_match** out) {
+    return guarded([&] { return match_selectors_body(ctx, geodata_id, selectors_id, ov, n_ov, out); });
+}
+void osmt_match_free(osmt_match* m) {
+    if (!m) return;
+    osmt_ctx* ctx = m->ctx;
+    (void)hipSetDevice(ctx->device);
+    dev_free(ctx, m->d_keep);
+    delete m;
+    ctx_release(ctx);
+}
+int osmt_match_read_declined_numbers(osmt_match* m, osmt_declined_number* out, size_t cap, size_t* n) {
+    return guarded([&] {
+        if (!m || !n) return fail(OSMT_INVALID_ARG, "NULL argument");
+        *n = m->declined.size();
+        if (out && cap < *n) return fail(OSMT_INVALID_ARG, "cap %zu is less than the %zu declined values", cap, *n);
+        if (out && *n) memcpy(out, m->declined.data(), *n * sizeof(osmt_declined_number));
+        return (int)OSMT_OK;
+    });
+}
+int osmt_match_read(osmt_match* m, uint32_t* entity_class, osmt_match_class* classes, uint32_t* class_selectors, const size_t caps[3], size_t counts[3]) {
+    return guarded([&] { return match_read_body(m, entity_class, classes, class_selectors, caps, counts); });
+}
+int osmt_register_style_bindings_matched(osmt_ctx* ctx, osmt_match* match, uint8_t zoom_lo, uint8_t zoom_hi, const uint32_t* class_style_off,
+                                         const uint32_t* class_styles, size_t n, uint32_t* out_bindings_id) {
+    return guarded([&] { return bindings_matched_body(ctx, match, zoom_lo, zoom_hi, class_style_off, class_styles, n, out_bindings_id); });
+}
+int osmt_debug_match_hash_bits(osmt_ctx* ctx, uint32_t bits) {
+    return guarded([&] {
+        if (!ctx) return fail(OSMT_INVALID_ARG, "NULL argument");
+        if (bits > 32u) return fail(OSMT_INVALID_ARG, "hash bits %u (0..32)", bits);
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        ctx->match_hash_bits = bits;
+        return (int)OSMT_OK;
+    });
 }
 
 } /* extern "C" */

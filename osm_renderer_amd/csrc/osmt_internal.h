@@ -691,6 +691,97 @@ hipError_t osmt_launch_al_count(const osmt_al_pass& a, hipStream_t st);
 /* k_al_project + k_al_waypts + k_al_emit + k_al_chars */
 hipError_t osmt_launch_al_emit(const osmt_al_pass& a, hipStream_t st);
 
+/* ---- selector matching (osmt_selmatch.hip) ------------------------------------------------------------------------ */
+/* the registered tags of a geodata file: the three kinds' CSRs joined, entities numbered nodes, ways, multipolygons */
+struct osmt_sm_tags_dev {
+    const uint32_t* tag_off; /* [n_ent + 1] into tags */
+    const uint4* tags;       /* (k_off, k_len, v_off, v_len) */
+    const uint8_t* strings;
+    uint32_t n_nodes, n_ways, n_mps, n_tags;
+};
+/* a registered selector set.  keys: the distinct test keys ascending as unsigned bytes; vals: per key its distinct EQUAL /
+ * NOT_EQUAL values, ascending too */
+struct osmt_sm_key {
+    uint32_t off, len;        /* in strings */
+    uint32_t val_first, n_vals;
+    uint32_t numeric, _pad;   /* some numeric test names the key */
+};
+struct osmt_sm_test { /* 24 bytes */
+    uint32_t kind, key; /* OSMT_TEST_*, index into keys */
+    uint32_t vid, _pad; /* EQUAL / NOT_EQUAL: the value's index among the key's values */
+    double value;
+};
+struct osmt_sm_sel {
+    uint32_t type, test_off, n_tests, _pad;
+};
+struct osmt_sm_sels_dev {
+    const osmt_sm_key* keys;
+    const uint2* vals; /* (off, len) in strings */
+    const uint8_t* strings;
+    const osmt_sm_sel* sels;
+    const osmt_sm_test* tests;
+    uint32_t n_keys, n_sels;
+};
+#define OSMT_SM_NONE 0xFFFFFFFFu
+/* osmt_sm_pass::tag_vf[].y */
+#define OSMT_SM_TRUE 1u     /* the value is yes, true or 1 */
+#define OSMT_SM_NUM 2u      /* tag_num holds its f64 */
+#define OSMT_SM_DECLINED 4u /* a numeric key's value the fast path declines and no override lists */
+/* words of osmt_sm_pass::tot */
+enum { OSMT_SM_T_DECLINED = 0, OSMT_SM_T_MATCHED, OSMT_SM_T_CLASSES, OSMT_SM_T_CLASS_SELS, OSMT_SM_T_N };
+struct osmt_sm_pass {
+    osmt_geo_dev geo;
+    osmt_sm_tags_dev tg;
+    osmt_sm_sels_dev ss;
+    const osmt_number_override* ov; /* [n_ov] ascending by (v_off, v_len) */
+    uint32_t n_ov, n_ent;
+    uint32_t n_declined, n_matched, n_classes, n_class_sels; /* totals, known once they have been read back */
+    uint32_t hash_mask, table_mask; /* the debug knob; table size - 1 (a power of two >= 2 n_ent) */
+    /* per tag */
+    uint32_t* tag_code; /* 2 k + 1: the tag's key is test key k; 2 k: it sorts in front of test key k (k = n_keys: behind all) */
+    uint2* tag_vf;      /* (value id among its key's values or NONE, OSMT_SM_* flags) */
+    double* tag_num;
+    uint32_t* decl_pos; /* [n_tags + 1] 1: declined; then the exclusive scan */
+    osmt_declined_number* declined; /* [n_declined] in tag order, duplicates included */
+    /* per entity */
+    uint32_t* sel_pos;  /* [n_ent + 1] matched selectors, then their exclusive scan */
+    uint32_t* ent_sels; /* [n_matched] */
+    long long* ent_layer; /* 0 without */
+    uint32_t* ent_key;  /* slot | has_layer << 2 */
+    uint32_t* ent_hash;
+    uint32_t* ent_tslot; /* the entity's class in the table */
+    uint32_t* first_pos; /* [n_ent + 1] 1: the lowest member of its class; then the exclusive scan: the class id */
+    uint32_t* ent_class; /* the result */
+    /* the class table: open addressing over representative entity numbers */
+    uint32_t* table;  /* [table_mask + 1] */
+    uint32_t* lowest; /* [table_mask + 1] the lowest member */
+    /* per class */
+    uint32_t* cls_pos;   /* [n_classes + 1] selectors, then their exclusive scan */
+    uint32_t* cls_first; /* [n_classes] */
+    osmt_match_class* classes;
+    uint32_t* class_sels; /* [n_class_sels] */
+    unsigned long long* blk;
+    unsigned long long* tot; /* [OSMT_SM_T_N] */
+};
+/* k_sm_tags + scan: per-tag codes, value ids, flags and numbers; tot[DECLINED] */
+hipError_t osmt_launch_sm_tags(const osmt_sm_pass& a, hipStream_t st);
+/* k_sm_declined: the (v_off, v_len) of the declined tags */
+hipError_t osmt_launch_sm_declined(const osmt_sm_pass& a, hipStream_t st);
+/* k_sm_match (count) + scan: tot[MATCHED] */
+hipError_t osmt_launch_sm_count(const osmt_sm_pass& a, hipStream_t st);
+/* k_sm_match (emit) + k_sm_class_insert + k_sm_class_mark + scan: tot[CLASSES] */
+hipError_t osmt_launch_sm_classes(const osmt_sm_pass& a, hipStream_t st);
+/* k_sm_class_count + scan: tot[CLASS_SELS] */
+hipError_t osmt_launch_sm_class_count(const osmt_sm_pass& a, hipStream_t st);
+/* k_sm_class_emit + k_sm_ent_class */
+hipError_t osmt_launch_sm_emit(const osmt_sm_pass& a, hipStream_t st);
+/* bindings per class, one kind: pos[0 .. n) = styles of the entity's class, scanned (*tot the 64-bit total) */
+hipError_t osmt_launch_sm_bind_count(const uint32_t* ent_class, const uint32_t* class_off, uint32_t n, uint32_t* pos, unsigned long long* blk,
+                                     unsigned long long* tot, hipStream_t st);
+/* out[pos[i] ..) = the styles of entity i's class */
+hipError_t osmt_launch_sm_bind_emit(const uint32_t* ent_class, const uint32_t* class_off, const uint32_t* class_styles, uint32_t n, const uint32_t* pos,
+                                    uint32_t* out, hipStream_t st);
+
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

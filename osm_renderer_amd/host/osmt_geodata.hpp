@@ -58,6 +58,7 @@ class Tags {
   public:
     Tags(const uint32_t* kv, size_t n_ints, const char* strings) : kv_(kv), n_(n_ints / 4), strings_(strings) {}
     size_t size() const { return n_; }
+    const uint32_t* raw() const { return kv_; } /* size() quadruples (k_off, k_len, v_off, v_len) as the file has them */
     std::pair<std::string_view, std::string_view> get_kv(size_t i) const {
         const uint32_t* r = kv_ + 4 * i;
         return {std::string_view(strings_ + r[0], r[1]), std::string_view(strings_ + r[2], r[3])};
@@ -174,6 +175,10 @@ class GeodataReader {
     std::pair<const uint32_t*, size_t> tile_node_ids(size_t i) const { return ints_by_ref(tiles_.at(i) + 8); }
     std::pair<const uint32_t*, size_t> tile_way_ids(size_t i) const { return ints_by_ref(tiles_.at(i) + 16); }
     std::pair<const uint32_t*, size_t> tile_multipolygon_ids(size_t i) const { return ints_by_ref(tiles_.at(i) + 24); }
+
+    /* the string pool every tag points into: from behind the int pool to the end of the file */
+    const uint8_t* strings() const { return reinterpret_cast<const uint8_t*>(strings_); }
+    size_t string_bytes() const { return (size_t)(reinterpret_cast<const char*>(base_) + len_ - strings_); }
 
     /* every node's (lat, lon), packed for osmt_batch.nodes: one upload serves every tile of the file */
     std::vector<double> node_table() const {
@@ -345,6 +350,34 @@ struct GeodataDesc {
     }
     GeodataDesc(const GeodataDesc&) = delete;
     GeodataDesc& operator=(const GeodataDesc&) = delete;
+};
+
+/* The tags of a geodata file as osmt_register_tags takes them, with owning vectors: per kind the offsets and the
+ * (k_off, k_len, v_off, v_len) quadruples copied out of the int pool; the strings stay in the reader's mapping.  `desc` points
+ * into the vectors and into the reader: valid as long as both live and this object is not copied from. */
+struct TagsDesc {
+    std::vector<uint32_t> node_tag_off{0u}, node_tags, way_tag_off{0u}, way_tags, multipolygon_tag_off{0u}, multipolygon_tags;
+    osmt_tags_desc desc{};
+
+    explicit TagsDesc(const GeodataReader& r) {
+        auto append = [](std::vector<uint32_t>& off, std::vector<uint32_t>& flat, const Tags& t) {
+            flat.insert(flat.end(), t.raw(), t.raw() + 4 * t.size());
+            if (flat.size() / 4 >= 0xFFFFFFFFull) throw std::runtime_error("geodata file too large for 32-bit offsets");
+            off.push_back((uint32_t)(flat.size() / 4));
+        };
+        for (size_t i = 0; i < r.node_count(); ++i) append(node_tag_off, node_tags, r.node_tags(i));
+        for (size_t i = 0; i < r.way_count(); ++i) append(way_tag_off, way_tags, r.way_tags(i));
+        for (size_t i = 0; i < r.multipolygon_count(); ++i) append(multipolygon_tag_off, multipolygon_tags, r.multipolygon_tags(i));
+        desc.node_tag_off = node_tag_off.data(), desc.node_tags = node_tags.data();
+        desc.n_nodes = r.node_count(), desc.n_node_tags = node_tags.size() / 4;
+        desc.way_tag_off = way_tag_off.data(), desc.way_tags = way_tags.data();
+        desc.n_ways = r.way_count(), desc.n_way_tags = way_tags.size() / 4;
+        desc.multipolygon_tag_off = multipolygon_tag_off.data(), desc.multipolygon_tags = multipolygon_tags.data();
+        desc.n_multipolygons = r.multipolygon_count(), desc.n_multipolygon_tags = multipolygon_tags.size() / 4;
+        desc.strings = r.strings(), desc.n_string_bytes = r.string_bytes();
+    }
+    TagsDesc(const TagsDesc&) = delete;
+    TagsDesc& operator=(const TagsDesc&) = delete;
 };
 
 /* The table osmt_register_node_mercator takes: per node of latlon[n][2] = (lat, lon) in degrees the part of coords_to_xy

@@ -45,6 +45,9 @@ EXPORTS = [
     "osmt_label_positions_tiles_begin", "osmt_label_tile_batch_expand",
     "osmt_validate_area_label_bindings", "osmt_register_area_label_bindings", "osmt_scene_build_tile_labels_all",
     "osmt_scene_read_declined_anchors", "osmt_scene_read_tile_area_labels",
+    "osmt_validate_tags", "osmt_register_tags", "osmt_validate_selectors", "osmt_register_selectors", "osmt_match_selectors",
+    "osmt_match_free", "osmt_match_read_declined_numbers", "osmt_match_read", "osmt_register_style_bindings_matched",
+    "osmt_debug_match_hash_bits",
 ]
 
 
@@ -180,6 +183,19 @@ def load():
         L.osmt_scene_build_tile_labels_all.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, C.c_size_t]
         L.osmt_scene_read_declined_anchors.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.osmt_scene_read_tile_area_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    if hasattr(L, "osmt_match_selectors"):  # absent only from older variant builds loaded through OSMT_LIB
+        sz = C.POINTER(C.c_size_t)
+        L.osmt_validate_tags.argtypes = [C.POINTER(abi.TagsDesc), C.c_uint32, vp]
+        L.osmt_register_tags.argtypes = [vp, C.c_uint32, C.POINTER(abi.TagsDesc)]
+        L.osmt_validate_selectors.argtypes = [C.POINTER(abi.SelectorsDesc)]
+        L.osmt_register_selectors.argtypes = [vp, C.POINTER(abi.SelectorsDesc), C.POINTER(C.c_uint32)]
+        L.osmt_match_selectors.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(vp)]
+        L.osmt_match_free.argtypes = [vp]
+        L.osmt_match_free.restype = None
+        L.osmt_match_read_declined_numbers.argtypes = [vp, vp, C.c_size_t, sz]
+        L.osmt_match_read.argtypes = [vp, vp, vp, vp, sz, sz]
+        L.osmt_register_style_bindings_matched.argtypes = [vp, vp, C.c_uint8, C.c_uint8, vp, vp, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.osmt_debug_match_hash_bits.argtypes = [vp, C.c_uint32]
     if hasattr(L, "osmt_label_positions_tiles"):  # absent only from older variant builds loaded through OSMT_LIB
         L.osmt_validate_node_mercator.argtypes = [dp, C.c_size_t, C.c_uint32, vp]
         L.osmt_register_node_mercator.argtypes = [vp, C.c_uint32, dp]

@@ -426,6 +426,28 @@ class Context:
         d = index.as_desc()
         check(load().osmt_register_tile_index(self._h, geodata_id, C.byref(d)))
 
+    def register_tags(self, geodata_id, tags):
+        """osmt_register_tags: the tags of a registered geodata file (selmatch.Tags or a ctypes osmt_tags_desc)."""
+        d = tags.as_desc() if hasattr(tags, "as_desc") else tags
+        check(load().osmt_register_tags(self._h, geodata_id, C.byref(d)))
+
+    def register_selectors(self, selectors):
+        """osmt_register_selectors: appends a selmatch.SelectorSet; returns its id."""
+        d = selectors.as_desc()
+        out = C.c_uint32()
+        check(load().osmt_register_selectors(self._h, C.byref(d), C.byref(out)))
+        return out.value
+
+    def match_selectors(self, geodata_id, selectors_id, overrides=None):
+        """osmt_match_selectors: a selmatch.Match; raises selmatch.Declined with the values to supply as overrides."""
+        from . import selmatch
+
+        return selmatch.match(self, geodata_id, selectors_id, overrides)
+
+    def debug_match_hash_bits(self, bits):
+        """osmt_debug_match_hash_bits: the class table of later matches keeps only the low `bits` bits of the key hash."""
+        check(load().osmt_debug_match_hash_bits(self._h, bits))
+
     def register_style_bindings(self, bindings):
         """osmt_register_style_bindings: appends a styled.StyleBindings table; returns its id."""
         d = bindings.as_desc()
