@@ -33,6 +33,12 @@ extern "C" {
 #define OSMT_MAX_ZOOM 18u   /* src/tile.rs:5  MAX_ZOOM  */
 #define OSMT_MAX_SCALE 4u
 #define OSMT_MAX_DASHES 16u /* dash-pattern entries per op (stylesheets use <= 6) */
+/* Fill groups of ONE scene: a group is the 16 coverage words (64 bytes) of one (fill op, 32x16-pixel sub-tile of the op's
+ * window).  A list entry holds a group's place in the fill arena as a 32-bit word index, so a scene whose fills need 2^28
+ * groups or more (a 16 GiB fill arena) is refused with OSMT_UNSUPPORTED by every upload, build and host-buffer call, with
+ * the exact figure in osmt_last_error(): split the batch.  A tile-covering fill is 128 * scale^2 groups: 2048 at scale 4,
+ * where 131 072 such ops in one batch reach the limit. */
+#define OSMT_MAX_FILL_GROUPS (1ull << 28)
 
 typedef enum osmt_status {
     OSMT_OK = 0,
@@ -405,8 +411,10 @@ int osmt_render_scene_stages(osmt_ctx* ctx, osmt_scene* scene, uint32_t stage_ma
 /* Attaches the label pass of every tile of the scene (Drawer::draw_labels,
  * drawer.rs:107-125,221-262); osmt_render_scene then returns the pixels after
  * blend_unfinished_pixels(true).  NULL / n_labels == 0 detaches.  Coordinates must
- * be finite and |v| <= 2^20.  osmt_render_scene_f64 keeps returning the canvas
- * BEFORE labels. */
+ * be finite and |v| <= 2^20.  A text whose coverage window — its rows inside the label box [-W, 2W), times the
+ * columns its draw_line calls span — has more than 2^24 cells is refused with OSMT_UNSUPPORTED ("coverage window of
+ * C x R cells is too large"), and so is a batch whose windows add up to more than 2^31 cells: nothing is attached.
+ * osmt_render_scene_f64 keeps returning the canvas BEFORE labels. */
 int osmt_scene_set_labels(osmt_ctx* ctx, osmt_scene* scene, const osmt_label_batch* labels);
 /* Label statuses of the last osmt_render_scene (label_generation_statuses,
  * tile_pixels.rs:160-162): ok[i] = 1 if label i succeeded.  Synchronises the stream.  Before the first render after

@@ -29,6 +29,7 @@ STYLED_MAX_TILE_AREAS = 65536  # (entity, style) pairs of one tile of an osmt_st
 STYLED_LDS_AREAS = 2048  # up to here osmt_scene_build_styled sorts a tile in LDS
 STYLED_MULTIPOLYGON = 0x80000000  # osmt_styled_area.entity: the entity is a multipolygon
 MAX_SCALE = 4
+MAX_FILL_GROUPS = 1 << 28  # fill groups (fill op x sub-tile of its window) of one scene: 2^28 or more are refused
 QUERY_MAX_TILE_CANDIDATES = 1 << 20  # references of one kind osmt_scene_build_tiles gathers for one tile before dedup
 QUERY_LDS_CANDIDATES = 8192  # up to here a tile's candidates are sorted in LDS
 BINDINGS_NONE = 0xFFFFFFFF  # osmt_tile_batch.bindings_of_zoom: the zoom has no bindings

@@ -1265,6 +1265,12 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
         if (d.recs_per_vseg <= 0.0) d.recs_per_vseg = 1e-9;
         ++d.uploads;
     }
+    /* A list entry carries a fill's position in the fill arena as a 32-bit WORD index (osmt_ent::arena = group * 16, built by
+     * k_sublist and the fold path of k_raster): it holds 2^28 groups = 16 GiB of coverage words, no more.  Such a scene is
+     * refused here, before anything is allocated — a 64-bit position would widen osmt_ent and k_raster's register budget. */
+    if (groups >= OSMT_MAX_FILL_GROUPS)
+        return fail(OSMT_UNSUPPORTED, "scene needs %llu fill groups (>= 2^28 = %llu, the most a list entry's 32-bit word index reaches): split the batch",
+                    groups, (unsigned long long)OSMT_MAX_FILL_GROUPS);
     if (groups >= 0xFFFFFFFFull || recs >= 0xFFFFFFFFull)
         return fail(OSMT_UNSUPPORTED, "scene needs %llu fill groups / %llu stroke records (> 2^32): split the batch", groups, recs);
     size_t off = 0;

@@ -1904,7 +1904,9 @@ __global__ __launch_bounds__(SUBLIST_THREADS) void k_sublist(const osmt_tile_job
                 const uint32_t col_left = (uint32_t)__builtin_amdgcn_readlane((int)row_n, (int)sx);
                 const uint32_t pos = (uint32_t)__popcll(bal & lanes_below);
                 if (hit && pos < col_left) {
-                    /* FILL: word index of this sub-tile's 16 rows; STROKE: the op's first slot */
+                    /* FILL: word index of this sub-tile's 16 rows; STROKE: the op's first slot.  The word index is 32 bits
+                     * (fill_rows_body writes the same words with a size_t index): it cannot wrap because a scene of
+                     * OSMT_MAX_FILL_GROUPS = 2^28 groups or more is refused before its arenas exist (scene_size_arenas) */
                     e.arena = is_stroke ? arena0 : (arena0 + (sy - sr0) * ncols + (sx - c0)) * SUBH;
                     g_ent[(size_t)col_cur + pos] = e;
                 }
@@ -2158,7 +2160,9 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
                     t.opacity = hi->opacity;
                     t.aux = strk ? hi->aux : hi->image_id;
                     t.nv = strk ? hi->rec_cap : 0u;
-                    /* FILL: word index of this sub-tile's 16 rows (sr0 | c0 << 8 | ncols << 16); STROKE: the op's first slot */
+                    /* FILL: word index of this sub-tile's 16 rows (sr0 | c0 << 8 | ncols << 16); STROKE: the op's first slot.
+                     * 32 bits hold it: a scene has fewer than OSMT_MAX_FILL_GROUPS = 2^28 groups (scene_size_arenas refuses the
+                     * others), so group * SUBH < 2^32 */
                     t.arena = strk ? arena0
                                    : (arena0 + (sub / subs_per_row - (geom & 255u)) * ((geom >> 16) & 255u) + (sub % subs_per_row - ((geom >> 8) & 255u))) * SUBH;
                     t.stage = 0u;

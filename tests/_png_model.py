@@ -92,11 +92,17 @@ def paeth_filter(rgb):
     return ((raw - pred) & 255).astype(np.uint8)
 
 class Bits:
-    def __init__(self): self.acc = 0; self.n = 0
-    def put(self, v, nb): self.acc |= v << self.n; self.n += nb
+    """LSB-first bit stream; whole bytes leave the accumulator every 4096 bits (one growing integer made a 1024-wide tile quadratic)"""
+    def __init__(self): self.acc = 0; self.n = 0; self.done = []
+    def put(self, v, nb):
+        self.acc |= v << self.n; self.n += nb
+        if self.n >= 4096:
+            k = self.n // 8
+            self.done.append((self.acc & ((1 << (8 * k)) - 1)).to_bytes(k, 'little'))
+            self.acc >>= 8 * k; self.n -= 8 * k
     def bytes(self):
         nb = (self.n + 7) // 8
-        return self.acc.to_bytes(nb, 'little')
+        return b''.join(self.done) + self.acc.to_bytes(nb, 'little')
 
 def lz_applies(W, H):
     """the kernel's fast path (k_png_encode_fast): the only one that searches for matches"""

@@ -141,7 +141,7 @@ def test_equal_keys_across_kinds_put_the_multipolygon_first(world):
     assert al.order_one_sort(W, M, st, w.way_gids(), w.mp_gids()) == order
 
 
-@pytest.mark.parametrize("scale", [1, 2])
+@pytest.mark.parametrize("scale", [1, 2, 3, 4])
 def test_mirror_with_the_hosts_libm_and_anchors(world, scale):
     """the defaults of the mirror — project_libm and osmt::HostAnchors — against Python floats and the anchors' own mirror"""
     w, r, refs = world

@@ -221,7 +221,7 @@ def _tiles_of(W):
     return t
 
 
-@pytest.mark.parametrize("scale", [1, 2])
+@pytest.mark.parametrize("scale", [1, 2, 3, 4])
 def test_built_batch_equals_the_mirror(gpu_ctx, shapes, scale):
     W = shapes
     tiles = _tiles_of(W)

@@ -95,17 +95,85 @@ def test_rasterizer_edge_cases(gpu_ctx, oracle):
     _check(gpu_ctx, oracle, dl, tl.build(), (), "edges")
 
 
-@pytest.mark.parametrize("scale", [1, 2])
+# scales 3 and 4: a fixed count per tile (20 * scale^2 labels take 14 s and 28 s to generate), and seeds at which the
+# oracle alone gives both outcomes (179 of 180 labels succeed at either scale)
+SYNTHETIC = {1: (20, 6), 2: (80, 7), 3: (30, 8), 4: (30, 11)}  # scale: (labels per tile, seed)
+
+
+@pytest.mark.parametrize("scale", [1, 2, 3, 4])
 def test_synthetic_labels_over_area_tiles(gpu_ctx, oracle, icon_ctx, scale):
     ids, imgs = icon_ctx
     n = 6
     dl = synth.make_tiles(synth.config_tiles(n), n_poly=12, n_line=10, scale=scale)
-    ll = labels.make_labels(n, labels_per_tile=20 * scale * scale, scale=scale, seed=5 + scale, n_images=3,
+    per_tile, seed = SYNTHETIC[scale]
+    assert scale > 2 or (per_tile, seed) == (20 * scale * scale, 5 + scale)
+    ll = labels.make_labels(n, labels_per_tile=per_tile, scale=scale, seed=seed, n_images=3,
                             image_sizes=[i.shape[:2] for i in [imgs[k] for k in ids]])
     # make_labels numbers images 0..n_images-1: map to the registered ids
     ll.labels["image_id"] = np.array(ids, dtype=np.uint32)[ll.labels["image_id"] % 3]
     got, st = _check(gpu_ctx, oracle, dl, ll, imgs, f"synthetic scale {scale}")
     assert 0 < st.sum() < len(st)  # both outcomes occur
+
+
+LABEL_LDS_CELLS = 576  # OSMT_LABEL_LDS_CELLS: a window of more columns takes k_label_cover_wide
+
+
+def border_labels(scale, ids):
+    """One tile's labels at the borders of the label box [-W, 2W) and of the tile, two text windows wider than the LDS band
+    (the second collides with the first), one that spans the whole box.  Returns (TileLabels, indices of the wide ones)."""
+    W = 256 * scale
+    tl = labels.TileLabels()
+    tl.label(icon=(ids[0], -W + 3.0, 40.0))            # 16 x 16, across the left border of the box
+    tl.label(icon=(ids[1], 2 * W - 4.5, W / 2))        # across the right border
+    tl.label(icon=(ids[0], W / 2, -W + 2.0))           # across the top
+    tl.label(icon=(ids[2], W / 2 + 0.5, 2 * W - 2.0))  # across the bottom
+    tl.label(icon=(ids[0], 2 * W - 1.0, -W + 1.0))     # a corner of the box
+    tl.label(text=_text((200, 20, 20), -W - 10, 60, -W + 30, 90))
+    tl.label(text=_text((20, 200, 20), 2 * W - 30, 50, 2 * W + 25, 90))
+    tl.label(text=_text((20, 20, 200), 100, -W - 20, 140, -W + 15))
+    tl.label(text=_text((90, 90, 20), 200, 2 * W - 15, 260, 2 * W + 40))
+    tl.label(text=_text((1, 2, 3), -W - 40, -W - 40, -W - 1, -W - 1))  # wholly outside the box: succeeds, draws nothing
+    tl.label(text=_text((120, 0, 120), 2 * W - 20.5, 2 * W - 20.25, 2 * W - 1.5, 2 * W - 0.75))  # the last rows and columns of the box
+    tl.label(text=_text((0, 120, 120), 2 * W - 10, 2 * W - 10, 2 * W - 5, 2 * W - 5))            # collides with it there
+    tl.label(icon=(ids[0], W - 8.0, W - 8.0), text=_text((0, 0, 0), W - 60, W - 40, W - 20, W - 20))  # the tile's far corner
+    tl.label(text=_text((250, 250, 0), W - 30, W - 30, W + 30, W + 30))  # collides with its text
+    tl.label(icon=(ids[1], 5.0, 3.0))  # across the tile's first row and column
+    wide = [15, 16, 17]
+    tl.label(text=_text((200, 0, 90), -300, W // 2, 700, W // 2 + 12))  # 1001 columns
+    tl.label(text=_text((0, 90, 200), 50, W // 2 + 6, 950, W // 2 + 20))  # 901 columns, collides with the one before
+    tl.label(text=_text((60, 60, 60), -W + 1, W - 70, 2 * W - 2, W - 62))  # the whole width of the box
+    assert all(x1 - x0 + 1 > LABEL_LDS_CELLS for x0, x1 in ((-300, 700), (50, 950), (-W + 1, 2 * W - 2)))
+    return tl, wide
+
+
+@pytest.mark.parametrize("scale", [3, 4])
+def test_label_box_borders_wide_windows_and_the_window_limit(gpu_ctx, oracle, icon_ctx, scale):
+    """The ownership map of k_label_resolve is (3W)^2 bits in global memory at these scales, 72 or 96 words per row; icons and
+    text windows on each of its borders, windows of more than OSMT_LABEL_LDS_CELLS columns (k_label_cover_wide), and one text
+    whose window passes 2^24 cells: refused with OSMT_UNSUPPORTED, nothing attached, the scene renders as before."""
+    from osm_renderer_amd import abi
+    from osm_renderer_amd.lib import OsmtError
+
+    ids, imgs = icon_ctx
+    W = 256 * scale
+    tb = TileBuilder(scale=scale, canvas=(255, 250, 240))
+    tb.fill([[(W // 3, W // 3), (W + 5, W // 3), (W + 5, W + 5), (W // 3, W + 5), (W // 3, W // 3)]], (100, 140, 180), 0.7)
+    dl = tb.build()
+    big = labels.TileLabels()
+    big.label(text=_text((9, 9, 9), 10, 10, 20, 20))
+    big.label(text=_text((5, 5, 5), -10000, -W, 10000, 2 * W - 1))  # 3W rows x 20 001 columns
+    assert 3 * W * 20001 > 1 << 24
+    scene = gpu_ctx.upload(dl)
+    plain = gpu_ctx.render(scene).cpu().numpy()
+    with pytest.raises(OsmtError) as e:
+        scene.set_labels(big.build())
+    assert e.value.code == abi.UNSUPPORTED and "coverage window" in str(e.value) and "too large" in str(e.value), str(e.value)
+    assert np.array_equal(gpu_ctx.render(scene).cpu().numpy(), plain)
+    scene.free()
+    tl, wide = border_labels(scale, ids)
+    got, st = _check(gpu_ctx, oracle, dl, tl.build(), imgs, f"borders scale {scale}")
+    assert st[wide].tolist() == [1, 0, 1] and st[:11].tolist() == [1] * 11 and st[11:15].tolist() == [0, 1, 0, 1]
+    assert (got != plain).any(axis=-1).sum() > 1000  # the labels reach the tile
 
 
 def test_labels_can_be_detached_and_rerendered(gpu_ctx, oracle):

@@ -40,9 +40,10 @@ def test_device_png_matches_model_and_decodes(gpu_ctx):
     assert lens[1] < 3000 and lens[0] > 196608  # flat tile ~2 KB; noise is slightly larger than raw RGB
 
 
-@pytest.mark.parametrize("scale", [1, 2])
+@pytest.mark.parametrize("scale", [1, 2, 3, 4])
 def test_render_batch_png_end_to_end(gpu_ctx, oracle, scale):
-    n = 5
+    """scales 3 and 4: widths 768 and 1024 take the two-pass kernel, here on a rendered batch with a label pass"""
+    n = 5 if scale <= 2 else 3  # (fewer tiles: the byte model of a 1024-wide file takes a second)
     dl = synth.make_tiles(synth.config_tiles(n), n_poly=20, n_line=15, scale=scale)
     ll = labels.make_labels(n, labels_per_tile=6, scale=scale, seed=8)
     files = gpu_ctx.render_batch_png(dl, ll)
@@ -55,6 +56,11 @@ def test_render_batch_png_end_to_end(gpu_ctx, oracle, scale):
     png = files[0]
     idat_len = int.from_bytes(png[33:37], "big")
     assert len(zlib.decompress(png[41 : 41 + idat_len])) == dl.dim * (3 * dl.dim + 1)
+    if scale >= 3:  # byte for byte the model's file, and every file's stream inflates to the filtered rows
+        for i, png in enumerate(files):
+            assert png == _png_model.encode(want[i]), f"tile {i}: bytes differ from the model"
+            idat_len = int.from_bytes(png[33:37], "big")
+            assert len(zlib.decompress(png[41 : 41 + idat_len])) == dl.dim * (3 * dl.dim + 1)
 
 
 @pytest.mark.parametrize("shape", [(70, 128), (33, 768), (5, 1024), (64, 64)])

@@ -140,7 +140,7 @@ def test_shaped_records_equal_the_model_bit_for_bit(gpu_ctx, tables):
     scene.free()
 
 
-@pytest.mark.parametrize("scale", [1, 2])
+@pytest.mark.parametrize("scale", [1, 2, 4])
 def test_string_form_equals_text_form(gpu_ctx, tables, scale):
     syn, ids = tables[2], tables[3]
     kw = dict(labels_per_tile=24, scale=scale, seed=60 + scale, n_images=len(ids), image_sizes=SIZES, line_frac=0.4, empty_frac=0.05)

@@ -44,7 +44,8 @@ def _build_both(gpu_ctx, r, gid, tiles, st, pool, first, scale=1, use_caps=True)
     return scene, scene.read_display_list(), want
 
 
-@pytest.mark.parametrize("seed,n_ways,scale,use_caps,with_oracle", [(13, 80, 1, True, True), (14, 50, 2, False, False)])
+@pytest.mark.parametrize("seed,n_ways,scale,use_caps,with_oracle", [(13, 80, 1, True, True), (14, 50, 2, False, False),
+                                                                    (13, 80, 3, True, True), (14, 50, 4, False, False)])
 def test_built_list_equals_the_scene_builders_bit_for_bit(tmp_path, gpu_ctx, oracle, seed, n_ways, scale, use_caps, with_oracle):
     r, rng = _scene(tmp_path, oracle, seed, n_ways=n_ways)
     st, pool = _random_styles(rng, 16 if with_oracle else 12, n_images=2)
@@ -69,7 +70,7 @@ def test_built_list_equals_the_scene_builders_bit_for_bit(tmp_path, gpu_ctx, ora
     px = gpu_ctx.render(scene).cpu().numpy()
     scene.check()
     assert np.array_equal(px, gpu_ctx.render_batch_host(want))
-    assert len(np.unique(px.reshape(-1, 4), axis=0)) > 100
+    assert len(np.unique(np.ascontiguousarray(px).view(np.uint32))) > 100  # distinct RGBA values
     if with_oracle:
         dl_o = DisplayList(want.jobs, want.ops.copy(), want.rings, want.coords, want.dashes, abi.COORD_NODE_REF, scale, nodes=want.nodes)
         dl_o.ops["image_id"] -= first_img  # the oracle's icon list starts at 0

@@ -71,8 +71,8 @@ def _assert_instances(got, want):
     assert np.array_equal(_u8(got), _u8(want))  # and the unused entries are zero, as documented
 
 
-@pytest.mark.parametrize("scale", [1, 2])
-@pytest.mark.parametrize("n_tiles, seed", [(1, 5), (8, 6), (300, 7)])
+@pytest.mark.parametrize("n_tiles, seed, scale", [(1, 5, 1), (8, 6, 1), (300, 7, 1), (1, 5, 2), (8, 6, 2), (300, 7, 2),
+                                                 (1, 5, 4), (8, 6, 4), (70, 7, 4)])  # (scale 4: 70 tiles, not 300 — 1.2 GB of pixels to read back)
 def test_instances_equal_the_model_and_everything_downstream_follows(gpu_ctx, oracle, tables, scale, n_tiles, seed):
     syn = tables[1]
     dl, tl = _case(tables, scale, n_tiles, seed + 10 * scale)
@@ -97,7 +97,7 @@ def test_instances_equal_the_model_and_everything_downstream_follows(gpu_ctx, or
     ll = gl.to_label_list(syn)
     assert segs.shape == ll.segs.shape and np.array_equal(_bits(segs), _bits(ll.segs))
     images = _images(tables)
-    sub = list(range(n_tiles)) if n_tiles <= 8 else list(range(0, n_tiles, 300 // 12))
+    sub = list(range(n_tiles)) if n_tiles <= 8 else list(range(0, n_tiles, n_tiles // 12))
     want, wst = oracle.render_batch(dl.subset(sub), images=images, threads=min(8, len(sub)), labels=ll.subset(sub), want_status=True)
     lab_sub = np.concatenate([np.arange(int(tl.job_label_off[i]), int(tl.job_label_off[i + 1])) for i in sub])
     assert np.array_equal(st[lab_sub], wst)

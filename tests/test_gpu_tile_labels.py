@@ -203,7 +203,7 @@ def _tiles_of(w):
     return t
 
 
-@pytest.mark.parametrize("scale", [1, 2])
+@pytest.mark.parametrize("scale", [1, 2, 3, 4])
 def test_built_batch_equals_the_mirror(gpu_ctx, shapes, scale):
     w = shapes
     tiles = _tiles_of(w)

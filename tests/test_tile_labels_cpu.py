@@ -140,7 +140,7 @@ def test_node_index_desc_reads_the_node_lists(world):
     tl.shim().tl_index_free(h)
 
 
-@pytest.mark.parametrize("scale", [1, 2])
+@pytest.mark.parametrize("scale", [1, 2, 3, 4])
 def test_mirror_equals_the_restatement(world, scale):
     r, refs, gids, nodes, bind = world
     st = _styles()
