@@ -1149,6 +1149,65 @@ int osmt_register_style_bindings_matched(osmt_ctx* ctx, osmt_match* match, uint8
  * the low `bits` bits of the key hash (32 = all; 0 puts every key into one probe chain).  The result must not change. */
 int osmt_debug_match_hash_bits(osmt_ctx* ctx, uint32_t bits);
 
+/* ---- label bindings from tags: per-class expansion and tag text on the GPU --------------------------------------- */
+/* What osmt_register_label_bindings / osmt_register_area_label_bindings take finished — per entity the (label style, text id)
+ * pairs and the text pool — made on the device (csrc/osmt_labelbind.hip) from the match, the registered tags and label
+ * bindings given PER CLASS.  An entity of class c gets, in push order, one osmt_label_binding per element of c's list: `style`
+ * is copied; `text` is OSMT_TEXT_NONE when text_key is OSMT_TEXT_NONE or the entity has no tag whose key equals the key's
+ * bytes (Tags::get_by_key(&text_style.text), text_placer.rs:42-45, reader.rs:351-373; &str order: unsigned bytes, a proper
+ * prefix sorts first), else the text of that tag's value.  The lookup is made whatever the style's has_* bytes say.
+ * The text pool: a text is a distinct value range (v_off, v_len) among the tags some binding of THIS table uses (the
+ * reference's saver interns whole strings, saver.rs:141-152: in its files equal strings are equal ranges).  Texts are
+ * numbered by their lowest-numbered user in the table's tag order — the node tags for the node table; the way tags, then the
+ * multipolygon tags for the area table — a pure function of the input.  A text's chars are the value decoded as UTF-8; an
+ * empty value is a text of 0 chars, not OSMT_TEXT_NONE.  A USED value that is not well-formed UTF-8 (Unicode Table 3-7: no
+ * overlong forms, no surrogates, nothing above U+10FFFF, no sequence cut off by the end of the value) is OSMT_INVALID_ARG
+ * naming the lowest-numbered offending tag (kind, entity, v_off), and nothing is registered; a value no binding uses is not
+ * looked at; no byte at or past v_off + v_len is read. */
+
+#define OSMT_LABEL_TEXT_KEYS_MAX 256u /* keys of one osmt_class_label_bindings_desc */
+
+typedef struct osmt_class_label_binding { /* 8 bytes: one element style_entities pushes for every member of the class */
+    uint32_t style;                       /* id from osmt_register_label_styles */
+    uint32_t text_key;                    /* index into the descriptor's keys (the tag text_style.text names), or OSMT_TEXT_NONE */
+} osmt_class_label_binding;
+
+typedef struct osmt_class_label_bindings_desc {
+    uint8_t zoom_lo, zoom_hi, _pad[6]; /* inclusive */
+    const uint32_t* class_off;         /* [n_classes + 1] into bindings, push order inside a class */
+    const osmt_class_label_binding* bindings;
+    size_t n_classes, n_bindings;
+    const uint32_t* key_off; /* [n_keys + 1] into key_bytes; keys need be neither sorted nor distinct; an empty key is legal */
+    const uint8_t* key_bytes;
+    size_t n_keys, n_key_bytes; /* n_keys <= OSMT_LABEL_TEXT_KEYS_MAX */
+} osmt_class_label_bindings_desc;
+
+/* The checks the two registrations below run first, without a device.  `match` and `ctx` may be NULL: the class count is
+ * then not compared and the style ids are not looked up.  OSMT_INVALID_ARG: a match of another context or a declined one;
+ * n_classes that is not the match's class count; offsets that do not start at 0, decrease or do not end at the pool length; a
+ * style id that is not registered at the time of the call; a text_key that is neither below n_keys nor OSMT_TEXT_NONE; a bad
+ * zoom range.  OSMT_UNSUPPORTED with the figure: more than OSMT_LABEL_TEXT_KEYS_MAX keys; pools beyond 32-bit indices.
+ * Lists of classes that hold no entity of the table's kinds are validated and otherwise unused. */
+int osmt_validate_class_label_bindings(const osmt_class_label_bindings_desc* d, osmt_match* match, osmt_ctx* ctx);
+/* The node table: an id of the kind osmt_register_label_bindings returns, for the geodata id of the match; the device table
+ * has exactly the layout that call makes and does not depend on the match after the call returns.  Beyond the validator:
+ * OSMT_INVALID_ARG for what osmt_validate_label_bindings demands of the geodata id and for ill-formed UTF-8 (above);
+ * OSMT_UNSUPPORTED with the figure for more than 2^32 - 2 bindings, 2^32 - 1 or more texts or chars. */
+int osmt_register_label_bindings_matched(osmt_ctx* ctx, osmt_match* match, const osmt_class_label_bindings_desc* d, uint32_t* out_bindings_id);
+/* The area table (ways + multipolygons): an id of the kind osmt_register_area_label_bindings returns; the geodata id needs
+ * what osmt_validate_area_label_bindings demands (tile index, Mercator factors).  Otherwise as above, the binding limit per
+ * kind. */
+int osmt_register_area_label_bindings_matched(osmt_ctx* ctx, osmt_match* match, const osmt_class_label_bindings_desc* d, uint32_t* out_bindings_id);
+/* Inspection of ANY registered label bindings table, host-made ones included.  counts = { bindings, texts, chars } is always
+ * set; NULL outputs ask for sizes; caps bound what is written (a smaller cap with a non-NULL output is OSMT_INVALID_ARG);
+ * node_off gets n_nodes + 1 entries, text_off n_texts + 1. */
+int osmt_read_label_bindings(osmt_ctx* ctx, uint32_t id, uint32_t* node_off, osmt_label_binding* bindings, uint32_t* text_off, uint32_t* chars,
+                             const size_t caps[3], size_t counts[3]);
+/* The same for an area table; counts = { way bindings, multipolygon bindings, texts, chars }. */
+int osmt_read_area_label_bindings(osmt_ctx* ctx, uint32_t id, uint32_t* way_off, osmt_label_binding* way_bindings, uint32_t* multipolygon_off,
+                                  osmt_label_binding* multipolygon_bindings, uint32_t* text_off, uint32_t* chars, const size_t caps[4],
+                                  size_t counts[4]);
+
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */
 int osmt_project(osmt_ctx* ctx, const double* latlon, size_t n, uint8_t zoom, uint32_t tile_x, uint32_t tile_y,

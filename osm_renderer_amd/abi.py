@@ -572,6 +572,31 @@ class MatchClass(C.Structure):
                 ("has_layer", C.c_uint8), ("_pad", C.c_uint8 * 2)]
 
 
+LABEL_TEXT_KEYS_MAX = 256  # keys of one osmt_class_label_bindings_desc
+
+
+class ClassLabelBinding(C.Structure):
+    _fields_ = [("style", C.c_uint32), ("text_key", C.c_uint32)]
+
+
+class ClassLabelBindingsDesc(C.Structure):
+    _fields_ = [
+        ("zoom_lo", C.c_uint8),
+        ("zoom_hi", C.c_uint8),
+        ("_pad", C.c_uint8 * 6),
+        ("class_off", C.POINTER(C.c_uint32)),
+        ("bindings", C.POINTER(ClassLabelBinding)),
+        ("n_classes", C.c_size_t),
+        ("n_bindings", C.c_size_t),
+        ("key_off", C.POINTER(C.c_uint32)),
+        ("key_bytes", C.POINTER(C.c_uint8)),
+        ("n_keys", C.c_size_t),
+        ("n_key_bytes", C.c_size_t),
+    ]
+
+
+assert C.sizeof(ClassLabelBinding) == 8
+assert C.sizeof(ClassLabelBindingsDesc) == 72
 assert C.sizeof(TagsDesc) == 112
 assert C.sizeof(SelectorTest) == 32
 assert C.sizeof(SelectorRec) == 16

@@ -29,6 +29,7 @@
 #include "osmt_geom.h"
 #include "osmt_internal.h"
 #include "osmt_numparse.h" /* osmt_bytes_cmp: the key order of osmt_validate_tags */
+#include "osmt_utf8.h"     /* the byte a refused tag value stops the decoder at */
 #include "osmt_png_table.h" /* PNG_LMAX, PNG_BLOCK_HDR_BITS: the slot bound */
 #include "../host/osmt_textplacer.hpp" /* osmt::validate_text_labels */
 #include "../host/osmt_textshaper.hpp" /* osmt::validate_font, osmt::validate_string_labels */
@@ -149,7 +150,7 @@ struct osmt_ctx {
         /* its tags (osmt_register_tags): at most one table, same rules */
         void* d_tags = nullptr;
         osmt_sm_tags_dev tags{};
-        size_t tags_string_bytes = 0;
+        size_t tags_string_bytes = 0, n_node_tags = 0, n_way_tags = 0;
     };
     std::vector<geodata_host> geodata;
     /* the selector sets of osmt_register_selectors: append-only, one device allocation each that never moves */
@@ -174,6 +175,7 @@ struct osmt_ctx {
         uint8_t zoom_lo = 0, zoom_hi = 0;
         void* d_pool = nullptr;
         osmt_tl_bind_dev dev{};
+        size_t n_nodes = 0, n_bindings = 0, n_texts = 0, n_chars = 0; /* osmt_read_label_bindings */
     };
     std::vector<label_bindings_host> label_bindings;
     /* the tables of osmt_register_area_label_bindings, under the same rules */
@@ -182,6 +184,7 @@ struct osmt_ctx {
         uint8_t zoom_lo = 0, zoom_hi = 0;
         void* d_pool = nullptr;
         osmt_al_bind_dev dev{};
+        size_t n_ways = 0, n_mps = 0, n_way_bindings = 0, n_mp_bindings = 0, n_texts = 0, n_chars = 0; /* osmt_read_area_label_bindings */
     };
     std::vector<area_label_bindings_host> area_label_bindings;
     /* the label styles of osmt_register_label_styles: records and ranks, replaced like the style table when it has grown */
@@ -3503,6 +3506,7 @@ static int register_label_bindings_body(osmt_ctx* ctx, const osmt_label_bindings
     h.dev.bindings = (const osmt_label_binding*)(pool + o_b);
     h.dev.text_off = (const uint32_t*)(pool + o_to);
     h.dev.chars = (const uint32_t*)(pool + o_c);
+    h.n_nodes = n_nodes, h.n_bindings = b->n_bindings, h.n_texts = b->n_texts, h.n_chars = b->n_chars;
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->label_bindings.size() + 1 >= 0xFFFFFFFFull) {
         (void)hipFree(pool);
@@ -4474,6 +4478,8 @@ static int register_area_label_bindings_body(osmt_ctx* ctx, const osmt_area_labe
     h.dev.mp_bind = (const osmt_label_binding*)(pool + o_mb);
     h.dev.text_off = (const uint32_t*)(pool + o_to);
     h.dev.chars = (const uint32_t*)(pool + o_c);
+    h.n_ways = n_ways, h.n_mps = n_mps, h.n_way_bindings = b->n_way_bindings, h.n_mp_bindings = b->n_multipolygon_bindings;
+    h.n_texts = b->n_texts, h.n_chars = b->n_chars;
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->area_label_bindings.size() + 1 >= 0xFFFFFFFFull) {
         (void)hipFree(pool);
@@ -6589,6 +6595,7 @@ int register_tags_body(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tags_desc*
     ctx->geodata[geodata_id].d_tags = pool;
     ctx->geodata[geodata_id].tags = d;
     ctx->geodata[geodata_id].tags_string_bytes = t->n_string_bytes;
+    ctx->geodata[geodata_id].n_node_tags = t->n_node_tags, ctx->geodata[geodata_id].n_way_tags = t->n_way_tags;
     return OSMT_OK;
 }
 
@@ -7085,6 +7092,369 @@ int osmt_debug_match_hash_bits(osmt_ctx* ctx, uint32_t bits) {
         std::lock_guard<std::mutex> lk(ctx->mu);
         ctx->match_hash_bits = bits;
         return (int)OSMT_OK;
+    });
+}
+
+} /* extern "C" */
+
+/* ---- label bindings per class (include/osmtile.h, csrc/osmt_labelbind.hip) ----------------------------------------- */
+namespace {
+
+int validate_class_label_bindings(const osmt_class_label_bindings_desc* d, osmt_match* m, osmt_ctx* ctx) {
+    const char* who = "label bindings per class";
+    if (!d) return fail(OSMT_INVALID_ARG, "%s: the descriptor is NULL", who);
+    if (m) {
+        if (ctx && m->ctx != ctx) return fail(OSMT_INVALID_ARG, "%s: the match belongs to another context", who);
+        if (!m->complete) return fail(OSMT_INVALID_ARG, "%s: the match is in the declined state", who);
+    }
+    if (d->zoom_lo > d->zoom_hi || d->zoom_hi > OSMT_MAX_ZOOM)
+        return fail(OSMT_INVALID_ARG, "%s: zoom range %u..%u (zoom_lo <= zoom_hi <= %u)", who, d->zoom_lo, d->zoom_hi, OSMT_MAX_ZOOM);
+    if (m && d->n_classes != m->n_classes) return fail(OSMT_INVALID_ARG, "%s: %zu classes, the match has %zu", who, d->n_classes, m->n_classes);
+    if (d->n_keys > OSMT_LABEL_TEXT_KEYS_MAX)
+        return fail(OSMT_UNSUPPORTED, "%s: %zu keys (> OSMT_LABEL_TEXT_KEYS_MAX = %u)", who, d->n_keys, OSMT_LABEL_TEXT_KEYS_MAX);
+    if (d->n_classes >= 0xFFFFFFFFull || d->n_bindings >= 0xFFFFFFFFull || d->n_key_bytes >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "%s: %zu classes, %zu bindings, %zu key bytes: too large for 32-bit indices", who, d->n_classes, d->n_bindings,
+                    d->n_key_bytes);
+    if (!d->class_off || !d->key_off || (d->n_bindings && !d->bindings) || (d->n_key_bytes && !d->key_bytes))
+        return fail(OSMT_INVALID_ARG, "%s: NULL array (every offset array has at least its first entry)", who);
+    int rc = check_offsets_of(who, "class_off", d->class_off, d->n_classes, d->n_bindings);
+    if (rc == OSMT_OK) rc = check_offsets_of(who, "key_off", d->key_off, d->n_keys, d->n_key_bytes);
+    if (rc != OSMT_OK) return rc;
+    size_t n_styles = SIZE_MAX;
+    if (ctx) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        n_styles = ctx->label_styles.size();
+    }
+    for (size_t i = 0; i < d->n_bindings; ++i) {
+        const osmt_class_label_binding& b = d->bindings[i];
+        if (b.style >= n_styles)
+            return fail(OSMT_INVALID_ARG, "%s: bindings[%zu].style = %u is not a registered label style (%zu styles)", who, i, b.style, n_styles);
+        if (b.text_key != OSMT_TEXT_NONE && b.text_key >= d->n_keys)
+            return fail(OSMT_INVALID_ARG, "%s: bindings[%zu].text_key = %u is neither one of the %zu keys nor OSMT_TEXT_NONE", who, i, b.text_key, d->n_keys);
+    }
+    return OSMT_OK;
+}
+
+int label_bindings_matched_body(osmt_ctx* ctx, osmt_match* m, const osmt_class_label_bindings_desc* d, uint32_t* out_id, bool area) {
+    const char* who = area ? "area label bindings per class" : "label bindings per class";
+    if (!ctx || !m || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    int rc = validate_class_label_bindings(d, m, ctx);
+    if (rc != OSMT_OK) return rc;
+    osmt_ctx::geodata_host geo;
+    uint32_t hash_bits = 32;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        geo = ctx->geodata[m->geodata_id]; /* a match exists only for a registered file with tags */
+        hash_bits = ctx->match_hash_bits;
+    }
+    if (area && !geo.d_index) return fail(OSMT_INVALID_ARG, "%s: geodata id %u has no tile index (osmt_register_tile_index)", who, m->geodata_id);
+    if (area && !geo.d_factors)
+        return fail(OSMT_INVALID_ARG, "%s: geodata id %u has no Mercator factors (osmt_register_node_mercator)", who, m->geodata_id);
+    HIP_TRY(hipSetDevice(ctx->device));
+    /* the device copy of the keys starts every key on a 4-byte boundary (k_lb_emit compares whole dwords); declared in front of
+     * the guard, whose destructor waits for the stream that may still read them */
+    std::vector<uint2> h_keys(d->n_keys);
+    std::vector<uint8_t> h_key_bytes;
+    struct work_guard {
+        osmt_ctx* ctx;
+        hipStream_t st = nullptr;
+        char* work[3] = {nullptr, nullptr, nullptr};
+        char* pool = nullptr; /* the table, until it is registered */
+        ~work_guard() {
+            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers */
+            for (char* p : work) dev_free(ctx, p);
+            if (pool) (void)hipFree(pool);
+            stream_release(ctx, st);
+        }
+    } wg{ctx};
+    HIP_TRY(stream_acquire(ctx, &wg.st));
+    hipStream_t st = wg.st;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 4), 256);
+        return o;
+    };
+    auto alloc = [&](char** p, const char* what) {
+        const hipError_t e = dev_alloc(ctx, (void**)p, off + 256);
+        if (e == hipSuccess) return (int)OSMT_OK;
+        *p = nullptr;
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the %s (%s) failed: %s", off, who, what, hipGetErrorString(e));
+    };
+    /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the stages, one line on stderr */
+    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    enum { EV_COUNT0, EV_COUNT1, EV_EMIT0, EV_EMIT1, EV_TEXTS1, EV_MEASURE0, EV_MEASURE1, EV_DECODE0, EV_DECODE1, EV_PATCH1, EV_N };
+    hipEvent_t ev[EV_N] = {};
+    struct ev_guard {
+        hipEvent_t* ev;
+        ~ev_guard() {
+            for (int i = 0; i < EV_N; ++i)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } evg{ev};
+    if (trace)
+        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+
+    /* the kinds of the table and its tags: the node table numbers the node tags, the area table the way tags, then the
+     * multipolygon tags */
+    const size_t first0 = area ? m->n_nodes : 0, n0 = area ? m->n_ways : m->n_nodes, first1 = m->n_nodes + m->n_ways, n1 = area ? m->n_mps : 0;
+    const size_t tag_base = area ? geo.n_node_tags : 0, n_tt = area ? (size_t)geo.tags.n_tags - geo.n_node_tags : geo.n_node_tags;
+    const size_t n_cls = d->n_classes, n_keys = d->n_keys;
+    for (size_t k = 0; k < n_keys; ++k) {
+        const uint32_t a = d->key_off[k], len = d->key_off[k + 1] - a;
+        h_keys[k] = make_uint2((uint32_t)h_key_bytes.size(), len);
+        h_key_bytes.insert(h_key_bytes.end(), d->key_bytes + a, d->key_bytes + a + len);
+        h_key_bytes.resize(align_up(h_key_bytes.size(), 4), 0);
+    }
+    size_t table = 2;
+    while (table < 2 * n_tt) table <<= 1;
+    const size_t o_co = carve((n_cls + 1) * 4), o_cb = carve(d->n_bindings * 8), o_k = carve(n_keys * 8), o_kb = carve(h_key_bytes.size());
+    const size_t o_p0 = carve((n0 + 1) * 4), o_p1 = carve((n1 + 1) * 4), o_blk = carve((std::max(std::max(n0, n1), n_tt) / 256 + 1) * 8);
+    const size_t o_tot = carve(OSMT_LB_T_N * 8), o_used = carve(n_tt * 4), o_ts = carve(n_tt * 4), o_fp = carve((n_tt + 1) * 4);
+    const size_t o_tab = carve(table * 4), o_low = carve(table * 4);
+    rc = alloc(&wg.work[0], "classes and tags");
+    if (rc != OSMT_OK) return rc;
+    char* w = wg.work[0];
+    HIP_TRY(hipMemcpyAsync(w + o_co, d->class_off, (n_cls + 1) * 4, hipMemcpyHostToDevice, st));
+    if (d->n_bindings) HIP_TRY(hipMemcpyAsync(w + o_cb, d->bindings, d->n_bindings * 8, hipMemcpyHostToDevice, st));
+    if (n_keys) HIP_TRY(hipMemcpyAsync(w + o_k, h_keys.data(), n_keys * 8, hipMemcpyHostToDevice, st));
+    if (!h_key_bytes.empty()) HIP_TRY(hipMemcpyAsync(w + o_kb, h_key_bytes.data(), h_key_bytes.size(), hipMemcpyHostToDevice, st));
+    osmt_lb_pass P;
+    memset(&P, 0, sizeof P);
+    P.tg = geo.tags;
+    P.ent_class = m->d_ent_class;
+    P.class_off = (const uint32_t*)(w + o_co);
+    P.class_bind = (const uint2*)(w + o_cb);
+    P.keys = (const uint2*)(w + o_k);
+    P.key_bytes = (const uint8_t*)(w + o_kb);
+    P.tag_base = (uint32_t)tag_base, P.n_tt = (uint32_t)n_tt;
+    P.hash_mask = hash_bits >= 32u ? 0xFFFFFFFFu : (1u << hash_bits) - 1u;
+    P.table_mask = (uint32_t)(table - 1);
+    P.used = (uint32_t*)(w + o_used);
+    P.tslot = (uint32_t*)(w + o_ts);
+    P.first_pos = (uint32_t*)(w + o_fp);
+    P.table = (uint32_t*)(w + o_tab);
+    P.lowest = (uint32_t*)(w + o_low);
+    P.blk = (unsigned long long*)(w + o_blk);
+    P.tot = (unsigned long long*)(w + o_tot);
+    uint32_t *pos0 = (uint32_t*)(w + o_p0), *pos1 = (uint32_t*)(w + o_p1);
+    unsigned long long tot[OSMT_LB_T_N] = {};
+    /* 1. count */
+    HIP_TRY(mark(EV_COUNT0));
+    HIP_TRY(osmt_launch_lb_begin(P, st));
+    HIP_TRY(osmt_launch_lb_count(P, (uint32_t)first0, (uint32_t)n0, pos0, P.tot + OSMT_LB_T_BIND0, st));
+    HIP_TRY(osmt_launch_lb_count(P, (uint32_t)first1, (uint32_t)n1, pos1, P.tot + OSMT_LB_T_BIND1, st));
+    HIP_TRY(mark(EV_COUNT1));
+    HIP_TRY(hipMemcpyAsync(tot, P.tot, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tot[OSMT_LB_T_BIND0] >= 0xFFFFFFFFull || tot[OSMT_LB_T_BIND1] >= 0xFFFFFFFFull) {
+        if (area)
+            return fail(OSMT_UNSUPPORTED, "%s: %llu way and %llu multipolygon bindings (> 2^32 - 2 of one kind)", who, tot[OSMT_LB_T_BIND0],
+                        tot[OSMT_LB_T_BIND1]);
+        return fail(OSMT_UNSUPPORTED, "%s: %llu node bindings (> 2^32 - 2)", who, tot[OSMT_LB_T_BIND0]);
+    }
+    const size_t nb0 = (size_t)tot[OSMT_LB_T_BIND0], nb1 = (size_t)tot[OSMT_LB_T_BIND1];
+    /* 2. emit with provisional texts, 3. texts */
+    off = 0;
+    const size_t o_b0 = carve(nb0 * 8), o_b1 = carve(nb1 * 8);
+    rc = alloc(&wg.work[1], "bindings");
+    if (rc != OSMT_OK) return rc;
+    osmt_label_binding *bind0 = (osmt_label_binding*)(wg.work[1] + o_b0), *bind1 = (osmt_label_binding*)(wg.work[1] + o_b1);
+    HIP_TRY(mark(EV_EMIT0));
+    HIP_TRY(osmt_launch_lb_emit(P, (uint32_t)first0, (uint32_t)n0, pos0, bind0, st));
+    HIP_TRY(osmt_launch_lb_emit(P, (uint32_t)first1, (uint32_t)n1, pos1, bind1, st));
+    HIP_TRY(mark(EV_EMIT1));
+    HIP_TRY(osmt_launch_lb_texts(P, st));
+    HIP_TRY(mark(EV_TEXTS1));
+    HIP_TRY(hipMemcpyAsync(tot + OSMT_LB_T_TEXTS, P.tot + OSMT_LB_T_TEXTS, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tot[OSMT_LB_T_TEXTS] >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "%s: %llu texts (>= 2^32 - 1)", who, tot[OSMT_LB_T_TEXTS]);
+    const size_t n_texts = (size_t)tot[OSMT_LB_T_TEXTS]; /* at most n_tt */
+    P.n_texts = (uint32_t)n_texts;
+    /* 4. measure */
+    off = 0;
+    const size_t o_tt = carve(n_texts * 4), o_to = carve((n_texts + 1) * 4);
+    rc = alloc(&wg.work[2], "texts");
+    if (rc != OSMT_OK) return rc;
+    P.text_tag = (uint32_t*)(wg.work[2] + o_tt);
+    P.text_off = (uint32_t*)(wg.work[2] + o_to);
+    HIP_TRY(mark(EV_MEASURE0));
+    HIP_TRY(osmt_launch_lb_measure(P, st));
+    HIP_TRY(mark(EV_MEASURE1));
+    HIP_TRY(hipMemcpyAsync(tot + OSMT_LB_T_CHARS, P.tot + OSMT_LB_T_CHARS, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tot[OSMT_LB_T_FIRST_BAD] != ~0ull) {
+        /* name the tag: its kind and entity from the tag offsets, its value range, the byte the decoder stops at */
+        const size_t t = tag_base + (size_t)tot[OSMT_LB_T_FIRST_BAD], n_ent = m->n_nodes + m->n_ways + m->n_mps;
+        std::vector<uint32_t> tag_off(n_ent + 1);
+        uint32_t q[4] = {};
+        HIP_TRY(copy_back(ctx, tag_off.data(), geo.tags.tag_off, (n_ent + 1) * 4));
+        HIP_TRY(copy_back(ctx, q, geo.tags.tags + t, 16));
+        std::vector<uint8_t> value(q[3]);
+        if (q[3]) HIP_TRY(copy_back(ctx, value.data(), geo.tags.strings + q[2], q[3]));
+        const size_t e = (size_t)(std::upper_bound(tag_off.begin(), tag_off.end(), (uint32_t)t) - tag_off.begin()) - 1;
+        const char* kind = e < m->n_nodes ? "node" : e < m->n_nodes + m->n_ways ? "way" : "multipolygon";
+        const size_t local = e < m->n_nodes ? e : e < m->n_nodes + m->n_ways ? e - m->n_nodes : e - m->n_nodes - m->n_ways;
+        uint32_t n_scalars = 0;
+        const uint32_t bad = osmt_utf8_validate(value.data(), q[3], &n_scalars);
+        return fail(OSMT_INVALID_ARG, "%s: the value of tag %zu of %s %zu (v_off %u, v_len %u) is not well-formed UTF-8 at byte %u; nothing is registered", who,
+                    t - tag_off[e], kind, local, q[2], q[3], bad);
+    }
+    if (tot[OSMT_LB_T_CHARS] >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "%s: %llu chars (>= 2^32 - 1)", who, tot[OSMT_LB_T_CHARS]);
+    const size_t n_chars = (size_t)tot[OSMT_LB_T_CHARS];
+    P.n_chars = (uint32_t)n_chars;
+    /* 5. the table, laid out as osmt_register_label_bindings / osmt_register_area_label_bindings lay it out; decode and patch in place */
+    off = 0;
+    size_t o_0o, o_1o = 0, o_0b, o_1b = 0, o_txo, o_c;
+    if (area) {
+        o_0o = carve((n0 + 1) * 4), o_1o = carve((n1 + 1) * 4), o_0b = carve(nb0 * 8), o_1b = carve(nb1 * 8), o_txo = carve((n_texts + 1) * 4), o_c = carve(n_chars * 4);
+    } else {
+        o_0o = carve((n0 + 1) * 4), o_0b = carve(nb0 * 8), o_txo = carve((n_texts + 1) * 4), o_c = carve(n_chars * 4);
+    }
+    HIP_TRY(hipMalloc((void**)&wg.pool, off));
+    char* pool = wg.pool;
+    HIP_TRY(hipMemcpyAsync(pool + o_0o, pos0, (n0 + 1) * 4, hipMemcpyDeviceToDevice, st));
+    if (nb0) HIP_TRY(hipMemcpyAsync(pool + o_0b, bind0, nb0 * 8, hipMemcpyDeviceToDevice, st));
+    if (area) {
+        HIP_TRY(hipMemcpyAsync(pool + o_1o, pos1, (n1 + 1) * 4, hipMemcpyDeviceToDevice, st));
+        if (nb1) HIP_TRY(hipMemcpyAsync(pool + o_1b, bind1, nb1 * 8, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipMemcpyAsync(pool + o_txo, P.text_off, (n_texts + 1) * 4, hipMemcpyDeviceToDevice, st));
+    P.chars = (uint32_t*)(pool + o_c);
+    HIP_TRY(mark(EV_DECODE0));
+    HIP_TRY(osmt_launch_lb_decode(P, st));
+    HIP_TRY(mark(EV_DECODE1));
+    HIP_TRY(osmt_launch_lb_patch(P, (osmt_label_binding*)(pool + o_0b), (uint32_t)nb0, st));
+    if (area) HIP_TRY(osmt_launch_lb_patch(P, (osmt_label_binding*)(pool + o_1b), (uint32_t)nb1, st));
+    HIP_TRY(mark(EV_PATCH1));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (trace) {
+        auto us = [&](int a, int b2) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
+            return ms * 1e3;
+        };
+        fprintf(stderr,
+                "osmt %s: count %.1f us, emit %.1f us, texts %.1f us, measure %.1f us, decode %.1f us, patch %.1f us (%zu entities, %zu tags, %zu "
+                "bindings, %zu texts, %zu chars)\n",
+                who, us(EV_COUNT0, EV_COUNT1), us(EV_EMIT0, EV_EMIT1), us(EV_EMIT1, EV_TEXTS1), us(EV_MEASURE0, EV_MEASURE1), us(EV_DECODE0, EV_DECODE1),
+                us(EV_DECODE1, EV_PATCH1), n0 + n1, n_tt, nb0 + nb1, n_texts, n_chars);
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (area) {
+        osmt_ctx::area_label_bindings_host h;
+        h.geodata_id = m->geodata_id, h.zoom_lo = d->zoom_lo, h.zoom_hi = d->zoom_hi;
+        h.d_pool = pool;
+        h.dev.way_off = (const uint32_t*)(pool + o_0o);
+        h.dev.mp_off = (const uint32_t*)(pool + o_1o);
+        h.dev.way_bind = (const osmt_label_binding*)(pool + o_0b);
+        h.dev.mp_bind = (const osmt_label_binding*)(pool + o_1b);
+        h.dev.text_off = (const uint32_t*)(pool + o_txo);
+        h.dev.chars = (const uint32_t*)(pool + o_c);
+        h.n_ways = n0, h.n_mps = n1, h.n_way_bindings = nb0, h.n_mp_bindings = nb1, h.n_texts = n_texts, h.n_chars = n_chars;
+        if (ctx->area_label_bindings.size() + 1 >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "area label bindings table too large");
+        *out_id = (uint32_t)ctx->area_label_bindings.size();
+        ctx->area_label_bindings.push_back(h);
+    } else {
+        osmt_ctx::label_bindings_host h;
+        h.geodata_id = m->geodata_id, h.zoom_lo = d->zoom_lo, h.zoom_hi = d->zoom_hi;
+        h.d_pool = pool;
+        h.dev.node_off = (const uint32_t*)(pool + o_0o);
+        h.dev.bindings = (const osmt_label_binding*)(pool + o_0b);
+        h.dev.text_off = (const uint32_t*)(pool + o_txo);
+        h.dev.chars = (const uint32_t*)(pool + o_c);
+        h.n_nodes = n0, h.n_bindings = nb0, h.n_texts = n_texts, h.n_chars = n_chars;
+        if (ctx->label_bindings.size() + 1 >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "label bindings table too large");
+        *out_id = (uint32_t)ctx->label_bindings.size();
+        ctx->label_bindings.push_back(h);
+    }
+    wg.pool = nullptr;
+    return OSMT_OK;
+}
+
+/* one array of a read call: refused when its cap is too small, copied when asked for */
+struct lb_read_part {
+    void* dst;
+    const void* src;
+    size_t count, elem, cap;
+};
+
+int read_bindings_parts(osmt_ctx* ctx, const char* who, const lb_read_part* parts, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (parts[i].dst && parts[i].cap < parts[i].count)
+            return fail(OSMT_INVALID_ARG, "%s: a cap of %zu is less than the table's %zu", who, parts[i].cap, parts[i].count);
+    HIP_TRY(hipSetDevice(ctx->device));
+    for (size_t i = 0; i < n; ++i)
+        if (parts[i].dst && parts[i].count) HIP_TRY(copy_back(ctx, parts[i].dst, parts[i].src, parts[i].count * parts[i].elem));
+    return OSMT_OK;
+}
+
+int read_label_bindings_body(osmt_ctx* ctx, uint32_t id, uint32_t* node_off, osmt_label_binding* bindings, uint32_t* text_off, uint32_t* chars,
+                             const size_t caps[3], size_t counts[3]) {
+    if (!ctx || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
+    osmt_ctx::label_bindings_host h;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (id >= ctx->label_bindings.size())
+            return fail(OSMT_INVALID_ARG, "label bindings id %u is not registered (%zu tables)", id, ctx->label_bindings.size());
+        h = ctx->label_bindings[id];
+    }
+    counts[0] = h.n_bindings, counts[1] = h.n_texts, counts[2] = h.n_chars;
+    if (!node_off && !bindings && !text_off && !chars) return OSMT_OK;
+    if (!caps) return fail(OSMT_INVALID_ARG, "NULL caps with an output");
+    /* the offset arrays have one entry more than their count; they follow the caps of what they index */
+    const lb_read_part parts[4] = {{node_off, h.dev.node_off, h.n_nodes + 1, 4, SIZE_MAX},
+                                   {bindings, h.dev.bindings, h.n_bindings, sizeof(osmt_label_binding), caps[0]},
+                                   {text_off, h.dev.text_off, h.n_texts + 1, 4, text_off && caps[1] < h.n_texts ? 0 : SIZE_MAX},
+                                   {chars, h.dev.chars, h.n_chars, 4, caps[2]}};
+    return read_bindings_parts(ctx, "osmt_read_label_bindings", parts, 4);
+}
+
+int read_area_label_bindings_body(osmt_ctx* ctx, uint32_t id, uint32_t* way_off, osmt_label_binding* way_bindings, uint32_t* mp_off,
+                                  osmt_label_binding* mp_bindings, uint32_t* text_off, uint32_t* chars, const size_t caps[4], size_t counts[4]) {
+    if (!ctx || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
+    osmt_ctx::area_label_bindings_host h;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (id >= ctx->area_label_bindings.size())
+            return fail(OSMT_INVALID_ARG, "area label bindings id %u is not registered (%zu tables)", id, ctx->area_label_bindings.size());
+        h = ctx->area_label_bindings[id];
+    }
+    counts[0] = h.n_way_bindings, counts[1] = h.n_mp_bindings, counts[2] = h.n_texts, counts[3] = h.n_chars;
+    if (!way_off && !way_bindings && !mp_off && !mp_bindings && !text_off && !chars) return OSMT_OK;
+    if (!caps) return fail(OSMT_INVALID_ARG, "NULL caps with an output");
+    const lb_read_part parts[6] = {{way_off, h.dev.way_off, h.n_ways + 1, 4, SIZE_MAX},
+                                   {way_bindings, h.dev.way_bind, h.n_way_bindings, sizeof(osmt_label_binding), caps[0]},
+                                   {mp_off, h.dev.mp_off, h.n_mps + 1, 4, SIZE_MAX},
+                                   {mp_bindings, h.dev.mp_bind, h.n_mp_bindings, sizeof(osmt_label_binding), caps[1]},
+                                   {text_off, h.dev.text_off, h.n_texts + 1, 4, text_off && caps[2] < h.n_texts ? 0 : SIZE_MAX},
+                                   {chars, h.dev.chars, h.n_chars, 4, caps[3]}};
+    return read_bindings_parts(ctx, "osmt_read_area_label_bindings", parts, 6);
+}
+
+}  // namespace
+
+extern "C" {
+
+int osmt_validate_class_label_bindings(const osmt_class_label_bindings_desc* d, osmt_match* match, osmt_ctx* ctx) {
+    return guarded([&] { return validate_class_label_bindings(d, match, ctx); });
+}
+int osmt_register_label_bindings_matched(osmt_ctx* ctx, osmt_match* match, const osmt_class_label_bindings_desc* d, uint32_t* out_bindings_id) {
+    return guarded([&] { return label_bindings_matched_body(ctx, match, d, out_bindings_id, false); });
+}
+int osmt_register_area_label_bindings_matched(osmt_ctx* ctx, osmt_match* match, const osmt_class_label_bindings_desc* d, uint32_t* out_bindings_id) {
+    return guarded([&] { return label_bindings_matched_body(ctx, match, d, out_bindings_id, true); });
+}
+int osmt_read_label_bindings(osmt_ctx* ctx, uint32_t id, uint32_t* node_off, osmt_label_binding* bindings, uint32_t* text_off, uint32_t* chars,
+                             const size_t caps[3], size_t counts[3]) {
+    return guarded([&] { return read_label_bindings_body(ctx, id, node_off, bindings, text_off, chars, caps, counts); });
+}
+int osmt_read_area_label_bindings(osmt_ctx* ctx, uint32_t id, uint32_t* way_off, osmt_label_binding* way_bindings, uint32_t* multipolygon_off,
+                                  osmt_label_binding* multipolygon_bindings, uint32_t* text_off, uint32_t* chars, const size_t caps[4],
+                                  size_t counts[4]) {
+    return guarded([&] {
+        return read_area_label_bindings_body(ctx, id, way_off, way_bindings, multipolygon_off, multipolygon_bindings, text_off, chars, caps, counts);
     });
 }
 

@@ -782,6 +782,57 @@ hipError_t osmt_launch_sm_bind_count(const uint32_t* ent_class, const uint32_t* 
 hipError_t osmt_launch_sm_bind_emit(const uint32_t* ent_class, const uint32_t* class_off, const uint32_t* class_styles, uint32_t n, const uint32_t* pos,
                                     uint32_t* out, hipStream_t st);
 
+/* ---- label bindings per class (osmt_labelbind.hip) ---------------------------------------------------------------- */
+/* words of osmt_lb_pass::tot; FIRST_BAD is the one word that is not a scan total */
+enum {
+    OSMT_LB_T_BIND0 = 0, /* bindings of the first kind (nodes, or ways) */
+    OSMT_LB_T_BIND1,     /* bindings of the second kind (multipolygons) */
+    OSMT_LB_T_TEXTS,     /* distinct value ranges some binding uses */
+    OSMT_LB_T_CHARS,     /* their scalars */
+    OSMT_LB_T_FIRST_BAD, /* the lowest-numbered tag of the table whose used value is not well-formed UTF-8 (none: all ones) */
+    OSMT_LB_T_N
+};
+/* One table: the node table has one kind (the nodes) and numbers the node tags; the area table has two (ways, then
+ * multipolygons) and numbers the way tags in front of the multipolygon tags.  Tag t of the table is tags[tag_base + t]. */
+struct osmt_lb_pass {
+    osmt_sm_tags_dev tg;
+    const uint32_t* ent_class;  /* the match's, [nodes + ways + multipolygons] */
+    const uint32_t* class_off;  /* [n_classes + 1] into class_bind */
+    const uint2* class_bind;    /* osmt_class_label_binding: (style, text_key) */
+    const uint2* keys;          /* [n_keys] (offset in key_bytes, a multiple of 4; length) */
+    const uint8_t* key_bytes;   /* the device copy starts every key on a 4-byte boundary */
+    uint32_t tag_base, n_tt;    /* the table's tags */
+    uint32_t n_texts, n_chars;  /* totals, known once they have been read back */
+    uint32_t hash_mask, table_mask; /* the debug knob; table size - 1 (a power of two >= 2 n_tt) */
+    /* per tag of the table */
+    uint32_t* used;      /* 1: some binding reads the tag's value; cleared first */
+    uint32_t* tslot;     /* a used tag's slot in the table */
+    uint32_t* first_pos; /* [n_tt + 1] 1: the lowest used tag of its value range; then the exclusive scan: the text id */
+    /* the text table: open addressing over representative tag numbers */
+    uint32_t* table;  /* [table_mask + 1] */
+    uint32_t* lowest; /* [table_mask + 1] the lowest member */
+    /* per text */
+    uint32_t* text_tag; /* [n_texts] its lowest user */
+    uint32_t* text_off; /* [n_texts + 1] scalars, then their exclusive scan */
+    uint32_t* chars;    /* [n_chars] */
+    unsigned long long* blk;
+    unsigned long long* tot; /* [OSMT_LB_T_N] */
+};
+/* sets tot[FIRST_BAD] to all ones and clears `used` */
+hipError_t osmt_launch_lb_begin(const osmt_lb_pass& a, hipStream_t st);
+/* k_lb_count + scan, one kind: pos[0 .. n) = bindings of the class of entity first + i, scanned (*tot the 64-bit total) */
+hipError_t osmt_launch_lb_count(const osmt_lb_pass& a, uint32_t first, uint32_t n, uint32_t* pos, unsigned long long* tot, hipStream_t st);
+/* k_lb_emit, one kind: out[pos[i] ..) = the bindings of entity first + i with the tag's number in the table as text; `used` */
+hipError_t osmt_launch_lb_emit(const osmt_lb_pass& a, uint32_t first, uint32_t n, const uint32_t* pos, osmt_label_binding* out, hipStream_t st);
+/* k_lb_text_insert + k_lb_text_mark + scan: tot[TEXTS] */
+hipError_t osmt_launch_lb_texts(const osmt_lb_pass& a, hipStream_t st);
+/* k_lb_text_list + k_lb_measure + scan: text_tag, text_off, tot[CHARS], tot[FIRST_BAD] */
+hipError_t osmt_launch_lb_measure(const osmt_lb_pass& a, hipStream_t st);
+/* k_lb_decode: chars */
+hipError_t osmt_launch_lb_decode(const osmt_lb_pass& a, hipStream_t st);
+/* k_lb_patch: the provisional tag numbers of bind[0 .. n) replaced by text ids */
+hipError_t osmt_launch_lb_patch(const osmt_lb_pass& a, osmt_label_binding* bind, uint32_t n, hipStream_t st);
+
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

@@ -10,6 +10,10 @@
  *   number_fast_path       the device's rule "exact by construction, else declined" (csrc/osmt_numparse.h), stated once
  *   HostNumbers            the overrides for the values osmt_match_selectors declined
  *   selectors_at_zoom      the zoom filter of area_matches, applied by the caller per class before it cascades
+ *   ClassLabelBindings     builder that fills an osmt_class_label_bindings_desc and pools the text keys
+ *   label_bindings_matched_host / area_label_bindings_matched_host
+ *                          the rule of osmt_register_label_bindings_matched / osmt_register_area_label_bindings_matched in
+ *                          plain C++: the arrays osmt_read_label_bindings / osmt_read_area_label_bindings return
  *
  * Host only; compile with -ffp-contract=off like everything that must agree with the device bit for bit.
  */
@@ -17,6 +21,7 @@
 #define OSMT_SELMATCH_HPP
 
 #include <cerrno>
+#include <algorithm>
 #include <cstdlib>
 #include <map>
 #include <string>
@@ -26,6 +31,7 @@
 
 #include "../../include/osmtile.h"
 #include "../csrc/osmt_numparse.h"
+#include "../csrc/osmt_utf8.h"
 #include "osmt_geodata.hpp"
 
 namespace osmt {
@@ -230,6 +236,176 @@ inline std::vector<uint32_t> selectors_at_zoom(const osmt_selectors_desc& d, con
         out.push_back(class_selectors[i]);
     }
     return out;
+}
+
+/* label bindings per class: add_class() starts the list of the next class, bind() appends to it; equal keys share one entry */
+class ClassLabelBindings {
+  public:
+    ClassLabelBindings(uint8_t zoom_lo, uint8_t zoom_hi) { desc_.zoom_lo = zoom_lo, desc_.zoom_hi = zoom_hi; }
+    void add_class() { off_.push_back((uint32_t)bindings_.size()); }
+    /* a style without text: has_key = false */
+    void bind(uint32_t style, std::string_view text_key, bool has_key = true) {
+        osmt_class_label_binding b{};
+        b.style = style, b.text_key = has_key ? key(text_key) : OSMT_TEXT_NONE;
+        bindings_.push_back(b);
+        off_.back() = (uint32_t)bindings_.size();
+    }
+    const osmt_class_label_bindings_desc& desc() {
+        desc_.class_off = off_.data(), desc_.bindings = bindings_.data();
+        desc_.n_classes = off_.size() - 1, desc_.n_bindings = bindings_.size();
+        desc_.key_off = key_off_.data(), desc_.key_bytes = (const uint8_t*)key_bytes_.data();
+        desc_.n_keys = key_off_.size() - 1, desc_.n_key_bytes = key_bytes_.size();
+        return desc_;
+    }
+
+  private:
+    uint32_t key(std::string_view k) {
+        const auto ins = ids_.emplace(std::string(k), (uint32_t)ids_.size());
+        if (ins.second) {
+            key_bytes_.append(k);
+            key_off_.push_back((uint32_t)key_bytes_.size());
+        }
+        return ins.first->second;
+    }
+    std::vector<uint32_t> off_{0u}, key_off_{0u};
+    std::vector<osmt_class_label_binding> bindings_;
+    std::string key_bytes_;
+    std::map<std::string, uint32_t> ids_;
+    osmt_class_label_bindings_desc desc_{};
+};
+
+/* what osmt_read_label_bindings (kind 0 = nodes) or osmt_read_area_label_bindings (kind 0 = ways, 1 = multipolygons) return */
+struct HostLabelTable {
+    bool ok = true; /* false: a used value is not well-formed UTF-8; bad_* name the lowest-numbered such tag, the arrays are empty */
+    const char* bad_kind = nullptr;
+    size_t bad_entity = 0, bad_tag = 0; /* the entity within its kind; the tag within the entity */
+    uint32_t bad_v_off = 0, bad_v_len = 0;
+    std::vector<uint32_t> off[2];
+    std::vector<osmt_label_binding> bindings[2];
+    std::vector<uint32_t> text_off{0u}, chars;
+};
+
+namespace labelbind_detail {
+struct Kind {
+    const char* name;
+    size_t first, count; /* in the numbering of entity_class: nodes, then ways, then multipolygons */
+};
+
+inline Tags tags_of(const osmt_tags_desc& t, size_t e) {
+    const uint32_t *off = t.node_tag_off, *kv = t.node_tags;
+    if (e >= t.n_nodes + t.n_ways)
+        e -= t.n_nodes + t.n_ways, off = t.multipolygon_tag_off, kv = t.multipolygon_tags;
+    else if (e >= t.n_nodes)
+        e -= t.n_nodes, off = t.way_tag_off, kv = t.way_tags;
+    return Tags(kv + 4 * (size_t)off[e], 4 * (size_t)(off[e + 1] - off[e]), (const char*)t.strings);
+}
+
+/* The rule, kind after kind, entity after entity: every element of the class's list is pushed; its text is the value of the
+ * tag whose key equals the key's bytes.  A text is a distinct (v_off, v_len) among the USED tags, numbered by its lowest user in
+ * the table's tag order; every used value must be well-formed UTF-8. */
+inline HostLabelTable table(const osmt_tags_desc& r, const uint32_t* entity_class, const osmt_class_label_bindings_desc& d, const Kind* kinds, int n_kinds) {
+    HostLabelTable out;
+    struct Use {
+        int kind;
+        size_t entity, tag, number; /* number: the tag's in the table */
+    };
+    using range_t = std::pair<uint32_t, uint32_t>;
+    std::map<range_t, Use> lowest; /* value range -> its lowest-numbered user */
+    std::vector<range_t> provisional[2]; /* per binding its value range; (NONE, NONE): no text */
+    const range_t none{OSMT_TEXT_NONE, OSMT_TEXT_NONE};
+    size_t tag_number = 0;
+    for (int k = 0; k < n_kinds; ++k) {
+        out.off[k].push_back(0u);
+        for (size_t i = 0; i < kinds[k].count; ++i) {
+            const Tags tags = tags_of(r, kinds[k].first + i);
+            const uint32_t c = entity_class[kinds[k].first + i];
+            for (uint32_t j = d.class_off[c]; j < d.class_off[c + 1]; ++j) {
+                const osmt_class_label_binding& b = d.bindings[j];
+                range_t found = none;
+                if (b.text_key != OSMT_TEXT_NONE) {
+                    const std::string_view key((const char*)d.key_bytes + d.key_off[b.text_key], d.key_off[b.text_key + 1] - d.key_off[b.text_key]);
+                    /* the keys of an entity are distinct: at most one tag has the key, however it is searched for */
+                    for (size_t t = 0; t < tags.size(); ++t)
+                        if (tags.get_kv(t).first == key) {
+                            found = range_t{tags.raw()[4 * t + 2], tags.raw()[4 * t + 3]};
+                            const Use u{k, i, t, tag_number + t};
+                            const auto ins = lowest.emplace(found, u);
+                            if (!ins.second && u.number < ins.first->second.number) ins.first->second = u;
+                        }
+                }
+                out.bindings[k].push_back(osmt_label_binding{b.style, OSMT_TEXT_NONE});
+                provisional[k].push_back(found);
+            }
+            out.off[k].push_back((uint32_t)out.bindings[k].size());
+            tag_number += tags.size();
+        }
+    }
+    /* the texts in the order of their lowest users */
+    std::vector<std::pair<size_t, range_t>> order;
+    for (const auto& kv : lowest) order.push_back({kv.second.number, kv.first});
+    std::sort(order.begin(), order.end());
+    std::map<range_t, uint32_t> id;
+    for (const auto& o : order) {
+        const range_t v = o.second;
+        const uint8_t* s = r.strings + v.first;
+        uint32_t n_scalars = 0;
+        if (osmt_utf8_validate(s, v.second, &n_scalars) != v.second) {
+            const Use& u = lowest[v];
+            HostLabelTable bad;
+            bad.ok = false, bad.bad_kind = kinds[u.kind].name, bad.bad_entity = u.entity, bad.bad_tag = u.tag;
+            bad.bad_v_off = v.first, bad.bad_v_len = v.second;
+            bad.text_off.clear();
+            return bad; /* `order` ascends by tag number: this is the lowest-numbered offender */
+        }
+        id[v] = (uint32_t)out.text_off.size() - 1u;
+        const size_t at = out.chars.size();
+        out.chars.resize(at + n_scalars);
+        osmt_utf8_decode(s, v.second, out.chars.data() + at);
+        out.text_off.push_back((uint32_t)out.chars.size());
+    }
+    for (int k = 0; k < n_kinds; ++k)
+        for (size_t j = 0; j < provisional[k].size(); ++j)
+            if (provisional[k][j] != none) out.bindings[k][j].text = id[provisional[k][j]];
+    return out;
+}
+}  // namespace labelbind_detail
+
+/* osmt_register_label_bindings_matched, on the host: `tags` as osmt_register_tags took them (osmt::TagsDesc over a reader),
+ * entity_class as osmt_match_read returns it (or HostMatch::entity_class) */
+inline HostLabelTable label_bindings_matched_host(const osmt_tags_desc& tags, const uint32_t* entity_class, const osmt_class_label_bindings_desc& d) {
+    const labelbind_detail::Kind kinds[1] = {{"node", 0, tags.n_nodes}};
+    return labelbind_detail::table(tags, entity_class, d, kinds, 1);
+}
+
+/* osmt_register_area_label_bindings_matched, on the host: the way tags are numbered in front of the multipolygon tags */
+inline HostLabelTable area_label_bindings_matched_host(const osmt_tags_desc& tags, const uint32_t* entity_class, const osmt_class_label_bindings_desc& d) {
+    const labelbind_detail::Kind kinds[2] = {{"way", tags.n_nodes, tags.n_ways}, {"multipolygon", tags.n_nodes + tags.n_ways, tags.n_multipolygons}};
+    return labelbind_detail::table(tags, entity_class, d, kinds, 2);
+}
+
+/* the C calls over the builder and the table struct (these four need libosmtile) */
+inline int register_label_bindings_matched(osmt_ctx* ctx, osmt_match* match, ClassLabelBindings& b, uint32_t* out_id) {
+    return osmt_register_label_bindings_matched(ctx, match, &b.desc(), out_id);
+}
+inline int register_area_label_bindings_matched(osmt_ctx* ctx, osmt_match* match, ClassLabelBindings& b, uint32_t* out_id) {
+    return osmt_register_area_label_bindings_matched(ctx, match, &b.desc(), out_id);
+}
+inline int read_label_bindings(osmt_ctx* ctx, uint32_t id, size_t n_nodes, HostLabelTable* out) {
+    size_t n[3] = {};
+    int rc = osmt_read_label_bindings(ctx, id, nullptr, nullptr, nullptr, nullptr, nullptr, n);
+    if (rc != OSMT_OK) return rc;
+    out->off[0].assign(n_nodes + 1, 0u), out->bindings[0].assign(n[0], osmt_label_binding{}), out->text_off.assign(n[1] + 1, 0u), out->chars.assign(n[2], 0u);
+    return osmt_read_label_bindings(ctx, id, out->off[0].data(), out->bindings[0].data(), out->text_off.data(), out->chars.data(), n, n);
+}
+inline int read_area_label_bindings(osmt_ctx* ctx, uint32_t id, size_t n_ways, size_t n_multipolygons, HostLabelTable* out) {
+    size_t n[4] = {};
+    int rc = osmt_read_area_label_bindings(ctx, id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n);
+    if (rc != OSMT_OK) return rc;
+    out->off[0].assign(n_ways + 1, 0u), out->off[1].assign(n_multipolygons + 1, 0u);
+    out->bindings[0].assign(n[0], osmt_label_binding{}), out->bindings[1].assign(n[1], osmt_label_binding{});
+    out->text_off.assign(n[2] + 1, 0u), out->chars.assign(n[3], 0u);
+    return osmt_read_area_label_bindings(ctx, id, out->off[0].data(), out->bindings[0].data(), out->off[1].data(), out->bindings[1].data(),
+                                         out->text_off.data(), out->chars.data(), n, n);
 }
 
 }  // namespace osmt

@@ -48,6 +48,8 @@ EXPORTS = [
     "osmt_validate_tags", "osmt_register_tags", "osmt_validate_selectors", "osmt_register_selectors", "osmt_match_selectors",
     "osmt_match_free", "osmt_match_read_declined_numbers", "osmt_match_read", "osmt_register_style_bindings_matched",
     "osmt_debug_match_hash_bits",
+    "osmt_validate_class_label_bindings", "osmt_register_label_bindings_matched", "osmt_register_area_label_bindings_matched",
+    "osmt_read_label_bindings", "osmt_read_area_label_bindings",
 ]
 
 
@@ -196,6 +198,13 @@ def load():
         L.osmt_match_read.argtypes = [vp, vp, vp, vp, sz, sz]
         L.osmt_register_style_bindings_matched.argtypes = [vp, vp, C.c_uint8, C.c_uint8, vp, vp, C.c_size_t, C.POINTER(C.c_uint32)]
         L.osmt_debug_match_hash_bits.argtypes = [vp, C.c_uint32]
+    if hasattr(L, "osmt_register_label_bindings_matched"):  # absent only from older variant builds loaded through OSMT_LIB
+        sz = C.POINTER(C.c_size_t)
+        L.osmt_validate_class_label_bindings.argtypes = [C.POINTER(abi.ClassLabelBindingsDesc), vp, vp]
+        L.osmt_register_label_bindings_matched.argtypes = [vp, vp, C.POINTER(abi.ClassLabelBindingsDesc), C.POINTER(C.c_uint32)]
+        L.osmt_register_area_label_bindings_matched.argtypes = [vp, vp, C.POINTER(abi.ClassLabelBindingsDesc), C.POINTER(C.c_uint32)]
+        L.osmt_read_label_bindings.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, sz, sz]
+        L.osmt_read_area_label_bindings.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, sz, sz]
     if hasattr(L, "osmt_label_positions_tiles"):  # absent only from older variant builds loaded through OSMT_LIB
         L.osmt_validate_node_mercator.argtypes = [dp, C.c_size_t, C.c_uint32, vp]
         L.osmt_register_node_mercator.argtypes = [vp, C.c_uint32, dp]

@@ -496,6 +496,35 @@ class Context:
         check(load().osmt_register_label_bindings(self._h, C.byref(d), C.byref(out)))
         return out.value
 
+    def read_label_bindings(self, bindings_id, n_nodes):
+        """osmt_read_label_bindings of any registered node table: (node_off [n_nodes + 1], bindings
+        (styled.LABEL_BINDING_DTYPE), text_off, chars) as numpy arrays."""
+        from .styled import LABEL_BINDING_DTYPE
+
+        L, n = load(), (C.c_size_t * 3)()
+        check(L.osmt_read_label_bindings(self._h, bindings_id, None, None, None, None, None, n))
+        off, bind = np.zeros(n_nodes + 1, np.uint32), np.zeros(n[0], LABEL_BINDING_DTYPE)
+        text_off, chars = np.zeros(n[1] + 1, np.uint32), np.zeros(n[2], np.uint32)
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+        caps = (C.c_size_t * 3)(*n)
+        check(L.osmt_read_label_bindings(self._h, bindings_id, ptr(off), ptr(bind), ptr(text_off), ptr(chars), caps, n))
+        return off, bind, text_off, chars
+
+    def read_area_label_bindings(self, bindings_id, n_ways, n_multipolygons):
+        """osmt_read_area_label_bindings of any registered area table: (way_off, way_bindings, multipolygon_off,
+        multipolygon_bindings, text_off, chars) as numpy arrays."""
+        from .styled import LABEL_BINDING_DTYPE
+
+        L, n = load(), (C.c_size_t * 4)()
+        check(L.osmt_read_area_label_bindings(self._h, bindings_id, None, None, None, None, None, None, None, n))
+        way_off, way = np.zeros(n_ways + 1, np.uint32), np.zeros(n[0], LABEL_BINDING_DTYPE)
+        mp_off, mp = np.zeros(n_multipolygons + 1, np.uint32), np.zeros(n[1], LABEL_BINDING_DTYPE)
+        text_off, chars = np.zeros(n[2] + 1, np.uint32), np.zeros(n[3], np.uint32)
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+        caps = (C.c_size_t * 4)(*n)
+        check(L.osmt_read_area_label_bindings(self._h, bindings_id, ptr(way_off), ptr(way), ptr(mp_off), ptr(mp), ptr(text_off), ptr(chars), caps, n))
+        return way_off, way, mp_off, mp, text_off, chars
+
     # -- glyph outlines (glyph-run labels) -----------------------------------------
     def register_glyphs(self, table):
         """osmt_register_glyphs: appends the outlines of a labels.GlyphTable; returns (and records in the table) the id

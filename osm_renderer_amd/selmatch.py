@@ -20,7 +20,8 @@ DECLINED_NUMBER_DTYPE = np.dtype([("v_off", "<u4"), ("v_len", "<u4")])
 MATCH_CLASS_DTYPE = np.dtype([("layer", "<i8"), ("sel_off", "<u4"), ("n_sels", "<u4"), ("first_entity", "<u4"), ("slot", "u1"), ("has_layer", "u1"),
                               ("_pad", "u1", (2,))])
 assert SELECTOR_REC_DTYPE.itemsize == 16 and SELECTOR_TEST_DTYPE.itemsize == 32 and NUMBER_OVERRIDE_DTYPE.itemsize == 24
-assert DECLINED_NUMBER_DTYPE.itemsize == 8 and MATCH_CLASS_DTYPE.itemsize == 24
+CLASS_LABEL_BINDING_DTYPE = np.dtype([("style", "<u4"), ("text_key", "<u4")])
+assert DECLINED_NUMBER_DTYPE.itemsize == 8 and MATCH_CLASS_DTYPE.itemsize == 24 and CLASS_LABEL_BINDING_DTYPE.itemsize == 8
 
 _STRING_KINDS = (abi.TEST_EQUAL, abi.TEST_NOT_EQUAL)
 
@@ -101,6 +102,35 @@ class Tags:
         return self.strings[v_off:v_off + v_len].tobytes()
 
 
+class ClassLabelBindings:
+    """osmt_class_label_bindings_desc.  class_bindings: per class one list of (label style id, index into `keys` or None), in
+    push order; keys: the tag names text_style.text may name (str or bytes; neither sorted nor distinct)."""
+
+    def __init__(self, zoom_lo, zoom_hi, class_bindings, keys=()):
+        self.zoom_lo, self.zoom_hi = int(zoom_lo), int(zoom_hi)
+        self.class_off = np.zeros(len(class_bindings) + 1, dtype=np.uint32)
+        if len(class_bindings):
+            self.class_off[1:] = np.cumsum([len(v) for v in class_bindings])
+        flat = [(int(s), abi.TEXT_NONE if k is None else int(k)) for v in class_bindings for s, k in v]
+        self.bindings = np.array(flat, dtype=CLASS_LABEL_BINDING_DTYPE).reshape(-1)
+        raw = [_bytes(k) for k in keys]
+        self.key_off = np.zeros(len(raw) + 1, dtype=np.uint32)
+        if raw:
+            self.key_off[1:] = np.cumsum([len(k) for k in raw])
+        self.key_bytes = np.frombuffer(b"".join(raw), dtype=np.uint8).copy()
+
+    def as_desc(self):
+        """ctypes osmt_class_label_bindings_desc pointing into this object's arrays (keep `self` alive)."""
+        u32 = C.POINTER(C.c_uint32)
+        d = abi.ClassLabelBindingsDesc()
+        d.zoom_lo, d.zoom_hi = self.zoom_lo, self.zoom_hi
+        d.class_off, d.bindings = self.class_off.ctypes.data_as(u32), self.bindings.ctypes.data_as(C.POINTER(abi.ClassLabelBinding))
+        d.n_classes, d.n_bindings = len(self.class_off) - 1, len(self.bindings)
+        d.key_off, d.key_bytes = self.key_off.ctypes.data_as(u32), self.key_bytes.ctypes.data_as(C.POINTER(C.c_uint8))
+        d.n_keys, d.n_key_bytes = len(self.key_off) - 1, len(self.key_bytes)
+        return d
+
+
 class Declined(OsmtError):
     """osmt_match_selectors declined tag values: `declined` (DECLINED_NUMBER_DTYPE) lists them; compute their f64 and call again."""
 
@@ -147,6 +177,22 @@ class Match:
         check(load().osmt_register_style_bindings_matched(self.ctx._h, self._h, zoom_lo, zoom_hi, C.c_void_p(off.ctypes.data),
                                                           C.c_void_p(flat.ctypes.data) if flat.size else None, len(class_styles), C.byref(out)))
         return out.value
+
+    def _register_labels(self, call, zoom_lo, zoom_hi, class_bindings, keys):
+        b = class_bindings if isinstance(class_bindings, ClassLabelBindings) else ClassLabelBindings(zoom_lo, zoom_hi, class_bindings, keys)
+        d, out = b.as_desc(), C.c_uint32()
+        check(call(self.ctx._h, self._h, C.byref(d), C.byref(out)))
+        return out.value
+
+    def register_label_bindings(self, zoom_lo, zoom_hi, class_bindings, keys=()):
+        """osmt_register_label_bindings_matched: the node table.  class_bindings: per class one list of (label style id, index
+        into `keys` or None); returns an id of the kind Context.register_label_bindings returns."""
+        return self._register_labels(load().osmt_register_label_bindings_matched, zoom_lo, zoom_hi, class_bindings, keys)
+
+    def register_area_label_bindings(self, zoom_lo, zoom_hi, class_bindings, keys=()):
+        """osmt_register_area_label_bindings_matched: the table of ways and multipolygons; returns an id of the kind
+        Context.register_area_label_bindings returns."""
+        return self._register_labels(load().osmt_register_area_label_bindings_matched, zoom_lo, zoom_hi, class_bindings, keys)
 
     def close(self):
         if self._h:
