@@ -1208,6 +1208,129 @@ int osmt_read_area_label_bindings(osmt_ctx* ctx, uint32_t id, uint32_t* way_off,
                                   osmt_label_binding* multipolygon_bindings, uint32_t* text_off, uint32_t* chars, const size_t caps[4],
                                   size_t counts[4]);
 
+/* ---- the cascade: styles per class and zoom from registered rules ------------------------------------------------ */
+/* The step of Styler::style_entities between the match and the tables (mapcss/styler.rs:128-160,205-242,277-429), on the
+ * device (csrc/osmt_cascade.hip): per class of an osmt_match and zoom 0 .. OSMT_MAX_ZOOM the fold of style_area over the
+ * class's selectors that admit the zoom (area_matches' zoom half, 501-515), then property_map_to_style of every layer but
+ * "*", in insertion order.  The styles of all (class, zoom, layer) are made distinct — as area records (osmt_style_rec with
+ * their dashes) and as label records (osmt_label_style_rec) — and numbered by their lowest user, user number
+ * ((class * 19) + zoom) * 8 + position; zooms at which every class has the same lists as at the zoom below are joined into
+ * ranges.  Nothing is approximate: casing_width = base + multiplier * w is a multiplication and an addition, never fused.
+ * What the device cannot know the caller resolves per property: from_color_name of an identifier, and the registered image
+ * of an icon-image / fill-image string (not in the icon cache: no icon, no image fill; drawer.rs:179-183,
+ * labeler.rs:53-66).  The host twin is osmt::cascade_host (host/osmt_cascade.hpp); DESIGN.md 3.15. */
+
+#define OSMT_CASCADE_MAX_LAYERS 8u       /* distinct layer names of one rule set, "*" and "default" included */
+#define OSMT_LAYER_DEFAULT 0xFFFFFFFFu   /* osmt_rules_desc.selector_layer: the selector names no layer */
+
+enum { /* the 20 property names property_map_to_style reads; every other name is OSMT_PROP_OTHER and is dropped */
+    OSMT_PROP_Z_INDEX = 0,
+    OSMT_PROP_FILL_POSITION,
+    OSMT_PROP_WIDTH,
+    OSMT_PROP_CASING_WIDTH,
+    OSMT_PROP_TEXT,
+    OSMT_PROP_FONT_SIZE,
+    OSMT_PROP_TEXT_COLOR,
+    OSMT_PROP_TEXT_POSITION,
+    OSMT_PROP_COLOR,
+    OSMT_PROP_FILL_COLOR,
+    OSMT_PROP_BACKGROUND_COLOR,
+    OSMT_PROP_OPACITY,
+    OSMT_PROP_FILL_OPACITY,
+    OSMT_PROP_DASHES,
+    OSMT_PROP_LINECAP,
+    OSMT_PROP_CASING_COLOR,
+    OSMT_PROP_CASING_DASHES,
+    OSMT_PROP_CASING_LINECAP,
+    OSMT_PROP_ICON_IMAGE,
+    OSMT_PROP_FILL_IMAGE,
+    OSMT_PROP_NAMES, /* 20 */
+    OSMT_PROP_OTHER = OSMT_PROP_NAMES
+};
+enum { OSMT_PV_IDENTIFIER = 0, OSMT_PV_STRING, OSMT_PV_COLOR, OSMT_PV_NUMBERS, OSMT_PV_WIDTH_DELTA, OSMT_PV_KINDS }; /* parser.rs PropertyValue */
+
+typedef struct osmt_rule_prop { /* 40 bytes: one `name: value;` of a rule */
+    uint8_t name;               /* OSMT_PROP_* */
+    uint8_t kind;               /* OSMT_PV_* */
+    uint8_t has_color;          /* COLOR: 1.  IDENTIFIER: from_color_name found it.  Otherwise 0 */
+    uint8_t rgb[3];             /* read when has_color */
+    uint8_t has_image;          /* IDENTIFIER / STRING of icon-image or fill-image: the string's icon is registered */
+    uint8_t _pad;
+    uint32_t image;             /* read when has_image: id from osmt_register_image */
+    uint32_t str_off, str_len;  /* IDENTIFIER / STRING: the bytes, in `strings` */
+    uint32_t num_off, n_nums;   /* NUMBERS: the list, in `numbers` */
+    uint32_t _pad2;
+    double delta;               /* WIDTH_DELTA */
+} osmt_rule_prop;
+
+typedef struct osmt_rules_desc {
+    uint32_t selectors_id;          /* the registered selector set the rules' selectors are */
+    uint32_t font_id;               /* id from osmt_register_font: the font of every label style with a font size */
+    const uint32_t* selector_rule;  /* [n_selectors] non-decreasing rule index */
+    const uint32_t* selector_layer; /* [n_selectors] index into the layer names, or OSMT_LAYER_DEFAULT */
+    size_t n_selectors;             /* the selector set's */
+    const uint32_t* layer_off;      /* [n_layers + 1] into layer_bytes; "*" and "default" are recognised by their bytes; equal names are one layer */
+    const uint8_t* layer_bytes;
+    size_t n_layers, n_layer_bytes;
+    const uint32_t* rule_prop_off; /* [n_rules + 1] into props, file order inside a rule */
+    const osmt_rule_prop* props;
+    size_t n_rules, n_props;
+    const double* numbers;
+    size_t n_numbers;
+    const uint8_t* strings;
+    size_t n_string_bytes;
+    double casing_width_multiplier; /* Styler::casing_width_multiplier */
+    double font_size_multiplier;    /* read when has_font_size_multiplier */
+    uint32_t has_font_size_multiplier, _pad;
+} osmt_rules_desc;
+
+typedef struct osmt_cascade osmt_cascade;
+
+/* The checks osmt_register_rules runs first, without a device; a NULL `ctx` skips the lookups of ids.  OSMT_INVALID_ARG,
+ * naming the offender: NULL with a non-zero count; offsets that do not start at 0, decrease or do not end at the pool
+ * length; a selector_rule that decreases or is >= n_rules; n_selectors that is not the selector set's; a name, kind or flag
+ * outside its values; a COLOR without has_color, has_color on a value that is neither COLOR nor IDENTIFIER, has_image on
+ * anything but an IDENTIFIER / STRING of icon-image or fill-image; a range outside its pool; an image that is not registered; a font_id that is not registered (asked
+ * only when some rule writes font-size); a multiplier that is NaN.  OSMT_UNSUPPORTED with the figure: more than
+ * OSMT_CASCADE_MAX_LAYERS distinct layer names ("*" and "default" counted, used by a selector or not); more than
+ * OSMT_LABEL_TEXT_KEYS_MAX distinct `text` strings; pools beyond 32-bit indices. */
+int osmt_validate_rules(const osmt_rules_desc* rules, osmt_ctx* ctx);
+/* Appends a rule set (append-only, the snapshot rules of selectors and styles).  At registration, on the host: per rule and
+ * name the LAST property of that name; the identifiers of line caps, text positions and fill-position as small codes; the
+ * distinct `text` strings (IDENTIFIER or STRING alike) pooled as keys, numbered by first appearance in file order.  No kernel
+ * touches a string. */
+int osmt_register_rules(osmt_ctx* ctx, const osmt_rules_desc* rules, uint32_t* out_rules_id);
+/* Runs the cascade on the device.  labels_all = 1: every style is also a label binding, as the reference pushes them;
+ * 0: only styles with an icon or a text style (the others draw nothing, labeler.rs:28-36).  OSMT_INVALID_ARG: a match of
+ * another context, a declined match, a match whose selector set is not the rules' set, an unknown rules id, labels_all that
+ * is not 0 or 1; whatever osmt_validate_styles / osmt_validate_label_styles refuse of a produced distinct record (checked
+ * on the host after the read-back, naming the record and the lowest (class, zoom, position) that produced it).
+ * OSMT_UNSUPPORTED with the figure: more than 2^31 styles over all (class, zoom) pairs (the table of distinct records has twice
+ * as many slots), more than 2^32 - 2 dashes, class styles or class label bindings over the zoom ranges.  *out is NULL on every
+ * error. */
+int osmt_cascade_classes(osmt_ctx* ctx, osmt_match* match, uint32_t rules_id, uint32_t labels_all, osmt_cascade** out);
+void osmt_cascade_free(osmt_cascade* cascade);
+/* counts = { distinct styles, dashes, distinct label styles, key bytes, keys, zoom ranges, class styles of all ranges, class
+ * label bindings of all ranges, classes } is always set; NULL outputs ask for sizes; caps[0 .. 8) bound what is written (a
+ * smaller cap with a non-NULL output is OSMT_INVALID_ARG).  zoom_lo / zoom_hi: the ranges, ascending, inclusive, together
+ * 0 .. OSMT_MAX_ZOOM.  Range r has class_style_off[r * (classes + 1) ..][classes + 1] into ITS part of class_styles, which
+ * starts at range_style_base[r] (ranges + 1 entries), and the same with class_off / bindings / range_binding_base.  Style
+ * indices are into the distinct lists of this cascade; text_key is into the keys or OSMT_TEXT_NONE. */
+int osmt_cascade_read(osmt_cascade* cascade, osmt_style_rec* styles, double* dashes, osmt_label_style_rec* label_styles, uint8_t* key_bytes,
+                      uint32_t* key_off, uint8_t* zoom_lo, uint8_t* zoom_hi, uint32_t* class_style_off, uint32_t* class_styles,
+                      uint32_t* range_style_base, uint32_t* class_off, osmt_class_label_binding* bindings, uint32_t* range_binding_base,
+                      const size_t caps[8], size_t counts[9]);
+#define OSMT_CASCADE_AREA_STYLES 1u /* osmt_register_styles + osmt_register_style_bindings_matched */
+#define OSMT_CASCADE_NODE_LABELS 2u /* osmt_register_label_styles + osmt_register_label_bindings_matched */
+#define OSMT_CASCADE_AREA_LABELS 4u /* osmt_register_label_styles + osmt_register_area_label_bindings_matched */
+/* Registers the distinct styles / label styles once and, per zoom range, the tables `what` asks for through the existing
+ * matched registrations (whose prerequisites and errors hold unchanged), and fills the per-zoom id arrays osmt_tile_batch and
+ * the two label builders take; an array `what` does not ask for may be NULL and is otherwise filled with OSMT_BINDINGS_NONE.
+ * `match` is the match the cascade was made from.  Registrations are append-only: an error half way leaves what was
+ * registered before it. */
+int osmt_cascade_register(osmt_ctx* ctx, osmt_cascade* cascade, osmt_match* match, uint32_t what, uint32_t bindings_of_zoom[OSMT_MAX_ZOOM + 1],
+                          uint32_t label_bindings_of_zoom[OSMT_MAX_ZOOM + 1], uint32_t area_label_bindings_of_zoom[OSMT_MAX_ZOOM + 1]);
+
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
 /* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */
 int osmt_project(osmt_ctx* ctx, const double* latlon, size_t n, uint8_t zoom, uint32_t tile_x, uint32_t tile_y,

@@ -604,3 +604,50 @@ assert C.sizeof(SelectorsDesc) == 48
 assert C.sizeof(NumberOverride) == 24
 assert C.sizeof(DeclinedNumber) == 8
 assert C.sizeof(MatchClass) == 24
+
+
+# ---- the cascade: styles per class and zoom from registered rules ----
+CASCADE_MAX_LAYERS = 8
+LAYER_DEFAULT = 0xFFFFFFFF  # osmt_rules_desc.selector_layer: the selector names no layer
+PROP_NAMES = ("z-index", "fill-position", "width", "casing-width", "text", "font-size", "text-color", "text-position", "color", "fill-color",
+              "background-color", "opacity", "fill-opacity", "dashes", "linecap", "casing-color", "casing-dashes", "casing-linecap", "icon-image",
+              "fill-image")  # OSMT_PROP_*: the index is the value
+PROP_OTHER = len(PROP_NAMES)
+PV_IDENTIFIER, PV_STRING, PV_COLOR, PV_NUMBERS, PV_WIDTH_DELTA = range(5)
+CASCADE_AREA_STYLES, CASCADE_NODE_LABELS, CASCADE_AREA_LABELS = 1, 2, 4
+
+
+class RuleProp(C.Structure):
+    _fields_ = [("name", C.c_uint8), ("kind", C.c_uint8), ("has_color", C.c_uint8), ("rgb", C.c_uint8 * 3), ("has_image", C.c_uint8), ("_pad", C.c_uint8),
+                ("image", C.c_uint32), ("str_off", C.c_uint32), ("str_len", C.c_uint32), ("num_off", C.c_uint32), ("n_nums", C.c_uint32),
+                ("_pad2", C.c_uint32), ("delta", C.c_double)]
+
+
+class RulesDesc(C.Structure):
+    _fields_ = [
+        ("selectors_id", C.c_uint32),
+        ("font_id", C.c_uint32),
+        ("selector_rule", C.POINTER(C.c_uint32)),
+        ("selector_layer", C.POINTER(C.c_uint32)),
+        ("n_selectors", C.c_size_t),
+        ("layer_off", C.POINTER(C.c_uint32)),
+        ("layer_bytes", C.POINTER(C.c_uint8)),
+        ("n_layers", C.c_size_t),
+        ("n_layer_bytes", C.c_size_t),
+        ("rule_prop_off", C.POINTER(C.c_uint32)),
+        ("props", C.POINTER(RuleProp)),
+        ("n_rules", C.c_size_t),
+        ("n_props", C.c_size_t),
+        ("numbers", C.POINTER(C.c_double)),
+        ("n_numbers", C.c_size_t),
+        ("strings", C.POINTER(C.c_uint8)),
+        ("n_string_bytes", C.c_size_t),
+        ("casing_width_multiplier", C.c_double),
+        ("font_size_multiplier", C.c_double),
+        ("has_font_size_multiplier", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
+assert C.sizeof(RuleProp) == 40
+assert C.sizeof(RulesDesc) == 152

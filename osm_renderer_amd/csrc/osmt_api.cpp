@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/osmtile.h"
+#include "osmt_cascade_tables.h" /* the tables of a rule set: osmt_cs_resolve */
 #include "osmt_geom.h"
 #include "osmt_internal.h"
 #include "osmt_numparse.h" /* osmt_bytes_cmp: the key order of osmt_validate_tags */
@@ -157,8 +158,18 @@ struct osmt_ctx {
     struct selectors_host {
         void* d_pool = nullptr;
         osmt_sm_sels_dev dev{};
+        std::shared_ptr<const std::vector<uint8_t>> zooms; /* [n_sels][2] the zooms a selector admits, inclusive: for the rule sets */
     };
     std::vector<selectors_host> selectors;
+    /* the rule sets of osmt_register_rules, under the same rules */
+    struct rules_host {
+        void* d_pool = nullptr;
+        osmt_cs_rules_dev dev{};
+        uint32_t selectors_id = 0;
+        std::shared_ptr<const std::vector<uint32_t>> key_off; /* the pooled `text` strings */
+        std::shared_ptr<const std::vector<uint8_t>> key_bytes;
+    };
+    std::vector<rules_host> rules;
     uint32_t match_hash_bits = 32; /* osmt_debug_match_hash_bits */
     /* the tables of osmt_register_style_bindings: append-only, one device allocation each that never moves, so a build
      * that holds a table's pointers is not disturbed by a later registration */
@@ -690,6 +701,8 @@ void ctx_teardown(osmt_ctx* ctx) {
         if (g.d_factors) (void)hipFree((void*)g.d_factors);
         if (g.d_tags) (void)hipFree(g.d_tags);
     }
+    for (auto& b : ctx->rules)
+        if (b.d_pool) (void)hipFree(b.d_pool);
     for (auto& b : ctx->selectors)
         if (b.d_pool) (void)hipFree(b.d_pool);
     for (auto& b : ctx->bindings)
@@ -6486,6 +6499,7 @@ int osmt_hbm_copy_probe(osmt_ctx* ctx, size_t bytes, uint32_t iters, double* out
 struct osmt_match {
     osmt_ctx* ctx = nullptr;
     uint32_t geodata_id = 0;
+    uint32_t selectors_id = 0;
     bool complete = false; /* false: the declined state, only the declined values can be read */
     std::vector<osmt_declined_number> declined;
     size_t n_nodes = 0, n_ways = 0, n_mps = 0, n_classes = 0, n_class_sels = 0;
@@ -6710,6 +6724,14 @@ int register_selectors_body(osmt_ctx* ctx, const osmt_selectors_desc* d, uint32_
     h.dev.sels = (const osmt_sm_sel*)(pool + o_sel);
     h.dev.tests = (const osmt_sm_test*)(pool + o_t);
     h.dev.n_keys = (uint32_t)h_keys.size(), h.dev.n_sels = (uint32_t)h_sels.size();
+    {
+        auto zooms = std::make_shared<std::vector<uint8_t>>(2 * d->n_selectors);
+        for (size_t i = 0; i < d->n_selectors; ++i) {
+            (*zooms)[2 * i] = d->selectors[i].has_min_zoom ? d->selectors[i].min_zoom : 0;
+            (*zooms)[2 * i + 1] = d->selectors[i].has_max_zoom ? d->selectors[i].max_zoom : 255;
+        }
+        h.zooms = zooms;
+    }
     std::lock_guard<std::mutex> lk(ctx->mu);
     *out_id = (uint32_t)ctx->selectors.size();
     ctx->selectors.push_back(h);
@@ -6910,6 +6932,7 @@ int match_selectors_body(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_
     std::unique_ptr<osmt_match> m(new osmt_match);
     m->ctx = ctx;
     m->geodata_id = geodata_id;
+    m->selectors_id = selectors_id;
     m->complete = true;
     m->n_nodes = geo.tags.n_nodes, m->n_ways = geo.tags.n_ways, m->n_mps = geo.tags.n_mps;
     m->n_classes = P.n_classes, m->n_class_sels = P.n_class_sels;
@@ -7456,6 +7479,508 @@ int osmt_read_area_label_bindings(osmt_ctx* ctx, uint32_t id, uint32_t* way_off,
     return guarded([&] {
         return read_area_label_bindings_body(ctx, id, way_off, way_bindings, multipolygon_off, multipolygon_bindings, text_off, chars, caps, counts);
     });
+}
+
+} /* extern "C" */
+
+/* ---- the cascade (include/osmtile.h, csrc/osmt_cascade.hip, csrc/osmt_cascade_rule.h) ------------------------------ */
+struct osmt_cascade {
+    osmt_ctx* ctx = nullptr;
+    uint32_t geodata_id = 0, selectors_id = 0;
+    size_t n_classes = 0;
+    std::vector<osmt_style_rec> styles;
+    std::vector<double> dashes;
+    std::vector<osmt_label_style_rec> label_styles;
+    std::shared_ptr<const std::vector<uint32_t>> key_off;
+    std::shared_ptr<const std::vector<uint8_t>> key_bytes;
+    std::vector<uint8_t> zoom_lo, zoom_hi;
+    std::vector<uint32_t> class_style_off, class_styles, range_style_base; /* [ranges][classes + 1], pooled, [ranges + 1] */
+    std::vector<uint32_t> class_off, range_binding_base;
+    std::vector<osmt_class_label_binding> bindings;
+};
+
+namespace {
+
+int validate_rules(const osmt_rules_desc* d, osmt_ctx* ctx, osmt_cs_tables* out_tables) {
+    if (!d) return fail(OSMT_INVALID_ARG, "rules are NULL");
+    if ((d->n_selectors && (!d->selector_rule || !d->selector_layer)) || (d->n_layer_bytes && !d->layer_bytes) || (d->n_props && !d->props) ||
+        (d->n_numbers && !d->numbers) || (d->n_string_bytes && !d->strings))
+        return fail(OSMT_INVALID_ARG, "rules: NULL array with non-zero count");
+    if (!d->layer_off || !d->rule_prop_off) return fail(OSMT_INVALID_ARG, "rules: NULL offset array (every offset array has at least its first entry)");
+    if (d->n_props >= 0xFFFFFFFFull || d->n_numbers >= 0xFFFFFFFFull || d->n_string_bytes >= 0xFFFFFFFFull || d->n_layer_bytes >= 0xFFFFFFFFull ||
+        d->n_rules >= 0xFFFFFFFFull / OSMT_PROP_NAMES || d->n_layers >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "rules: too large for 32-bit indices");
+    int rc = check_offsets_of("rules", "layer_off", d->layer_off, d->n_layers, d->n_layer_bytes);
+    if (rc == OSMT_OK) rc = check_offsets_of("rules", "rule_prop_off", d->rule_prop_off, d->n_rules, d->n_props);
+    if (rc != OSMT_OK) return rc;
+    if (std::isnan(d->casing_width_multiplier)) return fail(OSMT_INVALID_ARG, "rules: casing_width_multiplier is NaN");
+    if (d->has_font_size_multiplier > 1u) return fail(OSMT_INVALID_ARG, "rules: has_font_size_multiplier = %u (0 or 1)", d->has_font_size_multiplier);
+    if (d->has_font_size_multiplier && std::isnan(d->font_size_multiplier)) return fail(OSMT_INVALID_ARG, "rules: font_size_multiplier is NaN");
+    for (size_t i = 0; i < d->n_selectors; ++i) {
+        if (d->selector_rule[i] >= d->n_rules)
+            return fail(OSMT_INVALID_ARG, "rules: selector_rule[%zu] = %u is not below the %zu rules", i, d->selector_rule[i], d->n_rules);
+        if (i && d->selector_rule[i] < d->selector_rule[i - 1])
+            return fail(OSMT_INVALID_ARG, "rules: selector_rule[%zu] = %u decreases (selectors are in stylesheet order)", i, d->selector_rule[i]);
+        if (d->selector_layer[i] != OSMT_LAYER_DEFAULT && d->selector_layer[i] >= d->n_layers)
+            return fail(OSMT_INVALID_ARG, "rules: selector_layer[%zu] = %u is neither below the %zu layer names nor OSMT_LAYER_DEFAULT", i,
+                        d->selector_layer[i], d->n_layers);
+    }
+    size_t n_images = 0, n_fonts = 0;
+    if (ctx) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        n_images = ctx->images.size(), n_fonts = ctx->fonts.size();
+        if (d->selectors_id >= ctx->selectors.size())
+            return fail(OSMT_INVALID_ARG, "rules: selectors id %u is not registered (%zu sets)", d->selectors_id, ctx->selectors.size());
+        if (d->n_selectors != ctx->selectors[d->selectors_id].dev.n_sels)
+            return fail(OSMT_INVALID_ARG, "rules: %zu selectors, the selector set %u has %u", d->n_selectors, d->selectors_id,
+                        ctx->selectors[d->selectors_id].dev.n_sels);
+    }
+    bool writes_font_size = false;
+    for (size_t i = 0; i < d->n_props; ++i) {
+        const osmt_rule_prop& p = d->props[i];
+        if (p.name > OSMT_PROP_OTHER) return fail(OSMT_INVALID_ARG, "rules: property %zu: name %u is not an OSMT_PROP_* value", i, p.name);
+        if (p.kind >= OSMT_PV_KINDS) return fail(OSMT_INVALID_ARG, "rules: property %zu: kind %u is not an OSMT_PV_* value", i, p.kind);
+        if (p.has_color > 1 || p.has_image > 1) return fail(OSMT_INVALID_ARG, "rules: property %zu: a flag that is not 0 or 1", i);
+        const bool stringy = p.kind == OSMT_PV_IDENTIFIER || p.kind == OSMT_PV_STRING;
+        if (p.kind == OSMT_PV_COLOR && !p.has_color) return fail(OSMT_INVALID_ARG, "rules: property %zu: a COLOR value has has_color = 1", i);
+        if (p.has_color && p.kind != OSMT_PV_COLOR && p.kind != OSMT_PV_IDENTIFIER)
+            return fail(OSMT_INVALID_ARG, "rules: property %zu: has_color on a value that is neither COLOR nor IDENTIFIER", i);
+        if (p.has_image && !(stringy && (p.name == OSMT_PROP_ICON_IMAGE || p.name == OSMT_PROP_FILL_IMAGE)))
+            return fail(OSMT_INVALID_ARG, "rules: property %zu: has_image on a property that is not an IDENTIFIER or STRING of icon-image / fill-image", i);
+        if (stringy && (size_t)p.str_off + p.str_len > d->n_string_bytes)
+            return fail(OSMT_INVALID_ARG, "rules: property %zu: string %u..%zu leaves the %zu string bytes", i, p.str_off, (size_t)p.str_off + p.str_len,
+                        d->n_string_bytes);
+        if (p.kind == OSMT_PV_NUMBERS && (size_t)p.num_off + p.n_nums > d->n_numbers)
+            return fail(OSMT_INVALID_ARG, "rules: property %zu: numbers %u..%zu leave the %zu numbers", i, p.num_off, (size_t)p.num_off + p.n_nums, d->n_numbers);
+        if (ctx && stringy && (p.name == OSMT_PROP_ICON_IMAGE || p.name == OSMT_PROP_FILL_IMAGE) && p.has_image && p.image >= n_images)
+            return fail(OSMT_INVALID_ARG, "rules: property %zu: image %u is not registered (%zu images)", i, p.image, n_images);
+        if (p.name == OSMT_PROP_FONT_SIZE) writes_font_size = true;
+    }
+    if (ctx && writes_font_size && d->font_id >= n_fonts) return fail(OSMT_INVALID_ARG, "rules: font_id %u is not registered (%zu fonts)", d->font_id, n_fonts);
+    osmt_cs_tables local;
+    osmt_cs_tables& T = out_tables ? *out_tables : local;
+    size_t n_names = 0;
+    osmt_cs_resolve(*d, T, &n_names);
+    if (n_names > OSMT_CASCADE_MAX_LAYERS)
+        return fail(OSMT_UNSUPPORTED, "rules: %zu distinct layer names (> OSMT_CASCADE_MAX_LAYERS = %u)", n_names, OSMT_CASCADE_MAX_LAYERS);
+    if (T.key_off.size() - 1 > OSMT_LABEL_TEXT_KEYS_MAX)
+        return fail(OSMT_UNSUPPORTED, "rules: %zu distinct text strings (> OSMT_LABEL_TEXT_KEYS_MAX = %u)", T.key_off.size() - 1, OSMT_LABEL_TEXT_KEYS_MAX);
+    return OSMT_OK;
+}
+
+int register_rules_body(osmt_ctx* ctx, const osmt_rules_desc* d, uint32_t* out_id) {
+    if (!ctx || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    osmt_cs_tables T;
+    const int rc = validate_rules(d, ctx, &T);
+    if (rc != OSMT_OK) return rc;
+    std::shared_ptr<const std::vector<uint8_t>> zooms;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        zooms = ctx->selectors[d->selectors_id].zooms;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 8), 256);
+        return o;
+    };
+    const size_t o_p = carve(T.props.size() * sizeof(osmt_cs_prop)), o_l = carve(T.rule_last.size() * 4), o_r = carve(d->n_selectors * 4);
+    const size_t o_g = carve(d->n_selectors), o_z = carve(d->n_selectors * 2), o_n = carve(d->n_numbers * 8);
+    char* pool = nullptr;
+    HIP_TRY(hipMalloc((void**)&pool, off));
+    hipError_t e = hipSuccess;
+    auto put = [&](size_t o, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+    };
+    put(o_p, T.props.data(), T.props.size() * sizeof(osmt_cs_prop));
+    put(o_l, T.rule_last.data(), T.rule_last.size() * 4);
+    put(o_r, d->selector_rule, d->n_selectors * 4);
+    put(o_g, T.sel_layer.data(), d->n_selectors);
+    put(o_z, zooms->data(), d->n_selectors * 2);
+    put(o_n, d->numbers, d->n_numbers * 8);
+    if (e != hipSuccess) {
+        (void)hipFree(pool);
+        return fail(OSMT_HIP_ERROR, "rules upload failed: %s", hipGetErrorString(e));
+    }
+    osmt_ctx::rules_host h;
+    h.d_pool = pool;
+    h.selectors_id = d->selectors_id;
+    h.dev.props = (const osmt_cs_prop*)(pool + o_p);
+    h.dev.rule_last = (const uint32_t*)(pool + o_l);
+    h.dev.sel_rule = (const uint32_t*)(pool + o_r);
+    h.dev.sel_layer = (const uint8_t*)(pool + o_g);
+    h.dev.sel_zoom = (const uint8_t*)(pool + o_z);
+    h.dev.numbers = (const double*)(pool + o_n);
+    h.dev.n_sels = (uint32_t)d->n_selectors, h.dev.n_layers = T.n_layers, h.dev.star = T.star, h.dev.base = T.base;
+    h.dev.font_id = d->font_id;
+    h.dev.casing_width_multiplier = d->casing_width_multiplier;
+    h.dev.font_size_multiplier = d->has_font_size_multiplier ? d->font_size_multiplier : 1.0;
+    h.key_off = std::make_shared<std::vector<uint32_t>>(std::move(T.key_off));
+    h.key_bytes = std::make_shared<std::vector<uint8_t>>(std::move(T.key_bytes));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    *out_id = (uint32_t)ctx->rules.size();
+    ctx->rules.push_back(h);
+    return OSMT_OK;
+}
+
+int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32_t labels_all, osmt_cascade** out) {
+    if (!ctx || !m || !out) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (m->ctx != ctx) return fail(OSMT_INVALID_ARG, "cascade: the match belongs to another context");
+    if (!m->complete) return fail(OSMT_INVALID_ARG, "cascade: the match is in the declined state");
+    if (labels_all > 1u) return fail(OSMT_INVALID_ARG, "cascade: labels_all = %u (0 or 1)", labels_all);
+    osmt_ctx::rules_host rules;
+    uint32_t hash_bits = 32;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (rules_id >= ctx->rules.size()) return fail(OSMT_INVALID_ARG, "cascade: rules id %u is not registered (%zu sets)", rules_id, ctx->rules.size());
+        rules = ctx->rules[rules_id];
+        hash_bits = ctx->match_hash_bits;
+    }
+    if (rules.selectors_id != m->selectors_id)
+        return fail(OSMT_INVALID_ARG, "cascade: the match was made with selector set %u, the rules are over set %u", m->selectors_id, rules.selectors_id);
+    const size_t n_classes = m->n_classes;
+    if (n_classes * (size_t)OSMT_CS_ZOOMS >= 0xFFFFFFFFull / 32u)
+        return fail(OSMT_UNSUPPORTED, "cascade: %zu classes x %u zooms do not fit the 32-bit lane index", n_classes, OSMT_CS_ZOOMS);
+    HIP_TRY(hipSetDevice(ctx->device));
+    struct work_guard {
+        osmt_ctx* ctx;
+        hipStream_t st = nullptr;
+        std::vector<char*> work;
+        ~work_guard() {
+            if (st) (void)hipStreamSynchronize(st);
+            for (char* p : work) dev_free(ctx, p);
+            stream_release(ctx, st);
+        }
+    } wg{ctx};
+    HIP_TRY(stream_acquire(ctx, &wg.st));
+    hipStream_t st = wg.st;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + std::max<size_t>(bytes, 8), 256);
+        return o;
+    };
+    char* base = nullptr;
+    auto alloc = [&](const char* what) {
+        char* p = nullptr;
+        const hipError_t e = dev_alloc(ctx, (void**)&p, off + 256);
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the cascade (%s) failed: %s", off, what, hipGetErrorString(e));
+        wg.work.push_back(p);
+        base = p;
+        off = 0;
+        return (int)OSMT_OK;
+    };
+    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    enum { EV_0, EV_FOLD, EV_DISTINCT, EV_COMPACT, EV_RANGES, EV_N };
+    hipEvent_t ev[EV_N] = {};
+    struct ev_guard {
+        hipEvent_t* ev;
+        ~ev_guard() {
+            for (int i = 0; i < EV_N; ++i)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } evg{ev};
+    if (trace)
+        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+
+    unsigned long long tot[OSMT_CS_T_N] = {};
+    osmt_cs_pass P;
+    memset(&P, 0, sizeof P);
+    P.R = rules.dev;
+    P.classes = m->d_classes, P.class_sels = m->d_class_sels;
+    P.n_classes = (uint32_t)n_classes, P.n_pairs = (uint32_t)(n_classes * OSMT_CS_ZOOMS);
+    P.labels_all = labels_all;
+    P.hash_mask = hash_bits >= 32u ? 0xFFFFFFFFu : (1u << hash_bits) - 1u;
+    auto read_tot = [&](int first, int n) {
+        hipError_t e = hipMemcpyAsync(tot + first, P.tot + first, (size_t)n * 8, hipMemcpyDeviceToHost, st);
+        return e == hipSuccess ? hipStreamSynchronize(st) : e;
+    };
+    /* 1. count */
+    const size_t n_pairs = P.n_pairs;
+    const size_t o_pp = carve((n_pairs + 1) * 4), o_tot = carve(OSMT_CS_T_N * 8), o_zd = carve(OSMT_CS_ZOOMS * 4), o_blk0 = carve((n_pairs / 256 + 1) * 8);
+    int rc = alloc("pairs");
+    if (rc != OSMT_OK) return rc;
+    P.pair_pos = (uint32_t*)(base + o_pp);
+    P.tot = (unsigned long long*)(base + o_tot);
+    P.zoom_differs = (uint32_t*)(base + o_zd);
+    P.blk = (unsigned long long*)(base + o_blk0);
+    HIP_TRY(mark(EV_0));
+    HIP_TRY(osmt_launch_cs_count(P, st));
+    HIP_TRY(read_tot(OSMT_CS_T_STYLES, 1));
+    if (tot[OSMT_CS_T_STYLES] > 0x80000000ull)
+        return fail(OSMT_UNSUPPORTED, "cascade: %llu styles over all classes and zooms (the table of distinct records holds at most 2^31)", tot[OSMT_CS_T_STYLES]);
+    const size_t n_styles = (size_t)tot[OSMT_CS_T_STYLES];
+    P.n_styles = (uint32_t)n_styles;
+    /* 2. fold and records */
+    size_t table = 2;
+    while (table < 2 * n_styles) table <<= 1;
+    P.table_mask = (uint32_t)(table - 1);
+    const size_t o_rows = carve(n_styles * OSMT_CS_ROW_WORDS * 4), o_area = carve(n_styles * sizeof(osmt_style_rec)), o_lab = carve(n_styles * sizeof(osmt_label_style_rec));
+    const size_t o_key = carve(n_styles * 4), o_bp = carve((n_styles + 1) * 4), o_blk = carve((std::max(n_styles, n_pairs) / 256 + 1) * 8);
+    size_t o_hash[2], o_ts[2], o_fp[2], o_id[2], o_tab[2], o_low[2];
+    for (int k = 0; k < 2; ++k) {
+        o_hash[k] = carve(n_styles * 4), o_ts[k] = carve(n_styles * 4), o_fp[k] = carve((n_styles + 1) * 4), o_id[k] = carve(n_styles * 4);
+        o_tab[k] = carve(table * 4), o_low[k] = carve(table * 4);
+    }
+    rc = alloc("styles");
+    if (rc != OSMT_OK) return rc;
+    P.rows = (uint32_t*)(base + o_rows);
+    P.area = (osmt_style_rec*)(base + o_area);
+    P.label = (osmt_label_style_rec*)(base + o_lab);
+    P.text_key = (uint32_t*)(base + o_key);
+    P.bind_pos = (uint32_t*)(base + o_bp);
+    P.blk = (unsigned long long*)(base + o_blk);
+    for (int k = 0; k < 2; ++k) {
+        P.hash[k] = (uint32_t*)(base + o_hash[k]), P.tslot[k] = (uint32_t*)(base + o_ts[k]), P.first_pos[k] = (uint32_t*)(base + o_fp[k]);
+        P.id[k] = (uint32_t*)(base + o_id[k]), P.table[k] = (uint32_t*)(base + o_tab[k]), P.lowest[k] = (uint32_t*)(base + o_low[k]);
+    }
+    HIP_TRY(osmt_launch_cs_fold(P, st));
+    HIP_TRY(mark(EV_FOLD));
+    /* 3. distinct records */
+    HIP_TRY(osmt_launch_cs_distinct(P, st));
+    HIP_TRY(read_tot(OSMT_CS_T_BINDINGS, 3));
+    P.n_bindings = (uint32_t)tot[OSMT_CS_T_BINDINGS], P.n_area = (uint32_t)tot[OSMT_CS_T_AREA], P.n_label = (uint32_t)tot[OSMT_CS_T_LABEL];
+    const size_t n_area = P.n_area, n_label = P.n_label;
+    const size_t o_dp = carve((n_area + 1) * 4), o_r0 = carve(n_area * 4), o_r1 = carve(n_label * 4);
+    const size_t o_oa = carve(n_area * sizeof(osmt_style_rec)), o_ol = carve(n_label * sizeof(osmt_label_style_rec));
+    rc = alloc("distinct records");
+    if (rc != OSMT_OK) return rc;
+    P.dash_pos = (uint32_t*)(base + o_dp);
+    P.rep[0] = (uint32_t*)(base + o_r0), P.rep[1] = (uint32_t*)(base + o_r1);
+    P.out_area = (osmt_style_rec*)(base + o_oa);
+    P.out_label = (osmt_label_style_rec*)(base + o_ol);
+    HIP_TRY(osmt_launch_cs_rank(P, st));
+    HIP_TRY(read_tot(OSMT_CS_T_DASHES, 1));
+    HIP_TRY(mark(EV_DISTINCT));
+    const size_t n_dashes = (size_t)tot[OSMT_CS_T_DASHES]; /* at most 2 x 2^32 per record sum: checked against 32 bits below */
+    if (n_dashes >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "cascade: %zu dashes of the distinct styles (> 2^32 - 2)", n_dashes);
+    (void)carve(n_dashes * 8);
+    rc = alloc("dashes");
+    if (rc != OSMT_OK) return rc;
+    P.out_dashes = (double*)base;
+    HIP_TRY(osmt_launch_cs_compact(P, st));
+    uint32_t differs[OSMT_CS_ZOOMS] = {};
+    HIP_TRY(hipMemcpyAsync(differs, P.zoom_differs, sizeof differs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(mark(EV_COMPACT));
+    /* 4. zoom ranges: the maximal runs */
+    std::unique_ptr<osmt_cascade> c(new osmt_cascade);
+    for (uint32_t z = 0; z < OSMT_CS_ZOOMS; ++z) {
+        if (z == 0 || differs[z]) {
+            P.range_zoom[c->zoom_lo.size()] = (uint8_t)z;
+            c->zoom_lo.push_back((uint8_t)z);
+            c->zoom_hi.push_back((uint8_t)z);
+        } else {
+            c->zoom_hi.back() = (uint8_t)z;
+        }
+    }
+    const size_t n_ranges = c->zoom_lo.size(), n_rc = n_ranges * n_classes;
+    P.n_ranges = (uint32_t)n_ranges;
+    const size_t o_rs = carve((n_rc + 1) * 4), o_rb = carve((n_rc + 1) * 4), o_so = carve(n_ranges * (n_classes + 1) * 4), o_bo = carve(n_ranges * (n_classes + 1) * 4);
+    const size_t o_blk2 = carve((n_rc / 256 + 1) * 8);
+    rc = alloc("ranges");
+    if (rc != OSMT_OK) return rc;
+    P.rs_pos = (uint32_t*)(base + o_rs), P.rb_pos = (uint32_t*)(base + o_rb);
+    P.out_style_off = (uint32_t*)(base + o_so), P.out_bind_off = (uint32_t*)(base + o_bo);
+    P.blk = (unsigned long long*)(base + o_blk2);
+    HIP_TRY(osmt_launch_cs_range_count(P, st));
+    HIP_TRY(read_tot(OSMT_CS_T_RANGE_STYLES, 2));
+    if (tot[OSMT_CS_T_RANGE_STYLES] >= 0xFFFFFFFFull || tot[OSMT_CS_T_RANGE_BINDINGS] >= 0xFFFFFFFFull)
+        return fail(OSMT_UNSUPPORTED, "cascade: %llu class styles and %llu class label bindings over the %zu zoom ranges (> 2^32 - 2)", tot[OSMT_CS_T_RANGE_STYLES],
+                    tot[OSMT_CS_T_RANGE_BINDINGS], n_ranges);
+    const size_t n_rs = (size_t)tot[OSMT_CS_T_RANGE_STYLES], n_rb = (size_t)tot[OSMT_CS_T_RANGE_BINDINGS];
+    const size_t o_os = carve(n_rs * 4), o_ob = carve(n_rb * sizeof(osmt_class_label_binding));
+    rc = alloc("lists");
+    if (rc != OSMT_OK) return rc;
+    P.out_styles = (uint32_t*)(base + o_os);
+    P.out_binds = (osmt_class_label_binding*)(base + o_ob);
+    HIP_TRY(osmt_launch_cs_range_emit(P, st));
+    HIP_TRY(mark(EV_RANGES));
+    /* 5. the result comes to the host: the registrations take host arrays */
+    c->ctx = ctx, c->geodata_id = m->geodata_id, c->selectors_id = m->selectors_id, c->n_classes = n_classes;
+    c->key_off = rules.key_off, c->key_bytes = rules.key_bytes;
+    c->styles.resize(n_area), c->dashes.resize(n_dashes), c->label_styles.resize(n_label);
+    c->class_style_off.resize(n_ranges * (n_classes + 1)), c->class_off.resize(n_ranges * (n_classes + 1));
+    c->class_styles.resize(n_rs), c->bindings.resize(n_rb);
+    c->range_style_base.resize(n_ranges + 1), c->range_binding_base.resize(n_ranges + 1);
+    auto back = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
+    HIP_TRY(back(c->styles.data(), P.out_area, n_area * sizeof(osmt_style_rec)));
+    HIP_TRY(back(c->dashes.data(), P.out_dashes, n_dashes * 8));
+    HIP_TRY(back(c->label_styles.data(), P.out_label, n_label * sizeof(osmt_label_style_rec)));
+    HIP_TRY(back(c->class_style_off.data(), P.out_style_off, c->class_style_off.size() * 4));
+    HIP_TRY(back(c->class_off.data(), P.out_bind_off, c->class_off.size() * 4));
+    HIP_TRY(back(c->class_styles.data(), P.out_styles, n_rs * 4));
+    HIP_TRY(back(c->bindings.data(), P.out_binds, n_rb * sizeof(osmt_class_label_binding)));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t r = 0; r <= n_ranges; ++r) {
+        /* a range's base is the sum of the ranges before it: the last offset of each */
+        c->range_style_base[r] = r ? c->range_style_base[r - 1] + c->class_style_off[(r - 1) * (n_classes + 1) + n_classes] : 0u;
+        c->range_binding_base[r] = r ? c->range_binding_base[r - 1] + c->class_off[(r - 1) * (n_classes + 1) + n_classes] : 0u;
+    }
+    /* what the registrations would refuse of a produced record is refused here, naming its lowest user */
+    for (int k = 0; k < 2; ++k) {
+        const size_t n = k == 0 ? n_area : n_label;
+        size_t bad = n;
+        int vrc = OSMT_OK;
+        for (size_t i = 0; i < n && vrc == OSMT_OK; ++i) {
+            vrc = k == 0 ? validate_styles(&c->styles[i], 1, c->dashes.data(), n_dashes, ctx_image_count(ctx)) : validate_label_styles(&c->label_styles[i], 1, ctx);
+            if (vrc != OSMT_OK) bad = i;
+        }
+        if (vrc == OSMT_OK) continue;
+        const std::string why = g_last_error;
+        uint32_t s = 0, user[2] = {};
+        HIP_TRY(copy_back(ctx, &s, P.rep[k] + bad, 4));
+        HIP_TRY(copy_back(ctx, user, P.rows + (size_t)s * OSMT_CS_ROW_WORDS + OSMT_CS_ROW_PAIR, 8));
+        return fail(vrc == OSMT_UNSUPPORTED ? OSMT_UNSUPPORTED : OSMT_INVALID_ARG,
+                    "cascade: distinct %s %zu is refused (%s); it is produced first by class %u at zoom %u, layer position %u", k == 0 ? "style" : "label style", bad,
+                    why.c_str(), user[0] / OSMT_CS_ZOOMS, user[0] % OSMT_CS_ZOOMS, user[1]);
+    }
+    ctx->refs.fetch_add(1);
+    *out = c.release();
+    if (trace) {
+        auto us = [&](int a, int b2) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
+            return ms * 1e3;
+        };
+        fprintf(stderr,
+                "osmt cascade: count + fold + records %.1f us, distinct %.1f us, compact + zooms %.1f us, ranges %.1f us (%zu classes, %zu styles, %zu + %zu "
+                "distinct, %zu ranges)\n",
+                us(EV_0, EV_FOLD), us(EV_FOLD, EV_DISTINCT), us(EV_DISTINCT, EV_COMPACT), us(EV_COMPACT, EV_RANGES), n_classes, n_styles, n_area, n_label, n_ranges);
+    }
+    return OSMT_OK;
+}
+
+int cascade_read_body(osmt_cascade* c, osmt_style_rec* styles, double* dashes, osmt_label_style_rec* label_styles, uint8_t* key_bytes, uint32_t* key_off,
+                      uint8_t* zoom_lo, uint8_t* zoom_hi, uint32_t* class_style_off, uint32_t* class_styles, uint32_t* range_style_base, uint32_t* class_off,
+                      osmt_class_label_binding* bindings, uint32_t* range_binding_base, const size_t caps[8], size_t counts[9]) {
+    if (!c || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
+    const size_t n_ranges = c->zoom_lo.size();
+    counts[0] = c->styles.size(), counts[1] = c->dashes.size(), counts[2] = c->label_styles.size(), counts[3] = c->key_bytes->size();
+    counts[4] = c->key_off->size() - 1, counts[5] = n_ranges, counts[6] = c->class_styles.size(), counts[7] = c->bindings.size(), counts[8] = c->n_classes;
+    const bool any = styles || dashes || label_styles || key_bytes || key_off || zoom_lo || zoom_hi || class_style_off || class_styles || range_style_base ||
+                     class_off || bindings || range_binding_base;
+    if (!any) return OSMT_OK;
+    if (!caps) return fail(OSMT_INVALID_ARG, "NULL caps with an output");
+    const bool wants[8] = {styles != nullptr,
+                           dashes != nullptr,
+                           label_styles != nullptr,
+                           key_bytes != nullptr,
+                           key_off != nullptr,
+                           zoom_lo || zoom_hi || class_style_off || range_style_base || class_off || range_binding_base,
+                           class_styles != nullptr,
+                           bindings != nullptr};
+    for (int i = 0; i < 8; ++i)
+        if (wants[i] && caps[i] < counts[i]) return fail(OSMT_INVALID_ARG, "cascade read: caps[%d] = %zu is less than %zu", i, caps[i], counts[i]);
+    auto put = [](void* dst, const void* src, size_t bytes) {
+        if (dst && bytes) memcpy(dst, src, bytes);
+    };
+    put(styles, c->styles.data(), c->styles.size() * sizeof(osmt_style_rec));
+    put(dashes, c->dashes.data(), c->dashes.size() * 8);
+    put(label_styles, c->label_styles.data(), c->label_styles.size() * sizeof(osmt_label_style_rec));
+    put(key_bytes, c->key_bytes->data(), c->key_bytes->size());
+    put(key_off, c->key_off->data(), c->key_off->size() * 4);
+    put(zoom_lo, c->zoom_lo.data(), n_ranges);
+    put(zoom_hi, c->zoom_hi.data(), n_ranges);
+    put(class_style_off, c->class_style_off.data(), c->class_style_off.size() * 4);
+    put(class_styles, c->class_styles.data(), c->class_styles.size() * 4);
+    put(range_style_base, c->range_style_base.data(), c->range_style_base.size() * 4);
+    put(class_off, c->class_off.data(), c->class_off.size() * 4);
+    put(bindings, c->bindings.data(), c->bindings.size() * sizeof(osmt_class_label_binding));
+    put(range_binding_base, c->range_binding_base.data(), c->range_binding_base.size() * 4);
+    return OSMT_OK;
+}
+
+int cascade_register_body(osmt_ctx* ctx, osmt_cascade* c, osmt_match* m, uint32_t what, uint32_t* bind_of_zoom, uint32_t* label_of_zoom, uint32_t* area_label_of_zoom) {
+    if (!ctx || !c || !m) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (c->ctx != ctx || m->ctx != ctx) return fail(OSMT_INVALID_ARG, "cascade register: the cascade or the match belongs to another context");
+    if (!m->complete || m->n_classes != c->n_classes || m->geodata_id != c->geodata_id || m->selectors_id != c->selectors_id)
+        return fail(OSMT_INVALID_ARG, "cascade register: the match is not the one the cascade was made from");
+    const uint32_t all = OSMT_CASCADE_AREA_STYLES | OSMT_CASCADE_NODE_LABELS | OSMT_CASCADE_AREA_LABELS;
+    if (what == 0u || (what & ~all)) return fail(OSMT_INVALID_ARG, "cascade register: what = 0x%x (a non-empty set of OSMT_CASCADE_* bits)", what);
+    if (((what & OSMT_CASCADE_AREA_STYLES) && !bind_of_zoom) || ((what & OSMT_CASCADE_NODE_LABELS) && !label_of_zoom) ||
+        ((what & OSMT_CASCADE_AREA_LABELS) && !area_label_of_zoom))
+        return fail(OSMT_INVALID_ARG, "cascade register: NULL id array for a table `what` asks for");
+    for (uint32_t* a : {bind_of_zoom, label_of_zoom, area_label_of_zoom})
+        if (a) std::fill(a, a + OSMT_MAX_ZOOM + 1, OSMT_BINDINGS_NONE);
+    const size_t n = c->n_classes, n_ranges = c->zoom_lo.size();
+    int rc = OSMT_OK;
+    if (what & OSMT_CASCADE_AREA_STYLES) {
+        uint32_t first = 0;
+        rc = register_styles_body(ctx, c->styles.data(), c->styles.size(), c->dashes.data(), c->dashes.size(), &first);
+        std::vector<uint32_t> ids;
+        for (size_t r = 0; r < n_ranges && rc == OSMT_OK; ++r) {
+            ids.assign(c->class_styles.begin() + c->range_style_base[r], c->class_styles.begin() + c->range_style_base[r + 1]);
+            for (uint32_t& v : ids) v += first;
+            uint32_t id = 0;
+            rc = bindings_matched_body(ctx, m, c->zoom_lo[r], c->zoom_hi[r], c->class_style_off.data() + r * (n + 1), ids.data(), n, &id);
+            for (uint32_t z = c->zoom_lo[r]; rc == OSMT_OK && z <= c->zoom_hi[r]; ++z) bind_of_zoom[z] = id;
+        }
+        if (rc != OSMT_OK) return rc;
+    }
+    if (what & (OSMT_CASCADE_NODE_LABELS | OSMT_CASCADE_AREA_LABELS)) {
+        uint32_t first = 0;
+        rc = register_label_styles_body(ctx, c->label_styles.data(), c->label_styles.size(), &first);
+        std::vector<osmt_class_label_binding> b;
+        for (size_t r = 0; r < n_ranges && rc == OSMT_OK; ++r) {
+            b.assign(c->bindings.begin() + c->range_binding_base[r], c->bindings.begin() + c->range_binding_base[r + 1]);
+            for (osmt_class_label_binding& v : b) v.style += first;
+            osmt_class_label_bindings_desc d{};
+            d.zoom_lo = c->zoom_lo[r], d.zoom_hi = c->zoom_hi[r];
+            d.class_off = c->class_off.data() + r * (n + 1);
+            d.bindings = b.data();
+            d.n_classes = n, d.n_bindings = b.size();
+            d.key_off = c->key_off->data(), d.key_bytes = c->key_bytes->data();
+            d.n_keys = c->key_off->size() - 1, d.n_key_bytes = c->key_bytes->size();
+            uint32_t id = 0;
+            if (what & OSMT_CASCADE_NODE_LABELS) {
+                rc = label_bindings_matched_body(ctx, m, &d, &id, false);
+                for (uint32_t z = d.zoom_lo; rc == OSMT_OK && z <= d.zoom_hi; ++z) label_of_zoom[z] = id;
+            }
+            if (rc == OSMT_OK && (what & OSMT_CASCADE_AREA_LABELS)) {
+                rc = label_bindings_matched_body(ctx, m, &d, &id, true);
+                for (uint32_t z = d.zoom_lo; rc == OSMT_OK && z <= d.zoom_hi; ++z) area_label_of_zoom[z] = id;
+            }
+        }
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int osmt_validate_rules(const osmt_rules_desc* rules, osmt_ctx* ctx) {
+    return guarded([&] { return validate_rules(rules, ctx, nullptr); });
+}
+int osmt_register_rules(osmt_ctx* ctx, const osmt_rules_desc* rules, uint32_t* out_rules_id) {
+    return guarded([&] { return register_rules_body(ctx, rules, out_rules_id); });
+}
+int osmt_cascade_classes(osmt_ctx* ctx, osmt_match* match, uint32_t rules_id, uint32_t labels_all, osmt_cascade** out) {
+    return guarded([&] { return cascade_classes_body(ctx, match, rules_id, labels_all, out); });
+}
+void osmt_cascade_free(osmt_cascade* c) {
+    if (!c) return;
+    osmt_ctx* ctx = c->ctx;
+    delete c;
+    ctx_release(ctx);
+}
+int osmt_cascade_read(osmt_cascade* cascade, osmt_style_rec* styles, double* dashes, osmt_label_style_rec* label_styles, uint8_t* key_bytes,
+                      uint32_t* key_off, uint8_t* zoom_lo, uint8_t* zoom_hi, uint32_t* class_style_off, uint32_t* class_styles,
+                      uint32_t* range_style_base, uint32_t* class_off, osmt_class_label_binding* bindings, uint32_t* range_binding_base,
+                      const size_t caps[8], size_t counts[9]) {
+    return guarded([&] {
+        return cascade_read_body(cascade, styles, dashes, label_styles, key_bytes, key_off, zoom_lo, zoom_hi, class_style_off, class_styles, range_style_base,
+                                 class_off, bindings, range_binding_base, caps, counts);
+    });
+}
+int osmt_cascade_register(osmt_ctx* ctx, osmt_cascade* cascade, osmt_match* match, uint32_t what, uint32_t bindings_of_zoom[OSMT_MAX_ZOOM + 1],
+                          uint32_t label_bindings_of_zoom[OSMT_MAX_ZOOM + 1], uint32_t area_label_bindings_of_zoom[OSMT_MAX_ZOOM + 1]) {
+    return guarded([&] { return cascade_register_body(ctx, cascade, match, what, bindings_of_zoom, label_bindings_of_zoom, area_label_bindings_of_zoom); });
 }
 
 } /* extern "C" */

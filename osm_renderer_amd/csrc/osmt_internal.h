@@ -833,6 +833,78 @@ hipError_t osmt_launch_lb_decode(const osmt_lb_pass& a, hipStream_t st);
 /* k_lb_patch: the provisional tag numbers of bind[0 .. n) replaced by text ids */
 hipError_t osmt_launch_lb_patch(const osmt_lb_pass& a, osmt_label_binding* bind, uint32_t n, hipStream_t st);
 
+/* ---- the cascade (osmt_cascade.hip) ------------------------------------------------------------------------------- */
+struct osmt_cs_prop;
+/* a registered rule set */
+struct osmt_cs_rules_dev {
+    const osmt_cs_prop* props;
+    const uint32_t* rule_last;  /* [n_rules][OSMT_PROP_NAMES] */
+    const uint32_t* sel_rule;   /* [n_sels] */
+    const uint8_t* sel_layer;   /* [n_sels] 0 .. n_layers - 1 */
+    const uint8_t* sel_zoom;    /* [n_sels][2] the zooms the selector admits, inclusive (0, 255 without bounds) */
+    const double* numbers;
+    uint32_t n_sels, n_layers, star, base; /* star / base: the layers "*" and "default", or OSMT_CS_NONE */
+    uint32_t font_id, _pad;
+    double casing_width_multiplier, font_size_multiplier;
+};
+/* words of osmt_cs_pass::tot */
+enum { OSMT_CS_T_STYLES = 0, OSMT_CS_T_BINDINGS, OSMT_CS_T_AREA, OSMT_CS_T_LABEL, OSMT_CS_T_DASHES, OSMT_CS_T_RANGE_STYLES, OSMT_CS_T_RANGE_BINDINGS, OSMT_CS_T_N };
+struct osmt_cs_pass {
+    osmt_cs_rules_dev R;
+    const osmt_match_class* classes;
+    const uint32_t* class_sels;
+    uint32_t n_classes, n_pairs;  /* pairs: (class, zoom), number class * 19 + zoom */
+    uint32_t n_styles, n_bindings, n_area, n_label, n_ranges; /* totals, known once they have been read back */
+    uint32_t labels_all;
+    uint32_t hash_mask, table_mask;
+    /* per pair */
+    uint32_t* pair_pos; /* [n_pairs + 1] styles, then their exclusive scan */
+    /* per style (user): number = position in pair order, monotonic in ((class * 19) + zoom) * 8 + position */
+    uint32_t* rows;             /* [n_styles][OSMT_CS_ROW_WORDS] */
+    osmt_style_rec* area;       /* [n_styles] dashes as ranges of R.numbers */
+    osmt_label_style_rec* label;
+    uint32_t* text_key;
+    uint32_t* bind_pos;         /* [n_styles + 1] 1: the style is a label binding; then the exclusive scan */
+    uint32_t* hash[2];          /* area, label */
+    uint32_t* tslot[2];
+    uint32_t* first_pos[2];     /* [n_styles + 1] 1: the lowest user of its record; then the scan: the distinct id */
+    uint32_t* id[2];            /* the distinct id of the style's record (label: of a binding's, else undefined) */
+    uint32_t* table[2];         /* [table_mask + 1] */
+    uint32_t* lowest[2];
+    /* per distinct record */
+    uint32_t* dash_pos;         /* [n_area + 1] dashes of the record, then the scan */
+    osmt_style_rec* out_area;   /* [n_area] dashes as ranges of out_dashes */
+    double* out_dashes;
+    osmt_label_style_rec* out_label; /* [n_label] */
+    uint32_t* rep[2];           /* [n_area], [n_label] the lowest user */
+    /* zooms */
+    uint32_t* zoom_differs;     /* [19] 1: some class's lists at z differ from those at z - 1 (z >= 1) */
+    uint8_t range_zoom[OSMT_MAX_ZOOM + 1]; /* the first zoom of range r */
+    /* per (range, class), number range * n_classes + class */
+    uint32_t* rs_pos;           /* [n_ranges * n_classes + 1] styles, then the scan */
+    uint32_t* rb_pos;           /* the same for label bindings */
+    uint32_t* out_style_off;    /* [n_ranges][n_classes + 1] rebased to the range */
+    uint32_t* out_styles;       /* distinct area ids */
+    uint32_t* out_bind_off;
+    osmt_class_label_binding* out_binds;
+    unsigned long long* blk;
+    unsigned long long* tot; /* [OSMT_CS_T_N] */
+};
+/* k_cs_count + scan: tot[STYLES] */
+hipError_t osmt_launch_cs_count(const osmt_cs_pass& a, hipStream_t st);
+/* k_cs_fold + k_cs_records + scan: rows, records, hashes, tot[BINDINGS] */
+hipError_t osmt_launch_cs_fold(const osmt_cs_pass& a, hipStream_t st);
+/* k_cs_insert + k_cs_mark + scan, both kinds: tot[AREA], tot[LABEL] */
+hipError_t osmt_launch_cs_distinct(const osmt_cs_pass& a, hipStream_t st);
+/* k_cs_rank + scan: id, rep, dash_pos, tot[DASHES] */
+hipError_t osmt_launch_cs_rank(const osmt_cs_pass& a, hipStream_t st);
+/* k_cs_compact + k_cs_zoom_differs: out_area, out_dashes, out_label, zoom_differs */
+hipError_t osmt_launch_cs_compact(const osmt_cs_pass& a, hipStream_t st);
+/* k_cs_range_count + scans: tot[RANGE_STYLES], tot[RANGE_BINDINGS] */
+hipError_t osmt_launch_cs_range_count(const osmt_cs_pass& a, hipStream_t st);
+/* k_cs_range_emit */
+hipError_t osmt_launch_cs_range_emit(const osmt_cs_pass& a, hipStream_t st);
+
 /* out[i] = osmt_hypot(xy[2i], xy[2i + 1]) */
 hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStream_t st);
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */

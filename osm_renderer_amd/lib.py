@@ -50,6 +50,7 @@ EXPORTS = [
     "osmt_debug_match_hash_bits",
     "osmt_validate_class_label_bindings", "osmt_register_label_bindings_matched", "osmt_register_area_label_bindings_matched",
     "osmt_read_label_bindings", "osmt_read_area_label_bindings",
+    "osmt_validate_rules", "osmt_register_rules", "osmt_cascade_classes", "osmt_cascade_free", "osmt_cascade_read", "osmt_cascade_register",
 ]
 
 
@@ -205,6 +206,15 @@ def load():
         L.osmt_register_area_label_bindings_matched.argtypes = [vp, vp, C.POINTER(abi.ClassLabelBindingsDesc), C.POINTER(C.c_uint32)]
         L.osmt_read_label_bindings.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, sz, sz]
         L.osmt_read_area_label_bindings.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, sz, sz]
+    if hasattr(L, "osmt_cascade_classes"):  # absent only from older variant builds loaded through OSMT_LIB
+        sz = C.POINTER(C.c_size_t)
+        L.osmt_validate_rules.argtypes = [C.POINTER(abi.RulesDesc), vp]
+        L.osmt_register_rules.argtypes = [vp, C.POINTER(abi.RulesDesc), C.POINTER(C.c_uint32)]
+        L.osmt_cascade_classes.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+        L.osmt_cascade_free.argtypes = [vp]
+        L.osmt_cascade_free.restype = None
+        L.osmt_cascade_read.argtypes = [vp] * 14 + [sz, sz]
+        L.osmt_cascade_register.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp]
     if hasattr(L, "osmt_label_positions_tiles"):  # absent only from older variant builds loaded through OSMT_LIB
         L.osmt_validate_node_mercator.argtypes = [dp, C.c_size_t, C.c_uint32, vp]
         L.osmt_register_node_mercator.argtypes = [vp, C.c_uint32, dp]

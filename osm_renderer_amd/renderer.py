@@ -438,6 +438,13 @@ class Context:
         check(load().osmt_register_selectors(self._h, C.byref(d), C.byref(out)))
         return out.value
 
+    def register_rules(self, rules):
+        """osmt_register_rules: appends a selmatch.RuleSet; returns its id (Match.cascade takes it)."""
+        d = rules.as_desc()
+        out = C.c_uint32()
+        check(load().osmt_register_rules(self._h, C.byref(d), C.byref(out)))
+        return out.value
+
     def match_selectors(self, geodata_id, selectors_id, overrides=None):
         """osmt_match_selectors: a selmatch.Match; raises selmatch.Declined with the values to supply as overrides."""
         from . import selmatch

@@ -131,6 +131,149 @@ class ClassLabelBindings:
         return d
 
 
+RULE_PROP_DTYPE = np.dtype([("name", "u1"), ("kind", "u1"), ("has_color", "u1"), ("rgb", "u1", (3,)), ("has_image", "u1"), ("_pad", "u1"), ("image", "<u4"),
+                            ("str_off", "<u4"), ("str_len", "<u4"), ("num_off", "<u4"), ("n_nums", "<u4"), ("_pad2", "<u4"), ("delta", "<f8")])
+assert RULE_PROP_DTYPE.itemsize == 40
+_PROP_OF = {n: i for i, n in enumerate(abi.PROP_NAMES)}
+
+
+class RuleSet:
+    """osmt_rules_desc over a registered selector set.  rules: [(selector layers, properties)] in stylesheet order; the
+    selector layers are one entry per selector of the rule (None: no `::layer`; str / bytes: its name), the selectors being
+    those of the SelectorSet in the same order; a property is (name, kind, value[, extra]):
+      (name, PV_IDENTIFIER, id[, {"color": (r, g, b), "image": id}])   the caller's from_color_name / icon lookup, if any
+      (name, PV_STRING, s[, {"image": id}])
+      (name, PV_COLOR, (r, g, b))
+      (name, PV_NUMBERS, [floats])
+      (name, PV_WIDTH_DELTA, float)"""
+
+    def __init__(self, selectors_id, rules, casing_width_multiplier=2.0, font_size_multiplier=None, font_id=0):
+        self.selectors_id, self.font_id = int(selectors_id), int(font_id)
+        self.casing_width_multiplier, self.font_size_multiplier = float(casing_width_multiplier), font_size_multiplier
+        sel_rule, sel_layer, layer_off, layer_bytes = [], [], [0], bytearray()
+        rule_off, props, numbers, pool = [0], [], [], bytearray()
+        for r, (layers, ps) in enumerate(rules):
+            for layer in layers:
+                sel_rule.append(r)
+                if layer is None:
+                    sel_layer.append(abi.LAYER_DEFAULT)
+                else:
+                    sel_layer.append(len(layer_off) - 1)
+                    layer_bytes.extend(_bytes(layer))
+                    layer_off.append(len(layer_bytes))
+            for p in ps:
+                name, kind, value = p[0], p[1], p[2]
+                extra = p[3] if len(p) > 3 else {}
+                rec = np.zeros((), RULE_PROP_DTYPE)
+                rec["name"], rec["kind"] = _PROP_OF.get(name, abi.PROP_OTHER), kind
+                if kind in (abi.PV_IDENTIFIER, abi.PV_STRING):
+                    b = _bytes(value)
+                    rec["str_off"], rec["str_len"] = len(pool), len(b)
+                    pool.extend(b)
+                    if extra.get("image") is not None and name in ("icon-image", "fill-image"):
+                        rec["has_image"], rec["image"] = 1, extra["image"]
+                    if kind == abi.PV_IDENTIFIER and extra.get("color") is not None:
+                        rec["has_color"], rec["rgb"] = 1, extra["color"]
+                elif kind == abi.PV_COLOR:
+                    rec["has_color"], rec["rgb"] = 1, value
+                elif kind == abi.PV_NUMBERS:
+                    rec["num_off"], rec["n_nums"] = len(numbers), len(value)
+                    numbers.extend(float(v) for v in value)
+                else:
+                    rec["delta"] = float(value)
+                props.append(rec)
+            rule_off.append(len(props))
+        u32 = lambda a: np.array(a, dtype=np.uint32).reshape(-1)
+        self.selector_rule, self.selector_layer, self.layer_off, self.rule_prop_off = u32(sel_rule), u32(sel_layer), u32(layer_off), u32(rule_off)
+        self.layer_bytes = np.frombuffer(bytes(layer_bytes), dtype=np.uint8).copy()
+        self.props = np.array(props, dtype=RULE_PROP_DTYPE).reshape(-1)
+        self.numbers = np.array(numbers, dtype=np.float64).reshape(-1)
+        self.strings = np.frombuffer(bytes(pool), dtype=np.uint8).copy()
+
+    def as_desc(self):
+        """ctypes osmt_rules_desc pointing into this object's arrays (keep `self` alive)."""
+        u32, u8 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        d = abi.RulesDesc()
+        d.selectors_id, d.font_id = self.selectors_id, self.font_id
+        d.selector_rule, d.selector_layer, d.n_selectors = self.selector_rule.ctypes.data_as(u32), self.selector_layer.ctypes.data_as(u32), len(self.selector_rule)
+        d.layer_off, d.layer_bytes = self.layer_off.ctypes.data_as(u32), self.layer_bytes.ctypes.data_as(u8)
+        d.n_layers, d.n_layer_bytes = len(self.layer_off) - 1, len(self.layer_bytes)
+        d.rule_prop_off, d.props = self.rule_prop_off.ctypes.data_as(u32), self.props.ctypes.data_as(C.POINTER(abi.RuleProp))
+        d.n_rules, d.n_props = len(self.rule_prop_off) - 1, len(self.props)
+        d.numbers, d.n_numbers = self.numbers.ctypes.data_as(C.POINTER(C.c_double)), len(self.numbers)
+        d.strings, d.n_string_bytes = self.strings.ctypes.data_as(u8), len(self.strings)
+        d.casing_width_multiplier = self.casing_width_multiplier
+        d.has_font_size_multiplier = self.font_size_multiplier is not None
+        d.font_size_multiplier = 0.0 if self.font_size_multiplier is None else float(self.font_size_multiplier)
+        return d
+
+
+class CascadeResult:
+    """The arrays of osmt_cascade_read (or of the host mirror).  Range r covers zooms zoom_lo[r] .. zoom_hi[r]; its class lists
+    are class_style_off[r] / class_styles[range_style_base[r]:range_style_base[r + 1]] and class_off[r] / bindings[...]."""
+    FIELDS = ("styles", "dashes", "label_styles", "key_bytes", "key_off", "zoom_lo", "zoom_hi", "class_style_off", "class_styles", "range_style_base",
+              "class_off", "bindings", "range_binding_base")
+
+    def __init__(self, counts):
+        from .styled import LABEL_STYLE_REC_DTYPE, STYLE_REC_DTYPE
+
+        n_st, n_d, n_ls, n_kb, n_k, n_r, n_cs, n_b, n_c = [int(c) for c in counts]
+        self.n_classes = n_c
+        self.styles, self.dashes, self.label_styles = np.zeros(n_st, STYLE_REC_DTYPE), np.zeros(n_d, np.float64), np.zeros(n_ls, LABEL_STYLE_REC_DTYPE)
+        self.key_bytes, self.key_off = np.zeros(n_kb, np.uint8), np.zeros(n_k + 1, np.uint32)
+        self.zoom_lo, self.zoom_hi = np.zeros(n_r, np.uint8), np.zeros(n_r, np.uint8)
+        self.class_style_off, self.class_styles, self.range_style_base = np.zeros((n_r, n_c + 1), np.uint32), np.zeros(n_cs, np.uint32), np.zeros(n_r + 1, np.uint32)
+        self.class_off, self.bindings, self.range_binding_base = np.zeros((n_r, n_c + 1), np.uint32), np.zeros(n_b, CLASS_LABEL_BINDING_DTYPE), np.zeros(n_r + 1, np.uint32)
+
+    def arrays(self):
+        return [getattr(self, f) for f in self.FIELDS]
+
+    def pointers(self):
+        return [C.c_void_p(a.ctypes.data) for a in self.arrays()]
+
+    def keys(self):
+        return [self.key_bytes[self.key_off[i]:self.key_off[i + 1]].tobytes() for i in range(len(self.key_off) - 1)]
+
+    def range_of(self, zoom):
+        return int(np.nonzero((self.zoom_lo <= zoom) & (zoom <= self.zoom_hi))[0][0])
+
+    def class_styles_of(self, r):
+        """per class the distinct style indices of range r"""
+        pool, off = self.class_styles[self.range_style_base[r]:self.range_style_base[r + 1]], self.class_style_off[r]
+        return [pool[off[c]:off[c + 1]].tolist() for c in range(self.n_classes)]
+
+    def class_bindings_of(self, r):
+        """per class the (distinct label style index, key index or None) pairs of range r"""
+        pool, off = self.bindings[self.range_binding_base[r]:self.range_binding_base[r + 1]], self.class_off[r]
+        return [[(int(s), None if k == abi.TEXT_NONE else int(k)) for s, k in pool[off[c]:off[c + 1]].tolist()] for c in range(self.n_classes)]
+
+
+class Cascade:
+    """An osmt_cascade.  Free with close()."""
+
+    def __init__(self, match, handle):
+        self.match, self._h = match, handle
+
+    def read(self):
+        L, counts = load(), (C.c_size_t * 9)()
+        check(L.osmt_cascade_read(self._h, *([None] * 13), None, counts))
+        out = CascadeResult(counts)
+        caps = (C.c_size_t * 8)(*list(counts)[:8])
+        check(L.osmt_cascade_read(self._h, *out.pointers(), caps, counts))
+        return out
+
+    def register(self, what):
+        """osmt_cascade_register: (bindings_of_zoom, label_bindings_of_zoom, area_label_bindings_of_zoom), each uint32 [19]"""
+        ids = [np.full(abi.MAX_ZOOM + 1, abi.BINDINGS_NONE, np.uint32) for _ in range(3)]
+        check(load().osmt_cascade_register(self.match.ctx._h, self._h, self.match._h, what, *[C.c_void_p(a.ctypes.data) for a in ids]))
+        return tuple(ids)
+
+    def close(self):
+        if self._h:
+            load().osmt_cascade_free(self._h)
+            self._h = None
+
+
 class Declined(OsmtError):
     """osmt_match_selectors declined tag values: `declined` (DECLINED_NUMBER_DTYPE) lists them; compute their f64 and call again."""
 
@@ -193,6 +336,12 @@ class Match:
         """osmt_register_area_label_bindings_matched: the table of ways and multipolygons; returns an id of the kind
         Context.register_area_label_bindings returns."""
         return self._register_labels(load().osmt_register_area_label_bindings_matched, zoom_lo, zoom_hi, class_bindings, keys)
+
+    def cascade(self, rules_id, labels_all=True):
+        """osmt_cascade_classes over the rule set `rules_id` (Context.register_rules): a Cascade."""
+        h = C.c_void_p()
+        check(load().osmt_cascade_classes(self.ctx._h, self._h, rules_id, 1 if labels_all else 0, C.byref(h)))
+        return Cascade(self, h)
 
     def close(self):
         if self._h:
