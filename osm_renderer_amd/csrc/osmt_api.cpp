@@ -280,6 +280,10 @@ struct osmt_scene {
     osmt_srec* d_srec = nullptr;
     uint2* d_skey = nullptr;
     unsigned long long fmask_cap = 0, srec_cap = 0; /* 64-byte groups / records */
+    /* the fill slots of k_prebin (osmt_fill_slots.h), in the same allocation */
+    osmt_fill_slot* d_slots = nullptr;
+    unsigned long long slot_cap = 0;
+    uint32_t n_fill_pass = 0; /* passes of four slots, where the sizing run counted them; 0: not known (worst-case or guessed sizes) */
     /* host-side tables whose upload may still be in flight on the call's stream */
     std::vector<uint32_t> h_pt_job, h_op_aux, h_op_blk, h_op_vseg, h_op_job, h_lab_wide;
     std::vector<osmt_label_band> h_lab_bands;
@@ -1001,6 +1005,9 @@ osmt_prepass_args prepass_args(const osmt_scene* sc, bool sizing) {
     a.skey = sc->d_skey;
     a.fmask_cap = sizing ? 0ull : sc->fmask_cap;
     a.srec_cap = sizing ? 0ull : sc->srec_cap;
+    a.slots = sc->d_slots;
+    a.slot_cap = sizing ? 0ull : sc->slot_cap;
+    a.n_fill_pass = sc->n_fill_pass;
     a.err = sizing ? nullptr : sc->h_err; /* hipHostMallocMapped memory: one address on both sides (unified addressing) */
     return a;
 }
@@ -1268,11 +1275,13 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
             HIP_TRY(osmt_launch_project(s->d_jobs, s->d_pt_job, s->d_latlon, s->coord_kind == OSMT_COORD_NODE_REF ? s->d_node_refs : nullptr,
                                         s->n_pts, (double)s->scale, s->d_pts, st));
         HIP_TRY(osmt_launch_prepass(prepass_args(s, true), st));
-        unsigned long long totals[2] = {0ull, 0ull};
+        unsigned long long totals[4] = {0ull, 0ull, 0ull, 0ull}; /* [3]: fill slots, whole passes */
         HIP_TRY(hipMemcpyAsync(totals, s->d_cursors, sizeof totals, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         groups = totals[0];
         recs = totals[1];
+        /* (at least one block: 0 stands for "not counted") */
+        s->n_fill_pass = (uint32_t)std::max<unsigned long long>(std::min<unsigned long long>(totals[3] / OSMT_FILL_PASS_SLOTS, 0x7FFFFFFFull), 1ull);
         std::lock_guard<std::mutex> lk(ctx->cache_mu);
         osmt_ctx::arena_density& d = ctx->density[s->scale];
         if (n_fills) d.groups_per_fill = std::max(d.groups_per_fill * 0.98, (double)groups / (double)n_fills);
@@ -1305,6 +1314,9 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
     /* batches of many tiles: the arena in slices with a cursor each and an overflow slice behind them (osmt_list_slices.h) */
     const osmt_list_layout lay = osmt_list_layout_make(s->n_jobs, ents + 1);
     const size_t o_e = carve((size_t)lay.total * sizeof(osmt_ent));
+    /* one descriptor per (fill op, sub-tile row of its window) and the rounding of every k_opinfo workgroup */
+    const unsigned long long slot_cap = osmt_fill_slot_capacity(groups, n_fills, (uint32_t)(W / OSMT_SUB_H), s->n_ops);
+    const size_t o_q = carve((size_t)slot_cap * sizeof(osmt_fill_slot));
     hipError_t e = dev_alloc(ctx, (void**)&s->d_arena, off + 256);
     if (e != hipSuccess) {
         s->d_arena = nullptr;
@@ -1315,6 +1327,8 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
     s->d_skey = (uint2*)(s->d_arena + o_k);
     s->d_ent = (osmt_ent*)(s->d_arena + o_e);
     s->ent_cap = ents + 1;
+    s->d_slots = (osmt_fill_slot*)(s->d_arena + o_q);
+    s->slot_cap = slot_cap;
     /* OSMT_TRACE_UPLOAD=1 (diagnostic): what the arenas take, one line on stderr */
     static const bool trace_arenas = getenv("OSMT_TRACE_UPLOAD") != nullptr;
     if (trace_arenas)

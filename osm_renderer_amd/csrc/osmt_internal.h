@@ -8,6 +8,7 @@
 #include "../../include/osmtile.h"
 #include "osmt_glyph.h"
 #include "osmt_list_slices.h"
+#include "osmt_fill_slots.h"
 
 /* Sub-tile geometry of k_raster: OSMT_SUB_W x OSMT_SUB_H pixels per workgroup.  Sub-tile
  * coverage masks (osmt_raster_args.submask) have one 32-bit word per sub-tile ROW. */
@@ -312,7 +313,12 @@ struct osmt_prepass_args {
      * kernel needs of an edge / cap stub in ONE record, one level of loads (round 3 went vseg -> table slot -> op -> opinfo ->
      * osmt_op -> ring -> points; rounds 4-5 kept six arrays: six scattered partial-line stores per edge) */
     osmt_vseg* vseg;
-    unsigned long long* cursors; /* [0] fill arena (64-byte groups), [1] stroke arena (records), [2] list entries; zeroed by the launcher */
+    unsigned long long* cursors; /* [0] fill arena (64-byte groups), [1] stroke arena (records), [2] list entries, [3] fill slots
+                                  * (osmt_fill_slots.h; four times the pass count of k_prebin's fill role); zeroed by the launcher */
+    osmt_fill_slot* slots;       /* [slot_cap] one descriptor per (fill op, sub-tile row of its window), written by k_opinfo */
+    unsigned long long slot_cap; /* a multiple of four; 0 in the sizing pass (only the cursor is produced) */
+    uint32_t n_fill_pass;        /* passes of k_prebin's fill role where the sizing run counted them (the launcher makes its fill blocks
+                                  * from this count), else 0: ceil(n_ops / 2) blocks that stride through the passes the cursor shows */
     uint32_t* cnt;      /* [n_jobs][nsub], right behind the cursors (zeroed with them): ops that draw into the sub-tile; behind the
                          * counts, zeroed with them, the cursors of the list arena's slices (osmt_list_slices.h) */
     uint2* hdr;         /* [n_jobs][nsub]: k_sublist's (first entry, count) */

@@ -181,9 +181,6 @@ __device__ __forceinline__ uint32_t window_count(const SubWindow& w) {
  * 16 row words per sub-tile of its clipped window, a stroke op one record per (virtual segment, candidate sub-tile).
  * Offsets come from two global cursors (atomicAdd: the order of the ops in the arenas does not matter, k_raster
  * finds everything through osmt_opinfo).  With fmask_cap == srec_cap == 0 the kernel only sizes (upload-time pass). */
-#ifndef OSMT_V_OPINFO_THREADS
-#define OSMT_V_OPINFO_THREADS 64
-#endif
 constexpr uint32_t OPINFO_THREADS = OSMT_V_OPINFO_THREADS; /* ops per wave.  Half-empty waves, more of them (measured: config-2 pre-pass 257 us with
                                                            * 64, 274 with 32, 309 with 16) do not help: a wave runs as long as its longest op anyway */
 static_assert(OPINFO_THREADS == 64 || OPINFO_THREADS == 32 || OPINFO_THREADS == 16, "the wave scans read their totals from the last active lane");
@@ -192,10 +189,8 @@ static_assert(OPINFO_THREADS == 64 || OPINFO_THREADS == 32 || OPINFO_THREADS == 
  * for 0.4 ms of its 0.50.  The waves of a workgroup share ONE atomicAdd per cursor (totals and bases handed over through LDS):
  * pre-pass of config 2 0.232 -> 0.209 ms with four waves, 0.205 with eight; 2.80 -> 2.69 ms on 256 config-5 tiles
  * (profiles/r05_o_opinfo_waves_stage_times.txt). */
-#ifndef OSMT_V_OPINFO_WAVES
-#define OSMT_V_OPINFO_WAVES 8
-#endif
-constexpr uint32_t OPINFO_WAVES = OSMT_V_OPINFO_WAVES;
+constexpr uint32_t OPINFO_WAVES = OSMT_V_OPINFO_WAVES; /* (both defaults: osmt_fill_slots.h, which sizes the slot array from them) */
+static_assert(OPINFO_THREADS * OPINFO_WAVES == OSMT_FILL_SLOT_WG_OPS, "one slot reservation per workgroup");
 static_assert(OPINFO_WAVES == 1 || OPINFO_THREADS == 64, "several waves per workgroup: whole waves");
 __global__ __launch_bounds__(OPINFO_THREADS * OPINFO_WAVES) void k_opinfo(const osmt_prepass_args a) {
     const uint32_t op_lane = threadIdx.x % OPINFO_THREADS, op_wave = threadIdx.x / OPINFO_THREADS;
@@ -406,6 +401,11 @@ __global__ __launch_bounds__(OPINFO_THREADS * OPINFO_WAVES) void k_opinfo(const 
         const uint32_t f = (uint32_t)want_f;
         const uint32_t s_lo = (uint32_t)want_s & 0xFFFFu, s_hi = (uint32_t)(want_s >> 16);
         const uint32_t f_incl = wave_incl_scan(f);
+        /* fill slots (osmt_fill_slots.h): one per sub-tile row of the op's window, whether or not its arena reservation is granted */
+        const uint32_t nsr = want_f ? fill_geom_ok >> 24 : 0u;
+        const uint32_t q_incl = wave_incl_scan(nsr);
+        const uint32_t q_tot = (uint32_t)__builtin_amdgcn_readlane((int)q_incl, OPINFO_THREADS - 1);
+        uint32_t q_base = 0u;
         const unsigned long long s_incl = ((unsigned long long)wave_incl_scan(s_hi) << 16) + wave_incl_scan(s_lo);
         const uint32_t f_tot = (uint32_t)__builtin_amdgcn_readlane((int)f_incl, OPINFO_THREADS - 1);
         const unsigned long long s_tot = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(s_incl >> 32), OPINFO_THREADS - 1) << 32) |
@@ -415,13 +415,21 @@ __global__ __launch_bounds__(OPINFO_THREADS * OPINFO_WAVES) void k_opinfo(const 
             if (lane == 0u) {
                 if (f_tot) f_base = atomicAdd(&a.cursors[0], (unsigned long long)f_tot);
                 if (s_tot) s_base = atomicAdd(&a.cursors[1], s_tot);
+                if (q_tot) {
+                    const uint32_t q_res = osmt_fill_slots_round(q_tot);
+                    q_base = (uint32_t)atomicAdd(&a.cursors[3], (unsigned long long)q_res);
+                    for (uint32_t i = q_tot; i < q_res; ++i) /* the rounding: empty slots */
+                        if ((unsigned long long)q_base + i < a.slot_cap) a.slots[q_base + i] = osmt_fill_slot_empty();
+                }
             }
         } else {
             /* the workgroup's waves hand their totals to thread 0, which reserves for all of them and hands the bases back */
             __shared__ unsigned long long s_tot_f[OPINFO_WAVES], s_tot_s[OPINFO_WAVES];
+            __shared__ uint32_t s_tot_q[OPINFO_WAVES];
             if (lane == 0u) {
                 s_tot_f[op_wave] = f_tot;
                 s_tot_s[op_wave] = s_tot;
+                s_tot_q[op_wave] = q_tot;
             }
             __syncthreads();
             if (threadIdx.x == 0u) {
@@ -439,11 +447,27 @@ __global__ __launch_bounds__(OPINFO_THREADS * OPINFO_WAVES) void k_opinfo(const 
                     bf += tf;
                     bs += ts;
                 }
+                /* the workgroup's fill slots: whole passes, the rounding stored as empty slots */
+                uint32_t bq = 0u;
+                for (uint32_t w = 0; w < OPINFO_WAVES; ++w) bq += s_tot_q[w];
+                if (bq) {
+                    const uint32_t q_res = osmt_fill_slots_round(bq);
+                    const uint32_t q0 = (uint32_t)atomicAdd(&a.cursors[3], (unsigned long long)q_res);
+                    for (uint32_t i = bq; i < q_res; ++i)
+                        if ((unsigned long long)q0 + i < a.slot_cap) a.slots[q0 + i] = osmt_fill_slot_empty();
+                    bq = q0;
+                }
+                for (uint32_t w = 0; w < OPINFO_WAVES; ++w) {
+                    const uint32_t tq = s_tot_q[w];
+                    s_tot_q[w] = bq;
+                    bq += tq;
+                }
             }
             __syncthreads();
             if (lane == 0u) {
                 f_base = s_tot_f[op_wave];
                 s_base = s_tot_s[op_wave];
+                q_base = s_tot_q[op_wave];
             }
         }
         f_base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(f_base >> 32)) << 32) |
@@ -465,6 +489,24 @@ __global__ __launch_bounds__(OPINFO_THREADS * OPINFO_WAVES) void k_opinfo(const 
                 oi.fill_geom = fill_geom_ok;
             else if (a.err)
                 *(volatile uint32_t*)a.err = OSMT_PREPASS_ERR_FILL_ARENA;
+        }
+        q_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)q_base);
+        if (nsr && a.slot_cap) {
+            /* the op's descriptors, in row order; an op without its arena words stores empty slots.  (A descriptor past the
+             * array: only when guessed arenas were too small — the fill arena has then overflowed too, see osmt_fill_slots.h) */
+            const uint32_t first = q_base + osmt_fill_slot_first(0u, q_incl, nsr);
+            const uint32_t g = oi.fill_geom;
+            bool past = false;
+            for (uint32_t r = 0; r < nsr; ++r) {
+                if ((unsigned long long)first + r >= a.slot_cap) {
+                    past = true;
+                    break;
+                }
+                a.slots[first + r] = g ? osmt_fill_slot_make(o, oi.arena_off, r, g & 255u, (g >> 8) & 255u, (g >> 16) & 255u, oi.n_rings,
+                                                             oi.n_edges, oi.first_pt)
+                                       : osmt_fill_slot_empty();
+            }
+            if (past && a.err) *(volatile uint32_t*)a.err = OSMT_PREPASS_ERR_FILL_ARENA;
         }
     }
     if (live) a.info[o] = oi;
@@ -1245,11 +1287,13 @@ __device__ __noinline__ uint32_t fill_row_streaming(const osmt_ring* __restrict_
  * The unit of work is a CROSSING — an (edge, row) pair on which the edge leaves an un-poisoned record (fill.rs:66-87)
  * — not an (edge, row) combination: only a third of the combinations of a polygon's bounding rows cross, and a
  * polygon a few rows tall would leave most of a wave idle.
- *   pass     64 rows = four slots of 16; a slot is one sub-tile row of one FILL op.  A wave owns FILL_GROUP consecutive
- *            ops and deals their sub-tile rows to the slots in order: four rows of one tall polygon, or the rows of
- *            several small ones.  (FILL_GROUP, measured: pre-pass of config 2 / @2x / config 5 with 1: 263 / 140 / 1177 us,
- *            2: 252 / 145 / 1032, 3: 261 / 161 / 1028, 4: 261 / 169 / 1021, 8: 285 / 204 / 1015 — tall polygons want
- *            more waves, small ones fuller passes.)
+ *   pass     64 rows = four slots of 16; a slot is one sub-tile row of one FILL op.  k_opinfo writes one descriptor per
+ *            slot, in op order (osmt_fill_slots.h); a wave takes ONE pass = four consecutive descriptors, whichever ops
+ *            they belong to: four rows of one tall polygon, or the rows of several small ones.  (Before, a wave owned
+ *            FILL_GROUP consecutive ops and dealt their rows to passes of its own, the last one partly empty; measured then:
+ *            pre-pass of config 2 / @2x / config 5 with FILL_GROUP 1: 263 / 140 / 1177 us, 2: 252 / 145 / 1032,
+ *            3: 261 / 161 / 1028, 4: 261 / 169 / 1021, 8: 285 / 204 / 1015 — tall polygons want more waves, small ones
+ *            fuller passes.  Passes cut loose from ops give both.)
  *   step 1   lane = edge (64 per round; ops with more: further rounds, 64-edge blocks whose box misses the rows are
  *            skipped): rows of the pass the edge crosses -> a compact edge list with the running crossing count, and a
  *            difference array over the rows (+1 on the first row, -1 behind the last).
@@ -1262,10 +1306,15 @@ __device__ __noinline__ uint32_t fill_row_streaming(const osmt_ring* __restrict_
  *            here" bits of the op's sub-tile mask and the list counts of k_sublist fall out of the same words.
  * A window of rows with more crossing edges / crossings than the buffers hold is halved until it fits; a single row
  * beyond them streams its records storage-free (fill_row_streaming, cold). */
-#ifndef OSMT_V_FILL_GROUP
-#define OSMT_V_FILL_GROUP 2
+/* Passes per fill block.  A pass is the unit of WORK; a block is the unit of LAUNCH, and a single-wave workgroup that runs one
+ * pass pays its dispatch, its LDS set-up and its role arithmetic for ~2 us of work.  Two passes a block apart by the whole grid
+ * (not neighbours: those belong to the same tall polygon) — headline step 0.704 -> 0.692 ms, with 1: 0.702, with 3: 0.693
+ * (profiles/fill_slots_ab.txt). */
+#ifndef OSMT_V_FILL_BLOCK_PASSES
+#define OSMT_V_FILL_BLOCK_PASSES 2
 #endif
-constexpr uint32_t FILL_GROUP = OSMT_V_FILL_GROUP;
+constexpr uint32_t FILL_BLOCK_PASSES = OSMT_V_FILL_BLOCK_PASSES;
+static_assert(FILL_BLOCK_PASSES >= 1u, "a fill block runs at least one pass");
 constexpr uint32_t FILL_EMAX = 128;
 #ifndef OSMT_V_FILL_RMAX
 #define OSMT_V_FILL_RMAX 384
@@ -1287,67 +1336,38 @@ struct FillShared {
     uint32_t rowstart[64];
 };
 
-__device__ __forceinline__ void fill_rows_body(FillShared& sh, const uint32_t group, const uint32_t lane, const osmt_op* __restrict__ g_ops,
-                                               uint32_t n_ops, const osmt_opinfo* __restrict__ g_info, const osmt_ring* __restrict__ g_rings,
+__device__ __forceinline__ uint32_t fill_sel4(const uint32_t (&v)[4], uint32_t k) { return k == 0u ? v[0] : (k == 1u ? v[1] : (k == 2u ? v[2] : v[3])); }
+
+__device__ __forceinline__ void fill_rows_body(FillShared& sh, const uint32_t fblk, const uint32_t n_fblk, const uint32_t n_pass, const uint32_t lane,
+                                               const osmt_op* __restrict__ g_ops, const osmt_fill_slot* __restrict__ g_slots,
+                                               const osmt_ring* __restrict__ g_rings,
                                                const int2* __restrict__ g_pts, const uint32_t* __restrict__ g_op_blk,
                                                const osmt_blk_bbox* __restrict__ g_blk, uint32_t scale, uint32_t sub_rows,
                                                uint32_t* __restrict__ g_submask, uint32_t* __restrict__ g_fmask,
                                                const uint32_t* __restrict__ g_op_job, uint32_t* __restrict__ g_cnt) {
-    const uint32_t o_first = group * FILL_GROUP;
     const uint32_t n_sub_x = OSMT_TILE_SIZE * scale / SUB;
-    /* the group's ops and their sub-tile rows: slot t of the group = (op k, sub-tile row sr0_k + t - base_k) */
-    uint32_t g_geom[FILL_GROUP], g_arena[FILL_GROUP], g_base[FILL_GROUP + 1];
-    uint32_t g_ne[FILL_GROUP], g_pt0[FILL_GROUP]; /* SIMPLE ops (one ring, <= 16 edges): edge count and first point; else g_ne = 0xFFFFFFFF */
-    g_base[0] = 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < FILL_GROUP; ++k) {
-        uint32_t geom = 0u, arena = 0u, ne = 0u, pt0 = 0u;
-        if (o_first + k < n_ops) {
-            const osmt_opinfo* __restrict__ oi = &g_info[o_first + k];
-            const uint32_t kind = oi->kind;
-            if (kind == OSMT_OP_FILL_COLOR || kind == OSMT_OP_FILL_IMAGE) {
-                geom = oi->fill_geom; /* nsr == 0: no covered row inside the tile */
-                arena = oi->arena_off;
-                ne = 0xFFFFFFFFu;
-                if (oi->n_rings == 1u && oi->n_edges <= 16u) { /* everything about a small one-ring polygon is in its opinfo */
-                    ne = oi->n_edges;
-                    pt0 = oi->first_pt;
-                }
-            }
-        }
-        g_geom[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)geom);
-        g_arena[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)arena);
-        g_ne[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)ne);
-        g_pt0[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)pt0);
-        g_base[k + 1] = g_base[k] + (g_geom[k] >> 24);
-    }
-    const uint32_t n_slots = g_base[FILL_GROUP];
-    if (n_slots == 0u) return;
+    if (fblk >= n_pass) return;
     sh.rowfill[lane] = 0u;
     sh.diff[lane] = 0;
     if (lane == 0u) sh.diff[64] = 0;
     __syncthreads();
-    for (uint32_t t0 = 0; t0 < n_slots; t0 += 4u) {
-        /* ---- this lane's row: slot t0 + lane / 16 ---- */
-        const uint32_t t = t0 + (lane >> OSMT_SUB_H_LOG2);
-        const bool row_valid = t < n_slots;
-        uint32_t my_k = 0u;
-#pragma unroll
-        for (uint32_t k = 1; k < FILL_GROUP; ++k)
-            if (t >= g_base[k] && g_base[k] < n_slots) my_k = k;
-        uint32_t geom = g_geom[0], arena = g_arena[0], base = g_base[0];
-#pragma unroll
-        for (uint32_t k = 1; k < FILL_GROUP; ++k)
-            if (my_k == k) {
-                geom = g_geom[k];
-                arena = g_arena[k];
-                base = g_base[k];
-            }
-        const uint32_t my_o = o_first + my_k;
-        const uint32_t sr0 = geom & 255u, c0 = (geom >> 8) & 255u, ncols = row_valid ? (geom >> 16) & 255u : 0u;
-        const uint32_t sr = sr0 + (t - base);
+    /* (one pass per block where the scene was sized exactly; otherwise the blocks stride through the passes) */
+    for (uint32_t pass = fblk; pass < n_pass; pass += n_fblk) {
+        /* ---- this lane's row: slot lane / 16 of the pass, the four descriptors are one 64-byte line ---- */
+        const uint32_t q = lane >> OSMT_SUB_H_LOG2;
+        const uint4 ds = reinterpret_cast<const uint4*>(g_slots)[(size_t)pass * OSMT_FILL_PASS_SLOTS + q]; /* op, word0, geom, first_pt */
+        const uint32_t my_o = ds.x, geom = ds.z;
+        const uint32_t sr = osmt_fill_slot_sr(geom), c0 = osmt_fill_slot_c0(geom), ncols = osmt_fill_slot_ncols(geom);
+        const bool row_valid = ncols != 0u; /* an empty slot: the rounding of a k_opinfo workgroup, or an op without arena words */
         const int32_t y = (int32_t)(sr * SUBH + (lane & (SUBH - 1u)));
         uint32_t row_hit = 0u; /* absolute columns in which this row has coverage */
+        /* the four slots as the whole wave sees them (uniform) */
+        uint32_t s_op[4], s_geom[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            s_op[k] = (uint32_t)__builtin_amdgcn_readlane((int)ds.x, (int)(k * SUBH));
+            s_geom[k] = (uint32_t)__builtin_amdgcn_readlane((int)ds.z, (int)(k * SUBH));
+        }
 
         /* ---- windows of rows [w0, w0 + ww): halved while the buffers overflow ---- */
         uint32_t w0 = 0u, ww = 64u;
@@ -1357,48 +1377,24 @@ __device__ __forceinline__ void fill_rows_body(FillShared& sh, const uint32_t gr
             uint32_t n_list = 0u, n_cross = 0u;
             bool overflow = false;
             /* SIMPLE ops only in this window (the common case: a polygon is one ring of a few edges): ONE round for all of
-             * them, lane = (op lane / 16, edge lane % 16), instead of a round per op with a quarter of the lanes */
+             * them, lane = (slot lane / 16, edge lane % 16), every slot restricted to its own 16 rows */
             bool pooled = true;
 #pragma unroll
-            for (uint32_t k = 0; k < FILL_GROUP; ++k) {
-                const uint32_t s_lo = max(g_base[k], t0), s_hi = min(g_base[k + 1], t0 + 4u);
-                if (s_lo < s_hi && max((s_lo - t0) * SUBH, w0) < min((s_hi - t0) * SUBH, w0 + ww) && g_ne[k] == 0xFFFFFFFFu) pooled = false;
-            }
+            for (uint32_t k = 0; k < 4u; ++k)
+                if (s_geom[k] != 0u && !osmt_fill_slot_simple(s_geom[k]) && max(k * SUBH, w0) < min((k + 1u) * SUBH, w0 + ww)) pooled = false;
             if (pooled) {
-                /* the (at most four) ops with slots in this pass, in order: lane / 16 picks one of them */
-                uint32_t kq[4] = {0xFFu, 0xFFu, 0xFFu, 0xFFu}, nq = 0u;
-#pragma unroll
-                for (uint32_t q = 0; q < FILL_GROUP; ++q)
-                    if (max(g_base[q], t0) < min(g_base[q + 1], t0 + 4u)) {
-                        if (nq == 0u) kq[0] = q;
-                        if (nq == 1u) kq[1] = q;
-                        if (nq == 2u) kq[2] = q;
-                        if (nq == 3u) kq[3] = q;
-                        ++nq;
-                    }
-                const uint32_t qi = lane >> 4, e = lane & 15u;
-                const uint32_t k = qi == 0u ? kq[0] : (qi == 1u ? kq[1] : (qi == 2u ? kq[2] : kq[3]));
-                uint32_t kbase = g_base[0], kend = k == 0u ? g_base[1] : 0u, kgeom = g_geom[0], kne = k == 0u ? g_ne[0] : 0u, kpt0 = g_pt0[0];
-#pragma unroll
-                for (uint32_t q = 1; q < FILL_GROUP; ++q)
-                    if (k == q) {
-                        kbase = g_base[q];
-                        kend = g_base[q + 1];
-                        kgeom = g_geom[q];
-                        kne = g_ne[q];
-                        kpt0 = g_pt0[q];
-                    }
-                const uint32_t s_lo = max(kbase, t0), s_hi = min(kend, t0 + 4u);
+                const uint32_t e = lane & (SUBH - 1u);
+                const uint32_t kne = osmt_fill_slot_simple(geom) ? osmt_fill_slot_edges(geom) : 0u; /* 0 for an empty slot */
                 uint32_t cnt = 0u, l0 = 0u;
                 int32_t first = 0;
                 int2 p1 = make_int2(0, 0), p2 = p1;
-                if (s_lo < s_hi && e < kne) {
-                    const uint32_t la = max((s_lo - t0) * SUBH, w0), lb = min((s_hi - t0) * SUBH, w0 + ww);
+                if (e < kne) {
+                    const uint32_t la = max(q * SUBH, w0), lb = min((q + 1u) * SUBH, w0 + ww);
                     if (la < lb) {
-                        const int32_t ybase = ((int32_t)(kgeom & 255u) + (int32_t)t0 - (int32_t)kbase) * SUBH;
+                        const int32_t ybase = ((int32_t)sr - (int32_t)q) * SUBH; /* row of lane l of this slot: ybase + l */
                         const int32_t ya = ybase + (int32_t)la, yb = ybase + (int32_t)lb - 1;
-                        p1 = g_pts[kpt0 + e];
-                        p2 = g_pts[kpt0 + e + 1u];
+                        p1 = g_pts[ds.w + e];
+                        p2 = g_pts[ds.w + e + 1u];
                         const int32_t ytop = min(p1.y, p2.y), ybot = max(p1.y, p2.y);
                         first = max(ytop + 1, ya);
                         const int32_t last = min(ybot, yb);
@@ -1427,15 +1423,18 @@ __device__ __forceinline__ void fill_rows_body(FillShared& sh, const uint32_t gr
                 }
             } else
 #pragma unroll 1
-            for (uint32_t k = 0; k < FILL_GROUP; ++k) {
-                /* slots of op k inside this pass and window -> lanes [la, lb) */
-                const uint32_t s_lo = max(g_base[k], t0), s_hi = min(g_base[k + 1], t0 + 4u);
-                if (s_lo >= s_hi) continue;
-                const uint32_t la = max((s_lo - t0) * SUBH, w0), lb = min((s_hi - t0) * SUBH, w0 + ww);
+            for (uint32_t k = 0; k < 4u;) {
+                /* a run of consecutive slots [s_lo, s_hi) of one op (its sub-tile rows follow each other) -> lanes [la, lb) */
+                const uint32_t o = fill_sel4(s_op, k), gk = fill_sel4(s_geom, k);
+                const uint32_t s_lo = k;
+                ++k;
+                if (gk == 0u) continue;
+                while (k < 4u && fill_sel4(s_geom, k) != 0u && fill_sel4(s_op, k) == o) ++k;
+                const uint32_t s_hi = k;
+                const uint32_t la = max(s_lo * SUBH, w0), lb = min(s_hi * SUBH, w0 + ww);
                 if (la >= lb) continue;
-                const uint32_t o = o_first + k;
-                /* row of lane l of this op: (sr0_k + t0 + l / 16 - base_k) * 16 + l % 16 = ybase + l */
-                const int32_t ybase = ((int32_t)(g_geom[k] & 255u) + (int32_t)t0 - (int32_t)g_base[k]) * SUBH;
+                /* row of lane l of this run: (sr_first + l / 16 - s_lo) * 16 + l % 16 = ybase + l */
+                const int32_t ybase = ((int32_t)osmt_fill_slot_sr(gk) - (int32_t)s_lo) * SUBH;
                 const int32_t ya = ybase + (int32_t)la, yb = ybase + (int32_t)lb - 1;
                 const osmt_op* __restrict__ op = &g_ops[o];
                 const uint32_t ring_off = op->ring_off, n_rings = op->n_rings;
@@ -1509,7 +1508,7 @@ __device__ __forceinline__ void fill_rows_body(FillShared& sh, const uint32_t gr
                     for (uint32_t c = 0; c < ncols; ++c) {
                         const int32_t x0 = (int32_t)((c0 + c) * SUB);
                         const uint32_t m = fill_row_streaming(g_rings, g_pts, op->ring_off, op->n_rings, y, x0, x0 + SUB - 1);
-                        g_fmask[((size_t)arena + (size_t)(sr - sr0) * ncols + c) * SUBH + (lane & (SUBH - 1u))] = m;
+                        g_fmask[(size_t)ds.y + c * SUBH + (lane & (SUBH - 1u))] = m;
                         if (m) row_hit |= 1u << (c0 + c);
                     }
                 }
@@ -1579,7 +1578,7 @@ __device__ __forceinline__ void fill_rows_body(FillShared& sh, const uint32_t gr
                                 m |= bits << (uint32_t)(from - x0);
                             }
                         }
-                        g_fmask[((size_t)arena + (size_t)(sr - sr0) * ncols + c) * SUBH + (lane & (SUBH - 1u))] = m;
+                        g_fmask[(size_t)ds.y + c * SUBH + (lane & (SUBH - 1u))] = m;
                         if (m) row_hit |= 1u << (c0 + c);
                     }
                 }
@@ -1714,8 +1713,8 @@ __device__ __forceinline__ void stroke_bin_body(StrokeBinShared& sh, const uint3
 }
 
 /* Both binning jobs in ONE launch: n_vblk blocks bin OSMT_BIN_SEGS stroke segments each (latency-bound: a bisection, a
- * chain of dependent loads, scattered 72-byte stores), n_fgrp blocks build the coverage rows of FILL_GROUP ops each
- * (issue-bound).  The dispatcher places blocks in index order, so the two kinds overlap on the machine only when they
+ * chain of dependent loads, scattered 72-byte stores), n_fblk blocks build the coverage rows of passes of
+ * four fill slots (issue-bound; block f takes the passes f, f + n_fblk, ... below the count that k_opinfo left in the slot cursor).  The dispatcher places blocks in index order, so the two kinds overlap on the machine only when they
  * alternate in the grid: osmt_prebin_role spreads the stroke blocks evenly through it (osmt_prebin_roles.h). */
 __global__ __launch_bounds__(64) void k_prebin(const osmt_op* __restrict__ g_ops, uint32_t n_ops, const osmt_opinfo* __restrict__ g_info,
                                                const osmt_ring* __restrict__ g_rings, const int2* __restrict__ g_pts,
@@ -1724,7 +1723,9 @@ __global__ __launch_bounds__(64) void k_prebin(const osmt_op* __restrict__ g_ops
                                                uint32_t scale, uint32_t sub_rows, uint32_t* __restrict__ g_submask,
                                                uint32_t* __restrict__ g_fmask,
                                                osmt_srec* __restrict__ g_srec, uint2* __restrict__ g_skey, const uint32_t* __restrict__ g_op_job,
-                                               uint32_t* __restrict__ g_cnt, const osmt_vseg* __restrict__ g_vseg) {
+                                               uint32_t* __restrict__ g_cnt, const osmt_vseg* __restrict__ g_vseg,
+                                               const osmt_fill_slot* __restrict__ g_slots, const unsigned long long* __restrict__ g_slot_cursor,
+                                               unsigned long long slot_cap) {
     __shared__ union {
         FillShared fill;
         StrokeBinShared bin;
@@ -1741,8 +1742,8 @@ __global__ __launch_bounds__(64) void k_prebin(const osmt_op* __restrict__ g_ops
         stroke_bin_body(shu.bin, idx, threadIdx.x, g_info, n_vsegs, scale, sub_rows, g_submask,
                         g_srec, g_skey, g_op_job, g_cnt, g_vseg);
     else
-        fill_rows_body(shu.fill, idx, threadIdx.x, g_ops, n_ops, g_info, g_rings, g_pts, g_op_blk, g_blk, scale, sub_rows, g_submask, g_fmask,
-                       g_op_job, g_cnt);
+        fill_rows_body(shu.fill, idx, roles.n_fblk, osmt_fill_pass_count(*g_slot_cursor, slot_cap), threadIdx.x, g_ops, g_slots, g_rings, g_pts,
+                       g_op_blk, g_blk, scale, sub_rows, g_submask, g_fmask, g_op_job, g_cnt);
 }
 
 /* ---- k_sublist: the op bits turned round — one ordered list per (tile, sub-tile) ------------------------------------
@@ -2855,11 +2856,14 @@ hipError_t osmt_launch_prepass(const osmt_prepass_args& a, hipStream_t st, bool 
         hipLaunchKernelGGL(k_opinfo, dim3((a.n_ops + OPINFO_THREADS * OPINFO_WAVES - 1u) / (OPINFO_THREADS * OPINFO_WAVES)),
                            dim3(OPINFO_THREADS * OPINFO_WAVES), 0, st, a);
     if (a.fmask_cap == 0 && a.srec_cap == 0) return hipGetLastError(); /* sizing pass */
-    const osmt_prebin_map roles = osmt_prebin_map_make(osmt_prebin_n_vblk(a.n_vsegs, OSMT_BIN_SEGS), (a.n_ops + FILL_GROUP - 1u) / FILL_GROUP);
-    if (a.n_ops)
-        hipLaunchKernelGGL(k_prebin, dim3(roles.n_vblk + roles.n_fgrp), dim3(64), 0, st, a.ops, a.n_ops, a.info, a.rings, a.pts,
+    /* fill blocks: one per FILL_BLOCK_PASSES passes where the pass count is known (a scene sized exactly); else as many as two
+     * ops per block gave before.  Either way block f takes the passes f, f + n_fblk, ... that the cursor shows. */
+    const uint32_t n_vblk = osmt_prebin_n_vblk(a.n_vsegs, OSMT_BIN_SEGS);
+    const osmt_prebin_map roles = osmt_prebin_map_make(n_vblk, a.n_fill_pass ? (a.n_fill_pass + FILL_BLOCK_PASSES - 1u) / FILL_BLOCK_PASSES : (a.n_ops + 1u) / 2u);
+    if (a.n_ops && roles.n_vblk + roles.n_fblk)
+        hipLaunchKernelGGL(k_prebin, dim3(roles.n_vblk + roles.n_fblk), dim3(64), 0, st, a.ops, a.n_ops, a.info, a.rings, a.pts,
                            a.op_blk, a.blk, a.n_vsegs, roles,
-                           a.scale, a.sub_rows, a.submask, a.fmask, a.srec, a.skey, a.op_job, a.cnt, a.vseg);
+                           a.scale, a.sub_rows, a.submask, a.fmask, a.srec, a.skey, a.op_job, a.cnt, a.vseg, a.slots, a.cursors + 3, a.slot_cap);
     /* lists only for tiles with more than OSMT_FOLD_MAX_OPS ops (k_raster's waves put the others' together themselves) */
     if (a.n_jobs && (a.fold_max_ops == 0u || a.max_job_ops > a.fold_max_ops)) {
         const uint32_t Wt = OSMT_TILE_SIZE * a.scale;

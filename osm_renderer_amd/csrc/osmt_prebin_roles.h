@@ -1,11 +1,11 @@
 /*
  * osmt_prebin_roles.h — which block of k_prebin does what.
  *
- * The launch has n_vblk stroke blocks (OSMT_BIN_SEGS virtual segments each, latency-bound) and n_fgrp fill groups
- * (issue-bound).  The dispatcher places workgroups in index order, so stroke blocks that own the lowest indices all start
+ * The launch has n_vblk stroke blocks (OSMT_BIN_SEGS virtual segments each, latency-bound) and n_fblk fill blocks
+ * (passes of four fill slots, issue-bound).  The dispatcher places workgroups in index order, so stroke blocks that own the lowest indices all start
  * first and the two halves run one after the other.  Here the stroke blocks are spread evenly through the grid instead:
- * with T = n_vblk + n_fgrp and S(b) = floor(b * n_vblk / T) stroke blocks among the indices [0, b), block b is stroke
- * block S(b) when S(b + 1) > S(b) and fill group b - S(b) otherwise.  S(0) = 0, S(T) = n_vblk and S grows by at most
+ * with T = n_vblk + n_fblk and S(b) = floor(b * n_vblk / T) stroke blocks among the indices [0, b), block b is stroke
+ * block S(b) when S(b + 1) > S(b) and fill block b - S(b) otherwise.  S(0) = 0, S(T) = n_vblk and S grows by at most
  * one per index, so every block of either role is mapped exactly once, and any run [a, b) of indices holds
  * S(b) - S(a) stroke blocks, less than one away from its share (b - a) * n_vblk / T.
  *
@@ -41,19 +41,19 @@
 #endif
 
 struct osmt_prebin_map {
-    uint32_t n_vblk, n_fgrp; /* n_vblk + n_fgrp <= 2^31 - 1 (a grid's x dimension) */
-    uint64_t magic;          /* floor((2^64 - 1) / (n_vblk + n_fgrp)); unused when there are no blocks */
+    uint32_t n_vblk, n_fblk; /* n_vblk + n_fblk <= 2^31 - 1 (a grid's x dimension) */
+    uint64_t magic;          /* floor((2^64 - 1) / (n_vblk + n_fblk)); unused when there are no blocks */
 };
 
 OSMT_HD uint32_t osmt_prebin_n_vblk(uint32_t n_vsegs, uint32_t bin_segs) {
     return n_vsegs / bin_segs + (n_vsegs % bin_segs ? 1u : 0u);
 }
 
-OSMT_HD osmt_prebin_map osmt_prebin_map_make(uint32_t n_vblk, uint32_t n_fgrp) {
+OSMT_HD osmt_prebin_map osmt_prebin_map_make(uint32_t n_vblk, uint32_t n_fblk) {
     osmt_prebin_map m;
     m.n_vblk = n_vblk;
-    m.n_fgrp = n_fgrp;
-    const uint64_t T = (uint64_t)n_vblk + n_fgrp;
+    m.n_fblk = n_fblk;
+    const uint64_t T = (uint64_t)n_vblk + n_fblk;
     m.magic = T ? ~(uint64_t)0 / T : 0u; /* host only: the kernel gets the struct as an argument */
     return m;
 }
@@ -66,10 +66,10 @@ OSMT_HD uint64_t osmt_mulhi64(uint64_t a, uint64_t b) {
 #endif
 }
 
-/* Role of block b < n_vblk + n_fgrp: returns 1 and the stroke block's index, or 0 and the fill group's index. */
+/* Role of block b < n_vblk + n_fblk: returns 1 and the stroke block's index, or 0 and the fill block's index. */
 OSMT_HD uint32_t osmt_prebin_role(const osmt_prebin_map m, uint32_t b, uint32_t* idx) {
 #if OSMT_V_PREBIN_INTERLEAVE
-    const uint64_t T = (uint64_t)m.n_vblk + m.n_fgrp;
+    const uint64_t T = (uint64_t)m.n_vblk + m.n_fblk;
     const uint64_t x = (uint64_t)b * m.n_vblk; /* < 2^62 */
     uint64_t s = osmt_mulhi64(x, m.magic);     /* floor(x / T) or one less */
     uint64_t r = x - s * T;
