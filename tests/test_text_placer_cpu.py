@@ -5,65 +5,33 @@
     (tests/_text_placer_model.py) lay the reference's station text out with x_offset / baseline equal AS BITS to
     tests/golden/ref_glyph_runs.json — the values whose expansion reproduces the reference's golden label pixels;
   * the row counts of the fixture's texts (checked with the reference's font when the fixture was made);
-  * mirror == model bit for bit on > 20 000 seeded labels and on directed cases (the 32.0 threshold from both sides,
-    trailing and only whitespace, y_offset, widths <= 0, zero-length edges, a text exactly as long as its way and one
-    ulp longer, the advance <= 0 quirk, running off the end, ways of one point and none);
+  * mirror == model bit for bit on > 20 000 seeded labels and on the directed cases of tests/_text_place_cases.py, which
+    the device test (tests/test_gpu_text_edges.py) runs as well: the 32.0 threshold from both sides, trailing and only
+    whitespace, y_offset, widths <= 0, zero-length edges, a text exactly as long as its way and one ulp longer, the
+    advance <= 0 quirk, running off the end, ways of one point and none — and the same edges at lanes 63 / 64 and at
+    the first lane of a later chunk of glyphs or edges; each case brings its literal expectations;
   * every refusal of osmt_validate_text_labels, with its status."""
 import ctypes as C
 import json
-import math
 import os
 
 import numpy as np
 import pytest
 
 from osm_renderer_amd import abi, labels, lib
+from tests import _text_place_cases as pc
 from tests import _text_placer_model as model
 from tests import _text_shim
+from tests._text_place_cases import A, B, S64, SP, text_labels  # noqa: F401  (other test files import them from here)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 TEXTS = json.load(open(os.path.join(GOLD, "ref_text_runs.json")))
 RUNS = json.load(open(os.path.join(GOLD, "ref_glyph_runs.json")))
 PATCHES = json.load(open(os.path.join(GOLD, "ref_label_patches.json")))
 
-S64 = 1.0 / 64.0  # a scale whose products with small integers are exact
-
 
 def _u8(a):
     return np.ascontiguousarray(a).view(np.uint8)
-
-
-def text_labels(specs, n_jobs=1):
-    """One tile of text labels from dicts: glyphs [(id, advance, kern, whitespace)], position, scale, metrics
-    (ascent, descent, line_gap), y_offset, center, pts (already in walking order)."""
-    labs, runs, glyphs, pts = [], [], [], []
-    n_gl = n_pt = 0
-    for s in specs:
-        l, r = np.zeros((), labels.LABEL_DTYPE), np.zeros((), labels.TEXT_RUN_DTYPE)
-        g = np.array([tuple(t) for t in s["glyphs"]], dtype=labels.TEXT_GLYPH_DTYPE) if s["glyphs"] else np.zeros(0, labels.TEXT_GLYPH_DTYPE)
-        l["has_text"], l["text_color"] = 1, s.get("color", (10, 20, 30))
-        if "icon" in s:
-            l["has_icon"], l["image_id"], l["icon_center_x"], l["icon_center_y"] = 1, s["icon"], s["center"][0], s["center"][1]
-        l["seg_off"], l["n_segs"] = (n_gl if len(g) else 0), len(g)
-        r["position"], r["scale"] = s.get("position", abi.TEXT_CENTER), s.get("scale", S64)
-        r["ascent"], r["descent"], r["line_gap"] = s.get("metrics", (800, -200, 0))
-        if r["position"] == abi.TEXT_LINE:
-            p = np.array(s.get("pts", []), dtype=np.int32).reshape(-1, 2)
-            r["pt_off"], r["n_pts"] = (n_pt if len(p) else 0), len(p)
-            pts.append(p)
-            n_pt += len(p)
-        else:
-            r["y_offset"] = s.get("y_offset", 0)
-            r["center_x"], r["center_y"] = s.get("center", (100.0, 100.0))
-        labs.append(l)
-        runs.append(r)
-        glyphs.append(g)
-        n_gl += len(g)
-    way = np.concatenate(pts) if pts else np.zeros((0, 2), np.int32)
-    sincos = np.concatenate([labels.way_sincos(p) for p in pts]) if pts else np.zeros((0, 2))
-    offs = [0] + [len(labs)] * n_jobs
-    return labels.TextLabelList(np.array(labs, dtype=labels.LABEL_DTYPE), offs, np.array(runs, dtype=labels.TEXT_RUN_DTYPE),
-                                np.concatenate(glyphs), way, sincos)
 
 
 def fixture_text(text, size):
@@ -159,110 +127,63 @@ def test_mirror_equals_model_on_twenty_thousand_seeded_labels():
     assert n >= 20_000 and seen == {abi.GLYPH_CENTER, abi.GLYPH_LINE, abi.GLYPH_NONE}
 
 
-A, B, SP = 0, 1, 4  # glyph ids of the synthetic table: two letters and the space
+def run_case(name):
+    """One case of tests/_text_place_cases.py: the mirror equals the model byte for byte, and both hold the case's
+    literal expectations."""
+    case = pc.case(name)
+    got, gl = both(case.build(0))
+    case.check(got, gl)
+    case.check(gl.slots, gl)
 
 
 def test_row_break_at_exactly_the_threshold_from_both_sides():
-    # "A_B" at scale 1/64: A = 16.0, the space 8.0 -> current_row_width + w = 24 + 8 = 32.0, not > 32.0: one row
-    on = text_labels([dict(glyphs=[(A, 1024, 0, 0), (SP, 512, 0, 1), (B, 1024, 0, 0)])])
-    got, _ = both(on)
-    assert len(np.unique(got["p"][:, 1])) == 1
-    # one font unit more on the space: 24.015625 + 8.015625 > 32.0: the space closes its row and stays in it
-    over = text_labels([dict(glyphs=[(A, 1024, 0, 0), (SP, 513, 0, 1), (B, 1024, 0, 0)])])
-    got, _ = both(over)
-    assert got["p"][0, 1] == got["p"][1, 1] < got["p"][2, 1]
-    assert got["p"][0, 0] == 100.0 - (16.0 + 8.015625) / 2.0 and got["p"][2, 0] == 100.0 - 8.0
-    # the same width reached through a kern; and a non-whitespace glyph never breaks
-    kern = text_labels([dict(glyphs=[(A, 1024, 0, 0), (SP, 500, 13, 1), (B, 1024, 0, 0)])])
-    assert np.array_equal(both(kern)[0]["p"], got["p"])
-    wide = text_labels([dict(glyphs=[(A, 4096, 0, 0), (B, 4096, 0, 0)])])
-    assert len(np.unique(both(wide)[0]["p"][:, 1])) == 1
+    run_case("break-threshold")
 
 
 def test_whitespace_edge_cases_and_y_offset():
-    trailing = text_labels([dict(glyphs=[(A, 1024, 0, 0), (SP, 2048, 0, 1), (B, 1024, 0, 0), (SP, 2048, 0, 1)])])
-    got, _ = both(trailing)
-    assert len(np.unique(got["p"][:, 1])) == 2  # the last space closes the second row, no empty third one
-    only = text_labels([dict(glyphs=[(SP, 2048, 0, 1)] * 3)])
-    got, _ = both(only)
-    assert len(np.unique(got["p"][:, 1])) == 3 and (got["form"] == abi.GLYPH_CENTER).all()
-    g = [(A, 1024, 0, 0), (SP, 2048, 0, 1), (B, 1024, 0, 0)]
-    a, _ = both(text_labels([dict(glyphs=g, y_offset=0)]))
-    b, _ = both(text_labels([dict(glyphs=g, y_offset=8)]))
-    row_height = 800 * S64 + 200 * S64
-    assert a["p"][0, 1] == 100.0 - row_height * 2.0 / 2.0 + 800 * S64 and b["p"][0, 1] == 100.0 + 8.0 + 800 * S64
-    assert np.array_equal(a["p"][:, 0], b["p"][:, 0])
-    empty = text_labels([dict(glyphs=[]), dict(glyphs=g)])
-    got, gl = both(empty)
-    assert len(got) == 3 and gl.labels["n_segs"].tolist() == [0, 3]
+    run_case("whitespace-and-y-offset")
+    run_case("empty-label-first")
 
 
 def test_widths_that_are_not_positive():
-    # a kern larger than the advance: the width is negative, the pen moves back
-    tl = text_labels([dict(glyphs=[(A, 1024, 0, 0), (B, 100, -300, 0), (A, 0, 0, 0), (B, 640, 0, 0)])])
-    got, _ = both(tl)
-    total = 16.0 + (100 * S64 + -300 * S64) + 0.0 + 10.0
-    assert got["p"][0, 0] == 100.0 - total / 2.0 and got["p"][2, 0] < got["p"][1, 0] and got["p"][3, 0] == got["p"][2, 0]
-    # the kern of the FIRST glyph is ignored
-    a, _ = both(text_labels([dict(glyphs=[(A, 1024, -999, 0)])]))
-    b, _ = both(text_labels([dict(glyphs=[(A, 1024, 0, 0)])]))
-    assert np.array_equal(_u8(a), _u8(b))
-
-
-def _line(glyphs, pts, **kw):
-    return text_labels([dict(glyphs=glyphs, position=abi.TEXT_LINE, pts=pts, **kw)])
+    run_case("widths-not-positive")
 
 
 def test_line_with_zero_length_edges_and_bends():
-    pts = [(0, 0), (0, 0), (10, 0), (10, 0), (10, 0), (10, 20), (40, 60), (40, 60)]
-    got, _ = both(_line([(A, 640, 0, 0), (B, 640, 5, 0), (SP, 320, 0, 1), (A, 640, -7, 0)], pts))
-    assert (got["form"] == abi.GLYPH_LINE).all()
-    # total way length 10 + 20 + 50 = 80: the glyph centres lie on the way, the first on the vertical edge
-    assert got["p"][0, 4] == 10.0 and 0.0 < got["p"][0, 5] < 20.0
-    assert got["p"][0, 2] == math.sin(-math.atan2(20.0, 0.0)) and got["p"][0, 3] == math.cos(-math.atan2(20.0, 0.0))
-    assert (got["p"][:, 1] == (-200 * S64 + 800 * S64) / 2.0).all()
+    run_case("line-zero-length-edges-and-bends")
 
 
 def test_text_exactly_as_long_as_the_way_and_one_ulp_longer():
-    way = [(3, 7), (19, 7)]  # 16.0 long
-    got, gl = both(_line([(A, 1024, 0, 0)], way, scale=S64))
-    assert got["form"].tolist() == [abi.GLYPH_LINE] and got["p"][0].tolist() == [8.0, 600 * S64 / 2.0, -0.0, 1.0, 11.0, 7.0]
-    longer = math.nextafter(S64, 1.0)
-    assert 1024.0 * longer == math.nextafter(16.0, math.inf)
-    got, gl = both(_line([(A, 1024, 0, 0)], way, scale=longer))
-    assert got["form"].tolist() == [abi.GLYPH_NONE] and gl.labels["n_segs"].tolist() == [0] and gl.labels["has_text"].tolist() == [1]
-    assert len(gl.glyphs) == 0 and got["glyph_id"].tolist() == [A] and got["scale"][0] == longer and not got["p"].any()
+    run_case("line-exactly-as-long-as-the-way")
+    run_case("line-one-ulp-longer-than-the-way")
 
 
 def test_advance_not_positive_returns_the_last_point():
-    # cur_dist = 0 and a first glyph of negative width: compute_way_position(-8) never enters its loop
-    way = [(0, 0), (8, 0), (8, 24)]  # 32.0 long; the last edge points down
-    got, _ = both(_line([(A, -1024, 0, 0), (B, 3072, 0, 0)], way))
-    down = math.atan2(24.0, 0.0)
-    assert got["p"][0].tolist() == [-8.0, 600 * S64 / 2.0, math.sin(-down), math.cos(-down), 8.0, 24.0]
-    # the second glyph: cur_dist = -16, centre 24 -> advance 8.0 = the whole first edge (seg_dist >= to_travel)
-    assert got["p"][1, 4:].tolist() == [8.0, 0.0] and got["p"][1, 2:4].tolist() == [math.sin(-0.0), math.cos(-0.0)]
-    # exactly zero counts as "not positive" as well
-    got, _ = both(_line([(A, 0, 0, 0), (B, 640, 0, 0)], [(0, 0), (5, 0), (5, 5)]))
-    assert got["p"][0, 4:].tolist() == [5.0, 5.0] and got["p"][1, 4:].tolist() == [5.0, 0.0]
+    run_case("line-advance-not-positive")
 
 
 def test_running_off_the_end_returns_the_last_point():
-    # widths +40, -30: total 10 = the way's length, but the first glyph's centre (20) lies beyond the end
-    way = [(0, 0), (6, 0), (6, 4)]
-    got, _ = both(_line([(A, 2560, 0, 0), (B, -1920, 0, 0)], way))
-    up = math.atan2(4.0, 0.0)
-    assert got["p"][0, 2:].tolist() == [math.sin(-up), math.cos(-up), 6.0, 4.0]
-    assert got["form"].tolist() == [abi.GLYPH_LINE] * 2
+    run_case("line-running-off-the-end")
 
 
 def test_ways_of_one_point_and_of_none_place_nothing():
-    g = [(A, 64, 0, 0), (B, 64, 0, 0)]
-    tl = text_labels([dict(glyphs=g, position=abi.TEXT_LINE, pts=[]), dict(glyphs=g, position=abi.TEXT_LINE, pts=[(5, 5)]),
-                      dict(glyphs=g, position=abi.TEXT_LINE, pts=[(5, 5), (5, 5)]), dict(glyphs=g, position=abi.TEXT_LINE, pts=[(0, 0), (9, 0)])])
+    run_case("line-ways-of-one-point-and-of-none")
+
+
+NEW = [c.name for c in pc.cases() if c.name not in pc.OLD]
+
+
+@pytest.mark.parametrize("name", NEW)
+def test_cases_at_wave_and_chunk_edges(name):
+    run_case(name)
+
+
+def test_every_case_in_one_batch():
+    """All cases as one tile (what the device test uploads in one call): the slots of every case hold what they held alone."""
+    tl, spans = pc.merge([c.build(0) for c in pc.cases()])
     got, gl = both(tl)
-    assert got["form"].tolist() == [abi.GLYPH_NONE] * 6 + [abi.GLYPH_LINE] * 2  # two equal points: length 0 < width
-    assert gl.labels["n_segs"].tolist() == [0, 0, 0, 2] and gl.labels["seg_off"].tolist() == [0, 0, 0, 0]
+    for c, (a, n) in zip(pc.cases(), spans):
+        c.check(got[a : a + n])
 
 
 def test_a_long_text_and_a_long_way():
@@ -271,7 +192,7 @@ def test_a_long_text_and_a_long_way():
     got, _ = both(text_labels([dict(glyphs=g, scale=0.011)]))
     assert len(np.unique(got["p"][:, 1])) > 5
     pts = np.cumsum(rng.integers(-3, 8, size=(5000, 2)), axis=0).astype(np.int32)
-    got, _ = both(_line(g, labels.walking_order(pts).tolist(), scale=0.011))
+    got, _ = both(text_labels([dict(glyphs=g, position=abi.TEXT_LINE, pts=labels.walking_order(pts).tolist(), scale=0.011)]))
     assert (got["form"] == abi.GLYPH_LINE).all() and len(np.unique(got["p"][:, 2])) > 50
 
 

@@ -23,59 +23,16 @@ import pytest
 
 from osm_renderer_amd import abi, labels
 from tests import _shape_shim
+from tests import _text_shape_cases as sc
 from tests import _text_shaper_model as model
+from tests._text_shape_cases import FONT, RUNS, TEXTS, ref_font, string_labels, synth_font  # noqa: F401  (other test files import them from here)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-TEXTS = json.load(open(os.path.join(GOLD, "ref_text_runs.json")))
-RUNS = json.load(open(os.path.join(GOLD, "ref_glyph_runs.json")))
 PATCHES = json.load(open(os.path.join(GOLD, "ref_label_patches.json")))
-FONT = json.load(open(os.path.join(GOLD, "ref_font_tables.json")))
 
 
 def _u8(a):
     return np.ascontiguousarray(a).view(np.uint8)
-
-
-def ref_font(first_id=0, empty_id=None):
-    """The reference's font as a FontTable: glyph g's outline is first_id + its position in ref_glyph_runs.json's
-    glyphs; the glyphs the fixture has no outline for share the empty outline empty_id (default: right behind)."""
-    empty_id = first_id + len(RUNS["glyphs"]) if empty_id is None else empty_id
-    outline = [empty_id if o is None else first_id + o for o in FONT["outline"]]
-    a, d, g = FONT["v_metrics"]
-    return labels.FontTable(FONT["cmap"], FONT["advance"], outline, FONT["kern"], a, d, g)
-
-
-def string_labels(specs, n_jobs=1):
-    """One tile of string labels from dicts: chars (a str or code points), font (id), font_size, position, y_offset,
-    center, pts (already in walking order), has_text (default 1)."""
-    labs, runs, chars, pts = [], [], [], []
-    n_ch = n_pt = 0
-    for s in specs:
-        l, r = np.zeros((), labels.LABEL_DTYPE), np.zeros((), labels.STRING_RUN_DTYPE)
-        c = s.get("chars", [])
-        c = np.array([ord(ch) for ch in c] if isinstance(c, str) else list(c), dtype=np.uint32)
-        l["has_text"], l["text_color"] = s.get("has_text", 1), s.get("color", (10, 20, 30))
-        if "icon" in s:
-            l["has_icon"], l["image_id"], l["icon_center_x"], l["icon_center_y"] = 1, s["icon"], s["center"][0], s["center"][1]
-        l["seg_off"], l["n_segs"] = (n_ch if len(c) else 0), len(c)
-        r["position"], r["font_id"], r["font_size"] = s.get("position", abi.TEXT_CENTER), s.get("font", 0), s.get("font_size", 11.0)
-        if r["position"] == abi.TEXT_LINE:
-            p = np.array(s.get("pts", []), dtype=np.int32).reshape(-1, 2)
-            r["pt_off"], r["n_pts"] = (n_pt if len(p) else 0), len(p)
-            pts.append(p)
-            n_pt += len(p)
-        else:
-            r["y_offset"] = s.get("y_offset", 0)
-            r["center_x"], r["center_y"] = s.get("center", (100.0, 100.0))
-        labs.append(l)
-        runs.append(r)
-        chars.append(c)
-        n_ch += len(c)
-    way = np.concatenate(pts) if pts else np.zeros((0, 2), np.int32)
-    sincos = np.concatenate([labels.way_sincos(p) for p in pts]) if pts else np.zeros((0, 2))
-    offs = [0] + [len(labs)] * n_jobs
-    return labels.StringLabelList(np.array(labs, dtype=labels.LABEL_DTYPE), offs, np.array(runs, dtype=labels.STRING_RUN_DTYPE),
-                                  np.concatenate(chars) if chars else np.zeros(0, np.uint32), way, sincos)
 
 
 def station_string_labels(key, font_id=0, image_id=0):
@@ -142,81 +99,58 @@ def test_reference_texts_shape_to_the_fixture_records():
         assert np.array_equal(_u8(_shape_shim.shape_labels(sl, [font])), _u8(want))
 
 
-def synth_font(n_cmap, kern=(), first_cp=0x30, step=3, n_glyphs=None):
-    """n_cmap code points first_cp, first_cp + step, ... (gaps between them) -> glyphs 1, 2, ... cycling through n_glyphs
-    - 1 glyphs; glyph g has advance 100 + 7 g and outline 1000 + g."""
-    n_glyphs = n_glyphs or min(n_cmap + 1, 40)
-    cmap = [(first_cp + step * i, 1 + i % (n_glyphs - 1)) for i in range(n_cmap)]
-    return labels.FontTable(cmap, [100 + 7 * g for g in range(n_glyphs)], [1000 + g for g in range(n_glyphs)], kern)
+def run_case(name):
+    """One case of tests/_text_shape_cases.py: the batch is valid, the mirror equals the model byte for byte — on the whole
+    batch and text by text —, FontTable.shape gives the same records, and they hold the case's literal expectations.
+    Returns (records, StringLabelList, fonts)."""
+    case = sc.case(name)
+    sl, fonts = case.build()
+    assert _shape_shim.validate(sl, fonts) == (abi.OK, "")
+    got = _shape_shim.shape_labels(sl, fonts)
+    want = model.shape_labels(sl, [model.Font(f) for f in fonts])
+    assert got.shape == want.shape and np.array_equal(_u8(got), _u8(want))
+    for l, r in zip(sl.labels, sl.runs):
+        if l["has_text"] and l["n_segs"]:
+            a, n = int(l["seg_off"]), int(l["n_segs"])
+            assert np.array_equal(_u8(both(fonts[int(r["font_id"])], sl.chars[a : a + n])), _u8(got[a : a + n]))
+    assert np.array_equal(_u8(sl.to_text_label_list(fonts).glyphs), _u8(got))
+    case.check(got)
+    case.check(want)
+    return got, sl, fonts
 
 
-@pytest.mark.parametrize("n_cmap", [1, 2, 7, 8, 9, 1024, 1025])
+@pytest.mark.parametrize("n_cmap", sc.CMAP_SIZES)
 def test_cmap_bisection_at_every_size_and_position(n_cmap):
-    font = synth_font(n_cmap)
-    first, last = 0x30, 0x30 + 3 * (n_cmap - 1)
-    probes = [0, first - 1, first, first + 1, last - 1, last, last + 1, last + 2, 0x10FFFF, 0xD7FF, 0xE000]
-    probes += [first + 3 * i + d for i in range(0, n_cmap, max(1, n_cmap // 50)) for d in (0, 1, 2)]  # entries and the gaps behind them
-    got = both(font, probes)
-    listed = dict(font.cmap.tolist())
-    assert got["glyph_id"].tolist() == [1000 + listed.get(p, 0) for p in probes]
-    assert got["advance"].tolist() == [100 + 7 * listed.get(p, 0) for p in probes]
-    assert got["glyph_id"][2] != 1000 and got["glyph_id"][5] != 1000 and got["glyph_id"][0] == got["glyph_id"][1] == got["glyph_id"][6] == 1000
-    # every entry of the table, in one text
-    all_cps = font.cmap["code_point"].tolist()
-    assert both(font, all_cps)["glyph_id"].tolist() == [1000 + g for g in font.cmap["glyph"].tolist()]
+    assert sc.CMAP_SIZES == (1, 2, 7, 8, 9, 1024, 1025)
+    run_case(f"cmap-{n_cmap}")
 
 
 def test_kern_tables_empty_one_pair_first_last_signs_and_order():
-    cp = lambda g: 0x30 + 3 * (g - 1)  # the code point of glyph g in synth_font (g >= 1)
-    text = [cp(3), cp(5), cp(3), cp(5), cp(9)]  # pairs (3, 5), (5, 3), (3, 5), (5, 9)
-    assert both(synth_font(20), text)["kern"].tolist() == [0, 0, 0, 0, 0]  # no kern table
-    assert both(synth_font(20, [(3, 5, -40)]), text)["kern"].tolist() == [0, -40, 0, -40, 0]  # one pair
-    assert both(synth_font(20, [(5, 3, 25)]), text)["kern"].tolist() == [0, 0, 25, 0, 0]  # only the other order is listed
-    many = [(l, r, 10 * l - r) for l in range(1, 20) for r in range(1, 20) if (l, r) not in ((3, 5), (5, 3), (5, 9))]
-    assert both(synth_font(20, many), text)["kern"].tolist() == [0, 0, 0, 0, 0]  # everything but the wanted pairs
-    firstp = [(3, 5, 33)] + [(l, r, 1) for l in range(4, 20) for r in range(1, 20)]
-    assert both(synth_font(20, firstp), text)["kern"].tolist() == [0, 33, 1, 33, 1]  # the wanted pair is the first entry
-    lastp = [(l, r, -1) for l in range(1, 3) for r in range(1, 20)] + [(3, 5, -65535)]
-    assert both(synth_font(20, lastp), text)["kern"].tolist() == [0, -65535, 0, -65535, 0]  # ... the last entry
-    # the first glyph has no kern even when (glyph 0, g) and (g, g) are listed; a missing code point is glyph 0 and pairs as such
-    zero = [(0, 0, 7), (0, 3, 11), (3, 0, -13), (3, 3, 17)]
-    got = both(synth_font(20, zero), [cp(3), cp(3), 0x10FFFF, 0x10FFFF, cp(3)])
-    assert got["kern"].tolist() == [0, 17, -13, 7, 11] and got["glyph_id"].tolist() == [1003, 1003, 1000, 1000, 1003]
-    # left and right glyph indices beyond 16 bits keep their order in the key
-    big = labels.FontTable([(0x41, 70000), (0x42, 2), (0x43, 65536)], [5] * 70001, [9] * 70001, [(2, 70000, 4), (65536, 65536, 9), (70000, 2, -4)])
-    assert _shape_shim.validate_font(big, 10) == (abi.OK, "")
-    assert both(big, [0x41, 0x42, 0x41, 0x43, 0x43])["kern"].tolist() == [0, -4, 4, 0, 9]
+    run_case("kern-tables")
+    assert _shape_shim.validate_font(sc.big_font(9), 10) == (abi.OK, "")
 
 
 def test_whitespace_is_rusts_not_isspace():
     ws = sorted(labels.WHITE_SPACE)
     assert len(ws) == 25 and ws == [cp for cp in range(0x3002) if model.is_whitespace(cp)]
-    probes = sorted(set(ws) | {cp + d for cp in ws for d in (-1, 1)} | {0x1C, 0x1D, 0x1E, 0x1F, 0x180E, 0x200B, 0xFEFF, 0x2060, 0x10FFFF})
-    font = synth_font(9)
-    got = both(font, probes)
-    assert got["flags"].tolist() == [1 if p in labels.WHITE_SPACE else 0 for p in probes]
-    assert [p for p, f in zip(probes, got["flags"]) if f] == ws
+    got, sl, fonts = run_case("whitespace")
+    assert sl.chars.tolist() == sorted(set(ws) | {cp + d for cp in ws for d in (-1, 1)} | {0x1C, 0x1D, 0x1E, 0x1F, 0x180E, 0x200B, 0xFEFF, 0x2060, 0x10FFFF})
     # Python's idea differs exactly where the issue says it does
     assert all(chr(c).isspace() for c in (0x1C, 0x1D, 0x1E, 0x1F)) and not any(c in labels.WHITE_SPACE for c in (0x1C, 0x1F, 0x180E, 0x200B, 0xFEFF))
-    assert np.array_equal(_u8(font.shape(probes)), _u8(got))
+    assert np.array_equal(_u8(fonts[0].shape(sl.chars)), _u8(got))
 
 
 def test_a_kern_never_crosses_from_one_label_into_the_next():
-    cp = lambda g: 0x30 + 3 * (g - 1)
-    fonts = [synth_font(20, [(3, 5, -40), (5, 3, 9)]), synth_font(20, [(3, 5, 77)], first_cp=0x30 - 3)]  # font 1: the same code point is another glyph
-    fonts[1].font_id = 1
-    sl = string_labels([dict(chars=[cp(3), cp(5), cp(3)]), dict(chars=[cp(5), cp(3)]), dict(has_text=0), dict(chars=[]),
-                        dict(chars=[cp(5), cp(2), cp(4)], font=1), dict(chars=[cp(5)])])
-    assert _shape_shim.validate(sl, fonts) == (abi.OK, "")
-    got = _shape_shim.shape_labels(sl, fonts)
-    want = model.shape_labels(sl, [model.Font(f) for f in fonts])
-    assert np.array_equal(_u8(got), _u8(want))
-    # the first char of label 1 sits behind a 3 | 5 boundary (-40 if the pool's neighbour leaked in); in font 1 the chars of
-    # label 4 are glyphs 6, 3, 5
-    assert got["kern"].tolist() == [0, -40, 9, 0, 9, 0, 0, 77, 0]
-    assert got["glyph_id"][5] == 1006 and got["glyph_id"][3] == 1005  # cp(5) is glyph 6 in font 1
-    tl = sl.to_text_label_list(fonts)
-    assert np.array_equal(_u8(tl.glyphs), _u8(got))
+    run_case("kern-label-boundary")
+
+
+NEW = ["kern-at-block-borders", "kern-at-block-borders-reversed-pool", "reference-texts"]
+
+
+@pytest.mark.parametrize("name", NEW)
+def test_cases_at_block_borders_and_the_reference_texts_in_one_batch(name):
+    assert {c.name for c in sc.cases()} == {f"cmap-{n}" for n in sc.CMAP_SIZES} | {"kern-tables", "whitespace", "kern-label-boundary"} | set(NEW)
+    run_case(name)
 
 
 def test_make_string_labels_is_make_text_labels():
