@@ -1214,13 +1214,21 @@ int osmt_read_area_label_bindings(osmt_ctx* ctx, uint32_t id, uint32_t* way_off,
  * class's selectors that admit the zoom (area_matches' zoom half, 501-515), then property_map_to_style of every layer but
  * "*", in insertion order.  The styles of all (class, zoom, layer) are made distinct — as area records (osmt_style_rec with
  * their dashes) and as label records (osmt_label_style_rec) — and numbered by their lowest user, user number
- * ((class * 19) + zoom) * 8 + position; zooms at which every class has the same lists as at the zoom below are joined into
- * ranges.  Nothing is approximate: casing_width = base + multiplier * w is a multiplication and an addition, never fused.
+ * ((class * 19) + zoom) * 8 + position (positions 0 .. 7; for a rule set registered with OSMT_RULES_CLASS_LAYERS positions
+ * 0 .. 15, user number ((class * 19) + zoom) * 16 + position): styles are numbered by their lowest user in (class, zoom,
+ * position) order either way, so ids remain a pure function of the input.  Zooms at which every class has the same lists
+ * as at the zoom below are joined into ranges.  Nothing is approximate: casing_width = base + multiplier * w is a multiplication and an addition, never fused.
  * What the device cannot know the caller resolves per property: from_color_name of an identifier, and the registered image
  * of an icon-image / fill-image string (not in the icon cache: no icon, no image fill; drawer.rs:179-183,
  * labeler.rs:53-66).  The host twin is osmt::cascade_host (host/osmt_cascade.hpp); DESIGN.md 3.15. */
 
 #define OSMT_CASCADE_MAX_LAYERS 8u       /* distinct layer names of one rule set, "*" and "default" included */
+/* With OSMT_RULES_CLASS_LAYERS the names of the set and the layers of one class are bounded apart: layer numbers are local
+ * to a class (numbered by first appearance among the class's selectors), so a sheet may name many layers as long as no
+ * entity class collects more than OSMT_CASCADE_MAX_CLASS_LAYERS of them. */
+#define OSMT_RULES_CLASS_LAYERS 1u        /* flags of osmt_validate_rules_ex / osmt_register_rules_ex */
+#define OSMT_CASCADE_MAX_LAYER_NAMES 255u /* flagged set: distinct layer names, "*" and "default" included (a selector's layer is a byte) */
+#define OSMT_CASCADE_MAX_CLASS_LAYERS 16u /* flagged set: distinct layers over the selectors of ONE class, all zooms, "*" and "default" counted */
 #define OSMT_LAYER_DEFAULT 0xFFFFFFFFu   /* osmt_rules_desc.selector_layer: the selector names no layer */
 
 enum { /* the 20 property names property_map_to_style reads; every other name is OSMT_PROP_OTHER and is dropped */
@@ -1300,14 +1308,23 @@ int osmt_validate_rules(const osmt_rules_desc* rules, osmt_ctx* ctx);
  * distinct `text` strings (IDENTIFIER or STRING alike) pooled as keys, numbered by first appearance in file order.  No kernel
  * touches a string. */
 int osmt_register_rules(osmt_ctx* ctx, const osmt_rules_desc* rules, uint32_t* out_rules_id);
+/* The same two calls with flags; flags = 0 IS osmt_validate_rules / osmt_register_rules (same checks, same messages).  A bit
+ * other than OSMT_RULES_CLASS_LAYERS is OSMT_INVALID_ARG naming the value.  With OSMT_RULES_CLASS_LAYERS the bound on the
+ * names is OSMT_CASCADE_MAX_LAYER_NAMES (more: OSMT_UNSUPPORTED with the figure), and what bounds the cascade is the number
+ * of layers of one class, which only a match knows: osmt_cascade_classes checks it.  Over the same match a set of at most
+ * OSMT_CASCADE_MAX_LAYERS names gives the same bytes registered either way. */
+int osmt_validate_rules_ex(const osmt_rules_desc* rules, uint32_t flags, osmt_ctx* ctx);
+int osmt_register_rules_ex(osmt_ctx* ctx, const osmt_rules_desc* rules, uint32_t flags, uint32_t* out_rules_id);
 /* Runs the cascade on the device.  labels_all = 1: every style is also a label binding, as the reference pushes them;
  * 0: only styles with an icon or a text style (the others draw nothing, labeler.rs:28-36).  OSMT_INVALID_ARG: a match of
  * another context, a declined match, a match whose selector set is not the rules' set, an unknown rules id, labels_all that
  * is not 0 or 1; whatever osmt_validate_styles / osmt_validate_label_styles refuse of a produced distinct record (checked
  * on the host after the read-back, naming the record and the lowest (class, zoom, position) that produced it).
  * OSMT_UNSUPPORTED with the figure: more than 2^31 styles over all (class, zoom) pairs (the table of distinct records has twice
- * as many slots), more than 2^32 - 2 dashes, class styles or class label bindings over the zoom ranges.  *out is NULL on every
- * error. */
+ * as many slots), more than 2^32 - 2 dashes, class styles or class label bindings over the zoom ranges; for a rule set registered
+ * with OSMT_RULES_CLASS_LAYERS, a class whose selectors, taken over all zooms, name more than OSMT_CASCADE_MAX_CLASS_LAYERS
+ * distinct layers ("*" and "default" counted) — the message names the lowest such class and its exact layer count, nothing
+ * is registered and the context stays usable.  *out is NULL on every error. */
 int osmt_cascade_classes(osmt_ctx* ctx, osmt_match* match, uint32_t rules_id, uint32_t labels_all, osmt_cascade** out);
 void osmt_cascade_free(osmt_cascade* cascade);
 /* counts = { distinct styles, dashes, distinct label styles, key bytes, keys, zoom ranges, class styles of all ranges, class

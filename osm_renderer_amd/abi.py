@@ -608,6 +608,9 @@ assert C.sizeof(MatchClass) == 24
 
 # ---- the cascade: styles per class and zoom from registered rules ----
 CASCADE_MAX_LAYERS = 8
+RULES_CLASS_LAYERS = 1  # flags of osmt_validate_rules_ex / osmt_register_rules_ex: layer numbers local to a class
+CASCADE_MAX_LAYER_NAMES = 255
+CASCADE_MAX_CLASS_LAYERS = 16
 LAYER_DEFAULT = 0xFFFFFFFF  # osmt_rules_desc.selector_layer: the selector names no layer
 PROP_NAMES = ("z-index", "fill-position", "width", "casing-width", "text", "font-size", "text-color", "text-position", "color", "fill-color",
               "background-color", "opacity", "fill-opacity", "dashes", "linecap", "casing-color", "casing-dashes", "casing-linecap", "icon-image",

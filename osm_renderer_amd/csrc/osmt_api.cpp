@@ -7515,7 +7515,8 @@ struct osmt_cascade {
 
 namespace {
 
-int validate_rules(const osmt_rules_desc* d, osmt_ctx* ctx, osmt_cs_tables* out_tables) {
+int validate_rules(const osmt_rules_desc* d, uint32_t flags, osmt_ctx* ctx, osmt_cs_tables* out_tables) {
+    if (flags & ~OSMT_RULES_CLASS_LAYERS) return fail(OSMT_INVALID_ARG, "rules: flags = 0x%x (0 or OSMT_RULES_CLASS_LAYERS)", flags);
     if (!d) return fail(OSMT_INVALID_ARG, "rules are NULL");
     if ((d->n_selectors && (!d->selector_rule || !d->selector_layer)) || (d->n_layer_bytes && !d->layer_bytes) || (d->n_props && !d->props) ||
         (d->n_numbers && !d->numbers) || (d->n_string_bytes && !d->strings))
@@ -7575,17 +7576,19 @@ int validate_rules(const osmt_rules_desc* d, osmt_ctx* ctx, osmt_cs_tables* out_
     osmt_cs_tables& T = out_tables ? *out_tables : local;
     size_t n_names = 0;
     osmt_cs_resolve(*d, T, &n_names);
-    if (n_names > OSMT_CASCADE_MAX_LAYERS)
+    if ((flags & OSMT_RULES_CLASS_LAYERS) && n_names > OSMT_CASCADE_MAX_LAYER_NAMES)
+        return fail(OSMT_UNSUPPORTED, "rules: %zu distinct layer names (> OSMT_CASCADE_MAX_LAYER_NAMES = %u)", n_names, OSMT_CASCADE_MAX_LAYER_NAMES);
+    if (!(flags & OSMT_RULES_CLASS_LAYERS) && n_names > OSMT_CASCADE_MAX_LAYERS)
         return fail(OSMT_UNSUPPORTED, "rules: %zu distinct layer names (> OSMT_CASCADE_MAX_LAYERS = %u)", n_names, OSMT_CASCADE_MAX_LAYERS);
     if (T.key_off.size() - 1 > OSMT_LABEL_TEXT_KEYS_MAX)
         return fail(OSMT_UNSUPPORTED, "rules: %zu distinct text strings (> OSMT_LABEL_TEXT_KEYS_MAX = %u)", T.key_off.size() - 1, OSMT_LABEL_TEXT_KEYS_MAX);
     return OSMT_OK;
 }
 
-int register_rules_body(osmt_ctx* ctx, const osmt_rules_desc* d, uint32_t* out_id) {
+int register_rules_body(osmt_ctx* ctx, const osmt_rules_desc* d, uint32_t flags, uint32_t* out_id) {
     if (!ctx || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
     osmt_cs_tables T;
-    const int rc = validate_rules(d, ctx, &T);
+    const int rc = validate_rules(d, flags, ctx, &T);
     if (rc != OSMT_OK) return rc;
     std::shared_ptr<const std::vector<uint8_t>> zooms;
     {
@@ -7627,7 +7630,7 @@ int register_rules_body(osmt_ctx* ctx, const osmt_rules_desc* d, uint32_t* out_i
     h.dev.sel_zoom = (const uint8_t*)(pool + o_z);
     h.dev.numbers = (const double*)(pool + o_n);
     h.dev.n_sels = (uint32_t)d->n_selectors, h.dev.n_layers = T.n_layers, h.dev.star = T.star, h.dev.base = T.base;
-    h.dev.font_id = d->font_id;
+    h.dev.font_id = d->font_id, h.dev.flags = flags;
     h.dev.casing_width_multiplier = d->casing_width_multiplier;
     h.dev.font_size_multiplier = d->has_font_size_multiplier ? d->font_size_multiplier : 1.0;
     h.key_off = std::make_shared<std::vector<uint32_t>>(std::move(T.key_off));
@@ -7688,7 +7691,7 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
         return (int)OSMT_OK;
     };
     static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
-    enum { EV_0, EV_FOLD, EV_DISTINCT, EV_COMPACT, EV_RANGES, EV_N };
+    enum { EV_0, EV_LAYERS, EV_FOLD, EV_DISTINCT, EV_COMPACT, EV_RANGES, EV_N };
     hipEvent_t ev[EV_N] = {};
     struct ev_guard {
         hipEvent_t* ev;
@@ -7705,6 +7708,7 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     osmt_cs_pass P;
     memset(&P, 0, sizeof P);
     P.R = rules.dev;
+    const bool class_layers = (rules.dev.flags & OSMT_RULES_CLASS_LAYERS) != 0u;
     P.classes = m->d_classes, P.class_sels = m->d_class_sels;
     P.n_classes = (uint32_t)n_classes, P.n_pairs = (uint32_t)(n_classes * OSMT_CS_ZOOMS);
     P.labels_all = labels_all;
@@ -7716,15 +7720,28 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     /* 1. count */
     const size_t n_pairs = P.n_pairs;
     const size_t o_pp = carve((n_pairs + 1) * 4), o_tot = carve(OSMT_CS_T_N * 8), o_zd = carve(OSMT_CS_ZOOMS * 4), o_blk0 = carve((n_pairs / 256 + 1) * 8);
+    const size_t o_sl = class_layers ? carve(m->n_class_sels) : 0, o_ci = class_layers ? carve(n_classes * 4) : 0;
     int rc = alloc("pairs");
     if (rc != OSMT_OK) return rc;
+    if (class_layers) P.sel_local = (uint8_t*)(base + o_sl), P.class_info = (uint32_t*)(base + o_ci);
     P.pair_pos = (uint32_t*)(base + o_pp);
     P.tot = (unsigned long long*)(base + o_tot);
     P.zoom_differs = (uint32_t*)(base + o_zd);
     P.blk = (unsigned long long*)(base + o_blk0);
     HIP_TRY(mark(EV_0));
+    HIP_TRY(osmt_launch_cs_class_layers(P, st));
+    HIP_TRY(mark(EV_LAYERS));
     HIP_TRY(osmt_launch_cs_count(P, st));
-    HIP_TRY(read_tot(OSMT_CS_T_STYLES, 1));
+    HIP_TRY(read_tot(class_layers ? OSMT_CS_T_BAD_CLASS : OSMT_CS_T_STYLES, class_layers ? 2 : 1));
+    if (class_layers && tot[OSMT_CS_T_BAD_CLASS] != ~0ull) {
+        /* the lowest class over the bound; its exact count is in its word */
+        const size_t bad = (size_t)tot[OSMT_CS_T_BAD_CLASS];
+        uint32_t info = 0;
+        HIP_TRY(hipMemcpyAsync(&info, P.class_info + bad, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return fail(OSMT_UNSUPPORTED, "cascade: the selectors of class %zu name %u distinct layers (> OSMT_CASCADE_MAX_CLASS_LAYERS = %u)", bad,
+                    OSMT_CS_CI_LAYERS(info), OSMT_CASCADE_MAX_CLASS_LAYERS);
+    }
     if (tot[OSMT_CS_T_STYLES] > 0x80000000ull)
         return fail(OSMT_UNSUPPORTED, "cascade: %llu styles over all classes and zooms (the table of distinct records holds at most 2^31)", tot[OSMT_CS_T_STYLES]);
     const size_t n_styles = (size_t)tot[OSMT_CS_T_STYLES];
@@ -7863,8 +7880,9 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
         };
         fprintf(stderr,
                 "osmt cascade: count + fold + records %.1f us, distinct %.1f us, compact + zooms %.1f us, ranges %.1f us (%zu classes, %zu styles, %zu + %zu "
-                "distinct, %zu ranges)\n",
-                us(EV_0, EV_FOLD), us(EV_FOLD, EV_DISTINCT), us(EV_DISTINCT, EV_COMPACT), us(EV_COMPACT, EV_RANGES), n_classes, n_styles, n_area, n_label, n_ranges);
+                "distinct, %zu ranges), class layers %.1f us\n",
+                us(EV_LAYERS, EV_FOLD), us(EV_FOLD, EV_DISTINCT), us(EV_DISTINCT, EV_COMPACT), us(EV_COMPACT, EV_RANGES), n_classes, n_styles, n_area, n_label, n_ranges,
+                us(EV_0, EV_LAYERS));
     }
     return OSMT_OK;
 }
@@ -7968,12 +7986,14 @@ int cascade_register_body(osmt_ctx* ctx, osmt_cascade* c, osmt_match* m, uint32_
 
 extern "C" {
 
-int osmt_validate_rules(const osmt_rules_desc* rules, osmt_ctx* ctx) {
-    return guarded([&] { return validate_rules(rules, ctx, nullptr); });
+int osmt_validate_rules_ex(const osmt_rules_desc* rules, uint32_t flags, osmt_ctx* ctx) {
+    return guarded([&] { return validate_rules(rules, flags, ctx, nullptr); });
 }
-int osmt_register_rules(osmt_ctx* ctx, const osmt_rules_desc* rules, uint32_t* out_rules_id) {
-    return guarded([&] { return register_rules_body(ctx, rules, out_rules_id); });
+int osmt_validate_rules(const osmt_rules_desc* rules, osmt_ctx* ctx) { return osmt_validate_rules_ex(rules, 0u, ctx); }
+int osmt_register_rules_ex(osmt_ctx* ctx, const osmt_rules_desc* rules, uint32_t flags, uint32_t* out_rules_id) {
+    return guarded([&] { return register_rules_body(ctx, rules, flags, out_rules_id); });
 }
+int osmt_register_rules(osmt_ctx* ctx, const osmt_rules_desc* rules, uint32_t* out_rules_id) { return osmt_register_rules_ex(ctx, rules, 0u, out_rules_id); }
 int osmt_cascade_classes(osmt_ctx* ctx, osmt_match* match, uint32_t rules_id, uint32_t labels_all, osmt_cascade** out) {
     return guarded([&] { return cascade_classes_body(ctx, match, rules_id, labels_all, out); });
 }

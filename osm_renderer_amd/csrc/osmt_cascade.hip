@@ -3,9 +3,13 @@
  * and label styles, the zoom ranges and the per-class lists of every range (include/osmtile.h, "the cascade").
  *
  * Stages (count / scan / emit, as k_sm_bind_* and k_lb_*):
+ *   k_cs_class_layers  (a set registered with OSMT_RULES_CLASS_LAYERS only) one lane per class: the layers of the class's
+ *                      selectors numbered 0 .. 15 by first appearance, the class's own "*" and "default", its layer count; a
+ *                      class of more than 16 layers reports itself and the cascade is refused
  *   k_cs_count         one lane per (class, zoom): the layers the kept selectors create, "*" left out  -> scan: the styles
  *   k_cs_fold          32 lanes per (class, zoom), lane = property name: style_area (styler.rs:205-242) with the per-layer
- *                      last writers in 8 registers; the layer bookkeeping (which layers exist, insertion order, the copy
+ *                      last writers in 8 registers indexed by the set's layer number, or in 16 indexed by the class's
+ *                      (CLASS_LAYERS); the layer bookkeeping (which layers exist, insertion order, the copy
  *                      from "*") is computed identically by every lane.  Writes one row of last writers per style.
  *   k_cs_records       one lane per style: property_map_to_style (osmt_cs_style_of, shared with the host mirror), the two
  *                      records, the text key, the hashes; 1 where the style is a label binding             -> scan
@@ -37,6 +41,8 @@ constexpr uint32_t WG = 256u;
 constexpr uint32_t GROUP = 32u; /* lanes per (class, zoom) in k_cs_fold */
 constexpr uint32_t Z = OSMT_CS_ZOOMS;
 constexpr uint32_t L = OSMT_CASCADE_MAX_LAYERS;
+constexpr uint32_t LC = OSMT_CASCADE_MAX_CLASS_LAYERS;
+static_assert(L == 8u && LC == 16u, "k_cs_fold packs a layer's insertion slot into 4 bits and `exists` into the low bits of a word");
 
 inline dim3 grid_of(uint32_t n) { return dim3((n + WG - 1u) / WG); }
 
@@ -49,65 +55,131 @@ __device__ __forceinline__ uint32_t mix(uint32_t h, uint32_t v) {
 /* does selector s admit the zoom (area_matches, styler.rs:505-515) */
 __device__ __forceinline__ bool admits(const osmt_cs_rules_dev& R, uint32_t s, uint32_t zoom) { return zoom >= R.sel_zoom[2u * s] && zoom <= R.sel_zoom[2u * s + 1u]; }
 
+/* One lane per class of a set registered with OSMT_RULES_CLASS_LAYERS: one walk of the class's selectors, no zoom filter, that
+ * numbers the distinct set-wide layer numbers (0 .. 254) by first appearance.  The numbers met are a set of 256 bits and the
+ * set-wide number of every local layer a byte of two words, both in registers and indexed by unrolled selects.  A class of
+ * more than LC layers keeps its exact count, gets the local number LC - 1 for what does not fit (so that k_cs_count, which
+ * runs before the host has looked, stays inside its 16 bits) and reports itself; the host refuses the cascade. */
+__global__ __launch_bounds__(256) void k_cs_class_layers(osmt_cs_pass P) {
+    const uint32_t c = blockIdx.x * WG + threadIdx.x;
+    if (c >= P.n_classes) return;
+    const uint32_t s0 = P.classes[c].sel_off, n = P.classes[c].n_sels;
+    uint64_t seen[4] = {0ull, 0ull, 0ull, 0ull};
+    uint64_t ids[LC / 8u] = {0ull, 0ull};
+    uint32_t n_layers = 0u;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t g = P.R.sel_layer[P.class_sels[s0 + i]];
+        const uint64_t bit = 1ull << (g & 63u);
+        bool known = false;
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; ++w)
+            if (w == g >> 6) {
+                known = (seen[w] & bit) != 0ull;
+                seen[w] |= bit;
+            }
+        if (!known) {
+#pragma unroll
+            for (uint32_t w = 0; w < LC / 8u; ++w)
+                if (n_layers < LC && w == n_layers >> 3) ids[w] |= (uint64_t)g << (8u * (n_layers & 7u));
+            ++n_layers;
+        }
+        uint32_t local = LC - 1u;
+#pragma unroll
+        for (uint32_t k = 0; k < LC; ++k)
+            if (k < n_layers && (uint32_t)((ids[k >> 3] >> (8u * (k & 7u))) & 0xFFull) == g) local = k;
+        P.sel_local[s0 + i] = (uint8_t)local;
+    }
+    uint32_t star = 0xFFu, base = 0xFFu;
+#pragma unroll
+    for (uint32_t k = 0; k < LC; ++k) {
+        const uint32_t g = (uint32_t)((ids[k >> 3] >> (8u * (k & 7u))) & 0xFFull);
+        if (k < n_layers && g == P.R.star) star = k;
+        if (k < n_layers && g == P.R.base) base = k;
+    }
+    P.class_info[c] = star | (base << 8) | (n_layers << 16);
+    if (n_layers > LC) atomicMin(P.tot + OSMT_CS_T_BAD_CLASS, (unsigned long long)c);
+}
+
+/* the class's own "*" / "default" of a CLASS_LAYERS set, as the layer number k_cs_count and k_cs_fold compare with */
+__device__ __forceinline__ uint32_t local_or_none(uint32_t byte) { return byte == 0xFFu ? OSMT_CS_NONE : byte; }
+
+/* LOCAL: the set is registered with OSMT_RULES_CLASS_LAYERS, layer numbers are the class's (sel_local, class_info); otherwise they
+ * are the set's (R.sel_layer, R.star, R.base), below 8 */
+template <bool LOCAL>
 __global__ __launch_bounds__(256) void k_cs_count(osmt_cs_pass P) {
     const uint32_t pair = blockIdx.x * WG + threadIdx.x;
     if (pair >= P.n_pairs) return;
     const uint32_t c = pair / Z, zoom = pair % Z;
     const uint32_t s0 = P.classes[c].sel_off, n = P.classes[c].n_sels;
+    const uint32_t star = LOCAL ? local_or_none(OSMT_CS_CI_STAR(P.class_info[c])) : P.R.star;
     uint32_t exists = 0u;
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t s = P.class_sels[s0 + i];
-        if (admits(P.R, s, zoom)) exists |= 1u << P.R.sel_layer[s];
+        if (admits(P.R, s, zoom)) exists |= 1u << (LOCAL ? (uint32_t)P.sel_local[s0 + i] : (uint32_t)P.R.sel_layer[s]);
     }
-    if (P.R.star != OSMT_CS_NONE) exists &= ~(1u << P.R.star);
+    if (star != OSMT_CS_NONE) exists &= ~(1u << star);
     P.pair_pos[pair] = (uint32_t)__popc(exists);
 }
 
+template <uint32_t LAYERS>
+struct order_of {
+    typedef uint32_t type;
+};
+template <>
+struct order_of<16u> {
+    typedef uint64_t type;
+};
+
+template <uint32_t LAYERS, bool LOCAL>
 __global__ __launch_bounds__(256) void k_cs_fold(osmt_cs_pass P) {
+    typedef typename order_of<LAYERS>::type order_t;
     const uint32_t lane = threadIdx.x % GROUP;
     const uint32_t pair = (blockIdx.x * WG + threadIdx.x) / GROUP;
     const bool live = pair < P.n_pairs;
     const uint32_t c = live ? pair / Z : 0u, zoom = pair % Z;
     const uint32_t s0 = live ? P.classes[c].sel_off : 0u, n = live ? P.classes[c].n_sels : 0u;
     const uint32_t name = lane < OSMT_PROP_NAMES ? lane : 0u; /* lanes 20 .. 31 shadow name 0 and write nothing */
-    const uint32_t star = P.R.star;
-    uint32_t last[L];
+    const uint32_t info = LOCAL && live ? P.class_info[c] : 0xFFFFu;
+    const uint32_t star = LOCAL ? local_or_none(OSMT_CS_CI_STAR(info)) : P.R.star;
+    const uint32_t base = LOCAL ? local_or_none(OSMT_CS_CI_BASE(info)) : P.R.base;
+    uint32_t last[LAYERS];
 #pragma unroll
-    for (uint32_t l = 0; l < L; ++l) last[l] = OSMT_CS_NONE;
-    uint32_t exists = 0u, order = 0u, n_layers = 0u; /* order: 4 bits per layer, in insertion order */
+    for (uint32_t l = 0; l < LAYERS; ++l) last[l] = OSMT_CS_NONE;
+    uint32_t exists = 0u, n_layers = 0u;
+    order_t order = 0u; /* 4 bits per layer, in insertion order */
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t s = P.class_sels[s0 + i];
         if (!admits(P.R, s, zoom)) continue;
-        const uint32_t g = P.R.sel_layer[s];
+        const uint32_t g = LOCAL ? (uint32_t)P.sel_local[s0 + i] : (uint32_t)P.R.sel_layer[s];
         const uint32_t v = P.R.rule_last[P.R.sel_rule[s] * OSMT_PROP_NAMES + name];
         if (!(exists & (1u << g))) {
             /* a new layer starts as a copy of "*", if that exists (styler.rs:225-228) */
             uint32_t init = OSMT_CS_NONE;
             if (star != OSMT_CS_NONE && (exists & (1u << star))) {
 #pragma unroll
-                for (uint32_t l = 0; l < L; ++l)
+                for (uint32_t l = 0; l < LAYERS; ++l)
                     if (l == star) init = last[l];
             }
 #pragma unroll
-            for (uint32_t l = 0; l < L; ++l)
+            for (uint32_t l = 0; l < LAYERS; ++l)
                 if (l == g) last[l] = init;
             exists |= 1u << g;
-            order |= g << (4u * n_layers);
+            order |= (order_t)g << (4u * n_layers);
             ++n_layers;
         }
         if (v != OSMT_CS_NONE) {
             /* the rule's properties go to the layer, and from "*" to every layer that exists (230-237) */
             const uint32_t to = g == star ? exists : 1u << g;
 #pragma unroll
-            for (uint32_t l = 0; l < L; ++l)
+            for (uint32_t l = 0; l < LAYERS; ++l)
                 if (to & (1u << l)) last[l] = v;
         }
     }
     uint32_t base_width = OSMT_CS_NONE;
-    if (P.R.base != OSMT_CS_NONE && (exists & (1u << P.R.base))) {
+    if (base != OSMT_CS_NONE && (exists & (1u << base))) {
 #pragma unroll
-        for (uint32_t l = 0; l < L; ++l)
-            if (l == P.R.base) base_width = last[l];
+        for (uint32_t l = 0; l < LAYERS; ++l)
+            if (l == base) base_width = last[l];
     }
     /* every lane of the wave is here: the width lane of the group hands its "default" writer to lane 20 */
     base_width = __shfl(base_width, (int)((threadIdx.x & 63u) - lane + OSMT_PROP_WIDTH));
@@ -115,11 +187,11 @@ __global__ __launch_bounds__(256) void k_cs_fold(osmt_cs_pass P) {
     const uint32_t out0 = P.pair_pos[pair];
     uint32_t position = 0u;
     for (uint32_t k = 0; k < n_layers; ++k) {
-        const uint32_t g = (order >> (4u * k)) & 15u;
+        const uint32_t g = (uint32_t)(order >> (4u * k)) & 15u;
         if (g == star) continue;
         uint32_t v = OSMT_CS_NONE;
 #pragma unroll
-        for (uint32_t l = 0; l < L; ++l)
+        for (uint32_t l = 0; l < LAYERS; ++l)
             if (l == g) v = last[l];
         uint32_t* row = P.rows + (size_t)(out0 + position) * OSMT_CS_ROW_WORDS;
         if (lane < OSMT_PROP_NAMES) row[lane] = v;
@@ -307,15 +379,31 @@ __global__ __launch_bounds__(256) void k_cs_range_emit(osmt_cs_pass P) {
 
 }  // namespace
 
+hipError_t osmt_launch_cs_class_layers(const osmt_cs_pass& a, hipStream_t st) {
+    if (!(a.R.flags & OSMT_RULES_CLASS_LAYERS)) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(a.tot + OSMT_CS_T_BAD_CLASS, 0xFF, 8u, st);
+    if (e != hipSuccess) return e;
+    if (a.n_classes) hipLaunchKernelGGL(k_cs_class_layers, grid_of(a.n_classes), dim3(WG), 0, st, a);
+    return hipGetLastError();
+}
+
 hipError_t osmt_launch_cs_count(const osmt_cs_pass& a, hipStream_t st) {
-    if (a.n_pairs) hipLaunchKernelGGL(k_cs_count, grid_of(a.n_pairs), dim3(WG), 0, st, a);
+    if (a.n_pairs) {
+        if (a.R.flags & OSMT_RULES_CLASS_LAYERS)
+            hipLaunchKernelGGL(k_cs_count<true>, grid_of(a.n_pairs), dim3(WG), 0, st, a);
+        else
+            hipLaunchKernelGGL(k_cs_count<false>, grid_of(a.n_pairs), dim3(WG), 0, st, a);
+    }
     return osmt_tq_scan(a.pair_pos, a.n_pairs, a.blk, a.tot + OSMT_CS_T_STYLES, st);
 }
 
 hipError_t osmt_launch_cs_fold(const osmt_cs_pass& a, hipStream_t st) {
     if (a.n_pairs && a.n_styles) {
         const uint32_t blocks = (uint32_t)(((unsigned long long)a.n_pairs * GROUP + WG - 1u) / WG);
-        hipLaunchKernelGGL(k_cs_fold, dim3(blocks), dim3(WG), 0, st, a);
+        if (a.R.flags & OSMT_RULES_CLASS_LAYERS)
+            hipLaunchKernelGGL((k_cs_fold<LC, true>), dim3(blocks), dim3(WG), 0, st, a);
+        else
+            hipLaunchKernelGGL((k_cs_fold<L, false>), dim3(blocks), dim3(WG), 0, st, a);
         hipLaunchKernelGGL(k_cs_records, grid_of(a.n_styles), dim3(WG), 0, st, a);
     }
     return osmt_tq_scan(a.bind_pos, a.n_styles, a.blk, a.tot + OSMT_CS_T_BINDINGS, st);

@@ -846,26 +846,34 @@ struct osmt_cs_rules_dev {
     const osmt_cs_prop* props;
     const uint32_t* rule_last;  /* [n_rules][OSMT_PROP_NAMES] */
     const uint32_t* sel_rule;   /* [n_sels] */
-    const uint8_t* sel_layer;   /* [n_sels] 0 .. n_layers - 1 */
+    const uint8_t* sel_layer;   /* [n_sels] 0 .. n_layers - 1: the set-wide layer number (below 8, or below 255 with CLASS_LAYERS) */
     const uint8_t* sel_zoom;    /* [n_sels][2] the zooms the selector admits, inclusive (0, 255 without bounds) */
     const double* numbers;
     uint32_t n_sels, n_layers, star, base; /* star / base: the layers "*" and "default", or OSMT_CS_NONE */
-    uint32_t font_id, _pad;
+    uint32_t font_id, flags;    /* flags: OSMT_RULES_* of the registration */
     double casing_width_multiplier, font_size_multiplier;
 };
-/* words of osmt_cs_pass::tot */
-enum { OSMT_CS_T_STYLES = 0, OSMT_CS_T_BINDINGS, OSMT_CS_T_AREA, OSMT_CS_T_LABEL, OSMT_CS_T_DASHES, OSMT_CS_T_RANGE_STYLES, OSMT_CS_T_RANGE_BINDINGS, OSMT_CS_T_N };
+/* words of osmt_cs_pass::tot; BAD_CLASS is read back together with STYLES */
+enum { OSMT_CS_T_BAD_CLASS = 0, OSMT_CS_T_STYLES, OSMT_CS_T_BINDINGS, OSMT_CS_T_AREA, OSMT_CS_T_LABEL, OSMT_CS_T_DASHES, OSMT_CS_T_RANGE_STYLES, OSMT_CS_T_RANGE_BINDINGS, OSMT_CS_T_N };
+/* osmt_cs_pass::class_info: one word per class */
+#define OSMT_CS_CI_STAR(w) ((w) & 0xFFu)          /* the class's local number of "*", 0xFF: the class has none */
+#define OSMT_CS_CI_BASE(w) (((w) >> 8) & 0xFFu)   /* of "default" */
+#define OSMT_CS_CI_LAYERS(w) ((w) >> 16)          /* the class's distinct layers, exact, at most 255 */
 struct osmt_cs_pass {
     osmt_cs_rules_dev R;
     const osmt_match_class* classes;
     const uint32_t* class_sels;
+    /* a set registered with OSMT_RULES_CLASS_LAYERS only (k_cs_class_layers writes them, k_cs_count and k_cs_fold read them) */
+    uint8_t* sel_local;           /* [n_class_sels], parallel to class_sels: the selector's layer numbered inside its class by first
+                                     appearance, 0 .. 15 (clamped to 15 in a class over the bound, whose cascade is refused) */
+    uint32_t* class_info;         /* [n_classes] OSMT_CS_CI_* */
     uint32_t n_classes, n_pairs;  /* pairs: (class, zoom), number class * 19 + zoom */
     uint32_t n_styles, n_bindings, n_area, n_label, n_ranges; /* totals, known once they have been read back */
     uint32_t labels_all;
     uint32_t hash_mask, table_mask;
     /* per pair */
     uint32_t* pair_pos; /* [n_pairs + 1] styles, then their exclusive scan */
-    /* per style (user): number = position in pair order, monotonic in ((class * 19) + zoom) * 8 + position */
+    /* per style (user): number = position in pair order, monotonic in ((class * 19) + zoom) * 8 + position (* 16 with CLASS_LAYERS) */
     uint32_t* rows;             /* [n_styles][OSMT_CS_ROW_WORDS] */
     osmt_style_rec* area;       /* [n_styles] dashes as ranges of R.numbers */
     osmt_label_style_rec* label;
@@ -896,6 +904,9 @@ struct osmt_cs_pass {
     unsigned long long* blk;
     unsigned long long* tot; /* [OSMT_CS_T_N] */
 };
+/* k_cs_class_layers (a CLASS_LAYERS set only; otherwise nothing is launched): sel_local, class_info, tot[BAD_CLASS] = the lowest
+ * class of more than OSMT_CASCADE_MAX_CLASS_LAYERS layers, or all ones */
+hipError_t osmt_launch_cs_class_layers(const osmt_cs_pass& a, hipStream_t st);
 /* k_cs_count + scan: tot[STYLES] */
 hipError_t osmt_launch_cs_count(const osmt_cs_pass& a, hipStream_t st);
 /* k_cs_fold + k_cs_records + scan: rows, records, hashes, tot[BINDINGS] */

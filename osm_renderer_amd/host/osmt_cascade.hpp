@@ -98,6 +98,12 @@ class RuleSet {
         desc_.font_size_multiplier = font_size_multiplier.value_or(0.0);
         return desc_;
     }
+    /* OSMT_RULES_CLASS_LAYERS: up to OSMT_CASCADE_MAX_LAYER_NAMES names, at most OSMT_CASCADE_MAX_CLASS_LAYERS layers per class */
+    void class_layers(bool on) { flags_ = on ? OSMT_RULES_CLASS_LAYERS : 0u; }
+    uint32_t flags() const { return flags_; }
+    /* the last desc() through the library with this set's flags (for callers that link it) */
+    int validate(osmt_ctx* ctx) const { return osmt_validate_rules_ex(&desc_, flags_, ctx); }
+    int register_in(osmt_ctx* ctx, uint32_t* out_rules_id) const { return osmt_register_rules_ex(ctx, &desc_, flags_, out_rules_id); }
 
   private:
     void need_rule() const {
@@ -119,6 +125,7 @@ class RuleSet {
     std::vector<double> numbers_;
     std::string strings_, layer_bytes_;
     osmt_rules_desc desc_{};
+    uint32_t flags_ = 0u;
 };
 
 /* the arrays of osmt_cascade_read */

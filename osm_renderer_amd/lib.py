@@ -50,7 +50,7 @@ EXPORTS = [
     "osmt_debug_match_hash_bits",
     "osmt_validate_class_label_bindings", "osmt_register_label_bindings_matched", "osmt_register_area_label_bindings_matched",
     "osmt_read_label_bindings", "osmt_read_area_label_bindings",
-    "osmt_validate_rules", "osmt_register_rules", "osmt_cascade_classes", "osmt_cascade_free", "osmt_cascade_read", "osmt_cascade_register",
+    "osmt_validate_rules", "osmt_register_rules", "osmt_validate_rules_ex", "osmt_register_rules_ex", "osmt_cascade_classes", "osmt_cascade_free", "osmt_cascade_read", "osmt_cascade_register",
 ]
 
 
@@ -210,6 +210,9 @@ def load():
         sz = C.POINTER(C.c_size_t)
         L.osmt_validate_rules.argtypes = [C.POINTER(abi.RulesDesc), vp]
         L.osmt_register_rules.argtypes = [vp, C.POINTER(abi.RulesDesc), C.POINTER(C.c_uint32)]
+        if hasattr(L, "osmt_register_rules_ex"):  # absent only from older variant builds loaded through OSMT_LIB
+            L.osmt_validate_rules_ex.argtypes = [C.POINTER(abi.RulesDesc), C.c_uint32, vp]
+            L.osmt_register_rules_ex.argtypes = [vp, C.POINTER(abi.RulesDesc), C.c_uint32, C.POINTER(C.c_uint32)]
         L.osmt_cascade_classes.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.osmt_cascade_free.argtypes = [vp]
         L.osmt_cascade_free.restype = None

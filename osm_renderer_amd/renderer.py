@@ -438,12 +438,23 @@ class Context:
         check(load().osmt_register_selectors(self._h, C.byref(d), C.byref(out)))
         return out.value
 
-    def register_rules(self, rules):
-        """osmt_register_rules: appends a selmatch.RuleSet; returns its id (Match.cascade takes it)."""
+    def register_rules(self, rules, class_layers=False):
+        """osmt_register_rules_ex: appends a selmatch.RuleSet; returns its id (Match.cascade takes it).  class_layers:
+        OSMT_RULES_CLASS_LAYERS, up to 255 layer names with at most 16 layers per class instead of 8 names in all."""
         d = rules.as_desc()
         out = C.c_uint32()
-        check(load().osmt_register_rules(self._h, C.byref(d), C.byref(out)))
+        L = load()
+        if class_layers or hasattr(L, "osmt_register_rules_ex"):  # absent only from older variant builds loaded through OSMT_LIB
+            check(L.osmt_register_rules_ex(self._h, C.byref(d), abi.RULES_CLASS_LAYERS if class_layers else 0, C.byref(out)))
+        else:
+            check(L.osmt_register_rules(self._h, C.byref(d), C.byref(out)))
         return out.value
+
+    def validate_rules(self, rules, class_layers=False):
+        """osmt_validate_rules_ex against this context's registries; raises OsmtError with the refusal."""
+        from . import selmatch
+
+        selmatch.validate_rules(rules, class_layers, self)
 
     def match_selectors(self, geodata_id, selectors_id, overrides=None):
         """osmt_match_selectors: a selmatch.Match; raises selmatch.Declined with the values to supply as overrides."""

@@ -208,6 +208,13 @@ class RuleSet:
         return d
 
 
+def validate_rules(rules, class_layers=False, ctx=None):
+    """osmt_validate_rules_ex over a RuleSet: the checks of Context.register_rules(rules, class_layers) without a device
+    (ctx None: the lookups of ids are skipped).  Raises OsmtError with the refusal."""
+    d = rules.as_desc()
+    check(load().osmt_validate_rules_ex(C.byref(d), abi.RULES_CLASS_LAYERS if class_layers else 0, ctx._h if ctx is not None else None))
+
+
 class CascadeResult:
     """The arrays of osmt_cascade_read (or of the host mirror).  Range r covers zooms zoom_lo[r] .. zoom_hi[r]; its class lists
     are class_style_off[r] / class_styles[range_style_base[r]:range_style_base[r + 1]] and class_off[r] / bindings[...]."""
