@@ -24,6 +24,7 @@
 #include "osmt_internal.h"
 #include "osmt_prebin_roles.h"
 #include "osmt_project.h"
+#include "osmt_u8_over_255.h"
 
 namespace {
 
@@ -529,12 +530,7 @@ __device__ __forceinline__ double opacity_by_center_distance(double cd, double h
     return opacity_mul * v;
 }
 
-/* f64::from(c) / 255.0 for every u8 (tile_pixels.rs:226-228): the compiler folds each entry with a correctly rounded
- * IEEE division, so a lookup returns exactly what the reference computes — without three f64 divisions per op. */
-#define OSMT_C4(i) (double)(i) / 255.0, (double)((i) + 1) / 255.0, (double)((i) + 2) / 255.0, (double)((i) + 3) / 255.0
-#define OSMT_C16(i) OSMT_C4(i), OSMT_C4((i) + 4), OSMT_C4((i) + 8), OSMT_C4((i) + 12)
-#define OSMT_C64(i) OSMT_C16(i), OSMT_C16((i) + 16), OSMT_C16((i) + 32), OSMT_C16((i) + 48)
-__constant__ double k_u8_over_255[256] = {OSMT_C64(0), OSMT_C64(64), OSMT_C64(128), OSMT_C64(192)};
+/* f64::from(c) / 255.0 for every u8 (tile_pixels.rs:226-228): k_u8_over_255[] and osmt_u8_over_255(), osmt_u8_over_255.h */
 
 /* ---- the fused raster kernel and its two binning kernels ------------------------------------- */
 constexpr int SUB = OSMT_SUB_W;    /* sub-tile width in pixels (one 32-bit coverage word per row) */
@@ -542,9 +538,41 @@ constexpr int SUBH = OSMT_SUB_H;   /* sub-tile height */
 constexpr int NTHREADS = 64;       /* one wave per sub-tile: no cross-wave barrier anywhere */
 constexpr int PXT = SUB * SUBH / NTHREADS; /* pixels per thread */
 constexpr int ROWSTEP = NTHREADS / SUB;    /* rows between a thread's consecutive pixels */
+/* k_raster's chain of dependent loads: 1 = the start-up's loads in two levels (arguments -> {job record,
+ * list header}) in front of the entries, 0 = as the compiler orders them when left alone */
+#ifndef OSMT_V_CHAIN_START
+#define OSMT_V_CHAIN_START 1
+#endif
+/* 1 = the colours of a chunk's entries are computed (osmt_u8_over_255), 0 = looked up in the table: a trip between the
+ * entries and the staging loads */
+#ifndef OSMT_V_CHAIN_COLOR
+#define OSMT_V_CHAIN_COLOR 1
+#endif
+/* 1 = the staging loads of a chunk's fills and strokes are one trip, 0 = the fills' lanes, then the strokes' (up to three) */
+#ifndef OSMT_V_CHAIN_STAGE
+#define OSMT_V_CHAIN_STAGE 1
+#endif
+/* 1 = the three words of the `main` calculator a stroke visit needs travel with the staged constants, 0 = they are read
+ * from the table by every visit: a trip in front of the walk's item loop */
+#ifndef OSMT_V_CHAIN_VISIT
+#define OSMT_V_CHAIN_VISIT 1
+#endif
+/* 1 = the RGBA8 epilogue stores through one scalar base and 32-bit lane offsets, 0 = a 64-bit address per pixel, flat stores */
+#ifndef OSMT_V_CHAIN_STORE
+#define OSMT_V_CHAIN_STORE 1
+#endif
 #ifndef OSMT_V_OPCHUNK
 #define OSMT_V_OPCHUNK 16
 #endif
+#ifndef OSMT_V_STAGECAP
+#define OSMT_V_STAGECAP 16
+#endif
+#if OSMT_V_OPCHUNK <= OSMT_V_STAGECAP
+#define OSMT_STAGE_UNION 1 /* every entry of a chunk has a staging slot (RasterShared) */
+#else
+#define OSMT_STAGE_UNION 0
+#endif
+#define OSMT_CHAIN_VISIT (OSMT_V_CHAIN_VISIT && OSMT_STAGE_UNION) /* (the words are where every visit finds them only then) */
 /* list entries staged per pass (config 2: ~5 per sub-tile, config 5: ~155).  16 with STAGECAP 16: every fill and every
  * stroke of a chunk has its words / constants staged (with 32 and 8, two in five of config 5's fills fetched theirs with
  * a scalar load of their own in the middle of the per-op loop: 1.38 -> 1.32 ms on 64 config-5 tiles, config 2 unchanged) */
@@ -583,8 +611,21 @@ static_assert(sizeof(StagedEnt) == 48, "three 16-byte LDS loads");
 struct StrokeConst {
     double ff0, ft0, fd0, rfd0, mul0;
     uint32_t flags; /* STROKE_* */
+#if OSMT_CHAIN_VISIT
+    /* what a visit reads of the `main` calculator besides its segments, staged with the rest: read from the table where the
+     * walk uses them, the compiler moved the loads in front of the item loop of EVERY stroke visit and waited there.  They
+     * are read from the staging slot where they are used (OSMT_KC_MAIN), never through a copy of the record in registers. */
+    uint32_t n_segs;
+    double total_len, r_total;
+#else
     uint32_t _pad;
+#endif
 };
+#if OSMT_CHAIN_VISIT
+#define OSMT_KC_MAIN(sh, stage, sa, f, m) (SH_SCONST(sh, late_index(stage)).f)
+#else
+#define OSMT_KC_MAIN(sh, stage, sa, f, m) ((sa)->m)
+#endif
 constexpr uint32_t STROKE_PLAIN_MAIN = 1u; /* the main calculator has no dash segments */
 constexpr uint32_t STROKE_UNIT_FD = 2u;    /* feather_dist == 1.0 exactly */
 constexpr uint32_t STROKE_TINY_MUL = 4u;   /* opacity_mul below 1e-100 (or NaN): no shortcut may assume mul0 * v > 0 */
@@ -599,9 +640,6 @@ __device__ __forceinline__ uint32_t stroke_flags(const osmt_stroke_aux* __restri
 #endif
     return (n == 0 ? STROKE_PLAIN_MAIN : 0u) | (sa->fd0 == 1.0 ? STROKE_UNIT_FD : 0u) | (tiny ? STROKE_TINY_MUL : 0u) | (fast ? STROKE_DASH_FAST : 0u);
 }
-#ifndef OSMT_V_STAGECAP
-#define OSMT_V_STAGECAP 16
-#endif
 constexpr int STAGECAP = OSMT_V_STAGECAP; /* fills / strokes of one chunk whose data is staged in LDS; the rest reads global memory */
 
 /* What every perpendicular run of a record needs and only the record determines (line.rs:75-104), computed ONCE by the
@@ -622,11 +660,6 @@ constexpr uint32_t SEGW_INCX_NEG = 1u, SEGW_INCY_NEG = 2u, SEGW_SWAP = 4u, SEGW_
 #define OSMT_V_FILTCAP 256
 #endif
 constexpr uint32_t FILTCAP = OSMT_V_FILTCAP; /* slots of a group's stroke entries one filter pass looks at (four rounds of 64 lanes) */
-#if OSMT_V_OPCHUNK <= OSMT_V_STAGECAP
-#define OSMT_STAGE_UNION 1
-#else
-#define OSMT_STAGE_UNION 0
-#endif
 constexpr int DTAB_F = 7; /* start_from, start_to, end_from, end_to, opacity_mul, r_start, r_end */
 struct RasterShared {
     OSMT_DBG(uint32_t dbg[12];) /* diagnostic build: [0] stroke visits [1] passes [2] items [3] filter passes of groups [4] groups ended by the
@@ -1159,14 +1192,15 @@ __device__ __forceinline__ void walk_items_dashed(Shared& sh, uint32_t slot0, ui
  * the table of a round is wave-uniform (scalar loads). */
 template <class Shared>
 __device__ __forceinline__ void walk_items(Shared& sh, uint32_t lane, uint32_t slot0, uint32_t nslot, uint32_t item_base, uint32_t it_lo, uint32_t it_hi,
-                                           const StrokeConst& kc, uint32_t sflags, const osmt_stroke_aux* __restrict__ sa, double initial_opacity,
-                                           const SubRect& rc) {
+                                           const StrokeConst& kc, uint32_t stage, uint32_t sflags, const osmt_stroke_aux* __restrict__ sa,
+                                           double initial_opacity, const SubRect& rc) {
     OSMT_DBG(if (lane == 0u) { sh.dbg[1] += (it_hi - it_lo + 63u) / 64u; sh.dbg[2] += it_hi - it_lo; })
     const bool main_plain = (sflags & STROKE_PLAIN_MAIN) != 0u;
     const bool unit_fd = (sflags & (STROKE_UNIT_FD | STROKE_TINY_MUL)) == STROKE_UNIT_FD;
     const bool dash_fast = (sflags & STROKE_DASH_FAST) != 0u;
     if (dash_fast) {
-        walk_items_dashed(sh, slot0, nslot, item_base, it_lo, it_hi, kc, sa->main_n_segs, sa->main_total_len, sa->main_r_total, initial_opacity, rc);
+        walk_items_dashed(sh, slot0, nslot, item_base, it_lo, it_hi, kc, OSMT_KC_MAIN(sh, stage, sa, n_segs, main_n_segs), OSMT_KC_MAIN(sh, stage, sa, total_len, main_total_len),
+                          OSMT_KC_MAIN(sh, stage, sa, r_total, main_r_total), initial_opacity, rc);
         /* the op's cap stubs (another calculator, line.rs:22), if it has any in this sub-tile, go through the loop below */
         const uint32_t l_ = fresh_lane();
         if (!__ballot(l_ < nslot && (sh.der[slot0 + l_].w & SEGW_CAP) != 0u)) return;
@@ -1203,8 +1237,8 @@ __device__ __forceinline__ void walk_items(Shared& sh, uint32_t lane, uint32_t s
                 const bool cp = t == 1u; /* wave-uniform: the table of a round is read with scalar loads */
                 const osmt_raster_args* la = late_args();
                 const osmt_dash_seg* sgs = cp ? &sa->caps_seg : la->dseg + (size_t)(sa - la->aux) * OSMT_MAX_DASH_SEGS;
-                walk_dashed(st, kc, cp ? 1 : sa->main_n_segs, (cp ? sa->caps_has_orig : sa->main_has_orig) != 0, cp ? 0.0 : sa->main_total_len,
-                            cp ? 0.0 : sa->main_r_total, sgs, sa->half_width, r.traveled, initial_opacity, sh.plane);
+                walk_dashed(st, kc, cp ? 1 : (int)OSMT_KC_MAIN(sh, stage, sa, n_segs, main_n_segs), (cp ? sa->caps_has_orig : sa->main_has_orig) != 0,
+                            cp ? 0.0 : OSMT_KC_MAIN(sh, stage, sa, total_len, main_total_len), cp ? 0.0 : OSMT_KC_MAIN(sh, stage, sa, r_total, main_r_total), sgs, sa->half_width, r.traveled, initial_opacity, sh.plane);
             }
 #endif
         }
@@ -2039,7 +2073,20 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
     const uint32_t* OSMT_R g_fmask = a.fmask;
     const osmt_srec* OSMT_R g_srec = a.srec;
     const uint2* OSMT_R g_skey = a.skey;
+#if OSMT_V_CHAIN_START
+    /* Level 1 of a wave's start: everything the start needs of the argument block in ONE trip, in front of the early
+     * exit (left to itself the compiler fetches n_jobs and scale, waits, and asks for `jobs` behind the exit: a second
+     * trip).  The empty asm needs all four values, so all four loads are in flight before the first wait. */
+    const osmt_tile_job* OSMT_R g_jobs = a.jobs;
+    const uint2* OSMT_R g_hdr = a.hdr;
+    uint32_t g_n_jobs = a.n_jobs;
+    uint32_t g_scale = a.scale;
+    /* (the tables of the loops with them: asked for where they are first used, each was a trip to the argument segment in
+     * front of the loads it addresses.  Not volatile: behind a volatile asm no load is a scalar load.) */
+    asm("" : "+s"(g_n_jobs), "+s"(g_scale) : "s"(g_jobs), "s"(g_hdr), "s"(g_ent), "s"(g_aux), "s"(g_fmask), "s"(g_srec), "s"(g_skey));
+#else
     const uint32_t g_scale = a.scale;
+#endif
     __shared__ RasterShared sh;
 
     const uint32_t tid = threadIdx.x;
@@ -2055,9 +2102,45 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
     const uint32_t rest = b >> 3;
     const uint32_t tile = (rest / nsub) * 8u + xcd;
     const uint32_t sub = rest % nsub;
+#if OSMT_V_CHAIN_START
+    if (tile >= g_n_jobs) return;
+
+    /* Level 2: the tile's job record and (big batches) the sub-tile's list header, both addressed by the block index and
+     * the arguments alone, in ONE trip.  The record is wave-uniform: eight words by one scalar load, the canvas bytes
+     * taken from its words (byte loads are vector loads, and a branch on has_canvas put the colour loads behind them).
+     * The FOLD instantiation keeps the header behind the record: small batches may have no headers at all. */
+    struct alignas(32) JobWords {
+        uint32_t w[8]; /* osmt_tile_job: x, y, zoom | has_canvas << 8 | rgb[0] << 16 | rgb[1] << 24, rgb[2], n_ops, op_off, n_pts, pt_off */
+    };
+    static_assert(sizeof(osmt_tile_job) == sizeof(JobWords) && offsetof(osmt_tile_job, has_canvas) == 9 && offsetof(osmt_tile_job, canvas_rgb) == 10 &&
+                      offsetof(osmt_tile_job, n_ops) == 16 && offsetof(osmt_tile_job, op_off) == 20,
+                  "the job record as words");
+    uint32_t job_w2, job_w3, job_n_ops;
+    uint2 hdr_raw = make_uint2(0u, 0u);
+    if (FOLD) {
+        const JobWords jw = *reinterpret_cast<const JobWords*>(g_jobs + tile);
+        job_w2 = jw.w[2], job_w3 = jw.w[3], job_n_ops = jw.w[4];
+    } else {
+        /* one statement: written as two C++ loads the pair came out as load, wait, load, wait again — the register
+         * allocator reused a register of the first load's destination for the second one's address */
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        u32x4 jq; /* words 2 .. 5 of the record */
+        u32x2 hq;
+        asm("s_load_dwordx4 %0, %2, 0x8\n\t"
+            "s_load_dwordx2 %1, %3, 0x0\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&s"(jq), "=&s"(hq)
+            : "s"(g_jobs + tile), "s"(g_hdr + ((size_t)tile * nsub + sub)));
+        job_w2 = jq.x, job_w3 = jq.y, job_n_ops = jq.z;
+        hdr_raw = make_uint2(hq.x, hq.y);
+    }
+#else
     if (tile >= a.n_jobs) return;
 
     const osmt_tile_job job = a.jobs[tile];
+    const uint32_t job_n_ops = job.n_ops;
+#endif
     SubRect rc;
     const uint32_t sub_x = sub % subs_per_row, sub_y = sub / subs_per_row;
     rc.x0 = (int32_t)(sub_x * SUB);
@@ -2080,11 +2163,29 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
     double acc[PXT][3];
     {
         double r = 0.0, g = 0.0, bl = 0.0;
+#if OSMT_V_CHAIN_START
+        /* the canvas colour costs no trip: three exact quotients per wave instead of three loads behind the record
+         * (1.0 * c, the canvas alpha times the colour, is c) */
+        const bool has_canvas = ((job_w2 >> 8) & 255u) != 0u;
+        /* (back into scalar registers, where the table's values were: as vector values the three are live across the
+         * whole kernel for the sub-tile without entries, six registers the kernel does not have) */
+        auto uniform = [](double v) {
+            const long long b = __double_as_longlong(v);
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(b & 0xFFFFFFFFll));
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(b >> 32));
+            return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+        };
+        /* no canvas = opaque black = the quotients of 0: a select on the byte, no branch */
+        r = uniform(osmt_u8_over_255(has_canvas ? (job_w2 >> 16) & 255u : 0u));
+        g = uniform(osmt_u8_over_255(has_canvas ? job_w2 >> 24 : 0u));
+        bl = uniform(osmt_u8_over_255(has_canvas ? job_w3 & 255u : 0u));
+#else
         if (job.has_canvas) {
             r = 1.0 * k_u8_over_255[job.canvas_rgb[0]];
             g = 1.0 * k_u8_over_255[job.canvas_rgb[1]];
             bl = 1.0 * k_u8_over_255[job.canvas_rgb[2]];
         }
+#endif
 #pragma unroll
         for (int j = 0; j < PXT; ++j) {
             acc[AJ(j)][0] = r;
@@ -2104,7 +2205,7 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
      * kernel (32 us of a config-2 step, 8 us of a one-tile request) fewer. */
     /* FOLD: the instantiation small batches are rendered with (osmt_launch_raster); the other one is the kernel big batches
      * have always had — not an instruction of it differs */
-    const bool fold = FOLD && job.n_ops <= OSMT_FOLD_MAX_OPS;
+    const bool fold = FOLD && job_n_ops <= OSMT_FOLD_MAX_OPS;
     /* the op bits of this sub-tile, asked for again by every chunk (one chunk per sub-tile on config 2): a word that stayed
      * in a register across the chunk loop is a register the kernel does not have */
     auto op_bits = [&](unsigned long long* b0, unsigned long long* b1) {
@@ -2124,10 +2225,15 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
         op_bits(&b0, &b1);
         hdr.y = (uint32_t)__popcll(b0) + (uint32_t)__popcll(b1);
     } else {
-        /* (requested beside the job record, not behind it) a tile without ops is plain canvas (drawer.rs:60-131 with no
-         * areas): what its headers hold is never looked at — a scene without any op has no list kernel launch at all */
+        /* a tile without ops is plain canvas (drawer.rs:60-131 with no areas): what its headers hold is never looked
+         * at — a scene without any op has no list kernel launch at all.  The header is requested beside the job record
+         * (level 2 above; in the FOLD instantiation behind it) and the override is a select after both have arrived. */
+#if OSMT_V_CHAIN_START
+        hdr = FOLD ? a.hdr[(size_t)tile * nsub + sub] : hdr_raw;
+#else
         hdr = a.hdr[(size_t)tile * nsub + sub];
-        if (job.n_ops == 0u) hdr = make_uint2(0u, 0u);
+#endif
+        if (job_n_ops == 0u) hdr = make_uint2(0u, 0u);
     }
 #if defined(OSMT_ABL) && OSMT_ABL == 8
     const uint32_t n_ent = hdr.y > 0xFFFFFFF0u ? 1u : 0u; /* ablation: the list is not even staged */
@@ -2191,9 +2297,21 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
         __syncthreads(); /* the previous chunk's list is consumed */
         if (hit) {
             sh.nvi[fresh_lane()] = nv_scan; /* only the lanes of the chunk's entries are ever asked for theirs */
+#if OSMT_V_CHAIN_STAGE && OSMT_STAGE_UNION /* (a staging slot per entry, my_stage < STAGECAP: both kinds' 64 bytes in one place) */
+            /* asked for first, put into LDS below: the entry's colours are computed while the words travel */
+            const uint4* OSMT_R src = is_stroke ? reinterpret_cast<const uint4*>(&g_aux[e.aux]) + 1 : reinterpret_cast<const uint4*>(g_fmask + e.arena);
+            const uint4 w0 = src[0], w1 = src[1], w2 = src[2], w3 = src[3];
+#endif
             StagedEnt se;
+#if OSMT_V_CHAIN_COLOR
+            /* computed, not looked up: the three table loads were a round trip of their own between the entries and the
+             * staging loads below (the compiler waits for them before it issues those) */
+            const double cr = osmt_u8_over_255((e.kind_color >> 8) & 255u), cg = osmt_u8_over_255((e.kind_color >> 16) & 255u),
+                         cb = osmt_u8_over_255(e.kind_color >> 24);
+#else
             const double cr = k_u8_over_255[(e.kind_color >> 8) & 255u], cg = k_u8_over_255[(e.kind_color >> 16) & 255u],
                          cb = k_u8_over_255[e.kind_color >> 24];
+#endif
             const bool fc = e_kind == OSMT_OP_FILL_COLOR;
             se.c0 = fc ? e.opacity * cr : cr; /* from_color: o * (c / 255) */
             se.c1 = fc ? e.opacity * cg : cg;
@@ -2204,6 +2322,47 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
             se.aux = e.aux;
             se.nv = e.nv;
             sh.ent[lane] = se;
+#if OSMT_V_CHAIN_STAGE && OSMT_STAGE_UNION
+            {
+                /* ONE trip for the staging loads of a chunk: every entry's lane asks for 64 bytes — a fill's 16 coverage
+                 * words (one line), a stroke's constants (bytes 16 .. 80 of its osmt_stroke_aux: ff0 .. main_total_len) —
+                 * and all lanes wait once.  As two divergent blocks the fills' lanes waited for their words before the
+                 * strokes' lanes had asked for anything, and stroke_flags()'s short-circuit tests read main_has_orig and
+                 * main_total_len in two further trips behind main_n_segs. */
+                static_assert(offsetof(osmt_stroke_aux, ff0) == 16 && offsetof(osmt_stroke_aux, ft0) == 24 && offsetof(osmt_stroke_aux, fd0) == 32 &&
+                                  offsetof(osmt_stroke_aux, mul0) == 40 && offsetof(osmt_stroke_aux, rfd0) == 48 &&
+                                  offsetof(osmt_stroke_aux, main_n_segs) == 56 && offsetof(osmt_stroke_aux, main_has_orig) == 60 &&
+                                  offsetof(osmt_stroke_aux, main_total_len) == 64 && offsetof(osmt_stroke_aux, main_r_total) == 72 &&
+                                  sizeof(StrokeConst) == (OSMT_CHAIN_VISIT ? 64 : 48) && sizeof(uint32_t) * SUBH == 64,
+                              "the words the stroke constants are put together from");
+                uint4* dst = reinterpret_cast<uint4*>(&SH_FMASK(sh, my_stage)[0]);
+                dst[0] = w0; /* fill: words 0 .. 3; stroke: ff0, ft0 */
+                if (is_stroke) {
+                    auto f64_of = [](uint32_t lo, uint32_t hi) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); };
+                    const double fd0 = f64_of(w1.x, w1.y), mul0 = f64_of(w1.z, w1.w), total_len = f64_of(w3.x, w3.y);
+                    const int n = (int)w2.z;
+                    const bool tiny = !(mul0 >= 1e-100);
+#ifdef OSMT_V_NO_DASH_FAST
+                    const bool fast = false;
+#else
+                    const bool fast = n > 0 && w2.w == 0u && total_len > 0.0 && !tiny;
+#endif
+                    const uint32_t flags =
+                        (n == 0 ? STROKE_PLAIN_MAIN : 0u) | (fd0 == 1.0 ? STROKE_UNIT_FD : 0u) | (tiny ? STROKE_TINY_MUL : 0u) | (fast ? STROKE_DASH_FAST : 0u); /* = stroke_flags() */
+                    dst[1] = make_uint4(w1.x, w1.y, w2.x, w2.y); /* fd0, rfd0 */
+#if OSMT_CHAIN_VISIT
+                    dst[2] = make_uint4(w1.z, w1.w, flags, w2.z); /* mul0, flags, n_segs */
+                    dst[3] = w3;                                  /* total_len, r_total */
+#else
+                    dst[2] = make_uint4(w1.z, w1.w, flags, 0u);  /* mul0, flags, _pad */
+#endif
+                } else {
+                    dst[1] = w1;
+                    dst[2] = w2;
+                    dst[3] = w3;
+                }
+            }
+#else
             if (!is_stroke && my_stage < (uint32_t)STAGECAP) {
                 /* the fill's 16 coverage words (one 64-byte line), requested by the lane that staged the entry — beside the
                  * strokes' constants, not a round trip behind them */
@@ -2225,9 +2384,16 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
                 kc.rfd0 = sa->rfd0;
                 kc.mul0 = sa->mul0;
                 kc.flags = stroke_flags(sa);
+#if OSMT_CHAIN_VISIT
+                kc.n_segs = (uint32_t)sa->main_n_segs;
+                kc.total_len = sa->main_total_len;
+                kc.r_total = sa->main_r_total;
+#else
                 kc._pad = 0;
+#endif
                 SH_SCONST(sh, my_stage) = kc;
             }
+#endif
         }
         const bool any_stroke = sbal != 0ull;
         if (any_stroke && !plane_clean) {
@@ -2417,13 +2583,19 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
                     kc.rfd0 = sa->rfd0;
                     kc.mul0 = sa->mul0;
                     kc.flags = stroke_flags(sa);
+#if OSMT_CHAIN_VISIT
+                    kc.n_segs = (uint32_t)sa->main_n_segs;
+                    kc.total_len = sa->main_total_len;
+                    kc.r_total = sa->main_r_total;
+#else
                     kc._pad = 0;
+#endif
                 }
                 const uint32_t sflags = (uint32_t)__builtin_amdgcn_readfirstlane((int)kc.flags);
                 if (sflags & STROKE_DASH_FAST) { /* the op's DashSegments into LDS: the walk reads them per pixel */
                     const double* OSMT_R src = reinterpret_cast<const double*>(late_args()->dseg + (size_t)aux_i * OSMT_MAX_DASH_SEGS);
                     static_assert(sizeof(osmt_dash_seg) == 9 * sizeof(double), "nine doubles per DashSegment");
-                    const uint32_t nd = (uint32_t)sa->main_n_segs * (uint32_t)DTAB_F;
+                    const uint32_t nd = (uint32_t)OSMT_KC_MAIN(sh, stage, sa, n_segs, main_n_segs) * (uint32_t)DTAB_F;
                     for (uint32_t l = fresh_lane(); l < nd; l += 64u) {
                         const uint32_t sg = l / (uint32_t)DTAB_F, f = l % (uint32_t)DTAB_F;
                         (&sh.dtab[0][0])[l] = src[sg * 9u + (f < 5u ? f : f + 2u)];
@@ -2474,7 +2646,7 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
 #if defined(OSMT_ABL) && (OSMT_ABL == 1 || OSMT_ABL == 2)
                             (void)item_lo; (void)item_hi; /* ablation: the runs are not walked */
 #else
-                            walk_items(sh, lane, slot0, nslot, item_lo, item_lo, item_hi, kc, sflags, sa, cop, rc);
+                            walk_items(sh, lane, slot0, nslot, item_lo, item_lo, item_hi, kc, stage, sflags, sa, cop, rc);
 #endif
                         }
                     }
@@ -2664,6 +2836,22 @@ __global__ OSMT_RASTER_BOUNDS void k_raster(
         }
         return;
     }
+#if OSMT_V_CHAIN_STORE
+    if (!OUT_F64) {
+        /* RGBA8: one uniform base (the sub-tile's first pixel) and a 32-bit offset per lane that grows by a constant row
+         * stride — global stores with a scalar base instead of flat ones behind two 64-bit multiply-adds per pixel */
+        typedef __attribute__((address_space(1))) uint32_t global_u32;
+        uint8_t* const sub_out = reinterpret_cast<uint8_t*>(g_out) + (size_t)tile * g_out_tile_stride + ((size_t)rc.y0 * W + (size_t)rc.x0) * 4u;
+        const uint32_t off0 = (ly_o * W + lx_o) * 4u, row_step = (uint32_t)ROWSTEP * W * 4u; /* < 16 rows of at most 4096 pixels */
+#pragma unroll
+        for (int j = 0; j < PXT; ++j) {
+            const uint32_t v = f64_as_u8(255.0 * acc[AJ(j)][0]) | (f64_as_u8(255.0 * acc[AJ(j)][1]) << 8) |
+                               (f64_as_u8(255.0 * acc[AJ(j)][2]) << 16) | 0xFF000000u;
+            __builtin_nontemporal_store(v, (global_u32*)(sub_out + (off0 + (uint32_t)j * row_step)));
+        }
+        return;
+    }
+#endif
 #pragma unroll
     for (int j = 0; j < PXT; ++j) {
         const uint32_t row = ly_o + (uint32_t)j * ROWSTEP;
