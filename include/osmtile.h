@@ -1403,6 +1403,49 @@ typedef struct osmt_png_job osmt_png_job;
 int osmt_render_batch_png_begin(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels /* may be NULL */, osmt_png_job** out_job);
 int osmt_render_batch_png_end(osmt_png_job* job, uint8_t* out_png, size_t out_capacity, uint64_t* out_off);
 
+/* ---- host pixels and PNG files from any scene (Drawer::draw_tile for tile coordinates, drawer.rs:40-58) ----------
+ * The entries above start from a host-built osmt_batch.  These start from a scene of the context — osmt_scene_upload,
+ * osmt_scene_build_styled or osmt_scene_build_tiles, with whatever labels osmt_scene_set_*labels or
+ * osmt_scene_build_tile_labels[_all] attached — so a caller without a HIP runtime of its own goes from tile coordinates to
+ * files.  The scene is BORROWED: it is never consumed and renders the same afterwards, through any entry.
+ * Work runs on private streams of the context.  Before its first launch a call waits for the scene's own earlier launches
+ * (the pre-pass rewrites the scene's lists), so a second call — or a second _begin — on the SAME scene while a job is in
+ * flight is correct but serialised.  As with osmt_render_scene, one scene is driven by one thread at a time; different
+ * scenes of one context may be driven from different threads and run concurrently.  A scene of 0 tiles is valid.
+ * OSMT_INVALID_ARG: NULL arguments, a scene of another context, an unknown format, a stride below the tile size
+ * (W*W*4, RGB8: W*W*3), RGB8 with `out` or the stride not a multiple of 4.
+ *
+ * osmt_render_scene_host: the pixels of every tile at out + i * out_tile_stride_bytes, complete on return; the same three
+ * routes as osmt_render_batch* (zero-copy for at most OSMT_ZERO_COPY_TILES tiles into pinned memory, a two-stream chunked
+ * read-back for big pinned outputs, one copy otherwise).
+ * osmt_render_scene_png / _begin: the out_png / out_off contract of osmt_render_batch_png.  A job begun from a scene is
+ * ended by osmt_render_batch_png_end like any other (capacity too small: out_off[n_jobs] is the size needed; the job is
+ * freed whatever _end returns).  The job does not own the scene: the SCENE MUST OUTLIVE THE JOB — end (or abandon) the job
+ * before osmt_scene_free. */
+#define OSMT_PIXELS_RGBA8 0u
+#define OSMT_PIXELS_RGB8 1u /* packed triples, the memory of RgbTriples */
+int osmt_render_scene_host(osmt_ctx* ctx, osmt_scene* scene, uint32_t format, uint8_t* out, size_t out_tile_stride_bytes);
+int osmt_render_scene_png(osmt_ctx* ctx, osmt_scene* scene, uint8_t* out_png, size_t out_capacity, uint64_t* out_off);
+int osmt_render_scene_png_begin(osmt_ctx* ctx, osmt_scene* scene, osmt_png_job** out_job);
+
+/* The asynchronous device form: render, encode, file offsets and compaction are QUEUED on the caller's stream and nothing is
+ * waited for (the rules of osmt_render_scene).  Afterwards, in stream order: d_off[0 .. n_jobs] are the file offsets
+ * (exclusive 64-bit scan of the lengths, complete in every case), *d_status is 0 and file i is d_png[d_off[i] .. d_off[i+1]),
+ * or *d_status is 1 because d_off[n_jobs] > png_capacity and NOTHING was written to d_png.
+ * d_work: osmt_scene_png_work_bytes(ctx, scene) bytes of device memory, aligned to 256 — n framebuffers of W*W*4 bytes, then n
+ * slots of osmt_png_device_bound(W, W) bytes, then n 32-bit lengths, each part rounded up to a multiple of 256 bytes
+ * (W = OSMT_TILE_SIZE * scale; 0 tiles: 0 bytes, d_work and d_png may be NULL).  d_off is 8-byte aligned device memory.
+ * osmt_scene_png_work_bytes returns 0 on bad arguments. */
+size_t osmt_scene_png_work_bytes(osmt_ctx* ctx, osmt_scene* scene);
+int osmt_render_scene_png_device(osmt_ctx* ctx, osmt_scene* scene, void* d_work, size_t work_bytes, void* d_png, size_t png_capacity,
+                                 uint64_t* d_off /* [n_jobs + 1] */, uint32_t* d_status, void* stream);
+/* Test hook in the spirit of osmt_debug_hypot: the offset scan of the device form alone (k_png_offsets: one workgroup of
+ * OSMT_PNG_OFFSETS_GROUP threads walks n <= 2^31 lengths in passes).  d_len[n], d_off[n + 1] and d_status are device memory;
+ * queued on `stream`. */
+#define OSMT_PNG_OFFSETS_GROUP 256u
+int osmt_debug_png_offsets(osmt_ctx* ctx, const uint32_t* d_len, uint32_t n, uint64_t capacity, uint64_t* d_off, uint32_t* d_status,
+                           void* stream);
+
 /* ---- the per-request entry: one worker handle per server thread (SURVEY.md 8(b) "Threading") ----------------
  * The reference's server gives every request — ONE tile — to one of available_parallelism() worker threads, each
  * with a TilePixels of its own (src/http_server.rs:50-83,105-108,134-181: handle_connection -> draw_tile_png).

@@ -10,6 +10,8 @@ MAX_ZOOM = 18  # reference: src/tile.rs:5
 MAX_DASHES = 16
 
 OK, INVALID_ARG, OOM, HIP_ERROR, UNSUPPORTED, NO_DEVICE, RCCL_ERROR = 0, -1, -2, -3, -4, -5, -6
+PIXELS_RGBA8, PIXELS_RGB8 = 0, 1  # osmt_render_scene_host formats
+PNG_OFFSETS_GROUP = 256  # threads of k_png_offsets' one workgroup = lengths per pass (OSMT_PNG_OFFSETS_GROUP)
 COMM_ID_BYTES = 128
 MULTI_RGB8 = 1  # osmt_render_batch_multi_ex flags
 

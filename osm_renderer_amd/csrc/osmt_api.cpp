@@ -5123,49 +5123,29 @@ static int osmt_render_batch_labels_body(osmt_ctx* ctx, const osmt_batch* batch,
     return rc;
 }
 
-static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba, size_t stride,
-                                         bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels,
-                                         const osmt_text_label_batch* tlabels, const osmt_string_label_batch* slabels) {
-    if (!ctx || !out_rgba) return fail(OSMT_INVALID_ARG, "NULL argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = nullptr; /* the whole call lives on its own stream: concurrent callers overlap on the GPU */
-    HIP_TRY(stream_acquire(ctx, &st));
-    osmt_scene* sc = nullptr;
-    int rc = scene_upload_impl(ctx, batch, &sc, st, trusted, allow_guess);
-    if (rc != OSMT_OK) {
-        stream_release(ctx, st);
-        return rc;
-    }
-    if (labels || glabels || tlabels || slabels) {
-        rc = labels ? osmt_scene_set_labels(ctx, sc, labels)
-                    : glabels ? osmt_scene_set_glyph_labels(ctx, sc, glabels)
-                              : tlabels ? osmt_scene_set_text_labels(ctx, sc, tlabels) : osmt_scene_set_string_labels(ctx, sc, slabels);
-        if (rc != OSMT_OK) {
-            osmt_scene_free(sc);
-            stream_release(ctx, st);
-            return rc;
-        }
-    }
-    const size_t W = (size_t)OSMT_TILE_SIZE * batch->scale;
+/* The back half of every host-buffer render, where the scene exists: shared by the batch forms (a per-call scene that lives
+ * on `st`) and osmt_render_scene_host (a public scene, borrowed).  Takes one of three routes — zero-copy, the two-stream
+ * chunked read-back, one plain copy — and returns with the pixels in out_rgba and both streams idle.  The caller owns the
+ * scene and `st`. */
+static int scene_render_host_back(osmt_ctx* ctx, osmt_scene* sc, hipStream_t st, uint8_t* out_rgba, size_t stride, bool rgb) {
+    const uint32_t n_jobs = sc->n_jobs, scale = sc->scale;
+    const size_t W = (size_t)OSMT_TILE_SIZE * scale;
     const size_t tile_bytes = W * W * 4;                   /* what k_raster writes */
     const size_t host_bytes = rgb ? W * W * 3 : tile_bytes; /* what crosses PCIe */
-    if (stride < host_bytes) {
-        osmt_scene_free(sc);
-        stream_release(ctx, st);
-        return fail(OSMT_INVALID_ARG, rgb ? "out_tile_stride_bytes < W*H*3" : "out_tile_stride_bytes < W*H*4");
-    }
+    int rc = OSMT_OK;
+    if (stride < host_bytes) return fail(OSMT_INVALID_ARG, rgb ? "out_tile_stride_bytes < W*H*3" : "out_tile_stride_bytes < W*H*4");
     /* Output in pinned host memory (osmt_host_alloc / hipHostMalloc / a registered range) and a batch worth
      * splitting: kernels of chunk k overlap the D2H copy of chunk k-1 on a second stream. */
     bool pinned = false;
-    if (batch->n_jobs >= 2u * std::max<uint32_t>(1u, 128u / (batch->scale * batch->scale))) { /* the query is not free: only where it can pay */
+    if (n_jobs >= 2u * std::max<uint32_t>(1u, 128u / (scale * scale))) { /* the query is not free: only where it can pay */
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, out_rgba) == hipSuccess)
             pinned = at.type == hipMemoryTypeHost;
         else
             (void)hipGetLastError();
     }
-    const uint32_t chunk = std::max<uint32_t>(1u, 128u / (batch->scale * batch->scale));
-    if (pinned && batch->n_jobs >= 2u * chunk) {
+    const uint32_t chunk = std::max<uint32_t>(1u, 128u / (scale * scale));
+    if (pinned && n_jobs >= 2u * chunk) {
         hipStream_t s_k = st, s_c = nullptr; /* kernels stay on the call's stream (the scene was uploaded there) */
         hipEvent_t done[2] = {nullptr, nullptr}, freed[2] = {nullptr, nullptr};
         char* d_out = nullptr;
@@ -5181,8 +5161,8 @@ static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch,
         if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "pipeline setup failed: %s", hipGetErrorString(e));
         if (rc == OSMT_OK) rc = render_impl(ctx, sc, 1u | 2u | 8u, nullptr, tile_bytes, false, s_k);
         uint32_t c = 0;
-        for (uint32_t first = 0; rc == OSMT_OK && first < batch->n_jobs; first += chunk, ++c) {
-            const uint32_t cnt = (uint32_t)std::min<size_t>(chunk, batch->n_jobs - first);
+        for (uint32_t first = 0; rc == OSMT_OK && first < n_jobs; first += chunk, ++c) {
+            const uint32_t cnt = (uint32_t)std::min<size_t>(chunk, n_jobs - first);
             const int k = (int)(c & 1u);
             char* dst = rgb ? d_rgb + (size_t)k * chunk * host_bytes : d_out + (size_t)k * chunk * tile_bytes;
             if (c >= 2) e = hipStreamWaitEvent(s_k, freed[k], 0);
@@ -5211,11 +5191,9 @@ static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch,
             if (done[k]) (void)hipEventDestroy(done[k]);
             if (freed[k]) (void)hipEventDestroy(freed[k]);
         }
-        osmt_scene_free(sc);
         dev_free(ctx, d_out);
         dev_free(ctx, d_rgb);
         stream_release(ctx, s_c);
-        stream_release(ctx, st);
         return rc;
     }
     void* d_out = nullptr;
@@ -5232,7 +5210,7 @@ static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch,
         const char* v = getenv("OSMT_ZERO_COPY_TILES");
         return (uint32_t)(v ? std::min(std::max(atoi(v), 0), 64) : 16);
     }();
-    if (batch->n_jobs && batch->n_jobs <= zc_max && ((uintptr_t)out_rgba & 3u) == 0u && (stride & 3u) == 0u) {
+    if (n_jobs && n_jobs <= zc_max && ((uintptr_t)out_rgba & 3u) == 0u && (stride & 3u) == 0u) {
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, out_rgba) == hipSuccess) {
             if (at.type == hipMemoryTypeHost && at.devicePointer) {
@@ -5243,32 +5221,87 @@ static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch,
             (void)hipGetLastError(); /* pageable memory: not an error */
         }
     }
-    if (batch->n_jobs && !zero_copy) {
-        hipError_t e = dev_alloc(ctx, &d_out, batch->n_jobs * host_bytes); /* RGB8: written by k_raster as packed triples */
-        if (e != hipSuccess) {
-            osmt_scene_free(sc);
-            stream_release(ctx, st);
-            return fail(OSMT_OOM, "hipMalloc(output) failed: %s", hipGetErrorString(e));
-        }
+    if (n_jobs && !zero_copy) {
+        hipError_t e = dev_alloc(ctx, &d_out, n_jobs * host_bytes); /* RGB8: written by k_raster as packed triples */
+        if (e != hipSuccess) return fail(OSMT_OOM, "hipMalloc(output) failed: %s", hipGetErrorString(e));
     }
     rc = render_impl(ctx, sc, 7u | (rgb ? 32u : 0u), d_out ? d_out : (void*)4, zero_copy ? stride : host_bytes, false, st);
-    if (rc == OSMT_OK && batch->n_jobs) {
+    if (rc == OSMT_OK && n_jobs) {
         hipError_t e = hipSuccess;
         const void* src = d_out;
         if (rc == OSMT_OK && e == hipSuccess && !zero_copy) {
             if (stride == host_bytes)
-                e = hipMemcpyAsync(out_rgba, src, batch->n_jobs * host_bytes, hipMemcpyDeviceToHost, st);
+                e = hipMemcpyAsync(out_rgba, src, n_jobs * host_bytes, hipMemcpyDeviceToHost, st);
             else
-                e = hipMemcpy2DAsync(out_rgba, stride, src, host_bytes, host_bytes, batch->n_jobs, hipMemcpyDeviceToHost, st);
+                e = hipMemcpy2DAsync(out_rgba, stride, src, host_bytes, host_bytes, n_jobs, hipMemcpyDeviceToHost, st);
         }
-        if (rc == OSMT_OK && e == hipSuccess) e = batch->n_jobs <= 64 ? stream_sync_small(st) : hipStreamSynchronize(st);
+        if (rc == OSMT_OK && e == hipSuccess) e = n_jobs <= 64 ? stream_sync_small(st) : hipStreamSynchronize(st);
         if (e != hipSuccess) rc = fail(OSMT_HIP_ERROR, "readback failed: %s", hipGetErrorString(e));
     }
     if (rc == OSMT_OK) rc = label_error_check(sc, st);
-    osmt_scene_free(sc); /* waits for the call's stream */
+    if (rc != OSMT_OK) { /* whatever was queued may still write d_out; keep the reason across the wait */
+        const std::string msg = osmt_last_error();
+        (void)hipStreamSynchronize(st);
+        rc = fail(rc, "%s", msg.c_str());
+    }
     if (!zero_copy) dev_free(ctx, d_out);
+    return rc;
+}
+
+static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba, size_t stride,
+                                         bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels,
+                                         const osmt_text_label_batch* tlabels, const osmt_string_label_batch* slabels) {
+    if (!ctx || !out_rgba) return fail(OSMT_INVALID_ARG, "NULL argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = nullptr; /* the whole call lives on its own stream: concurrent callers overlap on the GPU */
+    HIP_TRY(stream_acquire(ctx, &st));
+    osmt_scene* sc = nullptr;
+    int rc = scene_upload_impl(ctx, batch, &sc, st, trusted, allow_guess);
+    if (rc != OSMT_OK) {
+        stream_release(ctx, st);
+        return rc;
+    }
+    if (labels || glabels || tlabels || slabels) {
+        rc = labels ? osmt_scene_set_labels(ctx, sc, labels)
+                    : glabels ? osmt_scene_set_glyph_labels(ctx, sc, glabels)
+                              : tlabels ? osmt_scene_set_text_labels(ctx, sc, tlabels) : osmt_scene_set_string_labels(ctx, sc, slabels);
+        if (rc != OSMT_OK) {
+            osmt_scene_free(sc);
+            stream_release(ctx, st);
+            return rc;
+        }
+    }
+    rc = scene_render_host_back(ctx, sc, st, out_rgba, stride, rgb);
+    const std::string msg = rc != OSMT_OK ? std::string(osmt_last_error()) : std::string();
+    const bool missed = g_arena_guess_missed; /* set by the back half's error check; osmt_scene_free does not touch it */
+    osmt_scene_free(sc); /* waits for the call's stream */
+    stream_release(ctx, st);
+    g_arena_guess_missed = missed;
+    return rc != OSMT_OK ? fail(rc, "%s", msg.c_str()) : OSMT_OK;
+}
+
+/* osmt_render_scene_host: the same back half on a borrowed public scene. */
+static int osmt_render_scene_host_body(osmt_ctx* ctx, osmt_scene* sc, uint32_t format, uint8_t* out, size_t stride) {
+    if (!ctx || !sc || !out) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (sc->ctx != ctx) return fail(OSMT_INVALID_ARG, "the scene belongs to another context");
+    if (format != OSMT_PIXELS_RGBA8 && format != OSMT_PIXELS_RGB8) return fail(OSMT_INVALID_ARG, "unknown pixel format %u", format);
+    const bool rgb = format == OSMT_PIXELS_RGB8;
+    const size_t W = (size_t)OSMT_TILE_SIZE * sc->scale;
+    if (stride < W * W * (rgb ? 3u : 4u)) return fail(OSMT_INVALID_ARG, rgb ? "out_tile_stride_bytes < W*H*3" : "out_tile_stride_bytes < W*H*4");
+    if (rgb && ((stride & 3u) || ((uintptr_t)out & 3u))) return fail(OSMT_INVALID_ARG, "RGB8 output: pointer or tile stride not a multiple of 4");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = nullptr;
+    HIP_TRY(stream_acquire(ctx, &st));
+    int rc = OSMT_OK;
+    const hipError_t e = scene_wait_idle(sc); /* the pre-pass rewrites the scene's lists: its earlier launches first */
+    if (e != hipSuccess) rc = fail(OSMT_HIP_ERROR, "scene: %s", hipGetErrorString(e));
+    if (rc == OSMT_OK) rc = scene_render_host_back(ctx, sc, st, out, stride, rgb);
     stream_release(ctx, st);
     return rc;
+}
+
+int osmt_render_scene_host(osmt_ctx* ctx, osmt_scene* scene, uint32_t format, uint8_t* out, size_t out_tile_stride_bytes) {
+    return guarded([&] { return osmt_render_scene_host_body(ctx, scene, format, out, out_tile_stride_bytes); });
 }
 
 int osmt_render_batch_rgb(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgb, size_t stride) {
@@ -5341,6 +5374,7 @@ struct osmt_png_job {
     osmt_ctx* ctx = nullptr;
     hipStream_t st = nullptr, s_c = nullptr; /* the job's own stream; the compaction / read-back stream (more than one chunk) */
     osmt_scene* sc = nullptr;
+    bool owns_scene = true;    /* false: begun from the caller's scene (osmt_render_scene_png_begin), which outlives the job */
     char* d = nullptr;         /* framebuffers of two chunks, PNG slots, lengths, offsets */
     char* d_blob = nullptr;    /* compacted files, ONLY when a chunk's dead framebuffers cannot take them (see png_end_body) */
     uint32_t* h_len = nullptr; /* pinned: lengths come back asynchronously, offsets go out */
@@ -5358,7 +5392,12 @@ static void png_job_release(osmt_png_job* j) {
     osmt_ctx* ctx = j->ctx;
     for (hipEvent_t v : j->ev)
         if (v) (void)hipEventDestroy(v);
-    if (j->sc) osmt_scene_free(j->sc); /* waits for the job's stream */
+    if (j->sc && j->owns_scene) {
+        osmt_scene_free(j->sc); /* waits for the job's stream */
+    } else { /* a borrowed scene stays; the job's buffers and streams go back only once nothing queued can touch them */
+        if (j->s_c) (void)hipStreamSynchronize(j->s_c);
+        if (j->st) (void)hipStreamSynchronize(j->st);
+    }
     dev_free(ctx, j->d);
     dev_free(ctx, j->d_blob);
     if (j->h_len) stage_release(ctx, j->h_len);
@@ -5371,12 +5410,8 @@ static void png_job_release(osmt_png_job* j) {
     ctx_release(ctx);
 }
 
-/* First half.  The pre-pass runs once for the whole batch; then the tiles go through raster -> PNG encode -> file lengths
- * in CHUNKS on the job's stream, all enqueued here; nothing is waited for. */
-static int png_begin_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, osmt_png_job** out_job, bool allow_guess = true) {
-    if (!ctx || !out_job) return fail(OSMT_INVALID_ARG, "NULL argument");
-    *out_job = nullptr;
-    HIP_TRY(hipSetDevice(ctx->device));
+/* A job with its context reference and its own stream, nothing else yet. */
+static int png_job_new(osmt_ctx* ctx, osmt_png_job** out) {
     osmt_png_job* j = new (std::nothrow) osmt_png_job();
     if (!j) return fail(OSMT_OOM, "out of host memory");
     j->ctx = ctx;
@@ -5387,17 +5422,23 @@ static int png_begin_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_lab
         ctx_release(ctx);
         return fail(OSMT_HIP_ERROR, "stream: %s", hipGetErrorString(e));
     }
-    j->batch = batch;
-    j->labels = labels;
-    int rc = scene_upload_impl(ctx, batch, &j->sc, j->st, false, allow_guess);
-    if (rc == OSMT_OK && labels) rc = osmt_scene_set_labels(ctx, j->sc, labels);
-    const uint32_t n = j->n = batch ? (uint32_t)batch->n_jobs : 0u;
-    if (rc == OSMT_OK && n) {
-        const uint32_t W = j->W = OSMT_TILE_SIZE * batch->scale;
+    *out = j;
+    return OSMT_OK;
+}
+
+/* The back half of both _begin forms, where the scene exists (j->sc: the batch form's own, or the caller's): the pre-pass
+ * once, then the tiles through raster -> PNG encode -> file lengths in CHUNKS on the job's stream, all enqueued here;
+ * nothing is waited for. */
+static int png_begin_back(osmt_ctx* ctx, osmt_png_job* j) {
+    int rc = OSMT_OK;
+    hipError_t e = hipSuccess;
+    const uint32_t n = j->n = j->sc->n_jobs, scale = j->sc->scale;
+    if (n) {
+        const uint32_t W = j->W = OSMT_TILE_SIZE * scale;
         const size_t tile_bytes = (size_t)W * W * 4, slot = j->slot = osmt_png_device_bound(W, W);
         /* the encoder is one workgroup per tile: below ~2 workgroups per CU it is latency-bound and a chunk costs more than
          * its overlap brings (measured on 1024 tiles: 1 chunk 4.21 ms, 2 chunks 4.10, 4 chunks 4.82, 8 chunks 7.07) */
-        const uint32_t min_chunk = std::max<uint32_t>(1u, 512u / (batch->scale * batch->scale));
+        const uint32_t min_chunk = std::max<uint32_t>(1u, 512u / (scale * scale));
         uint32_t chunk = n;
         if (n >= 2u * min_chunk) chunk = std::max<uint32_t>(min_chunk, (n + 1u) / 2u);
         /* OSMT_PNG_CHUNKS (diagnostic: force the number of chunks): read ONCE — getenv on every call from worker threads is
@@ -5452,6 +5493,47 @@ static int png_begin_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_lab
             }
         }
     }
+    return rc;
+}
+
+/* First half of the batch form: validate, upload, attach the labels, then the shared back half. */
+static int png_begin_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, osmt_png_job** out_job, bool allow_guess = true) {
+    if (!ctx || !out_job) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *out_job = nullptr;
+    HIP_TRY(hipSetDevice(ctx->device));
+    osmt_png_job* j = nullptr;
+    int rc = png_job_new(ctx, &j);
+    if (rc != OSMT_OK) return rc;
+    j->batch = batch;
+    j->labels = labels;
+    rc = scene_upload_impl(ctx, batch, &j->sc, j->st, false, allow_guess);
+    if (rc == OSMT_OK && labels) rc = osmt_scene_set_labels(ctx, j->sc, labels);
+    if (rc == OSMT_OK) rc = png_begin_back(ctx, j);
+    if (rc != OSMT_OK) {
+        const std::string msg = osmt_last_error();
+        png_job_release(j);
+        return fail(rc, "%s", msg.c_str());
+    }
+    *out_job = j;
+    return OSMT_OK;
+}
+
+/* First half of the scene form.  The scene is borrowed: the job waits for the scene's earlier launches (the pre-pass rewrites
+ * its lists — a second job on the same scene is therefore serialised behind the first one's raster), marks its own (render_impl)
+ * and never frees it. */
+static int scene_png_begin_body(osmt_ctx* ctx, osmt_scene* sc, osmt_png_job** out_job) {
+    if (out_job) *out_job = nullptr;
+    if (!ctx || !sc || !out_job) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (sc->ctx != ctx) return fail(OSMT_INVALID_ARG, "the scene belongs to another context");
+    HIP_TRY(hipSetDevice(ctx->device));
+    osmt_png_job* j = nullptr;
+    int rc = png_job_new(ctx, &j);
+    if (rc != OSMT_OK) return rc;
+    j->sc = sc;
+    j->owns_scene = false;
+    const hipError_t e = scene_wait_idle(sc);
+    if (e != hipSuccess) rc = fail(OSMT_HIP_ERROR, "scene: %s", hipGetErrorString(e));
+    if (rc == OSMT_OK) rc = png_begin_back(ctx, j);
     if (rc != OSMT_OK) {
         const std::string msg = osmt_last_error();
         png_job_release(j);
@@ -5535,7 +5617,7 @@ static int png_end_body(osmt_png_job* j, uint8_t* out_png, size_t out_capacity, 
     g_arena_guess_missed = false;
     if (rc == OSMT_OK) rc = label_error_check(j->sc, j->st);
     const std::string msg = rc != OSMT_OK ? std::string(osmt_last_error()) : std::string();
-    const bool missed = rc != OSMT_OK && g_arena_guess_missed;
+    const bool missed = rc != OSMT_OK && g_arena_guess_missed && j->owns_scene; /* public scenes are sized exactly: no retry */
     const osmt_batch* batch = j->batch;
     const osmt_label_batch* labels = j->labels;
     png_job_release(j);
@@ -5567,6 +5649,91 @@ int osmt_render_batch_png(osmt_ctx* ctx, const osmt_batch* batch, const osmt_lab
         if (rc != OSMT_OK) return rc;
         return png_end_body(j, out_png, out_capacity, out_off);
     });
+}
+
+int osmt_render_scene_png_begin(osmt_ctx* ctx, osmt_scene* scene, osmt_png_job** out_job) {
+    return guarded([&] { return scene_png_begin_body(ctx, scene, out_job); });
+}
+
+/* One call = begin + end, as the batch form. */
+int osmt_render_scene_png(osmt_ctx* ctx, osmt_scene* scene, uint8_t* out_png, size_t out_capacity, uint64_t* out_off) {
+    return guarded([&] {
+        if (!ctx || !scene || !out_off || (!out_png && out_capacity)) return fail(OSMT_INVALID_ARG, "NULL argument");
+        osmt_png_job* j = nullptr;
+        const int rc = scene_png_begin_body(ctx, scene, &j);
+        if (rc != OSMT_OK) return rc;
+        return png_end_body(j, out_png, out_capacity, out_off);
+    });
+}
+
+/* ---- the device form: everything on the caller's stream ---- */
+namespace {
+struct scene_png_work {
+    size_t o_rgba = 0, o_png = 0, o_len = 0, bytes = 0, tile_bytes = 0, slot = 0;
+};
+void scene_png_work_layout(const osmt_scene* sc, scene_png_work& w) {
+    const size_t W = (size_t)OSMT_TILE_SIZE * sc->scale, n = sc->n_jobs;
+    w.tile_bytes = W * W * 4;
+    w.slot = osmt_png_device_bound((uint32_t)W, (uint32_t)W);
+    w.o_rgba = 0;
+    w.o_png = align_up(n * w.tile_bytes, 256);
+    w.o_len = w.o_png + align_up(n * w.slot, 256);
+    w.bytes = w.o_len + align_up(n * 4, 256);
+}
+}  // namespace
+
+size_t osmt_scene_png_work_bytes(osmt_ctx* ctx, osmt_scene* scene) {
+    if (!ctx || !scene || scene->ctx != ctx) return 0;
+    scene_png_work w;
+    scene_png_work_layout(scene, w);
+    return w.bytes;
+}
+
+static int scene_png_device_body(osmt_ctx* ctx, osmt_scene* sc, void* d_work, size_t work_bytes, void* d_png, size_t png_capacity,
+                                 uint64_t* d_off, uint32_t* d_status, void* stream) {
+    if (!ctx || !sc || !d_off || !d_status) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (sc->ctx != ctx) return fail(OSMT_INVALID_ARG, "the scene belongs to another context");
+    scene_png_work w;
+    scene_png_work_layout(sc, w);
+    const uint32_t n = sc->n_jobs;
+    if (n && !d_work) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (!d_png && png_capacity) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (work_bytes < w.bytes) return fail(OSMT_INVALID_ARG, "work_bytes %zu < osmt_scene_png_work_bytes() = %zu", work_bytes, w.bytes);
+    if (((uintptr_t)d_work & 255u) || ((uintptr_t)d_off & 7u) || ((uintptr_t)d_status & 3u))
+        return fail(OSMT_INVALID_ARG, "d_work must be aligned to 256 bytes, d_off to 8, d_status to 4");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    char* const d = (char*)d_work;
+    uint32_t* const d_len = (uint32_t*)(d + w.o_len);
+    if (n) {
+        const uint32_t W = OSMT_TILE_SIZE * sc->scale;
+        int rc = render_impl(ctx, sc, 7u, d + w.o_rgba, w.tile_bytes, false, stream);
+        if (rc == OSMT_OK) rc = osmt_encode_png_device(ctx, d + w.o_rgba, w.tile_bytes, n, W, W, d + w.o_png, w.slot, d_len, stream);
+        if (rc != OSMT_OK) return rc;
+    }
+    HIP_TRY(osmt_launch_png_offsets(d_len, n, png_capacity, (unsigned long long*)d_off, d_status, st));
+    HIP_TRY(osmt_launch_png_compact(d + w.o_png, w.slot, d_len, (const unsigned long long*)d_off, n, d_png, st, d_status));
+    return OSMT_OK;
+}
+
+int osmt_render_scene_png_device(osmt_ctx* ctx, osmt_scene* scene, void* d_work, size_t work_bytes, void* d_png, size_t png_capacity,
+                                 uint64_t* d_off, uint32_t* d_status, void* stream) {
+    return guarded([&] { return scene_png_device_body(ctx, scene, d_work, work_bytes, d_png, png_capacity, d_off, d_status, stream); });
+}
+
+static int debug_png_offsets_body(osmt_ctx* ctx, const uint32_t* d_len, uint32_t n, uint64_t capacity, uint64_t* d_off, uint32_t* d_status,
+                                  void* stream) {
+    if (!ctx || !d_off || !d_status || (n && !d_len)) return fail(OSMT_INVALID_ARG, "NULL argument");
+    if (n > 0x80000000u) return fail(OSMT_INVALID_ARG, "more than 2^31 lengths");
+    if (((uintptr_t)d_len & 3u) || ((uintptr_t)d_off & 7u) || ((uintptr_t)d_status & 3u)) return fail(OSMT_INVALID_ARG, "misaligned device pointer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(osmt_launch_png_offsets(d_len, n, capacity, (unsigned long long*)d_off, d_status, (hipStream_t)stream));
+    return OSMT_OK;
+}
+
+int osmt_debug_png_offsets(osmt_ctx* ctx, const uint32_t* d_len, uint32_t n, uint64_t capacity, uint64_t* d_off, uint32_t* d_status,
+                           void* stream) {
+    return guarded([&] { return debug_png_offsets_body(ctx, d_len, n, capacity, d_off, d_status, stream); });
 }
 
 static int osmt_host_alloc_body(osmt_ctx* ctx, size_t bytes, void** out) {

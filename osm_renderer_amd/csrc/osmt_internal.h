@@ -927,8 +927,12 @@ hipError_t osmt_launch_hypot(const double* xy, uint32_t n, double* out, hipStrea
 /* RGBA8 framebuffers -> complete RGB8 PNG files, one per tile, out_len[i] bytes at out + i * out_stride */
 hipError_t osmt_launch_png(const void* rgba, size_t tile_stride, uint32_t n, uint32_t W, uint32_t H, uint32_t ihdr_crc, void* out,
                            size_t out_stride, uint32_t* out_len, hipStream_t st);
+/* status != NULL: the guarded form, which writes nothing when *status (device memory, set earlier on `st`) is not 0 */
 hipError_t osmt_launch_png_compact(const void* slots, size_t slot_stride, const uint32_t* len, const unsigned long long* off, uint32_t n,
-                                   void* blob, hipStream_t st);
+                                   void* blob, hipStream_t st, const uint32_t* status = nullptr);
+/* exclusive 64-bit scan of n <= 2^31 lengths into off[0 .. n]; *status = off[n] > capacity */
+hipError_t osmt_launch_png_offsets(const uint32_t* len, uint32_t n, unsigned long long capacity, unsigned long long* off, uint32_t* status,
+                                   hipStream_t st);
 hipError_t osmt_launch_copy16(const void* src, void* dst, size_t n16, bool read_only, hipStream_t st);
 hipError_t osmt_launch_composite(const void* planes, const double canvas[4], uint32_t n, uint32_t L, uint32_t npx,
                                  void* out, hipStream_t st);

@@ -860,12 +860,16 @@ __global__ __launch_bounds__(PNG_NT) __attribute__((amdgpu_waves_per_eu(PX == 4 
     }
 }
 
-/* gathers the variable-length PNG files of a batch into one blob: tile i -> blob[off[i] .. off[i] + len[i]) */
+/* gathers the variable-length PNG files of a batch into one blob: tile i -> blob[off[i] .. off[i] + len[i]).
+ * GUARDED (osmt_render_scene_png_device: the offsets come from k_png_offsets on the same stream, nobody has compared them with
+ * the blob's capacity on the host): a non-zero *status means the files do not fit, and nothing is written. */
+template <bool GUARDED>
 __global__ __launch_bounds__(256) void k_png_compact(const uint8_t* __restrict__ slots, size_t slot_stride,
                                                      const uint32_t* __restrict__ len, const unsigned long long* __restrict__ off,
-                                                     uint32_t n, uint8_t* __restrict__ blob) {
+                                                     uint32_t n, uint8_t* __restrict__ blob, const uint32_t* __restrict__ status) {
     const uint32_t tile = blockIdx.x;
     if (tile >= n) return;
+    if (GUARDED && *status != 0u) return;
     const uint8_t* __restrict__ src = slots + (size_t)tile * slot_stride;
     uint8_t* __restrict__ dst = blob + off[tile];
     const uint32_t L = len[tile];
@@ -873,10 +877,61 @@ __global__ __launch_bounds__(256) void k_png_compact(const uint8_t* __restrict__
 }
 
 hipError_t osmt_launch_png_compact(const void* slots, size_t slot_stride, const uint32_t* len, const unsigned long long* off, uint32_t n,
-                                   void* blob, hipStream_t st) {
+                                   void* blob, hipStream_t st, const uint32_t* status) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_png_compact, dim3(n), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(slots), slot_stride, len, off, n,
-                       reinterpret_cast<uint8_t*>(blob));
+    if (status)
+        hipLaunchKernelGGL((k_png_compact<true>), dim3(n), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(slots), slot_stride, len, off, n,
+                           reinterpret_cast<uint8_t*>(blob), status);
+    else
+        hipLaunchKernelGGL((k_png_compact<false>), dim3(n), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(slots), slot_stride, len, off, n,
+                           reinterpret_cast<uint8_t*>(blob), (const uint32_t*)nullptr);
+    return hipGetLastError();
+}
+
+/* File offsets on the device: the exclusive 64-bit scan of n 32-bit lengths into n + 1 offsets, so that a caller who stays on
+ * its stream gets one contiguous run of files without a round trip through the host.  ONE workgroup walks n in passes of
+ * OSMT_PNG_OFFSETS_GROUP lengths and carries the running total (64 bits: 2^14 files of 296 KB already pass 2^32) from pass to
+ * pass in a register every thread holds alike.  Inside a wave the inclusive prefix goes by cross-lane shifts, the four wave totals
+ * meet in LDS; no atomics.  status: 0, or 1 when off[n] > capacity — the offsets are complete either way. */
+#define PNG_SCAN_NT 256u
+static_assert(PNG_SCAN_NT == OSMT_PNG_OFFSETS_GROUP, "include/osmtile.h documents the workgroup's width");
+__global__ __launch_bounds__(PNG_SCAN_NT) void k_png_offsets(const uint32_t* __restrict__ len, uint32_t n, unsigned long long capacity,
+                                                             unsigned long long* __restrict__ off, uint32_t* __restrict__ status) {
+    __shared__ unsigned long long sh_wave[PNG_SCAN_NT / 64u];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    unsigned long long carry = 0ull;
+    for (uint32_t base = 0u; base < n; base += PNG_SCAN_NT) { /* n <= 2^31 (the launcher): base + tid cannot wrap */
+        const uint32_t i = base + tid;
+        const unsigned long long v = i < n ? (unsigned long long)len[i] : 0ull;
+        unsigned long long incl = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long t = __shfl_up(incl, d);
+            if ((int)lane >= d) incl += t;
+        }
+        if (lane == 63u) sh_wave[wave] = incl;
+        __syncthreads();
+        unsigned long long below = 0ull, total = 0ull;
+#pragma unroll
+        for (uint32_t w = 0u; w < PNG_SCAN_NT / 64u; ++w) {
+            const unsigned long long s = sh_wave[w];
+            if (w < wave) below += s;
+            total += s;
+        }
+        if (i < n) off[i] = carry + below + incl - v;
+        carry += total;
+        __syncthreads(); /* the next pass writes sh_wave again */
+    }
+    if (tid == 0u) {
+        off[n] = carry;
+        *status = carry > capacity ? 1u : 0u;
+    }
+}
+
+hipError_t osmt_launch_png_offsets(const uint32_t* len, uint32_t n, unsigned long long capacity, unsigned long long* off, uint32_t* status,
+                                   hipStream_t st) {
+    if (n > 0x80000000u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_png_offsets, dim3(1), dim3(PNG_SCAN_NT), 0, st, len, n, capacity, off, status);
     return hipGetLastError();
 }
 

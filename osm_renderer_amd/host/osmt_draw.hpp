@@ -147,22 +147,55 @@ class Context {
         check(osmt_register_label_bindings(ctx_, &desc, &id));
         return id;
     }
+    /* tile coordinates in, PNG files out (defined behind TileScene) */
+    template <class HostAnchor>
+    std::vector<std::vector<uint8_t>> render_tiles_png(const osmt_tile_batch& batch, const uint32_t* area_bindings_of_zoom,
+                                                       const uint32_t* node_bindings_of_zoom, HostAnchor host_anchor);
 
   private:
     osmt_ctx* ctx_ = nullptr;
 };
 
+/* Host output of any scene (osmt_render_scene_png / osmt_render_scene_host): what the scene classes below share.  The scene
+ * is borrowed: it renders the same afterwards. */
+inline std::vector<std::vector<uint8_t>> scene_render_png(osmt_ctx* ctx, osmt_scene* scene, size_t n_tiles, uint32_t scale) {
+    const uint32_t dim = TILE_SIZE * scale;
+    std::vector<uint8_t> blob(n_tiles * osmt_png_device_bound(dim, dim)); /* the worst case: the call cannot come back short */
+    std::vector<uint64_t> off(n_tiles + 1, 0);
+    check(osmt_render_scene_png(ctx, scene, blob.data(), blob.size(), off.data()));
+    std::vector<std::vector<uint8_t>> files(n_tiles);
+    for (size_t i = 0; i < n_tiles; ++i) files[i].assign(blob.begin() + (ptrdiff_t)off[i], blob.begin() + (ptrdiff_t)off[i + 1]);
+    return files;
+}
+/* packed RGB8 (the memory of RgbTriples), or RGBA8 with rgb = false; tile i at [i * dim * dim * (3 or 4)) */
+inline std::vector<uint8_t> scene_render_host(osmt_ctx* ctx, osmt_scene* scene, size_t n_tiles, uint32_t scale, bool rgb) {
+    const size_t dim = (size_t)TILE_SIZE * scale, stride = dim * dim * (rgb ? 3 : 4);
+    std::vector<uint8_t> out(n_tiles * stride + 4); /* never empty; operator new aligns far beyond the 4 bytes RGB8 asks for */
+    check(osmt_render_scene_host(ctx, scene, rgb ? OSMT_PIXELS_RGB8 : OSMT_PIXELS_RGBA8, out.data(), stride));
+    out.resize(n_tiles * stride);
+    return out;
+}
+
 /* A scene whose display list the GPU built from a styled batch (osmt_scene_build_styled): what SceneBuilder::add_tile per
- * tile + osmt_scene_upload give, from 8 bytes per styled area.  Render it with osmt_render_scene on raw(). */
+ * tile + osmt_scene_upload give, from 8 bytes per styled area.  Render it with osmt_render_scene on raw(), or straight to
+ * files / host pixels with render_png() / render_host(). */
 class StyledScene {
   public:
-    StyledScene(Context& ctx, const osmt_styled_batch& batch) { check(osmt_scene_build_styled(ctx.raw(), &batch, &scene_)); }
+    StyledScene(Context& ctx, const osmt_styled_batch& batch) : ctx_(&ctx), n_tiles_(batch.n_tiles), scale_(batch.scale) {
+        check(osmt_scene_build_styled(ctx.raw(), &batch, &scene_));
+    }
     ~StyledScene() { osmt_scene_free(scene_); }
     StyledScene(const StyledScene&) = delete;
     StyledScene& operator=(const StyledScene&) = delete;
     osmt_scene* raw() const { return scene_; }
+    size_t tile_count() const { return n_tiles_; }
+    std::vector<std::vector<uint8_t>> render_png() const { return scene_render_png(ctx_->raw(), scene_, n_tiles_, scale_); }
+    std::vector<uint8_t> render_host(bool rgb = true) const { return scene_render_host(ctx_->raw(), scene_, n_tiles_, scale_, rgb); }
 
   private:
+    Context* ctx_;
+    size_t n_tiles_;
+    uint32_t scale_;
     osmt_scene* scene_ = nullptr;
 };
 
@@ -186,7 +219,9 @@ struct TileAreaLabels : TileLabels {
  * and assembled on the GPU, the caller's way and multipolygon labels are drawn in front of them (drawer.rs:229-261). */
 class TileScene {
   public:
-    TileScene(Context& ctx, const osmt_tile_batch& batch) : ctx_(&ctx), n_tiles_(batch.n_tiles) { check(osmt_scene_build_tiles(ctx.raw(), &batch, &scene_)); }
+    TileScene(Context& ctx, const osmt_tile_batch& batch) : ctx_(&ctx), n_tiles_(batch.n_tiles), scale_(batch.scale) {
+        check(osmt_scene_build_tiles(ctx.raw(), &batch, &scene_));
+    }
     ~TileScene() { osmt_scene_free(scene_); }
     TileScene(const TileScene&) = delete;
     TileScene& operator=(const TileScene&) = delete;
@@ -224,6 +259,10 @@ class TileScene {
             anchors.swap(merged);
         }
     }
+    /* Drawer::draw_tile's tail for every tile of the scene (drawer.rs:48-57): the PNG files, written by the GPU — with whatever
+     * labels are attached; and the pixels themselves in host memory */
+    std::vector<std::vector<uint8_t>> render_png() const { return scene_render_png(ctx_->raw(), scene_, n_tiles_, scale_); }
+    std::vector<uint8_t> render_host(bool rgb = true) const { return scene_render_host(ctx_->raw(), scene_, n_tiles_, scale_, rgb); }
     /* the area batch the device built, before the splice */
     TileAreaLabels read_tile_area_labels() const {
         TileAreaLabels out;
@@ -248,8 +287,20 @@ class TileScene {
   private:
     Context* ctx_;
     size_t n_tiles_;
+    uint32_t scale_;
     osmt_scene* scene_ = nullptr;
 };
+
+/* Drawer::draw_tile (drawer.rs:40-58) for tile coordinates, in one call: build the scenes of `batch`, label them from the
+ * registered bindings (nullptr: none of that kind; host_anchor as in TileScene::build_all_labels), render, PNG files out —
+ * file i belongs to batch.tiles[i]. */
+template <class HostAnchor>
+inline std::vector<std::vector<uint8_t>> Context::render_tiles_png(const osmt_tile_batch& batch, const uint32_t* area_bindings_of_zoom,
+                                                                   const uint32_t* node_bindings_of_zoom, HostAnchor host_anchor) {
+    TileScene scene(*this, batch);
+    if (area_bindings_of_zoom || node_bindings_of_zoom) scene.build_all_labels(area_bindings_of_zoom, node_bindings_of_zoom, host_anchor);
+    return scene.render_png();
+}
 
 struct Filler { /* fill.rs:11-14 */
     enum Kind { ColorFill, ImageFill } kind;

@@ -51,6 +51,8 @@ EXPORTS = [
     "osmt_validate_class_label_bindings", "osmt_register_label_bindings_matched", "osmt_register_area_label_bindings_matched",
     "osmt_read_label_bindings", "osmt_read_area_label_bindings",
     "osmt_validate_rules", "osmt_register_rules", "osmt_validate_rules_ex", "osmt_register_rules_ex", "osmt_cascade_classes", "osmt_cascade_free", "osmt_cascade_read", "osmt_cascade_register",
+    "osmt_render_scene_host", "osmt_render_scene_png", "osmt_render_scene_png_begin", "osmt_scene_png_work_bytes",
+    "osmt_render_scene_png_device", "osmt_debug_png_offsets",
 ]
 
 
@@ -225,6 +227,14 @@ def load():
         L.osmt_label_positions_tiles.argtypes = [vp, C.POINTER(abi.LabelTileBatch), vp]
         L.osmt_label_positions_tiles_begin.argtypes = [vp, C.POINTER(abi.LabelTileBatch), C.POINTER(vp)]
         L.osmt_label_tile_batch_expand.argtypes = [vp, C.POINTER(abi.LabelTileBatch), vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "osmt_render_scene_png"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_render_scene_host.argtypes = [vp, vp, C.c_uint32, vp, C.c_size_t]
+        L.osmt_render_scene_png.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_uint64)]
+        L.osmt_render_scene_png_begin.argtypes = [vp, vp, C.POINTER(vp)]
+        L.osmt_scene_png_work_bytes.argtypes = [vp, vp]
+        L.osmt_scene_png_work_bytes.restype = C.c_size_t
+        L.osmt_render_scene_png_device.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
+        L.osmt_debug_png_offsets.argtypes = [vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

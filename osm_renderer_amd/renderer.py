@@ -30,6 +30,15 @@ def _stream_ptr(stream=None):
     return C.c_void_p(s.cuda_stream)
 
 
+def scene_png_work_layout(n_tiles, dim):
+    """The d_work buffer of osmt_render_scene_png_device for n_tiles tiles of dim x dim pixels, as include/osmtile.h
+    documents it: (framebuffer offset, slot offset, length offset, total bytes).  No device needed."""
+    up = lambda v: (v + 255) // 256 * 256
+    o_png = up(n_tiles * dim * dim * 4)
+    o_len = o_png + up(n_tiles * load().osmt_png_device_bound(dim, dim))
+    return 0, o_png, o_len, o_len + up(n_tiles * 4)
+
+
 class Scene:
     """A display-list batch resident in HBM (osmt_scene)."""
 
@@ -325,10 +334,14 @@ class PngJob:
     """A begun osmt_render_batch_png job.  Holds the display list (and labels) alive — the uploads are stream-ordered —
     and the native handle exactly once: png_end() takes it (the native call frees the job whatever it returns), a second
     png_end() raises instead of touching freed memory, and a job that is dropped without being ended is ended here with an
-    empty buffer, which releases its device buffers (about 0.9 GB per 1024 tiles)."""
+    empty buffer, which releases its device buffers (about 0.9 GB per 1024 tiles).
 
-    def __init__(self, h, dl, labels, b, lb):
-        self._h, self.dl, self.labels, self._b, self._lb = h, dl, labels, b, lb
+    A job of Context.scene_png_begin holds its Scene alive instead (`scene`; `dl` is None): the native job borrows the scene,
+    which must not be freed before the job is ended."""
+
+    def __init__(self, h, dl, labels, b, lb, scene=None):
+        self._h, self.dl, self.labels, self._b, self._lb, self.scene = h, dl, labels, b, lb, scene
+        self.n_jobs = scene.n_jobs if scene is not None else dl.n_jobs
 
     def take(self):
         if self._h is None:
@@ -340,7 +353,7 @@ class PngJob:
         """Ends the job without reading the files back (frees its device buffers)."""
         if self._h is not None:
             h, self._h = self._h, None
-            off = (C.c_uint64 * (self.dl.n_jobs + 1))()
+            off = (C.c_uint64 * (self.n_jobs + 1))()
             load().osmt_render_batch_png_end(h, None, 0, off)
 
     def __del__(self):
@@ -845,12 +858,73 @@ class Context:
 
         The native call frees the job WHATEVER it returns (include/osmtile.h): a job can be ended once.  A buffer that
         turns out too small therefore needs a new png_begin — size `out` with osmt_png_device_bound x tiles and it cannot."""
-        h, dl = job.take(), job.dl
-        off = np.zeros(dl.n_jobs + 1, dtype=np.uint64)
+        h, n = job.take(), job.n_jobs
+        off = np.zeros(n + 1, dtype=np.uint64)
+        job.offsets = off  # filled even when the call fails because `out` is too small: off[n] is the size needed
         check(load().osmt_render_batch_png_end(h, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, off.ctypes.data_as(C.POINTER(C.c_uint64))))
         if not as_bytes:
             return out, off
-        return [out[int(off[i]) : int(off[i + 1])].tobytes() for i in range(dl.n_jobs)]
+        return [out[int(off[i]) : int(off[i + 1])].tobytes() for i in range(n)]
+
+    # -- host pixels and PNG files from any scene -----------------------------------
+    def render_scene_host(self, scene: Scene, rgb=False, out=None, stride=None):
+        """osmt_render_scene_host: the scene's tiles as host pixels — RGBA8 [n, W, W, 4], or with rgb=True packed RGB8
+        [n, stride].  `out`: a uint8 array to fill (e.g. host_alloc()); `stride`: bytes from tile to tile (default: tight)."""
+        tight = scene.dim * scene.dim * (3 if rgb else 4)
+        stride = tight if stride is None else stride
+        if out is None:
+            out = np.empty((scene.n_jobs, scene.dim, scene.dim, 4) if (not rgb and stride == tight) else (scene.n_jobs, stride), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size >= scene.n_jobs * stride
+        check(load().osmt_render_scene_host(self._h, scene._h, abi.PIXELS_RGB8 if rgb else abi.PIXELS_RGBA8, C.c_void_p(out.ctypes.data), stride))
+        return out
+
+    def render_scene_png(self, scene: Scene, out=None, as_bytes=True):
+        """osmt_render_scene_png: the scene's tiles as PNG files (list of bytes); as_bytes=False returns (out, offsets)."""
+        n = scene.n_jobs
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if out is None:
+            out = np.empty(max(1, n * load().osmt_png_device_bound(scene.dim, scene.dim)), dtype=np.uint8)
+        check(load().osmt_render_scene_png(self._h, scene._h, C.c_void_p(out.ctypes.data), out.size, off.ctypes.data_as(C.POINTER(C.c_uint64))))
+        if not as_bytes:
+            return out, off
+        return [out[int(off[i]) : int(off[i + 1])].tobytes() for i in range(n)]
+
+    def scene_png_begin(self, scene: Scene):
+        """osmt_render_scene_png_begin: queues the scene's tiles, returns a PngJob for png_end (the job keeps `scene` alive)."""
+        h = C.c_void_p()
+        check(load().osmt_render_scene_png_begin(self._h, scene._h, C.byref(h)))
+        return PngJob(h, None, None, None, None, scene=scene)
+
+    def render_scene_png_device(self, scene: Scene, png=None, work=None, stream=None):
+        """osmt_render_scene_png_device, all on `stream`, nothing waited for: (png uint8 cuda tensor, offsets int64 cuda
+        tensor [n + 1], status int32 cuda tensor [1]).  `png`: the tensor to receive the files back to back (default: the
+        worst case); status 1 = it was too small, nothing written, the offsets complete."""
+        torch = _torch()
+        n = scene.n_jobs
+        need = load().osmt_scene_png_work_bytes(self._h, scene._h)
+        if work is None:
+            work = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
+        if png is None:
+            png = torch.empty((max(1, n * load().osmt_png_device_bound(scene.dim, scene.dim)),), dtype=torch.uint8, device=self.device)
+        assert png.is_cuda and png.dtype == torch.uint8 and png.is_contiguous() and work.is_cuda and work.dtype == torch.uint8
+        off = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+        status = torch.empty((1,), dtype=torch.int32, device=self.device)
+        check(load().osmt_render_scene_png_device(self._h, scene._h, C.c_void_p(work.data_ptr()), work.numel(), C.c_void_p(png.data_ptr()),
+                                                  png.numel(), C.c_void_p(off.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+        self._png_work = work  # stream-ordered use: stays alive until the next call replaces it
+        return png, off, status
+
+    def debug_png_offsets(self, lengths, capacity, stream=None):
+        """osmt_debug_png_offsets: the offset scan alone on an int32 / uint32 cuda tensor of lengths (read as uint32):
+        (offsets int64 [n + 1], status int32 [1]), queued on `stream`."""
+        torch = _torch()
+        assert lengths.is_cuda and lengths.is_contiguous() and lengths.element_size() == 4
+        n = lengths.numel()
+        off = torch.empty((n + 1,), dtype=torch.int64, device=lengths.device)
+        status = torch.full((1,), -1, dtype=torch.int32, device=lengths.device)
+        check(load().osmt_debug_png_offsets(self._h, C.c_void_p(lengths.data_ptr()) if n else None, n, int(capacity), C.c_void_p(off.data_ptr()),
+                                            C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+        return off, status
 
     def hbm_copy_probe(self, nbytes=1 << 30, iters=20):
         """osmt_hbm_copy_probe: (copy GB/s counting read + write, read-only GB/s) of a 16-byte-per-lane device stream."""
