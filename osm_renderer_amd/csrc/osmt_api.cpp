@@ -29,6 +29,7 @@
 #include "osmt_cascade_tables.h" /* the tables of a rule set: osmt_cs_resolve */
 #include "osmt_geom.h"
 #include "osmt_internal.h"
+#include "osmt_pool_layout.h"
 #include "osmt_numparse.h" /* osmt_bytes_cmp: the key order of osmt_validate_tags */
 #include "osmt_utf8.h"     /* the byte a refused tag value stops the decoder at */
 #include "osmt_png_table.h" /* PNG_LMAX, PNG_BLOCK_HDR_BITS: the slot bound */
@@ -36,6 +37,8 @@
 #include "../host/osmt_textshaper.hpp" /* osmt::validate_font, osmt::validate_string_labels */
 
 namespace {
+
+using osmt_host::pool_layout;
 
 thread_local std::string g_last_error;
 
@@ -550,6 +553,138 @@ void dev_free(osmt_ctx* ctx, void* p) {
     }
 }
 
+/* ---- a registered table on its way to the device ---- */
+struct table_upload {
+    char* pool = nullptr;
+    /* one device allocation that never moves once it is registered; a failure is remembered and skips the copies */
+    table_upload(const char* name, const pool_layout& pl) : name_(name) {
+        const hipError_t e = hipMalloc((void**)&pool, pl.size());
+        if (e == hipSuccess) return;
+        pool = nullptr;
+        rc_ = fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the %s failed: %s", pl.size(), name, hipGetErrorString(e));
+    }
+    table_upload(const table_upload&) = delete;
+    table_upload& operator=(const table_upload&) = delete;
+    ~table_upload() {
+        if (pool) (void)hipFree(pool);
+    }
+    /* blocking copies; after the first error the others are skipped */
+    void put(size_t o, const void* src, size_t bytes) {
+        if (rc_ != OSMT_OK || !bytes) return;
+        const hipError_t e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc_ = fail(OSMT_HIP_ERROR, "%s upload failed: %s", name_, hipGetErrorString(e)); /* every table says so, OOM or not */
+    }
+    /* OSMT_OK, or what the first failure reported */
+    int done() const { return rc_; }
+    /* registered: the context owns the allocation from here on */
+    void release() { pool = nullptr; }
+
+   private:
+    const char* name_;
+    int rc_ = OSMT_OK;
+};
+
+/* ---- what a per-call GPU pipeline holds while it runs ---- */
+bool trace_upload() {
+    static const bool v = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    return v;
+}
+
+struct call_work {
+    enum { MAX_WORK = 8, MAX_EV = 12 };
+    osmt_ctx* ctx;
+    hipStream_t st = nullptr;
+    char* work[MAX_WORK] = {}; /* dev_alloc buffers, given back at the end */
+    char* pool = nullptr;      /* a hipMalloc'ed table, until it is registered */
+    const bool trace = trace_upload(); /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the stages, one line on stderr */
+    hipEvent_t ev[MAX_EV] = {};
+
+    /* who: "tile query" in "hipMalloc(%zu) for the tile query (%s) failed"; borrowed: the caller's stream, or NULL — begin() takes a pooled one */
+    call_work(osmt_ctx* ctx_, const char* who, hipStream_t borrowed = nullptr) : ctx(ctx_), st(borrowed), who_(who), own_stream_(!borrowed) {}
+    call_work(const call_work&) = delete;
+    call_work& operator=(const call_work&) = delete;
+    ~call_work() {
+        if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's arrays */
+        for (char* p : work) dev_free(ctx, p);
+        if (pool) (void)hipFree(pool);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (own_stream_) stream_release(ctx, st);
+    }
+    int begin(int n_ev) {
+        if (n_ev > MAX_EV) return fail(OSMT_HIP_ERROR, "internal error: the %s marks %d trace events (at most %d)", who_, n_ev, (int)MAX_EV);
+        if (own_stream_) HIP_TRY(stream_acquire(ctx, &st));
+        if (trace)
+            for (; n_ev_ < n_ev; ++n_ev_) HIP_TRY(hipEventCreate(&ev[n_ev_]));
+        return OSMT_OK;
+    }
+    /* a work buffer of the layout's size (+ 256: the kernels' reads past a last element stay inside) */
+    int alloc(char** out, const pool_layout& pl, const char* what = nullptr) const {
+        const hipError_t e = dev_alloc(ctx, (void**)out, pl.size() + 256);
+        if (e == hipSuccess) return OSMT_OK;
+        *out = nullptr;
+        const int code = e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR;
+        if (!what) return fail(code, "hipMalloc(%zu) for the %s failed: %s", pl.size(), who_, hipGetErrorString(e));
+        return fail(code, "hipMalloc(%zu) for the %s (%s) failed: %s", pl.size(), who_, what, hipGetErrorString(e));
+    }
+    int alloc(int slot, const pool_layout& pl, const char* what = nullptr) {
+        if (slot < 0 || slot >= MAX_WORK) return fail(OSMT_HIP_ERROR, "internal error: the %s asks for work buffer %d (at most %d)", who_, slot, (int)MAX_WORK);
+        return alloc(&work[slot], pl, what);
+    }
+    int alloc_pool(const pool_layout& pl) {
+        const hipError_t e = hipMalloc((void**)&pool, pl.size());
+        if (e == hipSuccess) return OSMT_OK;
+        pool = nullptr;
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the %s (table) failed: %s", pl.size(), who_, hipGetErrorString(e));
+    }
+    /* i, a, b: below the n_ev of begin(); without the trace there are no events and nothing is recorded */
+    hipError_t mark(int i) const { return i < n_ev_ ? hipEventRecord(ev[i], st) : trace ? hipErrorInvalidValue : hipSuccess; }
+    double us(int a, int b) const {
+        float ms = 0.f;
+        if (a < n_ev_ && b < n_ev_) (void)hipEventElapsedTime(&ms, ev[a], ev[b]);
+        return ms * 1e3;
+    }
+
+   private:
+    const char* who_;
+    bool own_stream_;
+    int n_ev_ = 0; /* events created */
+};
+
+/* ---- the device copy of a registry that only grows ----
+ * A registration followed by a use makes NEW device arrays; the old ones move to osmt_ctx::image_graveyard and live until the
+ * context goes, so a kernel launched by another thread with the previous snapshot never reads freed memory.  All of the new
+ * arrays are allocated and filled, or none is and the context is as it was.  Called with ctx->mu held. */
+struct snap_part {
+    void** slot;      /* the context's pointer: replaced */
+    const void* src;
+    size_t bytes;     /* copied */
+    size_t min_bytes; /* allocated at least; 0 with bytes == 0: no allocation, the slot becomes NULL */
+};
+int snapshot_replace(osmt_ctx* ctx, const char* name, const snap_part* parts, int n) {
+    constexpr int MAX_PARTS = 4;
+    void* fresh[MAX_PARTS] = {nullptr, nullptr, nullptr, nullptr};
+    if (n > MAX_PARTS) return fail(OSMT_HIP_ERROR, "internal error: the %s has %d arrays (at most %d)", name, n, MAX_PARTS);
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n && e == hipSuccess; ++i) {
+        const size_t b = std::max(parts[i].bytes, parts[i].min_bytes);
+        if (b) e = hipMalloc(&fresh[i], b);
+        if (e != hipSuccess) fresh[i] = nullptr;
+    }
+    for (int i = 0; i < n && e == hipSuccess; ++i)
+        if (parts[i].bytes) e = hipMemcpy(fresh[i], parts[i].src, parts[i].bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        for (int i = 0; i < n; ++i)
+            if (fresh[i]) (void)hipFree(fresh[i]);
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "%s upload failed: %s", name, hipGetErrorString(e));
+    }
+    for (int i = 0; i < n; ++i) {
+        if (*parts[i].slot) ctx->image_graveyard.push_back(*parts[i].slot);
+        *parts[i].slot = fresh[i];
+    }
+    return OSMT_OK;
+}
+
 struct image_snapshot {
     const osmt_image_desc* desc = nullptr;
     const double4* pool = nullptr;
@@ -561,23 +696,11 @@ struct image_snapshot {
 int sync_images(osmt_ctx* ctx, image_snapshot* snap) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->images_dirty) {
-        osmt_image_desc* nd = nullptr;
-        double4* np = nullptr;
-        if (!ctx->images.empty()) {
-            HIP_TRY(hipMalloc((void**)&nd, ctx->images.size() * sizeof(osmt_image_desc)));
-            hipError_t e = hipMalloc((void**)&np, ctx->image_pool_host.size() * sizeof(double));
-            if (e == hipSuccess) e = hipMemcpy(nd, ctx->images.data(), ctx->images.size() * sizeof(osmt_image_desc), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(np, ctx->image_pool_host.data(), ctx->image_pool_host.size() * sizeof(double), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(nd);
-                if (np) (void)hipFree(np);
-                return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "icon registry upload failed: %s", hipGetErrorString(e));
-            }
-        }
-        if (ctx->d_images) ctx->image_graveyard.push_back(ctx->d_images);
-        if (ctx->d_image_pool) ctx->image_graveyard.push_back(ctx->d_image_pool);
-        ctx->d_images = nd;
-        ctx->d_image_pool = np;
+        /* an empty registry has no device arrays at all */
+        const snap_part parts[2] = {{(void**)&ctx->d_images, ctx->images.data(), ctx->images.size() * sizeof(osmt_image_desc), 0},
+                                    {(void**)&ctx->d_image_pool, ctx->image_pool_host.data(), ctx->image_pool_host.size() * sizeof(double), 0}};
+        const int rc = snapshot_replace(ctx, "icon registry", parts, 2);
+        if (rc != OSMT_OK) return rc;
         ctx->d_n_images = (uint32_t)ctx->images.size();
         ctx->images_dirty = false;
     }
@@ -599,23 +722,11 @@ struct glyph_snapshot {
 int sync_glyphs(osmt_ctx* ctx, glyph_snapshot* snap) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->glyphs_dirty) {
-        osmt_glyph_vertex* nv = nullptr;
-        uint32_t* no = nullptr;
-        const size_t nvb = std::max<size_t>(ctx->glyph_verts.size(), 1) * sizeof(osmt_glyph_vertex);
-        HIP_TRY(hipMalloc((void**)&no, ctx->glyph_voff.size() * sizeof(uint32_t)));
-        hipError_t e = hipMalloc((void**)&nv, nvb);
-        if (e == hipSuccess) e = hipMemcpy(no, ctx->glyph_voff.data(), ctx->glyph_voff.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !ctx->glyph_verts.empty())
-            e = hipMemcpy(nv, ctx->glyph_verts.data(), ctx->glyph_verts.size() * sizeof(osmt_glyph_vertex), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(no);
-            if (nv) (void)hipFree(nv);
-            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "glyph table upload failed: %s", hipGetErrorString(e));
-        }
-        if (ctx->d_glyph_verts) ctx->image_graveyard.push_back(ctx->d_glyph_verts);
-        if (ctx->d_glyph_voff) ctx->image_graveyard.push_back(ctx->d_glyph_voff);
-        ctx->d_glyph_verts = nv;
-        ctx->d_glyph_voff = no;
+        const snap_part parts[2] = {
+            {(void**)&ctx->d_glyph_voff, ctx->glyph_voff.data(), ctx->glyph_voff.size() * sizeof(uint32_t), 0}, /* never empty: voff[0] = 0 */
+            {(void**)&ctx->d_glyph_verts, ctx->glyph_verts.data(), ctx->glyph_verts.size() * sizeof(osmt_glyph_vertex), sizeof(osmt_glyph_vertex)}};
+        const int rc = snapshot_replace(ctx, "glyph table", parts, 2);
+        if (rc != OSMT_OK) return rc;
         ctx->d_n_glyphs = (uint32_t)(ctx->glyph_voff.size() - 1);
         ctx->glyphs_dirty = false;
     }
@@ -642,17 +753,16 @@ int sync_fonts(osmt_ctx* ctx, font_snapshot* snap) {
             if (f.d_pool) continue;
             const size_t b_cmap = f.cmap.size() * sizeof(osmt_cmap_entry), b_adv = f.advance.size() * 4, b_out = f.outline.size() * 4;
             const size_t b_kern = f.kern.size() * sizeof(osmt_kern_pair);
-            const size_t o_cmap = 0, o_adv = align_up(o_cmap + b_cmap, 256), o_out = align_up(o_adv + b_adv, 256), o_kern = align_up(o_out + b_out, 256);
-            char* pool = nullptr;
-            HIP_TRY(hipMalloc((void**)&pool, o_kern + std::max<size_t>(b_kern, 4)));
-            hipError_t e = b_cmap ? hipMemcpy(pool + o_cmap, f.cmap.data(), b_cmap, hipMemcpyHostToDevice) : hipSuccess;
-            if (e == hipSuccess) e = hipMemcpy(pool + o_adv, f.advance.data(), b_adv, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(pool + o_out, f.outline.data(), b_out, hipMemcpyHostToDevice);
-            if (e == hipSuccess && b_kern) e = hipMemcpy(pool + o_kern, f.kern.data(), b_kern, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(pool);
-                return fail(OSMT_HIP_ERROR, "font table upload failed: %s", hipGetErrorString(e));
-            }
+            pool_layout pl;
+            const size_t o_cmap = pl.add(b_cmap), o_adv = pl.add(b_adv), o_out = pl.add(b_out), o_kern = pl.add(b_kern);
+            table_upload up("font table", pl);
+            char* pool = up.pool;
+            up.put(o_cmap, f.cmap.data(), b_cmap);
+            up.put(o_adv, f.advance.data(), b_adv);
+            up.put(o_out, f.outline.data(), b_out);
+            up.put(o_kern, f.kern.data(), b_kern);
+            if (up.done() != OSMT_OK) return up.done();
+            up.release();
             f.d_pool = pool;
             f.dev.cmap = (const osmt_cmap_entry*)(pool + o_cmap);
             f.dev.advance = (const int32_t*)(pool + o_adv);
@@ -664,17 +774,10 @@ int sync_fonts(osmt_ctx* ctx, font_snapshot* snap) {
         }
         std::vector<osmt_font_dev> recs;
         for (const auto& fp : ctx->fonts) recs.push_back(fp->dev);
-        osmt_font_dev* nd = nullptr;
-        HIP_TRY(hipMalloc((void**)&nd, std::max<size_t>(recs.size(), 1) * sizeof(osmt_font_dev)));
-        if (!recs.empty()) {
-            const hipError_t e = hipMemcpy(nd, recs.data(), recs.size() * sizeof(osmt_font_dev), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(nd);
-                return fail(OSMT_HIP_ERROR, "font table upload failed: %s", hipGetErrorString(e));
-            }
-        }
-        if (ctx->d_fonts) ctx->image_graveyard.push_back(ctx->d_fonts);
-        ctx->d_fonts = nd;
+        /* as for every registry: an allocation the device has no memory for is OSMT_OOM, a failed copy OSMT_HIP_ERROR */
+        const snap_part part = {(void**)&ctx->d_fonts, recs.data(), recs.size() * sizeof(osmt_font_dev), sizeof(osmt_font_dev)};
+        const int rc = snapshot_replace(ctx, "font table", &part, 1);
+        if (rc != OSMT_OK) return rc;
         ctx->d_n_fonts = (uint32_t)recs.size();
         ctx->fonts_dirty = false;
     }
@@ -1111,8 +1214,6 @@ int render_impl(osmt_ctx* ctx, osmt_scene* sc, uint32_t stages, void* d_out, siz
 
 }  // namespace
 
-extern "C" {
-
 uint32_t osmt_version(void) { return (1u << 16) | 1u; }
 
 const char* osmt_last_error(void) { return g_last_error.c_str(); }
@@ -1298,29 +1399,24 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
                     groups, (unsigned long long)OSMT_MAX_FILL_GROUPS);
     if (groups >= 0xFFFFFFFFull || recs >= 0xFFFFFFFFull)
         return fail(OSMT_UNSUPPORTED, "scene needs %llu fill groups / %llu stroke records (> 2^32): split the batch", groups, recs);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
+    pool_layout pl;
     /* list entries: one per (op, sub-tile the op draws into) — at most one per fill group / stroke slot, and never more
      * than every op in every sub-tile */
     unsigned long long ents = std::min<unsigned long long>(groups + recs, ((unsigned long long)n_fills + s->n_strokes) * nsub);
     if (ents >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "scene needs %llu list entries (> 2^32): split the batch", ents);
-    const size_t o_f = carve((size_t)(groups + 1) * 64);
-    const size_t o_r = carve((size_t)(recs + 1) * sizeof(osmt_srec));
-    const size_t o_k = carve((size_t)(recs + 1) * 8);
+    const size_t o_f = pl.add((size_t)(groups + 1) * 64);
+    const size_t o_r = pl.add((size_t)(recs + 1) * sizeof(osmt_srec));
+    const size_t o_k = pl.add((size_t)(recs + 1) * 8);
     /* batches of many tiles: the arena in slices with a cursor each and an overflow slice behind them (osmt_list_slices.h) */
     const osmt_list_layout lay = osmt_list_layout_make(s->n_jobs, ents + 1);
-    const size_t o_e = carve((size_t)lay.total * sizeof(osmt_ent));
+    const size_t o_e = pl.add((size_t)lay.total * sizeof(osmt_ent));
     /* one descriptor per (fill op, sub-tile row of its window) and the rounding of every k_opinfo workgroup */
     const unsigned long long slot_cap = osmt_fill_slot_capacity(groups, n_fills, (uint32_t)(W / OSMT_SUB_H), s->n_ops);
-    const size_t o_q = carve((size_t)slot_cap * sizeof(osmt_fill_slot));
-    hipError_t e = dev_alloc(ctx, (void**)&s->d_arena, off + 256);
+    const size_t o_q = pl.add((size_t)slot_cap * sizeof(osmt_fill_slot));
+    hipError_t e = dev_alloc(ctx, (void**)&s->d_arena, pl.size() + 256);
     if (e != hipSuccess) {
         s->d_arena = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the pre-pass arenas failed: %s", off, hipGetErrorString(e));
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the pre-pass arenas failed: %s", pl.size(), hipGetErrorString(e));
     }
     s->d_fmask = (uint32_t*)(s->d_arena + o_f);
     s->d_srec = (osmt_srec*)(s->d_arena + o_r);
@@ -1334,7 +1430,7 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
     if (trace_arenas)
         fprintf(stderr, "osmt arenas: %u tiles, fill groups %llu, stroke records %llu, list entries %llu in %u slice(s) of %llu (+ overflow): "
                         "list arena %.1f MB of %.1f MB%s\n", s->n_jobs, groups, recs, ents + 1, lay.n_slices, lay.slice_cap,
-                (double)lay.total * sizeof(osmt_ent) / 1e6, (double)off / 1e6, guessed ? " (guessed)" : "");
+                (double)lay.total * sizeof(osmt_ent) / 1e6, (double)pl.size() / 1e6, guessed ? " (guessed)" : "");
     s->fmask_cap = groups + 1; /* never 0: 0 means "sizing pass" to the kernels */
     s->srec_cap = recs + 1;
     return OSMT_OK;
@@ -1347,25 +1443,20 @@ static int scene_size_arenas(osmt_ctx* ctx, osmt_scene* s, size_t n_fills, bool 
 struct scene_back {
     size_t o_info, o_aux, o_dseg, o_submask, o_blk, o_vseg, o_cursors, o_hdr;
 };
-static scene_back scene_carve_back(size_t& off, size_t n_jobs, size_t n_ops, size_t n_strokes, size_t n_blk, size_t n_vsegs, uint32_t scale) {
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
+static scene_back scene_carve_back(pool_layout& pl, size_t n_jobs, size_t n_ops, size_t n_strokes, size_t n_blk, size_t n_vsegs, uint32_t scale) {
     scene_back k;
-    k.o_info = carve(n_ops * sizeof(osmt_opinfo));
+    k.o_info = pl.add(n_ops * sizeof(osmt_opinfo));
     /* per virtual segment (not per point: two stroke ops may share a ring, e.g. a casing and its stroke) */
-    k.o_aux = carve((size_t)(n_strokes + 1) * sizeof(osmt_stroke_aux));
-    k.o_dseg = carve((size_t)(n_strokes + 1) * OSMT_MAX_DASH_SEGS * sizeof(osmt_dash_seg)); /* touched by dashed ops only */
+    k.o_aux = pl.add((size_t)(n_strokes + 1) * sizeof(osmt_stroke_aux));
+    k.o_dseg = pl.add((size_t)(n_strokes + 1) * OSMT_MAX_DASH_SEGS * sizeof(osmt_dash_seg)); /* touched by dashed ops only */
     const size_t sub_rows = (size_t)OSMT_TILE_SIZE * scale / OSMT_SUB_H;
-    k.o_submask = carve(n_ops * sub_rows * 4);
-    k.o_blk = carve((n_blk + 1) * sizeof(osmt_blk_bbox));
-    k.o_vseg = carve((n_vsegs + 1) * sizeof(osmt_vseg));
+    k.o_submask = pl.add(n_ops * sub_rows * 4);
+    k.o_blk = pl.add((n_blk + 1) * sizeof(osmt_blk_bbox));
+    k.o_vseg = pl.add((n_vsegs + 1) * sizeof(osmt_vseg));
     const size_t n_sub = ((size_t)OSMT_TILE_SIZE * scale / OSMT_SUB_W) * sub_rows;
     /* cursors + list counts + the cursors of the list arena's slices: zeroed together every frame */
-    k.o_cursors = carve((osmt_list_cursor_word0(n_jobs * n_sub) + OSMT_LIST_CURSOR_WORDS) * 4);
-    k.o_hdr = carve(n_jobs * n_sub * sizeof(uint2));
+    k.o_cursors = pl.add((osmt_list_cursor_word0(n_jobs * n_sub) + OSMT_LIST_CURSOR_WORDS) * 4);
+    k.o_hdr = pl.add(n_jobs * n_sub * sizeof(uint2));
     return k;
 }
 static void scene_point_back(osmt_scene* s, char* rbase, const scene_back& k) {
@@ -1391,30 +1482,26 @@ static int scene_upload_impl(osmt_ctx* ctx, const osmt_batch* b, osmt_scene** ou
      * the copies (they do not depend on it); the verdict is collected before the first kernel can be launched. */
     const bool big = b && coord_count(b) >= ((size_t)1 << 16);
     /* Where the host's own arrays go inside the scene's memory: known from the batch's sizes alone */
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
+    pool_layout pl;
     const bool ll = b && b->coord_kind == OSMT_COORD_LATLON_F64;
     const bool nr = b && b->coord_kind == OSMT_COORD_NODE_REF;
     size_t o_jobs = 0, o_ops = 0, o_rings = 0, o_latlon = 0, o_refs = 0, o_pts = 0, o_dashes = 0, o_ptjob = 0, o_opaux = 0, o_opblk = 0, o_opvseg = 0,
            o_opjob = 0, front_bytes = 0;
     if (b) {
-        o_jobs = carve(b->n_jobs * sizeof(osmt_tile_job));
-        o_ops = carve(b->n_ops * sizeof(osmt_op));
-        o_rings = carve(b->n_rings * sizeof(osmt_ring));
-        o_latlon = carve(ll ? b->n_pts * 16 : nr ? b->n_nodes * 16 : 0);
-        o_refs = carve(nr ? b->n_pts * 4 : 0);
-        o_pts = carve(b->n_pts * 8);
-        o_dashes = carve((b->n_dashes + 1) * 8);
-        o_ptjob = carve(b->n_pts * 4);
-        o_opaux = carve(b->n_ops * 4);
-        o_opblk = carve(b->n_ops * 4);
-        o_opvseg = carve(b->n_ops * 4);
-        o_opjob = carve(b->n_ops * 4);
-        front_bytes = off; /* everything the host provides sits in [0, front_bytes) */
+        o_jobs = pl.add(b->n_jobs * sizeof(osmt_tile_job));
+        o_ops = pl.add(b->n_ops * sizeof(osmt_op));
+        o_rings = pl.add(b->n_rings * sizeof(osmt_ring));
+        /* an array the coordinate kind does not have takes no room: a one-tile request stays as small as it was */
+        o_latlon = ll ? pl.add(b->n_pts * 16) : nr ? pl.add(b->n_nodes * 16) : pl.size();
+        o_refs = nr ? pl.add(b->n_pts * 4) : pl.size();
+        o_pts = pl.add(b->n_pts * 8);
+        o_dashes = pl.add((b->n_dashes + 1) * 8);
+        o_ptjob = pl.add(b->n_pts * 4);
+        o_opaux = pl.add(b->n_ops * 4);
+        o_opblk = pl.add(b->n_ops * 4);
+        o_opvseg = pl.add(b->n_ops * 4);
+        o_opjob = pl.add(b->n_ops * 4);
+        front_bytes = pl.size(); /* everything the host provides sits in [0, front_bytes) */
     }
     /* SPLIT upload (round 5; big stream-ordered uploads): the caller's arrays — 27 MB for 1024 config-2 tiles, 0.44 ms of
      * pageable copies — go to an allocation of their own and are copied by a helper thread WHILE this thread validates the jobs
@@ -1609,14 +1696,14 @@ static int scene_upload_impl(osmt_ctx* ctx, const osmt_batch* b, osmt_scene** ou
     s->scale = b->scale;
     s->coord_kind = b->coord_kind;
 
-    const scene_back bk = scene_carve_back(off, b->n_jobs, b->n_ops, n_strokes, n_blk, n_vsegs, b->scale);
-    s->bytes = off - (split ? front_bytes : 0) + 256;
+    const scene_back bk = scene_carve_back(pl, b->n_jobs, b->n_ops, n_strokes, n_blk, n_vsegs, b->scale);
+    s->bytes = pl.size() - (split ? front_bytes : 0) + 256;
     mark(1);
     hipError_t e = dev_alloc(ctx, (void**)&s->d_base, s->bytes);
     mark(2);
     if (e != hipSuccess) {
         scene_delete(s);
-        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) failed: %s", off,
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) failed: %s", pl.size(),
                     hipGetErrorString(e));
     }
     /* front offsets live in d_front when the upload is split, everything behind them in d_base */
@@ -1898,28 +1985,11 @@ int sync_styles(osmt_ctx* ctx, styles_snapshot* snap) {
             if (i && style_key_cmp(ctx->styles[order[i - 1]], ctx->styles[order[i]]) != 0) ++r;
             rank[order[i]] = r;
         }
-        osmt_style_rec* ds = nullptr;
-        uint32_t* dr = nullptr;
-        double* dd = nullptr;
-        const size_t nd = ctx->style_dashes.size();
-        hipError_t e = hipMalloc((void**)&ds, std::max<size_t>(n, 1) * sizeof(osmt_style_rec));
-        if (e == hipSuccess) e = hipMalloc((void**)&dr, std::max<size_t>(n, 1) * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&dd, std::max<size_t>(nd, 1) * 8);
-        if (e == hipSuccess && n) e = hipMemcpy(ds, ctx->styles.data(), n * sizeof(osmt_style_rec), hipMemcpyHostToDevice);
-        if (e == hipSuccess && n) e = hipMemcpy(dr, rank.data(), n * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && nd) e = hipMemcpy(dd, ctx->style_dashes.data(), nd * 8, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (ds) (void)hipFree(ds);
-            if (dr) (void)hipFree(dr);
-            if (dd) (void)hipFree(dd);
-            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "style table upload failed: %s", hipGetErrorString(e));
-        }
-        if (ctx->d_styles) ctx->image_graveyard.push_back(ctx->d_styles);
-        if (ctx->d_style_rank) ctx->image_graveyard.push_back(ctx->d_style_rank);
-        if (ctx->d_style_dashes) ctx->image_graveyard.push_back(ctx->d_style_dashes);
-        ctx->d_styles = ds;
-        ctx->d_style_rank = dr;
-        ctx->d_style_dashes = dd;
+        const snap_part parts[3] = {{(void**)&ctx->d_styles, ctx->styles.data(), n * sizeof(osmt_style_rec), sizeof(osmt_style_rec)},
+                                    {(void**)&ctx->d_style_rank, rank.data(), n * 4, 4},
+                                    {(void**)&ctx->d_style_dashes, ctx->style_dashes.data(), ctx->style_dashes.size() * 8, 8}};
+        const int rc = snapshot_replace(ctx, "style table", parts, 3);
+        if (rc != OSMT_OK) return rc;
         ctx->d_n_styles = (uint32_t)n;
         ctx->styles_dirty = false;
     }
@@ -2005,36 +2075,24 @@ int register_geodata_body(osmt_ctx* ctx, const osmt_geodata_desc* g, uint32_t* o
     }
     std::vector<uint32_t> poly_off(g->n_polygons + 1);
     for (size_t p = 0; p <= g->n_polygons; ++p) poly_off[p] = g->polygon_node_off[p] + (uint32_t)g->n_way_nodes;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_nodes = carve(g->n_nodes * 16), o_wgid = carve(g->n_ways * 8), o_mgid = carve(g->n_multipolygons * 8);
-    const size_t o_woff = carve((g->n_ways + 1) * 4), o_poff = carve((g->n_polygons + 1) * 4), o_moff = carve((g->n_multipolygons + 1) * 4);
-    const size_t o_mpol = carve(g->n_multipolygon_polygons * 4), o_idx = carve((g->n_way_nodes + g->n_polygon_nodes) * 4);
-    const size_t o_sum = carve(g->n_multipolygons * 8);
-    char* pool = nullptr;
-    HIP_TRY(hipMalloc((void**)&pool, off));
-    hipError_t e = hipSuccess;
-    auto put = [&](size_t o, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
-    };
-    put(o_nodes, g->nodes, g->n_nodes * 16);
-    put(o_wgid, g->way_ids, g->n_ways * 8);
-    put(o_mgid, g->multipolygon_ids, g->n_multipolygons * 8);
-    put(o_woff, g->way_node_off, (g->n_ways + 1) * 4);
-    put(o_poff, poly_off.data(), (g->n_polygons + 1) * 4);
-    put(o_moff, g->multipolygon_polygon_off, (g->n_multipolygons + 1) * 4);
-    put(o_mpol, g->multipolygon_polygons, g->n_multipolygon_polygons * 4);
-    put(o_idx, g->way_nodes, g->n_way_nodes * 4);
-    put(o_idx + g->n_way_nodes * 4, g->polygon_nodes, g->n_polygon_nodes * 4);
-    put(o_sum, mp_sum.data(), g->n_multipolygons * 8);
-    if (e != hipSuccess) {
-        (void)hipFree(pool);
-        return fail(OSMT_HIP_ERROR, "geodata upload failed: %s", hipGetErrorString(e));
-    }
+    pool_layout pl;
+    const size_t o_nodes = pl.add(g->n_nodes * 16), o_wgid = pl.add(g->n_ways * 8), o_mgid = pl.add(g->n_multipolygons * 8);
+    const size_t o_woff = pl.add((g->n_ways + 1) * 4), o_poff = pl.add((g->n_polygons + 1) * 4), o_moff = pl.add((g->n_multipolygons + 1) * 4);
+    const size_t o_mpol = pl.add(g->n_multipolygon_polygons * 4), o_idx = pl.add((g->n_way_nodes + g->n_polygon_nodes) * 4);
+    const size_t o_sum = pl.add(g->n_multipolygons * 8);
+    table_upload up("geodata", pl);
+    char* pool = up.pool;
+    up.put(o_nodes, g->nodes, g->n_nodes * 16);
+    up.put(o_wgid, g->way_ids, g->n_ways * 8);
+    up.put(o_mgid, g->multipolygon_ids, g->n_multipolygons * 8);
+    up.put(o_woff, g->way_node_off, (g->n_ways + 1) * 4);
+    up.put(o_poff, poly_off.data(), (g->n_polygons + 1) * 4);
+    up.put(o_moff, g->multipolygon_polygon_off, (g->n_multipolygons + 1) * 4);
+    up.put(o_mpol, g->multipolygon_polygons, g->n_multipolygon_polygons * 4);
+    up.put(o_idx, g->way_nodes, g->n_way_nodes * 4);
+    up.put(o_idx + g->n_way_nodes * 4, g->polygon_nodes, g->n_polygon_nodes * 4);
+    up.put(o_sum, mp_sum.data(), g->n_multipolygons * 8);
+    if (up.done() != OSMT_OK) return up.done();
     osmt_ctx::geodata_host h;
     h.n_nodes = g->n_nodes, h.n_ways = g->n_ways, h.n_mps = g->n_multipolygons;
     h.d_pool = pool;
@@ -2048,12 +2106,10 @@ int register_geodata_body(osmt_ctx* ctx, const osmt_geodata_desc* g, uint32_t* o
     h.dev.idx = (const uint32_t*)(pool + o_idx);
     h.dev.mp_sum = (const uint2*)(pool + o_sum);
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->geodata.size() + 1 >= 0xFFFFFFFFull) {
-        (void)hipFree(pool);
-        return fail(OSMT_INVALID_ARG, "geodata table too large");
-    }
+    if (ctx->geodata.size() + 1 >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "geodata table too large");
     *out_id = (uint32_t)ctx->geodata.size();
     ctx->geodata.push_back(h);
+    up.release();
     return OSMT_OK;
 }
 
@@ -2092,35 +2148,17 @@ struct styled_src {
 int styled_build_back(osmt_ctx* ctx, hipStream_t st, const osmt_ctx::geodata_host& geo, const styles_snapshot& ss, const styled_src& in,
                       osmt_scene** out_scene) {
     const size_t n_tiles = in.n_tiles, total = in.total, n_elems = 3 * total, n_blk = (n_elems + 255) / 256;
-    /* everything that lives only during the build: one allocation, given back at the end */
-    struct work_guard {
-        osmt_ctx* ctx;
-        hipStream_t st;
-        char* work = nullptr;
-        uint32_t* ring_src = nullptr;
-        ~work_guard() {
-            (void)hipStreamSynchronize(st); /* nothing may still read the buffers */
-            dev_free(ctx, work);
-            dev_free(ctx, ring_src);
-        }
-    } wg{ctx, st};
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    const size_t o_keys = carve(total * 16), o_sorted = carve(total * 4), o_pre = carve((size_t)OSMT_SQ_N * (n_elems + 1) * 4);
-    const size_t o_blk = carve((size_t)OSMT_SQ_N * std::max<size_t>(n_blk, 1) * 8), o_tot = carve(OSMT_STYLED_TOTALS * 8);
-    {
-        const hipError_t e = dev_alloc(ctx, (void**)&wg.work, off + 256);
-        if (e != hipSuccess) {
-            wg.work = nullptr;
-            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the styled build failed: %s", off, hipGetErrorString(e));
-        }
-    }
-    char* w = wg.work;
-    int rc = OSMT_OK;
+    /* everything that lives only during the build, given back at the end: work[0] one allocation, work[1] the rings' sources */
+    call_work wg(ctx, "styled build", st);
+    int rc = wg.begin(4);
+    if (rc != OSMT_OK) return rc;
+    const bool trace = wg.trace;
+    pool_layout pl;
+    const size_t o_keys = pl.add(total * 16), o_sorted = pl.add(total * 4), o_pre = pl.add((size_t)OSMT_SQ_N * (n_elems + 1) * 4);
+    const size_t o_blk = pl.add((size_t)OSMT_SQ_N * std::max<size_t>(n_blk, 1) * 8), o_tot = pl.add(OSMT_STYLED_TOTALS * 8);
+    rc = wg.alloc(0, pl);
+    if (rc != OSMT_OK) return rc;
+    char* w = wg.work[0];
     osmt_styled_pass P;
     memset(&P, 0, sizeof P);
     P.geo = geo.dev;
@@ -2139,21 +2177,10 @@ int styled_build_back(osmt_ctx* ctx, hipStream_t st, const osmt_ctx::geodata_hos
     P.pre = (uint32_t*)(w + o_pre);
     P.blk = (unsigned long long*)(w + o_blk);
     P.totals = (unsigned long long*)(w + o_tot);
-    /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the two launch sequences, one line on stderr */
-    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct ev_guard {
-        hipEvent_t* ev;
-        ~ev_guard() {
-            for (int i = 0; i < 4; ++i)
-                if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    } evg{ev};
-    if (trace)
-        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ev[i]));
-    if (trace) HIP_TRY(hipEventRecord(ev[0], st));
+    /* the trace: the device time of the two launch sequences */
+    HIP_TRY(wg.mark(0));
     HIP_TRY(osmt_launch_styled_count(P, st));
-    if (trace) HIP_TRY(hipEventRecord(ev[1], st));
+    HIP_TRY(wg.mark(1));
     unsigned long long tot[OSMT_STYLED_TOTALS];
     HIP_TRY(hipMemcpyAsync(tot, P.totals, sizeof tot, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -2181,23 +2208,23 @@ int styled_build_back(osmt_ctx* ctx, hipStream_t st, const osmt_ctx::geodata_hos
     s->scale = in.scale;
     s->coord_kind = OSMT_COORD_NODE_REF;
     /* the front arrays in the order of scene_upload_impl — without a node table: d_latlon is the registered one */
-    off = 0;
-    const size_t o_jobs = carve(n_tiles * sizeof(osmt_tile_job)), o_ops = carve(n_ops * sizeof(osmt_op)), o_rings = carve(n_rings * sizeof(osmt_ring));
-    const size_t o_refs = carve(n_pts * 4), o_pts = carve(n_pts * 8), o_dashes = carve((n_dashes + 1) * 8), o_ptjob = carve(n_pts * 4);
-    const size_t o_opaux = carve(n_ops * 4), o_opblk = carve(n_ops * 4), o_opvseg = carve(n_ops * 4), o_opjob = carve(n_ops * 4);
-    const scene_back bk = scene_carve_back(off, n_tiles, n_ops, n_strokes, n_blocks, n_vsegs, in.scale);
-    s->bytes = off + 256;
+    pl = pool_layout();
+    const size_t o_jobs = pl.add(n_tiles * sizeof(osmt_tile_job)), o_ops = pl.add(n_ops * sizeof(osmt_op)), o_rings = pl.add(n_rings * sizeof(osmt_ring));
+    const size_t o_refs = pl.add(n_pts * 4), o_pts = pl.add(n_pts * 8), o_dashes = pl.add((n_dashes + 1) * 8), o_ptjob = pl.add(n_pts * 4);
+    const size_t o_opaux = pl.add(n_ops * 4), o_opblk = pl.add(n_ops * 4), o_opvseg = pl.add(n_ops * 4), o_opjob = pl.add(n_ops * 4);
+    const scene_back bk = scene_carve_back(pl, n_tiles, n_ops, n_strokes, n_blocks, n_vsegs, in.scale);
+    s->bytes = pl.size() + 256;
     hipError_t e = dev_alloc(ctx, (void**)&s->d_base, s->bytes);
     if (e == hipSuccess) {
-        e = dev_alloc(ctx, (void**)&wg.ring_src, std::max<size_t>(n_rings, 1) * 4);
-        if (e != hipSuccess) wg.ring_src = nullptr;
+        e = dev_alloc(ctx, (void**)&wg.work[1], std::max<size_t>(n_rings, 1) * 4);
+        if (e != hipSuccess) wg.work[1] = nullptr;
     } else {
         s->d_base = nullptr;
     }
     if (e != hipSuccess) {
         dev_free(ctx, s->d_base);
         scene_delete(s);
-        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) failed: %s", pl.size(), hipGetErrorString(e));
     }
     char* base = s->d_base;
     s->d_jobs = (osmt_tile_job*)(base + o_jobs);
@@ -2222,13 +2249,13 @@ int styled_build_back(osmt_ctx* ctx, hipStream_t st, const osmt_ctx::geodata_hos
     P.op_aux = s->d_op_aux;
     P.op_blk = s->d_op_blk;
     P.op_vseg = s->d_op_vseg;
-    P.ring_src = wg.ring_src;
+    P.ring_src = (uint32_t*)wg.work[1];
     P.n_rings = (uint32_t)n_rings;
     P.n_refs = (uint32_t)n_pts;
-    if (trace) (void)hipEventRecord(ev[2], st);
+    (void)wg.mark(2);
     e = osmt_launch_styled_emit(P, st);
     if (e == hipSuccess) e = osmt_launch_ptjob(s->d_jobs, s->n_jobs, s->d_pt_job, s->n_pts, st);
-    if (trace) (void)hipEventRecord(ev[3], st);
+    (void)wg.mark(3);
     if (e != hipSuccess) {
         osmt_scene_free(s);
         return fail(OSMT_HIP_ERROR, "styled build failed: %s", hipGetErrorString(e));
@@ -2242,13 +2269,9 @@ int styled_build_back(osmt_ctx* ctx, hipStream_t st, const osmt_ctx::geodata_hos
         osmt_scene_free(s);
         return rc;
     }
-    if (trace) {
-        float ms_count = 0.f, ms_emit = 0.f;
-        (void)hipEventElapsedTime(&ms_count, ev[0], ev[1]);
-        (void)hipEventElapsedTime(&ms_emit, ev[2], ev[3]);
+    if (trace)
         fprintf(stderr, "osmt styled build: sort + count + scan kernels %.1f us, emit kernels %.1f us (%zu tiles, %zu areas, %zu ops)\n",
-                ms_count * 1e3, ms_emit * 1e3, n_tiles, total, n_ops);
-    }
+                wg.us(0, 1), wg.us(2, 3), n_tiles, total, n_ops);
     s->own_stream = nullptr; /* from here on a public scene: waits go through its last-use events */
     *out_scene = s;
     return OSMT_OK;
@@ -2279,33 +2302,15 @@ int scene_build_styled_body(osmt_ctx* ctx, const osmt_styled_batch* b, osmt_scen
         }
     if (a_hi < a_lo) a_lo = a_hi = 0;
     /* the caller's arrays on the device: given back when the build is over */
-    struct front_guard {
-        osmt_ctx* ctx;
-        hipStream_t st = nullptr;
-        char* work = nullptr;
-        ~front_guard() {
-            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's arrays */
-            dev_free(ctx, work);
-            stream_release(ctx, st);
-        }
-    } fg{ctx};
-    HIP_TRY(stream_acquire(ctx, &fg.st));
+    call_work fg(ctx, "styled build");
+    rc = fg.begin(0);
+    if (rc != OSMT_OK) return rc;
     hipStream_t st = fg.st;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    const size_t o_tiles = carve(n_tiles * sizeof(osmt_styled_tile)), o_base = carve((n_tiles + 1) * 4), o_areas = carve((a_hi - a_lo) * sizeof(osmt_styled_area));
-    {
-        const hipError_t e = dev_alloc(ctx, (void**)&fg.work, off + 256);
-        if (e != hipSuccess) {
-            fg.work = nullptr;
-            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the styled build failed: %s", off, hipGetErrorString(e));
-        }
-    }
-    char* w = fg.work;
+    pool_layout pl;
+    const size_t o_tiles = pl.add(n_tiles * sizeof(osmt_styled_tile)), o_base = pl.add((n_tiles + 1) * 4), o_areas = pl.add((a_hi - a_lo) * sizeof(osmt_styled_area));
+    rc = fg.alloc(0, pl);
+    if (rc != OSMT_OK) return rc;
+    char* w = fg.work[0];
     if (n_tiles) HIP_TRY(hipMemcpyAsync(w + o_tiles, b->tiles, n_tiles * sizeof(osmt_styled_tile), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(w + o_base, tile_base.data(), (n_tiles + 1) * 4, hipMemcpyHostToDevice, st));
     if (a_hi > a_lo) HIP_TRY(hipMemcpyAsync(w + o_areas, b->areas + a_lo, (a_hi - a_lo) * sizeof(osmt_styled_area), hipMemcpyHostToDevice, st));
@@ -2381,31 +2386,19 @@ int register_tile_index_body(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tile
         }
     }
     col_first.push_back((uint32_t)n);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_cx = carve(col_x.size() * 4), o_cf = carve(col_first.size() * 4), o_ty = carve(n * 4), o_wo = carve((n + 1) * 4);
-    const size_t o_w = carve(x->n_way_refs * 4), o_mo = carve((n + 1) * 4), o_m = carve(x->n_multipolygon_refs * 4);
-    char* pool = nullptr;
-    HIP_TRY(hipMalloc((void**)&pool, off));
-    hipError_t e = hipSuccess;
-    auto put = [&](size_t o, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
-    };
-    put(o_cx, col_x.data(), col_x.size() * 4);
-    put(o_cf, col_first.data(), col_first.size() * 4);
-    put(o_ty, tile_y.data(), n * 4);
-    put(o_wo, x->way_off, (n + 1) * 4);
-    put(o_w, x->ways, x->n_way_refs * 4);
-    put(o_mo, x->multipolygon_off, (n + 1) * 4);
-    put(o_m, x->multipolygons, x->n_multipolygon_refs * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(pool);
-        return fail(OSMT_HIP_ERROR, "tile index upload failed: %s", hipGetErrorString(e));
-    }
+    pool_layout pl;
+    const size_t o_cx = pl.add(col_x.size() * 4), o_cf = pl.add(col_first.size() * 4), o_ty = pl.add(n * 4), o_wo = pl.add((n + 1) * 4);
+    const size_t o_w = pl.add(x->n_way_refs * 4), o_mo = pl.add((n + 1) * 4), o_m = pl.add(x->n_multipolygon_refs * 4);
+    table_upload up("tile index", pl);
+    char* pool = up.pool;
+    up.put(o_cx, col_x.data(), col_x.size() * 4);
+    up.put(o_cf, col_first.data(), col_first.size() * 4);
+    up.put(o_ty, tile_y.data(), n * 4);
+    up.put(o_wo, x->way_off, (n + 1) * 4);
+    up.put(o_w, x->ways, x->n_way_refs * 4);
+    up.put(o_mo, x->multipolygon_off, (n + 1) * 4);
+    up.put(o_m, x->multipolygons, x->n_multipolygon_refs * 4);
+    if (up.done() != OSMT_OK) return up.done();
     osmt_tq_index_dev d{};
     d.col_x = (const uint32_t*)(pool + o_cx);
     d.col_first = (const uint32_t*)(pool + o_cf);
@@ -2417,12 +2410,10 @@ int register_tile_index_body(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tile
     d.n_cols = (uint32_t)col_x.size();
     d.n_tiles = (uint32_t)n;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->geodata[geodata_id].d_index) { /* another thread was first */
-        (void)hipFree(pool);
-        return fail(OSMT_INVALID_ARG, "geodata id %u has a tile index already (one per file)", geodata_id);
-    }
+    if (ctx->geodata[geodata_id].d_index) return fail(OSMT_INVALID_ARG, "geodata id %u has a tile index already (one per file)", geodata_id); /* another thread was first */
     ctx->geodata[geodata_id].d_index = pool;
     ctx->geodata[geodata_id].ix = d;
+    up.release();
     return OSMT_OK;
 }
 
@@ -2465,27 +2456,15 @@ int register_style_bindings_body(osmt_ctx* ctx, const osmt_style_bindings_desc* 
         std::lock_guard<std::mutex> lk(ctx->mu);
         n_ways = ctx->geodata[b->geodata_id].n_ways, n_mps = ctx->geodata[b->geodata_id].n_mps;
     }
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_wo = carve((n_ways + 1) * 4), o_w = carve(b->n_way_styles * 4), o_mo = carve((n_mps + 1) * 4), o_m = carve(b->n_multipolygon_styles * 4);
-    char* pool = nullptr;
-    HIP_TRY(hipMalloc((void**)&pool, off));
-    hipError_t e = hipSuccess;
-    auto put = [&](size_t o, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
-    };
-    put(o_wo, b->way_style_off, (n_ways + 1) * 4);
-    put(o_w, b->way_styles, b->n_way_styles * 4);
-    put(o_mo, b->multipolygon_style_off, (n_mps + 1) * 4);
-    put(o_m, b->multipolygon_styles, b->n_multipolygon_styles * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(pool);
-        return fail(OSMT_HIP_ERROR, "style bindings upload failed: %s", hipGetErrorString(e));
-    }
+    pool_layout pl;
+    const size_t o_wo = pl.add((n_ways + 1) * 4), o_w = pl.add(b->n_way_styles * 4), o_mo = pl.add((n_mps + 1) * 4), o_m = pl.add(b->n_multipolygon_styles * 4);
+    table_upload up("style bindings", pl);
+    char* pool = up.pool;
+    up.put(o_wo, b->way_style_off, (n_ways + 1) * 4);
+    up.put(o_w, b->way_styles, b->n_way_styles * 4);
+    up.put(o_mo, b->multipolygon_style_off, (n_mps + 1) * 4);
+    up.put(o_m, b->multipolygon_styles, b->n_multipolygon_styles * 4);
+    if (up.done() != OSMT_OK) return up.done();
     osmt_ctx::bindings_host h;
     h.geodata_id = b->geodata_id, h.zoom_lo = b->zoom_lo, h.zoom_hi = b->zoom_hi;
     h.d_pool = pool;
@@ -2494,12 +2473,10 @@ int register_style_bindings_body(osmt_ctx* ctx, const osmt_style_bindings_desc* 
     h.dev.mp_off = (const uint32_t*)(pool + o_mo);
     h.dev.mp_styles = (const uint32_t*)(pool + o_m);
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->bindings.size() + 1 >= 0xFFFFFFFFull) {
-        (void)hipFree(pool);
-        return fail(OSMT_INVALID_ARG, "bindings table too large");
-    }
+    if (ctx->bindings.size() + 1 >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "bindings table too large");
     *out_id = (uint32_t)ctx->bindings.size();
     ctx->bindings.push_back(h);
+    up.release();
     return OSMT_OK;
 }
 
@@ -2556,52 +2533,22 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
     }
     const size_t n_tiles = b->n_tiles;
     /* work[0]: per tile, work[1]: per item, work[2]: per candidate — given back at the end */
-    struct work_guard {
-        osmt_ctx* ctx;
-        hipStream_t st = nullptr;
-        char* work[3] = {nullptr, nullptr, nullptr};
-        ~work_guard() {
-            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's tiles */
-            for (char* p : work) dev_free(ctx, p);
-            stream_release(ctx, st);
-        }
-    } wg{ctx};
-    HIP_TRY(stream_acquire(ctx, &wg.st));
-    hipStream_t st = wg.st;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    auto alloc = [&](char** out, const char* what) {
-        const hipError_t e = dev_alloc(ctx, (void**)out, off + 256);
-        if (e == hipSuccess) return (int)OSMT_OK;
-        *out = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the tile query (%s) failed: %s", off, what, hipGetErrorString(e));
-    };
-    /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the stages, one line on stderr */
-    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    /* the trace: the device time of the stages */
     enum { EV_SPAN0, EV_SPAN1, EV_COL0, EV_COL1, EV_GATHER0, EV_SORT0, EV_MARK0, EV_MARK1, EV_EMIT0, EV_EMIT1, EV_N };
-    hipEvent_t ev[EV_N] = {};
-    struct ev_guard {
-        hipEvent_t* ev;
-        ~ev_guard() {
-            for (int i = 0; i < EV_N; ++i)
-                if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    } evg{ev};
-    if (trace)
-        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
-    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+    call_work wg(ctx, "tile query");
+    rc = wg.begin(EV_N);
+    if (rc != OSMT_OK) return rc;
+    hipStream_t st = wg.st;
+    const bool trace = wg.trace;
+    pool_layout pl;
 
     unsigned long long tot[OSMT_TQ_N] = {};
     osmt_tq_pass P;
     memset(&P, 0, sizeof P);
-    off = 0;
-    const size_t o_q = carve(n_tiles * sizeof(osmt_query_tile)), o_bind = carve(sizeof bind), o_c0 = carve(n_tiles * 4), o_ib = carve((n_tiles + 1) * 4);
-    const size_t o_tw = carve((n_tiles + 1) * 4), o_tm = carve((n_tiles + 1) * 4), o_tot = carve(OSMT_TQ_N * 8), o_blk0 = carve((n_tiles / 256 + 1) * 8);
-    rc = alloc(&wg.work[0], "tiles");
+    pl = pool_layout();
+    const size_t o_q = pl.add(n_tiles * sizeof(osmt_query_tile)), o_bind = pl.add(sizeof bind), o_c0 = pl.add(n_tiles * 4), o_ib = pl.add((n_tiles + 1) * 4);
+    const size_t o_tw = pl.add((n_tiles + 1) * 4), o_tm = pl.add((n_tiles + 1) * 4), o_tot = pl.add(OSMT_TQ_N * 8), o_blk0 = pl.add((n_tiles / 256 + 1) * 8);
+    rc = wg.alloc(0, pl, "tiles");
     if (rc != OSMT_OK) return rc;
     char* w0 = wg.work[0];
     size_t n_items = 0, n_way_cand = 0, n_mp_cand = 0, n_cand = 0, n_areas = 0;
@@ -2620,19 +2567,19 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
         P.tot = (unsigned long long*)(w0 + o_tot);
         P.blk = (unsigned long long*)(w0 + o_blk0);
         /* 1. span */
-        HIP_TRY(mark(EV_SPAN0));
+        HIP_TRY(wg.mark(EV_SPAN0));
         HIP_TRY(osmt_launch_tq_span(P, st));
-        HIP_TRY(mark(EV_SPAN1));
+        HIP_TRY(wg.mark(EV_SPAN1));
         HIP_TRY(hipMemcpyAsync(tot, P.tot, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (tot[OSMT_TQ_ITEMS] >= 0xFFFFFFFFull)
             return fail(OSMT_UNSUPPORTED, "tile batch needs %llu (tile, column) items (> 2^32): split the batch", tot[OSMT_TQ_ITEMS]);
         n_items = (size_t)tot[OSMT_TQ_ITEMS];
         /* 2. columns */
-        off = 0;
-        const size_t o_it = carve(n_items * 4), o_ws = carve(n_items * 4), o_ms = carve(n_items * 4), o_wb = carve((n_items + 1) * 4);
-        const size_t o_mb = carve((n_items + 1) * 4), o_blk1 = carve((n_items / 256 + 1) * 8);
-        rc = alloc(&wg.work[1], "columns");
+        pl = pool_layout();
+        const size_t o_it = pl.add(n_items * 4), o_ws = pl.add(n_items * 4), o_ms = pl.add(n_items * 4), o_wb = pl.add((n_items + 1) * 4);
+        const size_t o_mb = pl.add((n_items + 1) * 4), o_blk1 = pl.add((n_items / 256 + 1) * 8);
+        rc = wg.alloc(1, pl, "columns");
         if (rc != OSMT_OK) return rc;
         char* w1 = wg.work[1];
         P.n_items = (uint32_t)n_items;
@@ -2642,9 +2589,9 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
         P.wbase = (uint32_t*)(w1 + o_wb);
         P.mbase = (uint32_t*)(w1 + o_mb);
         P.blk = (unsigned long long*)(w1 + o_blk1);
-        HIP_TRY(mark(EV_COL0));
+        HIP_TRY(wg.mark(EV_COL0));
         HIP_TRY(osmt_launch_tq_columns(P, st));
-        HIP_TRY(mark(EV_COL1));
+        HIP_TRY(wg.mark(EV_COL1));
         /* first read-back: the candidate totals, the largest tile, the first tile over the limit — nothing is gathered before */
         HIP_TRY(hipMemcpyAsync(tot, P.tot, OSMT_TQ_OVER_CAND * 8 + 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -2664,9 +2611,9 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
                         tot[OSMT_TQ_WAYS] + tot[OSMT_TQ_MPS], tot[OSMT_TQ_WAYS], tot[OSMT_TQ_MPS]);
         n_way_cand = (size_t)tot[OSMT_TQ_WAYS], n_mp_cand = (size_t)tot[OSMT_TQ_MPS], n_cand = n_way_cand + n_mp_cand;
         /* 3. gather, 4. sort, mark */
-        off = 0;
-        const size_t o_cand = carve(n_cand * 4), o_apos = carve((n_cand + 1) * 4), o_blk2 = carve((n_cand / 256 + 1) * 8);
-        rc = alloc(&wg.work[2], "candidates");
+        pl = pool_layout();
+        const size_t o_cand = pl.add(n_cand * 4), o_apos = pl.add((n_cand + 1) * 4), o_blk2 = pl.add((n_cand / 256 + 1) * 8);
+        rc = wg.alloc(2, pl, "candidates");
         if (rc != OSMT_OK) return rc;
         char* w2 = wg.work[2];
         P.n_ways = (uint32_t)n_way_cand;
@@ -2689,20 +2636,20 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
             dev_free(ctx, areas);
         }
     } kg{ctx, st};
-    off = 0;
-    const size_t o_tiles = carve(n_tiles * sizeof(osmt_styled_tile)), o_base = carve((n_tiles + 1) * 4);
-    rc = alloc(&kg.head, "styled tiles");
+    pl = pool_layout();
+    const size_t o_tiles = pl.add(n_tiles * sizeof(osmt_styled_tile)), o_base = pl.add((n_tiles + 1) * 4);
+    rc = wg.alloc(&kg.head, pl, "styled tiles");
     if (rc != OSMT_OK) return rc;
     P.tiles = (osmt_styled_tile*)(kg.head + o_tiles);
     P.tile_base = (uint32_t*)(kg.head + o_base);
     if (n_tiles) {
-        HIP_TRY(mark(EV_GATHER0));
+        HIP_TRY(wg.mark(EV_GATHER0));
         HIP_TRY(osmt_launch_tq_gather(P, st));
-        HIP_TRY(mark(EV_SORT0));
+        HIP_TRY(wg.mark(EV_SORT0));
         HIP_TRY(osmt_launch_tq_sort(P, st));
-        HIP_TRY(mark(EV_MARK0));
+        HIP_TRY(wg.mark(EV_MARK0));
         HIP_TRY(osmt_launch_tq_mark(P, st));
-        HIP_TRY(mark(EV_MARK1));
+        HIP_TRY(wg.mark(EV_MARK1));
         /* second read-back: the area total, the most areas of a tile, the first tile over the limit */
         HIP_TRY(hipMemcpyAsync(tot + OSMT_TQ_AREAS, P.tot + OSMT_TQ_AREAS, 3 * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -2720,15 +2667,15 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
         HIP_TRY(hipMemsetAsync(P.tile_base, 0, 4, st));
     }
     /* 5. emit */
-    off = 0;
-    (void)carve(n_areas * sizeof(osmt_styled_area));
-    rc = alloc(&kg.areas, "styled areas");
+    pl = pool_layout();
+    (void)pl.add(n_areas * sizeof(osmt_styled_area));
+    rc = wg.alloc(&kg.areas, pl, "styled areas");
     if (rc != OSMT_OK) return rc;
     P.areas = (osmt_styled_area*)kg.areas;
     if (n_tiles) {
-        HIP_TRY(mark(EV_EMIT0));
+        HIP_TRY(wg.mark(EV_EMIT0));
         HIP_TRY(osmt_launch_tq_emit(P, st));
-        HIP_TRY(mark(EV_EMIT1));
+        HIP_TRY(wg.mark(EV_EMIT1));
     }
     styled_src in;
     in.tiles = P.tiles;
@@ -2748,16 +2695,11 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
     s->tq_geodata_id = b->geodata_id;
     kg.head = kg.areas = nullptr;
     if (trace && n_tiles) {
-        auto us = [&](int a, int b2) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
-            return ms * 1e3;
-        };
         fprintf(stderr,
                 "osmt tile query: span %.1f us, columns %.1f us, gather %.1f us, sort %.1f us, mark + scan %.1f us, emit %.1f us (%zu tiles, %zu items, "
                 "%zu + %zu candidates, at most %llu of one kind in a tile, %zu areas, at most %llu in a tile, %zu bytes sent)\n",
-                us(EV_SPAN0, EV_SPAN1), us(EV_COL0, EV_COL1), us(EV_GATHER0, EV_SORT0), us(EV_SORT0, EV_MARK0), us(EV_MARK0, EV_MARK1),
-                us(EV_EMIT0, EV_EMIT1), n_tiles, n_items, n_way_cand, n_mp_cand, tot[OSMT_TQ_MAX_CAND], n_areas, tot[OSMT_TQ_MAX_AREAS],
+                wg.us(EV_SPAN0, EV_SPAN1), wg.us(EV_COL0, EV_COL1), wg.us(EV_GATHER0, EV_SORT0), wg.us(EV_SORT0, EV_MARK0), wg.us(EV_MARK0, EV_MARK1),
+                wg.us(EV_EMIT0, EV_EMIT1), n_tiles, n_items, n_way_cand, n_mp_cand, tot[OSMT_TQ_MAX_CAND], n_areas, tot[OSMT_TQ_MAX_AREAS],
                 n_tiles * sizeof(osmt_query_tile) + sizeof bind);
     }
     return OSMT_OK;
@@ -2891,22 +2833,18 @@ static int glyph_labels_count(osmt_ctx* ctx, osmt_scene* sc, const osmt_glyph_la
         }
     }
     const size_t n_pairs = pair_inst.size();
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    const size_t o_inst = carve(gb ? n_glyphs * sizeof(osmt_glyph_instance) : 0);
+    pool_layout pl;
+    const size_t o_inst = pl.add(gb ? n_glyphs * sizeof(osmt_glyph_instance) : 0);
     /* text runs: what k_text_place reads */
     const size_t n_way = tb ? tb->n_way_pts : 0;
-    const size_t o_tlab = carve(tb ? n_labels * sizeof(osmt_label) : 0), o_trun = carve(tb ? n_labels * sizeof(osmt_text_run) : 0);
-    const size_t o_tgl = carve(tb && !label_font ? n_glyphs * sizeof(osmt_text_glyph) : 0), o_twp = carve(n_way * 8), o_tws = carve(n_way * 16);
+    const size_t o_tlab = pl.add(tb ? n_labels * sizeof(osmt_label) : 0), o_trun = pl.add(tb ? n_labels * sizeof(osmt_text_run) : 0);
+    const size_t o_tgl = pl.add(tb && !label_font ? n_glyphs * sizeof(osmt_text_glyph) : 0), o_twp = pl.add(n_way * 8), o_tws = pl.add(n_way * 16);
     /* string labels: what k_text_shape reads */
-    const size_t o_chr = carve(label_font ? n_glyphs * 4 : 0), o_lfn = carve(label_font ? n_labels * 4 : 0);
-    const size_t o_pi = carve(n_pairs * 4), o_pl = carve(n_pairs * 4), o_pc = carve(n_pairs * 4), o_pb = carve(n_pairs * 4);
-    const size_t o_blk = carve((n_pairs / 1024 + 1) * 4);
-    const size_t o_sum = carve(n_labels * sizeof(osmt_label_extent) + 4); /* the error word right behind: one read-back */
+    const size_t o_chr = pl.add(label_font ? n_glyphs * 4 : 0), o_lfn = pl.add(label_font ? n_labels * 4 : 0);
+    const size_t o_pi = pl.add(n_pairs * 4), o_pl = pl.add(n_pairs * 4), o_pc = pl.add(n_pairs * 4), o_pb = pl.add(n_pairs * 4);
+    const size_t o_blk = pl.add((n_pairs / 1024 + 1) * 4);
+    const size_t o_sum = pl.add(n_labels * sizeof(osmt_label_extent) + 4); /* the error word right behind: one read-back */
+    const size_t off = pl.size();
     HIP_TRY(dev_alloc(ctx, (void**)gtmp, off));
     char* base = *gtmp;
     gp->verts = snap.verts;
@@ -3205,31 +3143,26 @@ static int osmt_scene_set_labels_body(osmt_ctx* ctx, osmt_scene* sc, const osmt_
         bands.swap(dealt);
     }
 
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
+    pool_layout pl;
     const size_t EW = 3 * (size_t)W;
     const size_t words = (EW * EW + 31) / 32;
-    const size_t o_info = carve(n_labels * sizeof(osmt_labelinfo));
-    const size_t o_off = carve(((size_t)sc->n_jobs + 1) * 4);
-    const size_t o_segs = carve(n_segs_total * 32);
-    const size_t o_a = carve((cells + 1) * 8);
-    const size_t o_s = carve((wide_cells + 1) * 8);
-    const size_t o_bits = carve((bit_words + 2) * 8); /* + the word a funnel read may touch behind the last stream */
-    const size_t o_wide = carve((wide.size() + 1) * 4);
-    const size_t o_bands = carve((bands.size() + 1) * sizeof(osmt_label_band));
-    const size_t o_bm = carve(words * 4 <= 96 * 1024 ? 4 : (size_t)sc->n_jobs * words * 4); /* scale 1: the map lives in LDS */
-    const size_t o_tl = carve(n_labels * sizeof(osmt_tile_label));
-    const size_t o_tlc = carve((size_t)sc->n_jobs * 4);
-    const size_t o_ok = carve(n_labels);
-    const size_t o_err = carve(4);
-    hipError_t e = dev_alloc(ctx, (void**)&sc->d_lab_base, off + 256);
+    const size_t o_info = pl.add(n_labels * sizeof(osmt_labelinfo));
+    const size_t o_off = pl.add(((size_t)sc->n_jobs + 1) * 4);
+    const size_t o_segs = pl.add(n_segs_total * 32);
+    const size_t o_a = pl.add((cells + 1) * 8);
+    const size_t o_s = pl.add((wide_cells + 1) * 8);
+    const size_t o_bits = pl.add((bit_words + 2) * 8); /* + the word a funnel read may touch behind the last stream */
+    const size_t o_wide = pl.add((wide.size() + 1) * 4);
+    const size_t o_bands = pl.add((bands.size() + 1) * sizeof(osmt_label_band));
+    const size_t o_bm = pl.add(words * 4 <= 96 * 1024 ? 4 : (size_t)sc->n_jobs * words * 4); /* scale 1: the map lives in LDS */
+    const size_t o_tl = pl.add(n_labels * sizeof(osmt_tile_label));
+    const size_t o_tlc = pl.add((size_t)sc->n_jobs * 4);
+    const size_t o_ok = pl.add(n_labels);
+    const size_t o_err = pl.add(4);
+    hipError_t e = dev_alloc(ctx, (void**)&sc->d_lab_base, pl.size() + 256);
     if (e != hipSuccess) {
         sc->d_lab_base = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for labels failed: %s", off,
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for labels failed: %s", pl.size(),
                     hipGetErrorString(e));
     }
     char* base = sc->d_lab_base;
@@ -3351,39 +3284,25 @@ static int register_node_index_body(osmt_ctx* ctx, uint32_t geodata_id, const os
     const int rc = validate_node_index(x, geodata_id, ctx, &n);
     if (rc != OSMT_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_gid = carve(x->n_nodes * 8), o_off = carve((n + 1) * 4), o_refs = carve(x->n_node_refs * 4), o_zero = carve((n + 1) * 4);
-    char* pool = nullptr;
-    HIP_TRY(hipMalloc((void**)&pool, off));
+    pool_layout pl;
+    const size_t o_gid = pl.add(x->n_nodes * 8), o_off = pl.add((n + 1) * 4), o_refs = pl.add(x->n_node_refs * 4), o_zero = pl.add((n + 1) * 4);
+    table_upload up("node index", pl);
+    char* pool = up.pool;
     const std::vector<uint32_t> zeros(n + 1, 0u); /* the offsets of the empty second kind */
-    hipError_t e = hipSuccess;
-    auto put = [&](size_t o, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
-    };
-    put(o_gid, x->node_ids, x->n_nodes * 8);
-    put(o_off, x->node_off, (n + 1) * 4);
-    put(o_refs, x->nodes, x->n_node_refs * 4);
-    put(o_zero, zeros.data(), (n + 1) * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(pool);
-        return fail(OSMT_HIP_ERROR, "node index upload failed: %s", hipGetErrorString(e));
-    }
+    up.put(o_gid, x->node_ids, x->n_nodes * 8);
+    up.put(o_off, x->node_off, (n + 1) * 4);
+    up.put(o_refs, x->nodes, x->n_node_refs * 4);
+    up.put(o_zero, zeros.data(), (n + 1) * 4);
+    if (up.done() != OSMT_OK) return up.done();
     std::lock_guard<std::mutex> lk(ctx->mu);
     osmt_ctx::geodata_host& g = ctx->geodata[geodata_id];
-    if (g.d_node_index) { /* another thread was first */
-        (void)hipFree(pool);
-        return fail(OSMT_INVALID_ARG, "node index: geodata id %u has a node index already (one per file)", geodata_id);
-    }
+    if (g.d_node_index) return fail(OSMT_INVALID_ARG, "node index: geodata id %u has a node index already (one per file)", geodata_id); /* another thread was first */
     g.d_node_index = pool;
     g.d_node_gid = (const uint64_t*)(pool + o_gid);
     g.d_node_off = (const uint32_t*)(pool + o_off);
     g.d_node_refs = (const uint32_t*)(pool + o_refs);
     g.d_zero_off = (const uint32_t*)(pool + o_zero);
+    up.release();
     return OSMT_OK;
 }
 
@@ -3442,21 +3361,10 @@ static int sync_label_styles(osmt_ctx* ctx, const osmt_label_style_rec** styles,
             if (i && label_style_key_cmp(ctx->label_styles[order[i - 1]], ctx->label_styles[order[i]]) != 0) ++r;
             rk[order[i]] = r;
         }
-        osmt_label_style_rec* ds = nullptr;
-        uint32_t* dr = nullptr;
-        hipError_t e = hipMalloc((void**)&ds, std::max<size_t>(n, 1) * sizeof(osmt_label_style_rec));
-        if (e == hipSuccess) e = hipMalloc((void**)&dr, std::max<size_t>(n, 1) * 4);
-        if (e == hipSuccess && n) e = hipMemcpy(ds, ctx->label_styles.data(), n * sizeof(osmt_label_style_rec), hipMemcpyHostToDevice);
-        if (e == hipSuccess && n) e = hipMemcpy(dr, rk.data(), n * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (ds) (void)hipFree(ds);
-            if (dr) (void)hipFree(dr);
-            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "label style table upload failed: %s", hipGetErrorString(e));
-        }
-        if (ctx->d_label_styles) ctx->image_graveyard.push_back(ctx->d_label_styles);
-        if (ctx->d_label_rank) ctx->image_graveyard.push_back(ctx->d_label_rank);
-        ctx->d_label_styles = ds;
-        ctx->d_label_rank = dr;
+        const snap_part parts[2] = {{(void**)&ctx->d_label_styles, ctx->label_styles.data(), n * sizeof(osmt_label_style_rec), sizeof(osmt_label_style_rec)},
+                                    {(void**)&ctx->d_label_rank, rk.data(), n * 4, 4}};
+        const int rc = snapshot_replace(ctx, "label style table", parts, 2);
+        if (rc != OSMT_OK) return rc;
         ctx->d_n_label_styles = (uint32_t)n;
         ctx->label_styles_dirty = false;
     }
@@ -3504,28 +3412,16 @@ static int register_label_bindings_body(osmt_ctx* ctx, const osmt_label_bindings
     const int rc = validate_label_bindings(b, ctx, &n_nodes);
     if (rc != OSMT_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_no = carve((n_nodes + 1) * 4), o_b = carve(b->n_bindings * sizeof(osmt_label_binding)), o_to = carve((b->n_texts + 1) * 4);
-    const size_t o_c = carve(b->n_chars * 4);
-    char* pool = nullptr;
-    HIP_TRY(hipMalloc((void**)&pool, off));
-    hipError_t e = hipSuccess;
-    auto put = [&](size_t o, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
-    };
-    put(o_no, b->node_off, (n_nodes + 1) * 4);
-    put(o_b, b->bindings, b->n_bindings * sizeof(osmt_label_binding));
-    put(o_to, b->text_off, (b->n_texts + 1) * 4);
-    put(o_c, b->chars, b->n_chars * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(pool);
-        return fail(OSMT_HIP_ERROR, "label bindings upload failed: %s", hipGetErrorString(e));
-    }
+    pool_layout pl;
+    const size_t o_no = pl.add((n_nodes + 1) * 4), o_b = pl.add(b->n_bindings * sizeof(osmt_label_binding)), o_to = pl.add((b->n_texts + 1) * 4);
+    const size_t o_c = pl.add(b->n_chars * 4);
+    table_upload up("label bindings", pl);
+    char* pool = up.pool;
+    up.put(o_no, b->node_off, (n_nodes + 1) * 4);
+    up.put(o_b, b->bindings, b->n_bindings * sizeof(osmt_label_binding));
+    up.put(o_to, b->text_off, (b->n_texts + 1) * 4);
+    up.put(o_c, b->chars, b->n_chars * 4);
+    if (up.done() != OSMT_OK) return up.done();
     osmt_ctx::label_bindings_host h;
     h.geodata_id = b->geodata_id, h.zoom_lo = b->zoom_lo, h.zoom_hi = b->zoom_hi;
     h.d_pool = pool;
@@ -3535,12 +3431,10 @@ static int register_label_bindings_body(osmt_ctx* ctx, const osmt_label_bindings
     h.dev.chars = (const uint32_t*)(pool + o_c);
     h.n_nodes = n_nodes, h.n_bindings = b->n_bindings, h.n_texts = b->n_texts, h.n_chars = b->n_chars;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->label_bindings.size() + 1 >= 0xFFFFFFFFull) {
-        (void)hipFree(pool);
-        return fail(OSMT_INVALID_ARG, "label bindings table too large");
-    }
+    if (ctx->label_bindings.size() + 1 >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "label bindings table too large");
     *out_id = (uint32_t)ctx->label_bindings.size();
     ctx->label_bindings.push_back(h);
+    up.release();
     return OSMT_OK;
 }
 
@@ -3604,43 +3498,14 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     int rc = sync_label_styles(ctx, &d_styles, &d_rank);
     if (rc != OSMT_OK) return rc;
     /* work[0]: per tile, [1]: per item, [2]: per candidate, [3]: per label, [4]: the chars — given back at the end */
-    struct work_guard {
-        osmt_ctx* ctx;
-        hipStream_t st = nullptr;
-        char* work[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~work_guard() {
-            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers */
-            for (char* p : work) dev_free(ctx, p);
-            stream_release(ctx, st);
-        }
-    } wg{ctx};
-    HIP_TRY(stream_acquire(ctx, &wg.st));
-    hipStream_t st = wg.st;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    auto alloc = [&](char** out, const char* what) {
-        const hipError_t e = dev_alloc(ctx, (void**)out, off + 256);
-        if (e == hipSuccess) return (int)OSMT_OK;
-        *out = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the tile labels (%s) failed: %s", off, what, hipGetErrorString(e));
-    };
-    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    /* the trace: the device time of the stages */
     enum { EV_Q0, EV_Q1, EV_G0, EV_M0, EV_M1, EV_O0, EV_O1, EV_E0, EV_E1, EV_N };
-    hipEvent_t ev[EV_N] = {};
-    struct ev_guard {
-        hipEvent_t* ev;
-        ~ev_guard() {
-            for (int i = 0; i < EV_N; ++i)
-                if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    } evg{ev};
-    if (trace)
-        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
-    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+    call_work wg(ctx, "tile labels");
+    const int brc = wg.begin(EV_N);
+    if (brc != OSMT_OK) return brc;
+    hipStream_t st = wg.st;
+    const bool trace = wg.trace;
+    pool_layout pl;
 
     std::vector<osmt_label>& labels = nb->labels;
     std::vector<osmt_string_run>& runs = nb->runs;
@@ -3655,11 +3520,11 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         memset(&Q, 0, sizeof Q);
         osmt_tl_pass P;
         memset(&P, 0, sizeof P);
-        off = 0;
-        const size_t o_q = carve(n_tiles * sizeof(osmt_query_tile)), o_bind = carve(sizeof bind), o_c0 = carve(n_tiles * 4), o_ib = carve((n_tiles + 1) * 4);
-        const size_t o_tw = carve((n_tiles + 1) * 4), o_tm = carve((n_tiles + 1) * 4), o_tot = carve((OSMT_TQ_N + OSMT_TL_N) * 8);
-        const size_t o_blk0 = carve((n_tiles / 256 + 1) * 8), o_ih = carve(std::max<size_t>(icon_h.size(), 1) * 4), o_jo = carve((n_tiles + 1) * 4);
-        rc = alloc(&wg.work[0], "tiles");
+        pl = pool_layout();
+        const size_t o_q = pl.add(n_tiles * sizeof(osmt_query_tile)), o_bind = pl.add(sizeof bind), o_c0 = pl.add(n_tiles * 4), o_ib = pl.add((n_tiles + 1) * 4);
+        const size_t o_tw = pl.add((n_tiles + 1) * 4), o_tm = pl.add((n_tiles + 1) * 4), o_tot = pl.add((OSMT_TQ_N + OSMT_TL_N) * 8);
+        const size_t o_blk0 = pl.add((n_tiles / 256 + 1) * 8), o_ih = pl.add(std::max<size_t>(icon_h.size(), 1) * 4), o_jo = pl.add((n_tiles + 1) * 4);
+        rc = wg.alloc(0, pl, "tiles");
         if (rc != OSMT_OK) return rc;
         char* w0 = wg.work[0];
         HIP_TRY(hipMemcpyAsync(w0 + o_q, q.data(), n_tiles * sizeof(osmt_query_tile), hipMemcpyHostToDevice, st));
@@ -3677,17 +3542,17 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         Q.t_mbase = (uint32_t*)(w0 + o_tm);
         Q.tot = (unsigned long long*)(w0 + o_tot);
         Q.blk = (unsigned long long*)(w0 + o_blk0);
-        HIP_TRY(mark(EV_Q0));
+        HIP_TRY(wg.mark(EV_Q0));
         HIP_TRY(osmt_launch_tq_span(Q, st));
         HIP_TRY(hipMemcpyAsync(tq_tot, Q.tot, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (tq_tot[OSMT_TQ_ITEMS] >= 0xFFFFFFFFull)
             return fail(OSMT_UNSUPPORTED, "tile labels: the batch needs %llu (tile, column) items (> 2^32): split the batch", tq_tot[OSMT_TQ_ITEMS]);
         n_items = (size_t)tq_tot[OSMT_TQ_ITEMS];
-        off = 0;
-        const size_t o_it = carve(n_items * 4), o_ws = carve(n_items * 4), o_ms = carve(n_items * 4), o_wb = carve((n_items + 1) * 4);
-        const size_t o_mb = carve((n_items + 1) * 4), o_blk1 = carve((n_items / 256 + 1) * 8);
-        rc = alloc(&wg.work[1], "columns");
+        pl = pool_layout();
+        const size_t o_it = pl.add(n_items * 4), o_ws = pl.add(n_items * 4), o_ms = pl.add(n_items * 4), o_wb = pl.add((n_items + 1) * 4);
+        const size_t o_mb = pl.add((n_items + 1) * 4), o_blk1 = pl.add((n_items / 256 + 1) * 8);
+        rc = wg.alloc(1, pl, "columns");
         if (rc != OSMT_OK) return rc;
         char* w1 = wg.work[1];
         Q.n_items = (uint32_t)n_items;
@@ -3698,7 +3563,7 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         Q.mbase = (uint32_t*)(w1 + o_mb);
         Q.blk = (unsigned long long*)(w1 + o_blk1);
         HIP_TRY(osmt_launch_tq_columns(Q, st));
-        HIP_TRY(mark(EV_Q1));
+        HIP_TRY(wg.mark(EV_Q1));
         /* first read-back: the candidate total, the first tile over the limit — nothing is gathered before */
         HIP_TRY(hipMemcpyAsync(tq_tot, Q.tot, OSMT_TQ_OVER_CAND * 8 + 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -3713,15 +3578,15 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         if (tq_tot[OSMT_TQ_WAYS] >= 0xFFFFFFFFull)
             return fail(OSMT_UNSUPPORTED, "tile labels: the batch gathers %llu node references (> 2^32): split the batch", tq_tot[OSMT_TQ_WAYS]);
         n_cand = (size_t)tq_tot[OSMT_TQ_WAYS];
-        off = 0;
-        const size_t o_cand = carve(n_cand * 4), o_lpos = carve((n_cand + 1) * 4), o_blk2 = carve((n_cand / 256 + 1) * 8);
-        rc = alloc(&wg.work[2], "candidates");
+        pl = pool_layout();
+        const size_t o_cand = pl.add(n_cand * 4), o_lpos = pl.add((n_cand + 1) * 4), o_blk2 = pl.add((n_cand / 256 + 1) * 8);
+        rc = wg.alloc(2, pl, "candidates");
         if (rc != OSMT_OK) return rc;
         char* w2 = wg.work[2];
         Q.n_ways = (uint32_t)n_cand;
         Q.n_mps = 0u;
         Q.cand = (uint32_t*)(w2 + o_cand);
-        HIP_TRY(mark(EV_G0));
+        HIP_TRY(wg.mark(EV_G0));
         HIP_TRY(osmt_launch_tq_gather(Q, st));
         HIP_TRY(osmt_launch_tq_sort(Q, st));
         /* expand */
@@ -3741,9 +3606,9 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         P.job_label_off = (uint32_t*)(w0 + o_jo);
         P.blk = (unsigned long long*)(w2 + o_blk2);
         P.tot = Q.tot + OSMT_TQ_N;
-        HIP_TRY(mark(EV_M0));
+        HIP_TRY(wg.mark(EV_M0));
         HIP_TRY(osmt_launch_tl_mark(P, st));
-        HIP_TRY(mark(EV_M1));
+        HIP_TRY(wg.mark(EV_M1));
         /* second read-back: the label total, the most labels of a tile, the first tile over the limit */
         HIP_TRY(hipMemcpyAsync(tl_tot, P.tot, 3 * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -3758,11 +3623,11 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
             return fail(OSMT_UNSUPPORTED, "tile labels: the batch has %llu node labels (> 2^32): split the batch", tl_tot[OSMT_TL_LABELS]);
         n_labels = (size_t)tl_tot[OSMT_TL_LABELS];
         max_labels = tl_tot[OSMT_TL_MAX_LABELS];
-        off = 0;
-        const size_t o_keys = carve(n_labels * 16), o_eb = carve(n_labels * 4), o_en = carve(n_labels * 4), o_cp = carve((n_labels + 1) * 4);
-        const size_t o_cs = carve(n_labels * 4), o_blk3 = carve((n_labels / 256 + 1) * 8), o_lab = carve(n_labels * sizeof(osmt_label));
-        const size_t o_run = carve(n_labels * sizeof(osmt_string_run));
-        rc = alloc(&wg.work[3], "labels");
+        pl = pool_layout();
+        const size_t o_keys = pl.add(n_labels * 16), o_eb = pl.add(n_labels * 4), o_en = pl.add(n_labels * 4), o_cp = pl.add((n_labels + 1) * 4);
+        const size_t o_cs = pl.add(n_labels * 4), o_blk3 = pl.add((n_labels / 256 + 1) * 8), o_lab = pl.add(n_labels * sizeof(osmt_label));
+        const size_t o_run = pl.add(n_labels * sizeof(osmt_string_run));
+        rc = wg.alloc(3, pl, "labels");
         if (rc != OSMT_OK) return rc;
         char* w3 = wg.work[3];
         P.n_labels = (uint32_t)n_labels;
@@ -3774,24 +3639,24 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         P.blk = (unsigned long long*)(w3 + o_blk3);
         P.labels = (osmt_label*)(w3 + o_lab);
         P.runs = (osmt_string_run*)(w3 + o_run);
-        HIP_TRY(mark(EV_O0));
+        HIP_TRY(wg.mark(EV_O0));
         HIP_TRY(osmt_launch_tl_order(P, st));
-        HIP_TRY(mark(EV_O1));
+        HIP_TRY(wg.mark(EV_O1));
         /* third read-back: the char total */
         HIP_TRY(hipMemcpyAsync(tl_tot + OSMT_TL_CHARS, P.tot + OSMT_TL_CHARS, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (tl_tot[OSMT_TL_CHARS] >= 0xFFFFFFFFull)
             return fail(OSMT_UNSUPPORTED, "tile labels: the batch has %llu chars of label text (> 2^32): split the batch", tl_tot[OSMT_TL_CHARS]);
         n_chars = (size_t)tl_tot[OSMT_TL_CHARS];
-        off = 0;
-        (void)carve(n_chars * 4);
-        rc = alloc(&wg.work[4], "chars");
+        pl = pool_layout();
+        (void)pl.add(n_chars * 4);
+        rc = wg.alloc(4, pl, "chars");
         if (rc != OSMT_OK) return rc;
         P.n_chars = (uint32_t)n_chars;
         P.chars = (uint32_t*)wg.work[4];
-        HIP_TRY(mark(EV_E0));
+        HIP_TRY(wg.mark(EV_E0));
         HIP_TRY(osmt_launch_tl_emit(P, st));
-        HIP_TRY(mark(EV_E1));
+        HIP_TRY(wg.mark(EV_E1));
         /* the batch comes back: a few KB per tile */
         labels.resize(n_labels), runs.resize(n_labels), chars.resize(n_chars);
         if (n_labels) HIP_TRY(hipMemcpyAsync(labels.data(), P.labels, n_labels * sizeof(osmt_label), hipMemcpyDeviceToHost, st));
@@ -3800,15 +3665,10 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         HIP_TRY(hipMemcpyAsync(job_off.data(), P.job_label_off, (n_tiles + 1) * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (trace) {
-            auto us = [&](int a, int b2) {
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
-                return ms * 1e3;
-            };
             fprintf(stderr,
                     "osmt tile labels: span + columns %.1f us, gather + sort %.1f us, mark + scan %.1f us, expand + sort + count %.1f us, emit %.1f us "
                     "(%zu tiles, %zu items, %zu candidates, %zu labels, at most %llu in a tile, %zu chars, %zu bytes read back)\n",
-                    us(EV_Q0, EV_Q1), us(EV_G0, EV_M0), us(EV_M0, EV_M1), us(EV_O0, EV_O1), us(EV_E0, EV_E1), n_tiles, n_items, n_cand, n_labels, max_labels,
+                    wg.us(EV_Q0, EV_Q1), wg.us(EV_G0, EV_M0), wg.us(EV_M0, EV_M1), wg.us(EV_O0, EV_O1), wg.us(EV_E0, EV_E1), n_tiles, n_items, n_cand, n_labels, max_labels,
                     n_chars, n_labels * (sizeof(osmt_label) + sizeof(osmt_string_run)) + n_chars * 4 + (n_tiles + 1) * 4);
         }
     }
@@ -4083,15 +3943,10 @@ static int osmt_label_positions_begin_body(osmt_ctx* ctx, const osmt_label_reque
     HIP_TRY(stream_acquire(ctx, &j->st));
     const size_t n = j->n;
     const uint32_t n_slots = (uint32_t)std::min<size_t>(n, OSMT_PL_MAX_SLOTS);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    const size_t o_req = take(n * sizeof(osmt_pl_req)), o_rings = take(b->n_rings * sizeof(osmt_ring)), o_pts = take(b->n_pts * 16),
-                 o_keep = take(keep_words * 4), o_over = take(n * 4), o_back = take(n * sizeof(osmt_label_position) + 16),
-                 o_ws = take((size_t)n_slots * OSMT_PL_CELL_DOUBLES * OSMT_PL_GLOBAL_CELLS * sizeof(double));
+    pool_layout pl;
+    const size_t o_req = pl.add(n * sizeof(osmt_pl_req)), o_rings = pl.add(b->n_rings * sizeof(osmt_ring)), o_pts = pl.add(b->n_pts * 16),
+                 o_keep = pl.add(keep_words * 4), o_over = pl.add(n * 4), o_back = pl.add(n * sizeof(osmt_label_position) + 16),
+                 o_ws = pl.add((size_t)n_slots * OSMT_PL_CELL_DOUBLES * OSMT_PL_GLOBAL_CELLS * sizeof(double));
     const size_t back_bytes = n * sizeof(osmt_label_position) + 16;
     j->back_off = align_up(n * sizeof(osmt_pl_req), 64);
     j->stage = (char*)stage_acquire(ctx, j->back_off + back_bytes);
@@ -4102,6 +3957,7 @@ static int osmt_label_positions_begin_body(osmt_ctx* ctx, const osmt_label_reque
         rq[i] = {b->requests[i].ring_off, b->requests[i].n_rings, words, 0u, b->requests[i].scale};
         words += b->requests[i].n_rings;
     }
+    const size_t off = pl.size();
     HIP_TRY(dev_alloc(ctx, (void**)&j->d_base, off));
     char* d = j->d_base;
     HIP_TRY(hipMemcpyAsync(d + o_req, rq, n * sizeof(osmt_pl_req), hipMemcpyHostToDevice, j->st));
@@ -4202,22 +4058,16 @@ static int register_node_mercator_body(osmt_ctx* ctx, uint32_t geodata_id, const
     const int rc = validate_node_mercator(f, n, geodata_id, ctx);
     if (rc != OSMT_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    void* pool = nullptr;
-    HIP_TRY(hipMalloc(&pool, std::max<size_t>(n * 16, 16)));
-    if (n) {
-        const hipError_t e = hipMemcpy(pool, f, n * 16, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(pool);
-            return fail(OSMT_HIP_ERROR, "node mercator upload failed: %s", hipGetErrorString(e));
-        }
-    }
+    pool_layout pl;
+    (void)pl.add(n * 16);
+    table_upload up("node mercator", pl);
+    up.put(0, f, n * 16);
+    if (up.done() != OSMT_OK) return up.done();
     std::lock_guard<std::mutex> lk(ctx->mu);
     osmt_ctx::geodata_host& g = ctx->geodata[geodata_id];
-    if (g.d_factors) { /* another thread was first */
-        (void)hipFree(pool);
-        return fail(OSMT_INVALID_ARG, "node mercator: geodata id %u has its factors already (one table per file)", geodata_id);
-    }
-    g.d_factors = (const double2*)pool;
+    if (g.d_factors) return fail(OSMT_INVALID_ARG, "node mercator: geodata id %u has its factors already (one table per file)", geodata_id); /* another thread was first */
+    g.d_factors = (const double2*)up.pool;
+    up.release();
     return OSMT_OK;
 }
 
@@ -4266,15 +4116,11 @@ static int label_tiles_expand(osmt_ctx* ctx, const osmt_label_tile_batch* b, con
                               const std::function<size_t(size_t)>& extra_of, size_t* extra_off, osmt_an_pass* out_pass,
                               const osmt_label_tile_request* d_req = nullptr, const osmt_query_tile* d_tiles = nullptr) {
     const size_t n = b->n_requests;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_req = take(d_req ? 0 : n * sizeof(osmt_label_tile_request)), o_tiles = take(d_req ? 0 : b->n_tiles * sizeof(osmt_query_tile)),
-                 o_rpos = take((n + 1) * 4),
-                 o_ppos = take((n + 1) * 4), o_blk = take(((n + 255) / 256 + 1) * 8), o_tot = take(OSMT_AN_N * 8);
+    pool_layout pl;
+    const size_t o_req = pl.add(d_req ? 0 : n * sizeof(osmt_label_tile_request)), o_tiles = pl.add(d_req ? 0 : b->n_tiles * sizeof(osmt_query_tile)),
+                 o_rpos = pl.add((n + 1) * 4),
+                 o_ppos = pl.add((n + 1) * 4), o_blk = pl.add(((n + 255) / 256 + 1) * 8), o_tot = pl.add(OSMT_AN_N * 8);
+    size_t off = pl.size();
     HIP_TRY(dev_alloc(ctx, (void**)&j->d_front, off));
     char* d = j->d_front;
     if (!d_req) { /* d_req, d_tiles: the requests and tiles are on the device already (b->requests and b->tiles are not read) */
@@ -4304,10 +4150,10 @@ static int label_tiles_expand(osmt_ctx* ctx, const osmt_label_tile_batch* b, con
     a.n_pts = (uint32_t)n_pts;
     *out_pass = a;
     if (sizes_only) return OSMT_OK;
-    off = 0;
-    const size_t o_base = take((n_rings + 1) * 4), o_src = take(n_rings * 4), o_rreq = take(n_rings * 4), o_blk2 = take(((n_rings + 255) / 256 + 1) * 8),
-                 o_pl = take(n * sizeof(osmt_pl_req)), o_rings = take(n_rings * sizeof(osmt_ring)), o_pts = take(n_pts * 16);
-    *extra_off = off;
+    pl = pool_layout();
+    const size_t o_base = pl.add((n_rings + 1) * 4), o_src = pl.add(n_rings * 4), o_rreq = pl.add(n_rings * 4), o_blk2 = pl.add(((n_rings + 255) / 256 + 1) * 8),
+                 o_pl = pl.add(n * sizeof(osmt_pl_req)), o_rings = pl.add(n_rings * sizeof(osmt_ring)), o_pts = pl.add(n_pts * 16);
+    *extra_off = off = pl.size();
     HIP_TRY(dev_alloc(ctx, (void**)&j->d_base, off + extra_of((size_t)n_rings)));
     d = j->d_base;
     a.ring_base = (uint32_t*)(d + o_base);
@@ -4350,15 +4196,10 @@ static int osmt_label_positions_tiles_begin_body(osmt_ctx* ctx, const osmt_label
     /* the work areas of the search, behind the arrays of the projection */
     size_t o_keep = 0, o_over = 0, o_back = 0, o_ws = 0;
     auto search_bytes = [&](size_t n_rings) {
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            const size_t o = off;
-            off = align_up(off + std::max<size_t>(bytes, 4), 256);
-            return o;
-        };
-        o_keep = take(n_rings * 4), o_over = take(n * 4), o_back = take(back_bytes);
-        o_ws = take((size_t)n_slots * OSMT_PL_CELL_DOUBLES * OSMT_PL_GLOBAL_CELLS * sizeof(double));
-        return off;
+        pool_layout pl;
+        o_keep = pl.add(n_rings * 4), o_over = pl.add(n * 4), o_back = pl.add(back_bytes);
+        o_ws = pl.add((size_t)n_slots * OSMT_PL_CELL_DOUBLES * OSMT_PL_GLOBAL_CELLS * sizeof(double));
+        return pl.size();
     };
     osmt_an_pass p{};
     size_t x0 = 0;
@@ -4472,30 +4313,18 @@ static int register_area_label_bindings_body(osmt_ctx* ctx, const osmt_area_labe
     const int rc = validate_area_label_bindings(b, ctx, &n_ways, &n_mps);
     if (rc != OSMT_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_wo = carve((n_ways + 1) * 4), o_mo = carve((n_mps + 1) * 4), o_wb = carve(b->n_way_bindings * sizeof(osmt_label_binding));
-    const size_t o_mb = carve(b->n_multipolygon_bindings * sizeof(osmt_label_binding)), o_to = carve((b->n_texts + 1) * 4), o_c = carve(b->n_chars * 4);
-    char* pool = nullptr;
-    HIP_TRY(hipMalloc((void**)&pool, off));
-    hipError_t e = hipSuccess;
-    auto put = [&](size_t o, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
-    };
-    put(o_wo, b->way_off, (n_ways + 1) * 4);
-    put(o_mo, b->multipolygon_off, (n_mps + 1) * 4);
-    put(o_wb, b->way_bindings, b->n_way_bindings * sizeof(osmt_label_binding));
-    put(o_mb, b->multipolygon_bindings, b->n_multipolygon_bindings * sizeof(osmt_label_binding));
-    put(o_to, b->text_off, (b->n_texts + 1) * 4);
-    put(o_c, b->chars, b->n_chars * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(pool);
-        return fail(OSMT_HIP_ERROR, "area label bindings upload failed: %s", hipGetErrorString(e));
-    }
+    pool_layout pl;
+    const size_t o_wo = pl.add((n_ways + 1) * 4), o_mo = pl.add((n_mps + 1) * 4), o_wb = pl.add(b->n_way_bindings * sizeof(osmt_label_binding));
+    const size_t o_mb = pl.add(b->n_multipolygon_bindings * sizeof(osmt_label_binding)), o_to = pl.add((b->n_texts + 1) * 4), o_c = pl.add(b->n_chars * 4);
+    table_upload up("area label bindings", pl);
+    char* pool = up.pool;
+    up.put(o_wo, b->way_off, (n_ways + 1) * 4);
+    up.put(o_mo, b->multipolygon_off, (n_mps + 1) * 4);
+    up.put(o_wb, b->way_bindings, b->n_way_bindings * sizeof(osmt_label_binding));
+    up.put(o_mb, b->multipolygon_bindings, b->n_multipolygon_bindings * sizeof(osmt_label_binding));
+    up.put(o_to, b->text_off, (b->n_texts + 1) * 4);
+    up.put(o_c, b->chars, b->n_chars * 4);
+    if (up.done() != OSMT_OK) return up.done();
     osmt_ctx::area_label_bindings_host h;
     h.geodata_id = b->geodata_id, h.zoom_lo = b->zoom_lo, h.zoom_hi = b->zoom_hi;
     h.d_pool = pool;
@@ -4508,12 +4337,10 @@ static int register_area_label_bindings_body(osmt_ctx* ctx, const osmt_area_labe
     h.n_ways = n_ways, h.n_mps = n_mps, h.n_way_bindings = b->n_way_bindings, h.n_mp_bindings = b->n_multipolygon_bindings;
     h.n_texts = b->n_texts, h.n_chars = b->n_chars;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->area_label_bindings.size() + 1 >= 0xFFFFFFFFull) {
-        (void)hipFree(pool);
-        return fail(OSMT_INVALID_ARG, "area label bindings table too large");
-    }
+    if (ctx->area_label_bindings.size() + 1 >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "area label bindings table too large");
     *out_id = (uint32_t)ctx->area_label_bindings.size();
     ctx->area_label_bindings.push_back(h);
+    up.release();
     return OSMT_OK;
 }
 
@@ -4613,60 +4440,35 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     if (rc != OSMT_OK) return rc;
     /* the job carries the stream, the pinned words of the totals and the two allocations of the anchors' projection;
      * work[0]: per tile, [1]: per item, [2]: per candidate, [3]: per label, [4]: requests, [5]: chars and way points */
-    struct work_guard {
-        osmt_ctx* ctx;
-        osmt_label_job* j = nullptr;
-        char* work[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~work_guard() {
-            if (j && j->st) (void)hipStreamSynchronize(j->st); /* nothing may still read the buffers */
-            for (char* p : work) dev_free(ctx, p);
-            label_job_free(j);
-        }
-    } wg{ctx};
-    wg.j = new osmt_label_job();
-    osmt_label_job* j = wg.j;
+    struct job_guard {
+        osmt_label_job* j;
+        ~job_guard() { label_job_free(j); }
+    } jg{new osmt_label_job()};
+    osmt_label_job* j = jg.j;
     j->ctx = ctx;
     HIP_TRY(stream_acquire(ctx, &j->st));
     hipStream_t st = j->st;
+    /* the trace: the device time of the stages */
+    enum { EV_Q0, EV_Q1, EV_X0, EV_X1, EV_A0, EV_A1, EV_C0, EV_C1, EV_E0, EV_E1, EV_N };
+    call_work wg(ctx, "area labels", st); /* behind the job's guard: it waits for the job's stream before the job gives it back */
+    rc = wg.begin(EV_N);
+    if (rc != OSMT_OK) return rc;
+    const bool trace = wg.trace;
     j->stage = (char*)stage_acquire(ctx, 256);
     if (!j->stage) return fail(OSMT_OOM, "pinned staging for the totals could not be allocated");
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    auto alloc = [&](char** o, const char* what) {
-        const hipError_t e = dev_alloc(ctx, (void**)o, off + 256);
-        if (e == hipSuccess) return (int)OSMT_OK;
-        *o = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the area labels (%s) failed: %s", off, what, hipGetErrorString(e));
-    };
-    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
-    enum { EV_Q0, EV_Q1, EV_X0, EV_X1, EV_A0, EV_A1, EV_C0, EV_C1, EV_E0, EV_E1, EV_N };
-    hipEvent_t ev[EV_N] = {};
-    struct ev_guard {
-        hipEvent_t* ev;
-        ~ev_guard() {
-            for (int i = 0; i < EV_N; ++i)
-                if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    } evg{ev};
-    if (trace)
-        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
-    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+    pool_layout pl;
 
     unsigned long long tq_tot[OSMT_TQ_N] = {}, al_tot[OSMT_AL_N] = {};
     osmt_tq_pass Q;
     memset(&Q, 0, sizeof Q);
     osmt_al_pass P;
     memset(&P, 0, sizeof P);
-    off = 0;
-    const size_t o_q = carve(n_tiles * sizeof(osmt_query_tile)), o_bind = carve(sizeof bind), o_tqb = carve(sizeof tq_bind), o_c0 = carve(n_tiles * 4);
-    const size_t o_ib = carve((n_tiles + 1) * 4), o_tw = carve((n_tiles + 1) * 4), o_tm = carve((n_tiles + 1) * 4), o_tot = carve((OSMT_TQ_N + OSMT_AL_N) * 8);
-    const size_t o_blk0 = carve((n_tiles / 256 + 1) * 8), o_ih = carve(std::max<size_t>(icon_h.size(), 1) * 4), o_jo = carve((n_tiles + 1) * 4);
-    const size_t o_st = carve(n_tiles * sizeof(osmt_styled_tile)), o_an = carve(std::max<size_t>(n_anchors, 1) * sizeof(osmt_area_anchor));
-    rc = alloc(&wg.work[0], "tiles");
+    pl = pool_layout();
+    const size_t o_q = pl.add(n_tiles * sizeof(osmt_query_tile)), o_bind = pl.add(sizeof bind), o_tqb = pl.add(sizeof tq_bind), o_c0 = pl.add(n_tiles * 4);
+    const size_t o_ib = pl.add((n_tiles + 1) * 4), o_tw = pl.add((n_tiles + 1) * 4), o_tm = pl.add((n_tiles + 1) * 4), o_tot = pl.add((OSMT_TQ_N + OSMT_AL_N) * 8);
+    const size_t o_blk0 = pl.add((n_tiles / 256 + 1) * 8), o_ih = pl.add(std::max<size_t>(icon_h.size(), 1) * 4), o_jo = pl.add((n_tiles + 1) * 4);
+    const size_t o_st = pl.add(n_tiles * sizeof(osmt_styled_tile)), o_an = pl.add(std::max<size_t>(n_anchors, 1) * sizeof(osmt_area_anchor));
+    rc = wg.alloc(0, pl, "tiles");
     if (rc != OSMT_OK) return rc;
     char* w0 = wg.work[0];
     HIP_TRY(hipMemcpyAsync(w0 + o_q, q.data(), n_tiles * sizeof(osmt_query_tile), hipMemcpyHostToDevice, st));
@@ -4688,17 +4490,17 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     Q.blk = (unsigned long long*)(w0 + o_blk0);
     Q.tiles = (osmt_styled_tile*)(w0 + o_st);
     Q.tile_base = (uint32_t*)(w0 + o_jo);
-    HIP_TRY(mark(EV_Q0));
+    HIP_TRY(wg.mark(EV_Q0));
     HIP_TRY(osmt_launch_tq_span(Q, st));
     HIP_TRY(hipMemcpyAsync(tq_tot, Q.tot, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (tq_tot[OSMT_TQ_ITEMS] >= 0xFFFFFFFFull)
         return fail(OSMT_UNSUPPORTED, "area labels: the batch needs %llu (tile, column) items (> 2^32): split the batch", tq_tot[OSMT_TQ_ITEMS]);
     const size_t n_items = (size_t)tq_tot[OSMT_TQ_ITEMS];
-    off = 0;
-    const size_t o_it = carve(n_items * 4), o_ws = carve(n_items * 4), o_ms = carve(n_items * 4), o_wb = carve((n_items + 1) * 4);
-    const size_t o_mb = carve((n_items + 1) * 4), o_blk1 = carve((n_items / 256 + 1) * 8);
-    rc = alloc(&wg.work[1], "columns");
+    pl = pool_layout();
+    const size_t o_it = pl.add(n_items * 4), o_ws = pl.add(n_items * 4), o_ms = pl.add(n_items * 4), o_wb = pl.add((n_items + 1) * 4);
+    const size_t o_mb = pl.add((n_items + 1) * 4), o_blk1 = pl.add((n_items / 256 + 1) * 8);
+    rc = wg.alloc(1, pl, "columns");
     if (rc != OSMT_OK) return rc;
     char* w1 = wg.work[1];
     Q.n_items = (uint32_t)n_items;
@@ -4725,10 +4527,10 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     if (tq_tot[OSMT_TQ_WAYS] + tq_tot[OSMT_TQ_MPS] >= 0xFFFFFFFFull)
         return fail(OSMT_UNSUPPORTED, "area labels: the batch gathers %llu references (> 2^32): split the batch", tq_tot[OSMT_TQ_WAYS] + tq_tot[OSMT_TQ_MPS]);
     const size_t n_cand = (size_t)(tq_tot[OSMT_TQ_WAYS] + tq_tot[OSMT_TQ_MPS]);
-    off = 0;
-    const size_t o_cand = carve(n_cand * 4), o_apos = carve((n_cand + 1) * 4), o_need = carve((n_cand + 1) * 4), o_ov = carve(n_cand * 4);
-    const size_t o_blk2 = carve((n_cand / 256 + 1) * 8);
-    rc = alloc(&wg.work[2], "candidates");
+    pl = pool_layout();
+    const size_t o_cand = pl.add(n_cand * 4), o_apos = pl.add((n_cand + 1) * 4), o_need = pl.add((n_cand + 1) * 4), o_ov = pl.add(n_cand * 4);
+    const size_t o_blk2 = pl.add((n_cand / 256 + 1) * 8);
+    rc = wg.alloc(2, pl, "candidates");
     if (rc != OSMT_OK) return rc;
     char* w2 = wg.work[2];
     Q.n_ways = (uint32_t)tq_tot[OSMT_TQ_WAYS];
@@ -4739,7 +4541,7 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     HIP_TRY(osmt_launch_tq_gather(Q, st));
     HIP_TRY(osmt_launch_tq_sort(Q, st));
     HIP_TRY(osmt_launch_tq_mark(Q, st)); /* with the label bindings' offsets: apos counts labels, tile_base is job_label_off */
-    HIP_TRY(mark(EV_Q1));
+    HIP_TRY(wg.mark(EV_Q1));
     HIP_TRY(hipMemcpyAsync(tq_tot + OSMT_TQ_AREAS, Q.tot + OSMT_TQ_AREAS, 3 * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (tq_tot[OSMT_TQ_OVER_AREAS] != ~0ull) {
@@ -4753,11 +4555,11 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         return fail(OSMT_UNSUPPORTED, "area labels: the batch has %llu area labels (> 2^32): split the batch", tq_tot[OSMT_TQ_AREAS]);
     const size_t n_labels = (size_t)tq_tot[OSMT_TQ_AREAS];
     /* 2. expand: keys, element tables, the pairs that are searched */
-    off = 0;
-    const size_t o_keys = carve(n_labels * 16), o_eb = carve(n_labels * 4), o_es = carve(n_labels * 4), o_cp = carve((n_labels + 1) * 4);
-    const size_t o_cs = carve(n_labels * 4), o_pp = carve((n_labels + 1) * 4), o_ps = carve(n_labels * 4), o_blk3 = carve((n_labels / 256 + 1) * 8);
-    const size_t o_lab = carve(n_labels * sizeof(osmt_label)), o_run = carve(n_labels * sizeof(osmt_string_run));
-    rc = alloc(&wg.work[3], "labels");
+    pl = pool_layout();
+    const size_t o_keys = pl.add(n_labels * 16), o_eb = pl.add(n_labels * 4), o_es = pl.add(n_labels * 4), o_cp = pl.add((n_labels + 1) * 4);
+    const size_t o_cs = pl.add(n_labels * 4), o_pp = pl.add((n_labels + 1) * 4), o_ps = pl.add(n_labels * 4), o_blk3 = pl.add((n_labels / 256 + 1) * 8);
+    const size_t o_lab = pl.add(n_labels * sizeof(osmt_label)), o_run = pl.add(n_labels * sizeof(osmt_string_run));
+    rc = wg.alloc(3, pl, "labels");
     if (rc != OSMT_OK) return rc;
     char* w3 = wg.work[3];
     P.geo = geo.dev;
@@ -4789,7 +4591,7 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     P.runs = (osmt_string_run*)(w3 + o_run);
     P.tot = Q.tot + OSMT_TQ_N;
     P.blk = (unsigned long long*)(w2 + o_blk2);
-    HIP_TRY(mark(EV_X0));
+    HIP_TRY(wg.mark(EV_X0));
     HIP_TRY(osmt_launch_al_expand(P, st));
     {
         osmt_tl_pass S;
@@ -4797,7 +4599,7 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         S.keys = P.keys, S.job_label_off = Q.tile_base, S.n_tiles = (uint32_t)n_tiles;
         if (n_labels) HIP_TRY(osmt_launch_tl_sort(S, st));
     }
-    HIP_TRY(mark(EV_X1));
+    HIP_TRY(wg.mark(EV_X1));
     HIP_TRY(hipMemcpyAsync(j->stage, P.tot, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     memcpy(al_tot, j->stage, 8);
@@ -4805,11 +4607,11 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     /* 3. anchors: the requests stay on the device; only the totals that size the pools come back */
     uint32_t pl_cnt[4] = {0, 0, 0, 0};
     const uint32_t* d_cnt = nullptr;
-    HIP_TRY(mark(EV_A0));
+    HIP_TRY(wg.mark(EV_A0));
     if (n_req) {
-        off = 0;
-        (void)carve(n_req * sizeof(osmt_label_tile_request));
-        rc = alloc(&wg.work[4], "anchor requests");
+        pl = pool_layout();
+        (void)pl.add(n_req * sizeof(osmt_label_tile_request));
+        rc = wg.alloc(4, pl, "anchor requests");
         if (rc != OSMT_OK) return rc;
         P.n_req = (uint32_t)n_req;
         P.req = (osmt_label_tile_request*)wg.work[4];
@@ -4821,15 +4623,10 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         const uint32_t n_slots = (uint32_t)std::min<size_t>(n_req, OSMT_PL_MAX_SLOTS);
         size_t o_keep = 0, o_over = 0, o_back = 0, o_wsp = 0;
         auto search_bytes = [&](size_t n_rings) {
-            size_t o = 0;
-            auto take = [&](size_t bytes) {
-                const size_t at = o;
-                o = align_up(o + std::max<size_t>(bytes, 4), 256);
-                return at;
-            };
-            o_keep = take(n_rings * 4), o_over = take(n_req * 4), o_back = take(back_bytes);
-            o_wsp = take((size_t)n_slots * OSMT_PL_CELL_DOUBLES * OSMT_PL_GLOBAL_CELLS * sizeof(double));
-            return o;
+            pool_layout pl;
+            o_keep = pl.add(n_rings * 4), o_over = pl.add(n_req * 4), o_back = pl.add(back_bytes);
+            o_wsp = pl.add((size_t)n_slots * OSMT_PL_CELL_DOUBLES * OSMT_PL_GLOBAL_CELLS * sizeof(double));
+            return pl.size();
         };
         osmt_an_pass ap{};
         size_t x0 = 0;
@@ -4852,12 +4649,12 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         P.pos = a.out;
         d_cnt = a.cnt;
     }
-    HIP_TRY(mark(EV_A1));
+    HIP_TRY(wg.mark(EV_A1));
     /* 4. what every sorted label holds: chars and way points */
     P.blk = (unsigned long long*)(w3 + o_blk3);
-    HIP_TRY(mark(EV_C0));
+    HIP_TRY(wg.mark(EV_C0));
     HIP_TRY(osmt_launch_al_count(P, st));
-    HIP_TRY(mark(EV_C1));
+    HIP_TRY(wg.mark(EV_C1));
     HIP_TRY(hipMemcpyAsync(j->stage, P.tot, OSMT_AL_N * 8, hipMemcpyDeviceToHost, st));
     if (d_cnt) HIP_TRY(hipMemcpyAsync(j->stage + 64, d_cnt, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -4889,9 +4686,9 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         return fail(OSMT_UNSUPPORTED, "area labels: the batch has %llu way points of text along ways (> 2^32): split the batch", al_tot[OSMT_AL_PTS]);
     const size_t n_chars = (size_t)al_tot[OSMT_AL_CHARS], n_pts = (size_t)al_tot[OSMT_AL_PTS];
     /* 5. way points, records, chars */
-    off = 0;
-    const size_t o_ch = carve(n_chars * 4), o_pf = carve(n_pts * 8), o_pt = carve(n_pts * 8);
-    rc = alloc(&wg.work[5], "chars and way points");
+    pl = pool_layout();
+    const size_t o_ch = pl.add(n_chars * 4), o_pf = pl.add(n_pts * 8), o_pt = pl.add(n_pts * 8);
+    rc = wg.alloc(5, pl, "chars and way points");
     if (rc != OSMT_OK) return rc;
     char* w5 = wg.work[5];
     P.n_chars = (uint32_t)n_chars;
@@ -4899,9 +4696,9 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     P.chars = (uint32_t*)(w5 + o_ch);
     P.pts_fwd = (int2*)(w5 + o_pf);
     P.pts = (int2*)(w5 + o_pt);
-    HIP_TRY(mark(EV_E0));
+    HIP_TRY(wg.mark(EV_E0));
     HIP_TRY(osmt_launch_al_emit(P, st));
-    HIP_TRY(mark(EV_E1));
+    HIP_TRY(wg.mark(EV_E1));
     out->labels.resize(n_labels), out->runs.resize(n_labels), out->chars.resize(n_chars), out->pts.resize(2 * n_pts);
     if (n_labels) HIP_TRY(hipMemcpyAsync(out->labels.data(), P.labels, n_labels * sizeof(osmt_label), hipMemcpyDeviceToHost, st));
     if (n_labels) HIP_TRY(hipMemcpyAsync(out->runs.data(), P.runs, n_labels * sizeof(osmt_string_run), hipMemcpyDeviceToHost, st));
@@ -4914,15 +4711,10 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     area_label_angles(out->labels, out->runs, out->pts, &out->sincos);
     if (trace) {
         const double angle_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        auto us = [&](int a, int b2) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
-            return ms * 1e3;
-        };
         fprintf(stderr,
                 "osmt area labels: query %.1f us, expand + sort %.1f us, anchors %.1f us, count + scans %.1f us, emit %.1f us, host angles %.1f us "
                 "(%zu tiles, %zu candidates, %zu labels, %zu anchor requests, %zu chars, %zu way points, %zu bytes read back)\n",
-                us(EV_Q0, EV_Q1), us(EV_X0, EV_X1), us(EV_A0, EV_A1), us(EV_C0, EV_C1), us(EV_E0, EV_E1), angle_us, n_tiles, n_cand, n_labels, n_req, n_chars,
+                wg.us(EV_Q0, EV_Q1), wg.us(EV_X0, EV_X1), wg.us(EV_A0, EV_A1), wg.us(EV_C0, EV_C1), wg.us(EV_E0, EV_E1), angle_us, n_tiles, n_cand, n_labels, n_req, n_chars,
                 n_pts, n_labels * (sizeof(osmt_label) + sizeof(osmt_string_run)) + n_chars * 4 + n_pts * 8 + (n_tiles + 1) * 4);
     }
     return OSMT_OK;
@@ -5451,19 +5243,14 @@ static int png_begin_back(osmt_ctx* ctx, osmt_png_job* j) {
         if (forced_chunks) chunk = std::max<uint32_t>(1u, (n + (uint32_t)forced_chunks - 1u) / (uint32_t)forced_chunks);
         j->chunk = chunk;
         const uint32_t n_chunks = j->n_chunks = (n + chunk - 1u) / chunk;
-        size_t off = 0;
-        auto carve = [&](size_t bytes) {
-            const size_t o = off;
-            off = align_up(off + bytes, 256);
-            return o;
-        };
-        const size_t o_rgba = j->o_rgba = carve((size_t)std::min<uint32_t>(2u, n_chunks) * chunk * tile_bytes); /* two chunks of framebuffers, alternating */
+        pool_layout pl;
+        const size_t o_rgba = j->o_rgba = pl.add((size_t)std::min<uint32_t>(2u, n_chunks) * chunk * tile_bytes); /* two chunks of framebuffers, alternating */
         j->tile_bytes = tile_bytes;
-        j->o_png = carve((size_t)n * slot);
-        j->o_len = carve((size_t)n * 4);
-        j->o_off = carve((size_t)n * 8);
-        e = dev_alloc(ctx, (void**)&j->d, off);
-        if (e != hipSuccess) rc = fail(OSMT_OOM, "hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
+        j->o_png = pl.add((size_t)n * slot);
+        j->o_len = pl.add((size_t)n * 4);
+        j->o_off = pl.add((size_t)n * 8);
+        e = dev_alloc(ctx, (void**)&j->d, pl.size());
+        if (e != hipSuccess) rc = fail(OSMT_OOM, "hipMalloc(%zu) failed: %s", pl.size(), hipGetErrorString(e));
         if (rc == OSMT_OK) {
             j->h_len = (uint32_t*)stage_acquire(ctx, (size_t)n * 12 + 16);
             if (!j->h_len) rc = fail(OSMT_OOM, "pinned staging for %u file lengths", n);
@@ -5828,8 +5615,6 @@ int osmt_composite(osmt_ctx* ctx, const double* planes, const double canvas[4], 
     return guarded([&] { return osmt_composite_body(ctx, planes, canvas, n, L, W, H, out_rgba); });
 }
 
-} /* extern "C" */
-
 /* ======================= one node, several GPUs ======================= */
 struct osmt_batch_shard {
     osmt_batch b;
@@ -5934,8 +5719,6 @@ void comm_destroy(osmt_ctx* ctx) {
     ctx->d_count = nullptr;
 }
 }  // namespace
-
-extern "C" {
 
 static int shard_create_body(const osmt_batch* b, uint32_t rank, uint32_t world, osmt_batch_shard** out, bool trusted = false) {
     if (!out) return fail(OSMT_INVALID_ARG, "NULL argument");
@@ -6294,8 +6077,6 @@ int osmt_render_batch_multi_ex(osmt_ctx* const* ctxs, uint32_t n, const osmt_bat
     return guarded([&] { return render_batch_multi_body(ctxs, n, batch, labels, flags, out, stride, out_count); });
 }
 
-}  // extern "C"
-
 /* ---- the per-request entry: worker handles that gather concurrent one-tile requests -------------------------------
  * The reference's server hands ONE tile per request to each of available_parallelism() worker threads, every one with
  * its own TilePixels (src/http_server.rs:50-83,105-108,134-181).  Sixteen threads that each run the whole chain — five
@@ -6606,8 +6387,6 @@ int worker_render_body(osmt_worker* w, const osmt_batch* batch, const osmt_label
 
 }  // namespace
 
-extern "C" {
-
 int osmt_worker_create(osmt_ctx* ctx, osmt_worker** out_worker) {
     return guarded([&] {
         if (!ctx || !out_worker) return fail(OSMT_INVALID_ARG, "NULL argument");
@@ -6630,10 +6409,6 @@ void osmt_worker_destroy(osmt_worker* w) {
 int osmt_worker_render(osmt_worker* w, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgb, size_t out_tile_stride_bytes) {
     return guarded([&] { return worker_render_body(w, batch, labels, out_rgb, out_tile_stride_bytes); });
 }
-
-}  // extern "C"
-
-extern "C" {
 
 static int hbm_copy_probe_body(osmt_ctx* ctx, size_t bytes, uint32_t iters, double* out_copy, double* out_read) {
     if (!ctx || !out_copy) return fail(OSMT_INVALID_ARG, "NULL argument");
@@ -6673,8 +6448,6 @@ int osmt_debug_poison_enabled(void) { return poison_alloc() ? 1 : 0; }
 int osmt_hbm_copy_probe(osmt_ctx* ctx, size_t bytes, uint32_t iters, double* out_copy, double* out_read) {
     return guarded([&] { return hbm_copy_probe_body(ctx, bytes, iters, out_copy, out_read); });
 }
-
-} /* extern "C" */
 
 /* ---- selector matching (include/osmtile.h, csrc/osmt_selmatch.hip) ------------------------------------------------ */
 struct osmt_match {
@@ -6755,42 +6528,28 @@ int register_tags_body(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tags_desc*
         for (size_t i = 0; i < t->n_multipolygons; ++i) tag_off[e++] = (uint32_t)(t->n_node_tags + t->n_way_tags + t->multipolygon_tag_off[i]);
         tag_off[e] = (uint32_t)n_tags;
     }
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_off = carve((n_ent + 1) * 4), o_tags = carve(n_tags * 16), o_str = carve(t->n_string_bytes);
-    char* pool = nullptr;
-    HIP_TRY(hipMalloc((void**)&pool, off));
-    hipError_t e = hipSuccess;
-    auto put = [&](size_t o, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
-    };
-    put(o_off, tag_off.data(), (n_ent + 1) * 4);
-    put(o_tags, t->node_tags, t->n_node_tags * 16);
-    put(o_tags + t->n_node_tags * 16, t->way_tags, t->n_way_tags * 16);
-    put(o_tags + (t->n_node_tags + t->n_way_tags) * 16, t->multipolygon_tags, t->n_multipolygon_tags * 16);
-    put(o_str, t->strings, t->n_string_bytes);
-    if (e != hipSuccess) {
-        (void)hipFree(pool);
-        return fail(OSMT_HIP_ERROR, "tags upload failed: %s", hipGetErrorString(e));
-    }
+    pool_layout pl;
+    const size_t o_off = pl.add((n_ent + 1) * 4), o_tags = pl.add(n_tags * 16), o_str = pl.add(t->n_string_bytes);
+    table_upload up("tags", pl);
+    char* pool = up.pool;
+    up.put(o_off, tag_off.data(), (n_ent + 1) * 4);
+    up.put(o_tags, t->node_tags, t->n_node_tags * 16);
+    up.put(o_tags + t->n_node_tags * 16, t->way_tags, t->n_way_tags * 16);
+    up.put(o_tags + (t->n_node_tags + t->n_way_tags) * 16, t->multipolygon_tags, t->n_multipolygon_tags * 16);
+    up.put(o_str, t->strings, t->n_string_bytes);
+    if (up.done() != OSMT_OK) return up.done();
     osmt_sm_tags_dev d{};
     d.tag_off = (const uint32_t*)(pool + o_off);
     d.tags = (const uint4*)(pool + o_tags);
     d.strings = (const uint8_t*)(pool + o_str);
     d.n_nodes = (uint32_t)t->n_nodes, d.n_ways = (uint32_t)t->n_ways, d.n_mps = (uint32_t)t->n_multipolygons, d.n_tags = (uint32_t)n_tags;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->geodata[geodata_id].d_tags) { /* another thread was first */
-        (void)hipFree(pool);
-        return fail(OSMT_INVALID_ARG, "geodata id %u has tags already (one table per file)", geodata_id);
-    }
+    if (ctx->geodata[geodata_id].d_tags) return fail(OSMT_INVALID_ARG, "geodata id %u has tags already (one table per file)", geodata_id); /* another thread was first */
     ctx->geodata[geodata_id].d_tags = pool;
     ctx->geodata[geodata_id].tags = d;
     ctx->geodata[geodata_id].tags_string_bytes = t->n_string_bytes;
     ctx->geodata[geodata_id].n_node_tags = t->n_node_tags, ctx->geodata[geodata_id].n_way_tags = t->n_way_tags;
+    up.release();
     return OSMT_OK;
 }
 
@@ -6874,29 +6633,17 @@ int register_selectors_body(osmt_ctx* ctx, const osmt_selectors_desc* d, uint32_
         r.type = d->selectors[i].object_type, r.test_off = d->selectors[i].test_off, r.n_tests = d->selectors[i].n_tests;
         h_sels[i] = r;
     }
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_k = carve(h_keys.size() * sizeof(osmt_sm_key)), o_v = carve(h_vals.size() * sizeof(uint2)), o_s = carve(blob.size());
-    const size_t o_sel = carve(h_sels.size() * sizeof(osmt_sm_sel)), o_t = carve(h_tests.size() * sizeof(osmt_sm_test));
-    char* pool = nullptr;
-    HIP_TRY(hipMalloc((void**)&pool, off));
-    hipError_t e = hipSuccess;
-    auto put = [&](size_t o, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
-    };
-    put(o_k, h_keys.data(), h_keys.size() * sizeof(osmt_sm_key));
-    put(o_v, h_vals.data(), h_vals.size() * sizeof(uint2));
-    put(o_s, blob.data(), blob.size());
-    put(o_sel, h_sels.data(), h_sels.size() * sizeof(osmt_sm_sel));
-    put(o_t, h_tests.data(), h_tests.size() * sizeof(osmt_sm_test));
-    if (e != hipSuccess) {
-        (void)hipFree(pool);
-        return fail(OSMT_HIP_ERROR, "selectors upload failed: %s", hipGetErrorString(e));
-    }
+    pool_layout pl;
+    const size_t o_k = pl.add(h_keys.size() * sizeof(osmt_sm_key)), o_v = pl.add(h_vals.size() * sizeof(uint2)), o_s = pl.add(blob.size());
+    const size_t o_sel = pl.add(h_sels.size() * sizeof(osmt_sm_sel)), o_t = pl.add(h_tests.size() * sizeof(osmt_sm_test));
+    table_upload up("selectors", pl);
+    char* pool = up.pool;
+    up.put(o_k, h_keys.data(), h_keys.size() * sizeof(osmt_sm_key));
+    up.put(o_v, h_vals.data(), h_vals.size() * sizeof(uint2));
+    up.put(o_s, blob.data(), blob.size());
+    up.put(o_sel, h_sels.data(), h_sels.size() * sizeof(osmt_sm_sel));
+    up.put(o_t, h_tests.data(), h_tests.size() * sizeof(osmt_sm_test));
+    if (up.done() != OSMT_OK) return up.done();
     osmt_ctx::selectors_host h;
     h.d_pool = pool;
     h.dev.keys = (const osmt_sm_key*)(pool + o_k);
@@ -6916,6 +6663,7 @@ int register_selectors_body(osmt_ctx* ctx, const osmt_selectors_desc* d, uint32_
     std::lock_guard<std::mutex> lk(ctx->mu);
     *out_id = (uint32_t)ctx->selectors.size();
     ctx->selectors.push_back(h);
+    up.release();
     return OSMT_OK;
 }
 
@@ -6948,44 +6696,14 @@ int match_selectors_body(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_
                         o.v_off, o.v_len, i - 1);
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    struct work_guard {
-        osmt_ctx* ctx;
-        hipStream_t st = nullptr;
-        char* work[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~work_guard() {
-            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's overrides */
-            for (char* p : work) dev_free(ctx, p);
-            stream_release(ctx, st);
-        }
-    } wg{ctx};
-    HIP_TRY(stream_acquire(ctx, &wg.st));
-    hipStream_t st = wg.st;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    auto alloc = [&](char** p, const char* what) {
-        const hipError_t e = dev_alloc(ctx, (void**)p, off + 256);
-        if (e == hipSuccess) return (int)OSMT_OK;
-        *p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the selector match (%s) failed: %s", off, what, hipGetErrorString(e));
-    };
-    /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the stages, one line on stderr */
-    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    /* the trace: the device time of the stages */
     enum { EV_TAGS0, EV_TAGS1, EV_COUNT0, EV_COUNT1, EV_CLASS0, EV_CLASS1, EV_EMIT0, EV_EMIT1, EV_N };
-    hipEvent_t ev[EV_N] = {};
-    struct ev_guard {
-        hipEvent_t* ev;
-        ~ev_guard() {
-            for (int i = 0; i < EV_N; ++i)
-                if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    } evg{ev};
-    if (trace)
-        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
-    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+    call_work wg(ctx, "selector match");
+    const int brc = wg.begin(EV_N);
+    if (brc != OSMT_OK) return brc;
+    hipStream_t st = wg.st;
+    const bool trace = wg.trace;
+    pool_layout pl;
 
     const size_t n_ent = (size_t)geo.tags.n_nodes + geo.tags.n_ways + geo.tags.n_mps, n_tags = geo.tags.n_tags;
     unsigned long long tot[OSMT_SM_T_N] = {};
@@ -6998,10 +6716,10 @@ int match_selectors_body(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_
     P.n_ent = (uint32_t)n_ent;
     P.hash_mask = hash_bits >= 32u ? 0xFFFFFFFFu : (1u << hash_bits) - 1u;
     /* 1. tags */
-    off = 0;
-    const size_t o_ov = carve(n_ov * sizeof(osmt_number_override)), o_code = carve(n_tags * 4), o_vf = carve(n_tags * 8), o_num = carve(n_tags * 8);
-    const size_t o_dp = carve((n_tags + 1) * 4), o_blk = carve((std::max(n_tags, n_ent) / 256 + 1) * 8), o_tot = carve(OSMT_SM_T_N * 8);
-    int rc = alloc(&wg.work[0], "tags");
+    pl = pool_layout();
+    const size_t o_ov = pl.add(n_ov * sizeof(osmt_number_override)), o_code = pl.add(n_tags * 4), o_vf = pl.add(n_tags * 8), o_num = pl.add(n_tags * 8);
+    const size_t o_dp = pl.add((n_tags + 1) * 4), o_blk = pl.add((std::max(n_tags, n_ent) / 256 + 1) * 8), o_tot = pl.add(OSMT_SM_T_N * 8);
+    int rc = wg.alloc(0, pl, "tags");
     if (rc != OSMT_OK) return rc;
     char* w0 = wg.work[0];
     if (n_ov) HIP_TRY(hipMemcpyAsync(w0 + o_ov, ov, n_ov * sizeof(osmt_number_override), hipMemcpyHostToDevice, st));
@@ -7012,16 +6730,16 @@ int match_selectors_body(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_
     P.decl_pos = (uint32_t*)(w0 + o_dp);
     P.blk = (unsigned long long*)(w0 + o_blk);
     P.tot = (unsigned long long*)(w0 + o_tot);
-    HIP_TRY(mark(EV_TAGS0));
+    HIP_TRY(wg.mark(EV_TAGS0));
     HIP_TRY(osmt_launch_sm_tags(P, st));
-    HIP_TRY(mark(EV_TAGS1));
+    HIP_TRY(wg.mark(EV_TAGS1));
     HIP_TRY(hipMemcpyAsync(tot, P.tot, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (tot[OSMT_SM_T_DECLINED]) {
         const size_t n_decl = (size_t)tot[OSMT_SM_T_DECLINED];
-        off = 0;
-        (void)carve(n_decl * sizeof(osmt_declined_number));
-        rc = alloc(&wg.work[1], "declined values");
+        pl = pool_layout();
+        (void)pl.add(n_decl * sizeof(osmt_declined_number));
+        rc = wg.alloc(1, pl, "declined values");
         if (rc != OSMT_OK) return rc;
         P.n_declined = (uint32_t)n_decl;
         P.declined = (osmt_declined_number*)wg.work[1];
@@ -7053,10 +6771,10 @@ int match_selectors_body(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_
     size_t table = 2;
     while (table < 2 * n_ent) table <<= 1;
     P.table_mask = (uint32_t)(table - 1);
-    off = 0;
-    const size_t o_sp = carve((n_ent + 1) * 4), o_lay = carve(n_ent * 8), o_key = carve(n_ent * 4), o_hash = carve(n_ent * 4), o_ts = carve(n_ent * 4);
-    const size_t o_fp = carve((n_ent + 1) * 4), o_tab = carve(table * 4), o_low = carve(table * 4);
-    rc = alloc(&wg.work[1], "entities");
+    pl = pool_layout();
+    const size_t o_sp = pl.add((n_ent + 1) * 4), o_lay = pl.add(n_ent * 8), o_key = pl.add(n_ent * 4), o_hash = pl.add(n_ent * 4), o_ts = pl.add(n_ent * 4);
+    const size_t o_fp = pl.add((n_ent + 1) * 4), o_tab = pl.add(table * 4), o_low = pl.add(table * 4);
+    rc = wg.alloc(1, pl, "entities");
     if (rc != OSMT_OK) return rc;
     char* w1 = wg.work[1];
     P.sel_pos = (uint32_t*)(w1 + o_sp);
@@ -7067,48 +6785,48 @@ int match_selectors_body(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_
     P.first_pos = (uint32_t*)(w1 + o_fp);
     P.table = (uint32_t*)(w1 + o_tab);
     P.lowest = (uint32_t*)(w1 + o_low);
-    HIP_TRY(mark(EV_COUNT0));
+    HIP_TRY(wg.mark(EV_COUNT0));
     HIP_TRY(osmt_launch_sm_count(P, st));
-    HIP_TRY(mark(EV_COUNT1));
+    HIP_TRY(wg.mark(EV_COUNT1));
     HIP_TRY(hipMemcpyAsync(tot + OSMT_SM_T_MATCHED, P.tot + OSMT_SM_T_MATCHED, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (tot[OSMT_SM_T_MATCHED] >= 0xFFFFFFFFull)
         return fail(OSMT_UNSUPPORTED, "the match has %llu (entity, selector) pairs (> 2^32 - 2): split the selector set", tot[OSMT_SM_T_MATCHED]);
     P.n_matched = (uint32_t)tot[OSMT_SM_T_MATCHED];
     /* 3. lists and classes */
-    off = 0;
-    (void)carve((size_t)P.n_matched * 4);
-    rc = alloc(&wg.work[2], "selector lists");
+    pl = pool_layout();
+    (void)pl.add((size_t)P.n_matched * 4);
+    rc = wg.alloc(2, pl, "selector lists");
     if (rc != OSMT_OK) return rc;
     P.ent_sels = (uint32_t*)wg.work[2];
-    HIP_TRY(mark(EV_CLASS0));
+    HIP_TRY(wg.mark(EV_CLASS0));
     HIP_TRY(osmt_launch_sm_classes(P, st));
-    HIP_TRY(mark(EV_CLASS1));
+    HIP_TRY(wg.mark(EV_CLASS1));
     HIP_TRY(hipMemcpyAsync(tot + OSMT_SM_T_CLASSES, P.tot + OSMT_SM_T_CLASSES, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     P.n_classes = (uint32_t)tot[OSMT_SM_T_CLASSES]; /* at most n_ent */
-    off = 0;
-    const size_t o_cp = carve(((size_t)P.n_classes + 1) * 4), o_cf = carve((size_t)P.n_classes * 4);
-    rc = alloc(&wg.work[3], "classes");
+    pl = pool_layout();
+    const size_t o_cp = pl.add(((size_t)P.n_classes + 1) * 4), o_cf = pl.add((size_t)P.n_classes * 4);
+    rc = wg.alloc(3, pl, "classes");
     if (rc != OSMT_OK) return rc;
     P.cls_pos = (uint32_t*)(wg.work[3] + o_cp);
     P.cls_first = (uint32_t*)(wg.work[3] + o_cf);
-    HIP_TRY(mark(EV_EMIT0));
+    HIP_TRY(wg.mark(EV_EMIT0));
     HIP_TRY(osmt_launch_sm_class_count(P, st));
     HIP_TRY(hipMemcpyAsync(tot + OSMT_SM_T_CLASS_SELS, P.tot + OSMT_SM_T_CLASS_SELS, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     P.n_class_sels = (uint32_t)tot[OSMT_SM_T_CLASS_SELS]; /* at most n_matched */
     /* 4. the result: one allocation that goes to the match */
-    off = 0;
-    const size_t o_ec = carve(n_ent * 4), o_cl = carve((size_t)P.n_classes * sizeof(osmt_match_class)), o_cs = carve((size_t)P.n_class_sels * 4);
-    rc = alloc(&wg.work[4], "result");
+    pl = pool_layout();
+    const size_t o_ec = pl.add(n_ent * 4), o_cl = pl.add((size_t)P.n_classes * sizeof(osmt_match_class)), o_cs = pl.add((size_t)P.n_class_sels * 4);
+    rc = wg.alloc(4, pl, "result");
     if (rc != OSMT_OK) return rc;
     char* keep = wg.work[4];
     P.ent_class = (uint32_t*)(keep + o_ec);
     P.classes = (osmt_match_class*)(keep + o_cl);
     P.class_sels = (uint32_t*)(keep + o_cs);
     HIP_TRY(osmt_launch_sm_emit(P, st));
-    HIP_TRY(mark(EV_EMIT1));
+    HIP_TRY(wg.mark(EV_EMIT1));
     HIP_TRY(hipStreamSynchronize(st));
     std::unique_ptr<osmt_match> m(new osmt_match);
     m->ctx = ctx;
@@ -7123,15 +6841,10 @@ int match_selectors_body(osmt_ctx* ctx, uint32_t geodata_id, uint32_t selectors_
     ctx->refs.fetch_add(1);
     *out = m.release();
     if (trace) {
-        auto us = [&](int a, int b2) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
-            return ms * 1e3;
-        };
         fprintf(stderr,
                 "osmt selector match: tags %.1f us, count %.1f us, lists + classes %.1f us, records %.1f us (%zu entities, %zu tags, %u selectors, "
                 "%u pairs, %u classes)\n",
-                us(EV_TAGS0, EV_TAGS1), us(EV_COUNT0, EV_COUNT1), us(EV_CLASS0, EV_CLASS1), us(EV_EMIT0, EV_EMIT1), n_ent, n_tags, sel.dev.n_sels,
+                wg.us(EV_TAGS0, EV_TAGS1), wg.us(EV_COUNT0, EV_COUNT1), wg.us(EV_CLASS0, EV_CLASS1), wg.us(EV_EMIT0, EV_EMIT1), n_ent, n_tags, sel.dev.n_sels,
                 P.n_matched, P.n_classes);
     }
     return OSMT_OK;
@@ -7175,37 +6888,17 @@ int bindings_matched_body(osmt_ctx* ctx, osmt_match* m, uint8_t zoom_lo, uint8_t
                             ctx->styles.size());
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    struct work_guard {
-        osmt_ctx* ctx;
-        hipStream_t st = nullptr;
-        char* work = nullptr;
-        char* pool = nullptr; /* the table, until it is registered */
-        ~work_guard() {
-            if (st) (void)hipStreamSynchronize(st);
-            dev_free(ctx, work);
-            if (pool) (void)hipFree(pool);
-            stream_release(ctx, st);
-        }
-    } wg{ctx};
-    HIP_TRY(stream_acquire(ctx, &wg.st));
+    call_work wg(ctx, "bindings per class"); /* wg.pool: the table, until it is registered */
+    const int brc = wg.begin(0);
+    if (brc != OSMT_OK) return brc;
     hipStream_t st = wg.st;
     const size_t n_ways = m->n_ways, n_mps = m->n_mps;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    const size_t o_co = carve((n + 1) * 4), o_cs = carve(n_styles_in * 4), o_pw = carve((n_ways + 1) * 4), o_pm = carve((n_mps + 1) * 4);
-    const size_t o_blk = carve((std::max(n_ways, n_mps) / 256 + 1) * 8), o_tot = carve(16);
-    {
-        const hipError_t e = dev_alloc(ctx, (void**)&wg.work, off + 256);
-        if (e != hipSuccess) {
-            wg.work = nullptr;
-            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the bindings per class failed: %s", off, hipGetErrorString(e));
-        }
-    }
-    char* w = wg.work;
+    pool_layout pl;
+    const size_t o_co = pl.add((n + 1) * 4), o_cs = pl.add(n_styles_in * 4), o_pw = pl.add((n_ways + 1) * 4), o_pm = pl.add((n_mps + 1) * 4);
+    const size_t o_blk = pl.add((std::max(n_ways, n_mps) / 256 + 1) * 8), o_tot = pl.add(16);
+    const int arc = wg.alloc(0, pl);
+    if (arc != OSMT_OK) return arc;
+    char* w = wg.work[0];
     HIP_TRY(hipMemcpyAsync(w + o_co, class_off, (n + 1) * 4, hipMemcpyHostToDevice, st));
     if (n_styles_in) HIP_TRY(hipMemcpyAsync(w + o_cs, class_styles, n_styles_in * 4, hipMemcpyHostToDevice, st));
     const uint32_t* d_co = (const uint32_t*)(w + o_co);
@@ -7222,9 +6915,10 @@ int bindings_matched_body(osmt_ctx* ctx, osmt_match* m, uint8_t zoom_lo, uint8_t
     if (tot[0] >= 0xFFFFFFFFull || tot[1] >= 0xFFFFFFFFull)
         return fail(OSMT_UNSUPPORTED, "bindings per class: %llu way and %llu multipolygon bindings (> 2^32 - 2 of one kind)", tot[0], tot[1]);
     /* the table, laid out as osmt_register_style_bindings lays it out */
-    off = 0;
-    const size_t o_wo = carve((n_ways + 1) * 4), o_w = carve((size_t)tot[0] * 4), o_mo = carve((n_mps + 1) * 4), o_m = carve((size_t)tot[1] * 4);
-    HIP_TRY(hipMalloc((void**)&wg.pool, off));
+    pl = pool_layout();
+    const size_t o_wo = pl.add((n_ways + 1) * 4), o_w = pl.add((size_t)tot[0] * 4), o_mo = pl.add((n_mps + 1) * 4), o_m = pl.add((size_t)tot[1] * 4);
+    const int prc = wg.alloc_pool(pl);
+    if (prc != OSMT_OK) return prc;
     char* pool = wg.pool;
     HIP_TRY(hipMemcpyAsync(pool + o_wo, pw, (n_ways + 1) * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(pool + o_mo, pm, (n_mps + 1) * 4, hipMemcpyDeviceToDevice, st));
@@ -7247,8 +6941,6 @@ int bindings_matched_body(osmt_ctx* ctx, osmt_match* m, uint8_t zoom_lo, uint8_t
 }
 
 }  // namespace
-
-extern "C" {
 
 int osmt_validate_tags(const osmt_tags_desc* tags, uint32_t geodata_id, osmt_ctx* ctx) {
     return guarded([&] { return validate_tags(tags, geodata_id, ctx); });
@@ -7298,8 +6990,6 @@ int osmt_debug_match_hash_bits(osmt_ctx* ctx, uint32_t bits) {
         return (int)OSMT_OK;
     });
 }
-
-} /* extern "C" */
 
 /* ---- label bindings per class (include/osmtile.h, csrc/osmt_labelbind.hip) ----------------------------------------- */
 namespace {
@@ -7359,46 +7049,14 @@ int label_bindings_matched_body(osmt_ctx* ctx, osmt_match* m, const osmt_class_l
      * the guard, whose destructor waits for the stream that may still read them */
     std::vector<uint2> h_keys(d->n_keys);
     std::vector<uint8_t> h_key_bytes;
-    struct work_guard {
-        osmt_ctx* ctx;
-        hipStream_t st = nullptr;
-        char* work[3] = {nullptr, nullptr, nullptr};
-        char* pool = nullptr; /* the table, until it is registered */
-        ~work_guard() {
-            if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers */
-            for (char* p : work) dev_free(ctx, p);
-            if (pool) (void)hipFree(pool);
-            stream_release(ctx, st);
-        }
-    } wg{ctx};
-    HIP_TRY(stream_acquire(ctx, &wg.st));
-    hipStream_t st = wg.st;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 4), 256);
-        return o;
-    };
-    auto alloc = [&](char** p, const char* what) {
-        const hipError_t e = dev_alloc(ctx, (void**)p, off + 256);
-        if (e == hipSuccess) return (int)OSMT_OK;
-        *p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the %s (%s) failed: %s", off, who, what, hipGetErrorString(e));
-    };
-    /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the stages, one line on stderr */
-    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
+    /* the trace: the device time of the stages */
     enum { EV_COUNT0, EV_COUNT1, EV_EMIT0, EV_EMIT1, EV_TEXTS1, EV_MEASURE0, EV_MEASURE1, EV_DECODE0, EV_DECODE1, EV_PATCH1, EV_N };
-    hipEvent_t ev[EV_N] = {};
-    struct ev_guard {
-        hipEvent_t* ev;
-        ~ev_guard() {
-            for (int i = 0; i < EV_N; ++i)
-                if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    } evg{ev};
-    if (trace)
-        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
-    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
+    call_work wg(ctx, who);
+    const int brc = wg.begin(EV_N);
+    if (brc != OSMT_OK) return brc;
+    hipStream_t st = wg.st;
+    const bool trace = wg.trace;
+    pool_layout pl;
 
     /* the kinds of the table and its tags: the node table numbers the node tags, the area table the way tags, then the
      * multipolygon tags */
@@ -7413,11 +7071,11 @@ int label_bindings_matched_body(osmt_ctx* ctx, osmt_match* m, const osmt_class_l
     }
     size_t table = 2;
     while (table < 2 * n_tt) table <<= 1;
-    const size_t o_co = carve((n_cls + 1) * 4), o_cb = carve(d->n_bindings * 8), o_k = carve(n_keys * 8), o_kb = carve(h_key_bytes.size());
-    const size_t o_p0 = carve((n0 + 1) * 4), o_p1 = carve((n1 + 1) * 4), o_blk = carve((std::max(std::max(n0, n1), n_tt) / 256 + 1) * 8);
-    const size_t o_tot = carve(OSMT_LB_T_N * 8), o_used = carve(n_tt * 4), o_ts = carve(n_tt * 4), o_fp = carve((n_tt + 1) * 4);
-    const size_t o_tab = carve(table * 4), o_low = carve(table * 4);
-    rc = alloc(&wg.work[0], "classes and tags");
+    const size_t o_co = pl.add((n_cls + 1) * 4), o_cb = pl.add(d->n_bindings * 8), o_k = pl.add(n_keys * 8), o_kb = pl.add(h_key_bytes.size());
+    const size_t o_p0 = pl.add((n0 + 1) * 4), o_p1 = pl.add((n1 + 1) * 4), o_blk = pl.add((std::max(std::max(n0, n1), n_tt) / 256 + 1) * 8);
+    const size_t o_tot = pl.add(OSMT_LB_T_N * 8), o_used = pl.add(n_tt * 4), o_ts = pl.add(n_tt * 4), o_fp = pl.add((n_tt + 1) * 4);
+    const size_t o_tab = pl.add(table * 4), o_low = pl.add(table * 4);
+    rc = wg.alloc(0, pl, "classes and tags");
     if (rc != OSMT_OK) return rc;
     char* w = wg.work[0];
     HIP_TRY(hipMemcpyAsync(w + o_co, d->class_off, (n_cls + 1) * 4, hipMemcpyHostToDevice, st));
@@ -7445,11 +7103,11 @@ int label_bindings_matched_body(osmt_ctx* ctx, osmt_match* m, const osmt_class_l
     uint32_t *pos0 = (uint32_t*)(w + o_p0), *pos1 = (uint32_t*)(w + o_p1);
     unsigned long long tot[OSMT_LB_T_N] = {};
     /* 1. count */
-    HIP_TRY(mark(EV_COUNT0));
+    HIP_TRY(wg.mark(EV_COUNT0));
     HIP_TRY(osmt_launch_lb_begin(P, st));
     HIP_TRY(osmt_launch_lb_count(P, (uint32_t)first0, (uint32_t)n0, pos0, P.tot + OSMT_LB_T_BIND0, st));
     HIP_TRY(osmt_launch_lb_count(P, (uint32_t)first1, (uint32_t)n1, pos1, P.tot + OSMT_LB_T_BIND1, st));
-    HIP_TRY(mark(EV_COUNT1));
+    HIP_TRY(wg.mark(EV_COUNT1));
     HIP_TRY(hipMemcpyAsync(tot, P.tot, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (tot[OSMT_LB_T_BIND0] >= 0xFFFFFFFFull || tot[OSMT_LB_T_BIND1] >= 0xFFFFFFFFull) {
@@ -7460,32 +7118,32 @@ int label_bindings_matched_body(osmt_ctx* ctx, osmt_match* m, const osmt_class_l
     }
     const size_t nb0 = (size_t)tot[OSMT_LB_T_BIND0], nb1 = (size_t)tot[OSMT_LB_T_BIND1];
     /* 2. emit with provisional texts, 3. texts */
-    off = 0;
-    const size_t o_b0 = carve(nb0 * 8), o_b1 = carve(nb1 * 8);
-    rc = alloc(&wg.work[1], "bindings");
+    pl = pool_layout();
+    const size_t o_b0 = pl.add(nb0 * 8), o_b1 = pl.add(nb1 * 8);
+    rc = wg.alloc(1, pl, "bindings");
     if (rc != OSMT_OK) return rc;
     osmt_label_binding *bind0 = (osmt_label_binding*)(wg.work[1] + o_b0), *bind1 = (osmt_label_binding*)(wg.work[1] + o_b1);
-    HIP_TRY(mark(EV_EMIT0));
+    HIP_TRY(wg.mark(EV_EMIT0));
     HIP_TRY(osmt_launch_lb_emit(P, (uint32_t)first0, (uint32_t)n0, pos0, bind0, st));
     HIP_TRY(osmt_launch_lb_emit(P, (uint32_t)first1, (uint32_t)n1, pos1, bind1, st));
-    HIP_TRY(mark(EV_EMIT1));
+    HIP_TRY(wg.mark(EV_EMIT1));
     HIP_TRY(osmt_launch_lb_texts(P, st));
-    HIP_TRY(mark(EV_TEXTS1));
+    HIP_TRY(wg.mark(EV_TEXTS1));
     HIP_TRY(hipMemcpyAsync(tot + OSMT_LB_T_TEXTS, P.tot + OSMT_LB_T_TEXTS, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (tot[OSMT_LB_T_TEXTS] >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "%s: %llu texts (>= 2^32 - 1)", who, tot[OSMT_LB_T_TEXTS]);
     const size_t n_texts = (size_t)tot[OSMT_LB_T_TEXTS]; /* at most n_tt */
     P.n_texts = (uint32_t)n_texts;
     /* 4. measure */
-    off = 0;
-    const size_t o_tt = carve(n_texts * 4), o_to = carve((n_texts + 1) * 4);
-    rc = alloc(&wg.work[2], "texts");
+    pl = pool_layout();
+    const size_t o_tt = pl.add(n_texts * 4), o_to = pl.add((n_texts + 1) * 4);
+    rc = wg.alloc(2, pl, "texts");
     if (rc != OSMT_OK) return rc;
     P.text_tag = (uint32_t*)(wg.work[2] + o_tt);
     P.text_off = (uint32_t*)(wg.work[2] + o_to);
-    HIP_TRY(mark(EV_MEASURE0));
+    HIP_TRY(wg.mark(EV_MEASURE0));
     HIP_TRY(osmt_launch_lb_measure(P, st));
-    HIP_TRY(mark(EV_MEASURE1));
+    HIP_TRY(wg.mark(EV_MEASURE1));
     HIP_TRY(hipMemcpyAsync(tot + OSMT_LB_T_CHARS, P.tot + OSMT_LB_T_CHARS, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (tot[OSMT_LB_T_FIRST_BAD] != ~0ull) {
@@ -7509,14 +7167,15 @@ int label_bindings_matched_body(osmt_ctx* ctx, osmt_match* m, const osmt_class_l
     const size_t n_chars = (size_t)tot[OSMT_LB_T_CHARS];
     P.n_chars = (uint32_t)n_chars;
     /* 5. the table, laid out as osmt_register_label_bindings / osmt_register_area_label_bindings lay it out; decode and patch in place */
-    off = 0;
+    pl = pool_layout();
     size_t o_0o, o_1o = 0, o_0b, o_1b = 0, o_txo, o_c;
     if (area) {
-        o_0o = carve((n0 + 1) * 4), o_1o = carve((n1 + 1) * 4), o_0b = carve(nb0 * 8), o_1b = carve(nb1 * 8), o_txo = carve((n_texts + 1) * 4), o_c = carve(n_chars * 4);
+        o_0o = pl.add((n0 + 1) * 4), o_1o = pl.add((n1 + 1) * 4), o_0b = pl.add(nb0 * 8), o_1b = pl.add(nb1 * 8), o_txo = pl.add((n_texts + 1) * 4), o_c = pl.add(n_chars * 4);
     } else {
-        o_0o = carve((n0 + 1) * 4), o_0b = carve(nb0 * 8), o_txo = carve((n_texts + 1) * 4), o_c = carve(n_chars * 4);
+        o_0o = pl.add((n0 + 1) * 4), o_0b = pl.add(nb0 * 8), o_txo = pl.add((n_texts + 1) * 4), o_c = pl.add(n_chars * 4);
     }
-    HIP_TRY(hipMalloc((void**)&wg.pool, off));
+    const int prc = wg.alloc_pool(pl);
+    if (prc != OSMT_OK) return prc;
     char* pool = wg.pool;
     HIP_TRY(hipMemcpyAsync(pool + o_0o, pos0, (n0 + 1) * 4, hipMemcpyDeviceToDevice, st));
     if (nb0) HIP_TRY(hipMemcpyAsync(pool + o_0b, bind0, nb0 * 8, hipMemcpyDeviceToDevice, st));
@@ -7526,24 +7185,19 @@ int label_bindings_matched_body(osmt_ctx* ctx, osmt_match* m, const osmt_class_l
     }
     HIP_TRY(hipMemcpyAsync(pool + o_txo, P.text_off, (n_texts + 1) * 4, hipMemcpyDeviceToDevice, st));
     P.chars = (uint32_t*)(pool + o_c);
-    HIP_TRY(mark(EV_DECODE0));
+    HIP_TRY(wg.mark(EV_DECODE0));
     HIP_TRY(osmt_launch_lb_decode(P, st));
-    HIP_TRY(mark(EV_DECODE1));
+    HIP_TRY(wg.mark(EV_DECODE1));
     HIP_TRY(osmt_launch_lb_patch(P, (osmt_label_binding*)(pool + o_0b), (uint32_t)nb0, st));
     if (area) HIP_TRY(osmt_launch_lb_patch(P, (osmt_label_binding*)(pool + o_1b), (uint32_t)nb1, st));
-    HIP_TRY(mark(EV_PATCH1));
+    HIP_TRY(wg.mark(EV_PATCH1));
     HIP_TRY(hipStreamSynchronize(st));
     if (trace) {
-        auto us = [&](int a, int b2) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
-            return ms * 1e3;
-        };
         fprintf(stderr,
                 "osmt %s: count %.1f us, emit %.1f us, texts %.1f us, measure %.1f us, decode %.1f us, patch %.1f us (%zu entities, %zu tags, %zu "
                 "bindings, %zu texts, %zu chars)\n",
-                who, us(EV_COUNT0, EV_COUNT1), us(EV_EMIT0, EV_EMIT1), us(EV_EMIT1, EV_TEXTS1), us(EV_MEASURE0, EV_MEASURE1), us(EV_DECODE0, EV_DECODE1),
-                us(EV_DECODE1, EV_PATCH1), n0 + n1, n_tt, nb0 + nb1, n_texts, n_chars);
+                who, wg.us(EV_COUNT0, EV_COUNT1), wg.us(EV_EMIT0, EV_EMIT1), wg.us(EV_EMIT1, EV_TEXTS1), wg.us(EV_MEASURE0, EV_MEASURE1), wg.us(EV_DECODE0, EV_DECODE1),
+                wg.us(EV_DECODE1, EV_PATCH1), n0 + n1, n_tt, nb0 + nb1, n_texts, n_chars);
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (area) {
@@ -7639,8 +7293,6 @@ int read_area_label_bindings_body(osmt_ctx* ctx, uint32_t id, uint32_t* way_off,
 
 }  // namespace
 
-extern "C" {
-
 int osmt_validate_class_label_bindings(const osmt_class_label_bindings_desc* d, osmt_match* match, osmt_ctx* ctx) {
     return guarded([&] { return validate_class_label_bindings(d, match, ctx); });
 }
@@ -7661,8 +7313,6 @@ int osmt_read_area_label_bindings(osmt_ctx* ctx, uint32_t id, uint32_t* way_off,
         return read_area_label_bindings_body(ctx, id, way_off, way_bindings, multipolygon_off, multipolygon_bindings, text_off, chars, caps, counts);
     });
 }
-
-} /* extern "C" */
 
 /* ---- the cascade (include/osmtile.h, csrc/osmt_cascade.hip, csrc/osmt_cascade_rule.h) ------------------------------ */
 struct osmt_cascade {
@@ -7763,30 +7413,18 @@ int register_rules_body(osmt_ctx* ctx, const osmt_rules_desc* d, uint32_t flags,
         zooms = ctx->selectors[d->selectors_id].zooms;
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 8), 256);
-        return o;
-    };
-    const size_t o_p = carve(T.props.size() * sizeof(osmt_cs_prop)), o_l = carve(T.rule_last.size() * 4), o_r = carve(d->n_selectors * 4);
-    const size_t o_g = carve(d->n_selectors), o_z = carve(d->n_selectors * 2), o_n = carve(d->n_numbers * 8);
-    char* pool = nullptr;
-    HIP_TRY(hipMalloc((void**)&pool, off));
-    hipError_t e = hipSuccess;
-    auto put = [&](size_t o, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
-    };
-    put(o_p, T.props.data(), T.props.size() * sizeof(osmt_cs_prop));
-    put(o_l, T.rule_last.data(), T.rule_last.size() * 4);
-    put(o_r, d->selector_rule, d->n_selectors * 4);
-    put(o_g, T.sel_layer.data(), d->n_selectors);
-    put(o_z, zooms->data(), d->n_selectors * 2);
-    put(o_n, d->numbers, d->n_numbers * 8);
-    if (e != hipSuccess) {
-        (void)hipFree(pool);
-        return fail(OSMT_HIP_ERROR, "rules upload failed: %s", hipGetErrorString(e));
-    }
+    pool_layout pl;
+    const size_t o_p = pl.add(T.props.size() * sizeof(osmt_cs_prop)), o_l = pl.add(T.rule_last.size() * 4), o_r = pl.add(d->n_selectors * 4);
+    const size_t o_g = pl.add(d->n_selectors), o_z = pl.add(d->n_selectors * 2), o_n = pl.add(d->n_numbers * 8);
+    table_upload up("rules", pl);
+    char* pool = up.pool;
+    up.put(o_p, T.props.data(), T.props.size() * sizeof(osmt_cs_prop));
+    up.put(o_l, T.rule_last.data(), T.rule_last.size() * 4);
+    up.put(o_r, d->selector_rule, d->n_selectors * 4);
+    up.put(o_g, T.sel_layer.data(), d->n_selectors);
+    up.put(o_z, zooms->data(), d->n_selectors * 2);
+    up.put(o_n, d->numbers, d->n_numbers * 8);
+    if (up.done() != OSMT_OK) return up.done();
     osmt_ctx::rules_host h;
     h.d_pool = pool;
     h.selectors_id = d->selectors_id;
@@ -7805,6 +7443,7 @@ int register_rules_body(osmt_ctx* ctx, const osmt_rules_desc* d, uint32_t flags,
     std::lock_guard<std::mutex> lk(ctx->mu);
     *out_id = (uint32_t)ctx->rules.size();
     ctx->rules.push_back(h);
+    up.release();
     return OSMT_OK;
 }
 
@@ -7828,48 +7467,24 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     if (n_classes * (size_t)OSMT_CS_ZOOMS >= 0xFFFFFFFFull / 32u)
         return fail(OSMT_UNSUPPORTED, "cascade: %zu classes x %u zooms do not fit the 32-bit lane index", n_classes, OSMT_CS_ZOOMS);
     HIP_TRY(hipSetDevice(ctx->device));
-    struct work_guard {
-        osmt_ctx* ctx;
-        hipStream_t st = nullptr;
-        std::vector<char*> work;
-        ~work_guard() {
-            if (st) (void)hipStreamSynchronize(st);
-            for (char* p : work) dev_free(ctx, p);
-            stream_release(ctx, st);
-        }
-    } wg{ctx};
-    HIP_TRY(stream_acquire(ctx, &wg.st));
+    /* the trace: the device time of the stages */
+    enum { EV_0, EV_LAYERS, EV_FOLD, EV_DISTINCT, EV_COMPACT, EV_RANGES, EV_N };
+    call_work wg(ctx, "cascade");
+    const int brc = wg.begin(EV_N);
+    if (brc != OSMT_OK) return brc;
     hipStream_t st = wg.st;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + std::max<size_t>(bytes, 8), 256);
-        return o;
-    };
+    const bool trace = wg.trace;
+    pool_layout pl;
+    /* the stages' buffers: one slot each, `base` the newest, and the layout starts over behind every one */
     char* base = nullptr;
+    int n_work = 0;
     auto alloc = [&](const char* what) {
-        char* p = nullptr;
-        const hipError_t e = dev_alloc(ctx, (void**)&p, off + 256);
-        if (e != hipSuccess)
-            return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the cascade (%s) failed: %s", off, what, hipGetErrorString(e));
-        wg.work.push_back(p);
-        base = p;
-        off = 0;
+        const int arc = wg.alloc(n_work, pl, what);
+        if (arc != OSMT_OK) return arc;
+        base = wg.work[n_work++];
+        pl = pool_layout();
         return (int)OSMT_OK;
     };
-    static const bool trace = getenv("OSMT_TRACE_UPLOAD") != nullptr;
-    enum { EV_0, EV_LAYERS, EV_FOLD, EV_DISTINCT, EV_COMPACT, EV_RANGES, EV_N };
-    hipEvent_t ev[EV_N] = {};
-    struct ev_guard {
-        hipEvent_t* ev;
-        ~ev_guard() {
-            for (int i = 0; i < EV_N; ++i)
-                if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    } evg{ev};
-    if (trace)
-        for (int i = 0; i < EV_N; ++i) HIP_TRY(hipEventCreate(&ev[i]));
-    auto mark = [&](int i) { return trace ? hipEventRecord(ev[i], st) : hipSuccess; };
 
     unsigned long long tot[OSMT_CS_T_N] = {};
     osmt_cs_pass P;
@@ -7886,8 +7501,8 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     };
     /* 1. count */
     const size_t n_pairs = P.n_pairs;
-    const size_t o_pp = carve((n_pairs + 1) * 4), o_tot = carve(OSMT_CS_T_N * 8), o_zd = carve(OSMT_CS_ZOOMS * 4), o_blk0 = carve((n_pairs / 256 + 1) * 8);
-    const size_t o_sl = class_layers ? carve(m->n_class_sels) : 0, o_ci = class_layers ? carve(n_classes * 4) : 0;
+    const size_t o_pp = pl.add((n_pairs + 1) * 4), o_tot = pl.add(OSMT_CS_T_N * 8), o_zd = pl.add(OSMT_CS_ZOOMS * 4), o_blk0 = pl.add((n_pairs / 256 + 1) * 8);
+    const size_t o_sl = class_layers ? pl.add(m->n_class_sels) : 0, o_ci = class_layers ? pl.add(n_classes * 4) : 0;
     int rc = alloc("pairs");
     if (rc != OSMT_OK) return rc;
     if (class_layers) P.sel_local = (uint8_t*)(base + o_sl), P.class_info = (uint32_t*)(base + o_ci);
@@ -7895,9 +7510,9 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     P.tot = (unsigned long long*)(base + o_tot);
     P.zoom_differs = (uint32_t*)(base + o_zd);
     P.blk = (unsigned long long*)(base + o_blk0);
-    HIP_TRY(mark(EV_0));
+    HIP_TRY(wg.mark(EV_0));
     HIP_TRY(osmt_launch_cs_class_layers(P, st));
-    HIP_TRY(mark(EV_LAYERS));
+    HIP_TRY(wg.mark(EV_LAYERS));
     HIP_TRY(osmt_launch_cs_count(P, st));
     HIP_TRY(read_tot(class_layers ? OSMT_CS_T_BAD_CLASS : OSMT_CS_T_STYLES, class_layers ? 2 : 1));
     if (class_layers && tot[OSMT_CS_T_BAD_CLASS] != ~0ull) {
@@ -7917,12 +7532,12 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     size_t table = 2;
     while (table < 2 * n_styles) table <<= 1;
     P.table_mask = (uint32_t)(table - 1);
-    const size_t o_rows = carve(n_styles * OSMT_CS_ROW_WORDS * 4), o_area = carve(n_styles * sizeof(osmt_style_rec)), o_lab = carve(n_styles * sizeof(osmt_label_style_rec));
-    const size_t o_key = carve(n_styles * 4), o_bp = carve((n_styles + 1) * 4), o_blk = carve((std::max(n_styles, n_pairs) / 256 + 1) * 8);
+    const size_t o_rows = pl.add(n_styles * OSMT_CS_ROW_WORDS * 4), o_area = pl.add(n_styles * sizeof(osmt_style_rec)), o_lab = pl.add(n_styles * sizeof(osmt_label_style_rec));
+    const size_t o_key = pl.add(n_styles * 4), o_bp = pl.add((n_styles + 1) * 4), o_blk = pl.add((std::max(n_styles, n_pairs) / 256 + 1) * 8);
     size_t o_hash[2], o_ts[2], o_fp[2], o_id[2], o_tab[2], o_low[2];
     for (int k = 0; k < 2; ++k) {
-        o_hash[k] = carve(n_styles * 4), o_ts[k] = carve(n_styles * 4), o_fp[k] = carve((n_styles + 1) * 4), o_id[k] = carve(n_styles * 4);
-        o_tab[k] = carve(table * 4), o_low[k] = carve(table * 4);
+        o_hash[k] = pl.add(n_styles * 4), o_ts[k] = pl.add(n_styles * 4), o_fp[k] = pl.add((n_styles + 1) * 4), o_id[k] = pl.add(n_styles * 4);
+        o_tab[k] = pl.add(table * 4), o_low[k] = pl.add(table * 4);
     }
     rc = alloc("styles");
     if (rc != OSMT_OK) return rc;
@@ -7937,14 +7552,14 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
         P.id[k] = (uint32_t*)(base + o_id[k]), P.table[k] = (uint32_t*)(base + o_tab[k]), P.lowest[k] = (uint32_t*)(base + o_low[k]);
     }
     HIP_TRY(osmt_launch_cs_fold(P, st));
-    HIP_TRY(mark(EV_FOLD));
+    HIP_TRY(wg.mark(EV_FOLD));
     /* 3. distinct records */
     HIP_TRY(osmt_launch_cs_distinct(P, st));
     HIP_TRY(read_tot(OSMT_CS_T_BINDINGS, 3));
     P.n_bindings = (uint32_t)tot[OSMT_CS_T_BINDINGS], P.n_area = (uint32_t)tot[OSMT_CS_T_AREA], P.n_label = (uint32_t)tot[OSMT_CS_T_LABEL];
     const size_t n_area = P.n_area, n_label = P.n_label;
-    const size_t o_dp = carve((n_area + 1) * 4), o_r0 = carve(n_area * 4), o_r1 = carve(n_label * 4);
-    const size_t o_oa = carve(n_area * sizeof(osmt_style_rec)), o_ol = carve(n_label * sizeof(osmt_label_style_rec));
+    const size_t o_dp = pl.add((n_area + 1) * 4), o_r0 = pl.add(n_area * 4), o_r1 = pl.add(n_label * 4);
+    const size_t o_oa = pl.add(n_area * sizeof(osmt_style_rec)), o_ol = pl.add(n_label * sizeof(osmt_label_style_rec));
     rc = alloc("distinct records");
     if (rc != OSMT_OK) return rc;
     P.dash_pos = (uint32_t*)(base + o_dp);
@@ -7953,10 +7568,10 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     P.out_label = (osmt_label_style_rec*)(base + o_ol);
     HIP_TRY(osmt_launch_cs_rank(P, st));
     HIP_TRY(read_tot(OSMT_CS_T_DASHES, 1));
-    HIP_TRY(mark(EV_DISTINCT));
+    HIP_TRY(wg.mark(EV_DISTINCT));
     const size_t n_dashes = (size_t)tot[OSMT_CS_T_DASHES]; /* at most 2 x 2^32 per record sum: checked against 32 bits below */
     if (n_dashes >= 0xFFFFFFFFull) return fail(OSMT_UNSUPPORTED, "cascade: %zu dashes of the distinct styles (> 2^32 - 2)", n_dashes);
-    (void)carve(n_dashes * 8);
+    (void)pl.add(n_dashes * 8);
     rc = alloc("dashes");
     if (rc != OSMT_OK) return rc;
     P.out_dashes = (double*)base;
@@ -7964,7 +7579,7 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     uint32_t differs[OSMT_CS_ZOOMS] = {};
     HIP_TRY(hipMemcpyAsync(differs, P.zoom_differs, sizeof differs, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(mark(EV_COMPACT));
+    HIP_TRY(wg.mark(EV_COMPACT));
     /* 4. zoom ranges: the maximal runs */
     std::unique_ptr<osmt_cascade> c(new osmt_cascade);
     for (uint32_t z = 0; z < OSMT_CS_ZOOMS; ++z) {
@@ -7978,8 +7593,8 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     }
     const size_t n_ranges = c->zoom_lo.size(), n_rc = n_ranges * n_classes;
     P.n_ranges = (uint32_t)n_ranges;
-    const size_t o_rs = carve((n_rc + 1) * 4), o_rb = carve((n_rc + 1) * 4), o_so = carve(n_ranges * (n_classes + 1) * 4), o_bo = carve(n_ranges * (n_classes + 1) * 4);
-    const size_t o_blk2 = carve((n_rc / 256 + 1) * 8);
+    const size_t o_rs = pl.add((n_rc + 1) * 4), o_rb = pl.add((n_rc + 1) * 4), o_so = pl.add(n_ranges * (n_classes + 1) * 4), o_bo = pl.add(n_ranges * (n_classes + 1) * 4);
+    const size_t o_blk2 = pl.add((n_rc / 256 + 1) * 8);
     rc = alloc("ranges");
     if (rc != OSMT_OK) return rc;
     P.rs_pos = (uint32_t*)(base + o_rs), P.rb_pos = (uint32_t*)(base + o_rb);
@@ -7991,13 +7606,13 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
         return fail(OSMT_UNSUPPORTED, "cascade: %llu class styles and %llu class label bindings over the %zu zoom ranges (> 2^32 - 2)", tot[OSMT_CS_T_RANGE_STYLES],
                     tot[OSMT_CS_T_RANGE_BINDINGS], n_ranges);
     const size_t n_rs = (size_t)tot[OSMT_CS_T_RANGE_STYLES], n_rb = (size_t)tot[OSMT_CS_T_RANGE_BINDINGS];
-    const size_t o_os = carve(n_rs * 4), o_ob = carve(n_rb * sizeof(osmt_class_label_binding));
+    const size_t o_os = pl.add(n_rs * 4), o_ob = pl.add(n_rb * sizeof(osmt_class_label_binding));
     rc = alloc("lists");
     if (rc != OSMT_OK) return rc;
     P.out_styles = (uint32_t*)(base + o_os);
     P.out_binds = (osmt_class_label_binding*)(base + o_ob);
     HIP_TRY(osmt_launch_cs_range_emit(P, st));
-    HIP_TRY(mark(EV_RANGES));
+    HIP_TRY(wg.mark(EV_RANGES));
     /* 5. the result comes to the host: the registrations take host arrays */
     c->ctx = ctx, c->geodata_id = m->geodata_id, c->selectors_id = m->selectors_id, c->n_classes = n_classes;
     c->key_off = rules.key_off, c->key_bytes = rules.key_bytes;
@@ -8040,16 +7655,11 @@ int cascade_classes_body(osmt_ctx* ctx, osmt_match* m, uint32_t rules_id, uint32
     ctx->refs.fetch_add(1);
     *out = c.release();
     if (trace) {
-        auto us = [&](int a, int b2) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[a], ev[b2]);
-            return ms * 1e3;
-        };
         fprintf(stderr,
                 "osmt cascade: count + fold + records %.1f us, distinct %.1f us, compact + zooms %.1f us, ranges %.1f us (%zu classes, %zu styles, %zu + %zu "
                 "distinct, %zu ranges), class layers %.1f us\n",
-                us(EV_LAYERS, EV_FOLD), us(EV_FOLD, EV_DISTINCT), us(EV_DISTINCT, EV_COMPACT), us(EV_COMPACT, EV_RANGES), n_classes, n_styles, n_area, n_label, n_ranges,
-                us(EV_0, EV_LAYERS));
+                wg.us(EV_LAYERS, EV_FOLD), wg.us(EV_FOLD, EV_DISTINCT), wg.us(EV_DISTINCT, EV_COMPACT), wg.us(EV_COMPACT, EV_RANGES), n_classes, n_styles, n_area, n_label, n_ranges,
+                wg.us(EV_0, EV_LAYERS));
     }
     return OSMT_OK;
 }
@@ -8151,8 +7761,6 @@ int cascade_register_body(osmt_ctx* ctx, osmt_cascade* c, osmt_match* m, uint32_
 
 }  // namespace
 
-extern "C" {
-
 int osmt_validate_rules_ex(const osmt_rules_desc* rules, uint32_t flags, osmt_ctx* ctx) {
     return guarded([&] { return validate_rules(rules, flags, ctx, nullptr); });
 }
@@ -8183,5 +7791,3 @@ int osmt_cascade_register(osmt_ctx* ctx, osmt_cascade* cascade, osmt_match* matc
                           uint32_t label_bindings_of_zoom[OSMT_MAX_ZOOM + 1], uint32_t area_label_bindings_of_zoom[OSMT_MAX_ZOOM + 1]) {
     return guarded([&] { return cascade_register_body(ctx, cascade, match, what, bindings_of_zoom, label_bindings_of_zoom, area_label_bindings_of_zoom); });
 }
-
-} /* extern "C" */

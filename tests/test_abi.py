@@ -31,6 +31,25 @@ def test_library_exports_every_declared_symbol():
     assert L.osmt_version() >> 16 == 1
 
 
+_ONCE_LEAKED = ("check_offsets", "check_offsets_of", "ctx_image_count", "register_geodata_body", "register_style_bindings_body", "register_styles_body",
+                "register_tile_index_body", "scene_build_styled_body", "scene_build_tiles_body", "scene_png_work_layout", "scene_read_display_list_body",
+                "scene_read_styled_areas_body", "style_key_cmp", "styled_build_back", "sync_styles", "validate_geodata", "validate_style_bindings",
+                "validate_styled_batch", "validate_styles", "validate_tile_batch", "validate_tile_index")
+
+
+def test_library_exports_no_unprefixed_helper():
+    """Helpers of the host side once had C linkage by accident and left the library under these names, where any other C code of
+    the process could collide with them.  They are internal now; the C ABI itself still resolves, name by name."""
+    if not os.path.exists(lib.LIB_PATH):
+        pytest.fail("libosmtile.so is not built: run __graft_entry__.build()")
+    L = C.CDLL(lib.LIB_PATH)
+    for name in _ONCE_LEAKED:
+        with pytest.raises(AttributeError):
+            getattr(L, name)
+    for name in lib.EXPORTS:
+        assert getattr(L, name) is not None, name
+
+
 def test_struct_layouts_match_the_header():
     s = _shim.lib().shim_sizeof
     assert s(0) == C.sizeof(abi.Op) == display_list.OP_DTYPE.itemsize == 64
