@@ -715,7 +715,7 @@ int osmt_scene_max_tile_ops(osmt_ctx* ctx, osmt_scene* scene, uint32_t* out_max_
  * neighbourhood, their way and multipolygon lists gathered, sorted, made unique, multipolygons without polygons dropped —
  * expands every entity by its bound styles and hands the resulting styled batch to the build of osmt_scene_build_styled:
  * byte for byte the display list that call builds from the batch osmt::styled_areas_of_tile (host/osmt_tilequery.hpp)
- * makes on the host.  The osm_ids debug filter of the reference is not supported. */
+ * makes on the host.  The osm_ids filter of the reference is osmt_scene_build_tiles_filtered below. */
 
 #define OSMT_QUERY_MAX_TILE_CANDIDATES (1u << 20) /* way (or multipolygon) references gathered for ONE tile before dedup */
 #define OSMT_QUERY_LDS_CANDIDATES 8192u           /* up to here a tile's candidates are sorted in LDS (32 KB of u32) */
@@ -787,6 +787,42 @@ int osmt_scene_build_tiles(osmt_ctx* ctx, const osmt_tile_batch* batch, osmt_sce
  * from any other source, or when areas_cap is less than *n_areas. */
 int osmt_scene_read_styled_areas(osmt_ctx* ctx, osmt_scene* scene, osmt_styled_tile* tiles, osmt_styled_area* areas,
                                  size_t areas_cap, size_t* n_areas);
+
+/* ---- the osm_ids filter: a set of global ids as bit-planes on the GPU -------------------------------------------- */
+/* The one argument of get_entities_in_tile_with_neighbors(tile, osm_ids) (reader.rs:60,95-99): filter_entities_by_ids
+ * (reader.rs:254-262) keeps an entity iff its global_id() is in the set.  ONE set serves nodes, ways and multipolygons alike
+ * (the reference holds one HashSet<u64>): an id that a node and a way share keeps both.  `ids` may come in any order, with
+ * repeats; n == 0 is a valid filter that keeps nothing (Some(empty)) and is not OSMT_ID_FILTER_NONE (None).
+ *
+ * Registration sorts and dedups the set on the host (once per filter, small), uploads it, and the device builds one bit-plane
+ * per kind, 1 bit per entity of the geodata file (csrc/osmt_idfilter.hip): a lower-bound bisection per entity.  A registered
+ * filter is one allocation that never moves; append-only with the snapshot rule of bindings, styles and fonts: a later
+ * registration never disturbs a scene that is already built.  The node plane is built iff a node index
+ * (osmt_register_node_index: it carries the nodes' global ids) is registered for the geodata id AT THAT MOMENT.
+ *
+ * Order of the drops and the limits, as in the reference, which gathers, sorts, dedups, drops polygon-less multipolygons and
+ * filters LAST: the per-tile candidate limit OSMT_QUERY_MAX_TILE_CANDIDATES and the candidate totals are judged BEFORE the
+ * filter (a filtered build gathers what an unfiltered one gathers); the area limit OSMT_STYLED_MAX_TILE_AREAS, the label limit
+ * OSMT_TILE_LABELS_MAX and the area and label totals are judged AFTER it. */
+#define OSMT_ID_FILTER_NONE 0xFFFFFFFFu
+/* OSMT_INVALID_ARG, naming the offender: n >= 2^31; a NULL array with a non-zero count; an unknown geodata id (a NULL `ctx`
+ * has none).  The first two need no context. */
+int osmt_validate_id_filter(const uint64_t* ids, size_t n, uint32_t geodata_id, osmt_ctx* ctx);
+/* Validates, builds the planes and returns the filter's id. */
+int osmt_register_id_filter(osmt_ctx* ctx, uint32_t geodata_id, const uint64_t* ids, size_t n, uint32_t* out_filter_id);
+/* Inspection: the three bit-planes as 32-bit words, entity e = bit e % 32 of word e / 32; a plane has whole 64-bit words and the
+ * bits past the entity count are 0.  counts = { way words, multipolygon words, node words (0 without a node plane) } is always
+ * set; caps bound what is written (a smaller cap with a non-NULL output is OSMT_INVALID_ARG); each output may be NULL. */
+int osmt_read_id_filter(osmt_ctx* ctx, uint32_t filter_id, uint32_t* way_words, uint32_t* mp_words, uint32_t* node_words,
+                        const size_t caps[3], size_t counts[3]);
+/* osmt_scene_build_tiles with the filter: with OSMT_ID_FILTER_NONE it IS that call; otherwise the scene holds the filter's
+ * snapshot, and osmt_scene_build_tile_labels and osmt_scene_build_tile_labels_all apply it to nodes, ways and multipolygons —
+ * one filter per scene, as there is one per request in the reference.  OSMT_INVALID_ARG: an unknown filter id, a filter of
+ * another geodata id than the batch's.  A label build with node bindings on a scene whose filter has no node plane is
+ * OSMT_INVALID_ARG: register the node index first, then the filter.  A handed-in anchor
+ * (osmt_scene_build_tile_labels_all) whose entity the filter removed is treated as every listed pair that has no labels in
+ * its tile: it is validated like the others and then not looked at. */
+int osmt_scene_build_tiles_filtered(osmt_ctx* ctx, const osmt_tile_batch* batch, uint32_t filter_id, osmt_scene** out_scene);
 
 /* ---- label anchors from tile coordinates: the exact projection on the GPU ---------------------------------------- */
 /* osmt_label_positions for callers that hold a registered geodata file: a request is 8 bytes — an entity and a tile — and
@@ -1462,6 +1498,63 @@ int osmt_worker_create(osmt_ctx* ctx, osmt_worker** out_worker);
 void osmt_worker_destroy(osmt_worker* worker);
 int osmt_worker_render(osmt_worker* worker, const osmt_batch* batch, const osmt_label_batch* labels /* may be NULL */, uint8_t* out_rgb,
                        size_t out_tile_stride_bytes);
+
+/* ---- tile requests: (z, x, y, scale) in, PNG out ------------------------------------------------------------------ */
+/* The reference's request handler (try_handle_connection, src/http_server.rs:134-181) as one step: what a server renders
+ * its requests with — geodata, bindings per zoom, canvas, filter — is stated ONCE, in a tile server; a request is then tile
+ * coordinates and a scale.  The server is immutable, holds a reference on its context like a scene or a worker, and is
+ * validated once: every id known, of this geodata id and covering the zoom it is listed under, the filter of this geodata id,
+ * a node index (and, with a filter, a node plane) where node labels are bound.  A label array that is all
+ * OSMT_BINDINGS_NONE means no labels of that kind. */
+typedef struct osmt_tile_server_desc {
+    uint32_t geodata_id, use_caps_for_dashes;
+    uint32_t id_filter; /* from osmt_register_id_filter, or OSMT_ID_FILTER_NONE */
+    uint8_t has_canvas, canvas_rgb[3];
+    uint32_t bindings_of_zoom[OSMT_MAX_ZOOM + 1];            /* osmt_register_style_bindings[_matched] / osmt_cascade_register */
+    uint32_t area_label_bindings_of_zoom[OSMT_MAX_ZOOM + 1]; /* all OSMT_BINDINGS_NONE: no labels of that kind */
+    uint32_t node_label_bindings_of_zoom[OSMT_MAX_ZOOM + 1];
+} osmt_tile_server_desc;
+typedef struct osmt_tile_server osmt_tile_server;
+typedef struct osmt_tile_coord { /* 12 bytes */
+    uint32_t x, y, zoom;
+} osmt_tile_coord;
+
+/* OSMT_INVALID_ARG, naming the offender (a NULL `ctx` knows no geodata id). */
+int osmt_validate_tile_server(const osmt_tile_server_desc* d, osmt_ctx* ctx);
+int osmt_tile_server_create(osmt_ctx* ctx, const osmt_tile_server_desc* d, osmt_tile_server** out);
+void osmt_tile_server_free(osmt_tile_server* s);
+/* Tiles in, files out, in one call, on the library's own streams: osmt_scene_build_tiles[_filtered], then — if a label array
+ * is not all-NONE — osmt_scene_build_tile_labels_all, then osmt_render_scene_png, then the scene is freed.  out_png / out_off
+ * [n + 1] follow the osmt_render_batch_png contract: the offsets are filled even when out_capacity is too small
+ * (OSMT_INVALID_ARG), so the call can be repeated; n * osmt_png_device_bound(W, W) always suffices.  n == 0 is OSMT_OK and
+ * touches no device.  A tile at a zoom whose style bindings are OSMT_BINDINGS_NONE is OSMT_INVALID_ARG, and so is one at a
+ * zoom with NONE in a label array that is not all-NONE: judged for this call alone, by the rules of osmt_validate_tile_batch
+ * and osmt_scene_build_tile_labels_all.  `anchors` follow the osmt_scene_build_tile_labels_all contract (tile = index into
+ * `tiles`).  When the anchor search declines pairs the call is OSMT_UNSUPPORTED as that call is, and the declined list is kept
+ * for the calling thread (osmt_last_declined_anchors): compute the anchors and call again.  A label is never wrong and
+ * never dropped. */
+int osmt_tile_server_render_png(osmt_tile_server* s, const osmt_tile_coord* tiles, size_t n, uint32_t scale,
+                                const osmt_area_anchor* anchors, size_t n_anchors, uint8_t* out_png, size_t out_capacity,
+                                uint64_t* out_off /* [n + 1] */);
+/* The pairs the last osmt_tile_server_render_png / osmt_worker_render_tile_png call of THIS thread declined (tile = index into
+ * that call's tiles; empty after a call that declined nothing).  Thread-local like osmt_last_error.  *n is always set; out
+ * may be NULL; a cap below *n with a non-NULL out is OSMT_INVALID_ARG. */
+int osmt_last_declined_anchors(osmt_area_anchor* out, size_t cap, size_t* n);
+/* The per-request entry: one tile, one file.  Group commit exactly as osmt_worker_render does it: the requester validates its
+ * own request and queues it; a request that finds fewer than OSMT_WORKER_INFLIGHT groups on the device (a count it shares with
+ * osmt_worker_render) becomes leader and takes the waiting requests of the server and scale at the head of the queue, in
+ * arrival order, up to the first request of another server or scale (the next leader's) and up to 64 tiles — mixed zooms share
+ * a group — and runs the body of osmt_tile_server_render_png once into pinned staging; every
+ * requester copies its own file out.  No timer: a lone request never waits.  If the group's run fails for any reason every
+ * member is run alone, so a bad request or a declined anchor fails alone and the others get their files; a member's declined
+ * list (tile 0 in each) is left for ITS thread.  anchors: tile == 0 in each.  out_capacity too small: OSMT_INVALID_ARG,
+ * *out_len is the size needed and nothing is written; osmt_png_device_bound(W, W) always suffices. */
+int osmt_worker_render_tile_png(osmt_worker* w, osmt_tile_server* s, const osmt_tile_coord* tile, uint32_t scale,
+                                const osmt_area_anchor* anchors, size_t n_anchors, uint8_t* out_png, size_t out_capacity,
+                                size_t* out_len);
+/* Inspection: stats = { requests queued, groups run, tiles of the largest group } of osmt_worker_render_tile_png since the
+ * context was created. */
+int osmt_worker_tile_stats(osmt_ctx* ctx, uint64_t stats[3]);
 
 /* ---- one node, several GPUs ------------------------------------------------ */
 /* The reference deals tiles round-robin to its worker threads, each with its own TilePixels

@@ -35,6 +35,7 @@ MAX_FILL_GROUPS = 1 << 28  # fill groups (fill op x sub-tile of its window) of o
 QUERY_MAX_TILE_CANDIDATES = 1 << 20  # references of one kind osmt_scene_build_tiles gathers for one tile before dedup
 QUERY_LDS_CANDIDATES = 8192  # up to here a tile's candidates are sorted in LDS
 BINDINGS_NONE = 0xFFFFFFFF  # osmt_tile_batch.bindings_of_zoom: the zoom has no bindings
+ID_FILTER_NONE = 0xFFFFFFFF  # osmt_scene_build_tiles_filtered: no osm_ids filter (an EMPTY filter keeps nothing)
 TILE_LABELS_MAX = 65536  # (node, style) labels osmt_scene_build_tile_labels builds for one tile
 TEXT_NONE = 0xFFFFFFFF  # osmt_label_binding.text: the tag text_style.text names is absent on the node
 LABEL_POSITION_NONE, LABEL_POSITION_CENTER, LABEL_POSITION_LINE = 0, 1, 2  # osmt_label_style_rec.text_position
@@ -517,6 +518,27 @@ class AreaAnchor(C.Structure):  # osmt_area_anchor
 
 assert C.sizeof(AreaLabelBindingsDesc) == 88
 assert C.sizeof(AreaAnchor) == 32
+
+
+# ---- tile requests (osmt_tile_server_*, osmt_worker_render_tile_png) ------------------------------------------------
+class TileServerDesc(C.Structure):  # osmt_tile_server_desc
+    _fields_ = [
+        ("geodata_id", C.c_uint32),
+        ("use_caps_for_dashes", C.c_uint32),
+        ("id_filter", C.c_uint32),
+        ("has_canvas", C.c_uint8),
+        ("canvas_rgb", C.c_uint8 * 3),
+        ("bindings_of_zoom", C.c_uint32 * (MAX_ZOOM + 1)),
+        ("area_label_bindings_of_zoom", C.c_uint32 * (MAX_ZOOM + 1)),
+        ("node_label_bindings_of_zoom", C.c_uint32 * (MAX_ZOOM + 1)),
+    ]
+
+
+class TileCoord(C.Structure):  # osmt_tile_coord
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("zoom", C.c_uint32)]
+
+
+assert C.sizeof(TileServerDesc) == 16 + 3 * 4 * (MAX_ZOOM + 1) and C.sizeof(TileCoord) == 12
 
 
 # ---- selector matching (osmt_match_selectors) ----------------------------------------------------------------------

@@ -33,6 +33,7 @@
 #include "osmt_numparse.h" /* osmt_bytes_cmp: the key order of osmt_validate_tags */
 #include "osmt_utf8.h"     /* the byte a refused tag value stops the decoder at */
 #include "osmt_png_table.h" /* PNG_LMAX, PNG_BLOCK_HDR_BITS: the slot bound */
+#include "../host/osmt_idfilter.hpp"   /* osmt::id_filter_set: the sort and dedup of a registered id filter */
 #include "../host/osmt_textplacer.hpp" /* osmt::validate_text_labels */
 #include "../host/osmt_textshaper.hpp" /* osmt::validate_font, osmt::validate_string_labels */
 
@@ -201,6 +202,15 @@ struct osmt_ctx {
         size_t n_ways = 0, n_mps = 0, n_way_bindings = 0, n_mp_bindings = 0, n_texts = 0, n_chars = 0; /* osmt_read_area_label_bindings */
     };
     std::vector<area_label_bindings_host> area_label_bindings;
+    /* the id filters of osmt_register_id_filter, under the same rules: the sorted set and the three planes in one allocation */
+    struct id_filter_host {
+        uint32_t geodata_id = 0;
+        bool on = false; /* in a scene: it was built with this filter */
+        void* d_pool = nullptr;
+        const uint32_t *way = nullptr, *mp = nullptr, *node = nullptr; /* node: NULL without a node plane */
+        size_t n_way_words = 0, n_mp_words = 0, n_node_words = 0;      /* 32-bit words */
+    };
+    std::vector<id_filter_host> id_filters;
     /* the label styles of osmt_register_label_styles: records and ranks, replaced like the style table when it has grown */
     std::vector<osmt_label_style_rec> label_styles;
     osmt_label_style_rec* d_label_styles = nullptr;
@@ -241,6 +251,9 @@ struct osmt_ctx {
     std::condition_variable co_cv;
     std::deque<struct coalesce_req*> co_queue;
     int co_in_flight = 0;
+    /* the same for osmt_worker_render_tile_png: its own queue, the SAME count of groups in flight, and osmt_worker_tile_stats */
+    std::deque<struct tile_req*> co_tile_queue;
+    uint64_t co_tile_stats[3] = {0, 0, 0}; /* requests, groups run, tiles of the largest group */
     /* osmt_label_positions_stats: requests / left the LDS tier / answered TOO_LARGE of the last completed call (cache_mu) */
     uint64_t pl_stats[3] = {0, 0, 0};
 };
@@ -336,6 +349,7 @@ struct osmt_scene {
     size_t n_tq_areas = 0;
     std::vector<osmt_query_tile> h_tq_tiles; /* the tiles it was built from, for osmt_scene_build_tile_labels */
     uint32_t tq_geodata_id = 0;
+    osmt_ctx::id_filter_host tq_filter; /* the snapshot of the filter it was built with (osmt_scene_build_tiles_filtered); `on` false: none */
     /* the node batch the last osmt_scene_build_tile_labels read back (osmt_scene_read_tile_labels) */
     std::vector<osmt_label> h_tl_labels;
     std::vector<osmt_string_run> h_tl_runs;
@@ -817,6 +831,8 @@ void ctx_teardown(osmt_ctx* ctx) {
     for (auto& b : ctx->label_bindings)
         if (b.d_pool) (void)hipFree(b.d_pool);
     for (auto& b : ctx->area_label_bindings)
+        if (b.d_pool) (void)hipFree(b.d_pool);
+    for (auto& b : ctx->id_filters)
         if (b.d_pool) (void)hipFree(b.d_pool);
     if (ctx->d_label_styles) (void)hipFree(ctx->d_label_styles);
     if (ctx->d_label_rank) (void)hipFree(ctx->d_label_rank);
@@ -2515,13 +2531,22 @@ int validate_tile_batch(const osmt_tile_batch* b, osmt_ctx* ctx, osmt_tq_bind_de
     return OSMT_OK;
 }
 
-int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene** out_scene) {
+int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, uint32_t filter_id, osmt_scene** out_scene) {
     if (!ctx || !out_scene) return fail(OSMT_INVALID_ARG, "NULL argument");
     *out_scene = nullptr;
     osmt_tq_bind_dev bind[OSMT_MAX_ZOOM + 1];
     memset(bind, 0, sizeof bind);
     int rc = validate_tile_batch(b, ctx, bind);
     if (rc != OSMT_OK) return rc;
+    osmt_ctx::id_filter_host flt;
+    if (filter_id != OSMT_ID_FILTER_NONE) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (filter_id >= ctx->id_filters.size()) return fail(OSMT_INVALID_ARG, "id filter %u is not registered (%zu filters)", filter_id, ctx->id_filters.size());
+        flt = ctx->id_filters[filter_id];
+        if (flt.geodata_id != b->geodata_id)
+            return fail(OSMT_INVALID_ARG, "id filter %u belongs to geodata id %u, not %u", filter_id, flt.geodata_id, b->geodata_id);
+        flt.on = true;
+    }
     HIP_TRY(hipSetDevice(ctx->device));
     styles_snapshot ss;
     rc = sync_styles(ctx, &ss);
@@ -2557,6 +2582,7 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
         HIP_TRY(hipMemcpyAsync(w0 + o_bind, bind, sizeof bind, hipMemcpyHostToDevice, st));
         P.ix = geo.ix;
         P.geo_mp_off = geo.dev.mp_off;
+        if (flt.on) P.keep_way = flt.way, P.keep_mp = flt.mp;
         P.bind = (const osmt_tq_bind_dev*)(w0 + o_bind);
         P.q = (const osmt_query_tile*)(w0 + o_q);
         P.n_tiles = (uint32_t)n_tiles;
@@ -2693,6 +2719,7 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, osmt_scene**
     s->n_tq_areas = n_areas;
     s->h_tq_tiles.assign(b->tiles, b->tiles + n_tiles);
     s->tq_geodata_id = b->geodata_id;
+    s->tq_filter = flt;
     kg.head = kg.areas = nullptr;
     if (trace && n_tiles) {
         fprintf(stderr,
@@ -2732,7 +2759,115 @@ int scene_read_display_list_body(osmt_ctx* ctx, osmt_scene* sc, osmt_tile_job* j
     return OSMT_OK;
 }
 
+/* ---- the id filter: filter_entities_by_ids (reader.rs:254-262) as three bit-planes ---- */
+/* geo (optional): the file's record at the time of the call */
+int validate_id_filter(const uint64_t* ids, size_t n, uint32_t geodata_id, osmt_ctx* ctx, osmt_ctx::geodata_host* geo) {
+    if (n >= 0x80000000ull) return fail(OSMT_INVALID_ARG, "id filter: %zu ids (at most 2^31 - 1)", n);
+    if (n && !ids) return fail(OSMT_INVALID_ARG, "id filter: ids is NULL with n = %zu", n);
+    if (!ctx) return fail(OSMT_INVALID_ARG, "id filter: geodata id %u is not registered (no context)", geodata_id);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (geodata_id >= ctx->geodata.size()) return fail(OSMT_INVALID_ARG, "id filter: geodata id %u is not registered (%zu files)", geodata_id, ctx->geodata.size());
+    if (geo) *geo = ctx->geodata[geodata_id];
+    return OSMT_OK;
+}
+
+int register_id_filter_body(osmt_ctx* ctx, uint32_t geodata_id, const uint64_t* ids, size_t n, uint32_t* out_id) {
+    if (!ctx || !out_id) return fail(OSMT_INVALID_ARG, "NULL argument");
+    osmt_ctx::geodata_host geo;
+    const int rc = validate_id_filter(ids, n, geodata_id, ctx, &geo);
+    if (rc != OSMT_OK) return rc;
+    /* once per filter and small: the host sorts and dedups, the device bisects */
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu); /* judged before any device work; once more where the filter is appended */
+        if (ctx->id_filters.size() + 1 >= 0xFFFFFFFFull)
+            return fail(OSMT_INVALID_ARG, "id filter: the context holds %zu filters already (at most 2^32 - 2)", ctx->id_filters.size());
+    }
+    const std::vector<uint64_t> set = osmt::id_filter_set(ids, n);
+    const bool nodes = geo.d_node_index != nullptr; /* the nodes' global ids come with the node index */
+    const size_t count[3] = {geo.n_ways, geo.n_mps, nodes ? geo.n_nodes : 0};
+    for (size_t c : count)
+        if (c >= 0xFFFFFF00ull) return fail(OSMT_UNSUPPORTED, "id filter: %zu entities of one kind do not fit 32-bit indices", c);
+    HIP_TRY(hipSetDevice(ctx->device));
+    pool_layout pl;
+    const size_t o_ids = pl.add(set.size() * 8);
+    size_t o_plane[3], words[3]; /* 32-bit words: whole 64-bit words of the kernel */
+    for (int k = 0; k < 3; ++k) words[k] = (count[k] + 63) / 64 * 2, o_plane[k] = pl.add(words[k] * 4);
+    table_upload up("id filter", pl);
+    char* pool = up.pool;
+    if (up.done() != OSMT_OK) return up.done();
+    if (poison_alloc()) HIP_TRY(dev_poison(ctx, pool, pl.size())); /* the planes are written by k_idf_plane alone */
+    up.put(o_ids, set.data(), set.size() * 8);
+    if (up.done() != OSMT_OK) return up.done();
+    {
+        hipStream_t st = nullptr;
+        HIP_TRY(stream_acquire(ctx, &st));
+        const uint64_t* d_ids = (const uint64_t*)(pool + o_ids);
+        hipEvent_t ev[2] = {nullptr, nullptr}; /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the three planes */
+        const bool trace = trace_upload() && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+        if (trace) (void)hipEventRecord(ev[0], st);
+        hipError_t e = osmt_launch_idf_plane(geo.dev.way_gid, (uint32_t)count[0], d_ids, (uint32_t)set.size(), (uint32_t*)(pool + o_plane[0]), st);
+        if (e == hipSuccess) e = osmt_launch_idf_plane(geo.dev.mp_gid, (uint32_t)count[1], d_ids, (uint32_t)set.size(), (uint32_t*)(pool + o_plane[1]), st);
+        if (e == hipSuccess && nodes) e = osmt_launch_idf_plane(geo.d_node_gid, (uint32_t)count[2], d_ids, (uint32_t)set.size(), (uint32_t*)(pool + o_plane[2]), st);
+        if (trace) (void)hipEventRecord(ev[1], st);
+        const hipError_t es = hipStreamSynchronize(st); /* the table is complete before anyone can name it */
+        float ms = 0.f;
+        if (trace && e == hipSuccess && es == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+            fprintf(stderr, "osmt id filter: planes %.1f us (%zu ways, %zu multipolygons, %zu nodes, %zu ids of %zu given)\n", ms * 1e3, count[0], count[1],
+                    count[2], set.size(), n);
+        for (hipEvent_t v : ev)
+            if (v) (void)hipEventDestroy(v);
+        stream_release(ctx, st);
+        HIP_TRY(e);
+        HIP_TRY(es);
+    }
+    osmt_ctx::id_filter_host h;
+    h.geodata_id = geodata_id;
+    h.d_pool = pool;
+    h.way = (const uint32_t*)(pool + o_plane[0]);
+    h.mp = (const uint32_t*)(pool + o_plane[1]);
+    h.node = nodes ? (const uint32_t*)(pool + o_plane[2]) : nullptr;
+    h.n_way_words = words[0], h.n_mp_words = words[1], h.n_node_words = words[2];
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->id_filters.size() + 1 >= 0xFFFFFFFFull) /* other threads filled the table meanwhile */
+        return fail(OSMT_INVALID_ARG, "id filter: the context holds %zu filters already (at most 2^32 - 2)", ctx->id_filters.size());
+    *out_id = (uint32_t)ctx->id_filters.size();
+    ctx->id_filters.push_back(h);
+    up.release();
+    return OSMT_OK;
+}
+
+int read_id_filter_body(osmt_ctx* ctx, uint32_t filter_id, uint32_t* way_words, uint32_t* mp_words, uint32_t* node_words, const size_t* caps, size_t* counts) {
+    if (!ctx || !counts) return fail(OSMT_INVALID_ARG, "NULL argument");
+    osmt_ctx::id_filter_host h;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (filter_id >= ctx->id_filters.size()) return fail(OSMT_INVALID_ARG, "id filter %u is not registered (%zu filters)", filter_id, ctx->id_filters.size());
+        h = ctx->id_filters[filter_id];
+    }
+    counts[0] = h.n_way_words, counts[1] = h.n_mp_words, counts[2] = h.n_node_words;
+    uint32_t* const out[3] = {way_words, mp_words, node_words};
+    const uint32_t* const src[3] = {h.way, h.mp, h.node};
+    if ((way_words || mp_words || node_words) && !caps) return fail(OSMT_INVALID_ARG, "caps is NULL");
+    for (int k = 0; k < 3; ++k)
+        if (out[k] && caps[k] < counts[k]) return fail(OSMT_INVALID_ARG, "caps[%d] = %zu is less than the plane's %zu words", k, caps[k], counts[k]);
+    HIP_TRY(hipSetDevice(ctx->device));
+    for (int k = 0; k < 3; ++k)
+        if (out[k] && counts[k]) HIP_TRY(copy_back(ctx, out[k], src[k], counts[k] * 4));
+    return OSMT_OK;
+}
+
 }  // namespace
+
+int osmt_validate_id_filter(const uint64_t* ids, size_t n, uint32_t geodata_id, osmt_ctx* ctx) {
+    return guarded([&] { return validate_id_filter(ids, n, geodata_id, ctx, nullptr); });
+}
+int osmt_register_id_filter(osmt_ctx* ctx, uint32_t geodata_id, const uint64_t* ids, size_t n, uint32_t* out_filter_id) {
+    return guarded([&] { return register_id_filter_body(ctx, geodata_id, ids, n, out_filter_id); });
+}
+int osmt_read_id_filter(osmt_ctx* ctx, uint32_t filter_id, uint32_t* way_words, uint32_t* mp_words, uint32_t* node_words, const size_t caps[3],
+                        size_t counts[3]) {
+    return guarded([&] { return read_id_filter_body(ctx, filter_id, way_words, mp_words, node_words, caps, counts); });
+}
 
 int osmt_validate_geodata(const osmt_geodata_desc* geodata) {
     return guarded([&] { return validate_geodata(geodata); });
@@ -2768,7 +2903,10 @@ int osmt_validate_tile_batch(const osmt_tile_batch* batch, osmt_ctx* ctx) {
     return guarded([&] { return validate_tile_batch(batch, ctx, nullptr); });
 }
 int osmt_scene_build_tiles(osmt_ctx* ctx, const osmt_tile_batch* batch, osmt_scene** out_scene) {
-    return guarded([&] { return scene_build_tiles_body(ctx, batch, out_scene); });
+    return guarded([&] { return scene_build_tiles_body(ctx, batch, OSMT_ID_FILTER_NONE, out_scene); });
+}
+int osmt_scene_build_tiles_filtered(osmt_ctx* ctx, const osmt_tile_batch* batch, uint32_t filter_id, osmt_scene** out_scene) {
+    return guarded([&] { return scene_build_tiles_body(ctx, batch, filter_id, out_scene); });
 }
 int osmt_scene_read_styled_areas(osmt_ctx* ctx, osmt_scene* scene, osmt_styled_tile* tiles, osmt_styled_area* areas, size_t areas_cap,
                                  size_t* n_areas) {
@@ -3465,6 +3603,11 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         std::lock_guard<std::mutex> lk(ctx->mu);
         geo = ctx->geodata[sc->tq_geodata_id];
         if (!geo.d_node_index) return fail(OSMT_INVALID_ARG, "geodata id %u has no node index (osmt_register_node_index)", sc->tq_geodata_id);
+        if (sc->tq_filter.on && !sc->tq_filter.node)
+            return fail(OSMT_INVALID_ARG,
+                        "the scene's id filter has no node plane: it was registered before the node index of geodata id %u; register the node index first "
+                        "(osmt_register_node_index), then the filter, and build the scene again",
+                        sc->tq_geodata_id);
         for (uint32_t z = 0; z <= OSMT_MAX_ZOOM; ++z) {
             if (!zoom_used[z]) continue;
             const uint32_t id = bindings_of_zoom[z];
@@ -3602,6 +3745,7 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         P.scale = sc->scale;
         P.t_base = Q.t_wbase;
         P.cand = Q.cand;
+        if (sc->tq_filter.on) P.keep_node = sc->tq_filter.node;
         P.lpos = (uint32_t*)(w2 + o_lpos);
         P.job_label_off = (uint32_t*)(w0 + o_jo);
         P.blk = (unsigned long long*)(w2 + o_blk2);
@@ -4479,6 +4623,7 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     /* 1. the query over the way and multipolygon pools, as osmt_scene_build_tiles runs it */
     Q.ix = geo.ix;
     Q.geo_mp_off = geo.dev.mp_off;
+    if (sc->tq_filter.on) Q.keep_way = sc->tq_filter.way, Q.keep_mp = sc->tq_filter.mp; /* the scene's filter: one per request (reader.rs:60) */
     Q.bind = (const osmt_tq_bind_dev*)(w0 + o_tqb);
     Q.q = (const osmt_query_tile*)(w0 + o_q);
     Q.n_tiles = (uint32_t)n_tiles;
@@ -6408,6 +6553,369 @@ void osmt_worker_destroy(osmt_worker* w) {
 
 int osmt_worker_render(osmt_worker* w, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgb, size_t out_tile_stride_bytes) {
     return guarded([&] { return worker_render_body(w, batch, labels, out_rgb, out_tile_stride_bytes); });
+}
+
+/* ---- tile requests: (z, x, y, scale) in, PNG out ---------------------------------------------------------------------
+ * try_handle_connection (src/http_server.rs:134-181) per request: get_entities_in_tile_with_neighbors(tile, osm_ids) ->
+ * draw_tile -> PNG bytes.  A tile server states once what every request is rendered with — geodata, bindings per zoom,
+ * canvas, filter; osmt_tile_server_render_png is build (filtered or not) -> label -> osmt_render_scene_png -> free for a
+ * list of tiles, and osmt_worker_render_tile_png gathers the one-tile requests of concurrent threads into such lists by the
+ * group commit of osmt_worker_render above, sharing its cap on groups in flight. */
+struct osmt_tile_server {
+    osmt_ctx* ctx = nullptr;
+    osmt_tile_server_desc d{};
+    bool area_labels = false, node_labels = false; /* the label array is not all OSMT_BINDINGS_NONE */
+};
+
+namespace {
+
+/* the pairs the last tile-server call of this thread declined (osmt_last_declined_anchors) */
+thread_local std::vector<osmt_area_anchor> tl_declined;
+
+bool any_bound(const uint32_t* of_zoom) {
+    for (uint32_t z = 0; z <= OSMT_MAX_ZOOM; ++z)
+        if (of_zoom[z] != OSMT_BINDINGS_NONE) return true;
+    return false;
+}
+
+int validate_tile_server(const osmt_tile_server_desc* d, osmt_ctx* ctx) {
+    if (!d) return fail(OSMT_INVALID_ARG, "tile server: the description is NULL");
+    if (!ctx) return fail(OSMT_INVALID_ARG, "tile server: geodata id %u is not registered (no context)", d->geodata_id);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (d->geodata_id >= ctx->geodata.size())
+        return fail(OSMT_INVALID_ARG, "tile server: geodata id %u is not registered (%zu files)", d->geodata_id, ctx->geodata.size());
+    if (!ctx->geodata[d->geodata_id].d_index)
+        return fail(OSMT_INVALID_ARG, "tile server: geodata id %u has no tile index (osmt_register_tile_index)", d->geodata_id);
+    /* one table of one kind under one zoom: known, of this file, covering that zoom */
+    auto table_ok = [&](const char* kind, uint32_t id, uint32_t z, size_t n, uint32_t geodata_id, uint32_t lo, uint32_t hi) {
+        if (id >= n) return fail(OSMT_INVALID_ARG, "tile server: %s id %u of zoom %u is not registered (%zu tables)", kind, id, z, n);
+        if (geodata_id != d->geodata_id)
+            return fail(OSMT_INVALID_ARG, "tile server: %s id %u of zoom %u belongs to geodata id %u, not %u", kind, id, z, geodata_id, d->geodata_id);
+        if (z < lo || z > hi) return fail(OSMT_INVALID_ARG, "tile server: %s id %u covers zooms %u..%u, not zoom %u", kind, id, lo, hi, z);
+        return (int)OSMT_OK;
+    };
+    for (uint32_t z = 0; z <= OSMT_MAX_ZOOM; ++z) {
+        int rc = OSMT_OK;
+        uint32_t id = d->bindings_of_zoom[z];
+        if (id != OSMT_BINDINGS_NONE) {
+            const bool known = id < ctx->bindings.size();
+            rc = table_ok("bindings", id, z, ctx->bindings.size(), known ? ctx->bindings[id].geodata_id : 0u, known ? ctx->bindings[id].zoom_lo : 0u,
+                          known ? ctx->bindings[id].zoom_hi : 0u);
+            if (rc != OSMT_OK) return rc;
+        }
+        id = d->area_label_bindings_of_zoom[z];
+        if (id != OSMT_BINDINGS_NONE) {
+            const bool known = id < ctx->area_label_bindings.size();
+            rc = table_ok("area label bindings", id, z, ctx->area_label_bindings.size(), known ? ctx->area_label_bindings[id].geodata_id : 0u,
+                          known ? ctx->area_label_bindings[id].zoom_lo : 0u, known ? ctx->area_label_bindings[id].zoom_hi : 0u);
+            if (rc != OSMT_OK) return rc;
+        }
+        id = d->node_label_bindings_of_zoom[z];
+        if (id != OSMT_BINDINGS_NONE) {
+            const bool known = id < ctx->label_bindings.size();
+            rc = table_ok("node label bindings", id, z, ctx->label_bindings.size(), known ? ctx->label_bindings[id].geodata_id : 0u,
+                          known ? ctx->label_bindings[id].zoom_lo : 0u, known ? ctx->label_bindings[id].zoom_hi : 0u);
+            if (rc != OSMT_OK) return rc;
+        }
+    }
+    if (any_bound(d->node_label_bindings_of_zoom) && !ctx->geodata[d->geodata_id].d_node_index)
+        return fail(OSMT_INVALID_ARG, "tile server: node label bindings, but geodata id %u has no node index (osmt_register_node_index)", d->geodata_id);
+    if (d->id_filter != OSMT_ID_FILTER_NONE) {
+        if (d->id_filter >= ctx->id_filters.size())
+            return fail(OSMT_INVALID_ARG, "tile server: id filter %u is not registered (%zu filters)", d->id_filter, ctx->id_filters.size());
+        const osmt_ctx::id_filter_host& f = ctx->id_filters[d->id_filter];
+        if (f.geodata_id != d->geodata_id)
+            return fail(OSMT_INVALID_ARG, "tile server: id filter %u belongs to geodata id %u, not %u", d->id_filter, f.geodata_id, d->geodata_id);
+        if (any_bound(d->node_label_bindings_of_zoom) && !f.node)
+            return fail(OSMT_INVALID_ARG,
+                        "tile server: node label bindings, but id filter %u has no node plane: register the node index first (osmt_register_node_index), "
+                        "then the filter",
+                        d->id_filter);
+    }
+    return OSMT_OK;
+}
+
+/* what a requesting thread judges of its own tiles before anything is queued or built: the rules of osmt_validate_tile_batch and
+ * of osmt_scene_build_tile_labels_all for the zooms these tiles have */
+int tile_request_ok(const osmt_tile_server* s, const osmt_tile_coord* tiles, size_t n, uint32_t scale) {
+    if (scale < 1 || scale > OSMT_MAX_SCALE) return fail(OSMT_INVALID_ARG, "scale %u not in 1..%u", scale, OSMT_MAX_SCALE);
+    for (size_t t = 0; t < n; ++t) {
+        const osmt_tile_coord& q = tiles[t];
+        if (q.zoom > OSMT_MAX_ZOOM) return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u > MAX_ZOOM (src/tile.rs:5)", t, q.zoom);
+        if (q.x >= (1u << q.zoom) || q.y >= (1u << q.zoom))
+            return fail(OSMT_INVALID_ARG, "tile %zu: (x, y) = (%u, %u) outside the %u x %u tiles of zoom %u", t, q.x, q.y, 1u << q.zoom, 1u << q.zoom, q.zoom);
+        if (s->d.bindings_of_zoom[q.zoom] == OSMT_BINDINGS_NONE)
+            return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u has no bindings (OSMT_BINDINGS_NONE)", t, q.zoom);
+        if (s->area_labels && s->d.area_label_bindings_of_zoom[q.zoom] == OSMT_BINDINGS_NONE)
+            return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u has no area label bindings (OSMT_BINDINGS_NONE)", t, q.zoom);
+        if (s->node_labels && s->d.node_label_bindings_of_zoom[q.zoom] == OSMT_BINDINGS_NONE)
+            return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u has no label bindings (OSMT_BINDINGS_NONE)", t, q.zoom);
+    }
+    return OSMT_OK;
+}
+
+/* build (filtered or not) -> label -> PNG -> free, on the library's own streams.  tiles have passed tile_request_ok.  declined (may be
+ * NULL): gets the pairs the anchor search declined when that is why the call fails. */
+int tile_server_run(osmt_tile_server* s, const osmt_tile_coord* tiles, size_t n, uint32_t scale, const osmt_area_anchor* anchors, size_t n_anchors,
+                    uint8_t* out_png, size_t out_capacity, uint64_t* out_off, std::vector<osmt_area_anchor>* declined) {
+    osmt_ctx* ctx = s->ctx;
+    std::vector<osmt_query_tile> q(n);
+    for (size_t t = 0; t < n; ++t) {
+        osmt_query_tile& o = q[t];
+        memset(&o, 0, sizeof o);
+        o.x = tiles[t].x, o.y = tiles[t].y, o.zoom = (uint8_t)tiles[t].zoom;
+        o.has_canvas = s->d.has_canvas ? 1 : 0;
+        if (o.has_canvas) memcpy(o.canvas_rgb, s->d.canvas_rgb, 3);
+    }
+    osmt_tile_batch b;
+    memset(&b, 0, sizeof b);
+    b.tiles = q.data(), b.n_tiles = n;
+    b.geodata_id = s->d.geodata_id, b.scale = scale, b.use_caps_for_dashes = s->d.use_caps_for_dashes;
+    memcpy(b.bindings_of_zoom, s->d.bindings_of_zoom, sizeof b.bindings_of_zoom);
+    osmt_scene* sc = nullptr;
+    int rc = scene_build_tiles_body(ctx, &b, s->d.id_filter, &sc);
+    if (rc != OSMT_OK) return rc;
+    if (s->area_labels || s->node_labels)
+        rc = scene_build_tile_labels_all_body(ctx, sc, s->area_labels ? s->d.area_label_bindings_of_zoom : nullptr,
+                                              s->node_labels ? s->d.node_label_bindings_of_zoom : nullptr, anchors, n_anchors);
+    if (rc == OSMT_OK) rc = osmt_render_scene_png(ctx, sc, out_png, out_capacity, out_off);
+    if (rc == OSMT_OK) {
+        osmt_scene_free(sc);
+        return OSMT_OK;
+    }
+    const std::string why = osmt_last_error(); /* freeing a scene may report nothing, but it must not lose this */
+    if (declined && rc == OSMT_UNSUPPORTED) *declined = sc->h_al_declined;
+    osmt_scene_free(sc);
+    return fail(rc, "%s", why.c_str());
+}
+
+int tile_server_render_png_body(osmt_tile_server* s, const osmt_tile_coord* tiles, size_t n, uint32_t scale, const osmt_area_anchor* anchors,
+                                size_t n_anchors, uint8_t* out_png, size_t out_capacity, uint64_t* out_off) {
+    tl_declined.clear();
+    if (!s || !out_off || (n && !tiles) || (!out_png && out_capacity) || (n_anchors && !anchors)) return fail(OSMT_INVALID_ARG, "NULL argument");
+    const int rc = tile_request_ok(s, tiles, n, scale);
+    if (rc != OSMT_OK) return rc;
+    if (n == 0) {
+        out_off[0] = 0; /* no tiles, no files: no device is touched */
+        return OSMT_OK;
+    }
+    return tile_server_run(s, tiles, n, scale, anchors, n_anchors, out_png, out_capacity, out_off, &tl_declined);
+}
+
+}  // namespace
+
+/* ---- the per-request entry for tile coordinates ---- */
+struct tile_group {
+    osmt_ctx* ctx = nullptr;
+    void* stage = nullptr;
+    std::atomic<int> pending{0}; /* requesters that still have to copy their file out of `stage` */
+};
+
+struct tile_req {
+    osmt_tile_server* s = nullptr;
+    osmt_tile_coord tile{};
+    uint32_t scale = 1;
+    const osmt_area_anchor* anchors = nullptr;
+    size_t n_anchors = 0;
+    uint8_t* out = nullptr;
+    size_t cap = 0;
+    bool taken = false, done = false, ran = false; /* ran: rendered on its own (rc, len and declined are its verdict) */
+    int rc = OSMT_OK;
+    std::string err;
+    std::vector<osmt_area_anchor> declined; /* tile 0 in each: what its own run declined */
+    tile_group* grp = nullptr;              /* where the file is (NULL: already in `out`, or failed) */
+    const uint8_t* src = nullptr;
+    size_t len = 0; /* the file's size, also when it did not fit */
+};
+
+namespace {
+
+void tile_run_group(osmt_ctx* ctx, const std::vector<tile_req*>& reqs) {
+    auto run_alone = [&](tile_req* r) {
+        uint64_t off[2] = {0, 0};
+        r->rc = guarded([&] { return tile_server_run(r->s, &r->tile, 1, r->scale, r->anchors, r->n_anchors, r->out, r->cap, off, &r->declined); });
+        r->ran = true;
+        r->len = (size_t)off[1];
+        if (r->rc != OSMT_OK) r->err = osmt_last_error();
+    };
+    if (reqs.size() == 1) {
+        run_alone(reqs[0]);
+        return;
+    }
+    const size_t n = reqs.size(), W = (size_t)OSMT_TILE_SIZE * reqs[0]->scale, slot = osmt_png_device_bound((uint32_t)W, (uint32_t)W);
+    int rc = OSMT_OK;
+    void* stage = nullptr;
+    std::vector<uint64_t> off;
+    try {
+        /* the tiles concatenated; every requester's anchors re-based from tile 0 to its index: ascending by (tile, entity) already */
+        std::vector<osmt_tile_coord> tiles(n);
+        std::vector<osmt_area_anchor> anchors;
+        off.assign(n + 1, 0);
+        for (size_t i = 0; i < n; ++i) {
+            tiles[i] = reqs[i]->tile;
+            for (size_t k = 0; k < reqs[i]->n_anchors; ++k) {
+                osmt_area_anchor a = reqs[i]->anchors[k];
+                a.tile = (uint32_t)i;
+                anchors.push_back(a);
+            }
+        }
+        stage = stage_acquire(ctx, n * slot);
+        if (!stage)
+            rc = OSMT_OOM;
+        else
+            rc = guarded([&] {
+                return tile_server_run(reqs[0]->s, tiles.data(), n, reqs[0]->scale, anchors.data(), anchors.size(), (uint8_t*)stage, n * slot, off.data(), nullptr);
+            });
+    } catch (...) {
+        rc = OSMT_OOM;
+    }
+    tile_group* g = rc == OSMT_OK ? new (std::nothrow) tile_group() : nullptr;
+    if (!g) {
+        /* whatever went wrong (a member's anchors refused, a declined pair, no pinned memory): every member on its own, so that a
+         * bad request or a declined anchor fails alone and the others get their files */
+        if (stage) stage_release(ctx, stage);
+        for (tile_req* r : reqs) run_alone(r);
+        return;
+    }
+    g->ctx = ctx;
+    g->stage = stage;
+    g->pending.store((int)n);
+    for (size_t i = 0; i < n; ++i) {
+        reqs[i]->grp = g;
+        reqs[i]->src = (const uint8_t*)stage + off[i];
+        reqs[i]->len = (size_t)(off[i + 1] - off[i]);
+        reqs[i]->rc = OSMT_OK;
+    }
+}
+
+int worker_render_tile_png_body(osmt_worker* w, osmt_tile_server* s, const osmt_tile_coord* tile, uint32_t scale, const osmt_area_anchor* anchors,
+                                size_t n_anchors, uint8_t* out_png, size_t out_capacity, size_t* out_len) {
+    tl_declined.clear();
+    if (!w || !w->ctx || !s || !tile || !out_len || (!out_png && out_capacity) || (n_anchors && !anchors)) return fail(OSMT_INVALID_ARG, "NULL argument");
+    *out_len = 0;
+    if (s->ctx != w->ctx) return fail(OSMT_INVALID_ARG, "the tile server belongs to another context than the worker");
+    osmt_ctx* ctx = w->ctx;
+    int rc = tile_request_ok(s, tile, 1, scale); /* by the requesting thread: a bad request never joins a group */
+    if (rc != OSMT_OK) return rc;
+    for (size_t k = 0; k < n_anchors; ++k)
+        if (anchors[k].tile != 0u) return fail(OSMT_INVALID_ARG, "anchor %zu: tile %u (a request is one tile: tile 0)", k, anchors[k].tile);
+
+    tile_req me;
+    me.s = s, me.tile = *tile, me.scale = scale;
+    me.anchors = anchors, me.n_anchors = n_anchors;
+    me.out = out_png, me.cap = out_capacity;
+    std::vector<tile_req*> group;
+    group.reserve(CO_MAX_TILES);
+    {
+        std::unique_lock<std::mutex> lk(ctx->co_mu);
+        ctx->co_tile_queue.push_back(&me);
+        ++ctx->co_tile_stats[0];
+        for (;;) {
+            if (me.done) break;
+            if (!me.taken && ctx->co_in_flight < co_max_in_flight()) {
+                /* leader: the waiting requests of the server and scale at the HEAD of the queue, in arrival order, up to the first
+                 * request of another server or scale — that one is the next leader's, as in osmt_worker_render.  The leader's own
+                 * request may sit behind such a request: then it leads the group in front first and looks again.  Running other
+                 * threads' requests (the group, or its members alone) overwrites THIS thread's osmt_last_error and declined list in
+                 * between; both are set again from its own request on the way out (fail() and the swap below). */
+                const tile_req* r0 = ctx->co_tile_queue.front();
+                while (!ctx->co_tile_queue.empty() && group.size() < CO_MAX_TILES) {
+                    tile_req* r = ctx->co_tile_queue.front();
+                    if (r->s != r0->s || r->scale != r0->scale) break; /* the next leader's */
+                    r->taken = true;
+                    group.push_back(r);
+                    ctx->co_tile_queue.pop_front();
+                }
+                ++ctx->co_in_flight; /* shared with osmt_worker_render: both entries together keep the cap */
+                ++ctx->co_tile_stats[1];
+                if (group.size() > ctx->co_tile_stats[2]) ctx->co_tile_stats[2] = group.size();
+                lk.unlock();
+                /* whatever happens in there, the group's members are marked done and the slot is given back: followers wait on
+                 * co_cv with no timeout */
+                try {
+                    tile_run_group(ctx, group);
+                } catch (...) {
+                    for (tile_req* r : group)
+                        if (!r->grp && !r->ran) r->rc = OSMT_OOM;
+                }
+                lk.lock();
+                --ctx->co_in_flight;
+                for (tile_req* r : group) r->done = true;
+                group.clear();
+                ctx->co_cv.notify_all();
+                continue;
+            }
+            ctx->co_cv.wait(lk);
+        }
+    }
+    tl_declined.swap(me.declined); /* left for ITS thread, whoever led the group */
+    *out_len = me.len;
+    if (me.rc != OSMT_OK) return fail(me.rc, "%s", me.err.c_str());
+    if (me.grp) {
+        const bool fits = me.len <= out_capacity;
+        if (fits) memcpy(out_png, me.src, me.len);
+        tile_group* g = me.grp;
+        if (g->pending.fetch_sub(1) == 1) {
+            stage_release(g->ctx, g->stage);
+            delete g;
+        }
+        if (!fits) return fail(OSMT_INVALID_ARG, "out_capacity %zu < %zu bytes of PNG data", out_capacity, me.len);
+    }
+    return OSMT_OK;
+}
+
+}  // namespace
+
+int osmt_validate_tile_server(const osmt_tile_server_desc* d, osmt_ctx* ctx) {
+    return guarded([&] { return validate_tile_server(d, ctx); });
+}
+int osmt_tile_server_create(osmt_ctx* ctx, const osmt_tile_server_desc* d, osmt_tile_server** out) {
+    return guarded([&] {
+        if (!ctx || !out) return fail(OSMT_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        const int rc = validate_tile_server(d, ctx);
+        if (rc != OSMT_OK) return rc;
+        osmt_tile_server* s = new osmt_tile_server();
+        s->ctx = ctx;
+        s->d = *d;
+        s->area_labels = any_bound(d->area_label_bindings_of_zoom);
+        s->node_labels = any_bound(d->node_label_bindings_of_zoom);
+        ctx->refs.fetch_add(1); /* like a scene or a worker: the context outlives its servers */
+        *out = s;
+        return (int)OSMT_OK;
+    });
+}
+void osmt_tile_server_free(osmt_tile_server* s) {
+    if (!s) return;
+    osmt_ctx* ctx = s->ctx;
+    delete s;
+    if (ctx) ctx_release(ctx);
+}
+int osmt_tile_server_render_png(osmt_tile_server* s, const osmt_tile_coord* tiles, size_t n, uint32_t scale, const osmt_area_anchor* anchors,
+                                size_t n_anchors, uint8_t* out_png, size_t out_capacity, uint64_t* out_off) {
+    return guarded([&] { return tile_server_render_png_body(s, tiles, n, scale, anchors, n_anchors, out_png, out_capacity, out_off); });
+}
+int osmt_last_declined_anchors(osmt_area_anchor* out, size_t cap, size_t* n) {
+    return guarded([&] {
+        if (!n) return fail(OSMT_INVALID_ARG, "NULL argument");
+        *n = tl_declined.size();
+        if (!out) return (int)OSMT_OK;
+        if (cap < *n) return fail(OSMT_INVALID_ARG, "out holds %zu anchors, the last call declined %zu", cap, *n);
+        if (*n) memcpy(out, tl_declined.data(), *n * sizeof(osmt_area_anchor));
+        return (int)OSMT_OK;
+    });
+}
+int osmt_worker_render_tile_png(osmt_worker* w, osmt_tile_server* s, const osmt_tile_coord* tile, uint32_t scale, const osmt_area_anchor* anchors,
+                                size_t n_anchors, uint8_t* out_png, size_t out_capacity, size_t* out_len) {
+    return guarded([&] { return worker_render_tile_png_body(w, s, tile, scale, anchors, n_anchors, out_png, out_capacity, out_len); });
+}
+int osmt_worker_tile_stats(osmt_ctx* ctx, uint64_t stats[3]) {
+    return guarded([&] {
+        if (!ctx || !stats) return fail(OSMT_INVALID_ARG, "NULL argument");
+        std::lock_guard<std::mutex> lk(ctx->co_mu);
+        for (int k = 0; k < 3; ++k) stats[k] = ctx->co_tile_stats[k];
+        return (int)OSMT_OK;
+    });
 }
 
 static int hbm_copy_probe_body(osmt_ctx* ctx, size_t bytes, uint32_t iters, double* out_copy, double* out_read) {

@@ -508,6 +508,9 @@ struct osmt_tq_pass {
     const uint32_t* geo_mp_off;   /* osmt_geo_dev::mp_off: a multipolygon without polygons is dropped */
     const osmt_tq_bind_dev* bind; /* [OSMT_MAX_ZOOM + 1] the bindings of each zoom (zooms no tile has: never read) */
     const osmt_query_tile* q;     /* [n_tiles] */
+    /* the planes of a registered id filter (osmt_idfilter.hip), bit `id` of word id / 32; NULL: no filter.  A candidate whose bit
+     * is 0 counts nothing: the filter is the last drop, behind the repeats and the multipolygons without polygons */
+    const uint32_t *keep_way, *keep_mp;
     uint32_t n_tiles, n_items, n_ways, n_mps; /* the last three: totals, known once they have been read back */
     /* per tile */
     uint32_t* span_c0;   /* [n_tiles] first present column of the tile's rectangle */
@@ -542,6 +545,11 @@ hipError_t osmt_launch_tq_mark(const osmt_tq_pass& a, hipStream_t st);
 /* k_tq_emit: the styled areas */
 hipError_t osmt_launch_tq_emit(const osmt_tq_pass& a, hipStream_t st);
 
+/* ---- the id filter (osmt_idfilter.hip) -------------------------------------------------------------------------- */
+/* k_idf_plane: bit e of `plane` = gid[e] is in ids[0 .. n_ids) (ascending, unique); plane has ceil(n / 64) 64-bit words and every
+ * one of them is written; n == 0 launches nothing */
+hipError_t osmt_launch_idf_plane(const uint64_t* gid, uint32_t n, const uint64_t* ids, uint32_t n_ids, uint32_t* plane, hipStream_t st);
+
 /* ---- node labels of tile-built scenes (osmt_tilelabels.hip) ----------------------------------------------------- */
 /* The query half is the k_tq_* stages over the NODE pools: osmt_tq_pass::ix with way_off / ways = the node lists and
  * mp_off = an array of zeros (no second kind), so span, columns, gather and sort run unchanged. */
@@ -575,6 +583,7 @@ struct osmt_tl_pass {
     uint32_t scale;
     const uint32_t* t_base; /* [n_tiles + 1] candidates of the tiles in front (osmt_tq_pass::t_wbase) */
     const uint32_t* cand;   /* sorted per tile */
+    const uint32_t* keep_node; /* the node plane of a registered id filter, or NULL: no filter */
     uint32_t* lpos;         /* [n_cand + 1] labels of the candidate (0 for a repeat), then their exclusive scan */
     uint32_t* job_label_off; /* [n_tiles + 1] */
     ulonglong2* keys;       /* [n_labels] rank:32 | gid:64 | element position in the tile:32, sorted in place per tile */

@@ -6,8 +6,9 @@
  * the node pools.  The host twin, and the yardstick of the tests, is osmt::node_labels_of_tile (host/osmt_tilelabels.hpp).
  * gfx950 only.
  *
- *   k_tl_mark    one lane per sorted candidate: 0 for a repeat of its predecessor, else the number of bindings of the node
- *                under the tile's zoom.  A scan turns the counts into label positions.
+ *   k_tl_mark    one lane per sorted candidate: 0 for a repeat of its predecessor and for a node an id filter does not
+ *                list (reader.rs:95-99), else the number of bindings of the node under the tile's zoom.  A scan turns the
+ *                counts into label positions.
  *   k_tl_tiles   one lane per tile: job_label_off, the most labels of a tile, the first tile over OSMT_TILE_LABELS_MAX.
  *   k_tl_expand  one lane per candidate again: per (node, binding) a 16-byte key rank:32 | gid:64 | position in the tile:32
  *                and, by that position, the binding and the node.  The rank is the style's dense rank under (layer or 0,
@@ -57,7 +58,8 @@ __global__ __launch_bounds__(256) void k_tl_mark(osmt_tl_pass P) {
     if (p >= P.n_cand) return;
     const uint32_t t = owner_of(P.t_base, P.n_tiles, p);
     const uint32_t id = P.cand[p];
-    const bool first = p == P.t_base[t] || P.cand[p - 1u] != id;
+    bool first = p == P.t_base[t] || P.cand[p - 1u] != id;
+    if (P.keep_node && !((P.keep_node[id >> 5] >> (id & 31u)) & 1u)) first = false; /* filter_entities_by_ids; uniform: a kernel argument */
     const osmt_tl_bind_dev B = P.bind[P.q[t].zoom];
     P.lpos[p] = first ? B.node_off[id + 1u] - B.node_off[id] : 0u;
 }

@@ -18,8 +18,9 @@
  *                  along a slice, so loads and stores coalesce.  A tile's ways land in front of its multipolygons.
  *   k_tq_sort      one workgroup per (tile, kind): the one-direction bitonic network of k_styled_sort on 32-bit keys, in LDS up
  *                  to OSMT_QUERY_LDS_CANDIDATES ids and in place in device memory beyond.
- *   k_tq_mark      one lane per sorted candidate: 0 for a repeat of its predecessor and for a multipolygon without
- *                  polygons (reader.rs:86-93), else the number of styles bound to the entity under the tile's zoom.  A scan
+ *   k_tq_mark      one lane per sorted candidate: 0 for a repeat of its predecessor, for a multipolygon without
+ *                  polygons (reader.rs:86-93) and for an entity an id filter does not list (reader.rs:95-99), else the
+ *                  number of styles bound to the entity under the tile's zoom.  A scan
  *                  turns the counts into area positions.
  *   k_tq_tiles     one lane per tile: its osmt_styled_tile, tile_base, the most areas of a tile, the first tile over the limit.
  *   k_tq_emit      one lane per candidate again: its osmt_styled_area records, in binding order.
@@ -273,6 +274,8 @@ __device__ __forceinline__ void eval(const osmt_tq_pass& P, uint32_t p, slot& o)
     o.id = id;
     o.mp = k >= nw;
     o.counts = k == 0u || k == nw || P.cand[p - 1u] != id;
+    const uint32_t* keep = o.mp ? P.keep_mp : P.keep_way; /* both NULL or neither: kernel arguments, the test is uniform */
+    if (keep && !((keep[id >> 5] >> (id & 31u)) & 1u)) o.counts = false; /* filter_entities_by_ids (reader.rs:254-262) */
     if (o.mp) {
         if (P.geo_mp_off[id + 1u] == P.geo_mp_off[id]) o.counts = false;
         o.styles_off = B.mp_off[id];

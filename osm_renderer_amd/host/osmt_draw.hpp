@@ -147,10 +147,18 @@ class Context {
         check(osmt_register_label_bindings(ctx_, &desc, &id));
         return id;
     }
-    /* tile coordinates in, PNG files out (defined behind TileScene) */
+    /* the osm_ids filter of get_entities_in_tile_with_neighbors (reader.rs:60,95-99) as a registered set of global ids: any
+     * order, repeats allowed, an empty set keeps nothing.  Register the node index first if the scenes' nodes are labelled. */
+    uint32_t register_id_filter(uint32_t geodata_id, const std::vector<uint64_t>& osm_ids) {
+        uint32_t id = 0;
+        check(osmt_register_id_filter(ctx_, geodata_id, osm_ids.data(), osm_ids.size(), &id));
+        return id;
+    }
+    /* tile coordinates in, PNG files out (defined behind TileScene); id_filter: from register_id_filter, or OSMT_ID_FILTER_NONE */
     template <class HostAnchor>
     std::vector<std::vector<uint8_t>> render_tiles_png(const osmt_tile_batch& batch, const uint32_t* area_bindings_of_zoom,
-                                                       const uint32_t* node_bindings_of_zoom, HostAnchor host_anchor);
+                                                       const uint32_t* node_bindings_of_zoom, HostAnchor host_anchor,
+                                                       uint32_t id_filter = OSMT_ID_FILTER_NONE);
 
   private:
     osmt_ctx* ctx_ = nullptr;
@@ -199,6 +207,39 @@ class StyledScene {
     osmt_scene* scene_ = nullptr;
 };
 
+/* One round of the TOO_LARGE retry loop: the pairs a call declined (`more`) are computed on this thread by
+ * host_anchor(tile index, entity) -> osmt_label_position and merged into the anchors the next call hands in.  A declined pair
+ * was not listed: the two lists are disjoint and each ascending by (tile, entity). */
+template <class HostAnchor>
+inline void add_computed_anchors(std::vector<osmt_area_anchor>& anchors, std::vector<osmt_area_anchor>& more, HostAnchor& host_anchor) {
+    for (osmt_area_anchor& a : more) {
+        const osmt_label_position p = host_anchor(a.tile, a.entity);
+        a.x = p.x, a.y = p.y, a.status = p.status;
+    }
+    std::vector<osmt_area_anchor> merged(anchors.size() + more.size());
+    std::merge(anchors.begin(), anchors.end(), more.begin(), more.end(), merged.begin(), [](const osmt_area_anchor& a, const osmt_area_anchor& b) {
+        return a.tile < b.tile || (a.tile == b.tile && a.entity < b.entity);
+    });
+    anchors.swap(merged);
+}
+/* The loop itself for the tile-server calls, whose declined pairs are the calling thread's (osmt_last_declined_anchors):
+ * call(anchors) -> the C call's return code.  Returns how many anchors the host computed. */
+template <class Call, class HostAnchor>
+inline size_t retry_with_host_anchors(Call call, HostAnchor host_anchor) {
+    std::vector<osmt_area_anchor> anchors;
+    for (;;) {
+        const int rc = call(anchors);
+        if (rc == OSMT_OK) return anchors.size();
+        const std::string why = osmt_last_error();
+        size_t n = 0;
+        check(osmt_last_declined_anchors(nullptr, 0, &n));
+        if (rc != OSMT_UNSUPPORTED || n == 0) throw Error(rc, why);
+        std::vector<osmt_area_anchor> more(n);
+        check(osmt_last_declined_anchors(more.data(), n, &n));
+        add_computed_anchors(anchors, more, host_anchor);
+    }
+}
+
 /* The node labels a TileScene built on the GPU, as read back: label l reads chars[labels[l].seg_off .. + n_segs), tile t owns
  * labels [job_label_off[t], job_label_off[t + 1]). */
 struct TileLabels {
@@ -219,8 +260,10 @@ struct TileAreaLabels : TileLabels {
  * and assembled on the GPU, the caller's way and multipolygon labels are drawn in front of them (drawer.rs:229-261). */
 class TileScene {
   public:
-    TileScene(Context& ctx, const osmt_tile_batch& batch) : ctx_(&ctx), n_tiles_(batch.n_tiles), scale_(batch.scale) {
-        check(osmt_scene_build_tiles(ctx.raw(), &batch, &scene_));
+    /* id_filter: from Context::register_id_filter — only listed entities are drawn and labelled; OSMT_ID_FILTER_NONE: all */
+    TileScene(Context& ctx, const osmt_tile_batch& batch, uint32_t id_filter = OSMT_ID_FILTER_NONE)
+        : ctx_(&ctx), n_tiles_(batch.n_tiles), scale_(batch.scale) {
+        check(osmt_scene_build_tiles_filtered(ctx.raw(), &batch, id_filter, &scene_));
     }
     ~TileScene() { osmt_scene_free(scene_); }
     TileScene(const TileScene&) = delete;
@@ -247,16 +290,7 @@ class TileScene {
             if (rc != OSMT_UNSUPPORTED || n == 0) throw Error(rc, why);
             std::vector<osmt_area_anchor> more(n);
             check(osmt_scene_read_declined_anchors(ctx_->raw(), scene_, more.data(), n, &n));
-            for (osmt_area_anchor& a : more) {
-                const osmt_label_position p = host_anchor(a.tile, a.entity);
-                a.x = p.x, a.y = p.y, a.status = p.status;
-            }
-            /* a declined pair was not listed: the two lists are disjoint and each ascending */
-            std::vector<osmt_area_anchor> merged(anchors.size() + more.size());
-            std::merge(anchors.begin(), anchors.end(), more.begin(), more.end(), merged.begin(), [](const osmt_area_anchor& a, const osmt_area_anchor& b) {
-                return a.tile < b.tile || (a.tile == b.tile && a.entity < b.entity);
-            });
-            anchors.swap(merged);
+            add_computed_anchors(anchors, more, host_anchor);
         }
     }
     /* Drawer::draw_tile's tail for every tile of the scene (drawer.rs:48-57): the PNG files, written by the GPU — with whatever
@@ -296,11 +330,84 @@ class TileScene {
  * file i belongs to batch.tiles[i]. */
 template <class HostAnchor>
 inline std::vector<std::vector<uint8_t>> Context::render_tiles_png(const osmt_tile_batch& batch, const uint32_t* area_bindings_of_zoom,
-                                                                   const uint32_t* node_bindings_of_zoom, HostAnchor host_anchor) {
-    TileScene scene(*this, batch);
+                                                                   const uint32_t* node_bindings_of_zoom, HostAnchor host_anchor,
+                                                                   uint32_t id_filter) {
+    TileScene scene(*this, batch, id_filter);
     if (area_bindings_of_zoom || node_bindings_of_zoom) scene.build_all_labels(area_bindings_of_zoom, node_bindings_of_zoom, host_anchor);
     return scene.render_png();
 }
+
+/* What a server renders its requests with, stated once (osmt_tile_server): geodata, bindings per zoom, canvas, id filter.
+ * Immutable; one instance serves every thread. */
+class TileServer {
+  public:
+    TileServer(Context& ctx, const osmt_tile_server_desc& desc) { check(osmt_tile_server_create(ctx.raw(), &desc, &server_)); }
+    ~TileServer() { osmt_tile_server_free(server_); }
+    TileServer(const TileServer&) = delete;
+    TileServer& operator=(const TileServer&) = delete;
+    osmt_tile_server* raw() const { return server_; }
+    /* a description with no bindings, no filter and the canvas given: fill in the ids per zoom */
+    static osmt_tile_server_desc describe(uint32_t geodata_id, const std::optional<Color>& canvas = std::nullopt) {
+        osmt_tile_server_desc d{};
+        d.geodata_id = geodata_id, d.use_caps_for_dashes = 1, d.id_filter = OSMT_ID_FILTER_NONE;
+        if (canvas) d.has_canvas = 1, d.canvas_rgb[0] = canvas->r, d.canvas_rgb[1] = canvas->g, d.canvas_rgb[2] = canvas->b;
+        for (uint32_t z = 0; z <= OSMT_MAX_ZOOM; ++z)
+            d.bindings_of_zoom[z] = d.area_label_bindings_of_zoom[z] = d.node_label_bindings_of_zoom[z] = OSMT_BINDINGS_NONE;
+        return d;
+    }
+    /* Tiles in, files out (osmt_tile_server_render_png): file i belongs to tiles[i].  host_anchor(tile index, entity) computes
+     * the anchors the device declines, as in TileScene::build_all_labels; *on_host (may be NULL) gets their number. */
+    template <class HostAnchor>
+    std::vector<std::vector<uint8_t>> render_png(const std::vector<osmt_tile_coord>& tiles, uint32_t scale, HostAnchor host_anchor,
+                                                 size_t* on_host = nullptr) const {
+        const uint32_t dim = TILE_SIZE * scale;
+        std::vector<uint8_t> blob(tiles.size() * osmt_png_device_bound(dim, dim)); /* the worst case: the call cannot come back short */
+        std::vector<uint64_t> off(tiles.size() + 1, 0);
+        const size_t n = retry_with_host_anchors(
+            [&](const std::vector<osmt_area_anchor>& anchors) {
+                return osmt_tile_server_render_png(server_, tiles.data(), tiles.size(), scale, anchors.data(), anchors.size(), blob.data(), blob.size(),
+                                                   off.data());
+            },
+            host_anchor);
+        if (on_host) *on_host = n;
+        std::vector<std::vector<uint8_t>> files(tiles.size());
+        for (size_t i = 0; i < tiles.size(); ++i) files[i].assign(blob.begin() + (ptrdiff_t)off[i], blob.begin() + (ptrdiff_t)off[i + 1]);
+        return files;
+    }
+
+  private:
+    osmt_tile_server* server_ = nullptr;
+};
+
+/* The per-thread request handle of the reference's server loop (http_server.rs:50-83): concurrent render_tile_png calls of the
+ * workers of one context, for the same server and scale, share launches (osmt_worker_render_tile_png). */
+class Worker {
+  public:
+    explicit Worker(Context& ctx) { check(osmt_worker_create(ctx.raw(), &worker_)); }
+    ~Worker() { osmt_worker_destroy(worker_); }
+    Worker(const Worker&) = delete;
+    Worker& operator=(const Worker&) = delete;
+    osmt_worker* raw() const { return worker_; }
+    /* One tile, one file.  host_anchor(0, entity) computes the anchors the device declines for THIS tile. */
+    template <class HostAnchor>
+    std::vector<uint8_t> render_tile_png(const TileServer& server, const osmt_tile_coord& tile, uint32_t scale, HostAnchor host_anchor,
+                                         size_t* on_host = nullptr) {
+        const uint32_t dim = TILE_SIZE * scale;
+        std::vector<uint8_t> file(osmt_png_device_bound(dim, dim));
+        size_t len = 0;
+        const size_t n = retry_with_host_anchors(
+            [&](const std::vector<osmt_area_anchor>& anchors) {
+                return osmt_worker_render_tile_png(worker_, server.raw(), &tile, scale, anchors.data(), anchors.size(), file.data(), file.size(), &len);
+            },
+            host_anchor);
+        if (on_host) *on_host = n;
+        file.resize(len);
+        return file;
+    }
+
+  private:
+    osmt_worker* worker_ = nullptr;
+};
 
 struct Filler { /* fill.rs:11-14 */
     enum Kind { ColorFill, ImageFill } kind;

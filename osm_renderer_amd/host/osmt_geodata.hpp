@@ -31,6 +31,7 @@
 #include <stdexcept>
 #include <string>
 #include <string_view>
+#include <unordered_set>
 #include <utility>
 #include <vector>
 
@@ -215,9 +216,10 @@ class GeodataReader {
         }
     }
 
-    /* reader.rs:60-98 get_entities_in_tile_with_neighbors (without the osm_ids filter): the 3x3 neighbourhood,
-     * sorted, unique; multipolygons without polygons are dropped */
-    OsmEntityIds get_entities_in_tile_with_neighbors(uint8_t zoom, uint32_t x, uint32_t y) const {
+    /* reader.rs:60-98 get_entities_in_tile_with_neighbors: the 3x3 neighbourhood, sorted, unique; multipolygons without
+     * polygons are dropped; then, with osm_ids (:95-99), filter_entities_by_ids (:254-262) on each kind: an entity stays iff
+     * its global id is in the set.  nullptr is None: no filter; an empty set keeps nothing */
+    OsmEntityIds get_entities_in_tile_with_neighbors(uint8_t zoom, uint32_t x, uint32_t y, const std::unordered_set<uint64_t>* osm_ids = nullptr) const {
         OsmEntityIds ids;
         for (int dx = -1; dx <= 1; ++dx)
             for (int dy = -1; dy <= 1; ++dy)
@@ -232,6 +234,14 @@ class GeodataReader {
         ids.multipolygons.erase(std::remove_if(ids.multipolygons.begin(), ids.multipolygons.end(),
                                                [&](uint32_t m) { return multipolygon_polygon_ids(m).second == 0; }),
                                 ids.multipolygons.end());
+        if (osm_ids) {
+            auto keep = [&](std::vector<uint32_t>& v, auto global_id) {
+                v.erase(std::remove_if(v.begin(), v.end(), [&](uint32_t e) { return osm_ids->count(global_id(e)) == 0; }), v.end());
+            };
+            keep(ids.nodes, [&](uint32_t e) { return node_global_id(e); });
+            keep(ids.ways, [&](uint32_t e) { return way_global_id(e); });
+            keep(ids.multipolygons, [&](uint32_t e) { return multipolygon_global_id(e); });
+        }
         return ids;
     }
 

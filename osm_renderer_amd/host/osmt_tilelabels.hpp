@@ -123,11 +123,11 @@ struct NodeLabels {
  * Returns the number of labels appended. */
 template <class Project>
 size_t node_labels_of_tile(const GeodataReader& reader, uint8_t zoom, uint32_t x, uint32_t y, uint32_t scale, const std::vector<LabelStyle>& styles,
-                           const LabelBindings& bindings, Project project, NodeLabels& out) {
+                           const LabelBindings& bindings, Project project, NodeLabels& out, const std::unordered_set<uint64_t>* osm_ids = nullptr) {
     struct Bound : Style { /* one pushed element: the keys sort_styled reads, and what it carries */
         osmt_label_binding b;
     };
-    const OsmEntityIds ids = reader.get_entities_in_tile_with_neighbors(zoom, x, y);
+    const OsmEntityIds ids = reader.get_entities_in_tile_with_neighbors(zoom, x, y, osm_ids); /* osm_ids: the scene's id filter, nullptr: none */
     std::vector<Bound> bound;
     std::vector<uint32_t> node_of;
     for (uint32_t n : ids.nodes) {

@@ -89,9 +89,11 @@ class StyleBindings {
 
 /* What osmt_scene_build_tiles derives for tile (zoom, x, y): every way of get_entities_in_tile_with_neighbors in ascending
  * local id, then every multipolygon (those without polygons are dropped there), each repeated once per bound style in
- * binding order.  An entity without a bound style contributes nothing. */
-inline std::vector<osmt_styled_area> styled_areas_of_tile(const GeodataReader& reader, const StyleBindings& bindings, uint8_t zoom, uint32_t x, uint32_t y) {
-    const OsmEntityIds ids = reader.get_entities_in_tile_with_neighbors(zoom, x, y);
+ * binding order.  An entity without a bound style contributes nothing.  osm_ids: the filter of
+ * osmt_scene_build_tiles_filtered (nullptr: none), applied where the reference applies it: last, inside the query. */
+inline std::vector<osmt_styled_area> styled_areas_of_tile(const GeodataReader& reader, const StyleBindings& bindings, uint8_t zoom, uint32_t x, uint32_t y,
+                                                          const std::unordered_set<uint64_t>* osm_ids = nullptr) {
+    const OsmEntityIds ids = reader.get_entities_in_tile_with_neighbors(zoom, x, y, osm_ids);
     std::vector<osmt_styled_area> out;
     for (uint32_t w : ids.ways) {
         const auto st = bindings.way(w);

@@ -53,6 +53,9 @@ EXPORTS = [
     "osmt_validate_rules", "osmt_register_rules", "osmt_validate_rules_ex", "osmt_register_rules_ex", "osmt_cascade_classes", "osmt_cascade_free", "osmt_cascade_read", "osmt_cascade_register",
     "osmt_render_scene_host", "osmt_render_scene_png", "osmt_render_scene_png_begin", "osmt_scene_png_work_bytes",
     "osmt_render_scene_png_device", "osmt_debug_png_offsets",
+    "osmt_validate_id_filter", "osmt_register_id_filter", "osmt_read_id_filter", "osmt_scene_build_tiles_filtered",
+    "osmt_validate_tile_server", "osmt_tile_server_create", "osmt_tile_server_free", "osmt_tile_server_render_png",
+    "osmt_last_declined_anchors", "osmt_worker_render_tile_png", "osmt_worker_tile_stats",
 ]
 
 
@@ -235,6 +238,22 @@ def load():
         L.osmt_scene_png_work_bytes.restype = C.c_size_t
         L.osmt_render_scene_png_device.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
         L.osmt_debug_png_offsets.argtypes = [vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp]
+    if hasattr(L, "osmt_register_id_filter"):  # absent only from older variant builds loaded through OSMT_LIB
+        u64p, sz = C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)
+        L.osmt_validate_id_filter.argtypes = [u64p, C.c_size_t, C.c_uint32, vp]
+        L.osmt_register_id_filter.argtypes = [vp, C.c_uint32, u64p, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.osmt_read_id_filter.argtypes = [vp, C.c_uint32, vp, vp, vp, sz, sz]
+        L.osmt_scene_build_tiles_filtered.argtypes = [vp, C.POINTER(abi.TileBatch), C.c_uint32, C.POINTER(vp)]
+    if hasattr(L, "osmt_tile_server_create"):  # absent only from older variant builds loaded through OSMT_LIB
+        sz = C.POINTER(C.c_size_t)
+        L.osmt_validate_tile_server.argtypes = [C.POINTER(abi.TileServerDesc), vp]
+        L.osmt_tile_server_create.argtypes = [vp, C.POINTER(abi.TileServerDesc), C.POINTER(vp)]
+        L.osmt_tile_server_free.argtypes = [vp]
+        L.osmt_tile_server_free.restype = None
+        L.osmt_tile_server_render_png.argtypes = [vp, C.POINTER(abi.TileCoord), C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint64)]
+        L.osmt_last_declined_anchors.argtypes = [vp, C.c_size_t, sz]
+        L.osmt_worker_render_tile_png.argtypes = [vp, vp, C.POINTER(abi.TileCoord), C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, sz]
+        L.osmt_worker_tile_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

@@ -318,9 +318,105 @@ class Worker:
                                         out.ctypes.data_as(C.POINTER(C.c_uint8)), tight))
         return out
 
+    def render_tile_png(self, server, tile, scale=1, anchors=None, out=None):
+        """osmt_worker_render_tile_png: the PNG file (bytes) of one tile (zoom, x, y) of a TileServer; concurrent requests of
+        the same server and scale share a group.  anchors: labels.AREA_ANCHOR_DTYPE with tile == 0, for pairs an earlier
+        request declined (last_declined_anchors()).  out: a uint8 buffer of the caller's (default: the bound for the scale)."""
+        from .labels import AREA_ANCHOR_DTYPE
+
+        z, x, y = tile
+        t = abi.TileCoord(int(x), int(y), int(z))
+        n = 0
+        if anchors is not None:
+            anchors = np.ascontiguousarray(anchors, dtype=AREA_ANCHOR_DTYPE)
+            n = len(anchors)
+        if out is None:
+            out = np.empty(load().osmt_png_device_bound(256 * scale, 256 * scale), np.uint8)
+        got = C.c_size_t()
+        rc = load().osmt_worker_render_tile_png(self._h, server._h, C.byref(t), scale, C.c_void_p(anchors.ctypes.data) if n else None, n,
+                                                C.c_void_p(out.ctypes.data) if out.size else None, out.size, C.byref(got))
+        self.last_len = got.value  # the size needed, also when the buffer was too small
+        check(rc)
+        return out[: got.value].tobytes()
+
     def close(self):
         if getattr(self, "_h", None):
             load().osmt_worker_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def last_declined_anchors():
+    """osmt_last_declined_anchors: the (tile, entity) pairs the last tile-server call of THIS thread declined, as a
+    labels.AREA_ANCHOR_DTYPE array."""
+    from .labels import AREA_ANCHOR_DTYPE
+
+    L, n = load(), C.c_size_t()
+    check(L.osmt_last_declined_anchors(None, 0, C.byref(n)))
+    out = np.zeros(n.value, AREA_ANCHOR_DTYPE)
+    if n.value:
+        check(L.osmt_last_declined_anchors(C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+    return out
+
+
+class TileServer:
+    """osmt_tile_server: what a server renders its requests with, stated once.  bindings / area_label_bindings /
+    node_label_bindings: {zoom: id} (a zoom that is missing has none; an empty dict: no labels of that kind); id_filter: from
+    Context.register_id_filter or None; canvas: (r, g, b) or None."""
+
+    def __init__(self, ctx, geodata_id, bindings, area_label_bindings=None, node_label_bindings=None, id_filter=None, canvas=(241, 238, 232),
+                 use_caps_for_dashes=True):
+        self.ctx = ctx
+        self.desc = self.describe(geodata_id, bindings, area_label_bindings, node_label_bindings, id_filter, canvas, use_caps_for_dashes)
+        h = C.c_void_p()
+        check(load().osmt_tile_server_create(ctx._h, C.byref(self.desc), C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def describe(geodata_id, bindings, area_label_bindings=None, node_label_bindings=None, id_filter=None, canvas=(241, 238, 232), use_caps_for_dashes=True):
+        d = abi.TileServerDesc()
+        d.geodata_id, d.use_caps_for_dashes = int(geodata_id), int(bool(use_caps_for_dashes))
+        d.id_filter = abi.ID_FILTER_NONE if id_filter is None else int(id_filter)
+        if canvas is not None:
+            d.has_canvas = 1
+            d.canvas_rgb[0], d.canvas_rgb[1], d.canvas_rgb[2] = canvas
+        for arr, b in ((d.bindings_of_zoom, bindings), (d.area_label_bindings_of_zoom, area_label_bindings), (d.node_label_bindings_of_zoom, node_label_bindings)):
+            b = dict(b or {})
+            for z in range(abi.MAX_ZOOM + 1):
+                arr[z] = int(b.get(z, abi.BINDINGS_NONE))
+        return d
+
+    def render_png(self, tiles, scale=1, anchors=None, out=None, as_bytes=True):
+        """osmt_tile_server_render_png: the PNG files of tiles [(zoom, x, y)] — build (filtered or not), label, render, encode in
+        one call.  anchors: labels.AREA_ANCHOR_DTYPE for pairs an earlier call declined (last_declined_anchors()).  Returns the
+        files as a list of bytes, or with as_bytes=False (blob, offsets); `offsets` is kept on self.last_offsets either way."""
+        from .labels import AREA_ANCHOR_DTYPE
+
+        n = len(tiles)
+        t = (abi.TileCoord * max(n, 1))(*[abi.TileCoord(int(x), int(y), int(z)) for z, x, y in tiles])
+        na = 0
+        if anchors is not None:
+            anchors = np.ascontiguousarray(anchors, dtype=AREA_ANCHOR_DTYPE)
+            na = len(anchors)
+        if out is None:
+            out = np.empty(n * load().osmt_png_device_bound(256 * scale, 256 * scale), np.uint8)
+        off = (C.c_uint64 * (n + 1))()
+        rc = load().osmt_tile_server_render_png(self._h, t, n, scale, C.c_void_p(anchors.ctypes.data) if na else None, na,
+                                                C.c_void_p(out.ctypes.data) if out.size else None, out.size, off)
+        self.last_offsets = np.array(off[:], dtype=np.uint64)
+        check(rc)
+        if not as_bytes:
+            return out, self.last_offsets
+        return [out[int(off[i]) : int(off[i + 1])].tobytes() for i in range(n)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().osmt_tile_server_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -368,6 +464,16 @@ class Context:
 
     def worker(self):
         return Worker(self)
+
+    def tile_server(self, geodata_id, bindings, **kw):
+        return TileServer(self, geodata_id, bindings, **kw)
+
+    def worker_tile_stats(self):
+        """osmt_worker_tile_stats: (requests, groups run, tiles of the largest group) of Worker.render_tile_png since the context
+        was created"""
+        st = (C.c_uint64 * 3)()
+        check(load().osmt_worker_tile_stats(self._h, st))
+        return tuple(int(v) for v in st)
 
     def __init__(self, device=0):
         torch = _torch()
@@ -491,12 +597,37 @@ class Context:
         b = batch.as_batch()
         check(load().osmt_validate_tile_batch(C.byref(b), self._h))
 
-    def build_tiles(self, batch) -> Scene:
-        """osmt_scene_build_tiles: the scene of a styled.TileBatch — tile query, style lookup and display list on the GPU."""
+    def build_tiles(self, batch, id_filter=None) -> Scene:
+        """osmt_scene_build_tiles: the scene of a styled.TileBatch — tile query, style lookup and display list on the GPU.
+        id_filter: an id from register_id_filter (osmt_scene_build_tiles_filtered): only listed entities are drawn, and the
+        scene's label builds apply the same filter; None: no filter."""
         b = batch.as_batch()
         h = C.c_void_p()
-        check(load().osmt_scene_build_tiles(self._h, C.byref(b), C.byref(h)))
+        if id_filter is None:
+            check(load().osmt_scene_build_tiles(self._h, C.byref(b), C.byref(h)))
+        else:
+            check(load().osmt_scene_build_tiles_filtered(self._h, C.byref(b), int(id_filter), C.byref(h)))
         return Scene._built(self, h, batch.n_jobs, batch.scale, getattr(self, "_geodata_nodes", {}).get(batch.geodata_id))
+
+    # -- the osm_ids filter -----------------------------------------------------------
+    def register_id_filter(self, geodata_id, ids):
+        """osmt_register_id_filter: a set of global ids (any order, repeats allowed; empty: keeps nothing) as bit-planes over
+        the nodes, ways and multipolygons of a registered geodata file; returns the filter id for build_tiles."""
+        a = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        out = C.c_uint32()
+        check(load().osmt_register_id_filter(self._h, geodata_id, a.ctypes.data_as(C.POINTER(C.c_uint64)) if len(a) else None, len(a), C.byref(out)))
+        return out.value
+
+    def read_id_filter(self, filter_id):
+        """osmt_read_id_filter: the (way, multipolygon, node) bit-planes as uint32 arrays; entity e is bit e % 32 of word e // 32;
+        the node plane is empty if no node index was registered when the filter was."""
+        L, n = load(), (C.c_size_t * 3)()
+        check(L.osmt_read_id_filter(self._h, filter_id, None, None, None, None, n))
+        planes = [np.zeros(n[k], np.uint32) for k in range(3)]
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+        caps = (C.c_size_t * 3)(n[0], n[1], n[2])
+        check(L.osmt_read_id_filter(self._h, filter_id, ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), caps, n))
+        return tuple(planes)
 
     # -- node labels of tile-built scenes ---------------------------------------------
     def register_node_index(self, geodata_id, index):
