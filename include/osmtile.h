@@ -1385,7 +1385,17 @@ int osmt_cascade_register(osmt_ctx* ctx, osmt_cascade* cascade, osmt_match* matc
                           uint32_t label_bindings_of_zoom[OSMT_MAX_ZOOM + 1], uint32_t area_label_bindings_of_zoom[OSMT_MAX_ZOOM + 1]);
 
 /* ---- projection only (tile.rs:88-106 + point.rs:11-19) ------------------ */
-/* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32 */
+/* xy[i] = round(coords_to_xy_tile_relative(latlon[i], tile) * scale) as i32, latlon = n pairs (lat, lon) in degrees.
+ * The contract, as tests/test_gpu_projection_domain.py tests it against the bounded model of tests/_projection_model.py:
+ *   x  is identical to the reference's for every input: the longitude path is IEEE arithmetic alone.
+ *   y  passes through the device's tan and log, the reference's through its host's.  It is identical to the reference's
+ *      unless the real value of ry * scale lies within the derived bound of a round() tie (k + 1/2): with tan within 5 ulp
+ *      and log within 3 ulp of the correctly rounded value (the OpenCL full-profile bounds the device library conforms to)
+ *      that bound is at most 2.4e-7 px (zoom 18, scale 4; it halves with every zoom below).  Inside it the answer is one of
+ *      the two neighbouring integers.
+ *   Coordinates are NOT checked by this entry (the batch entries refuse what lies outside |lat| <= OSMT_MAX_ABS_LAT,
+ *   |lon| <= 180): a NaN gives 0, what does not fit an i32 saturates, as `f64 as i32` does.
+ * zoom > OSMT_MAX_ZOOM is refused with OSMT_INVALID_ARG; tile_x / tile_y are taken as they are. */
 int osmt_project(osmt_ctx* ctx, const double* latlon, size_t n, uint8_t zoom, uint32_t tile_x, uint32_t tile_y,
                  double scale, int32_t* xy);
 

@@ -968,8 +968,10 @@ int validate_coords_range(const osmt_batch* b, size_t lo, size_t hi) {
                 return fail(OSMT_UNSUPPORTED, "point %zu: |coordinate| > 2^28", i / 2);
     } else {
         /* The closed forms and the Bresenham state of the kernels need |pixel coordinate| <= 2^28 (osmt_geom.h); with
-         * zoom <= 18 and scale <= 4 that holds for every (lat, lon) of the Web-Mercator square.  Outside it (or for a
-         * NaN / infinity) Point::from_node saturates (point.rs:11-19) and the integer walks would overflow. */
+         * zoom <= 18 and scale <= 4 that holds for every (lat, lon) of the Web-Mercator square (|lat| <= 85.0511...).  The
+         * band up to OSMT_MAX_ABS_LAT admitted here lies 19 187 px outside it at zoom 18: up to scale 3 still within 2^28
+         * under every tile, at scale 4 up to 2^28 + 76 748 under a tile of the opposite edge.  Further out
+         * (or for a NaN / infinity) Point::from_node saturates (point.rs:11-19) and the integer walks would overflow. */
         const double* ll = b->coord_kind == OSMT_COORD_NODE_REF ? b->nodes : b->latlon;
         for (size_t i = lo; i < hi; ++i) {
             const double lat = ll[2 * i], lon = ll[2 * i + 1];
@@ -5689,6 +5691,8 @@ void osmt_host_free(osmt_ctx* ctx, void* p) {
 static int osmt_project_body(osmt_ctx* ctx, const double* latlon, size_t n, uint8_t zoom, uint32_t tx, uint32_t ty, double scale,
                  int32_t* xy) {
     if (!ctx || (n && (!latlon || !xy))) return fail(OSMT_INVALID_ARG, "NULL argument");
+    /* 1u << zoom is undefined from 32 and 256 * 2^zoom wraps to 0 at 24: refused as every other entry refuses it */
+    if (zoom > OSMT_MAX_ZOOM) return fail(OSMT_INVALID_ARG, "zoom %u > MAX_ZOOM (src/tile.rs:5)", zoom);
     if (n >= 0xFFFFFFFFull) return fail(OSMT_INVALID_ARG, "too many points");
     if (n == 0) return OSMT_OK;
     HIP_TRY(hipSetDevice(ctx->device));
