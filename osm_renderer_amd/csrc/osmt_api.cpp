@@ -3,45 +3,17 @@
  * of include/osmtile.h.  No CPU rendering path exists here on purpose: every entry point
  * either runs the HIP kernels or fails with an error code.
  */
-#include <hip/hip_runtime.h>
+#include "osmt_host.h"
 
-#include <algorithm>
-#include <chrono>
-#include <atomic>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <condition_variable>
-#include <deque>
-#include <functional>
-#include <map>
-#include <dlfcn.h>
-
-#include <memory>
-#include <mutex>
-#include <thread>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "../../include/osmtile.h"
-#include "osmt_cascade_tables.h" /* the tables of a rule set: osmt_cs_resolve */
-#include "osmt_geom.h"
-#include "osmt_internal.h"
-#include "osmt_pool_layout.h"
-#include "osmt_numparse.h" /* osmt_bytes_cmp: the key order of osmt_validate_tags */
-#include "osmt_utf8.h"     /* the byte a refused tag value stops the decoder at */
-#include "osmt_png_table.h" /* PNG_LMAX, PNG_BLOCK_HDR_BITS: the slot bound */
-#include "../host/osmt_idfilter.hpp"   /* osmt::id_filter_set: the sort and dedup of a registered id filter */
-#include "../host/osmt_textplacer.hpp" /* osmt::validate_text_labels */
-#include "../host/osmt_textshaper.hpp" /* osmt::validate_font, osmt::validate_string_labels */
+using namespace osmt_host;
 
 namespace {
 
-using osmt_host::pool_layout;
-
 thread_local std::string g_last_error;
+
+}  // namespace
+
+namespace osmt_host {
 
 int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -53,20 +25,9 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-/* No C++ exception may cross the C boundary (a std::bad_alloc from a host-side table, say): every entry point
- * runs its body through this. */
-template <class F>
-int guarded(F&& f) noexcept {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        return fail(OSMT_OOM, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(OSMT_HIP_ERROR, "internal error: %s", e.what());
-    } catch (...) {
-        return fail(OSMT_HIP_ERROR, "internal error");
-    }
-}
+}  // namespace osmt_host
+
+namespace {
 
 #define HIP_TRY(expr)                                                                            \
     do {                                                                                         \
@@ -82,287 +43,6 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 /* error reporting for the other translation units of the library */
 int osmt_fail_public(int code, const char* msg) { return fail(code, "%s", msg); }
-
-struct osmt_ctx {
-    int device = 0;
-    std::mutex mu; /* guards the image registry */
-    /* Device buffers of finished calls, kept for the next one: a per-request server loop uploads, renders and frees
-     * a scene per call, and hipMalloc / hipFree of a few hundred MB cost more than the kernels. */
-    struct cached_buf {
-        void* p;
-        size_t bytes;
-        bool used;
-        uint64_t tick; /* when it was last handed out: the idle buffers given back to the driver are the least recently used */
-    };
-    std::mutex cache_mu;
-    std::vector<cached_buf> cache;
-    uint64_t cache_tick = 0;
-    /* idle non-blocking streams: every host-buffer call runs on its own stream, so calls from the reference's N
-     * worker threads (http_server.rs:50-83) overlap on the GPU instead of queueing behind the NULL stream */
-    std::vector<hipStream_t> idle_streams;
-    hipStream_t poison_stream = nullptr; /* OSMT_POISON_ALLOC: the fills run on a stream of the highest priority (dev_poison) */
-    std::vector<cached_buf> host_cache; /* pinned staging buffers (one packed H2D copy per small call) */
-    std::vector<osmt_image_desc> images;
-    std::vector<double> image_pool_host; /* premultiplied f64 RGBA */
-    /* Device copy of the registry.  A registration followed by a render makes a NEW pair of buffers; the old pair
-     * moves to `image_graveyard` and lives until the context goes, so a kernel launched by another worker thread
-     * with the previous snapshot never reads freed memory (registrations are rare: once per icon at start-up). */
-    osmt_image_desc* d_images = nullptr;
-    double4* d_image_pool = nullptr;
-    uint32_t d_n_images = 0;
-    std::vector<void*> image_graveyard;
-    bool images_dirty = false;
-    /* the glyph table of osmt_register_glyphs (outlines of glyph-run labels), same snapshot rules as the icons: a
-     * registration followed by a use makes a new device pair, the old one joins image_graveyard */
-    std::vector<osmt_glyph_vertex> glyph_verts;
-    std::vector<uint32_t> glyph_voff{0u};
-    osmt_glyph_vertex* d_glyph_verts = nullptr;
-    uint32_t* d_glyph_voff = nullptr;
-    uint32_t d_n_glyphs = 0;
-    bool glyphs_dirty = false;
-    /* the fonts of osmt_register_font (string labels).  The host copies serve the validation (metrics, table sizes) and
-     * the upload; a font's tables get ONE device allocation at their first use and never move, so only the array of
-     * osmt_font_dev records is replaced when a font is appended — the old array joins image_graveyard, and a launch
-     * that holds it keeps reading valid records of valid tables */
-    struct font_host {
-        std::vector<osmt_cmap_entry> cmap;
-        std::vector<int32_t> advance;
-        std::vector<uint32_t> outline;
-        std::vector<osmt_kern_pair> kern;
-        osmt_font_desc view{}; /* over the vectors above */
-        void* d_pool = nullptr;
-        osmt_font_dev dev{};
-    };
-    std::vector<std::shared_ptr<font_host>> fonts;
-    osmt_font_dev* d_fonts = nullptr;
-    uint32_t d_n_fonts = 0;
-    bool fonts_dirty = false;
-    /* the geodata files of osmt_register_geodata (scenes built on the device): one device allocation per file, made at
-     * registration, that never moves and lives as long as the context — a built scene's node table points into it */
-    struct geodata_host {
-        size_t n_nodes = 0, n_ways = 0, n_mps = 0;
-        void* d_pool = nullptr;
-        osmt_geo_dev dev{};
-        /* its z18 tile index (osmt_register_tile_index): at most one, an allocation of its own under the same rules */
-        void* d_index = nullptr;
-        osmt_tq_index_dev ix{};
-        /* the node lists of that index and the nodes' global ids (osmt_register_node_index): at most one, same rules */
-        void* d_node_index = nullptr;
-        const uint32_t *d_node_off = nullptr, *d_node_refs = nullptr, *d_zero_off = nullptr; /* [ix.n_tiles + 1], pool, [ix.n_tiles + 1] zeros */
-        const uint64_t* d_node_gid = nullptr;
-        /* the Mercator factors of its nodes (osmt_register_node_mercator): at most one table, same rules */
-        const double2* d_factors = nullptr; /* [n_nodes] */
-        /* its tags (osmt_register_tags): at most one table, same rules */
-        void* d_tags = nullptr;
-        osmt_sm_tags_dev tags{};
-        size_t tags_string_bytes = 0, n_node_tags = 0, n_way_tags = 0;
-    };
-    std::vector<geodata_host> geodata;
-    /* the selector sets of osmt_register_selectors: append-only, one device allocation each that never moves */
-    struct selectors_host {
-        void* d_pool = nullptr;
-        osmt_sm_sels_dev dev{};
-        std::shared_ptr<const std::vector<uint8_t>> zooms; /* [n_sels][2] the zooms a selector admits, inclusive: for the rule sets */
-    };
-    std::vector<selectors_host> selectors;
-    /* the rule sets of osmt_register_rules, under the same rules */
-    struct rules_host {
-        void* d_pool = nullptr;
-        osmt_cs_rules_dev dev{};
-        uint32_t selectors_id = 0;
-        std::shared_ptr<const std::vector<uint32_t>> key_off; /* the pooled `text` strings */
-        std::shared_ptr<const std::vector<uint8_t>> key_bytes;
-    };
-    std::vector<rules_host> rules;
-    uint32_t match_hash_bits = 32; /* osmt_debug_match_hash_bits */
-    /* the tables of osmt_register_style_bindings: append-only, one device allocation each that never moves, so a build
-     * that holds a table's pointers is not disturbed by a later registration */
-    struct bindings_host {
-        uint32_t geodata_id = 0;
-        uint8_t zoom_lo = 0, zoom_hi = 0;
-        void* d_pool = nullptr;
-        osmt_tq_bind_dev dev{};
-    };
-    std::vector<bindings_host> bindings;
-    /* the tables of osmt_register_label_bindings, under the same rules */
-    struct label_bindings_host {
-        uint32_t geodata_id = 0;
-        uint8_t zoom_lo = 0, zoom_hi = 0;
-        void* d_pool = nullptr;
-        osmt_tl_bind_dev dev{};
-        size_t n_nodes = 0, n_bindings = 0, n_texts = 0, n_chars = 0; /* osmt_read_label_bindings */
-    };
-    std::vector<label_bindings_host> label_bindings;
-    /* the tables of osmt_register_area_label_bindings, under the same rules */
-    struct area_label_bindings_host {
-        uint32_t geodata_id = 0;
-        uint8_t zoom_lo = 0, zoom_hi = 0;
-        void* d_pool = nullptr;
-        osmt_al_bind_dev dev{};
-        size_t n_ways = 0, n_mps = 0, n_way_bindings = 0, n_mp_bindings = 0, n_texts = 0, n_chars = 0; /* osmt_read_area_label_bindings */
-    };
-    std::vector<area_label_bindings_host> area_label_bindings;
-    /* the id filters of osmt_register_id_filter, under the same rules: the sorted set and the three planes in one allocation */
-    struct id_filter_host {
-        uint32_t geodata_id = 0;
-        bool on = false; /* in a scene: it was built with this filter */
-        void* d_pool = nullptr;
-        const uint32_t *way = nullptr, *mp = nullptr, *node = nullptr; /* node: NULL without a node plane */
-        size_t n_way_words = 0, n_mp_words = 0, n_node_words = 0;      /* 32-bit words */
-    };
-    std::vector<id_filter_host> id_filters;
-    /* the label styles of osmt_register_label_styles: records and ranks, replaced like the style table when it has grown */
-    std::vector<osmt_label_style_rec> label_styles;
-    osmt_label_style_rec* d_label_styles = nullptr;
-    uint32_t* d_label_rank = nullptr;
-    uint32_t d_n_label_styles = 0;
-    bool label_styles_dirty = false;
-    /* the styles of osmt_register_styles, same snapshot rules as the glyph table: a registration followed by a build makes
-     * a new device triple (records, ranks, dash pool), the old one joins image_graveyard */
-    std::vector<osmt_style_rec> styles;
-    std::vector<double> style_dashes;
-    osmt_style_rec* d_styles = nullptr;
-    uint32_t* d_style_rank = nullptr;
-    double* d_style_dashes = nullptr;
-    uint32_t d_n_styles = 0;
-    bool styles_dirty = false;
-    /* one reference for the handle returned by osmt_create + one per live scene: osmt_destroy on a context that still
-     * has scenes only drops the handle's reference, the last osmt_scene_free tears the context down */
-    std::atomic<int> refs{1};
-    /* RCCL communicator of the tile-count reduction (osmt_comm_init_*): ncclComm_t, rank and size */
-    void* comm = nullptr;
-    uint32_t comm_rank = 0, comm_size = 0;
-    unsigned long long* d_count = nullptr; /* device words of the reductions: [0], [1] blocking call, [2], [3] enqueued one */
-    /* One pinned, device-visible word per live scene: a pre-pass kernel whose arena reservation does not fit stores a code
-     * there (osmt_prepass_args.err) and the host reads it behind the synchronisation it does anyway — an internal error
-     * surfaces as OSMT_HIP_ERROR instead of blank tiles, and costs no copy and no extra wait. */
-    uint32_t* err_page = nullptr;
-    std::vector<uint16_t> err_free;
-    /* What the pre-pass arenas of recent big uploads needed per fill op / per virtual stroke segment, by scale: the next
-     * big upload of a host-buffer call takes its arenas from these densities (+ 25 %) instead of asking the device with a
-     * counting run of the pre-pass and a round trip; see scene_size_arenas (guarded by cache_mu). */
-    struct arena_density {
-        double groups_per_fill = 0.0, recs_per_vseg = 0.0;
-        uint32_t uploads = 0;
-    } density[OSMT_MAX_SCALE + 1];
-    /* The gathering point of the per-request entry (osmt_worker_render): requests of concurrent worker threads wait here
-     * and are rendered together, see the "coalescing worker" section. */
-    std::mutex co_mu;
-    std::condition_variable co_cv;
-    std::deque<struct coalesce_req*> co_queue;
-    int co_in_flight = 0;
-    /* the same for osmt_worker_render_tile_png: its own queue, the SAME count of groups in flight, and osmt_worker_tile_stats */
-    std::deque<struct tile_req*> co_tile_queue;
-    uint64_t co_tile_stats[3] = {0, 0, 0}; /* requests, groups run, tiles of the largest group */
-    /* osmt_label_positions_stats: requests / left the LDS tier / answered TOO_LARGE of the last completed call (cache_mu) */
-    uint64_t pl_stats[3] = {0, 0, 0};
-};
-
-struct osmt_scene {
-    osmt_ctx* ctx = nullptr;
-    uint32_t n_jobs = 0, n_ops = 0, n_rings = 0, n_pts = 0, n_dashes = 0, n_strokes = 0;
-    uint32_t scale = 1, coord_kind = 0, n_blk = 0;
-    char* d_base = nullptr; /* one allocation, carved below */
-    char* d_front = nullptr; /* big uploads: the arrays the host provides, in an allocation of their own (copied by a helper thread while the tables are built) */
-    size_t bytes = 0;
-    osmt_tile_job* d_jobs = nullptr;
-    osmt_op* d_ops = nullptr;
-    osmt_ring* d_rings = nullptr;
-    double* d_latlon = nullptr;     /* per point, or the node table (OSMT_COORD_NODE_REF) */
-    uint32_t* d_node_refs = nullptr;
-    int32_t* d_pts = nullptr;
-    double* d_dashes = nullptr;
-    uint32_t* d_pt_job = nullptr;
-    uint32_t* d_op_aux = nullptr;
-    osmt_opinfo* d_info = nullptr;
-    osmt_stroke_aux* d_aux = nullptr;
-    osmt_dash_seg* d_dseg = nullptr;
-    uint32_t* d_submask = nullptr;
-    uint32_t* d_op_blk = nullptr;
-    uint32_t* d_op_vseg = nullptr; /* op -> its first virtual segment (stroke ops with segments) */
-    osmt_blk_bbox* d_blk = nullptr;
-    uint32_t* d_op_job = nullptr;
-    osmt_vseg* d_vseg = nullptr; /* per virtual segment: end points, traveled, length, slot offset, op (k_opinfo -> k_prebin) */
-    unsigned long long* d_cursors = nullptr; /* 4 words; the per-sub-tile list counts follow (one memset) */
-    uint32_t* d_cnt = nullptr;
-    uint2* d_hdr = nullptr;
-    osmt_ent* d_ent = nullptr;
-    unsigned long long ent_cap = 0;
-    uint32_t n_fill_ops = 0;
-    uint32_t n_vsegs = 0;
-    /* the two arenas of the pre-pass (fill coverage words, stroke records + keys): one allocation, sized at upload */
-    char* d_arena = nullptr;
-    uint32_t* d_fmask = nullptr;
-    osmt_srec* d_srec = nullptr;
-    uint2* d_skey = nullptr;
-    unsigned long long fmask_cap = 0, srec_cap = 0; /* 64-byte groups / records */
-    /* the fill slots of k_prebin (osmt_fill_slots.h), in the same allocation */
-    osmt_fill_slot* d_slots = nullptr;
-    unsigned long long slot_cap = 0;
-    uint32_t n_fill_pass = 0; /* passes of four slots, where the sizing run counted them; 0: not known (worst-case or guessed sizes) */
-    /* host-side tables whose upload may still be in flight on the call's stream */
-    std::vector<uint32_t> h_pt_job, h_op_aux, h_op_blk, h_op_vseg, h_op_job, h_lab_wide;
-    std::vector<osmt_label_band> h_lab_bands;
-    std::vector<osmt_labelinfo> h_lab_info;
-    hipStream_t own_stream = nullptr; /* internal per-call scene: everything about it happens on this stream */
-    /* public scenes: one event per stream the scene was rendered on, recorded behind the last launch that reads it.
-     * osmt_scene_free / set_labels / read_* wait for THESE events only — never for the device — so worker threads
-     * with their own scenes and streams do not stall each other (http_server.rs:50-83: independent workers). */
-    std::mutex use_mu;
-    std::vector<std::pair<hipStream_t, hipEvent_t>> last_use;
-    void* h_stage = nullptr;          /* pinned staging of a packed upload, returned to the pool when the scene goes */
-    uint32_t* h_err = nullptr;        /* the scene's word of osmt_ctx::err_page (NULL: none left, errors stay unreported) */
-    uint32_t max_job_ops = 0;         /* most ops of any of the scene's tiles: at most OSMT_FOLD_MAX_OPS = no list kernel */
-    bool arena_guess = false;         /* the arenas were sized from osmt_ctx::density, not by the device: an overflow is a miss, not a bug */
-    /* label pass (osmt_scene_set_labels): its own allocation */
-    uint32_t n_labels = 0, n_label_segs = 0;
-    char* d_lab_base = nullptr;
-    osmt_labelinfo* d_lab = nullptr;
-    uint32_t* d_job_label_off = nullptr;
-    double* d_lab_segs = nullptr;
-    double* d_lab_a = nullptr;
-    double* d_lab_s_wide = nullptr;
-    uint32_t* d_lab_wide = nullptr;
-    osmt_label_band* d_lab_bands = nullptr;
-    unsigned long long* d_lab_bits = nullptr;
-    uint32_t n_lab_bands = 0;
-    uint32_t n_lab_wide = 0;
-    bool lab_cover_valid = false; /* a render has written the coverage planes of the attached labels (osmt_scene_read_label_cover) */
-    uint32_t* d_lab_bitmap = nullptr;
-    uint8_t* d_lab_ok = nullptr;
-    uint32_t* d_lab_err = nullptr;
-    osmt_tile_label* d_tile_labels = nullptr;
-    uint32_t* d_tile_label_cnt = nullptr;
-    /* text-run labels (osmt_scene_set_text_labels): the glyph instances k_text_place wrote, kept for
-     * osmt_scene_read_glyph_instances; an allocation of its own, gone with the next set call */
-    osmt_glyph_instance* d_text_inst = nullptr;
-    uint32_t n_text_inst = 0;
-    /* string labels (osmt_scene_set_string_labels): the records k_text_shape wrote and k_text_place read, kept for
-     * osmt_scene_read_text_glyphs under the same rules */
-    osmt_text_glyph* d_text_glyphs = nullptr;
-    uint32_t n_text_glyphs = 0;
-    /* a scene of osmt_scene_build_tiles: the styled batch the device derived, kept for osmt_scene_read_styled_areas */
-    char* d_tq = nullptr;           /* tiles + tile_base */
-    char* d_tq_areas_buf = nullptr; /* the areas */
-    const osmt_styled_tile* d_tq_tiles = nullptr;
-    const osmt_styled_area* d_tq_areas = nullptr;
-    size_t n_tq_areas = 0;
-    std::vector<osmt_query_tile> h_tq_tiles; /* the tiles it was built from, for osmt_scene_build_tile_labels */
-    uint32_t tq_geodata_id = 0;
-    osmt_ctx::id_filter_host tq_filter; /* the snapshot of the filter it was built with (osmt_scene_build_tiles_filtered); `on` false: none */
-    /* the node batch the last osmt_scene_build_tile_labels read back (osmt_scene_read_tile_labels) */
-    std::vector<osmt_label> h_tl_labels;
-    std::vector<osmt_string_run> h_tl_runs;
-    std::vector<uint32_t> h_tl_chars, h_tl_off;
-    /* the area batch the last osmt_scene_build_tile_labels_all read back (osmt_scene_read_tile_area_labels), and the pairs
-     * its anchor search declined (osmt_scene_read_declined_anchors) */
-    std::vector<osmt_label> h_al_labels;
-    std::vector<osmt_string_run> h_al_runs;
-    std::vector<uint32_t> h_al_chars, h_al_off;
-    std::vector<int32_t> h_al_pts;
-    std::vector<double> h_al_sincos;
-    std::vector<osmt_area_anchor> h_al_declined;
-};
 
 namespace {
 
@@ -514,6 +194,10 @@ void err_slot_release(osmt_ctx* ctx, uint32_t* w) {
     ctx->err_free.push_back((uint16_t)(w - ctx->err_page));
 }
 
+}  // namespace
+
+namespace osmt_host {
+
 void* stage_acquire(osmt_ctx* ctx, size_t bytes) {
     bytes = align_up(bytes ? bytes : 1, (size_t)64 << 10);
     {
@@ -547,6 +231,10 @@ void stage_release(osmt_ctx* ctx, void* p) {
     for (auto& c : ctx->host_cache)
         if (c.p == p) c.used = false;
 }
+
+}  // namespace osmt_host
+
+namespace {
 
 void dev_free(osmt_ctx* ctx, void* p) {
     if (!p) return;
@@ -848,9 +536,17 @@ void ctx_teardown(osmt_ctx* ctx) {
     delete ctx;
 }
 
+}  // namespace
+
+namespace osmt_host {
+
 void ctx_release(osmt_ctx* ctx) {
     if (ctx->refs.fetch_sub(1) == 1) ctx_teardown(ctx);
 }
+
+}  // namespace osmt_host
+
+namespace {
 
 /* The wait at the end of a small request: the work behind it is ~100 us of kernels, and a thread that sleeps in the driver
  * until the completion interrupt wakes it adds a noticeable share of that on top.  Poll the stream for a bounded time
@@ -1081,14 +777,22 @@ int validate_nodes(const osmt_batch* b, size_t lo, size_t hi) {
     return b->coord_kind == OSMT_COORD_NODE_REF ? validate_coords_range(b, lo, hi) : OSMT_OK;
 }
 
+}  // namespace
+
+namespace osmt_host {
+
 /* the whole batch on the calling thread; with_coords = false: the caller scans the coordinates itself (big uploads do it
  * on helper threads, validate_coords_range over the whole pool) */
-int validate_batch(const osmt_batch* b, bool with_coords = true) {
+int validate_batch(const osmt_batch* b, bool with_coords) {
     int rc = validate_batch_global(b);
     for (size_t j = 0; rc == OSMT_OK && j < b->n_jobs; ++j) rc = validate_job(b, j, with_coords);
     if (rc == OSMT_OK && with_coords) rc = validate_nodes(b, 0, b->n_nodes);
     return rc;
 }
+
+}  // namespace osmt_host
+
+namespace {
 
 /* Arguments of stage 2 (k_opinfo -> k_fill_rows -> k_stroke_bin); sizing: only the arena cursors are produced. */
 osmt_prepass_args prepass_args(const osmt_scene* sc, bool sizing) {
@@ -1888,11 +1592,13 @@ void osmt_scene_free(osmt_scene* s) {
 namespace {
 
 /* offs: count + 1 entries from 0 to `total`, never decreasing */
-int check_offsets(const char* what, const uint32_t* offs, size_t count, size_t total) {
-    if (offs[0] != 0u) return fail(OSMT_INVALID_ARG, "geodata: %s[0] is %u, not 0", what, offs[0]);
+int check_offsets_of(const char* who, const char* what, const uint32_t* offs, size_t count, size_t total) {
+    if (offs[0] != 0u) return fail(OSMT_INVALID_ARG, "%s: %s[0] is %u, not 0", who, what, offs[0]);
     for (size_t i = 0; i < count; ++i)
-        if (offs[i + 1] < offs[i]) return fail(OSMT_INVALID_ARG, "geodata: %s[%zu] = %u is less than the entry before it (%u)", what, i + 1, offs[i + 1], offs[i]);
-    if ((size_t)offs[count] != total) return fail(OSMT_INVALID_ARG, "geodata: %s[%zu] = %u does not end at the %zu entries it indexes", what, count, offs[count], total);
+        if (offs[i + 1] < offs[i])
+            return fail(OSMT_INVALID_ARG, "%s: %s[%zu] = %u is less than the entry before it (%u)", who, what, i + 1, offs[i + 1], offs[i]);
+    if ((size_t)offs[count] != total)
+        return fail(OSMT_INVALID_ARG, "%s: %s[%zu] = %u does not end at the %zu entries it indexes", who, what, count, offs[count], total);
     return OSMT_OK;
 }
 
@@ -1905,9 +1611,9 @@ int validate_geodata(const osmt_geodata_desc* g) {
     if (g->n_nodes >= 0xFFFFFFFFull || g->n_ways >= 0x7FFFFFFFull || g->n_multipolygons >= 0x7FFFFFFFull || g->n_polygons >= 0xFFFFFFFFull ||
         g->n_multipolygon_polygons >= 0xFFFFFFFFull || (unsigned long long)g->n_way_nodes + g->n_polygon_nodes >= 0xFFFFFFFFull)
         return fail(OSMT_UNSUPPORTED, "geodata: too large for 32-bit indices (ways and multipolygons: 31 bits)");
-    int rc = check_offsets("way_node_off", g->way_node_off, g->n_ways, g->n_way_nodes);
-    if (rc == OSMT_OK) rc = check_offsets("polygon_node_off", g->polygon_node_off, g->n_polygons, g->n_polygon_nodes);
-    if (rc == OSMT_OK) rc = check_offsets("multipolygon_polygon_off", g->multipolygon_polygon_off, g->n_multipolygons, g->n_multipolygon_polygons);
+    int rc = check_offsets_of("geodata", "way_node_off", g->way_node_off, g->n_ways, g->n_way_nodes);
+    if (rc == OSMT_OK) rc = check_offsets_of("geodata", "polygon_node_off", g->polygon_node_off, g->n_polygons, g->n_polygon_nodes);
+    if (rc == OSMT_OK) rc = check_offsets_of("geodata", "multipolygon_polygon_off", g->multipolygon_polygon_off, g->n_multipolygons, g->n_multipolygon_polygons);
     if (rc != OSMT_OK) return rc;
     for (size_t i = 0; i < g->n_way_nodes; ++i)
         if (g->way_nodes[i] >= g->n_nodes) return fail(OSMT_INVALID_ARG, "geodata: way_nodes[%zu] = %u is not a node (%zu nodes)", i, g->way_nodes[i], g->n_nodes);
@@ -2342,17 +2048,6 @@ int scene_build_styled_body(osmt_ctx* ctx, const osmt_styled_batch* b, osmt_scen
 }
 
 /* ---- scenes built from tile coordinates (include/osmtile.h, csrc/osmt_tilequery.hip) ---------------------------------- */
-/* offs: count + 1 entries from 0 to `total`, never decreasing */
-int check_offsets_of(const char* who, const char* what, const uint32_t* offs, size_t count, size_t total) {
-    if (offs[0] != 0u) return fail(OSMT_INVALID_ARG, "%s: %s[0] is %u, not 0", who, what, offs[0]);
-    for (size_t i = 0; i < count; ++i)
-        if (offs[i + 1] < offs[i])
-            return fail(OSMT_INVALID_ARG, "%s: %s[%zu] = %u is less than the entry before it (%u)", who, what, i + 1, offs[i + 1], offs[i]);
-    if ((size_t)offs[count] != total)
-        return fail(OSMT_INVALID_ARG, "%s: %s[%zu] = %u does not end at the %zu entries it indexes", who, what, count, offs[count], total);
-    return OSMT_OK;
-}
-
 int validate_tile_index(const osmt_tile_index_desc* x, size_t n_ways, size_t n_mps) {
     if (!x) return fail(OSMT_INVALID_ARG, "tile index is NULL");
     if ((x->n_tiles && !x->tile_xy) || !x->way_off || (x->n_way_refs && !x->ways) || !x->multipolygon_off || (x->n_multipolygon_refs && !x->multipolygons))
@@ -2532,6 +2227,10 @@ int validate_tile_batch(const osmt_tile_batch* b, osmt_ctx* ctx, osmt_tq_bind_de
     }
     return OSMT_OK;
 }
+
+}  // namespace
+
+namespace osmt_host {
 
 int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, uint32_t filter_id, osmt_scene** out_scene) {
     if (!ctx || !out_scene) return fail(OSMT_INVALID_ARG, "NULL argument");
@@ -2733,6 +2432,10 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, uint32_t fil
     }
     return OSMT_OK;
 }
+
+}  // namespace osmt_host
+
+namespace {
 
 int scene_read_styled_areas_body(osmt_ctx* ctx, osmt_scene* sc, osmt_styled_tile* tiles, osmt_styled_area* areas, size_t areas_cap, size_t* n_areas) {
     if (!ctx || !sc || !n_areas) return fail(OSMT_INVALID_ARG, "NULL argument");
@@ -4867,7 +4570,9 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     return OSMT_OK;
 }
 
-static int scene_build_tile_labels_all_body(osmt_ctx* ctx, osmt_scene* sc, const uint32_t* area_of_zoom, const uint32_t* node_of_zoom,
+namespace osmt_host {
+
+int scene_build_tile_labels_all_body(osmt_ctx* ctx, osmt_scene* sc, const uint32_t* area_of_zoom, const uint32_t* node_of_zoom,
                                             const osmt_area_anchor* anchors, size_t n_anchors) {
     if (!ctx || !sc || sc->ctx != ctx) return fail(OSMT_INVALID_ARG, "bad ctx/scene");
     if (!sc->d_tq) return fail(OSMT_INVALID_ARG, "the scene was not built by osmt_scene_build_tiles: it has no tiles to query");
@@ -4899,6 +4604,8 @@ static int scene_build_tile_labels_all_body(osmt_ctx* ctx, osmt_scene* sc, const
     sc->h_al_sincos.swap(ab.sincos);
     return OSMT_OK;
 }
+
+}  // namespace osmt_host
 
 static int scene_read_declined_anchors_body(osmt_ctx* ctx, osmt_scene* sc, osmt_area_anchor* out, size_t cap, size_t* n) {
     if (!ctx || !sc || sc->ctx != ctx || !n) return fail(OSMT_INVALID_ARG, "NULL argument");
@@ -5049,10 +4756,12 @@ static int osmt_render_batch_labels_once(osmt_ctx* ctx, const osmt_batch* batch,
                                          bool rgb, bool trusted, bool allow_guess, const osmt_glyph_label_batch* glabels,
                                          const osmt_text_label_batch* tlabels, const osmt_string_label_batch* slabels);
 
+namespace osmt_host {
+
 /* the host-buffer render: arenas guessed from the recent densities first; a miss renders again with exact sizing */
-static int osmt_render_batch_labels_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,
-                                         size_t stride, bool rgb = false, bool trusted = false, const osmt_glyph_label_batch* glabels = nullptr,
-                                         const osmt_text_label_batch* tlabels = nullptr, const osmt_string_label_batch* slabels = nullptr) {
+int osmt_render_batch_labels_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,
+                                         size_t stride, bool rgb, bool trusted, const osmt_glyph_label_batch* glabels,
+                                         const osmt_text_label_batch* tlabels, const osmt_string_label_batch* slabels) {
     g_arena_guess_missed = false;
     int rc = osmt_render_batch_labels_once(ctx, batch, labels, out_rgba, stride, rgb, trusted, true, glabels, tlabels, slabels);
     if (rc != OSMT_OK && g_arena_guess_missed) {
@@ -5061,6 +4770,8 @@ static int osmt_render_batch_labels_body(osmt_ctx* ctx, const osmt_batch* batch,
     }
     return rc;
 }
+
+}  // namespace osmt_host
 
 /* The back half of every host-buffer render, where the scene exists: shared by the batch forms (a per-call scene that lives
  * on `st`) and osmt_render_scene_host (a public scene, borrowed).  Takes one of three routes — zero-copy, the two-stream
@@ -6224,702 +5935,6 @@ int osmt_render_batch_multi(osmt_ctx* const* ctxs, uint32_t n, const osmt_batch*
 int osmt_render_batch_multi_ex(osmt_ctx* const* ctxs, uint32_t n, const osmt_batch* batch, const osmt_label_batch* labels, uint32_t flags,
                                uint8_t* out, size_t stride, uint64_t* out_count) {
     return guarded([&] { return render_batch_multi_body(ctxs, n, batch, labels, flags, out, stride, out_count); });
-}
-
-/* ---- the per-request entry: worker handles that gather concurrent one-tile requests -------------------------------
- * The reference's server hands ONE tile per request to each of available_parallelism() worker threads, every one with
- * its own TilePixels (src/http_server.rs:50-83,105-108,134-181).  Sixteen threads that each run the whole chain — five
- * pre-pass launches, a raster launch for 128 waves, a copy, a synchronisation — for one tile queue up behind each other
- * on the device (round 3: 17 k tiles/s, p99 9.6 ms from 16 workers).  The GPU renders 16 tiles in the time of one, so
- * the requests are gathered ("group commit"): a request that finds fewer than OSMT_WORKER_INFLIGHT groups on the
- * device becomes a leader at once and takes EVERY request that is waiting (up to 64 tiles) with it; requests that
- * arrive while the device is busy wait for the next leader.  No timer: a lone request never waits for company, and
- * the group size follows the load.  The leader merges the display lists (a valid batch: op ranges partition the merged
- * pool, every request was validated by its own thread), renders them with ONE launch sequence into pinned staging and
- * every requester copies its own tiles out in parallel.  A group of one skips all of that and is osmt_render_batch_rgb. */
-struct coalesce_group {
-    osmt_ctx* ctx = nullptr;
-    void* stage = nullptr;
-    std::atomic<int> pending{0}; /* requesters that still have to copy their tiles out of `stage` */
-};
-
-struct coalesce_req {
-    const osmt_batch* b = nullptr;
-    const osmt_label_batch* lb = nullptr;
-    uint8_t* out = nullptr;
-    size_t stride = 0;
-    bool taken = false, done = false, ran = false; /* ran: rendered on its own (rc is its verdict) */
-    int rc = OSMT_OK;
-    std::string err;
-    coalesce_group* grp = nullptr; /* where the pixels are (NULL: already in `out`, or failed) */
-    const uint8_t* src = nullptr;
-};
-
-struct osmt_worker {
-    osmt_ctx* ctx = nullptr;
-};
-
-namespace {
-
-constexpr size_t CO_MAX_TILES = 64;
-
-int co_max_in_flight() {
-    static const int v = [] {
-        const char* e = getenv("OSMT_WORKER_INFLIGHT");
-        /* 16 / 32 native threads, one-tile requests: 48 / 64 k tiles/s with 1, 45 / 72 k with 2, 35 / 53 k with 3, 28 / 49 k with 4,
-         * 20 / 37 k with 6 (profiles/r04_j_worker_inflight.txt): every group in flight is a host thread in the runtime, and
-         * they queue up behind each other's calls */
-        return e ? std::min(std::max(atoi(e), 1), 16) : 2;
-    }();
-    return v;
-}
-
-/* the display lists (and label lists) of several requests as ONE batch, in request order */
-struct merged_batch {
-    std::vector<osmt_tile_job> jobs;
-    std::vector<osmt_op> ops;
-    std::vector<osmt_ring> rings;
-    std::vector<double> latlon; /* per point, or the concatenated node tables */
-    std::vector<int32_t> points;
-    std::vector<uint32_t> node_refs;
-    std::vector<double> dashes;
-    std::vector<osmt_label> labels;
-    std::vector<uint32_t> job_label_off;
-    std::vector<double> segs;
-    osmt_batch b;
-    osmt_label_batch lb;
-    bool has_labels = false;
-};
-
-void merge_requests(const std::vector<coalesce_req*>& reqs, merged_batch* m) {
-    const osmt_batch* b0 = reqs[0]->b;
-    const bool ll = b0->coord_kind == OSMT_COORD_LATLON_F64, nr = b0->coord_kind == OSMT_COORD_NODE_REF;
-    for (const coalesce_req* r : reqs)
-        if (r->lb && r->lb->n_labels) m->has_labels = true;
-    if (m->has_labels) m->job_label_off.push_back(0u);
-    for (const coalesce_req* r : reqs) {
-        const osmt_batch* b = r->b;
-        const uint32_t op0 = (uint32_t)m->ops.size(), ring0 = (uint32_t)m->rings.size(), dash0 = (uint32_t)m->dashes.size();
-        const uint32_t pt0 = (uint32_t)(ll ? m->latlon.size() / 2 : nr ? m->node_refs.size() : m->points.size() / 2);
-        const uint32_t node0 = nr ? (uint32_t)(m->latlon.size() / 2) : 0u;
-        for (size_t j = 0; j < b->n_jobs; ++j) {
-            osmt_tile_job job = b->jobs[j];
-            job.op_off += op0;
-            job.pt_off += pt0;
-            m->jobs.push_back(job);
-        }
-        for (size_t o = 0; o < b->n_ops; ++o) {
-            osmt_op op = b->ops[o];
-            if (op.kind != OSMT_OP_NONE) {
-                op.ring_off += ring0;
-                if (op.kind == OSMT_OP_STROKE && op.has_dashes) op.dashes_off += dash0;
-            }
-            m->ops.push_back(op);
-        }
-        for (size_t k = 0; k < b->n_rings; ++k) {
-            osmt_ring ring = b->rings[k];
-            ring.first_pt += pt0;
-            m->rings.push_back(ring);
-        }
-        if (ll) {
-            m->latlon.insert(m->latlon.end(), b->latlon, b->latlon + 2 * b->n_pts);
-        } else if (nr) {
-            m->latlon.insert(m->latlon.end(), b->nodes, b->nodes + 2 * b->n_nodes);
-            for (size_t i = 0; i < b->n_pts; ++i) m->node_refs.push_back(b->node_refs[i] + node0);
-        } else {
-            m->points.insert(m->points.end(), b->points, b->points + 2 * b->n_pts);
-        }
-        if (b->n_dashes) m->dashes.insert(m->dashes.end(), b->dashes, b->dashes + b->n_dashes);
-        if (m->has_labels) {
-            const osmt_label_batch* lb = r->lb;
-            const uint32_t lab0 = (uint32_t)m->labels.size(), seg0 = (uint32_t)(m->segs.size() / 4);
-            if (lb && lb->n_labels) {
-                for (size_t i = 0; i < lb->n_labels; ++i) {
-                    osmt_label l = lb->labels[i];
-                    l.seg_off += seg0;
-                    m->labels.push_back(l);
-                }
-                m->segs.insert(m->segs.end(), lb->segs, lb->segs + 4 * lb->n_segs);
-                for (size_t j = 0; j < b->n_jobs; ++j) m->job_label_off.push_back(lab0 + lb->job_label_off[j + 1]);
-            } else {
-                for (size_t j = 0; j < b->n_jobs; ++j) m->job_label_off.push_back(lab0);
-            }
-        }
-    }
-    memset(&m->b, 0, sizeof m->b);
-    m->b.jobs = m->jobs.data();
-    m->b.n_jobs = m->jobs.size();
-    m->b.ops = m->ops.data();
-    m->b.n_ops = m->ops.size();
-    m->b.rings = m->rings.data();
-    m->b.n_rings = m->rings.size();
-    m->b.coord_kind = b0->coord_kind;
-    m->b.scale = b0->scale;
-    m->b.n_pts = ll ? m->latlon.size() / 2 : nr ? m->node_refs.size() : m->points.size() / 2;
-    m->b.latlon = ll ? m->latlon.data() : nullptr;
-    m->b.points = (!ll && !nr) ? m->points.data() : nullptr;
-    m->b.nodes = nr ? m->latlon.data() : nullptr;
-    m->b.n_nodes = nr ? m->latlon.size() / 2 : 0;
-    m->b.node_refs = nr ? m->node_refs.data() : nullptr;
-    m->b.dashes = m->dashes.data();
-    m->b.n_dashes = m->dashes.size();
-    memset(&m->lb, 0, sizeof m->lb);
-    m->lb.labels = m->labels.data();
-    m->lb.n_labels = m->labels.size();
-    m->lb.job_label_off = m->job_label_off.data();
-    m->lb.segs = m->segs.data();
-    m->lb.n_segs = m->segs.size() / 4;
-}
-
-/* label batches are validated where they are attached (osmt_scene_set_labels); here only what merging itself reads */
-int label_batch_shape_ok(const osmt_batch* b, const osmt_label_batch* lb) {
-    if (!lb || !lb->n_labels) return OSMT_OK;
-    if (!lb->labels || !lb->job_label_off || (lb->n_segs && !lb->segs)) return fail(OSMT_INVALID_ARG, "label batch: NULL pool");
-    if (lb->n_labels >= 0x7FFFFFFFull || lb->n_segs >= 0x7FFFFFFFull) return fail(OSMT_INVALID_ARG, "label batch too large");
-    if (lb->job_label_off[0] != 0u) return fail(OSMT_INVALID_ARG, "job_label_off[0] must be 0");
-    for (size_t j = 0; j < b->n_jobs; ++j)
-        if (lb->job_label_off[j + 1] < lb->job_label_off[j] || lb->job_label_off[j + 1] > lb->n_labels)
-            return fail(OSMT_INVALID_ARG, "job_label_off not monotonic / out of range at tile %zu", j);
-    if (lb->job_label_off[b->n_jobs] != lb->n_labels) return fail(OSMT_INVALID_ARG, "job_label_off[n_jobs] != n_labels");
-    /* a label's draw_line calls must lie in ITS request's pool: re-based into the merged pool an out-of-range seg_off would
-     * land in another request's calls and pass the merged check instead of failing alone */
-    for (size_t i = 0; i < lb->n_labels; ++i)
-        if ((unsigned long long)lb->labels[i].seg_off + lb->labels[i].n_segs > lb->n_segs)
-            return fail(OSMT_INVALID_ARG, "label %zu: seg_off + n_segs beyond the batch's draw_line calls", i);
-    return OSMT_OK;
-}
-
-/* renders the requests of one group; fills rc / err / grp / src of every request (the caller marks them done) */
-void coalesce_run_group(osmt_ctx* ctx, const std::vector<coalesce_req*>& reqs) {
-    auto run_alone = [&](coalesce_req* r) {
-        /* its requester has validated it: trusted, like the merged batch (no second pass over the ops and points) */
-        r->rc = guarded([&] {
-            return osmt_render_batch_labels_body(ctx, r->b, (r->lb && r->lb->n_labels) ? r->lb : nullptr, r->out, r->stride, true, true);
-        });
-        r->ran = true;
-        if (r->rc != OSMT_OK) r->err = osmt_last_error();
-    };
-    if (reqs.size() == 1) {
-        run_alone(reqs[0]);
-        return;
-    }
-    const size_t W = (size_t)OSMT_TILE_SIZE * reqs[0]->b->scale, tile_rgb = W * W * 3;
-    size_t n_tiles = 0;
-    for (const coalesce_req* r : reqs) n_tiles += r->b->n_jobs;
-    int rc = OSMT_OK;
-    void* stage = nullptr;
-    /* OSMT_TRACE_WORKER=1 (diagnostic): one stderr line per gathered group — requests, tiles, merge and render time */
-    static const bool trace_worker = getenv("OSMT_TRACE_WORKER") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto t1 = t0;
-    try {
-        merged_batch m;
-        merge_requests(reqs, &m);
-        stage = stage_acquire(ctx, n_tiles * tile_rgb);
-        t1 = std::chrono::steady_clock::now();
-        if (!stage) {
-            rc = OSMT_OOM;
-        } else {
-            rc = osmt_render_batch_labels_body(ctx, &m.b, m.has_labels ? &m.lb : nullptr, (uint8_t*)stage, tile_rgb, true, true);
-        }
-    } catch (...) {
-        rc = OSMT_OOM;
-    }
-    if (trace_worker) {
-        const auto t2 = std::chrono::steady_clock::now();
-        fprintf(stderr, "osmt worker group: %zu requests, %zu tiles, merge+staging %.0f us, render %.0f us, rc %d\n", reqs.size(), n_tiles,
-                std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count(), rc);
-    }
-    if (rc != OSMT_OK) {
-        /* whatever went wrong (one request's labels refused, no pinned memory): every request on its own, so that a bad
-         * one fails alone */
-        if (stage) stage_release(ctx, stage);
-        for (coalesce_req* r : reqs) run_alone(r);
-        return;
-    }
-    coalesce_group* g = new (std::nothrow) coalesce_group();
-    if (!g) {
-        stage_release(ctx, stage);
-        for (coalesce_req* r : reqs) run_alone(r);
-        return;
-    }
-    g->ctx = ctx;
-    g->stage = stage;
-    g->pending.store((int)reqs.size());
-    size_t first = 0;
-    for (coalesce_req* r : reqs) {
-        r->grp = g;
-        r->src = (const uint8_t*)stage + first * tile_rgb;
-        r->rc = OSMT_OK;
-        first += r->b->n_jobs;
-    }
-}
-
-int worker_render_body(osmt_worker* w, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgb, size_t stride) {
-    if (!w || !w->ctx || !out_rgb) return fail(OSMT_INVALID_ARG, "NULL argument");
-    osmt_ctx* ctx = w->ctx;
-    int rc = validate_batch(batch); /* by the requesting thread: the merged batch is trusted */
-    if (rc != OSMT_OK) return rc;
-    rc = label_batch_shape_ok(batch, labels);
-    if (rc != OSMT_OK) return rc;
-    const size_t W = (size_t)OSMT_TILE_SIZE * batch->scale, tile_rgb = W * W * 3;
-    if (stride < tile_rgb) return fail(OSMT_INVALID_ARG, "out_tile_stride_bytes < W*H*3");
-    if (batch->n_jobs == 0) return OSMT_OK;
-    if (batch->n_jobs > CO_MAX_TILES) return osmt_render_batch_rgb(ctx, batch, labels, out_rgb, stride); /* a batch of its own anyway */
-
-    coalesce_req me;
-    me.b = batch;
-    me.lb = labels;
-    me.out = out_rgb;
-    me.stride = stride;
-    std::vector<coalesce_req*> group;
-    group.reserve(CO_MAX_TILES); /* every request has at least one tile: push_back below cannot throw */
-    {
-        std::unique_lock<std::mutex> lk(ctx->co_mu);
-        ctx->co_queue.push_back(&me);
-        for (;;) {
-            if (me.done) break;
-            if (!me.taken && ctx->co_in_flight < co_max_in_flight()) {
-                /* leader: everything that waits and fits, in arrival order (its own request is in there) */
-                size_t tiles = 0;
-                /* the merged pools are indexed with 32 bits and rendered without a second validation: a request that
-                 * would take any pool past 2^31 entries waits for the next leader (alone it is what its own validation saw) */
-                unsigned long long pool[7] = {0, 0, 0, 0, 0, 0, 0};
-                const osmt_batch* b0 = ctx->co_queue.front()->b;
-                while (!ctx->co_queue.empty()) {
-                    coalesce_req* r = ctx->co_queue.front();
-                    if (r->b->scale != b0->scale || r->b->coord_kind != b0->coord_kind) break; /* the next leader's */
-                    if (!group.empty() && tiles + r->b->n_jobs > CO_MAX_TILES) break;
-                    const unsigned long long add[7] = {r->b->n_ops, r->b->n_rings, r->b->n_pts, r->b->n_nodes, r->b->n_dashes,
-                                                       r->lb ? r->lb->n_labels : 0ull, r->lb ? r->lb->n_segs : 0ull};
-                    bool fits32 = true;
-                    for (int k = 0; k < 7; ++k) fits32 = fits32 && pool[k] + add[k] < 0x7FFFFFFFull;
-                    if (!group.empty() && !fits32) break;
-                    for (int k = 0; k < 7; ++k) pool[k] += add[k];
-                    tiles += r->b->n_jobs;
-                    r->taken = true;
-                    group.push_back(r);
-                    ctx->co_queue.pop_front();
-                }
-                ++ctx->co_in_flight;
-                lk.unlock();
-                /* whatever happens in there, the group's members are marked done and the slot is given back: followers
-                 * wait on co_cv with no timeout */
-                try {
-                    coalesce_run_group(ctx, group);
-                } catch (...) {
-                    for (coalesce_req* r : group)
-                        if (!r->grp && !r->ran) r->rc = OSMT_OOM; /* (err stays empty: assigning a string could throw again) */
-                }
-                lk.lock();
-                --ctx->co_in_flight;
-                for (coalesce_req* r : group) r->done = true;
-                group.clear();
-                ctx->co_cv.notify_all();
-                continue; /* its own request may have been behind an incompatible one: look again */
-            }
-            ctx->co_cv.wait(lk);
-        }
-    }
-    if (me.rc != OSMT_OK) return fail(me.rc, "%s", me.err.c_str());
-    if (me.grp) {
-        /* the requester's own share of the read-back: pinned staging -> its buffer, all requesters in parallel */
-        for (size_t j = 0; j < batch->n_jobs; ++j) memcpy(out_rgb + j * stride, me.src + j * tile_rgb, tile_rgb);
-        coalesce_group* g = me.grp;
-        if (g->pending.fetch_sub(1) == 1) {
-            stage_release(g->ctx, g->stage);
-            delete g;
-        }
-    }
-    return OSMT_OK;
-}
-
-}  // namespace
-
-int osmt_worker_create(osmt_ctx* ctx, osmt_worker** out_worker) {
-    return guarded([&] {
-        if (!ctx || !out_worker) return fail(OSMT_INVALID_ARG, "NULL argument");
-        osmt_worker* w = new (std::nothrow) osmt_worker();
-        if (!w) return fail(OSMT_OOM, "out of host memory");
-        w->ctx = ctx;
-        ctx->refs.fetch_add(1); /* like a scene: the context outlives its workers */
-        *out_worker = w;
-        return (int)OSMT_OK;
-    });
-}
-
-void osmt_worker_destroy(osmt_worker* w) {
-    if (!w) return;
-    osmt_ctx* ctx = w->ctx;
-    delete w;
-    if (ctx) ctx_release(ctx);
-}
-
-int osmt_worker_render(osmt_worker* w, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgb, size_t out_tile_stride_bytes) {
-    return guarded([&] { return worker_render_body(w, batch, labels, out_rgb, out_tile_stride_bytes); });
-}
-
-/* ---- tile requests: (z, x, y, scale) in, PNG out ---------------------------------------------------------------------
- * try_handle_connection (src/http_server.rs:134-181) per request: get_entities_in_tile_with_neighbors(tile, osm_ids) ->
- * draw_tile -> PNG bytes.  A tile server states once what every request is rendered with — geodata, bindings per zoom,
- * canvas, filter; osmt_tile_server_render_png is build (filtered or not) -> label -> osmt_render_scene_png -> free for a
- * list of tiles, and osmt_worker_render_tile_png gathers the one-tile requests of concurrent threads into such lists by the
- * group commit of osmt_worker_render above, sharing its cap on groups in flight. */
-struct osmt_tile_server {
-    osmt_ctx* ctx = nullptr;
-    osmt_tile_server_desc d{};
-    bool area_labels = false, node_labels = false; /* the label array is not all OSMT_BINDINGS_NONE */
-};
-
-namespace {
-
-/* the pairs the last tile-server call of this thread declined (osmt_last_declined_anchors) */
-thread_local std::vector<osmt_area_anchor> tl_declined;
-
-bool any_bound(const uint32_t* of_zoom) {
-    for (uint32_t z = 0; z <= OSMT_MAX_ZOOM; ++z)
-        if (of_zoom[z] != OSMT_BINDINGS_NONE) return true;
-    return false;
-}
-
-int validate_tile_server(const osmt_tile_server_desc* d, osmt_ctx* ctx) {
-    if (!d) return fail(OSMT_INVALID_ARG, "tile server: the description is NULL");
-    if (!ctx) return fail(OSMT_INVALID_ARG, "tile server: geodata id %u is not registered (no context)", d->geodata_id);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (d->geodata_id >= ctx->geodata.size())
-        return fail(OSMT_INVALID_ARG, "tile server: geodata id %u is not registered (%zu files)", d->geodata_id, ctx->geodata.size());
-    if (!ctx->geodata[d->geodata_id].d_index)
-        return fail(OSMT_INVALID_ARG, "tile server: geodata id %u has no tile index (osmt_register_tile_index)", d->geodata_id);
-    /* one table of one kind under one zoom: known, of this file, covering that zoom */
-    auto table_ok = [&](const char* kind, uint32_t id, uint32_t z, size_t n, uint32_t geodata_id, uint32_t lo, uint32_t hi) {
-        if (id >= n) return fail(OSMT_INVALID_ARG, "tile server: %s id %u of zoom %u is not registered (%zu tables)", kind, id, z, n);
-        if (geodata_id != d->geodata_id)
-            return fail(OSMT_INVALID_ARG, "tile server: %s id %u of zoom %u belongs to geodata id %u, not %u", kind, id, z, geodata_id, d->geodata_id);
-        if (z < lo || z > hi) return fail(OSMT_INVALID_ARG, "tile server: %s id %u covers zooms %u..%u, not zoom %u", kind, id, lo, hi, z);
-        return (int)OSMT_OK;
-    };
-    for (uint32_t z = 0; z <= OSMT_MAX_ZOOM; ++z) {
-        int rc = OSMT_OK;
-        uint32_t id = d->bindings_of_zoom[z];
-        if (id != OSMT_BINDINGS_NONE) {
-            const bool known = id < ctx->bindings.size();
-            rc = table_ok("bindings", id, z, ctx->bindings.size(), known ? ctx->bindings[id].geodata_id : 0u, known ? ctx->bindings[id].zoom_lo : 0u,
-                          known ? ctx->bindings[id].zoom_hi : 0u);
-            if (rc != OSMT_OK) return rc;
-        }
-        id = d->area_label_bindings_of_zoom[z];
-        if (id != OSMT_BINDINGS_NONE) {
-            const bool known = id < ctx->area_label_bindings.size();
-            rc = table_ok("area label bindings", id, z, ctx->area_label_bindings.size(), known ? ctx->area_label_bindings[id].geodata_id : 0u,
-                          known ? ctx->area_label_bindings[id].zoom_lo : 0u, known ? ctx->area_label_bindings[id].zoom_hi : 0u);
-            if (rc != OSMT_OK) return rc;
-        }
-        id = d->node_label_bindings_of_zoom[z];
-        if (id != OSMT_BINDINGS_NONE) {
-            const bool known = id < ctx->label_bindings.size();
-            rc = table_ok("node label bindings", id, z, ctx->label_bindings.size(), known ? ctx->label_bindings[id].geodata_id : 0u,
-                          known ? ctx->label_bindings[id].zoom_lo : 0u, known ? ctx->label_bindings[id].zoom_hi : 0u);
-            if (rc != OSMT_OK) return rc;
-        }
-    }
-    if (any_bound(d->node_label_bindings_of_zoom) && !ctx->geodata[d->geodata_id].d_node_index)
-        return fail(OSMT_INVALID_ARG, "tile server: node label bindings, but geodata id %u has no node index (osmt_register_node_index)", d->geodata_id);
-    if (d->id_filter != OSMT_ID_FILTER_NONE) {
-        if (d->id_filter >= ctx->id_filters.size())
-            return fail(OSMT_INVALID_ARG, "tile server: id filter %u is not registered (%zu filters)", d->id_filter, ctx->id_filters.size());
-        const osmt_ctx::id_filter_host& f = ctx->id_filters[d->id_filter];
-        if (f.geodata_id != d->geodata_id)
-            return fail(OSMT_INVALID_ARG, "tile server: id filter %u belongs to geodata id %u, not %u", d->id_filter, f.geodata_id, d->geodata_id);
-        if (any_bound(d->node_label_bindings_of_zoom) && !f.node)
-            return fail(OSMT_INVALID_ARG,
-                        "tile server: node label bindings, but id filter %u has no node plane: register the node index first (osmt_register_node_index), "
-                        "then the filter",
-                        d->id_filter);
-    }
-    return OSMT_OK;
-}
-
-/* what a requesting thread judges of its own tiles before anything is queued or built: the rules of osmt_validate_tile_batch and
- * of osmt_scene_build_tile_labels_all for the zooms these tiles have */
-int tile_request_ok(const osmt_tile_server* s, const osmt_tile_coord* tiles, size_t n, uint32_t scale) {
-    if (scale < 1 || scale > OSMT_MAX_SCALE) return fail(OSMT_INVALID_ARG, "scale %u not in 1..%u", scale, OSMT_MAX_SCALE);
-    for (size_t t = 0; t < n; ++t) {
-        const osmt_tile_coord& q = tiles[t];
-        if (q.zoom > OSMT_MAX_ZOOM) return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u > MAX_ZOOM (src/tile.rs:5)", t, q.zoom);
-        if (q.x >= (1u << q.zoom) || q.y >= (1u << q.zoom))
-            return fail(OSMT_INVALID_ARG, "tile %zu: (x, y) = (%u, %u) outside the %u x %u tiles of zoom %u", t, q.x, q.y, 1u << q.zoom, 1u << q.zoom, q.zoom);
-        if (s->d.bindings_of_zoom[q.zoom] == OSMT_BINDINGS_NONE)
-            return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u has no bindings (OSMT_BINDINGS_NONE)", t, q.zoom);
-        if (s->area_labels && s->d.area_label_bindings_of_zoom[q.zoom] == OSMT_BINDINGS_NONE)
-            return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u has no area label bindings (OSMT_BINDINGS_NONE)", t, q.zoom);
-        if (s->node_labels && s->d.node_label_bindings_of_zoom[q.zoom] == OSMT_BINDINGS_NONE)
-            return fail(OSMT_INVALID_ARG, "tile %zu: zoom %u has no label bindings (OSMT_BINDINGS_NONE)", t, q.zoom);
-    }
-    return OSMT_OK;
-}
-
-/* build (filtered or not) -> label -> PNG -> free, on the library's own streams.  tiles have passed tile_request_ok.  declined (may be
- * NULL): gets the pairs the anchor search declined when that is why the call fails. */
-int tile_server_run(osmt_tile_server* s, const osmt_tile_coord* tiles, size_t n, uint32_t scale, const osmt_area_anchor* anchors, size_t n_anchors,
-                    uint8_t* out_png, size_t out_capacity, uint64_t* out_off, std::vector<osmt_area_anchor>* declined) {
-    osmt_ctx* ctx = s->ctx;
-    std::vector<osmt_query_tile> q(n);
-    for (size_t t = 0; t < n; ++t) {
-        osmt_query_tile& o = q[t];
-        memset(&o, 0, sizeof o);
-        o.x = tiles[t].x, o.y = tiles[t].y, o.zoom = (uint8_t)tiles[t].zoom;
-        o.has_canvas = s->d.has_canvas ? 1 : 0;
-        if (o.has_canvas) memcpy(o.canvas_rgb, s->d.canvas_rgb, 3);
-    }
-    osmt_tile_batch b;
-    memset(&b, 0, sizeof b);
-    b.tiles = q.data(), b.n_tiles = n;
-    b.geodata_id = s->d.geodata_id, b.scale = scale, b.use_caps_for_dashes = s->d.use_caps_for_dashes;
-    memcpy(b.bindings_of_zoom, s->d.bindings_of_zoom, sizeof b.bindings_of_zoom);
-    osmt_scene* sc = nullptr;
-    int rc = scene_build_tiles_body(ctx, &b, s->d.id_filter, &sc);
-    if (rc != OSMT_OK) return rc;
-    if (s->area_labels || s->node_labels)
-        rc = scene_build_tile_labels_all_body(ctx, sc, s->area_labels ? s->d.area_label_bindings_of_zoom : nullptr,
-                                              s->node_labels ? s->d.node_label_bindings_of_zoom : nullptr, anchors, n_anchors);
-    if (rc == OSMT_OK) rc = osmt_render_scene_png(ctx, sc, out_png, out_capacity, out_off);
-    if (rc == OSMT_OK) {
-        osmt_scene_free(sc);
-        return OSMT_OK;
-    }
-    const std::string why = osmt_last_error(); /* freeing a scene may report nothing, but it must not lose this */
-    if (declined && rc == OSMT_UNSUPPORTED) *declined = sc->h_al_declined;
-    osmt_scene_free(sc);
-    return fail(rc, "%s", why.c_str());
-}
-
-int tile_server_render_png_body(osmt_tile_server* s, const osmt_tile_coord* tiles, size_t n, uint32_t scale, const osmt_area_anchor* anchors,
-                                size_t n_anchors, uint8_t* out_png, size_t out_capacity, uint64_t* out_off) {
-    tl_declined.clear();
-    if (!s || !out_off || (n && !tiles) || (!out_png && out_capacity) || (n_anchors && !anchors)) return fail(OSMT_INVALID_ARG, "NULL argument");
-    const int rc = tile_request_ok(s, tiles, n, scale);
-    if (rc != OSMT_OK) return rc;
-    if (n == 0) {
-        out_off[0] = 0; /* no tiles, no files: no device is touched */
-        return OSMT_OK;
-    }
-    return tile_server_run(s, tiles, n, scale, anchors, n_anchors, out_png, out_capacity, out_off, &tl_declined);
-}
-
-}  // namespace
-
-/* ---- the per-request entry for tile coordinates ---- */
-struct tile_group {
-    osmt_ctx* ctx = nullptr;
-    void* stage = nullptr;
-    std::atomic<int> pending{0}; /* requesters that still have to copy their file out of `stage` */
-};
-
-struct tile_req {
-    osmt_tile_server* s = nullptr;
-    osmt_tile_coord tile{};
-    uint32_t scale = 1;
-    const osmt_area_anchor* anchors = nullptr;
-    size_t n_anchors = 0;
-    uint8_t* out = nullptr;
-    size_t cap = 0;
-    bool taken = false, done = false, ran = false; /* ran: rendered on its own (rc, len and declined are its verdict) */
-    int rc = OSMT_OK;
-    std::string err;
-    std::vector<osmt_area_anchor> declined; /* tile 0 in each: what its own run declined */
-    tile_group* grp = nullptr;              /* where the file is (NULL: already in `out`, or failed) */
-    const uint8_t* src = nullptr;
-    size_t len = 0; /* the file's size, also when it did not fit */
-};
-
-namespace {
-
-void tile_run_group(osmt_ctx* ctx, const std::vector<tile_req*>& reqs) {
-    auto run_alone = [&](tile_req* r) {
-        uint64_t off[2] = {0, 0};
-        r->rc = guarded([&] { return tile_server_run(r->s, &r->tile, 1, r->scale, r->anchors, r->n_anchors, r->out, r->cap, off, &r->declined); });
-        r->ran = true;
-        r->len = (size_t)off[1];
-        if (r->rc != OSMT_OK) r->err = osmt_last_error();
-    };
-    if (reqs.size() == 1) {
-        run_alone(reqs[0]);
-        return;
-    }
-    const size_t n = reqs.size(), W = (size_t)OSMT_TILE_SIZE * reqs[0]->scale, slot = osmt_png_device_bound((uint32_t)W, (uint32_t)W);
-    int rc = OSMT_OK;
-    void* stage = nullptr;
-    std::vector<uint64_t> off;
-    try {
-        /* the tiles concatenated; every requester's anchors re-based from tile 0 to its index: ascending by (tile, entity) already */
-        std::vector<osmt_tile_coord> tiles(n);
-        std::vector<osmt_area_anchor> anchors;
-        off.assign(n + 1, 0);
-        for (size_t i = 0; i < n; ++i) {
-            tiles[i] = reqs[i]->tile;
-            for (size_t k = 0; k < reqs[i]->n_anchors; ++k) {
-                osmt_area_anchor a = reqs[i]->anchors[k];
-                a.tile = (uint32_t)i;
-                anchors.push_back(a);
-            }
-        }
-        stage = stage_acquire(ctx, n * slot);
-        if (!stage)
-            rc = OSMT_OOM;
-        else
-            rc = guarded([&] {
-                return tile_server_run(reqs[0]->s, tiles.data(), n, reqs[0]->scale, anchors.data(), anchors.size(), (uint8_t*)stage, n * slot, off.data(), nullptr);
-            });
-    } catch (...) {
-        rc = OSMT_OOM;
-    }
-    tile_group* g = rc == OSMT_OK ? new (std::nothrow) tile_group() : nullptr;
-    if (!g) {
-        /* whatever went wrong (a member's anchors refused, a declined pair, no pinned memory): every member on its own, so that a
-         * bad request or a declined anchor fails alone and the others get their files */
-        if (stage) stage_release(ctx, stage);
-        for (tile_req* r : reqs) run_alone(r);
-        return;
-    }
-    g->ctx = ctx;
-    g->stage = stage;
-    g->pending.store((int)n);
-    for (size_t i = 0; i < n; ++i) {
-        reqs[i]->grp = g;
-        reqs[i]->src = (const uint8_t*)stage + off[i];
-        reqs[i]->len = (size_t)(off[i + 1] - off[i]);
-        reqs[i]->rc = OSMT_OK;
-    }
-}
-
-int worker_render_tile_png_body(osmt_worker* w, osmt_tile_server* s, const osmt_tile_coord* tile, uint32_t scale, const osmt_area_anchor* anchors,
-                                size_t n_anchors, uint8_t* out_png, size_t out_capacity, size_t* out_len) {
-    tl_declined.clear();
-    if (!w || !w->ctx || !s || !tile || !out_len || (!out_png && out_capacity) || (n_anchors && !anchors)) return fail(OSMT_INVALID_ARG, "NULL argument");
-    *out_len = 0;
-    if (s->ctx != w->ctx) return fail(OSMT_INVALID_ARG, "the tile server belongs to another context than the worker");
-    osmt_ctx* ctx = w->ctx;
-    int rc = tile_request_ok(s, tile, 1, scale); /* by the requesting thread: a bad request never joins a group */
-    if (rc != OSMT_OK) return rc;
-    for (size_t k = 0; k < n_anchors; ++k)
-        if (anchors[k].tile != 0u) return fail(OSMT_INVALID_ARG, "anchor %zu: tile %u (a request is one tile: tile 0)", k, anchors[k].tile);
-
-    tile_req me;
-    me.s = s, me.tile = *tile, me.scale = scale;
-    me.anchors = anchors, me.n_anchors = n_anchors;
-    me.out = out_png, me.cap = out_capacity;
-    std::vector<tile_req*> group;
-    group.reserve(CO_MAX_TILES);
-    {
-        std::unique_lock<std::mutex> lk(ctx->co_mu);
-        ctx->co_tile_queue.push_back(&me);
-        ++ctx->co_tile_stats[0];
-        for (;;) {
-            if (me.done) break;
-            if (!me.taken && ctx->co_in_flight < co_max_in_flight()) {
-                /* leader: the waiting requests of the server and scale at the HEAD of the queue, in arrival order, up to the first
-                 * request of another server or scale — that one is the next leader's, as in osmt_worker_render.  The leader's own
-                 * request may sit behind such a request: then it leads the group in front first and looks again.  Running other
-                 * threads' requests (the group, or its members alone) overwrites THIS thread's osmt_last_error and declined list in
-                 * between; both are set again from its own request on the way out (fail() and the swap below). */
-                const tile_req* r0 = ctx->co_tile_queue.front();
-                while (!ctx->co_tile_queue.empty() && group.size() < CO_MAX_TILES) {
-                    tile_req* r = ctx->co_tile_queue.front();
-                    if (r->s != r0->s || r->scale != r0->scale) break; /* the next leader's */
-                    r->taken = true;
-                    group.push_back(r);
-                    ctx->co_tile_queue.pop_front();
-                }
-                ++ctx->co_in_flight; /* shared with osmt_worker_render: both entries together keep the cap */
-                ++ctx->co_tile_stats[1];
-                if (group.size() > ctx->co_tile_stats[2]) ctx->co_tile_stats[2] = group.size();
-                lk.unlock();
-                /* whatever happens in there, the group's members are marked done and the slot is given back: followers wait on
-                 * co_cv with no timeout */
-                try {
-                    tile_run_group(ctx, group);
-                } catch (...) {
-                    for (tile_req* r : group)
-                        if (!r->grp && !r->ran) r->rc = OSMT_OOM;
-                }
-                lk.lock();
-                --ctx->co_in_flight;
-                for (tile_req* r : group) r->done = true;
-                group.clear();
-                ctx->co_cv.notify_all();
-                continue;
-            }
-            ctx->co_cv.wait(lk);
-        }
-    }
-    tl_declined.swap(me.declined); /* left for ITS thread, whoever led the group */
-    *out_len = me.len;
-    if (me.rc != OSMT_OK) return fail(me.rc, "%s", me.err.c_str());
-    if (me.grp) {
-        const bool fits = me.len <= out_capacity;
-        if (fits) memcpy(out_png, me.src, me.len);
-        tile_group* g = me.grp;
-        if (g->pending.fetch_sub(1) == 1) {
-            stage_release(g->ctx, g->stage);
-            delete g;
-        }
-        if (!fits) return fail(OSMT_INVALID_ARG, "out_capacity %zu < %zu bytes of PNG data", out_capacity, me.len);
-    }
-    return OSMT_OK;
-}
-
-}  // namespace
-
-int osmt_validate_tile_server(const osmt_tile_server_desc* d, osmt_ctx* ctx) {
-    return guarded([&] { return validate_tile_server(d, ctx); });
-}
-int osmt_tile_server_create(osmt_ctx* ctx, const osmt_tile_server_desc* d, osmt_tile_server** out) {
-    return guarded([&] {
-        if (!ctx || !out) return fail(OSMT_INVALID_ARG, "NULL argument");
-        *out = nullptr;
-        const int rc = validate_tile_server(d, ctx);
-        if (rc != OSMT_OK) return rc;
-        osmt_tile_server* s = new osmt_tile_server();
-        s->ctx = ctx;
-        s->d = *d;
-        s->area_labels = any_bound(d->area_label_bindings_of_zoom);
-        s->node_labels = any_bound(d->node_label_bindings_of_zoom);
-        ctx->refs.fetch_add(1); /* like a scene or a worker: the context outlives its servers */
-        *out = s;
-        return (int)OSMT_OK;
-    });
-}
-void osmt_tile_server_free(osmt_tile_server* s) {
-    if (!s) return;
-    osmt_ctx* ctx = s->ctx;
-    delete s;
-    if (ctx) ctx_release(ctx);
-}
-int osmt_tile_server_render_png(osmt_tile_server* s, const osmt_tile_coord* tiles, size_t n, uint32_t scale, const osmt_area_anchor* anchors,
-                                size_t n_anchors, uint8_t* out_png, size_t out_capacity, uint64_t* out_off) {
-    return guarded([&] { return tile_server_render_png_body(s, tiles, n, scale, anchors, n_anchors, out_png, out_capacity, out_off); });
-}
-int osmt_last_declined_anchors(osmt_area_anchor* out, size_t cap, size_t* n) {
-    return guarded([&] {
-        if (!n) return fail(OSMT_INVALID_ARG, "NULL argument");
-        *n = tl_declined.size();
-        if (!out) return (int)OSMT_OK;
-        if (cap < *n) return fail(OSMT_INVALID_ARG, "out holds %zu anchors, the last call declined %zu", cap, *n);
-        if (*n) memcpy(out, tl_declined.data(), *n * sizeof(osmt_area_anchor));
-        return (int)OSMT_OK;
-    });
-}
-int osmt_worker_render_tile_png(osmt_worker* w, osmt_tile_server* s, const osmt_tile_coord* tile, uint32_t scale, const osmt_area_anchor* anchors,
-                                size_t n_anchors, uint8_t* out_png, size_t out_capacity, size_t* out_len) {
-    return guarded([&] { return worker_render_tile_png_body(w, s, tile, scale, anchors, n_anchors, out_png, out_capacity, out_len); });
-}
-int osmt_worker_tile_stats(osmt_ctx* ctx, uint64_t stats[3]) {
-    return guarded([&] {
-        if (!ctx || !stats) return fail(OSMT_INVALID_ARG, "NULL argument");
-        std::lock_guard<std::mutex> lk(ctx->co_mu);
-        for (int k = 0; k < 3; ++k) stats[k] = ctx->co_tile_stats[k];
-        return (int)OSMT_OK;
-    });
 }
 
 static int hbm_copy_probe_body(osmt_ctx* ctx, size_t bytes, uint32_t iters, double* out_copy, double* out_read) {

@@ -3,6 +3,8 @@ numpy mirrors have the header's layout.  No compute calls (no GPU needed)."""
 import ctypes as C
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -48,6 +50,33 @@ def test_library_exports_no_unprefixed_helper():
             getattr(L, name)
     for name in lib.EXPORTS:
         assert getattr(L, name) is not None, name
+
+
+def _defined_dynamic_symbols():
+    """(type letter, name) of every symbol the built library defines, as `nm -D --defined-only` lists them."""
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("no nm on the path")
+    if not os.path.exists(lib.LIB_PATH):
+        pytest.fail("libosmtile.so is not built: run __graft_entry__.build()")
+    out = subprocess.run([nm, "-D", "--defined-only", lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    syms = [tuple(line.split()[-2:]) for line in out.splitlines() if len(line.split()) >= 2]
+    assert syms, "nm listed nothing"
+    return syms
+
+
+def test_library_defines_exactly_the_c_abi():
+    """The host side is several translation units: a helper they share has external linkage and would leave the library with
+    default visibility.  The unmangled functions the library defines are the C ABI, name for name."""
+    c_functions = {name for kind, name in _defined_dynamic_symbols() if kind == "T" and not name.startswith("_Z")}
+    assert c_functions == set(lib.EXPORTS)
+
+
+def test_no_shared_host_helper_leaves_the_library():
+    """What the host files share lives in namespace osmt_host with hidden visibility (csrc/osmt_host.h): no dynamic symbol of
+    any kind names it.  (osmt_host_alloc and osmt_host_free are entries of the C ABI and the only names excepted.)"""
+    leaked = [name for _, name in _defined_dynamic_symbols() if "osmt_host" in name and name not in lib.EXPORTS]
+    assert leaked == []
 
 
 def test_struct_layouts_match_the_header():
