@@ -1427,7 +1427,8 @@ int osmt_encode_png(const uint8_t* rgba, uint32_t width, uint32_t height, size_t
  * framebuffer; a map tile shrinks 5-8x, so a server moves 30-50 KB per tile over PCIe instead of 256 KB and spends
  * no host time in zlib.
  * d_rgba: n framebuffers (RGBA8, rows tightly packed) tile_stride bytes apart; d_png: n slots png_stride >=
- * osmt_png_device_bound(W, H) bytes apart (multiples of 4); d_len[i] = size of file i.  W multiple of 4, <= 1024. */
+ * osmt_png_device_bound(W, H) bytes apart (multiples of 4); d_len[i] = size of file i.  W multiple of 4, <= 1024;
+ * H <= 1024.  Anything else is OSMT_UNSUPPORTED before a kernel is launched (osmt_last_error names the width or the height). */
 size_t osmt_png_device_bound(uint32_t width, uint32_t height);
 int osmt_encode_png_device(osmt_ctx* ctx, const void* d_rgba, size_t tile_stride_bytes, uint32_t n, uint32_t width, uint32_t height,
                            void* d_png, size_t png_stride_bytes, uint32_t* d_len, void* stream);

@@ -5002,6 +5002,8 @@ static int osmt_encode_png_device_body(osmt_ctx* ctx, const void* d_rgba, size_t
     if (n == 0) return OSMT_OK;
     if (!d_rgba || !d_png || !d_len) return fail(OSMT_INVALID_ARG, "NULL device pointer");
     if (W == 0 || H == 0 || W > 1024 || (W % 4) != 0) return fail(OSMT_UNSUPPORTED, "PNG width %u not supported (multiple of 4, <= 1024)", W);
+    /* k_png_encode keeps one LDS word per row (position, Adler sums): PNG_MAX_W of them */
+    if (H > 1024) return fail(OSMT_UNSUPPORTED, "PNG height %u not supported (<= 1024)", H);
     if (tile_stride < (size_t)W * H * 4 || (tile_stride % 4) != 0) return fail(OSMT_INVALID_ARG, "tile stride too small / not a multiple of 4");
     if (png_stride < osmt_png_device_bound(W, H) || (png_stride % 4) != 0) return fail(OSMT_INVALID_ARG, "png_stride < osmt_png_device_bound()");
     HIP_TRY(hipSetDevice(ctx->device));

@@ -125,6 +125,7 @@ __device__ __forceinline__ void png_put(uint32_t* buf, uint32_t& pos, uint32_t b
 }
 
 #define PNG_MAX_W 1024u
+#define PNG_MAX_H 1024u /* k_png_encode: sh_rowpos, sh_a1, sh_a2 hold one word per row; osmt_launch_png and the C entry refuse more */
 #ifndef OSMT_V_PNG_WAVES
 #define OSMT_V_PNG_WAVES 4
 #endif
@@ -244,8 +245,8 @@ __global__ __launch_bounds__(64 * PNG_WAVES) void k_png_encode(const uint8_t* __
     __shared__ uint8_t sh_f[PNG_WAVES][3u * PNG_MAX_W + 4u];
     __shared__ uint32_t sh_bits[PNG_WAVES][(PNG_LMAX * (3u * PNG_MAX_W + 1u)) / 32u + 4u];
     __shared__ uint32_t sh_tab[PNG_TAB_WORDS];
-    __shared__ uint32_t sh_rowpos[PNG_MAX_W + 1u]; /* pass 1: bits of row y; after the scan: its absolute bit position */
-    __shared__ uint32_t sh_a1[PNG_MAX_W], sh_a2[PNG_MAX_W];
+    __shared__ uint32_t sh_rowpos[PNG_MAX_H + 1u]; /* pass 1: bits of row y; after the scan: its absolute bit position */
+    __shared__ uint32_t sh_a1[PNG_MAX_H], sh_a2[PNG_MAX_H];
     __shared__ uint32_t sh_crc_tab[256];
     __shared__ uint32_t sh_col[32];
     __shared__ uint32_t sh_raw[64 * PNG_WAVES];
@@ -939,6 +940,7 @@ hipError_t osmt_launch_png(const void* rgba, size_t tile_stride, uint32_t n, uin
                            size_t out_stride, uint32_t* out_len, hipStream_t st) {
     if (n == 0) return hipSuccess;
     if (W > PNG_MAX_W) return hipErrorInvalidValue;
+    if (H > PNG_MAX_H) return hipErrorInvalidValue; /* k_png_encode's per-row LDS arrays; the fast path is held to the same bound */
     /* OSMT_PNG_LZ=0: runs only, as before round 6 (bigger files, a shorter kernel): for measurements */
     static const uint32_t lz_enable = [] {
         const char* v = getenv("OSMT_PNG_LZ");

@@ -949,7 +949,8 @@ class Context:
 
     # -- PNG files from the GPU ----------------------------------------------------
     def encode_png_device(self, rgba, stream=None):
-        """osmt_encode_png_device on a uint8 cuda tensor [n, H, W, 4]: (slots uint8 [n, bound], lengths int32 [n])."""
+        """osmt_encode_png_device on a uint8 cuda tensor [n, H, W, 4]: (slots uint8 [n, bound], lengths int32 [n]).
+        W is a multiple of 4 and at most 1024, H at most 1024: anything else raises OsmtError (OSMT_UNSUPPORTED) before a launch."""
         torch = _torch()
         assert rgba.is_cuda and rgba.dtype == torch.uint8 and rgba.is_contiguous()
         n, H, W, four = rgba.shape
