@@ -1,8 +1,10 @@
 /*
- * osmt_host.h — what the host files of libosmtile.so (osmt_api.cpp, osmt_host_worker.cpp) share: the context and scene objects,
- * guarded(), and the declarations of what one file takes from the other.  Internal: nothing declared here leaves the library
+ * osmt_host.h — what the host files of libosmtile.so (osmt_api.cpp, osmt_host_worker.cpp, osmt_host_multi.cpp,
+ * osmt_host_tagstyle.cpp) share: the context and scene objects, guarded(), HIP_TRY, the two per-call holders table_upload and
+ * call_work, and the declarations of what one file takes from another.  Internal: nothing declared here leaves the library
  * (hidden visibility).  Nothing here is a variable, a static function or an anonymous namespace: every function has ONE
- * definition, in the .cpp named above its declaration, and is documented there; every thread-local stays private to its file.
+ * definition, in the .cpp named above its declaration, and is documented there (inline here: guarded, align_up and the members
+ * of the two holders); every thread-local and every cached setting stays private to its file.
  */
 #ifndef OSMT_HOST_H
 #define OSMT_HOST_H
@@ -51,6 +53,16 @@ struct tile_req;     /* osmt_worker_render_tile_png */
 
 /* osmt_api.cpp: the message osmt_last_error() returns, per thread */
 int fail(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                            \
+    do {                                                                                         \
+        hipError_t _e = (expr);                                                                  \
+        if (_e != hipSuccess)                                                                    \
+            return fail(_e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "%s failed: %s", #expr, \
+                        hipGetErrorString(_e));                                                  \
+    } while (0)
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 /* No C++ exception may cross the C boundary (a std::bad_alloc from a host-side table, say): every entry point
  * runs its body through this. */
@@ -353,16 +365,128 @@ struct osmt_scene {
 namespace osmt_host {
 
 /* ---- osmt_api.cpp ---- */
+bool poison_alloc();
+hipError_t dev_alloc(osmt_ctx* ctx, void** out, size_t bytes);
+hipError_t stream_acquire(osmt_ctx* ctx, hipStream_t* out);
+void stream_release(osmt_ctx* ctx, hipStream_t st);
 void* stage_acquire(osmt_ctx* ctx, size_t bytes);
 void stage_release(osmt_ctx* ctx, void* p);
+void dev_free(osmt_ctx* ctx, void* p);
+bool trace_upload();
 void ctx_release(osmt_ctx* ctx);
+hipError_t copy_back(osmt_ctx* ctx, void* dst, const void* src, size_t bytes);
+int validate_batch_global(const osmt_batch* b);
+int validate_job(const osmt_batch* b, size_t j, bool with_coords = true);
+int validate_nodes(const osmt_batch* b, size_t lo, size_t hi);
 int validate_batch(const osmt_batch* b, bool with_coords = true);
+int check_offsets_of(const char* who, const char* what, const uint32_t* offs, size_t count, size_t total);
+int validate_styles(const osmt_style_rec* st, size_t n, const double* dashes, size_t n_dashes, size_t n_images);
+size_t ctx_image_count(osmt_ctx* ctx);
+int register_styles_body(osmt_ctx* ctx, const osmt_style_rec* st, size_t n, const double* dashes, size_t n_dashes, uint32_t* out_first);
+int validate_label_styles(const osmt_label_style_rec* st, size_t n, osmt_ctx* ctx);
+int register_label_styles_body(osmt_ctx* ctx, const osmt_label_style_rec* st, size_t n, uint32_t* out_first);
 int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, uint32_t filter_id, osmt_scene** out_scene);
 int scene_build_tile_labels_all_body(osmt_ctx* ctx, osmt_scene* sc, const uint32_t* area_of_zoom, const uint32_t* node_of_zoom,
                                      const osmt_area_anchor* anchors, size_t n_anchors);
 int osmt_render_batch_labels_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,
                                   size_t stride, bool rgb = false, bool trusted = false, const osmt_glyph_label_batch* glabels = nullptr,
                                   const osmt_text_label_batch* tlabels = nullptr, const osmt_string_label_batch* slabels = nullptr);
+
+/* ---- osmt_host_multi.cpp ---- */
+void comm_destroy(osmt_ctx* ctx); /* ctx_teardown: the communicator and the words of the reductions go with the context */
+
+/* ---- a registered table on its way to the device ---- */
+struct table_upload {
+    char* pool = nullptr;
+    /* one device allocation that never moves once it is registered; a failure is remembered and skips the copies */
+    table_upload(const char* name, const pool_layout& pl) : name_(name) {
+        const hipError_t e = hipMalloc((void**)&pool, pl.size());
+        if (e == hipSuccess) return;
+        pool = nullptr;
+        rc_ = fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the %s failed: %s", pl.size(), name, hipGetErrorString(e));
+    }
+    table_upload(const table_upload&) = delete;
+    table_upload& operator=(const table_upload&) = delete;
+    ~table_upload() {
+        if (pool) (void)hipFree(pool);
+    }
+    /* blocking copies; after the first error the others are skipped */
+    void put(size_t o, const void* src, size_t bytes) {
+        if (rc_ != OSMT_OK || !bytes) return;
+        const hipError_t e = hipMemcpy(pool + o, src, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc_ = fail(OSMT_HIP_ERROR, "%s upload failed: %s", name_, hipGetErrorString(e)); /* every table says so, OOM or not */
+    }
+    /* OSMT_OK, or what the first failure reported */
+    int done() const { return rc_; }
+    /* registered: the context owns the allocation from here on */
+    void release() { pool = nullptr; }
+
+   private:
+    const char* name_;
+    int rc_ = OSMT_OK;
+};
+
+/* ---- what a per-call GPU pipeline holds while it runs ---- */
+struct call_work {
+    enum { MAX_WORK = 8, MAX_EV = 12 };
+    osmt_ctx* ctx;
+    hipStream_t st = nullptr;
+    char* work[MAX_WORK] = {}; /* dev_alloc buffers, given back at the end */
+    char* pool = nullptr;      /* a hipMalloc'ed table, until it is registered */
+    const bool trace = trace_upload(); /* OSMT_TRACE_UPLOAD=1 (diagnostic): the device time of the stages, one line on stderr */
+    hipEvent_t ev[MAX_EV] = {};
+
+    /* who: "tile query" in "hipMalloc(%zu) for the tile query (%s) failed"; borrowed: the caller's stream, or NULL — begin() takes a pooled one */
+    call_work(osmt_ctx* ctx_, const char* who, hipStream_t borrowed = nullptr) : ctx(ctx_), st(borrowed), who_(who), own_stream_(!borrowed) {}
+    call_work(const call_work&) = delete;
+    call_work& operator=(const call_work&) = delete;
+    ~call_work() {
+        if (st) (void)hipStreamSynchronize(st); /* nothing may still read the buffers or the caller's arrays */
+        for (char* p : work) dev_free(ctx, p);
+        if (pool) (void)hipFree(pool);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (own_stream_) stream_release(ctx, st);
+    }
+    int begin(int n_ev) {
+        if (n_ev > MAX_EV) return fail(OSMT_HIP_ERROR, "internal error: the %s marks %d trace events (at most %d)", who_, n_ev, (int)MAX_EV);
+        if (own_stream_) HIP_TRY(stream_acquire(ctx, &st));
+        if (trace)
+            for (; n_ev_ < n_ev; ++n_ev_) HIP_TRY(hipEventCreate(&ev[n_ev_]));
+        return OSMT_OK;
+    }
+    /* a work buffer of the layout's size (+ 256: the kernels' reads past a last element stay inside) */
+    int alloc(char** out, const pool_layout& pl, const char* what = nullptr) const {
+        const hipError_t e = dev_alloc(ctx, (void**)out, pl.size() + 256);
+        if (e == hipSuccess) return OSMT_OK;
+        *out = nullptr;
+        const int code = e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR;
+        if (!what) return fail(code, "hipMalloc(%zu) for the %s failed: %s", pl.size(), who_, hipGetErrorString(e));
+        return fail(code, "hipMalloc(%zu) for the %s (%s) failed: %s", pl.size(), who_, what, hipGetErrorString(e));
+    }
+    int alloc(int slot, const pool_layout& pl, const char* what = nullptr) {
+        if (slot < 0 || slot >= MAX_WORK) return fail(OSMT_HIP_ERROR, "internal error: the %s asks for work buffer %d (at most %d)", who_, slot, (int)MAX_WORK);
+        return alloc(&work[slot], pl, what);
+    }
+    int alloc_pool(const pool_layout& pl) {
+        const hipError_t e = hipMalloc((void**)&pool, pl.size());
+        if (e == hipSuccess) return OSMT_OK;
+        pool = nullptr;
+        return fail(e == hipErrorOutOfMemory ? OSMT_OOM : OSMT_HIP_ERROR, "hipMalloc(%zu) for the %s (table) failed: %s", pl.size(), who_, hipGetErrorString(e));
+    }
+    /* i, a, b: below the n_ev of begin(); without the trace there are no events and nothing is recorded */
+    hipError_t mark(int i) const { return i < n_ev_ ? hipEventRecord(ev[i], st) : trace ? hipErrorInvalidValue : hipSuccess; }
+    double us(int a, int b) const {
+        float ms = 0.f;
+        if (a < n_ev_ && b < n_ev_) (void)hipEventElapsedTime(&ms, ev[a], ev[b]);
+        return ms * 1e3;
+    }
+
+   private:
+    const char* who_;
+    bool own_stream_;
+    int n_ev_ = 0; /* events created */
+};
 
 }  // namespace osmt_host
 
