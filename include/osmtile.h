@@ -717,7 +717,9 @@ int osmt_scene_max_tile_ops(osmt_ctx* ctx, osmt_scene* scene, uint32_t* out_max_
  * byte for byte the display list that call builds from the batch osmt::styled_areas_of_tile (host/osmt_tilequery.hpp)
  * makes on the host.  The osm_ids filter of the reference is osmt_scene_build_tiles_filtered below. */
 
-#define OSMT_QUERY_MAX_TILE_CANDIDATES (1u << 20) /* way (or multipolygon) references gathered for ONE tile before dedup */
+/* way (or multipolygon) references gathered for ONE tile before dedup: from the z18 index every z18 reference of the
+ * neighbourhood, from a pyramid level (osmt_register_tile_pyramid) at most roughly 9 x its distinct entities */
+#define OSMT_QUERY_MAX_TILE_CANDIDATES (1u << 20)
 #define OSMT_QUERY_LDS_CANDIDATES 8192u           /* up to here a tile's candidates are sorted in LDS (32 KB of u32) */
 #define OSMT_BINDINGS_NONE 0xFFFFFFFFu
 
@@ -787,6 +789,51 @@ int osmt_scene_build_tiles(osmt_ctx* ctx, const osmt_tile_batch* batch, osmt_sce
  * from any other source, or when areas_cap is less than *n_areas. */
 int osmt_scene_read_styled_areas(osmt_ctx* ctx, osmt_scene* scene, osmt_styled_tile* tiles, osmt_styled_area* areas,
                                  size_t areas_cap, size_t* n_areas);
+
+/* ---- the tile index pyramid: coarser levels of the z18 index, built on the GPU ---------------------------------- */
+/* The geodata file holds the z18 level only, so a tile of zoom z gathers from 9 * 4^(18 - z) index tiles, and an entity is
+ * gathered once for every z18 tile of its bounding range inside the neighbourhood.  Level L (0 <= L <= 18, s = 18 - L) of a
+ * registered tile index has the tiles (x >> s, y >> s) of ALL its tiles (a tile with empty lists still gives its parent a
+ * tile), strictly ascending by (x, y), and per tile and kind the union of the lists of its z18 children, ascending and without
+ * repeats.  The kinds are ways, multipolygons and — iff a node index (osmt_register_node_index) is registered for the geodata
+ * id at the moment of the call — nodes.  Level 18 is the registered index with every list sorted and made unique.  The
+ * registered index itself stays as it is.
+ *
+ * The rectangle of a tile's neighbourhood has z18 bounds that are multiples of 2^(18 - L) for every L >= zoom, so it covers a
+ * z18 tile iff it covers the tile's parent at level L: gathered from level L, the tile's entity SET is the one gathered from
+ * z18, and everything behind the dedup sees the same input.  Every tile query of the library (osmt_scene_build_tiles[_filtered],
+ * both label builds, the tile server, the worker's tile requests) reads, per tile, the SMALLEST REGISTERED LEVEL >= THE TILE'S
+ * ZOOM, and the z18 index where there is none (the node query: the z18 node index unless that level has node lists).  With
+ * level z a tile gathers from at most 9 index tiles and names an entity at most 9 times.
+ *
+ * The limits are judged on what is gathered: OSMT_QUERY_MAX_TILE_CANDIDATES then bounds roughly 9 x the distinct entities of a
+ * neighbourhood instead of its z18 references.  A build that was accepted without a pyramid is accepted with one (a level never
+ * gathers more than z18 does), and a pyramid moves the refusal of a dense extract several zooms down — not to zoom 0: the
+ * distinct entities of a large extract exceed the limit by themselves.
+ *
+ * The levels are built on the device (csrc/osmt_tilepyramid.hip: an LSD radix sort of (parent tile, id) pairs per kind, each
+ * level from the next finer one that is being built, the finest from the registered index).  A level is one allocation that
+ * never moves and lives as long as the context; one pyramid per geodata id. */
+#define OSMT_PYRAMID_ALL_LEVELS 0x7FFFFu /* bits 0 .. 18 */
+/* OSMT_INVALID_ARG, naming the offender: a mask of 0 or with bits above 18 (these need no context); an unknown geodata id (a
+ * NULL `ctx` has none), one without a tile index, one that has a pyramid already. */
+int osmt_validate_tile_pyramid(uint32_t geodata_id, uint32_t level_mask, osmt_ctx* ctx);
+/* Builds the levels of `level_mask` (bit L = level L).  OSMT_UNSUPPORTED with the exact figure and the level: a pair total or a
+ * reference total that does not fit 32 bits.  A failed call registers nothing and leaves the context usable. */
+int osmt_register_tile_pyramid(osmt_ctx* ctx, uint32_t geodata_id, uint32_t level_mask);
+/* Which levels exist (0: no pyramid) and which of them have node lists. */
+int osmt_tile_pyramid_levels(osmt_ctx* ctx, uint32_t geodata_id, uint32_t* out_mask, uint32_t* out_node_mask);
+/* Inspection: one level copied back.  counts = { tiles, way refs, multipolygon refs, node refs } is always set; each output may
+ * be NULL (all NULL: ask for the sizes); caps = the capacities of { tile_xy (in tiles), ways, mps, nodes } (NULL: not checked), an
+ * output that is too small is OSMT_INVALID_ARG.  The offset arrays have tiles + 1 entries.  A level without node lists has 0
+ * node refs and writes node_off as zeros.  OSMT_INVALID_ARG for a level that was not registered. */
+int osmt_read_tile_pyramid(osmt_ctx* ctx, uint32_t geodata_id, uint32_t level, uint32_t* tile_xy, uint32_t* way_off, uint32_t* ways,
+                           uint32_t* mp_off, uint32_t* mps, uint32_t* node_off, uint32_t* nodes, const size_t caps[4], size_t counts[4]);
+/* Of the last completed tile query of this context: { (tile, column) items, way candidates, multipolygon candidates, node
+ * candidates } as gathered, before dedup — what tests and tools use to see that a level was read.  A query of ways and
+ * multipolygons (osmt_scene_build_tiles[_filtered], the area labels) reports 0 node candidates, the node query of the tile labels
+ * 0 way and multipolygon candidates. */
+int osmt_tile_query_stats(osmt_ctx* ctx, uint64_t stats[4]);
 
 /* ---- the osm_ids filter: a set of global ids as bit-planes on the GPU -------------------------------------------- */
 /* The one argument of get_entities_in_tile_with_neighbors(tile, osm_ids) (reader.rs:60,95-99): filter_entities_by_ids

@@ -35,6 +35,7 @@ MAX_FILL_GROUPS = 1 << 28  # fill groups (fill op x sub-tile of its window) of o
 QUERY_MAX_TILE_CANDIDATES = 1 << 20  # references of one kind osmt_scene_build_tiles gathers for one tile before dedup
 QUERY_LDS_CANDIDATES = 8192  # up to here a tile's candidates are sorted in LDS
 BINDINGS_NONE = 0xFFFFFFFF  # osmt_tile_batch.bindings_of_zoom: the zoom has no bindings
+PYRAMID_ALL_LEVELS = 0x7FFFF  # osmt_register_tile_pyramid: bits 0 .. 18, one per level
 ID_FILTER_NONE = 0xFFFFFFFF  # osmt_scene_build_tiles_filtered: no osm_ids filter (an EMPTY filter keeps nothing)
 TILE_LABELS_MAX = 65536  # (node, style) labels osmt_scene_build_tile_labels builds for one tile
 TEXT_NONE = 0xFFFFFFFF  # osmt_label_binding.text: the tag text_style.text names is absent on the node

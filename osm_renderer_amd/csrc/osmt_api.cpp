@@ -2062,6 +2062,7 @@ int register_tile_index_body(osmt_ctx* ctx, uint32_t geodata_id, const osmt_tile
     d.mps = (const uint32_t*)(pool + o_m);
     d.n_cols = (uint32_t)col_x.size();
     d.n_tiles = (uint32_t)n;
+    d.level = OSMT_MAX_ZOOM;
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->geodata[geodata_id].d_index) return fail(OSMT_INVALID_ARG, "geodata id %u has a tile index already (one per file)", geodata_id); /* another thread was first */
     ctx->geodata[geodata_id].d_index = pool;
@@ -2221,7 +2222,7 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, uint32_t fil
     if (n_tiles) {
         HIP_TRY(hipMemcpyAsync(w0 + o_q, b->tiles, n_tiles * sizeof(osmt_query_tile), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(w0 + o_bind, bind, sizeof bind, hipMemcpyHostToDevice, st));
-        P.ix = geo.ix;
+        tq_bind_levels(geo, false, geo.ix, P);
         P.geo_mp_off = geo.dev.mp_off;
         if (flt.on) P.keep_way = flt.way, P.keep_mp = flt.mp;
         P.bind = (const osmt_tq_bind_dev*)(w0 + o_bind);
@@ -2277,6 +2278,7 @@ int scene_build_tiles_body(osmt_ctx* ctx, const osmt_tile_batch* b, uint32_t fil
             return fail(OSMT_UNSUPPORTED, "tile batch gathers %llu references (%llu way + %llu multipolygon, > 2^32): split the batch",
                         tot[OSMT_TQ_WAYS] + tot[OSMT_TQ_MPS], tot[OSMT_TQ_WAYS], tot[OSMT_TQ_MPS]);
         n_way_cand = (size_t)tot[OSMT_TQ_WAYS], n_mp_cand = (size_t)tot[OSMT_TQ_MPS], n_cand = n_way_cand + n_mp_cand;
+        tq_stats_set(ctx, n_items, n_way_cand, n_mp_cand, 0);
         /* 3. gather, 4. sort, mark */
         pl = pool_layout();
         const size_t o_cand = pl.add(n_cand * 4), o_apos = pl.add((n_cand + 1) * 4), o_blk2 = pl.add((n_cand / 256 + 1) * 8);
@@ -3323,9 +3325,10 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         HIP_TRY(hipMemcpyAsync(w0 + o_bind, bind, sizeof bind, hipMemcpyHostToDevice, st));
         if (!icon_h.empty()) HIP_TRY(hipMemcpyAsync(w0 + o_ih, icon_h.data(), icon_h.size() * 4, hipMemcpyHostToDevice, st));
         /* the query over the node pools: the node lists as the "ways", no second kind */
-        Q.ix = geo.ix;
-        Q.ix.way_off = geo.d_node_off, Q.ix.ways = geo.d_node_refs;
-        Q.ix.mp_off = geo.d_zero_off, Q.ix.mps = geo.d_node_refs;
+        osmt_tq_index_dev z18 = geo.ix;
+        z18.way_off = geo.d_node_off, z18.ways = geo.d_node_refs;
+        z18.mp_off = geo.d_zero_off, z18.mps = geo.d_node_refs;
+        tq_bind_levels(geo, true, z18, Q);
         Q.q = (const osmt_query_tile*)(w0 + o_q);
         Q.n_tiles = (uint32_t)n_tiles;
         Q.span_c0 = (uint32_t*)(w0 + o_c0);
@@ -3370,6 +3373,7 @@ static int tile_node_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
         if (tq_tot[OSMT_TQ_WAYS] >= 0xFFFFFFFFull)
             return fail(OSMT_UNSUPPORTED, "tile labels: the batch gathers %llu node references (> 2^32): split the batch", tq_tot[OSMT_TQ_WAYS]);
         n_cand = (size_t)tq_tot[OSMT_TQ_WAYS];
+        tq_stats_set(ctx, n_items, 0, 0, n_cand);
         pl = pool_layout();
         const size_t o_cand = pl.add(n_cand * 4), o_lpos = pl.add((n_cand + 1) * 4), o_blk2 = pl.add((n_cand / 256 + 1) * 8);
         rc = wg.alloc(2, pl, "candidates");
@@ -4270,7 +4274,7 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     if (!icon_h.empty()) HIP_TRY(hipMemcpyAsync(w0 + o_ih, icon_h.data(), icon_h.size() * 4, hipMemcpyHostToDevice, st));
     if (n_anchors) HIP_TRY(hipMemcpyAsync(w0 + o_an, anchors, n_anchors * sizeof(osmt_area_anchor), hipMemcpyHostToDevice, st));
     /* 1. the query over the way and multipolygon pools, as osmt_scene_build_tiles runs it */
-    Q.ix = geo.ix;
+    tq_bind_levels(geo, false, geo.ix, Q);
     Q.geo_mp_off = geo.dev.mp_off;
     if (sc->tq_filter.on) Q.keep_way = sc->tq_filter.way, Q.keep_mp = sc->tq_filter.mp; /* the scene's filter: one per request (reader.rs:60) */
     Q.bind = (const osmt_tq_bind_dev*)(w0 + o_tqb);
@@ -4321,6 +4325,7 @@ static int tile_area_labels_build(osmt_ctx* ctx, osmt_scene* sc, const uint32_t*
     if (tq_tot[OSMT_TQ_WAYS] + tq_tot[OSMT_TQ_MPS] >= 0xFFFFFFFFull)
         return fail(OSMT_UNSUPPORTED, "area labels: the batch gathers %llu references (> 2^32): split the batch", tq_tot[OSMT_TQ_WAYS] + tq_tot[OSMT_TQ_MPS]);
     const size_t n_cand = (size_t)(tq_tot[OSMT_TQ_WAYS] + tq_tot[OSMT_TQ_MPS]);
+    tq_stats_set(ctx, n_items, tq_tot[OSMT_TQ_WAYS], tq_tot[OSMT_TQ_MPS], 0);
     pl = pool_layout();
     const size_t o_cand = pl.add(n_cand * 4), o_apos = pl.add((n_cand + 1) * 4), o_need = pl.add((n_cand + 1) * 4), o_ov = pl.add(n_cand * 4);
     const size_t o_blk2 = pl.add((n_cand / 256 + 1) * 8);

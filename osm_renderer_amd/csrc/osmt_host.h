@@ -1,7 +1,7 @@
 /*
  * osmt_host.h — what the host files of libosmtile.so (osmt_api.cpp, osmt_host_worker.cpp, osmt_host_multi.cpp,
- * osmt_host_tagstyle.cpp) share: the context and scene objects, guarded(), HIP_TRY, the two per-call holders table_upload and
- * call_work, and the declarations of what one file takes from another.  Internal: nothing declared here leaves the library
+ * osmt_host_tagstyle.cpp, osmt_host_pyramid.cpp) share: the context and scene objects, guarded(), HIP_TRY, the two per-call
+ * holders table_upload and call_work, and the declarations of what one file takes from another.  Internal: nothing declared here leaves the library
  * (hidden visibility).  Nothing here is a variable, a static function or an anonymous namespace: every function has ONE
  * definition, in the .cpp named above its declaration, and is documented there (inline here: guarded, align_up and the members
  * of the two holders); every thread-local and every cached setting stays private to its file.
@@ -148,6 +148,24 @@ struct osmt_ctx {
         void* d_node_index = nullptr;
         const uint32_t *d_node_off = nullptr, *d_node_refs = nullptr, *d_zero_off = nullptr; /* [ix.n_tiles + 1], pool, [ix.n_tiles + 1] zeros */
         const uint64_t* d_node_gid = nullptr;
+        /* its tile index pyramid (osmt_register_tile_pyramid, osmt_host_pyramid.cpp): at most one.  A level is a dev_alloc
+         * buffer that is never given back: it never moves and goes with the context's buffers */
+        struct pyramid_level {
+            osmt_tq_index_dev ix{};          /* as the tile query reads it */
+            const uint32_t* tile_x = nullptr; /* [ix.n_tiles], for osmt_read_tile_pyramid */
+            const uint32_t *node_off = nullptr, *nodes = nullptr, *zero_off = nullptr; /* node lists (or NULL), [ix.n_tiles + 1] zeros */
+            size_t n_way_refs = 0, n_mp_refs = 0, n_node_refs = 0;
+        };
+        struct pyramid_host {
+            uint32_t mask = 0, node_mask = 0;
+            pyramid_level level[OSMT_MAX_ZOOM + 1];
+            /* [OSMT_MAX_ZOOM + 1] each, device memory, written once at registration: the index a tile of each zoom reads — the
+             * smallest level >= the zoom, the z18 index where there is none; node_table (NULL without node lists): the same
+             * over the node lists */
+            const osmt_tq_index_dev *area_table = nullptr, *node_table = nullptr;
+        };
+        std::shared_ptr<const pyramid_host> pyramid;
+        bool pyramid_building = false; /* a registration is under way: a second one is refused */
         /* the Mercator factors of its nodes (osmt_register_node_mercator): at most one table, same rules */
         const double2* d_factors = nullptr; /* [n_nodes] */
         /* its tags (osmt_register_tags): at most one table, same rules */
@@ -254,6 +272,9 @@ struct osmt_ctx {
     uint64_t co_tile_stats[3] = {0, 0, 0}; /* requests, groups run, tiles of the largest group */
     /* osmt_label_positions_stats: requests / left the LDS tier / answered TOO_LARGE of the last completed call (cache_mu) */
     uint64_t pl_stats[3] = {0, 0, 0};
+    /* osmt_tile_query_stats: (tile, column) items and way / multipolygon / node candidates the last completed tile query
+     * gathered, before dedup (cache_mu) */
+    uint64_t tq_stats[4] = {0, 0, 0, 0};
 };
 
 struct osmt_scene {
@@ -391,6 +412,14 @@ int scene_build_tile_labels_all_body(osmt_ctx* ctx, osmt_scene* sc, const uint32
 int osmt_render_batch_labels_body(osmt_ctx* ctx, const osmt_batch* batch, const osmt_label_batch* labels, uint8_t* out_rgba,
                                   size_t stride, bool rgb = false, bool trusted = false, const osmt_glyph_label_batch* glabels = nullptr,
                                   const osmt_text_label_batch* tlabels = nullptr, const osmt_string_label_batch* slabels = nullptr);
+
+/* ---- osmt_host_pyramid.cpp ---- */
+/* The index a tile query reads per zoom: P.ix = z18 (the registered index in the form the query reads), and P.ixz = the
+ * resident table of the file's pyramid for the kind (nodes: the node query of the tile labels, which reads node lists as its
+ * "ways"), NULL where the file has no pyramid that serves the kind.  Nothing is uploaded. */
+void tq_bind_levels(const osmt_ctx::geodata_host& geo, bool nodes, const osmt_tq_index_dev& z18, osmt_tq_pass& P);
+/* what osmt_tile_query_stats reports from now on */
+void tq_stats_set(osmt_ctx* ctx, uint64_t items, uint64_t ways, uint64_t mps, uint64_t nodes);
 
 /* ---- osmt_host_multi.cpp ---- */
 void comm_destroy(osmt_ctx* ctx); /* ctx_teardown: the communicator and the words of the reductions go with the context */

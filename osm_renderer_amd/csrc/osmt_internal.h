@@ -486,6 +486,7 @@ struct osmt_tq_index_dev {
     const uint32_t* mp_off;    /* [n_tiles + 1] into mps */
     const uint32_t* mps;
     uint32_t n_cols, n_tiles;
+    uint32_t level; /* the zoom of its tiles: OSMT_MAX_ZOOM for the registered index, L for level L of its pyramid */
 };
 /* a registered bindings table: entity -> its style ids, in push order */
 struct osmt_tq_bind_dev {
@@ -504,8 +505,12 @@ enum {
     OSMT_TQ_N
 };
 struct osmt_tq_pass {
-    osmt_tq_index_dev ix;
-    const uint32_t* geo_mp_off;   /* osmt_geo_dev::mp_off: a multipolygon without polygons is dropped */
+    osmt_tq_index_dev ix; /* the registered z18 index: what every tile reads while ixz is NULL */
+    /* [OSMT_MAX_ZOOM + 1], device memory: the index a tile of each zoom reads — the smallest level >= the zoom of the geodata's
+     * pyramid (osmt_tilepyramid.hip), the z18 index where there is none.  NULL: no pyramid, every kernel reads `ix` and computes
+     * what it computed before there were levels.  A tile's items slice the pools of its zoom's index. */
+    const osmt_tq_index_dev* ixz;
+    const uint32_t* geo_mp_off;  /* osmt_geo_dev::mp_off: a multipolygon without polygons is dropped */
     const osmt_tq_bind_dev* bind; /* [OSMT_MAX_ZOOM + 1] the bindings of each zoom (zooms no tile has: never read) */
     const osmt_query_tile* q;     /* [n_tiles] */
     /* the planes of a registered id filter (osmt_idfilter.hip), bit `id` of word id / 32; NULL: no filter.  A candidate whose bit
@@ -544,6 +549,37 @@ hipError_t osmt_launch_tq_sort(const osmt_tq_pass& a, hipStream_t st);
 hipError_t osmt_launch_tq_mark(const osmt_tq_pass& a, hipStream_t st);
 /* k_tq_emit: the styled areas */
 hipError_t osmt_launch_tq_emit(const osmt_tq_pass& a, hipStream_t st);
+
+/* ---- the tile index pyramid (osmt_tilepyramid.hip) ------------------------------------------------------------- */
+#define OSMT_PYR_SORT_BLOCK 1024u /* pairs one workgroup of the sort takes */
+#define OSMT_PYR_DIGITS 9u        /* 8-bit digits of a pair: 0..3 of the id, 4..8 of the 36-bit key (x << 18 | y) */
+/* one kind's lists of the finer index a level is built from (the registered index, or a level): n_refs = off[n_tiles], read
+ * back by the host; a source of references has at least one tile, and a tile at least one column */
+struct osmt_pyr_src {
+    const uint32_t *col_x, *col_first, *tile_y, *off, *pool;
+    uint32_t n_cols, n_tiles, n_refs;
+    uint32_t shift; /* a parent coordinate = the source's >> shift */
+};
+/* k_pyr_pairs: key[r], id[r] of every reference r < s.n_refs */
+hipError_t osmt_launch_pyr_pairs(const osmt_pyr_src& s, unsigned long long* key, uint32_t* id, hipStream_t st);
+/* k_pyr_tilekeys: (parent key, 0) of every source tile */
+hipError_t osmt_launch_pyr_tilekeys(const osmt_pyr_src& s, unsigned long long* key, uint32_t* id, hipStream_t st);
+/* k_pyr_digits: hist[OSMT_PYR_DIGITS][256] of n pairs (zeroed here) */
+hipError_t osmt_launch_pyr_digits(const unsigned long long* key, const uint32_t* id, uint32_t n, uint32_t* hist, hipStream_t st);
+/* one stable pass over `digit`: k_pyr_hist -> osmt_tq_scan -> k_pyr_scatter.  counts: 256 * blocks + 1 words, blk: blocks + 1,
+ * with blocks = ceil(n / OSMT_PYR_SORT_BLOCK); tot: one word */
+hipError_t osmt_launch_pyr_pass(const unsigned long long* key, const uint32_t* id, uint32_t n, uint32_t digit, uint32_t* counts, unsigned long long* blk,
+                                unsigned long long* tot, unsigned long long* out_key, uint32_t* out_id, hipStream_t st);
+/* k_pyr_mark + scans over sorted pairs: pos[n + 1] numbers the distinct pairs (tot[0]); cpos[n + 1] (or NULL) the distinct x
+ * (tot[1]); blk: n / 256 + 1 words */
+hipError_t osmt_launch_pyr_mark(const unsigned long long* key, const uint32_t* id, uint32_t n, uint32_t* pos, uint32_t* cpos, unsigned long long* blk,
+                                unsigned long long* tot, hipStream_t st);
+/* the level's tiles and column directory from the tiles' job: tile_x, tile_y [n_tiles], col_x [n_cols], col_first [n_cols + 1] */
+hipError_t osmt_launch_pyr_emit_tiles(const unsigned long long* key, uint32_t n, const uint32_t* pos, const uint32_t* cpos, uint32_t n_tiles, uint32_t n_cols,
+                                      uint32_t* tile_x, uint32_t* tile_y, uint32_t* col_x, uint32_t* col_first, hipStream_t st);
+/* one kind's lists from its job: off [n_tiles + 1], pool [pos[n]]; tile_x, tile_y: what osmt_launch_pyr_emit_tiles wrote */
+hipError_t osmt_launch_pyr_emit_lists(const unsigned long long* key, const uint32_t* id, uint32_t n, const uint32_t* pos, const uint32_t* tile_x,
+                                      const uint32_t* tile_y, uint32_t n_tiles, uint32_t* off, uint32_t* pool, hipStream_t st);
 
 /* ---- the id filter (osmt_idfilter.hip) -------------------------------------------------------------------------- */
 /* k_idf_plane: bit e of `plane` = gid[e] is in ids[0 .. n_ids) (ascending, unique); plane has ceil(n / 64) 64-bit words and every

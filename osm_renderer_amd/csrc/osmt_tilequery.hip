@@ -5,6 +5,9 @@
  * thread, for a whole batch.  The result is the styled batch osmt_styled.hip starts from.  The host twin, and the yardstick of
  * the tests, is osmt::styled_areas_of_tile (host/osmt_tilequery.hpp).  gfx950 only.
  *
+ * A tile reads the registered z18 index, or — where the geodata id has a pyramid (osmt_tilepyramid.hip) — the smallest level L >=
+ * its zoom: osmt_tq_pass::ixz names the index of every zoom, and below "z18", "18" and "2^18" read "level L", "L" and "2^L".
+ *
  *   k_tq_span      one lane per requested tile: the rectangle of z18 tiles its 3 x 3 neighbourhood covers,
  *                  (x - 1) f <= tx <= (x + 2) f - 1 with f = 2^(18 - zoom), clipped to [0, 2^18) (every index coordinate is
  *                  below 2^18, so the reference's u32 wrap at the world's edge is this clip), and by two bisections in the
@@ -40,7 +43,6 @@ namespace {
 
 constexpr uint32_t WG = 256u;
 constexpr uint32_t SORT_WG = 1024u;
-constexpr uint32_t WORLD = 1u << OSMT_MAX_ZOOM; /* z18 tiles per axis */
 
 /* the first index in [lo, hi) whose value is >= v (hi if none) */
 __device__ __forceinline__ uint32_t lower_bound(const uint32_t* __restrict__ a, uint32_t lo, uint32_t hi, uint32_t v) {
@@ -89,12 +91,17 @@ __device__ __forceinline__ uint32_t tile_of_slot(const osmt_tq_pass& P, uint32_t
     return lo;
 }
 
-/* the clipped range of z18 coordinates the neighbourhood of coordinate c covers at `zoom` (c < 2^zoom: at most 2^19 before the clip) */
-__device__ __forceinline__ void clip_range(uint32_t c, uint32_t zoom, uint32_t& lo, uint32_t& hi) {
-    const uint32_t sh = OSMT_MAX_ZOOM - zoom;
+/* the index a tile of `zoom` reads: its pyramid level, or the registered z18 index */
+__device__ __forceinline__ osmt_tq_index_dev index_of(const osmt_tq_pass& P, uint32_t zoom) { return P.ixz ? P.ixz[zoom] : P.ix; }
+
+/* the clipped range of level-`level` coordinates the neighbourhood of coordinate c covers at `zoom` <= level (c < 2^zoom: at
+ * most 2^19 before the clip).  The rectangle's z18 bounds are multiples of 2^(18 - level), so the level's tiles it covers are
+ * exactly the parents of the z18 tiles it covers */
+__device__ __forceinline__ void clip_range(uint32_t c, uint32_t zoom, uint32_t level, uint32_t& lo, uint32_t& hi) {
+    const uint32_t sh = level - zoom, world = 1u << level;
     lo = c ? (c - 1u) << sh : 0u;
     hi = ((c + 2u) << sh) - 1u;
-    if (hi > WORLD - 1u) hi = WORLD - 1u;
+    if (hi > world - 1u) hi = world - 1u;
 }
 
 /* ---- scan: a[0 .. n) -> its exclusive scan, a[n] = the total (mod 2^32), *tot = the total ------------------------------ */
@@ -173,10 +180,11 @@ __global__ __launch_bounds__(256) void k_tq_span(osmt_tq_pass P) {
     }
     if (t >= P.n_tiles) return;
     const osmt_query_tile q = P.q[t];
+    const osmt_tq_index_dev ix = index_of(P, q.zoom);
     uint32_t xlo, xhi;
-    clip_range(q.x, q.zoom, xlo, xhi);
-    const uint32_t c0 = lower_bound(P.ix.col_x, 0u, P.ix.n_cols, xlo);
-    const uint32_t c1 = upper_bound(P.ix.col_x, c0, P.ix.n_cols, xhi);
+    clip_range(q.x, q.zoom, ix.level, xlo, xhi);
+    const uint32_t c0 = lower_bound(ix.col_x, 0u, ix.n_cols, xlo);
+    const uint32_t c1 = upper_bound(ix.col_x, c0, ix.n_cols, xhi);
     P.span_c0[t] = c0;
     P.item_base[t] = c1 - c0;
 }
@@ -187,17 +195,18 @@ __global__ __launch_bounds__(256) void k_tq_columns(osmt_tq_pass P) {
     const uint32_t t = owner_of(P.item_base, P.n_tiles, i);
     const uint32_t col = P.span_c0[t] + (i - P.item_base[t]);
     const osmt_query_tile q = P.q[t];
+    const osmt_tq_index_dev ix = index_of(P, q.zoom);
     uint32_t ylo, yhi;
-    clip_range(q.y, q.zoom, ylo, yhi);
-    const uint32_t a = P.ix.col_first[col], b = P.ix.col_first[col + 1u];
-    const uint32_t i0 = lower_bound(P.ix.tile_y, a, b, ylo);
-    const uint32_t i1 = upper_bound(P.ix.tile_y, i0, b, yhi);
-    const uint32_t w0 = P.ix.way_off[i0], m0 = P.ix.mp_off[i0];
+    clip_range(q.y, q.zoom, ix.level, ylo, yhi);
+    const uint32_t a = ix.col_first[col], b = ix.col_first[col + 1u];
+    const uint32_t i0 = lower_bound(ix.tile_y, a, b, ylo);
+    const uint32_t i1 = upper_bound(ix.tile_y, i0, b, yhi);
+    const uint32_t w0 = ix.way_off[i0], m0 = ix.mp_off[i0];
     P.item_tile[i] = t;
     P.item_wsrc[i] = w0;
     P.item_msrc[i] = m0;
-    P.wbase[i] = P.ix.way_off[i1] - w0;
-    P.mbase[i] = P.ix.mp_off[i1] - m0;
+    P.wbase[i] = ix.way_off[i1] - w0;
+    P.mbase[i] = ix.mp_off[i1] - m0;
 }
 
 /* a tile's slices are disjoint parts of a pool of fewer than 2^32 references: its counts are exact even where the bases wrapped */
@@ -228,7 +237,9 @@ __global__ __launch_bounds__(256) void k_tq_gather(osmt_tq_pass P) {
     const uint32_t tw = P.t_wbase[t], tm = P.t_mbase[t];
     const uint32_t src = (MP ? P.item_msrc : P.item_wsrc)[i] + (c - base[i]);
     const uint32_t dst = MP ? tw + tm + (P.t_wbase[t + 1u] - tw) + (c - tm) : tw + tm + (c - tw);
-    P.cand[dst] = (MP ? P.ix.mps : P.ix.ways)[src];
+    const uint32_t* pool = MP ? P.ix.mps : P.ix.ways; /* the pools the item slices: those of its tile's zoom */
+    if (P.ixz) pool = MP ? P.ixz[P.q[t].zoom].mps : P.ixz[P.q[t].zoom].ways;
+    P.cand[dst] = pool[src];
 }
 
 /* ---- sort -------------------------------------------------------------------------------------------------------- */

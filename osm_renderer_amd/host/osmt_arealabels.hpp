@@ -218,13 +218,13 @@ size_t area_labels_of_entities(const GeodataReader& reader, const OsmEntityIds& 
     return areas.size();
 }
 
-/* the same for tile (zoom, x, y), with the query */
+/* the same for tile (zoom, x, y), with the query; pyramid: the levels registered for the file (nullptr: none) */
 template <class Project, class Anchor>
 size_t area_labels_of_tile(const GeodataReader& reader, uint8_t zoom, uint32_t x, uint32_t y, uint32_t scale, const std::vector<LabelStyle>& styles,
                            const AreaLabelBindings& bindings, Project project, Anchor anchor, AreaLabels& out,
-                           const std::unordered_set<uint64_t>* osm_ids = nullptr) {
+                           const std::unordered_set<uint64_t>* osm_ids = nullptr, const TilePyramid* pyramid = nullptr) {
     /* osm_ids: the scene's id filter (nullptr: none); an entity it removes is never asked for an anchor */
-    return area_labels_of_entities(reader, reader.get_entities_in_tile_with_neighbors(zoom, x, y, osm_ids), scale, styles, bindings, project, anchor, out);
+    return area_labels_of_entities(reader, entities_of_tile(reader, zoom, x, y, osm_ids, pyramid), scale, styles, bindings, project, anchor, out);
 }
 
 }  // namespace osmt

@@ -26,6 +26,7 @@
 #include "../../include/osmtile.h"
 #include "osmt_geodata.hpp"
 #include "osmt_styled.hpp"
+#include "osmt_tilequery.hpp" /* TilePyramid, entities_of_tile */
 
 namespace osmt {
 
@@ -120,14 +121,16 @@ struct NodeLabels {
  * get_entities_in_tile_with_neighbors in ascending local id, each expanded by its bindings in push order
  * (Styler::style_entities), stably sorted by compare_styled_entities(.., for_labels = true), and per element what
  * Labeler::label_entity does with a node.  project(node, lat, lon) -> Point::from_node of that node for this tile and scale.
+ * pyramid: the levels registered for the file (nullptr: none) — the result does not depend on it.
  * Returns the number of labels appended. */
 template <class Project>
 size_t node_labels_of_tile(const GeodataReader& reader, uint8_t zoom, uint32_t x, uint32_t y, uint32_t scale, const std::vector<LabelStyle>& styles,
-                           const LabelBindings& bindings, Project project, NodeLabels& out, const std::unordered_set<uint64_t>* osm_ids = nullptr) {
+                           const LabelBindings& bindings, Project project, NodeLabels& out, const std::unordered_set<uint64_t>* osm_ids = nullptr,
+                           const TilePyramid* pyramid = nullptr) {
     struct Bound : Style { /* one pushed element: the keys sort_styled reads, and what it carries */
         osmt_label_binding b;
     };
-    const OsmEntityIds ids = reader.get_entities_in_tile_with_neighbors(zoom, x, y, osm_ids); /* osm_ids: the scene's id filter, nullptr: none */
+    const OsmEntityIds ids = entities_of_tile(reader, zoom, x, y, osm_ids, pyramid); /* osm_ids: the scene's id filter, nullptr: none */
     std::vector<Bound> bound;
     std::vector<uint32_t> node_of;
     for (uint32_t n : ids.nodes) {

@@ -6,13 +6,19 @@
  *                        pushes for it (styler.rs:128-160 memoises exactly this per (entity, zoom)), in push order;
  *   styled_areas_of_tile the host mirror of the device query: the (entity, style) pairs of one tile, written over
  *                        GeodataReader::get_entities_in_tile_with_neighbors (reader.rs:60-133) — it shares no code with the
- *                        kernels' rectangle arithmetic and is the yardstick of their tests.
+ *                        kernels' rectangle arithmetic and is the yardstick of their tests;
+ *   tile_pyramid_level   a level of the tile index pyramid (osmt_register_tile_pyramid) from its definition, a std::map of
+ *                        std::sets; TilePyramid and entities_of_tile are the mirror query over such levels.
  */
 #ifndef OSMT_TILEQUERY_HPP
 #define OSMT_TILEQUERY_HPP
 
+#include <algorithm>
 #include <cstdint>
+#include <map>
+#include <set>
 #include <stdexcept>
+#include <unordered_set>
 #include <utility>
 #include <vector>
 
@@ -87,13 +93,102 @@ class StyleBindings {
     osmt_style_bindings_desc desc_{};
 };
 
+/* One level of a tile index pyramid (osmt_register_tile_pyramid), in the layout osmt_read_tile_pyramid copies back. */
+struct TilePyramidLevel {
+    uint32_t level = 0;
+    bool has_nodes = false;
+    std::vector<uint32_t> tile_xy, way_off{0u}, ways, mp_off{0u}, mps, node_off{0u}, nodes;
+    size_t tile_count() const { return tile_xy.size() / 2; }
+};
+
+/* Level `level` of `index` from its definition: the tiles are the distinct (x >> s, y >> s), s = 18 - level, over ALL tiles of
+ * the index (a tile with empty lists still gives its parent a tile), ascending by (x, y); per tile and kind the union of its
+ * z18 children's lists, ascending and without repeats.  node_off / nodes: the node lists of the index's tiles
+ * (osmt_node_index_desc), nullptr: a level without node lists.  The yardstick of the device build. */
+inline TilePyramidLevel tile_pyramid_level(const osmt_tile_index_desc& index, uint32_t level, const uint32_t* node_off = nullptr,
+                                           const uint32_t* nodes = nullptr) {
+    if (level > OSMT_MAX_ZOOM) throw std::out_of_range("tile_pyramid_level: level above 18");
+    const uint32_t s = OSMT_MAX_ZOOM - level;
+    struct Lists {
+        std::set<uint32_t> kind[3];
+    };
+    std::map<std::pair<uint32_t, uint32_t>, Lists> tiles;
+    for (size_t i = 0; i < index.n_tiles; ++i) {
+        Lists& t = tiles[{index.tile_xy[2 * i] >> s, index.tile_xy[2 * i + 1] >> s}];
+        t.kind[0].insert(index.ways + index.way_off[i], index.ways + index.way_off[i + 1]);
+        t.kind[1].insert(index.multipolygons + index.multipolygon_off[i], index.multipolygons + index.multipolygon_off[i + 1]);
+        if (node_off) t.kind[2].insert(nodes + node_off[i], nodes + node_off[i + 1]);
+    }
+    TilePyramidLevel out;
+    out.level = level, out.has_nodes = node_off != nullptr;
+    for (const auto& kv : tiles) {
+        out.tile_xy.push_back(kv.first.first);
+        out.tile_xy.push_back(kv.first.second);
+        out.ways.insert(out.ways.end(), kv.second.kind[0].begin(), kv.second.kind[0].end());
+        out.mps.insert(out.mps.end(), kv.second.kind[1].begin(), kv.second.kind[1].end());
+        out.nodes.insert(out.nodes.end(), kv.second.kind[2].begin(), kv.second.kind[2].end());
+        out.way_off.push_back((uint32_t)out.ways.size());
+        out.mp_off.push_back((uint32_t)out.mps.size());
+        out.node_off.push_back((uint32_t)out.nodes.size());
+    }
+    return out;
+}
+
+/* The registered levels of one geodata file, by level. */
+struct TilePyramid {
+    std::map<uint32_t, TilePyramidLevel> levels;
+    /* the level a tile of `zoom` reads: the smallest registered one >= zoom; nullptr: none, the z18 index */
+    const TilePyramidLevel* level_for(uint32_t zoom) const {
+        const auto it = levels.lower_bound(zoom);
+        return it == levels.end() ? nullptr : &it->second;
+    }
+};
+
+/* get_entities_in_tile_with_neighbors as the device runs it with a pyramid: ways and multipolygons gathered from the level the
+ * tile reads, nodes too where that level has node lists (else from the z18 index), then the reference's sort, dedup, drop of
+ * multipolygons without polygons and id filter.  A level's tile belongs to the neighbourhood iff its ancestor at `zoom` is one
+ * of the 3 x 3 tiles around (x, y).  pyramid == nullptr, or no level >= zoom: the reader's own walk. */
+inline OsmEntityIds entities_of_tile(const GeodataReader& reader, uint8_t zoom, uint32_t x, uint32_t y, const std::unordered_set<uint64_t>* osm_ids = nullptr,
+                                     const TilePyramid* pyramid = nullptr) {
+    const TilePyramidLevel* lv = pyramid ? pyramid->level_for(zoom) : nullptr;
+    if (!lv) return reader.get_entities_in_tile_with_neighbors(zoom, x, y, osm_ids);
+    OsmEntityIds ids;
+    const uint32_t sh = lv->level - zoom;
+    for (size_t i = 0; i < lv->tile_count(); ++i) {
+        const int64_t ax = lv->tile_xy[2 * i] >> sh, ay = lv->tile_xy[2 * i + 1] >> sh;
+        if (ax < (int64_t)x - 1 || ax > (int64_t)x + 1 || ay < (int64_t)y - 1 || ay > (int64_t)y + 1) continue;
+        ids.ways.insert(ids.ways.end(), lv->ways.begin() + lv->way_off[i], lv->ways.begin() + lv->way_off[i + 1]);
+        ids.multipolygons.insert(ids.multipolygons.end(), lv->mps.begin() + lv->mp_off[i], lv->mps.begin() + lv->mp_off[i + 1]);
+        if (lv->has_nodes) ids.nodes.insert(ids.nodes.end(), lv->nodes.begin() + lv->node_off[i], lv->nodes.begin() + lv->node_off[i + 1]);
+    }
+    auto uniq = [](std::vector<uint32_t>& v) {
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+    };
+    uniq(ids.ways), uniq(ids.multipolygons), uniq(ids.nodes);
+    ids.multipolygons.erase(std::remove_if(ids.multipolygons.begin(), ids.multipolygons.end(),
+                                           [&](uint32_t m) { return reader.multipolygon_polygon_ids(m).second == 0; }),
+                            ids.multipolygons.end());
+    if (osm_ids) {
+        auto keep = [&](std::vector<uint32_t>& v, auto global_id) {
+            v.erase(std::remove_if(v.begin(), v.end(), [&](uint32_t e) { return osm_ids->count(global_id(e)) == 0; }), v.end());
+        };
+        keep(ids.nodes, [&](uint32_t e) { return reader.node_global_id(e); });
+        keep(ids.ways, [&](uint32_t e) { return reader.way_global_id(e); });
+        keep(ids.multipolygons, [&](uint32_t e) { return reader.multipolygon_global_id(e); });
+    }
+    if (!lv->has_nodes) ids.nodes = reader.get_entities_in_tile_with_neighbors(zoom, x, y, osm_ids).nodes;
+    return ids;
+}
+
 /* What osmt_scene_build_tiles derives for tile (zoom, x, y): every way of get_entities_in_tile_with_neighbors in ascending
  * local id, then every multipolygon (those without polygons are dropped there), each repeated once per bound style in
  * binding order.  An entity without a bound style contributes nothing.  osm_ids: the filter of
- * osmt_scene_build_tiles_filtered (nullptr: none), applied where the reference applies it: last, inside the query. */
+ * osmt_scene_build_tiles_filtered (nullptr: none), applied where the reference applies it: last, inside the query.
+ * pyramid: the levels registered for the file (nullptr: none) — the result does not depend on it. */
 inline std::vector<osmt_styled_area> styled_areas_of_tile(const GeodataReader& reader, const StyleBindings& bindings, uint8_t zoom, uint32_t x, uint32_t y,
-                                                          const std::unordered_set<uint64_t>* osm_ids = nullptr) {
-    const OsmEntityIds ids = reader.get_entities_in_tile_with_neighbors(zoom, x, y, osm_ids);
+                                                          const std::unordered_set<uint64_t>* osm_ids = nullptr, const TilePyramid* pyramid = nullptr) {
+    const OsmEntityIds ids = entities_of_tile(reader, zoom, x, y, osm_ids, pyramid);
     std::vector<osmt_styled_area> out;
     for (uint32_t w : ids.ways) {
         const auto st = bindings.way(w);

@@ -545,6 +545,39 @@ class Context:
         d = index.as_desc()
         check(load().osmt_register_tile_index(self._h, geodata_id, C.byref(d)))
 
+    def register_tile_pyramid(self, geodata_id, level_mask=abi.PYRAMID_ALL_LEVELS):
+        """osmt_register_tile_pyramid: builds the levels of level_mask (bit L = level L) of the file's tile index on the device.
+        A tile of zoom z then reads the smallest registered level >= z.  One pyramid per file."""
+        check(load().osmt_register_tile_pyramid(self._h, geodata_id, level_mask))
+
+    def tile_pyramid_levels(self, geodata_id):
+        """osmt_tile_pyramid_levels: (mask of the levels that exist, mask of those with node lists); (0, 0) without a pyramid."""
+        m, n = C.c_uint32(), C.c_uint32()
+        check(load().osmt_tile_pyramid_levels(self._h, geodata_id, C.byref(m), C.byref(n)))
+        return m.value, n.value
+
+    def read_tile_pyramid(self, geodata_id, level):
+        """osmt_read_tile_pyramid: one level as a dict of uint32 arrays — tile_xy [n][2], way_off, ways, mp_off, mps, node_off,
+        nodes (a level without node lists: node_off of zeros, no nodes)."""
+        L = load()
+        counts = (C.c_size_t * 4)()
+        check(L.osmt_read_tile_pyramid(self._h, geodata_id, level, None, None, None, None, None, None, None, None, counts))
+        n, nw, nm, nn = (int(c) for c in counts)
+        out = {"tile_xy": np.zeros((n, 2), np.uint32), "way_off": np.zeros(n + 1, np.uint32), "ways": np.zeros(nw, np.uint32),
+               "mp_off": np.zeros(n + 1, np.uint32), "mps": np.zeros(nm, np.uint32), "node_off": np.zeros(n + 1, np.uint32),
+               "nodes": np.zeros(nn, np.uint32)}
+        caps = (C.c_size_t * 4)(n, nw, nm, nn)
+        check(L.osmt_read_tile_pyramid(self._h, geodata_id, level, *(out[k].ctypes.data for k in ("tile_xy", "way_off", "ways", "mp_off", "mps", "node_off", "nodes")),
+                                       caps, counts))
+        return out
+
+    def tile_query_stats(self):
+        """osmt_tile_query_stats: ((tile, column) items, way, multipolygon, node candidates) the last completed tile query of this
+        context gathered, before dedup"""
+        st = (C.c_uint64 * 4)()
+        check(load().osmt_tile_query_stats(self._h, st))
+        return tuple(int(v) for v in st)
+
     def register_tags(self, geodata_id, tags):
         """osmt_register_tags: the tags of a registered geodata file (selmatch.Tags or a ctypes osmt_tags_desc)."""
         d = tags.as_desc() if hasattr(tags, "as_desc") else tags
