@@ -835,6 +835,44 @@ int osmt_read_tile_pyramid(osmt_ctx* ctx, uint32_t geodata_id, uint32_t level, u
  * 0 way and multipolygon candidates. */
 int osmt_tile_query_stats(osmt_ctx* ctx, uint64_t stats[4]);
 
+/* ---- the z18 tile index itself, built on the GPU from nodes, ways and multipolygons -------------------------------- */
+/* get_tile_references (saver.rs:167-226) over the registered geodata and its registered Mercator factors
+ * (osmt_register_node_mercator), for a caller whose geodata does not come from the importer's file:
+ *
+ *   node tile    with the factors (fx, fy) of a node, x = (u32)(fx * 2^26) >> 8, y = (u32)(fy * 2^26) >> 8 (tile.rs:30-38: the
+ *                product with a power of two is exact, `as u32` truncates, / 256 is the shift).  Every node is listed in its tile.
+ *   ways         a way with at least one node is listed in every tile of the inclusive rectangle [min x, max x] x [min y, max y]
+ *                over its nodes' tiles, the tiles none of its nodes touches included; a way without nodes is listed nowhere.
+ *   multipolygons the same over all nodes of all their polygons; a polygon without nodes contributes nothing, a multipolygon
+ *                without polygons or with empty polygons only is listed nowhere.
+ *   tiles        a tile exists iff a node, a way or a multipolygon is listed in it; tiles ascend by (x, y), every list ascends
+ *                without repeats (the BTreeMap / BTreeSet order the file holds).
+ *   factor 1.0   gives coordinate 2^18, which osmt_validate_tile_index refuses and no query reaches: the build is refused with
+ *                OSMT_UNSUPPORTED, naming the lowest such node and whether it is its x or its y factor.  Never guessed, never
+ *                clamped.
+ *
+ * The result equals the importer's index FOR THE REGISTERED FACTORS.  Reproducing a given file's index bit for bit needs factors
+ * computed the way the importer's libm computes them: a node whose factor lies within an ulp of a tile edge can land in the
+ * neighbouring tile under another tan / log.
+ *
+ * The built index is the geodata id's tile index: tile queries, both label builds, the pyramid, the id filter, the tile server and
+ * the worker entries read it as they read a registered one.  One tile index per file, registered or built. */
+/* OSMT_INVALID_ARG, naming the offender: an unknown geodata id (a NULL `ctx` has none), one without Mercator factors, one that
+ * has a tile index already; node_ids non-NULL with n_nodes different from the geodata's, or while a node index is registered. */
+int osmt_validate_tile_index_build(uint32_t geodata_id, const uint64_t* node_ids, size_t n_nodes, osmt_ctx* ctx);
+/* Builds and installs the index.  The node lists are always built; with node_ids ([n_nodes] the nodes' global ids) the node index
+ * is registered in the same call as osmt_register_node_index would leave it, with NULL none is (osmt_read_tile_index gives the
+ * lists, osmt_register_node_index takes them later).  OSMT_UNSUPPORTED with the exact figure, decided before the pairs get a
+ * buffer: a way, multipolygon or node reference total, or a total of tile keys (the kinds' distinct tiles, summed), that does
+ * not fit 32 bits (>= 2^32 - 1); a factor of exactly 1.0.  A second build, or two threads building one id: one OSMT_OK, the other
+ * OSMT_INVALID_ARG.  A failed call registers nothing, gives its buffers back and leaves the context usable. */
+int osmt_build_tile_index(osmt_ctx* ctx, uint32_t geodata_id, const uint64_t* node_ids, size_t n_nodes);
+/* Inspection, in the shape of osmt_read_tile_pyramid: the geodata id's tile index, built or registered (a registered one in its
+ * registered order).  The node lists come back if a node index is registered or the index was built; otherwise there are 0 node
+ * refs and node_off is zeros.  OSMT_INVALID_ARG without a tile index. */
+int osmt_read_tile_index(osmt_ctx* ctx, uint32_t geodata_id, uint32_t* tile_xy, uint32_t* way_off, uint32_t* ways, uint32_t* mp_off,
+                         uint32_t* mps, uint32_t* node_off, uint32_t* nodes, const size_t caps[4], size_t counts[4]);
+
 /* ---- the osm_ids filter: a set of global ids as bit-planes on the GPU -------------------------------------------- */
 /* The one argument of get_entities_in_tile_with_neighbors(tile, osm_ids) (reader.rs:60,95-99): filter_entities_by_ids
  * (reader.rs:254-262) keeps an entity iff its global_id() is in the set.  ONE set serves nodes, ways and multipolygons alike

@@ -417,8 +417,8 @@ void ctx_teardown(osmt_ctx* ctx) {
     for (auto& g : ctx->geodata)
     {
         if (g.d_pool) (void)hipFree(g.d_pool);
-        if (g.d_index) (void)hipFree(g.d_index);
-        if (g.d_node_index) (void)hipFree(g.d_node_index);
+        if (g.d_index && !g.index_built) (void)hipFree(g.d_index); /* a built index is one of ctx->cache's buffers */
+        if (g.d_node_index && !g.node_index_built) (void)hipFree(g.d_node_index);
         if (g.d_factors) (void)hipFree((void*)g.d_factors);
         if (g.d_tags) (void)hipFree(g.d_tags);
     }
@@ -1751,6 +1751,7 @@ int register_geodata_body(osmt_ctx* ctx, const osmt_geodata_desc* g, uint32_t* o
     if (up.done() != OSMT_OK) return up.done();
     osmt_ctx::geodata_host h;
     h.n_nodes = g->n_nodes, h.n_ways = g->n_ways, h.n_mps = g->n_multipolygons;
+    h.n_polys = g->n_polygons, h.n_way_nodes = g->n_way_nodes, h.n_poly_nodes = g->n_polygon_nodes, h.n_mp_polys = g->n_multipolygon_polygons;
     h.d_pool = pool;
     h.dev.nodes = (const double*)(pool + o_nodes);
     h.dev.way_gid = (const uint64_t*)(pool + o_wgid);

@@ -139,6 +139,7 @@ struct osmt_ctx {
      * registration, that never moves and lives as long as the context — a built scene's node table points into it */
     struct geodata_host {
         size_t n_nodes = 0, n_ways = 0, n_mps = 0;
+        size_t n_polys = 0, n_way_nodes = 0, n_poly_nodes = 0, n_mp_polys = 0; /* the other lengths of dev's arrays (osmt_build_tile_index) */
         void* d_pool = nullptr;
         osmt_geo_dev dev{};
         /* its z18 tile index (osmt_register_tile_index): at most one, an allocation of its own under the same rules */
@@ -148,6 +149,13 @@ struct osmt_ctx {
         void* d_node_index = nullptr;
         const uint32_t *d_node_off = nullptr, *d_node_refs = nullptr, *d_zero_off = nullptr; /* [ix.n_tiles + 1], pool, [ix.n_tiles + 1] zeros */
         const uint64_t* d_node_gid = nullptr;
+        /* an index built on the device (osmt_build_tile_index, osmt_host_pyramid.cpp): d_index, and d_node_index where the build
+         * registered the node index too, then name ONE dev_alloc buffer that is never given back and goes with the context's
+         * buffers — the teardown frees only what a registration allocated itself.  The build always makes the node lists:
+         * built_node_off / built_nodes ([ix.n_tiles + 1], pool) serve osmt_read_tile_index where no node index is registered */
+        bool index_built = false, node_index_built = false;
+        bool index_building = false; /* a build is under way: a second one is refused */
+        const uint32_t *built_node_off = nullptr, *built_nodes = nullptr;
         /* its tile index pyramid (osmt_register_tile_pyramid, osmt_host_pyramid.cpp): at most one.  A level is a dev_alloc
          * buffer that is never given back: it never moves and goes with the context's buffers */
         struct pyramid_level {

@@ -581,6 +581,38 @@ hipError_t osmt_launch_pyr_emit_tiles(const unsigned long long* key, uint32_t n,
 hipError_t osmt_launch_pyr_emit_lists(const unsigned long long* key, const uint32_t* id, uint32_t n, const uint32_t* pos, const uint32_t* tile_x,
                                       const uint32_t* tile_y, uint32_t n_tiles, uint32_t* off, uint32_t* pool, hipStream_t st);
 
+/* ---- the z18 tile index built from geometry (osmt_tileindex.hip) ------------------------------------------------- */
+/* words of osmt_tix_pass::words */
+enum {
+    OSMT_TIX_OFFENDER = 0, /* the lowest 2 * node + axis (0: x, 1: y) whose factor is exactly 1.0; none: all ones */
+    OSMT_TIX_WAY_REFS,     /* the exact (tile, way) total */
+    OSMT_TIX_MP_REFS,      /* the exact (tile, multipolygon) total */
+    OSMT_TIX_SCAN,         /* the total of the scan under way (saturated counts: not read back) */
+    OSMT_TIX_WORDS
+};
+struct osmt_tix_pass {
+    osmt_geo_dev geo;
+    const double2* factors; /* [n_nodes] */
+    uint32_t n_nodes, n_ways, n_polys, n_mps, n_way_nodes, n_poly_nodes, n_mp_polys;
+    uint32_t *tx, *ty;                  /* [n_nodes] the nodes' tiles */
+    uint4 *way_box, *poly_box, *mp_box; /* {min_x, max_x, min_y, max_y}; {~0, 0, ~0, 0}: no node */
+    uint32_t *way_cnt, *mp_cnt;         /* [n + 1] tiles of the entity (saturated), then their exclusive scan */
+    unsigned long long* blk;            /* max(n_ways, n_mps) / 256 + 1 words */
+    unsigned long long* words;          /* [OSMT_TIX_WORDS] */
+};
+/* k_tix_init, k_tix_node_tiles, k_tix_bbox (ways, polygons), k_tix_mp_bbox, k_tix_count + scan (ways, multipolygons):
+ * everything up to the words the host reads back */
+hipError_t osmt_launch_tix_boxes(const osmt_tix_pass& a, hipStream_t st);
+/* k_tix_pairs: the n_refs = off[n_ent] (key, entity) pairs of one kind */
+hipError_t osmt_launch_tix_pairs(const uint32_t* off, uint32_t n_ent, const uint4* box, uint32_t n_refs, unsigned long long* key, uint32_t* id, hipStream_t st);
+/* k_tix_node_pairs: (key of the node's tile, node) */
+hipError_t osmt_launch_tix_node_pairs(const uint32_t* tx, const uint32_t* ty, uint32_t n, unsigned long long* key, uint32_t* id, hipStream_t st);
+/* k_tix_keymark + scan over n sorted pairs: head[n + 1] numbers the distinct keys, *tot their count; blk: n / 256 + 1 words */
+hipError_t osmt_launch_tix_keymark(const unsigned long long* key, uint32_t n, uint32_t* head, unsigned long long* blk, unsigned long long* tot, hipStream_t st);
+/* k_tix_keycompact: (distinct key, 0) into out_key / out_id [head[n]] */
+hipError_t osmt_launch_tix_keycompact(const unsigned long long* key, uint32_t n, const uint32_t* head, unsigned long long* out_key, uint32_t* out_id,
+                                      hipStream_t st);
+
 /* ---- the id filter (osmt_idfilter.hip) -------------------------------------------------------------------------- */
 /* k_idf_plane: bit e of `plane` = gid[e] is in ids[0 .. n_ids) (ascending, unique); plane has ceil(n / 64) 64-bit words and every
  * one of them is written; n == 0 launches nothing */

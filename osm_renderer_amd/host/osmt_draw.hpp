@@ -132,6 +132,13 @@ class Context {
      * osmt_tilelabels.hpp), the label half of the Style records, and a table node -> (label style, text) per zoom range
      * (osmt::LabelBindings there) */
     void register_node_index(uint32_t geodata_id, const osmt_node_index_desc& desc) { check(osmt_register_node_index(ctx_, geodata_id, &desc)); }
+    /* the z18 tile index built on the device from the registered Mercator factors (osmt_build_tile_index); node_ids: the nodes'
+     * global ids, one per node of the geodata, registers the node index too; nullptr: the tile index alone */
+    void build_tile_index(uint32_t geodata_id, const std::vector<uint64_t>* node_ids = nullptr) {
+        static const uint64_t none = 0; /* a file of 0 nodes still asks for the node index with a non-NULL pointer */
+        const uint64_t* ids = !node_ids ? nullptr : node_ids->empty() ? &none : node_ids->data();
+        check(osmt_build_tile_index(ctx_, geodata_id, ids, node_ids ? node_ids->size() : 0));
+    }
     uint32_t register_label_styles(const std::vector<osmt_label_style_rec>& styles) {
         uint32_t first = 0;
         check(osmt_register_label_styles(ctx_, styles.data(), styles.size(), &first));

@@ -134,6 +134,96 @@ inline TilePyramidLevel tile_pyramid_level(const osmt_tile_index_desc& index, ui
     return out;
 }
 
+/* The z18 tile index of a geodata file from its definition (get_tile_references, saver.rs:167-226, with max_zoom_tile of
+ * tile.rs:30-38 over the registered Mercator factors): the host twin and yardstick of osmt_build_tile_index.  The vectors are
+ * what an osmt_tile_index_desc and an osmt_node_index_desc point to (index_desc, node_desc: valid as long as this object lives
+ * and is not copied from; node_desc.node_ids is the caller's). */
+struct BuiltTileIndex {
+    std::vector<uint32_t> tile_xy, way_off{0u}, ways, mp_off{0u}, mps, node_off{0u}, nodes;
+    /* a factor of exactly 1.0 (coordinate 2^18): the build is refused and the arrays are empty */
+    bool refused = false;
+    size_t refused_node = 0;
+    int refused_axis = 0; /* 0: x, 1: y */
+    size_t tile_count() const { return tile_xy.size() / 2; }
+    osmt_tile_index_desc index_desc() const {
+        osmt_tile_index_desc d{};
+        d.tile_xy = tile_xy.data(), d.n_tiles = tile_count();
+        d.way_off = way_off.data(), d.ways = ways.data(), d.n_way_refs = ways.size();
+        d.multipolygon_off = mp_off.data(), d.multipolygons = mps.data(), d.n_multipolygon_refs = mps.size();
+        return d;
+    }
+    osmt_node_index_desc node_desc(const uint64_t* node_ids, size_t n_nodes) const {
+        osmt_node_index_desc d{};
+        d.node_ids = node_ids, d.n_nodes = n_nodes;
+        d.node_off = node_off.data(), d.nodes = nodes.data(), d.n_node_refs = nodes.size();
+        return d;
+    }
+};
+
+/* the z18 tile coordinate of a Mercator factor in [0, 1]: (u32)(f * 2^26) / 256 — the product is exact, the conversion truncates */
+inline uint32_t max_zoom_coordinate(double factor) {
+    if (!(factor >= 0.0) || !(factor <= 1.0)) throw std::out_of_range("max_zoom_coordinate: factor is not finite or outside [0, 1]"); /* what osmt_register_node_mercator refuses */
+    return (uint32_t)(factor * 67108864.0) >> 8;
+}
+
+/* factors: [n_nodes][2] as osmt_register_node_mercator takes them (osmt::mercator_factors) */
+inline BuiltTileIndex tile_index_of(const osmt_geodata_desc& g, const double* factors) {
+    BuiltTileIndex out;
+    const uint32_t world = 1u << OSMT_MAX_ZOOM;
+    std::vector<std::pair<uint32_t, uint32_t>> tile(g.n_nodes);
+    for (size_t i = 0; i < g.n_nodes; ++i) {
+        tile[i] = {max_zoom_coordinate(factors[2 * i]), max_zoom_coordinate(factors[2 * i + 1])};
+        if (tile[i].first >= world || tile[i].second >= world) {
+            out.refused = true, out.refused_node = i, out.refused_axis = tile[i].first >= world ? 0 : 1;
+            return out;
+        }
+    }
+    struct Lists {
+        std::set<uint32_t> kind[3]; /* ways, multipolygons, nodes */
+    };
+    std::map<std::pair<uint32_t, uint32_t>, Lists> tiles;
+    for (size_t i = 0; i < g.n_nodes; ++i) tiles[tile[i]].kind[2].insert((uint32_t)i);
+    struct Box {
+        uint32_t x0 = ~0u, x1 = 0u, y0 = ~0u, y1 = 0u;
+        bool any = false;
+        void add(const std::pair<uint32_t, uint32_t>& t) {
+            x0 = std::min(x0, t.first), x1 = std::max(x1, t.first), y0 = std::min(y0, t.second), y1 = std::max(y1, t.second), any = true;
+        }
+    };
+    auto spread = [&](const Box& b, int kind, uint32_t id) {
+        if (!b.any) return;
+        for (uint32_t x = b.x0; x <= b.x1; ++x)
+            for (uint32_t y = b.y0; y <= b.y1; ++y) tiles[{x, y}].kind[kind].insert(id);
+    };
+    for (size_t w = 0; w < g.n_ways; ++w) {
+        Box b;
+        for (uint32_t k = g.way_node_off[w]; k < g.way_node_off[w + 1]; ++k) b.add(tile[g.way_nodes[k]]);
+        spread(b, 0, (uint32_t)w);
+    }
+    for (size_t m = 0; m < g.n_multipolygons; ++m) {
+        Box b;
+        for (uint32_t k = g.multipolygon_polygon_off[m]; k < g.multipolygon_polygon_off[m + 1]; ++k) {
+            const uint32_t p = g.multipolygon_polygons[k];
+            for (uint32_t q = g.polygon_node_off[p]; q < g.polygon_node_off[p + 1]; ++q) b.add(tile[g.polygon_nodes[q]]);
+        }
+        spread(b, 1, (uint32_t)m);
+    }
+    for (const auto& kv : tiles) {
+        out.tile_xy.push_back(kv.first.first);
+        out.tile_xy.push_back(kv.first.second);
+        out.ways.insert(out.ways.end(), kv.second.kind[0].begin(), kv.second.kind[0].end());
+        out.mps.insert(out.mps.end(), kv.second.kind[1].begin(), kv.second.kind[1].end());
+        out.nodes.insert(out.nodes.end(), kv.second.kind[2].begin(), kv.second.kind[2].end());
+        if (out.ways.size() >= 0xFFFFFFFFull || out.mps.size() >= 0xFFFFFFFFull) throw std::runtime_error("tile_index_of: too large for 32-bit offsets");
+        out.way_off.push_back((uint32_t)out.ways.size());
+        out.mp_off.push_back((uint32_t)out.mps.size());
+        out.node_off.push_back((uint32_t)out.nodes.size());
+    }
+    return out;
+}
+
+inline BuiltTileIndex tile_index_of(const GeodataDesc& g, const double* factors) { return tile_index_of(g.desc, factors); }
+
 /* The registered levels of one geodata file, by level. */
 struct TilePyramid {
     std::map<uint32_t, TilePyramidLevel> levels;

@@ -57,6 +57,7 @@ EXPORTS = [
     "osmt_validate_tile_server", "osmt_tile_server_create", "osmt_tile_server_free", "osmt_tile_server_render_png",
     "osmt_last_declined_anchors", "osmt_worker_render_tile_png", "osmt_worker_tile_stats",
     "osmt_validate_tile_pyramid", "osmt_register_tile_pyramid", "osmt_tile_pyramid_levels", "osmt_read_tile_pyramid", "osmt_tile_query_stats",
+    "osmt_validate_tile_index_build", "osmt_build_tile_index", "osmt_read_tile_index",
 ]
 
 
@@ -262,6 +263,11 @@ def load():
         L.osmt_tile_pyramid_levels.argtypes = [vp, C.c_uint32, u32p, u32p]
         L.osmt_read_tile_pyramid.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, sz, sz]
         L.osmt_tile_query_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "osmt_build_tile_index"):  # absent only from older variant builds loaded through OSMT_LIB
+        u64p, sz = C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)
+        L.osmt_validate_tile_index_build.argtypes = [C.c_uint32, u64p, C.c_size_t, vp]
+        L.osmt_build_tile_index.argtypes = [vp, C.c_uint32, u64p, C.c_size_t]
+        L.osmt_read_tile_index.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, sz, sz]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

@@ -571,6 +571,34 @@ class Context:
                                        caps, counts))
         return out
 
+    def build_tile_index(self, geodata_id, node_ids=None):
+        """osmt_build_tile_index: the file's z18 tile index built on the device from its registered Mercator factors
+        (register_node_mercator) and its topology, installed as register_tile_index would install it.  node_ids: the nodes'
+        global ids (uint64, one per node) registers the node index in the same call; None: the tile index alone."""
+        ids, n = None, 0
+        if node_ids is not None:
+            a = np.ascontiguousarray(node_ids, dtype=np.uint64).reshape(-1)
+            n = len(a)
+            keep = a if n else np.zeros(1, np.uint64)  # never empty: a pointer to pass
+            ids = keep.ctypes.data_as(C.POINTER(C.c_uint64))
+        check(load().osmt_validate_tile_index_build(geodata_id, ids, n, self._h))
+        check(load().osmt_build_tile_index(self._h, geodata_id, ids, n))
+
+    def read_tile_index(self, geodata_id):
+        """osmt_read_tile_index: the file's z18 tile index, built or registered, as a dict of uint32 arrays — tile_xy [n][2],
+        way_off, ways, mp_off, mps, node_off, nodes (no node index and not built: node_off of zeros, no nodes)."""
+        L = load()
+        counts = (C.c_size_t * 4)()
+        check(L.osmt_read_tile_index(self._h, geodata_id, None, None, None, None, None, None, None, None, counts))
+        n, nw, nm, nn = (int(c) for c in counts)
+        out = {"tile_xy": np.zeros((n, 2), np.uint32), "way_off": np.zeros(n + 1, np.uint32), "ways": np.zeros(nw, np.uint32),
+               "mp_off": np.zeros(n + 1, np.uint32), "mps": np.zeros(nm, np.uint32), "node_off": np.zeros(n + 1, np.uint32),
+               "nodes": np.zeros(nn, np.uint32)}
+        caps = (C.c_size_t * 4)(n, nw, nm, nn)
+        check(L.osmt_read_tile_index(self._h, geodata_id, *(out[k].ctypes.data for k in ("tile_xy", "way_off", "ways", "mp_off", "mps", "node_off", "nodes")),
+                                     caps, counts))
+        return out
+
     def tile_query_stats(self):
         """osmt_tile_query_stats: ((tile, column) items, way, multipolygon, node candidates) the last completed tile query of this
         context gathered, before dedup"""
