@@ -873,6 +873,72 @@ int osmt_build_tile_index(osmt_ctx* ctx, uint32_t geodata_id, const uint64_t* no
 int osmt_read_tile_index(osmt_ctx* ctx, uint32_t geodata_id, uint32_t* tile_xy, uint32_t* way_off, uint32_t* ways, uint32_t* mp_off,
                          uint32_t* mps, uint32_t* node_off, uint32_t* nodes, const size_t caps[4], size_t counts[4]);
 
+/* ---- multipolygon rings assembled on the GPU from relations' member ways ------------------------------------------ */
+/* find_polygons_in_multipolygon (find_polygons.rs, called from importer.rs:278-293 over RawRelation::to_segments,
+ * importer.rs:516-537), for a caller whose geodata does not come from the importer's file: OSM relations with `inner` / `outer`
+ * member ways in, the polygon and multipolygon arrays of osmt_geodata_desc out.  Per relation, in relation order:
+ *
+ *   segments     for every way reference in order and every idx in 1 .. len(way): (node[idx - 1], node[idx], role).  Ways come in
+ *                as they are stored (postprocess_node_refs is not part of this).
+ *   connections  per POSITION — the bits of (lat, lon): -0.0 and 0.0 are two vertices, two NaNs of equal bits are one — the list of
+ *                (other side, segment), filled for idx ascending with node1's entry, then node2's: the order inside a list is
+ *                2 * idx + side.  A segment whose two positions are equal stands twice on one list.
+ *   rings        for start ascending over the segments still available: first = node1's position, walk from node2's.  Each
+ *                step takes the FIRST entry of the current position's list that has the start segment's role, is available, and
+ *                whose other side is no vertex this ring has used, unless it is `first`.  The ring closes when the other side is
+ *                `first` and is valid with at least 3 segments.  No candidate, or a short ring: the WHOLE relation is rejected,
+ *                with the two figures of the importer's message — complete rings so far, segments unmatched before this ring.
+ *   polygons     per ring node1's id of its first segment, then per segment node2's id if the last id pushed equals node1's id,
+ *                else node1's id: a comparison of IDS, where the search compares positions.
+ *   multipolygons an accepted relation is one multipolygon with the relation's global id, its polygons appended in ring order; a
+ *                relation without segments is accepted with no polygons; a rejected one leaves nothing behind.
+ *
+ * The search is greedy and order-dependent: the arrays equal the importer's for the same input, ring by ring.  The host twin
+ * is osmt::assemble_multipolygons_host (host/osmt_polygons.hpp). */
+typedef struct osmt_relations_desc {
+    const double* nodes; /* [n_nodes][2] = (lat, lon); compared by their bits, any bit pattern is allowed */
+    size_t n_nodes;
+    const uint32_t* way_node_off; /* [n_ways + 1] into way_nodes; offsets as in osmt_geodata_desc */
+    size_t n_ways;
+    const uint32_t* way_nodes; /* node indices */
+    size_t n_way_nodes;
+    const uint64_t* relation_ids;     /* [n_relations] global ids */
+    const uint32_t* relation_way_off; /* [n_relations + 1] into relation_ways / relation_way_inner */
+    size_t n_relations;
+    const uint32_t* relation_ways;     /* way indices */
+    const uint8_t* relation_way_inner; /* the reference's role: 0 outer, 1 inner */
+    size_t n_relation_ways;
+} osmt_relations_desc;
+
+/* what became of one relation; rings_built and unmatched are the figures of the importer's message for a rejected relation
+ * (an accepted one: its ring count and 0) */
+typedef struct osmt_relation_status {
+    uint32_t accepted, rings_built, unmatched;
+} osmt_relation_status;
+
+typedef struct osmt_polygons osmt_polygons; /* an assembly's result, on the device until it is freed */
+
+/* The checks osmt_assemble_multipolygons runs first, without a device.  OSMT_INVALID_ARG, naming the offender: a NULL array with
+ * a non-zero count; bad offsets; a node or way index out of range; a role byte above 1.  OSMT_UNSUPPORTED, with the figure: a
+ * segment total of 2^31 or more (an endpoint is 2 * segment + side in 32 bits); n_nodes at or above 2^32 - 1. */
+int osmt_validate_relations(const osmt_relations_desc* relations);
+/* Uploads the arrays, assembles every relation on the device (csrc/osmt_polygons.hip) and waits for the result.  A refused or
+ * failed call allocates no result, gives its buffers back and leaves the context usable. */
+int osmt_assemble_multipolygons(osmt_ctx* ctx, const osmt_relations_desc* relations, osmt_polygons** out);
+/* counts = { polygons, polygon nodes, multipolygons, multipolygon polygons } */
+int osmt_polygons_counts(const osmt_polygons* p, size_t counts[4]);
+/* The arrays in exactly the form osmt_geodata_desc takes: polygon_node_off [counts[0] + 1], polygon_nodes [counts[1]],
+ * multipolygon_ids [counts[2]], multipolygon_polygon_off [counts[2] + 1], multipolygon_polygons [counts[3]]; status
+ * [n_relations]; multipolygon_relation [counts[2]]: the index of the relation a multipolygon came from, so the caller can carry
+ * its tags over.  A NULL output is skipped; the caller's buffers have the sizes osmt_polygons_counts gave. */
+int osmt_polygons_read(osmt_ctx* ctx, const osmt_polygons* p, uint32_t* polygon_node_off, uint32_t* polygon_nodes, uint64_t* multipolygon_ids,
+                       uint32_t* multipolygon_polygon_off, uint32_t* multipolygon_polygons, osmt_relation_status* status,
+                       uint32_t* multipolygon_relation);
+void osmt_polygons_free(osmt_polygons* p);
+/* Test hook in the spirit of osmt_debug_match_hash_bits: the vertex table of later assemblies of this context keeps only the
+ * low `bits` bits of the position hash (32 = all; 0 puts every vertex into one probe chain).  The result must not change. */
+int osmt_debug_vertex_hash_bits(osmt_ctx* ctx, uint32_t bits);
+
 /* ---- the osm_ids filter: a set of global ids as bit-planes on the GPU -------------------------------------------- */
 /* The one argument of get_entities_in_tile_with_neighbors(tile, osm_ids) (reader.rs:60,95-99): filter_entities_by_ids
  * (reader.rs:254-262) keeps an entity iff its global_id() is in the set.  ONE set serves nodes, ways and multipolygons alike

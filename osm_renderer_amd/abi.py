@@ -288,6 +288,23 @@ class GeodataDesc(C.Structure):
     ]
 
 
+class RelationsDesc(C.Structure):  # osmt_relations_desc
+    _fields_ = [
+        ("nodes", C.POINTER(C.c_double)),
+        ("n_nodes", C.c_size_t),
+        ("way_node_off", C.POINTER(C.c_uint32)),
+        ("n_ways", C.c_size_t),
+        ("way_nodes", C.POINTER(C.c_uint32)),
+        ("n_way_nodes", C.c_size_t),
+        ("relation_ids", C.POINTER(C.c_uint64)),
+        ("relation_way_off", C.POINTER(C.c_uint32)),
+        ("n_relations", C.c_size_t),
+        ("relation_ways", C.POINTER(C.c_uint32)),
+        ("relation_way_inner", C.POINTER(C.c_uint8)),
+        ("n_relation_ways", C.c_size_t),
+    ]
+
+
 class StyleRec(C.Structure):
     _fields_ = [
         ("layer", C.c_int64),

@@ -613,6 +613,55 @@ hipError_t osmt_launch_tix_keymark(const unsigned long long* key, uint32_t n, ui
 hipError_t osmt_launch_tix_keycompact(const unsigned long long* key, uint32_t n, const uint32_t* head, unsigned long long* out_key, uint32_t* out_id,
                                       hipStream_t st);
 
+/* ---- multipolygon rings from relations' member ways (osmt_polygons.hip) ------------------------------------------ */
+/* words of osmt_mpa_pass::words */
+enum {
+    OSMT_MPA_SEGMENTS = 0, /* the exact segment total */
+    OSMT_MPA_SCAN,         /* the total of the way references' scan (equal to the above when it fits 32 bits) */
+    OSMT_MPA_MPS,          /* accepted relations */
+    OSMT_MPA_POLYS,        /* their rings */
+    OSMT_MPA_NODES,        /* their polygon nodes */
+    OSMT_MPA_WORDS
+};
+struct osmt_mpa_pass {
+    /* the caller's arrays on the device */
+    const ulonglong2* node_bits; /* [n_nodes] the bits of (lat, lon) */
+    const uint32_t *way_off, *way_nodes, *rel_way_off, *rel_ways;
+    const uint8_t* rel_inner;
+    const uint64_t* rel_ids;
+    uint32_t n_nodes, n_ways, n_rels, n_refs;
+    uint32_t* ref_off;  /* [n_refs + 1] segments of a way reference, then their exclusive scan */
+    uint32_t* rel_seg;  /* [n_rels + 1] a relation's first segment */
+    uint32_t *rel_acc, *rel_rings, *rel_nodes; /* [n_rels + 1] what the walk found, then their exclusive scans */
+    unsigned long long *blk, *words; /* max(n_refs, n_rels) / 256 + 1 words; [OSMT_MPA_WORDS] */
+    /* sized once the segment total is known; e = 2 * segment + side is an endpoint */
+    uint32_t n_segs;
+    uint32_t hash_bits, table_mask; /* osmt_debug_vertex_hash_bits; slots - 1 */
+    uint32_t* seg_nodes; /* [2 * n_segs] the node of an endpoint */
+    uint32_t* seg_rel;   /* [n_segs] */
+    uint8_t* seg_state;  /* [n_segs] role | 2 while the segment is available */
+    uint32_t* table;     /* [table_mask + 1] lowest endpoint of a (relation, position) */
+    uint32_t* canon;     /* [2 * n_segs] the vertex of an endpoint: the lowest endpoint of its relation at its position */
+    uint2* ent;          /* [2 * n_segs] sorted adjacency: {endpoint, vertex of its other side}, both less the relation's 2 * first segment */
+    uint32_t* gstart;    /* [2 * n_segs] by endpoint: where its list starts if it is a vertex, else all ones; relation-local */
+    uint32_t* stamp;     /* [2 * n_segs] by vertex: the serial of the last ring that used it */
+    uint32_t* ring_seg;  /* [n_segs] the segments of a relation's rings in walk order, relation-local */
+    uint32_t* ring_end;  /* [n_segs / 3 + 1] at n_first_segment / 3 + k: segments walked when ring k closed */
+    osmt_relation_status* status; /* [n_rels] */
+    /* the result */
+    uint32_t *poly_node_off, *poly_nodes, *mp_poly_off, *mp_polys, *mp_rel;
+    uint64_t* mp_ids;
+};
+/* k_mpa_count + scan + k_mpa_reloff: ref_off, rel_seg and words[OSMT_MPA_SEGMENTS] (words zeroed here) */
+hipError_t osmt_launch_mpa_count(const osmt_mpa_pass& a, hipStream_t st);
+/* k_mpa_segments, k_mpa_fill + k_mpa_vertices + k_mpa_canon: segments, the vertex table, canon and the (vertex, endpoint)
+ * pairs to sort */
+hipError_t osmt_launch_mpa_vertices(const osmt_mpa_pass& a, unsigned long long* key, uint32_t* id, hipStream_t st);
+/* k_mpa_adjacency over the sorted pairs, k_mpa_walk, the scans of what it found */
+hipError_t osmt_launch_mpa_walk(const osmt_mpa_pass& a, const unsigned long long* key, const uint32_t* id, hipStream_t st);
+/* k_mpa_emit: the five arrays and mp_rel */
+hipError_t osmt_launch_mpa_emit(const osmt_mpa_pass& a, hipStream_t st);
+
 /* ---- the id filter (osmt_idfilter.hip) -------------------------------------------------------------------------- */
 /* k_idf_plane: bit e of `plane` = gid[e] is in ids[0 .. n_ids) (ascending, unique); plane has ceil(n / 64) 64-bit words and every
  * one of them is written; n == 0 launches nothing */

@@ -139,6 +139,26 @@ class Context {
         const uint64_t* ids = !node_ids ? nullptr : node_ids->empty() ? &none : node_ids->data();
         check(osmt_build_tile_index(ctx_, geodata_id, ids, node_ids ? node_ids->size() : 0));
     }
+    /* multipolygon rings assembled on the device from relations' member ways (osmt_assemble_multipolygons).  `out` is the helper
+     * osmt::AssembledPolygons (host/osmt_polygons.hpp, or anything with its vectors): out.into(geodata_desc) writes the arrays
+     * into an osmt::GeodataDesc, and the chain goes on with register_geodata, register_node_mercator and build_tile_index */
+    template <class Polygons>
+    void assemble_multipolygons(const osmt_relations_desc& relations, Polygons& out) {
+        check(osmt_validate_relations(&relations));
+        osmt_polygons* p = nullptr;
+        check(osmt_assemble_multipolygons(ctx_, &relations, &p));
+        size_t n[4] = {0, 0, 0, 0};
+        int rc = osmt_polygons_counts(p, n);
+        if (rc == OSMT_OK) {
+            out.polygon_node_off.assign(n[0] + 1, 0u), out.polygon_nodes.assign(n[1], 0u), out.multipolygon_ids.assign(n[2], 0u);
+            out.multipolygon_polygon_off.assign(n[2] + 1, 0u), out.multipolygon_polygons.assign(n[3], 0u), out.multipolygon_relation.assign(n[2], 0u);
+            out.status.assign(relations.n_relations, osmt_relation_status{0u, 0u, 0u});
+            rc = osmt_polygons_read(ctx_, p, out.polygon_node_off.data(), out.polygon_nodes.data(), out.multipolygon_ids.data(), out.multipolygon_polygon_off.data(),
+                                    out.multipolygon_polygons.data(), out.status.data(), out.multipolygon_relation.data());
+        }
+        osmt_polygons_free(p);
+        check(rc);
+    }
     uint32_t register_label_styles(const std::vector<osmt_label_style_rec>& styles) {
         uint32_t first = 0;
         check(osmt_register_label_styles(ctx_, styles.data(), styles.size(), &first));

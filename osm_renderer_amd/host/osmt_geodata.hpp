@@ -349,6 +349,12 @@ struct GeodataDesc {
             multipolygon_ids.push_back(r.multipolygon_global_id(i));
             append(multipolygon_polygon_off, multipolygon_polygons, r.multipolygon_polygon_ids(i));
         }
+        repoint();
+    }
+    /* no file: the caller fills the vectors (osmt::AssembledPolygons::into fills the polygon half) and calls repoint() */
+    GeodataDesc() { repoint(); }
+    /* `desc` over the vectors as they are now */
+    void repoint() {
         desc.nodes = nodes.data(), desc.n_nodes = nodes.size() / 2;
         desc.way_ids = way_ids.data(), desc.way_node_off = way_node_off.data(), desc.n_ways = way_ids.size();
         desc.way_nodes = way_nodes.data(), desc.n_way_nodes = way_nodes.size();

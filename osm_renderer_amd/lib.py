@@ -58,6 +58,8 @@ EXPORTS = [
     "osmt_last_declined_anchors", "osmt_worker_render_tile_png", "osmt_worker_tile_stats",
     "osmt_validate_tile_pyramid", "osmt_register_tile_pyramid", "osmt_tile_pyramid_levels", "osmt_read_tile_pyramid", "osmt_tile_query_stats",
     "osmt_validate_tile_index_build", "osmt_build_tile_index", "osmt_read_tile_index",
+    "osmt_validate_relations", "osmt_assemble_multipolygons", "osmt_polygons_counts", "osmt_polygons_read", "osmt_polygons_free",
+    "osmt_debug_vertex_hash_bits",
 ]
 
 
@@ -268,6 +270,14 @@ def load():
         L.osmt_validate_tile_index_build.argtypes = [C.c_uint32, u64p, C.c_size_t, vp]
         L.osmt_build_tile_index.argtypes = [vp, C.c_uint32, u64p, C.c_size_t]
         L.osmt_read_tile_index.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, sz, sz]
+    if hasattr(L, "osmt_assemble_multipolygons"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_validate_relations.argtypes = [vp]
+        L.osmt_assemble_multipolygons.argtypes = [vp, vp, C.POINTER(vp)]
+        L.osmt_polygons_counts.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.osmt_polygons_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.osmt_polygons_free.argtypes = [vp]
+        L.osmt_polygons_free.restype = None
+        L.osmt_debug_vertex_hash_bits.argtypes = [vp, C.c_uint32]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

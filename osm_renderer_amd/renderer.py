@@ -599,6 +599,38 @@ class Context:
                                      caps, counts))
         return out
 
+    def assemble_multipolygons(self, relations):
+        """osmt_assemble_multipolygons: the polygons and multipolygons of `relations` (styled.Relations), assembled on the device as
+        the importer's find_polygons_in_multipolygon assembles them.  A dict of numpy arrays in the form osmt_geodata_desc takes —
+        polygon_node_off, polygon_nodes, multipolygon_ids, multipolygon_polygon_off, multipolygon_polygons — plus status
+        (styled.RELATION_STATUS_DTYPE, one per relation) and multipolygon_relation (the relation a multipolygon came from);
+        styled.Geodata.from_arrays makes a Geodata of it."""
+        from . import styled
+
+        L = load()
+        d = relations.as_desc()
+        check(L.osmt_validate_relations(C.byref(d)))
+        h = C.c_void_p()
+        check(L.osmt_assemble_multipolygons(self._h, C.byref(d), C.byref(h)))
+        try:
+            counts = (C.c_size_t * 4)()
+            check(L.osmt_polygons_counts(h, counts))
+            n_polys, n_nodes, n_mps, n_mp_polys = (int(c) for c in counts)
+            out = {"polygon_node_off": np.zeros(n_polys + 1, np.uint32), "polygon_nodes": np.zeros(n_nodes, np.uint32),
+                   "multipolygon_ids": np.zeros(n_mps, np.uint64), "multipolygon_polygon_off": np.zeros(n_mps + 1, np.uint32),
+                   "multipolygon_polygons": np.zeros(n_mp_polys, np.uint32), "status": np.zeros(int(d.n_relations), styled.RELATION_STATUS_DTYPE),
+                   "multipolygon_relation": np.zeros(n_mps, np.uint32)}
+            check(L.osmt_polygons_read(self._h, h, *(out[k].ctypes.data for k in ("polygon_node_off", "polygon_nodes", "multipolygon_ids",
+                                                                                 "multipolygon_polygon_off", "multipolygon_polygons", "status",
+                                                                                 "multipolygon_relation"))))
+        finally:
+            L.osmt_polygons_free(h)
+        return out
+
+    def debug_vertex_hash_bits(self, bits):
+        """osmt_debug_vertex_hash_bits (test hook): later assemblies keep only the low `bits` bits of the position hash"""
+        check(load().osmt_debug_vertex_hash_bits(self._h, bits))
+
     def tile_query_stats(self):
         """osmt_tile_query_stats: ((tile, column) items, way, multipolygon, node candidates) the last completed tile query of this
         context gathered, before dedup"""

@@ -54,6 +54,19 @@ class Geodata:
         self.multipolygon_ids = np.array([m[0] for m in multipolygons], dtype=np.uint64)
         self.multipolygon_polygon_off, self.multipolygon_polygons = _csr([m[1] for m in multipolygons])
 
+    @classmethod
+    def from_arrays(cls, nodes, way_ids, way_node_off, way_nodes, polygons):
+        """A Geodata over flat arrays: the ways as they are, the polygon and multipolygon arrays from `polygons`, the dict
+        Context.assemble_multipolygons returns (or any with its five array names)."""
+        g = cls(nodes)
+        g.way_ids = np.ascontiguousarray(way_ids, dtype=np.uint64).reshape(-1)
+        g.way_node_off, g.way_nodes = np.ascontiguousarray(way_node_off, dtype=np.uint32), np.ascontiguousarray(way_nodes, dtype=np.uint32)
+        g.polygon_node_off, g.polygon_nodes = np.ascontiguousarray(polygons["polygon_node_off"], dtype=np.uint32), np.ascontiguousarray(polygons["polygon_nodes"], dtype=np.uint32)
+        g.multipolygon_ids = np.ascontiguousarray(polygons["multipolygon_ids"], dtype=np.uint64)
+        g.multipolygon_polygon_off = np.ascontiguousarray(polygons["multipolygon_polygon_off"], dtype=np.uint32)
+        g.multipolygon_polygons = np.ascontiguousarray(polygons["multipolygon_polygons"], dtype=np.uint32)
+        return g
+
     def as_desc(self):
         """ctypes osmt_geodata_desc pointing into this object's arrays (keep `self` alive)."""
         u32, u64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -66,6 +79,35 @@ class Geodata:
         d.multipolygon_ids, d.multipolygon_polygon_off = self.multipolygon_ids.ctypes.data_as(u64), self.multipolygon_polygon_off.ctypes.data_as(u32)
         d.n_multipolygons = len(self.multipolygon_ids)
         d.multipolygon_polygons, d.n_multipolygon_polygons = self.multipolygon_polygons.ctypes.data_as(u32), len(self.multipolygon_polygons)
+        return d
+
+
+RELATION_STATUS_DTYPE = np.dtype([("accepted", "<u4"), ("rings_built", "<u4"), ("unmatched", "<u4")])
+assert RELATION_STATUS_DTYPE.itemsize == 12
+
+
+class Relations:
+    """The flat arrays of osmt_relations_desc.  nodes: [n, 2] (lat, lon), compared by their bits; ways: [[node idx]];
+    relations: [(global id, [(way idx, inner)])] with inner 0 / 1 (the importer's role)."""
+
+    def __init__(self, nodes, ways=(), relations=()):
+        self.nodes = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, 2)
+        self.way_node_off, self.way_nodes = _csr([list(w) for w in ways])
+        self.relation_ids = np.array([r[0] for r in relations], dtype=np.uint64)
+        self.relation_way_off, self.relation_ways = _csr([[w for w, _ in r[1]] for r in relations])
+        self.relation_way_inner = np.array([i for r in relations for _, i in r[1]], dtype=np.uint8)
+
+    def as_desc(self):
+        """ctypes osmt_relations_desc pointing into this object's arrays (keep `self` alive)."""
+        u32 = C.POINTER(C.c_uint32)
+        d = abi.RelationsDesc()
+        d.nodes, d.n_nodes = self.nodes.ctypes.data_as(C.POINTER(C.c_double)), len(self.nodes)
+        d.way_node_off, d.n_ways = self.way_node_off.ctypes.data_as(u32), len(self.way_node_off) - 1
+        d.way_nodes, d.n_way_nodes = self.way_nodes.ctypes.data_as(u32), len(self.way_nodes)
+        d.relation_ids, d.relation_way_off = self.relation_ids.ctypes.data_as(C.POINTER(C.c_uint64)), self.relation_way_off.ctypes.data_as(u32)
+        d.n_relations = len(self.relation_ids)
+        d.relation_ways, d.relation_way_inner = self.relation_ways.ctypes.data_as(u32), self.relation_way_inner.ctypes.data_as(C.POINTER(C.c_uint8))
+        d.n_relation_ways = len(self.relation_ways)
         return d
 
 
