@@ -879,7 +879,7 @@ int osmt_read_tile_index(osmt_ctx* ctx, uint32_t geodata_id, uint32_t* tile_xy, 
  * member ways in, the polygon and multipolygon arrays of osmt_geodata_desc out.  Per relation, in relation order:
  *
  *   segments     for every way reference in order and every idx in 1 .. len(way): (node[idx - 1], node[idx], role).  Ways come in
- *                as they are stored (postprocess_node_refs is not part of this).
+ *                as they are stored: postprocess_node_refs ran before, in osmt_resolve_refs (below) or at the caller.
  *   connections  per POSITION — the bits of (lat, lon): -0.0 and 0.0 are two vertices, two NaNs of equal bits are one — the list of
  *                (other side, segment), filled for idx ascending with node1's entry, then node2's: the order inside a list is
  *                2 * idx + side.  A segment whose two positions are equal stands twice on one list.
@@ -938,6 +938,67 @@ void osmt_polygons_free(osmt_polygons* p);
 /* Test hook in the spirit of osmt_debug_match_hash_bits: the vertex table of later assemblies of this context keeps only the
  * low `bits` bits of the position hash (32 = all; 0 puts every vertex into one probe chain).  The result must not change. */
 int osmt_debug_vertex_hash_bits(osmt_ctx* ctx, uint32_t bits);
+
+/* ---- OSM ids resolved on the GPU: way and relation references to local indices, ways deduped ----------------------- */
+/* The three steps of importer.rs between the elements a parser hands over and the local indices every other call takes:
+ * OsmEntityStorage::translate_id (importer.rs:45-71), the silent drop of references that do not resolve
+ * (importer.rs:365-400) and postprocess_node_refs (importer.rs:334-353, called at importer.rs:260).  Elements come per kind
+ * and in file order; selecting relations by type=multipolygon and dropping members that are no ways stay with the caller.
+ *
+ *   translate    a reference g of way w resolves to the LARGEST node index i < way_nodes_seen[w] with node_ids[i] == g:
+ *                HashMap::insert overwrites, so a later element of an id wins, and an element not yet read does not exist.
+ *                way_nodes_seen NULL: every way sees every node (a file that writes nodes, then ways, then relations).
+ *                Relation members resolve the same way over way_ids / relation_ways_seen and carry their role byte along.
+ *   drop         a reference without such an index is dropped; the others keep their order.  Every element stays stored: a
+ *                shadowed duplicate keeps its index and is never referenced.
+ *   dedup        over a way's references AFTER the drop: position 0 is kept; position idx >= 1 is kept iff no position
+ *                1 <= j < idx has the same UNORDERED pair {refs[j], refs[j - 1]} — refs is the list before any removal, so
+ *                the predecessor is the original neighbour, not the last one kept.  ([a,b,a,c] gives [a,b,c].)  This is what
+ *                the importer's running HashSet computes: every visited pair is in the set afterwards in one orientation
+ *                or the other, so "not seen" is "the first occurrence of the unordered pair in this way" (DESIGN.md
+ *                section 3.20).  Relation members are not deduped: the importer does not dedup them.
+ *
+ * The result is in exactly the form osmt_relations_desc and osmt_geodata_desc take.  The host twin is
+ * osmt::resolve_refs_host (host/osmt_resolve.hpp). */
+typedef struct osmt_raw_osm_desc {
+    const uint64_t* node_ids; /* [n_nodes] global ids, any 64 bits */
+    size_t n_nodes;
+    const uint64_t* way_ids;     /* [n_ways] */
+    const uint32_t* way_ref_off; /* [n_ways + 1] into way_refs */
+    size_t n_ways;
+    const uint64_t* way_refs; /* the `nd ref` values in order */
+    size_t n_way_refs;
+    const uint32_t* relation_ref_off; /* [n_relations + 1] into relation_refs / relation_ref_inner */
+    size_t n_relations;
+    const uint64_t* relation_refs;     /* the ids of the type="way" members in order */
+    const uint8_t* relation_ref_inner; /* role == "inner": 0 / 1 */
+    size_t n_relation_refs;
+    const uint32_t* way_nodes_seen;     /* [n_ways] nodes that precede the way in the file, or NULL: all of them */
+    const uint32_t* relation_ways_seen; /* [n_relations] ways that precede the relation in the file, or NULL: all of them */
+} osmt_raw_osm_desc;
+
+typedef struct osmt_resolved osmt_resolved; /* a resolution's result, on the device until it is freed */
+
+/* The checks osmt_resolve_refs runs first, without a device.  OSMT_INVALID_ARG, naming the offender: a NULL array with a
+ * non-zero count; bad offsets; a role byte above 1; a *_seen value above its element count.  OSMT_UNSUPPORTED, with the
+ * figure: n_nodes, n_ways or n_relations at or above 2^32 - 1 (an index is 32 bits and all ones marks "none"); a reference
+ * total at or above 2^32 - 1. */
+int osmt_validate_resolve(const osmt_raw_osm_desc* raw);
+/* Uploads the arrays, resolves every reference on the device (csrc/osmt_resolve.hip) and waits for the result.  A refused or
+ * failed call allocates no result, gives its buffers back and leaves the context usable. */
+int osmt_resolve_refs(osmt_ctx* ctx, const osmt_raw_osm_desc* raw, osmt_resolved** out);
+/* counts = { way nodes kept, relation ways kept, node references unresolved, node references removed as repeats, way
+ * references unresolved } */
+int osmt_resolved_counts(const osmt_resolved* r, size_t counts[5]);
+/* way_node_off [n_ways + 1], way_nodes [counts[0]], relation_way_off [n_relations + 1], relation_ways [counts[1]],
+ * relation_way_inner [counts[1]].  A NULL output is skipped. */
+int osmt_resolved_read(osmt_ctx* ctx, const osmt_resolved* r, uint32_t* way_node_off, uint32_t* way_nodes, uint32_t* relation_way_off,
+                       uint32_t* relation_ways, uint8_t* relation_way_inner);
+void osmt_resolved_free(osmt_resolved* r);
+/* Test hook in the spirit of osmt_debug_vertex_hash_bits: ways of up to `n` resolved references (at most 1024) of later
+ * resolutions of this context find their repeats in LDS, one wave per way; longer ways go through the global sort.  0 sends
+ * every way through the sort.  The result must not change. */
+int osmt_debug_resolve_short_way_max(osmt_ctx* ctx, uint32_t n);
 
 /* ---- the osm_ids filter: a set of global ids as bit-planes on the GPU -------------------------------------------- */
 /* The one argument of get_entities_in_tile_with_neighbors(tile, osm_ids) (reader.rs:60,95-99): filter_entities_by_ids

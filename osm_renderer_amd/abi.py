@@ -305,6 +305,25 @@ class RelationsDesc(C.Structure):  # osmt_relations_desc
     ]
 
 
+class RawOsmDesc(C.Structure):  # osmt_raw_osm_desc
+    _fields_ = [
+        ("node_ids", C.POINTER(C.c_uint64)),
+        ("n_nodes", C.c_size_t),
+        ("way_ids", C.POINTER(C.c_uint64)),
+        ("way_ref_off", C.POINTER(C.c_uint32)),
+        ("n_ways", C.c_size_t),
+        ("way_refs", C.POINTER(C.c_uint64)),
+        ("n_way_refs", C.c_size_t),
+        ("relation_ref_off", C.POINTER(C.c_uint32)),
+        ("n_relations", C.c_size_t),
+        ("relation_refs", C.POINTER(C.c_uint64)),
+        ("relation_ref_inner", C.POINTER(C.c_uint8)),
+        ("n_relation_refs", C.c_size_t),
+        ("way_nodes_seen", C.POINTER(C.c_uint32)),
+        ("relation_ways_seen", C.POINTER(C.c_uint32)),
+    ]
+
+
 class StyleRec(C.Structure):
     _fields_ = [
         ("layer", C.c_int64),

@@ -1,6 +1,6 @@
 /*
  * osmt_host.h — what the host files of libosmtile.so (osmt_api.cpp, osmt_host_worker.cpp, osmt_host_multi.cpp,
- * osmt_host_tagstyle.cpp, osmt_host_pyramid.cpp, osmt_host_polygons.cpp) share: the context and scene objects, guarded(), HIP_TRY, the two per-call
+ * osmt_host_tagstyle.cpp, osmt_host_pyramid.cpp, osmt_host_polygons.cpp, osmt_host_resolve.cpp) share: the context and scene objects, guarded(), HIP_TRY, the two per-call
  * holders table_upload and call_work, and the declarations of what one file takes from another.  Internal: nothing declared here leaves the library
  * (hidden visibility).  Nothing here is a variable, a static function or an anonymous namespace: every function has ONE
  * definition, in the .cpp named above its declaration, and is documented there (inline here: guarded, align_up and the members
@@ -200,6 +200,7 @@ struct osmt_ctx {
     std::vector<rules_host> rules;
     uint32_t match_hash_bits = 32; /* osmt_debug_match_hash_bits */
     uint32_t vertex_hash_bits = 32; /* osmt_debug_vertex_hash_bits (osmt_host_polygons.cpp) */
+    uint32_t resolve_short_way_max = OSMT_RES_SHORT_WAY_DEFAULT; /* osmt_debug_resolve_short_way_max (osmt_host_resolve.cpp) */
     /* the tables of osmt_register_style_bindings: append-only, one device allocation each that never moves, so a build
      * that holds a table's pointers is not disturbed by a later registration */
     struct bindings_host {

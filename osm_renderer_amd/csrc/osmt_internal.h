@@ -566,6 +566,13 @@ hipError_t osmt_launch_pyr_pairs(const osmt_pyr_src& s, unsigned long long* key,
 hipError_t osmt_launch_pyr_tilekeys(const osmt_pyr_src& s, unsigned long long* key, uint32_t* id, hipStream_t st);
 /* k_pyr_digits: hist[OSMT_PYR_DIGITS][256] of n pairs (zeroed here) */
 hipError_t osmt_launch_pyr_digits(const unsigned long long* key, const uint32_t* id, uint32_t n, uint32_t* hist, hipStream_t st);
+/* A pass sorts on any digit below OSMT_PYR_PASS_DIGITS: 4 + b is byte b of the key, b = 0..7.  The histogram above stops at
+ * OSMT_PYR_DIGITS because its callers' keys have 36 bits; a caller whose key is any 64 bits and whose ids already ascend
+ * (the id resolution, osmt_resolve.hip) takes k_pyr_keydigits instead: hist[OSMT_PYR_KEY_DIGITS][256] of the key's bytes
+ * alone (zeroed here), row b for pass digit 4 + b. */
+#define OSMT_PYR_KEY_DIGITS 8u
+#define OSMT_PYR_PASS_DIGITS 12u
+hipError_t osmt_launch_pyr_keydigits(const unsigned long long* key, uint32_t n, uint32_t* hist, hipStream_t st);
 /* one stable pass over `digit`: k_pyr_hist -> osmt_tq_scan -> k_pyr_scatter.  counts: 256 * blocks + 1 words, blk: blocks + 1,
  * with blocks = ceil(n / OSMT_PYR_SORT_BLOCK); tot: one word */
 hipError_t osmt_launch_pyr_pass(const unsigned long long* key, const uint32_t* id, uint32_t n, uint32_t digit, uint32_t* counts, unsigned long long* blk,
@@ -661,6 +668,48 @@ hipError_t osmt_launch_mpa_vertices(const osmt_mpa_pass& a, unsigned long long* 
 hipError_t osmt_launch_mpa_walk(const osmt_mpa_pass& a, const unsigned long long* key, const uint32_t* id, hipStream_t st);
 /* k_mpa_emit: the five arrays and mp_rel */
 hipError_t osmt_launch_mpa_emit(const osmt_mpa_pass& a, hipStream_t st);
+
+/* ---- OSM ids resolved to local indices (osmt_resolve.hip) -------------------------------------------------------- */
+#define OSMT_RES_SHORT_WAY_CAP 1024u    /* the most osmt_debug_resolve_short_way_max takes: 24 KiB of LDS for one wave */
+#define OSMT_RES_SHORT_WAY_DEFAULT 256u /* ways up to this many resolved references find their repeats in LDS */
+/* one kind's references on their way from global ids to local indices: ways' node references, or relations' way members */
+struct osmt_res_refs {
+    const unsigned long long* table_key; /* [n_table] the elements' global ids, sorted; equal ids in index order */
+    const uint32_t* table_id;            /* [n_table] their indices */
+    uint32_t n_table;
+    const uint32_t* off;             /* [n_owners + 1] into refs */
+    const uint32_t* seen;            /* [n_owners] elements an owner's references may resolve to, or NULL: n_table */
+    const unsigned long long* refs;  /* [n_refs] global ids */
+    const uint8_t* role;             /* [n_refs] carried along, or NULL */
+    uint32_t n_owners, n_refs;
+    uint32_t* local;  /* [n_refs] the index a reference resolves to, all ones: none */
+    uint32_t* pos;    /* [n_refs + 1] 1: resolved, then its exclusive scan */
+    uint32_t* out_off;   /* [n_owners + 1] */
+    uint32_t* out_local; /* [pos[n_refs]] */
+    uint8_t* out_role;   /* [pos[n_refs]], or NULL */
+    unsigned long long *blk, *tot; /* n_refs / 256 + 1 words; one word: references resolved */
+};
+/* id[i] = i for i < n: the indices of a table before its sort */
+hipError_t osmt_launch_res_iota(uint32_t* id, uint32_t n, hipStream_t st);
+/* k_res_translate + scan + k_res_compact: local, pos, out_off, out_local, out_role, *tot */
+hipError_t osmt_launch_res_translate(const osmt_res_refs& a, hipStream_t st);
+/* the dedup of the ways' resolved references: off [n_ways + 1], refs [off[n_ways]] as osmt_launch_res_translate wrote them */
+struct osmt_res_dedup {
+    const uint32_t *off, *refs;
+    uint32_t n_ways, short_max; /* osmt_debug_resolve_short_way_max */
+    uint32_t* keep;             /* [n_refs_cap + 1] 1: kept, then its exclusive scan */
+    uint32_t* long_pos;         /* [n_ways + 1] pairs a way sends through the sort, then their exclusive scan */
+    unsigned long long *blk, *tot; /* max(n_refs_cap, n_ways) / 256 + 1 words; tot[0]: pairs to sort, tot[1]: references kept */
+};
+/* k_res_short (one wave per way of up to short_max references, LDS) and k_res_longcount + scan: keep of the short ways and of
+ * every position 0, long_pos, tot[0] */
+hipError_t osmt_launch_res_short(const osmt_res_dedup& a, hipStream_t st);
+/* k_res_longpairs: key = min << 32 | max, id = the position in refs, of the n_pairs = tot[0] pairs of the long ways */
+hipError_t osmt_launch_res_longpairs(const osmt_res_dedup& a, uint32_t n_pairs, unsigned long long* key, uint32_t* id, hipStream_t st);
+/* k_res_longmark over the sorted pairs (none: nothing), then the scan of keep over n_refs references: tot[1] */
+hipError_t osmt_launch_res_mark(const osmt_res_dedup& a, uint32_t n_pairs, const unsigned long long* key, const uint32_t* id, uint32_t n_refs, hipStream_t st);
+/* k_res_emit: out_off [n_ways + 1], out_nodes [tot[1]] */
+hipError_t osmt_launch_res_emit(const osmt_res_dedup& a, uint32_t n_refs, uint32_t* out_off, uint32_t* out_nodes, hipStream_t st);
 
 /* ---- the id filter (osmt_idfilter.hip) -------------------------------------------------------------------------- */
 /* k_idf_plane: bit e of `plane` = gid[e] is in ids[0 .. n_ids) (ascending, unique); plane has ceil(n / 64) 64-bit words and every

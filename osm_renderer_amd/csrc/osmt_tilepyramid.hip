@@ -13,6 +13,9 @@
  *   k_pyr_digits    the histograms of all nine 8-bit digits of the pairs (four of the id, five of the 36-bit key) in one
  *                   read: the host skips every digit whose histogram has one non-empty bin (the ids' high bytes, the key's
  *                   high bits), so a sort runs as many passes as its pairs have digits that differ.
+ *   k_pyr_keydigits the same for a caller whose key is any 64 bits and whose ids need no passes (osmt_resolve.hip): the
+ *                   histograms of the key's eight bytes.  A pass takes any of the twelve digits; the callers above never ask
+ *                   for the last three, so their passes and results are what they were.
  *   k_pyr_hist      one pass of the LSD radix sort, per workgroup of OSMT_PYR_SORT_BLOCK pairs: an LDS histogram of the
  *                   digit, stored as counts[digit][workgroup]; the tile query's scan turns the counts into bases.
  *   k_pyr_scatter   the same workgroups again: four rounds of 256 pairs; in a round a lane finds the lanes of its wave with
@@ -45,6 +48,7 @@ static_assert(BINS == WG, "one lane per bin");
 
 typedef unsigned long long u64;
 
+/* d < OSMT_PYR_PASS_DIGITS: 0..3 the bytes of the id, 4..11 the bytes of the key */
 __device__ __forceinline__ uint32_t digit_of(u64 key, uint32_t id, uint32_t d) {
     return d < 4u ? (id >> (8u * d)) & 255u : (uint32_t)(key >> (8u * (d - 4u))) & 255u;
 }
@@ -104,6 +108,24 @@ __global__ __launch_bounds__(256) void k_pyr_digits(const u64* __restrict__ key,
     }
     __syncthreads();
     for (uint32_t d = 0; d < OSMT_PYR_DIGITS; ++d) {
+        const uint32_t c = h[d * BINS + threadIdx.x];
+        if (c) atomicAdd(&hist[d * BINS + threadIdx.x], c);
+    }
+}
+
+/* hist: [OSMT_PYR_KEY_DIGITS][256], zeroed before the launch: the eight bytes of the key, nothing of the id */
+__global__ __launch_bounds__(256) void k_pyr_keydigits(const u64* __restrict__ key, uint32_t n, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[OSMT_PYR_KEY_DIGITS * BINS];
+    for (uint32_t d = 0; d < OSMT_PYR_KEY_DIGITS; ++d) h[d * BINS + threadIdx.x] = 0u;
+    __syncthreads();
+    for (uint32_t j = 0; j < ROUNDS; ++j) {
+        const uint32_t e = blockIdx.x * OSMT_PYR_SORT_BLOCK + j * WG + threadIdx.x;
+        if (e >= n) break;
+        const u64 k = key[e];
+        for (uint32_t d = 0; d < OSMT_PYR_KEY_DIGITS; ++d) atomicAdd(&h[d * BINS + digit_of(k, 0u, 4u + d)], 1u);
+    }
+    __syncthreads();
+    for (uint32_t d = 0; d < OSMT_PYR_KEY_DIGITS; ++d) {
         const uint32_t c = h[d * BINS + threadIdx.x];
         if (c) atomicAdd(&hist[d * BINS + threadIdx.x], c);
     }
@@ -235,6 +257,13 @@ hipError_t osmt_launch_pyr_digits(const unsigned long long* key, const uint32_t*
     const hipError_t e = hipMemsetAsync(hist, 0, OSMT_PYR_DIGITS * BINS * 4u, st);
     if (e != hipSuccess) return e;
     if (n) hipLaunchKernelGGL(k_pyr_digits, dim3(sort_blocks(n)), dim3(WG), 0, st, key, id, n, hist);
+    return hipGetLastError();
+}
+
+hipError_t osmt_launch_pyr_keydigits(const unsigned long long* key, uint32_t n, uint32_t* hist, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(hist, 0, OSMT_PYR_KEY_DIGITS * BINS * 4u, st);
+    if (e != hipSuccess) return e;
+    if (n) hipLaunchKernelGGL(k_pyr_keydigits, dim3(sort_blocks(n)), dim3(WG), 0, st, key, n, hist);
     return hipGetLastError();
 }
 

@@ -159,6 +159,25 @@ class Context {
         osmt_polygons_free(p);
         check(rc);
     }
+    /* OSM ids resolved to local indices on the device (osmt_resolve_refs): the step before assemble_multipolygons.  `out` is
+     * osmt::ResolvedRefs (host/osmt_resolve.hpp, or anything with its vectors and counts) */
+    template <class Resolved>
+    void resolve_refs(const osmt_raw_osm_desc& raw, Resolved& out) {
+        check(osmt_validate_resolve(&raw));
+        osmt_resolved* r = nullptr;
+        check(osmt_resolve_refs(ctx_, &raw, &r));
+        size_t n[5] = {0, 0, 0, 0, 0};
+        int rc = osmt_resolved_counts(r, n);
+        if (rc == OSMT_OK) {
+            out.way_node_off.assign(raw.n_ways + 1, 0u), out.way_nodes.assign(n[0], 0u), out.relation_way_off.assign(raw.n_relations + 1, 0u);
+            out.relation_ways.assign(n[1], 0u), out.relation_way_inner.assign(n[1], 0u);
+            for (int i = 0; i < 5; ++i) out.counts[i] = n[i];
+            rc = osmt_resolved_read(ctx_, r, out.way_node_off.data(), out.way_nodes.data(), out.relation_way_off.data(), out.relation_ways.data(),
+                                    out.relation_way_inner.data());
+        }
+        osmt_resolved_free(r);
+        check(rc);
+    }
     uint32_t register_label_styles(const std::vector<osmt_label_style_rec>& styles) {
         uint32_t first = 0;
         check(osmt_register_label_styles(ctx_, styles.data(), styles.size(), &first));

@@ -60,6 +60,8 @@ EXPORTS = [
     "osmt_validate_tile_index_build", "osmt_build_tile_index", "osmt_read_tile_index",
     "osmt_validate_relations", "osmt_assemble_multipolygons", "osmt_polygons_counts", "osmt_polygons_read", "osmt_polygons_free",
     "osmt_debug_vertex_hash_bits",
+    "osmt_validate_resolve", "osmt_resolve_refs", "osmt_resolved_counts", "osmt_resolved_read", "osmt_resolved_free",
+    "osmt_debug_resolve_short_way_max",
 ]
 
 
@@ -278,6 +280,14 @@ def load():
         L.osmt_polygons_free.argtypes = [vp]
         L.osmt_polygons_free.restype = None
         L.osmt_debug_vertex_hash_bits.argtypes = [vp, C.c_uint32]
+    if hasattr(L, "osmt_resolve_refs"):  # absent only from older variant builds loaded through OSMT_LIB
+        L.osmt_validate_resolve.argtypes = [vp]
+        L.osmt_resolve_refs.argtypes = [vp, vp, C.POINTER(vp)]
+        L.osmt_resolved_counts.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.osmt_resolved_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.osmt_resolved_free.argtypes = [vp]
+        L.osmt_resolved_free.restype = None
+        L.osmt_debug_resolve_short_way_max.argtypes = [vp, C.c_uint32]
     L.osmt_png_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.osmt_png_bound.restype = C.c_size_t
     L.osmt_encode_png.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]

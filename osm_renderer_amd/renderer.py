@@ -631,6 +631,36 @@ class Context:
         """osmt_debug_vertex_hash_bits (test hook): later assemblies keep only the low `bits` bits of the position hash"""
         check(load().osmt_debug_vertex_hash_bits(self._h, bits))
 
+    def resolve_refs(self, raw):
+        """osmt_resolve_refs: the global ids of `raw` (styled.RawOsm) resolved to local indices on the device as the importer's
+        translate_id, its drop of unresolved references and its postprocess_node_refs resolve them.  A dict of numpy arrays in
+        the form osmt_relations_desc and osmt_geodata_desc take — way_node_off, way_nodes, relation_way_off, relation_ways,
+        relation_way_inner — plus counts: (way nodes kept, relation ways kept, node references unresolved, node references
+        removed as repeats, way references unresolved).  styled.Relations.from_resolved makes the Relations of it."""
+        L = load()
+        d = raw.as_desc()
+        check(L.osmt_validate_resolve(C.byref(d)))
+        h = C.c_void_p()
+        check(L.osmt_resolve_refs(self._h, C.byref(d), C.byref(h)))
+        try:
+            counts = (C.c_size_t * 5)()
+            check(L.osmt_resolved_counts(h, counts))
+            counts = tuple(int(c) for c in counts)
+            out = {"way_node_off": np.zeros(int(d.n_ways) + 1, np.uint32), "way_nodes": np.zeros(counts[0], np.uint32),
+                   "relation_way_off": np.zeros(int(d.n_relations) + 1, np.uint32), "relation_ways": np.zeros(counts[1], np.uint32),
+                   "relation_way_inner": np.zeros(counts[1], np.uint8)}
+            check(L.osmt_resolved_read(self._h, h, *(out[k].ctypes.data for k in ("way_node_off", "way_nodes", "relation_way_off", "relation_ways",
+                                                                                 "relation_way_inner"))))
+            out["counts"] = counts
+        finally:
+            L.osmt_resolved_free(h)
+        return out
+
+    def debug_resolve_short_way_max(self, n):
+        """osmt_debug_resolve_short_way_max (test hook): later resolutions dedup ways of up to n references in LDS, longer ones
+        through the sort; 0: every way through the sort"""
+        check(load().osmt_debug_resolve_short_way_max(self._h, n))
+
     def tile_query_stats(self):
         """osmt_tile_query_stats: ((tile, column) items, way, multipolygon, node candidates) the last completed tile query of this
         context gathered, before dedup"""

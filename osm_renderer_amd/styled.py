@@ -97,6 +97,20 @@ class Relations:
         self.relation_way_off, self.relation_ways = _csr([[w for w, _ in r[1]] for r in relations])
         self.relation_way_inner = np.array([i for r in relations for _, i in r[1]], dtype=np.uint8)
 
+    @classmethod
+    def from_resolved(cls, nodes, relation_ids, resolved):
+        """The relations of a resolution: `resolved` is the dict Context.resolve_refs returns (or any with its five array
+        names), relation_ids the relations' global ids in the order the RawOsm listed them."""
+        r = cls(nodes)
+        u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+        r.way_node_off, r.way_nodes = u32(resolved["way_node_off"]), u32(resolved["way_nodes"])
+        r.relation_ids = np.ascontiguousarray(relation_ids, dtype=np.uint64).reshape(-1)
+        r.relation_way_off, r.relation_ways = u32(resolved["relation_way_off"]), u32(resolved["relation_ways"])
+        r.relation_way_inner = np.ascontiguousarray(resolved["relation_way_inner"], dtype=np.uint8).reshape(-1)
+        if len(r.relation_way_off) != len(r.relation_ids) + 1:
+            raise ValueError(f"{len(r.relation_ids)} relation ids for {len(r.relation_way_off) - 1} resolved relations")
+        return r
+
     def as_desc(self):
         """ctypes osmt_relations_desc pointing into this object's arrays (keep `self` alive)."""
         u32 = C.POINTER(C.c_uint32)
@@ -108,6 +122,46 @@ class Relations:
         d.n_relations = len(self.relation_ids)
         d.relation_ways, d.relation_way_inner = self.relation_ways.ctypes.data_as(u32), self.relation_way_inner.ctypes.data_as(C.POINTER(C.c_uint8))
         d.n_relation_ways = len(self.relation_ways)
+        return d
+
+
+class RawOsm:
+    """The flat arrays of osmt_raw_osm_desc: elements as a parser hands them over, per kind and in file order.  node_ids:
+    global ids; ways: [(global id, [node id])]; relations: [(global id, [(way id, inner)])] with the type="way" members only
+    and inner 0 / 1.  nodes_seen [n ways] / ways_seen [n relations]: how many nodes (ways) precede each way (relation) in the
+    file, None: all of them.  relation_ids is kept for styled.Relations.from_resolved; the resolution does not read it."""
+
+    def __init__(self, node_ids, ways=(), relations=(), nodes_seen=None, ways_seen=None):
+        u64 = lambda v: np.array([int(x) for x in v], dtype=np.uint64)
+        self.node_ids = u64(node_ids)
+        self.way_ids = u64([w[0] for w in ways])
+        self.way_ref_off = np.concatenate([[0], np.cumsum([len(w[1]) for w in ways], dtype=np.int64)]).astype(np.uint32)
+        self.way_refs = u64([g for w in ways for g in w[1]])
+        self.relation_ids = u64([r[0] for r in relations])
+        self.relation_ref_off = np.concatenate([[0], np.cumsum([len(r[1]) for r in relations], dtype=np.int64)]).astype(np.uint32)
+        self.relation_refs = u64([g for r in relations for g, _ in r[1]])
+        self.relation_ref_inner = np.array([i for r in relations for _, i in r[1]], dtype=np.uint8)
+        self.way_nodes_seen = None if nodes_seen is None else np.array(nodes_seen, dtype=np.uint32).reshape(-1)
+        self.relation_ways_seen = None if ways_seen is None else np.array(ways_seen, dtype=np.uint32).reshape(-1)
+        if self.way_nodes_seen is not None and len(self.way_nodes_seen) != len(self.way_ids):
+            raise ValueError(f"nodes_seen has {len(self.way_nodes_seen)} entries for {len(self.way_ids)} ways")
+        if self.relation_ways_seen is not None and len(self.relation_ways_seen) != len(self.relation_ids):
+            raise ValueError(f"ways_seen has {len(self.relation_ways_seen)} entries for {len(self.relation_ids)} relations")
+
+    def as_desc(self):
+        """ctypes osmt_raw_osm_desc pointing into this object's arrays (keep `self` alive)."""
+        u32, u64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        d = abi.RawOsmDesc()
+        d.node_ids, d.n_nodes = self.node_ids.ctypes.data_as(u64), len(self.node_ids)
+        d.way_ids, d.way_ref_off, d.n_ways = self.way_ids.ctypes.data_as(u64), self.way_ref_off.ctypes.data_as(u32), len(self.way_ids)
+        d.way_refs, d.n_way_refs = self.way_refs.ctypes.data_as(u64), len(self.way_refs)
+        d.relation_ref_off, d.n_relations = self.relation_ref_off.ctypes.data_as(u32), len(self.relation_ref_off) - 1
+        d.relation_refs, d.relation_ref_inner = self.relation_refs.ctypes.data_as(u64), self.relation_ref_inner.ctypes.data_as(C.POINTER(C.c_uint8))
+        d.n_relation_refs = len(self.relation_refs)
+        if self.way_nodes_seen is not None:
+            d.way_nodes_seen = self.way_nodes_seen.ctypes.data_as(u32)
+        if self.relation_ways_seen is not None:
+            d.relation_ways_seen = self.relation_ways_seen.ctypes.data_as(u32)
         return d
 
 
