@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libosmtile.so")
 SOURCES = ["osmt_kernels.hip", "osmt_labels.hip", "osmt_glyphs.hip", "osmt_textplace.hip", "osmt_textshape.hip", "osmt_polylabel.hip", "osmt_styled.hip", "osmt_tilequery.hip", "osmt_tilepyramid.hip", "osmt_tileindex.hip", "osmt_polygons.hip", "osmt_resolve.hip", "osmt_idfilter.hip", "osmt_tilelabels.hip", "osmt_arealabels.hip", "osmt_selmatch.hip", "osmt_labelbind.hip", "osmt_cascade.hip", "osmt_anchors.hip", "osmt_pngenc.hip", "osmt_api.cpp", "osmt_host_worker.cpp", "osmt_host_multi.cpp", "osmt_host_tagstyle.cpp", "osmt_host_pyramid.cpp", "osmt_host_polygons.cpp", "osmt_host_resolve.cpp", "osmt_png.cpp"]
-HEADERS = ["osmt_bitonic.h", "osmt_cascade_rule.h", "osmt_cascade_tables.h", "osmt_fill_slots.h", "osmt_geom.h", "osmt_glyph.h", "osmt_host.h", "osmt_internal.h", "osmt_list_slices.h", "osmt_numparse.h", "osmt_png_table.h", "osmt_pool_layout.h", "osmt_prebin_roles.h", "osmt_project.h", "osmt_u8_over_255.h", "osmt_utf8.h", os.path.join("..", "host", "osmt_idfilter.hpp"), os.path.join("..", "host", "osmt_textplacer.hpp"),
+HEADERS = ["osmt_bitonic.h", "osmt_cascade_rule.h", "osmt_cascade_tables.h", "osmt_fill_slots.h", "osmt_geom.h", "osmt_glyph.h", "osmt_host.h", "osmt_internal.h", "osmt_list_slices.h", "osmt_numparse.h", "osmt_png_table.h", "osmt_pool_layout.h", "osmt_prebin_roles.h", "osmt_probe_slots.h", "osmt_project.h", "osmt_u8_over_255.h", "osmt_utf8.h", os.path.join("..", "host", "osmt_idfilter.hpp"), os.path.join("..", "host", "osmt_textplacer.hpp"),
            os.path.join("..", "host", "osmt_textshaper.hpp"),
            os.path.join("..", "..", "include", "osmtile.h")]
 # -ffp-contract=off: the reference never fuses a*b+c; its u8 output truncates, so an FMA flips pixels.

@@ -5,6 +5,7 @@
  * ones into the arrays osmt_geodata_desc takes.  Shares osmt_host.h with the other host files.
  */
 #include "osmt_host.h"
+#include "osmt_probe_slots.h" /* osmt_vertex_slots: the vertex table's size */
 
 using namespace osmt_host;
 
@@ -147,8 +148,7 @@ int assemble_body(osmt_ctx* ctx, const osmt_relations_desc* d, osmt_polygons** o
     int at = 0;
     if (S) {
         /* at least twice as many slots as endpoints: a power of two, 2^32 at the most (then still more slots than endpoints) */
-        uint64_t slots = 64;
-        while (slots < 2 * (uint64_t)E && slots < (1ull << 32)) slots <<= 1;
+        const uint64_t slots = osmt_vertex_slots(E);
         P.table_mask = (uint32_t)(slots - 1);
         const size_t n_wg = (E + OSMT_PYR_SORT_BLOCK - 1) / OSMT_PYR_SORT_BLOCK;
         pool_layout pl;

@@ -40,6 +40,7 @@
 #include <stdint.h>
 
 #include "osmt_internal.h"
+#include "osmt_probe_slots.h"
 
 namespace {
 
@@ -101,24 +102,15 @@ __global__ __launch_bounds__(256) void k_mpa_fill(uint32_t* __restrict__ a, uint
     if (i <= (u64)n_minus_1) a[i] = v;
 }
 
-__device__ __forceinline__ uint32_t hash_of(ulonglong2 p, uint32_t rel) {
-    u64 h = p.x * 0x9E3779B97F4A7C15ull;
-    h ^= h >> 29;
-    h = (h + p.y) * 0xBF58476D1CE4E5B9ull;
-    h ^= h >> 32;
-    h = (h + rel) * 0x94D049BB133111EBull;
-    return (uint32_t)(h >> 32);
-}
-
 __device__ __forceinline__ bool same_vertex(const osmt_mpa_pass& P, uint32_t e, uint32_t rel, ulonglong2 pos) {
     if (P.seg_rel[e >> 1] != rel) return false;
     const ulonglong2 q = P.node_bits[P.seg_nodes[e]];
     return q.x == pos.x && q.y == pos.y;
 }
 
+/* the vertex hash and where a probe starts: osmt_probe_slots.h, shared with the host test that counts which probes wrap */
 __device__ __forceinline__ uint32_t first_slot(const osmt_mpa_pass& P, ulonglong2 pos, uint32_t rel) {
-    const uint32_t keep = P.hash_bits >= 32u ? NONE : (1u << P.hash_bits) - 1u;
-    return hash_of(pos, rel) & keep & P.table_mask;
+    return osmt_vertex_first_slot(pos.x, pos.y, rel, P.hash_bits, P.table_mask);
 }
 
 /* The table has at least twice as many slots as there are endpoints, so a probe meets an empty slot or its own vertex within

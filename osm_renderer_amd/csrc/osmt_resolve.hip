@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "osmt_internal.h"
+#include "osmt_probe_slots.h"
 
 namespace {
 
@@ -95,14 +96,10 @@ __global__ __launch_bounds__(256) void k_res_compact(osmt_res_refs A) {
     if (r <= A.n_owners) A.out_off[r] = A.pos[A.off[r]];
 }
 
-__device__ __forceinline__ u64 pair_key(uint32_t a, uint32_t b) { return a < b ? ((u64)a << 32) | b : ((u64)b << 32) | a; }
+/* the pair key, its hash and a way's table size: osmt_probe_slots.h, shared with the host test that counts which probes wrap */
+__device__ __forceinline__ u64 pair_key(uint32_t a, uint32_t b) { return osmt_pair_key(a, b); }
 
-__device__ __forceinline__ uint32_t hash_of(u64 k) {
-    k *= 0x9E3779B97F4A7C15ull;
-    k ^= k >> 29;
-    k *= 0xBF58476D1CE4E5B9ull;
-    return (uint32_t)(k >> 32);
-}
+__device__ __forceinline__ uint32_t hash_of(u64 k) { return osmt_pair_hash(k); }
 
 /* One wave per way.  lds: tkey [slots_cap] then tpos [slots_cap], slots_cap a power of two >= 2 * short_max. */
 __global__ __launch_bounds__(64) void k_res_short(osmt_res_dedup A, uint32_t slots_cap) {
@@ -117,8 +114,7 @@ __global__ __launch_bounds__(64) void k_res_short(osmt_res_dedup A, uint32_t slo
         if (lane < len) A.keep[b + lane] = 1u;
         return;
     }
-    uint32_t slots = 64u;
-    while (slots < 2u * (len - 1u)) slots <<= 1; /* <= slots_cap: len <= short_max */
+    const uint32_t slots = osmt_pair_slots(len); /* <= slots_cap: len <= short_max */
     const uint32_t mask = slots - 1u;
     for (uint32_t s = lane; s < slots; s += 64u) tkey[s] = EMPTY, tpos[s] = NONE;
     __syncthreads();
